@@ -276,13 +276,28 @@ def quick_kmeans(X, k, iters, seed, device):
             xb = Xt[i:i + 65536]
             dist = (xb * xb).sum(1, keepdim=True) - 2 * xb @ C.T + (C * C).sum(1)[None]
             assign[i:i + 65536] = dist.argmin(1)
-        sums = torch.zeros_like(C).index_add_(0, assign, Xt)
+        det = torch.are_deterministic_algorithms_enabled()
+        torch.use_deterministic_algorithms(True)        # index_add_ without atomics: the same centres every run
+        try:
+            sums = torch.zeros_like(C).index_add_(0, assign, Xt)
+        finally:
+            torch.use_deterministic_algorithms(det)
         cnt = torch.bincount(assign, minlength=k)
         C = sums / cnt.clamp(min=1).unsqueeze(1)
         empty = (cnt == 0).nonzero().flatten()
         if len(empty):  # re-seed empty clusters on data points so that every list is active
             C[empty] = Xt[torch.randperm(len(X), generator=g)[:len(empty)].to(device)]
     return C.cpu().numpy().astype(np.float64)
+
+
+def fit_pq(pq, sample, seed):
+    """FastPQ.fit, the same codebook every run: its k-means (and rotation) draw from numpy's global generator, and
+    sklearn's multi-threaded k-means sums in an order that depends on the threads — one thread, seeded."""
+    import sklearn.cluster  # noqa: F401 - loads sklearn's OpenMP runtime now, so that the limit below reaches it
+    from threadpoolctl import threadpool_limits
+    np.random.seed(seed)
+    with threadpool_limits(1):
+        pq.fit(sample)
 
 
 def load_real(args):
@@ -339,7 +354,7 @@ def build_index(args, device, X=None):
     C = quick_kmeans(sample, args.n_clusters, 8, args.seed, device)
     C = C.astype(np.float32)          # what sklearn's KMeans returns for float32 data (ivf.py:31-45)
     ivf.all_centers = C / np.linalg.norm(C, axis=1, keepdims=True) if ang else C   # ivf.py:36-45
-    ivf.pq.fit(sample[:min(len(sample), 30000)])
+    fit_pq(ivf.pq, sample[:min(len(sample), 30000)], args.seed)
     log(f"[bench] fit done in {time.time() - t0:.1f}s")
     ivf.build(X, n_probes=args.build_probes, device=True)   # build.hip: same lists and codes as numpy
     log(f"[bench] build done in {time.time() - t0:.1f}s")
@@ -389,8 +404,8 @@ def build_index_c5(args, device):
         sigma = float(args.c5_sigma)
     args.c5_point_sigma = sigma
     ivf = IVF("euclidean", args.n_clusters, FastPQ(2))
-    # The FIT (k-means on the GPU: atomics; ortho_group / k-means of FastPQ.fit: numpy's global RNG)
-    # is not bit-reproducible from run to run, and a list-sharded index needs every rank to hold
+    # The FIT (k-means on the GPU; ortho_group / k-means of FastPQ.fit: numpy's global RNG, seeded)
+    # need not be bit-reproducible across hosts, and a list-sharded index needs every rank to hold
     # the SAME centres and codebook: rank 0 fits first (main() orders the ranks) and leaves the
     # fitted parameters in the cache directory; the other ranks load them.  The BUILD from those
     # parameters is deterministic (seeded generator, stable sort) and runs on every rank.
@@ -407,7 +422,7 @@ def build_index_c5(args, device):
         ns = min(args.n, 1_000_000)
         sample = synth_rows_host(ns, args.d, args.seed, cent, sigma)   # rows 0..ns: a uniform sample of the clusters
         ivf.all_centers = quick_kmeans(sample, args.n_clusters, 6, args.seed, device).astype(np.float32)
-        ivf.pq.fit(sample[:30000])
+        fit_pq(ivf.pq, sample[:30000], args.seed)
         del sample
         torch.cuda.empty_cache()
         try:
@@ -1391,8 +1406,11 @@ def main():
     ap.add_argument("--warmup-seconds", type=float, default=0.5,
                     help="warm up for at least this long, whatever --warmup says")
     ap.add_argument("--windows", type=int, default=0,
-                    help="windows of --steps steps in the timed region (0: ~2400 steps in all, 3..61 windows); "
-                         "ms_per_step is the median window")
+                    help="windows the --steps timed steps are cut into (0: windows of >= 4 launches, at most 61); "
+                         "ms_per_step is the median window behind the first")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write the ids of its last step as DIR/ids.npy (float64, "
+                         "-1 = no neighbour; rank r > 0: ids_rank<r>.npy)")
     ap.add_argument("--data-file", default=None,
                     help=".npy of float vectors (GloVe-100, SIFT-1M ...): the protocol of examples/bench.py:67-70 "
                          "(seed 10, shuffle, last --nq rows are the queries) instead of the synthetic stand-in")
@@ -1410,12 +1428,6 @@ def main():
         args.py_cpu_sample = min(args.py_cpu_sample, 50)     # (N > 1: every rank generates and builds the
         #  same index from the seed, then keeps the codes of the lists it owns: tk_index_shard_resident)
 
-    # HIP maps every stream of the process onto GPU_MAX_HW_QUEUES hardware queues (default 4); streams that
-    # share one run in order.  The pipelined index needs four (caller, front, two replay streams: r04: more
-    # gain nothing for it); a list-sharded rank keeps --shard-depth batches in flight, each a chain of ~50
-    # short dependent kernels on its own stream — eight queues: 0.131 -> 0.114 ms per step of one rank's
-    # share of W = 8 (profiles/r05/rank_share_depth_queues.txt).  Read once, when HIP initialises.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch
     import torch.distributed as dist
     ang = args.metric == "angular"
@@ -1539,18 +1551,24 @@ def main():
     if world > 1:
         dist.barrier()
     dev.set_profiling(4)        # HIP events around the stages of every 4th batch, read after the region
-    # Timed region: `windows` x --steps steps in one continuous run, bracketed by barrier +
-    # synchronize on both sides.  A completion event (recorded by the library behind the last kernel
-    # of a batch, on whichever internal stream it ran) closes every window of EXACTLY --steps steps;
-    # ms_per_step = the median window.  Why not one window: with several batches in flight a region
-    # pays the pipeline's fill and drain once (~1.5 ms: 10 % of a 20-step region, 1 % of a 200-step
-    # one) — the windows behind the first measure what a server that keeps submitting sustains,
-    # the whole-region figure (fill and drain included) is reported beside it as `drained`.
-    K = args.steps
-    # (round 6: ~2 400 steps — 61 windows of the driver's 20 — instead of ~600: the four streams fall into and out of a slower
-    #  phase that lasts 40-100+ ms at a time; the median of half a second sees both where 0.12 s saw one)
-    target_steps = 600 if args.workload == "c5" else 2400
-    n_win = args.windows if args.windows > 0 else max(3, min(61, -(-target_steps // K)))
+    # Timed region: EXACTLY --steps steps in one continuous run, bracketed by barrier + synchronize on
+    # both sides, cut into windows of whole launches (a coalesced pair of steps is one launch).  A
+    # completion event (recorded by the library behind the last kernel of a batch, on whichever
+    # internal stream it ran) closes every window; ms_per_step = the median of the windows' ms per
+    # step behind the first.  Why not one window: with several batches in flight a region pays the
+    # pipeline's fill and drain once (~1.5 ms: 10 % of a 20-step region, 1 % of a 200-step one) —
+    # the windows behind the first measure what a server that keeps submitting sustains, the
+    # whole-region figure (fill and drain included) is reported beside it as `drained`.  (The four
+    # streams fall into and out of a slower phase that lasts 40-100+ ms at a time, DESIGN 3.6: give
+    # --steps enough steps for half a second or more when the figure has to see both.)
+    K = max(1, args.steps)
+    unit = launch_batches(args)
+    n_units = max(1, K // unit)
+    n_win = args.windows if args.windows > 0 else min(61, max(1, n_units // 4))
+    n_win = max(1, min(n_win, n_units))
+    bounds = sorted(set([0, K] + [K * w // n_win // unit * unit for w in range(1, n_win)]))
+    n_win = len(bounds) - 1
+    win_steps = [bounds[w + 1] - bounds[w] for w in range(n_win)]
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_win + 1)]
     for e in evs:
         e.record()              # materialises the HIP event; the library re-records it
@@ -1561,8 +1579,8 @@ def main():
     t0 = time.perf_counter()
     evs[0].record()
     for w in range(n_win):
-        for i in range(K):
-            step(evs[w + 1].cuda_event if (by_events and i == K - 1) else None)
+        for i in range(bounds[w], bounds[w + 1]):
+            step(evs[w + 1].cuda_event if (by_events and i == bounds[w + 1] - 1) else None)
         if not by_events:
             dev.join(stream)
             evs[w + 1].record()
@@ -1573,8 +1591,13 @@ def main():
         dist.barrier()
     region = time.perf_counter() - t0
     win_ms = [evs[w].elapsed_time(evs[w + 1]) for w in range(n_win)]      # window 0 includes the fill
-    steady = sorted(win_ms[1:]) if n_win > 1 else win_ms
-    elapsed = steady[len(steady) // 2] * 1e-3        # seconds per --steps steps: the median window
+    per_step = [win_ms[w] / win_steps[w] for w in range(n_win)]
+    steady = sorted(per_step[1:]) if n_win > 1 else per_step
+    elapsed = steady[len(steady) // 2] * 1e-3 * K     # seconds per --steps steps: the median window's rate
+    if args.dump_outputs:       # what the caller of the timed path received from its last step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ids.npy" if rank == 0 else f"ids_rank{rank}.npy"),
+                batches[(K - 1) % N_BATCHES]["out"].cpu().numpy().astype(np.float64))
     stages, scan_bytes, n_prof = dev.last_profile()
     plain_ms_timed = getattr(dev, "last_plain_kernel_ms", 0.0)      # HIP events around the plain kernel alone
     plain_stats_timed = dev.plain_stats()       # of the last batch of the timed region (a pair of steps when coalescing)
@@ -1604,9 +1627,9 @@ def main():
         log(f"[bench] replay rounds not counted: {e!r}")
     if args.profile_only:
         if rank == 0:
-            print(json.dumps({"profile_only": True, "ms_per_step": elapsed / args.steps * 1e3,
-                              "host_enqueue_ms_per_step": host_enqueue / (n_win * K) * 1e3,
-                              "ms_per_step_drained": region / (n_win * K) * 1e3, "windows_ms": win_ms,
+            print(json.dumps({"profile_only": True, "ms_per_step": elapsed / K * 1e3,
+                              "host_enqueue_ms_per_step": host_enqueue / K * 1e3,
+                              "ms_per_step_drained": region / K * 1e3, "windows_ms": win_ms,
                               "stage_ms": stages, "isolated_stage_ms": iso_stages, "plain_kernel_ms": plain_ms_timed,
                               "scan_bytes": scan_bytes, "iso_scan_bytes": iso_bytes}), flush=True)
         if world > 1:
@@ -1740,7 +1763,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    qps = args.nq * world * args.steps / elapsed
+    qps = args.nq * world * K / elapsed
     scan_ms = stages["scan"]
     achieved = scan_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
     traffic, traffic_src = None, "not measured"
@@ -1991,16 +2014,16 @@ def main():
                   if args.workload == "c5" else
                   f"queries/sec at Recall10@10, {args.data} {args.metric} d={args.d} (synthetic), IVF+4-bit PQ",
         "value": qps, "unit": "queries/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "timing": {"windows": n_win, "steps_per_window": K, "window_ms": win_ms,
-                   "ms_per_step_is": "median over the windows behind the first, each EXACTLY --steps steps of one "
+        "warmup": args.warmup, "ms_per_step": elapsed / K * 1e3,
+        "timing": {"windows": n_win, "steps_per_window": win_steps, "window_ms": win_ms,
+                   "ms_per_step_is": "median ms per step over the windows behind the first, which cut the --steps steps of one "
                                      "continuous run (completion events of the batches; fill and drain of the "
                                      "pipeline are in `drained`)",
-                   "drained": {"steps": n_win * K, "ms_per_step": region / (n_win * K) * 1e3,
-                               "queries_per_s": args.nq * world * n_win * K / region,
+                   "drained": {"steps": K, "ms_per_step": region / K * 1e3,
+                               "queries_per_s": args.nq * world * K / region,
                                "note": "the whole region by the host clock, barrier + synchronize on both "
                                        "sides, pipeline fill and drain included"},
-                   "host_enqueue_ms_per_step": host_enqueue / (n_win * K) * 1e3,
+                   "host_enqueue_ms_per_step": host_enqueue / K * 1e3,
                    "warmup_steps_run": n_warm, "distinct_batches": N_BATCHES},
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "int8 (saturating PQ sums) + f32 (tables, rescoring)",
