@@ -463,6 +463,37 @@ int tk_index_query_batch_dev_ex(tk_index *ix, const float *q_dev, const void *q_
                                 int64_t *out_ids_dev, int64_t *out_ids_pinned, void *done_event,
                                 void *stream);
 int64_t tk_index_max_sub_batch(tk_index *ix, int k, int n_probes, int pass_1);
+
+/* Allowed sets: IVF.query restricted to a subset of the rows (one tenant, one category, "not deleted").
+ * A query with allowed set A returns what IVF.query (ivf.py:106-163) returns when `insert` in query_pq
+ * (_fast_pq_256.pyx:114-118, _fast_pq.pyx:197-201) runs only for labels in A; everything else is the
+ * reference's: coarse stage and probe order, pass_1, the stale bound per 16-row block, the -1 removal and
+ * the `len(indices) <= k` early return (ivf.py:152-156), knn_brute1 over the surviving candidates
+ * (ivf.py:157-163).  Results are bit for bit those of that guarded reference.
+ * tk_allow_create: mask = N bytes over row ids 0..N-1 (nonzero = allowed), uploaded once and turned on the
+ * device into 16 bits per stored chunk in list-position order, from the index's device-resident labels (so
+ * indexes built in HBM work too).  A set belongs to the layout of the lists it was made for: after the lists
+ * are set again a query with it fails (TK_ERR_STATE).  Not for list-sharded indexes.
+ * tk_allow_count: allowed stored rows (a label stored in two lists counts twice), < 0 on error.
+ * tk_allow_destroy: enqueues the index's calls still owed, waits for the device, frees the set.  Destroy
+ * every set of an index before the index. */
+typedef struct tk_allow tk_allow;
+int tk_allow_create(tk_index *ix, const uint8_t *mask, int64_t n, tk_allow **out);
+int64_t tk_allow_count(const tk_allow *a);
+int tk_allow_destroy(tk_allow *a);
+/* tk_index_query_batch / tk_index_query_batch_dev_ex with an allowed set (NULL: the unrestricted call).
+ * A set that allows every stored row takes the unrestricted path.  With tk_index_set_coalesce(ix, 2) only
+ * calls with the same set (or none) pair up.  The automatic plain-scan state (tk_index_set_plain_scan 0)
+ * is the unrestricted traffic's: restricted calls take the exact scan in that mode and leave the state
+ * as it is; mode 2 runs them on the plain path too. */
+int tk_index_query_batch_allow(tk_index *ix, const tk_allow *allow, const float *q, const void *q_pq,
+                               int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                               int64_t *out_ids, int64_t *out_probes, int64_t *out_heap_idx,
+                               int32_t *out_heap_val);
+int tk_index_query_batch_dev_allow(tk_index *ix, const tk_allow *allow, const float *q_dev,
+                                   const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k, int n_probes,
+                                   int pass_1, int64_t *out_ids_dev, int64_t *out_ids_pinned,
+                                   void *done_event, void *stream);
 /* hipStream_t on which to copy a batch's inputs in (pipelined mode: the index's front stream,
  * where the batch's first kernel runs; NULL: use the stream the batch is enqueued on) */
 void *tk_index_input_stream(tk_index *ix);

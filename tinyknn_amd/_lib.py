@@ -138,6 +138,14 @@ SIGNATURES = {
                                               C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
     "tk_index_max_sub_batch": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "tk_allow_create": (C.c_int, [C.c_void_p, _u8p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "tk_allow_count": (C.c_int64, [C.c_void_p]),
+    "tk_allow_destroy": (C.c_int, [C.c_void_p]),
+    "tk_index_query_batch_allow": (C.c_int, [C.c_void_p, C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64,
+                                             C.c_int, C.c_int, C.c_int, _i64p, _i64p, _i64p, _i32p]),
+    "tk_index_query_batch_dev_allow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
     "tk_index_pending": (C.c_int, [C.c_void_p]),
     "tk_index_input_stream": (C.c_void_p, [C.c_void_p]),
     "tk_index_info": (C.c_int, [C.c_void_p, _i64p]),

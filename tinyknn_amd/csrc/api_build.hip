@@ -257,6 +257,7 @@ extern "C" int tk_index_build_dev(tk_index *ix, int normalise, const float *all_
     ix->total_ids = T;
     ix->max_list_chunks = (int)maxc;
     ix->have_centers = ix->have_lists = ix->have_data = true;
+    ix->lists_gen++;
     TRY(build_twins(ix, N));
     if (n_active_out) *n_active_out = L;
     return TK_OK;

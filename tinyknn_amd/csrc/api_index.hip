@@ -262,6 +262,7 @@ static int set_lists_impl(tk_index *ix, const int64_t *list_sizes, const uint64_
     ix->total_ids = ioff[L];
     ix->max_list_chunks = (int)maxc;
     ix->have_lists = true;
+    ix->lists_gen++;
     {   // labels that repeat: where every row's other copies are (the lane replay's duplicate test)
         int64_t mx = -1, mn = 0;
         for (int64_t i = 0; i < ioff[L]; i++) {
@@ -913,10 +914,21 @@ static void plain_verdict_event(tk_index *ix, Work &w, int64_t nq, hipStream_t s
     }
 }
 
+// The allowed set over the probed chunks of queries [q0, q0 + nq) (allow.hip) — all of them, or (`only`) those of the
+// flag list: behind the list scans and every re-scan, in front of every replay that reads dist / mins
+static void apply_allow(Work &w, int64_t q0, int64_t nq, const Plan &p, const tk_allow *allow, hipStream_t st,
+                        const int *only = nullptr)
+{
+    if (allow)
+        tk_launch_allow_pass(w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, nq,
+                             w.slot_prefix.as<int>() + q0 * (p.S + 1), w.slot_chunk0.as<int64_t>() + q0 * p.S, p.S,
+                             allow->bits.as<uint16_t>(), 1, only, st);
+}
+
 // list_built: the lane replay compiled the list of flagged queries itself (tk_launch_heap_replay_lanes' flag_list); the
 // count then reaches the host through the packed kernel behind the re-scan (plain_verdict_event there)
 static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, hipStream_t st,
-                           bool list_built = false)
+                           const tk_allow *allow, bool list_built = false)
 {
     int *list = w.flag_list.as<int>();
     if (!list_built) {
@@ -927,6 +939,7 @@ static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const 
                           w.slot_prefix.as<int>() + q0 * (p.S + 1), w.slot_chunk0.as<int64_t>() + q0 * p.S,
                           p.S, (int)p.cap, w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, 1,
                           ix->order, st, list);
+    apply_allow(w, q0, nq, p, allow, st, list);
 }
 
 // The tail behind a lane (or register-heap) replay that rode with the plain kernel: the queries it flagged — the lemma's
@@ -953,7 +966,7 @@ static void replay_flagged_tail(tk_index *ix, Work &w, int64_t nq, const Plan &p
 
 int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
                       const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain,
-                      TkSecond q2, TkSecond out2, int *plain_flag)
+                      TkSecond q2, TkSecond out2, int *plain_flag, const tk_allow *allow)
 {
     const int *slot_exact = plain ? w.plain0.as<int>() + q0 : nullptr;     // (first plain chunk per query)
     const int *qlim = plain ? w.qlim.as<int>() + q0 : nullptr;
@@ -961,6 +974,7 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     const int *slot_n = w.slot_n.as<int>() + q0 * p.S;
     const int64_t *slot_loff = w.slot_loff.as<int64_t>() + q0 * p.S;
     unsigned char *repeat_flag = w.repeat_flag.as<unsigned char>() + q0;
+    apply_allow(w, q0, nq, p, allow, st);
     // heaps start fresh here, so packed entries apply.  Distinct labels: one query per
     // lane (or per wave for big heaps), and the few queries whose probe list wrapped a -1
     // (a list may then be scanned twice) re-run with the duplicate test.  Repeating labels
@@ -996,7 +1010,7 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
                                          p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
                                          w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, 1, 1, st);
         } else if (plain) {
-            rescan_flagged(ix, w, q0, nq, p, st, true);
+            rescan_flagged(ix, w, q0, nq, p, st, allow, true);
             replay_flagged_tail(ix, w, nq, p, slot_prefix, slot_n, slot_loff, repeat_flag, st);
             plain_verdict_event(ix, w, nq, st);
         }
@@ -1021,11 +1035,11 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
             // flag 2 = the lane replay's "bound above the limit at the first plain block", flag 1 = a probe list that
             // names a list twice: exact re-scan of both kinds (the lane replay listed them), then ONE launch of the
             // packed kernel with the duplicate test from fresh heaps (where labels are distinct the test never fires)
-            rescan_flagged(ix, w, q0, nq, p, st, true);
+            rescan_flagged(ix, w, q0, nq, p, st, allow, true);
             replay_flagged_tail(ix, w, nq, p, slot_prefix, slot_n, slot_loff, repeat_flag, st);
             plain_verdict_event(ix, w, nq, st);
         } else if (plain) {
-            rescan_flagged(ix, w, q0, nq, p, st);
+            rescan_flagged(ix, w, q0, nq, p, st, allow);
             tk_launch_heap_replay_packed(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n, slot_loff,
                                          p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
                                          w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, 2, 0, st);
@@ -1060,7 +1074,7 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
                                          p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
                                          w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, 1, 1, st);
         } else if (plain) {         // (flags 1 and 2 alike: re-scan, one launch of the packed kernel)
-            rescan_flagged(ix, w, q0, nq, p, st, true);
+            rescan_flagged(ix, w, q0, nq, p, st, allow, true);
             replay_flagged_tail(ix, w, nq, p, slot_prefix, slot_n, slot_loff, repeat_flag, st);
             plain_verdict_event(ix, w, nq, st);
         } else {
@@ -1079,7 +1093,7 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
                                         ix->ids32.as<int32_t>(), st, slot_exact, qlim))
             return fail(TK_ERR_HIP, "hipFuncSetAttribute(LDS size) failed");
         if (plain) {
-            rescan_flagged(ix, w, q0, nq, p, st);
+            rescan_flagged(ix, w, q0, nq, p, st, allow);
             tk_launch_heap_replay_packed(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n, slot_loff,
                                          p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
                                          w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, 1, 1, st);
@@ -1149,7 +1163,17 @@ struct Pending {
     } subs[2];
     int n_subs = 0;
     TkSecond q2, qpq2, out2;   // rows of the second call (empty: one call)
+    const tk_allow *allow = nullptr;   // allowed set of the batch (NULL: every row)
 };
+
+// A restricted batch (allowed set) in the automatic plain-scan mode takes the exact scan and never touches the
+// state: a selective set flags many queries, and its verdicts would pause the plain path for the unrestricted traffic
+// (DESIGN §3.8).  Modes 1 and 2 hold for every batch.
+static bool plain_for(tk_index *ix, const Pending &b)
+{
+    if (b.allow && plain_adaptive(ix)) return false;
+    return plain_now(ix, b.p);
+}
 
 // depth == 1
 static int run_batch_inline(tk_index *ix, Pending &b, const void *qpq_dev, int qpq_f64)
@@ -1160,7 +1184,7 @@ static int run_batch_inline(tk_index *ix, Pending &b, const void *qpq_dev, int q
     hipStream_t st = b.st;
     TRY(prof_begin(ix, w, b.nq, p, st, b.pf));
     b.units = use_units(ix, b.nq, p);
-    b.plain = b.units && plain_now(ix, p);
+    b.plain = b.units && plain_for(ix, b);
     w.last_plain = b.plain;
     TRY(stage_tables(ix, w, qpq_dev, qpq_f64, b.nq, st, b.pf, b.plain, b.qpq2));
     launch_coarse_scan(ix, w, b.nq, p, st);
@@ -1192,7 +1216,7 @@ static int run_batch_inline(tk_index *ix, Pending &b, const void *qpq_dev, int q
                               (int)p.cap, w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(),
                               p.cap_min, 1, ix->order, st);
     TRY(b.pf.mark(st));
-    TRY(stage_back(ix, w, b.q_dev, 0, b.nq, b.k, p, b.out_dev, st, b.pf, b.plain, b.q2, b.out2));
+    TRY(stage_back(ix, w, b.q_dev, 0, b.nq, b.k, p, b.out_dev, st, b.pf, b.plain, b.q2, b.out2, nullptr, b.allow));
     TRY(batch_epilogue(b, st));
     HIPCHECK(hipGetLastError());
     return TK_OK;
@@ -1278,7 +1302,7 @@ static int pipeline_step(tk_index *ix, Pending *prev, Pending *cur)
         HIPCHECK(hipEventRecord(prev->w->scanned, st));
         HIPCHECK(hipStreamWaitEvent(prev->sl, prev->w->scanned, 0));
         TRY(stage_back(ix, *prev->w, prev->q_dev, 0, prev->nq, prev->k, prev->p, prev->out_dev,
-                       prev->sl, prev->pf, prev->plain, prev->q2, prev->out2));
+                       prev->sl, prev->pf, prev->plain, prev->q2, prev->out2, nullptr, prev->allow));
         TRY(batch_epilogue(*prev, prev->sl));
         HIPCHECK(hipEventRecord(prev->w->done, prev->sl));
         prev->w->busy = true;
@@ -1483,7 +1507,7 @@ static int pipe_launch(tk_index *ix, Pending &b, const void *qpq, int q_pq_is_f6
     TRY(reserve(ix, w, sub, k, p));
     TRY(prof_begin(ix, w, b.nq, p, b.sl, b.pf));
     b.units = use_units(ix, b.nq, p);
-    b.plain = b.units && plain_now(ix, p);
+    b.plain = b.units && plain_for(ix, b);
     w.last_plain = b.plain;
     TK_DBG_SYNC("launch: reserved");
     TRY(stage_tables(ix, w, qpq, q_pq_is_f64, b.nq, stt, b.pf, b.plain, b.qpq2));
@@ -1535,14 +1559,14 @@ static int launch_held(tk_index *ix)
 
 static int coalesce_call(tk_index *ix, const Plan &p, const float *q_dev, const void *q_pq_dev, int q_pq_is_f64,
                          int64_t nq, int k, int n_probes, int pass_1, int64_t *out_ids_dev,
-                         int64_t *out_ids_pinned, hipEvent_t done_ev, hipStream_t caller)
+                         int64_t *out_ids_pinned, hipEvent_t done_ev, hipStream_t caller, const tk_allow *allow)
 {
     const Pending::Sub sub{out_ids_dev, nq, out_ids_pinned, ix->host_out_kernel, done_ev, q_dev, q_pq_dev};
     if (ix->held) {
         Pending &h = *ix->held;
         const bool joins = h.k == k && ix->held_n_probes == n_probes && ix->held_pass_1 == pass_1 &&
                            ix->held_f64 == q_pq_is_f64 && ix->held_caller == caller &&
-                           h.subs[0].nq + nq <= ix->held_rows;
+                           h.subs[0].nq + nq <= ix->held_rows && h.allow == allow;
         if (joins) {
             hipStream_t stt = ix->held_stt;
             if (stt != caller) {            // the second call's inputs: the caller's work so far
@@ -1571,6 +1595,7 @@ static int coalesce_call(tk_index *ix, const Plan &p, const float *q_dev, const 
     b.st = b.sf = b.sl = caller;
     b.subs[0] = sub;
     b.n_subs = 1;
+    b.allow = allow;
     hipStream_t stt = nullptr;
     TRY(pipe_begin(ix, b, caller, stt));
     const int64_t ms = sub_batch(p);
@@ -1589,12 +1614,18 @@ static int coalesce_call(tk_index *ix, const Plan &p, const float *q_dev, const 
 static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_pq_dev,
                                 int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
                                 int64_t *out_ids_dev, int64_t *out_ids_pinned, hipEvent_t done_ev,
-                                void *stream)
+                                void *stream, const tk_allow *allow = nullptr)
 {
     Plan p;
     TRY(make_plan(ix, k, n_probes, pass_1, p));
     ARGCHECK(nq >= 0, "nq");
     ARGCHECK(!ix->sharded, "list-sharded index: use tk_index_shard_scan_dev / _finish_dev");
+    if (allow) {
+        ARGCHECK(allow->ix == ix, "the allowed set belongs to another index");
+        if (allow->lists_gen != ix->lists_gen)
+            return fail(TK_ERR_STATE, "the allowed set was made for an earlier layout of the lists: make it again");
+        allow = allow_effective(allow);
+    }
     hipStream_t caller = (hipStream_t)stream;
     {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1612,7 +1643,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     //  profiles/r04/bench_full_first.json)
     if (ix->depth > 1 && ix->coalesce == 2 && (ix->ids_unique || twin_replay(ix, p)) && nq >= 1 && nq <= ms)
         return coalesce_call(ix, p, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev,
-                             out_ids_pinned, done_ev, caller);
+                             out_ids_pinned, done_ev, caller, allow);
     if (ix->held) TRY(launch_held(ix));
     // a batch beyond one workspace goes in EQUAL parts (30 000 queries at 100M x 128, 22 500 to a workspace: 2 x 15 000,
     // not 22 500 + 7 500 — the small rest fell below the list-major scan's threshold and took the query-major kernel)
@@ -1635,6 +1666,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
         b.host_out_kernel = ix->host_out_kernel;
         b.user_ev = done_ev;
         b.st = b.sf = b.sl = caller;
+        b.allow = allow;
         const void *qpq = (const char *)q_pq_dev + (size_t)o * ix->dq * esz;
         if (ix->depth == 1) {
             ix->calls++;
@@ -1779,10 +1811,9 @@ extern "C" int tk_index_quiesce(tk_index *ix)
     return TK_OK;
 }
 
-extern "C" int tk_index_query_batch(tk_index *ix, const float *q, const void *q_pq,
-                                    int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
-                                    int64_t *out_ids, int64_t *out_probes, int64_t *out_heap_idx,
-                                    int32_t *out_heap_val)
+static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
+                            int n_probes, int pass_1, int64_t *out_ids, int64_t *out_probes, int64_t *out_heap_idx,
+                            int32_t *out_heap_val, const tk_allow *allow)
 {
     IXLOCK(ix);
     Plan p;
@@ -1798,8 +1829,8 @@ extern "C" int tk_index_query_batch(tk_index *ix, const float *q, const void *q_
     TRY(outbuf.ensure((size_t)nq * k * 8));
     HIPCHECK(hipMemcpy(ix->q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(ix->qpq.p, q_pq, (size_t)nq * ix->dq * esz, hipMemcpyHostToDevice));
-    int r = tk_index_query_batch_dev(ix, ix->q.as<float>(), ix->qpq.p, q_pq_is_f64, nq, k, n_probes,
-                                     pass_1, outbuf.as<int64_t>(), nullptr);
+    int r = query_batch_dev_impl(ix, ix->q.as<float>(), ix->qpq.p, q_pq_is_f64, nq, k, n_probes, pass_1,
+                                 outbuf.as<int64_t>(), nullptr, nullptr, nullptr, allow);
     if (r == TK_OK) r = flush_pending(ix);
     const Work &lw = ix->works[(ix->calls + ix->works.size() - 1) % ix->works.size()];   // last used
     if (r == TK_OK) {
@@ -1815,6 +1846,38 @@ extern "C" int tk_index_query_batch(tk_index *ix, const float *q, const void *q_
     }
     outbuf.release();
     return r;
+}
+
+extern "C" int tk_index_query_batch(tk_index *ix, const float *q, const void *q_pq,
+                                    int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                                    int64_t *out_ids, int64_t *out_probes, int64_t *out_heap_idx,
+                                    int32_t *out_heap_val)
+{
+    return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
+                            out_heap_val, nullptr);
+}
+
+// the restricted calls (allow.hip) — extend IVF.query, ivf.py:106-163: `insert` (_fast_pq_256.pyx:114-118,
+// _fast_pq.pyx:197-201) only for the set's labels
+extern "C" int tk_index_query_batch_allow(tk_index *ix, const tk_allow *allow, const float *q, const void *q_pq,
+                                          int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                                          int64_t *out_ids, int64_t *out_probes, int64_t *out_heap_idx,
+                                          int32_t *out_heap_val)
+{
+    if (!allow) return fail(TK_ERR_ARG, "bad argument: null allowed set");
+    return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
+                            out_heap_val, allow);
+}
+
+extern "C" int tk_index_query_batch_dev_allow(tk_index *ix, const tk_allow *allow, const float *q_dev,
+                                              const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k, int n_probes,
+                                              int pass_1, int64_t *out_ids_dev, int64_t *out_ids_pinned,
+                                              void *done_event, void *stream)
+{
+    IXLOCK(ix);
+    if (!allow) return fail(TK_ERR_ARG, "bad argument: null allowed set");
+    return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev,
+                                out_ids_pinned, (hipEvent_t)done_event, stream, allow);
 }
 
 extern "C" int tk_index_set_heap_mode(tk_index *ix, int mode)

@@ -191,6 +191,7 @@ struct tk_index {
     int opt_replay_twin = 1;   // TK_OPT_REPLAY_TWIN: 1 = the lane replay decides `insert`'s duplicate test from the twin table
     int64_t total_chunks = 0, total_ids = 0;
     int max_list_chunks = 0;
+    uint64_t lists_gen = 0;    // counts the times the lists were (re-)set: an allowed set is valid for one layout
     bool ids_unique = false;   // no label occurs twice => the lane-per-query replay is exact
     int heap_mode = 0;         // 0 auto (pair for small batches, lanes, else packed wave), 1 general wave, 2 packed wave, 3 pair
     int opt_pair_nq = 8192;    // TK_OPT_PAIR_NQ: batches up to this many queries take the wave-per-query register heap
@@ -254,6 +255,16 @@ struct tk_index {
     int64_t last_nq = 0;
 };
 
+// an allowed set (allow.hip): 16 bits per stored chunk in list-position order, for ONE layout of the lists
+struct tk_allow {
+    tk_index *ix = nullptr;
+    DevBuf bits;
+    int64_t count = 0;         // allowed stored rows (a label stored twice counts twice)
+    int64_t stored = 0;        // stored rows of the layout
+    uint64_t lists_gen = 0;    // tk_index::lists_gen when it was made
+};
+// the set a batch applies: NULL where the set allows every stored row (no kernel at all)
+const tk_allow *allow_effective(const tk_allow *a);
 struct Plan {
     int kc, rescore, R, S;
     int64_t cap;       // uint4 per query in the distance buffer
@@ -327,5 +338,6 @@ int stage_coarse_rest(tk_index *ix, Work &w, const float *q_dev, int64_t nq, con
 // *plain_flag instead of being scanned again (the codes are on other ranks: the batch is repeated)
 int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
                const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain = false,
-               TkSecond q2 = TkSecond(), TkSecond out2 = TkSecond(), int *plain_flag = nullptr);
+               TkSecond q2 = TkSecond(), TkSecond out2 = TkSecond(), int *plain_flag = nullptr,
+               const tk_allow *allow = nullptr);
 int head_chunks_of(const tk_index *ix, const Plan &p);    // chunks of a first probed list the exact kernel keeps (head mode)

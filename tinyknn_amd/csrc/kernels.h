@@ -47,6 +47,12 @@ void tk_launch_scan_probes(const uint4 *codes, int M, const uint4 *tables, int64
                            int max_flat_chunks, uint4 *dist, int64_t cap, uint8_t *mins,
                            int64_t min_stride, int signd, int order, hipStream_t s,
                            const int *only = nullptr);
+// allow.hip: the allowed set applied to the probed chunks of a batch — disallowed bytes of dist take the empty value
+// (127 signed, 255 unsigned), touched chunks' minima are recomputed.  bits: 16 per stored chunk (list_chunk_off order);
+// only: NULL (all nq queries) or [count, q_0, ...] (nq = its capacity)
+void tk_launch_allow_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
+                          const int *slot_prefix, const int64_t *slot_chunk0, int S, const uint16_t *bits,
+                          int signd, const int *only, hipStream_t s);
 // list (nq + 1 ints): list[0] = number of flagged queries, list[1..] = their ids in order
 // host_count (page-locked host word or NULL) receives the count too
 void tk_launch_flagged_list(const unsigned char *flags, int64_t nq, int *list, hipStream_t s,

@@ -152,6 +152,61 @@ def _copies_carry_one_code(ivf, n_lists):
     return bool((sg[1:][same] == sg[:-1][same]).all())
 
 
+class AllowSet:
+    """The rows a query may return (tinyknn_hip.h: tk_allow_create): a bool mask of length N or an array of row
+    ids, turned once into a device bitmap over the index's stored rows.  Reuse it across calls; close() frees it
+    (after the index's calls still owed have run).  len() = allowed stored rows (a row stored in two lists counts
+    twice).  A set belongs to the lists it was made for: once they are set again, queries with it fail."""
+
+    def __init__(self, dev, ids_or_mask):
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_info(dev.handle, _lib.ptr(info, _lib._i64p)))
+        N = int(info[6])
+        mask = self.mask_of(ids_or_mask, N)
+        self._dev = dev
+        h = C.c_void_p()
+        _lib.check(_lib.lib().tk_allow_create(dev.handle, _lib.ptr(mask, _lib._u8p), N, C.byref(h)))
+        self._h = h.value
+
+    @staticmethod
+    def mask_of(ids_or_mask, N):
+        """uint8 (N,) mask of a bool mask of length N or of an array of row ids in [0, N)"""
+        a = np.asarray(ids_or_mask)
+        if a.dtype == np.bool_:
+            if a.shape != (N,):
+                raise ValueError(f"allowed: a bool mask must have shape ({N},), got {a.shape}")
+            return np.ascontiguousarray(a, dtype=np.uint8)
+        if a.ndim == 1 and (a.size == 0 or np.issubdtype(a.dtype, np.integer)):
+            a = a.astype(np.int64, copy=False)
+            if a.size and (a.min() < 0 or a.max() >= N):
+                raise ValueError(f"allowed: row ids must lie in [0, {N})")
+            mask = np.zeros(N, dtype=np.uint8)
+            mask[a] = 1
+            return mask
+        raise TypeError("allowed: a bool mask of length N, a 1-d integer array of row ids, or an AllowSet")
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise ValueError("allowed set is closed")
+        return self._h
+
+    def __len__(self):
+        return int(_lib.check(_lib.lib().tk_allow_count(self.handle)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if _lib.owns_handles() and getattr(self._dev, "_h", None):
+                _lib.check(_lib.lib().tk_allow_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceIndex:
     """HBM-resident copy of a built IVF (C ABI: tk_index_*)."""
 
@@ -217,6 +272,7 @@ class DeviceIndex:
         self._R = None
         self._streams = {}
         self._live_streams = weakref.WeakSet()
+        self._live_allows = weakref.WeakSet()
         if pq.R is not None:    # fast mode (device front end) needs the rotation on the device
             R = np.ascontiguousarray(pq.R, dtype=np.float64)
             _lib.check(L.tk_index_set_rotation(self._h, R.ctypes.data, R.shape[1]))
@@ -328,11 +384,27 @@ class DeviceIndex:
     def handle(self):
         return self._h
 
+    def allow(self, ids_or_mask):
+        """A prepared allowed set for the `allowed=` argument of the query calls (AllowSet)."""
+        a = AllowSet(self, ids_or_mask)
+        self._live_allows.add(a)
+        return a
+
+    def _allow_of(self, allowed):
+        """(set, temporary) for an `allowed=` argument: a prepared set of this index, or a mask / ids made into one"""
+        if isinstance(allowed, AllowSet):
+            if allowed._dev is not self:
+                raise ValueError("allowed: the set was prepared for another index")
+            return allowed, False
+        return AllowSet(self, allowed), True
+
     def close(self):
         # every session on this index, the caller's own included: a session that outlived the
         # index would drain and join a freed handle
         for st in list(getattr(self, "_live_streams", ())):
             st.close()
+        for a in list(getattr(self, "_live_allows", ())):
+            a.close()
         self._streams = {}
         if getattr(self, "_h", None):
             if _lib.owns_handles():
@@ -389,8 +461,12 @@ class DeviceIndex:
         except Exception:
             pass
 
-    def query_batch(self, qn, q_pq, k, n_probes, pass_1=None, debug=False):
-        """qn: (nq, d) float32 normalised queries; q_pq: (nq, dq) table-build queries."""
+    def query_batch(self, qn, q_pq, k, n_probes, pass_1=None, debug=False, *, allowed=None):
+        """qn: (nq, d) float32 normalised queries; q_pq: (nq, dq) table-build queries.
+        allowed: None, or the rows the queries may return — an AllowSet (allow()), a bool mask of length N or row
+        ids (tk_index_query_batch_allow: the reference's `insert` only for those labels)."""
+        if allowed is not None:
+            return self._query_batch_allow(qn, q_pq, k, n_probes, pass_1, debug, allowed)
         qn = np.ascontiguousarray(qn, dtype=np.float32)
         is64 = q_pq.dtype != np.float32
         q_pq = np.ascontiguousarray(q_pq, dtype=np.float64 if is64 else np.float32)
@@ -423,6 +499,38 @@ class DeviceIndex:
             return out, dict(probes=probes, heap_idx=hidx, heap_val=hval)
         return out
 
+    def _query_batch_allow(self, qn, q_pq, k, n_probes, pass_1, debug, allowed):
+        aset, temp = self._allow_of(allowed)
+        try:
+            qn = np.ascontiguousarray(qn, dtype=np.float32)
+            is64 = q_pq.dtype != np.float32
+            q_pq = np.ascontiguousarray(q_pq, dtype=np.float64 if is64 else np.float32)
+            nq = qn.shape[0]
+            assert qn.shape[1] == self.d and q_pq.shape == (nq, self.dq)
+            out = np.full((nq, k), -1, dtype=np.int64)
+            R = pass_1 if pass_1 else (n_probes + 1) * k + 1
+            probes = hidx = hval = None
+            if debug:
+                probes = np.zeros((nq, min(n_probes, self.n_lists)), dtype=np.int64)
+                hidx = np.zeros((nq, R), dtype=np.int64)
+                hval = np.zeros((nq, R), dtype=np.int32)
+            # (one sub-batch at a time keeps the debug outputs of every row)
+            step = nq if not debug else max(1, self.max_sub_batch(k, n_probes, pass_1))
+            for o in range(0, nq, max(step, 1)):
+                e = min(nq, o + step)
+                _lib.check(_lib.lib().tk_index_query_batch_allow(
+                    self._h, aset.handle, _lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o,
+                    int(k), int(n_probes), int(pass_1 or 0), _lib.ptr(out[o:e], _lib._i64p),
+                    None if probes is None else _lib.ptr(probes[o:e], _lib._i64p),
+                    None if hidx is None else _lib.ptr(hidx[o:e], _lib._i64p),
+                    None if hval is None else _lib.ptr(hval[o:e], _lib._i32p)))
+        finally:
+            if temp:
+                aset.close()
+        if debug:
+            return out, dict(probes=probes, heap_idx=hidx, heap_val=hval)
+        return out
+
     def query_batch_raw(self, qs, k, n_probes, pass_1=None):
         """Fast mode: raw float32 queries, normalisation / padding / rotation on the device
         (tk_index_prepare_dev: within 1 ulp of the host's BLAS results, not bit-identical)."""
@@ -445,14 +553,24 @@ class DeviceIndex:
         return out
 
     def query_batch_dev(self, qn_ptr, qpq_ptr, qpq_is_f64, nq, k, n_probes, out_ptr,
-                        pass_1=None, stream=0, done_event=None):
+                        pass_1=None, stream=0, done_event=None, *, allowed=None):
         """Device pointers in, device pointer out, enqueued on `stream` (no sync).
         done_event: a hipEvent_t (integer handle) recorded behind the batch's last kernel, on
         whichever internal stream that runs (tk_index_query_batch_dev_ex).
         With set_pipeline(depth > 1) the kernels of a call run up to three calls later, and with
         set_coalesce(2) they read the queries from, and write the ids to, these very buffers (no
         staging copy): all three buffers belong to the library until join() — or the call's
-        done_event — as include/tinyknn_hip.h says for tk_index_set_pipeline."""
+        done_event — as include/tinyknn_hip.h says for tk_index_set_pipeline.
+        allowed: None or an AllowSet of this index (allow()), which must stay open until the call has run
+        (tk_index_query_batch_dev_allow)."""
+        if allowed is not None:
+            if not isinstance(allowed, AllowSet):
+                raise TypeError("query_batch_dev: allowed= takes a prepared set (DeviceIndex.allow / IVF.allow)")
+            aset, _ = self._allow_of(allowed)
+            _lib.check(_lib.lib().tk_index_query_batch_dev_allow(
+                self._h, aset.handle, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes),
+                int(pass_1 or 0), out_ptr, None, None if done_event is None else C.c_void_p(int(done_event)), stream))
+            return
         if done_event is None:
             _lib.check(_lib.lib().tk_index_query_batch_dev(
                 self._h, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes),
@@ -1008,15 +1126,22 @@ class IVF:
         assert qp.shape[1] == dq
         return qn, qp
 
-    def query(self, q, k, n_probes=1, pass_1=None):
-        """Top-k ids for one query.  reference: ivf.py:106-163"""
+    def allow(self, ids_or_mask):
+        """Prepare an allowed set (a bool mask over the N rows, or row ids) for `allowed=`: made once on the
+        device, reused across calls; .close() frees it, len() = allowed stored rows."""
+        return self._unsharded_device_index().allow(ids_or_mask)
+
+    def query(self, q, k, n_probes=1, pass_1=None, *, allowed=None):
+        """Top-k ids for one query.  reference: ivf.py:106-163
+        allowed: the rows it may return (a bool mask of length N, row ids, or allow()'s set) — the reference's
+        query with `insert` only for those labels."""
         q = np.ascontiguousarray(q, dtype=np.float32)
         assert self.data.shape[1] == q.shape[0]
         qn, qp = self._prepare(q[None, :])
-        out = self._unsharded_device_index().query_batch(qn, qp, k, n_probes, pass_1)[0]
+        out = self._unsharded_device_index().query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed)[0]
         return out[out != -1] if out[-1] == -1 else out
 
-    def query_batch(self, qs, k, n_probes=1, pass_1=None, fast=False):
+    def query_batch(self, qs, k, n_probes=1, pass_1=None, fast=False, *, allowed=None):
         """(nq, d) queries -> (nq, k) int64 ids, rows padded with -1 when the
         reference would return fewer than k ids.  (The reference's README shows a
         2-d `ivf.query(queries, ...)` that its code does not support; this is that
@@ -1024,6 +1149,13 @@ class IVF:
         of numpy's per-query BLAS calls (35 ms per 10 000 queries on the host) — within
         1 ulp of them, so a rare id can differ from the reference's; the default is exact."""
         self._unsharded_device_index()
+        if allowed is not None:
+            if fast:
+                raise NotImplementedError("IVF.query_batch: fast=True with allowed= is not supported; "
+                                          "use the exact default (fast=False)")
+            qs = np.array(qs, dtype=np.float32, order="C", copy=True)
+            qn, qp = self._prepare(qs)
+            return self.device_index().query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed)
         if fast:
             return self.device_index().query_batch_raw(qs, k, n_probes, pass_1)
         R = self.pq.R
