@@ -24,6 +24,16 @@ def test_heap_larger_than_lds_is_refused_and_index_survives(small):
     np.testing.assert_array_equal(dev.query_batch(g["qn"], g["qpq"], 10, 5), g["ids_p5"])
 
 
+def test_scan_and_plain_modes_beyond_the_documented_ones_are_refused(small):
+    """tk_index_set_scan_mode / tk_index_set_plain_scan take 0-2 (tinyknn_hip.h); 3 is TK_ERR_ARG (-1)."""
+    from tinyknn_amd import _lib
+    g, ivf = small
+    dev = ivf.device_index()
+    L = _lib.lib()
+    assert [L.tk_index_set_scan_mode(dev._h, 3), L.tk_index_set_plain_scan(dev._h, 3)] == [-1, -1]
+    np.testing.assert_array_equal(dev.query_batch(g["qn"], g["qpq"], 10, 5), g["ids_p5"])
+
+
 @pytest.mark.parametrize("pass_1", [149, 150, 232, 574, 575, 1500])
 def test_heap_sizes_around_the_lane_kernel_limits(small, oracle, pass_1):
     """pass_1 = 574 is the largest heap of the lane-per-query kernel, 149 with the duplicate test;

@@ -100,6 +100,20 @@ extern "C" int tk_estimate_pq(const uint64_t *data, int64_t chunks, int M, const
     return tk_estimate_pq_batch(data, chunks, M, tables, 1, out, signd, order);
 }
 
+// ONE query's replay over the rows of a flat scan: one slot (slots_i: prefix[0..1], n; slots_l: label offset)
+template <class Bufs>
+static TkReplayJob flat_replay_job(Bufs &b, int64_t chunks, int64_t cap_min, const int64_t *labels, int64_t *heap_idx,
+                                   int32_t *heap_val, int R, int signd)
+{
+    TkReplayJob j;
+    j.dist = b.out.template as<uint4>(); j.cap = chunks; j.nq = 1;
+    j.mins = b.mins.template as<uint8_t>(); j.cap_min = cap_min;
+    j.slot_prefix = b.slots_i.template as<int>(); j.slot_n = b.slots_i.template as<int>() + 2;
+    j.slot_label_off = b.slots_l.template as<int64_t>(); j.S = 1; j.slots_uniform = 1;
+    j.labels = labels; j.heap_idx = heap_idx; j.heap_val = heap_val; j.R = R; j.signd = signd;
+    return j;
+}
+
 extern "C" int tk_query_pq(const uint64_t *data, int64_t chunks, int M, int64_t n,
                            const uint64_t *tables, int64_t *indices, int32_t *vals, int R,
                            int signd, const int64_t *labels, int order)
@@ -144,18 +158,15 @@ extern "C" int tk_query_pq(const uint64_t *data, int64_t chunks, int M, int64_t 
     // wave-per-query replay with the heap in registers (heap.hip: heap_replay_pair_kernel; position entries without labels,
     // (value, label64) entries with the reference's duplicate test with them) instead of the general kernel's LDS heap —
     // ~300 instead of ~2 000 cycles per insert.  Same arrays out.
-    bool fresh_heap = R <= TK_PAIR_MAX_R && chunks * 16 <= 0xffffff;
+    bool fresh_heap = R <= TK_PAIR_MAX_R && tk_positions_fit(chunks);
     for (int i = 0; i < R && fresh_heap; i++) fresh_heap = indices[i] == -1 && vals[i] == (signd ? 127 : 255);
+    const TkReplayJob j = flat_replay_job(S, chunks, cap_min, S.labels.as<int64_t>(), S.hidx.as<int64_t>(),
+                                          S.hval.as<int32_t>(), R, signd);
     if (fresh_heap) {
-        if (tk_launch_heap_replay_pair(S.out.as<uint4>(), chunks, 1, S.mins.as<uint8_t>(), cap_min, S.slots_i.as<int>(),
-                                       S.slots_i.as<int>() + 2, S.slots_l.as<int64_t>(), 1, S.labels.as<int64_t>(),
-                                       S.hidx.as<int64_t>(), S.hval.as<int32_t>(), R, signd, 1, nullptr, labels ? 1 : 0, st))
+        if (tk_launch_heap_replay_pair(j, nullptr, labels ? TK_PAIR_DEDUPE_ALL : 0, st))
             return fail(TK_ERR_HIP, "heap_replay_pair_kernel launch failed");
     } else {
-        tk_launch_heap_replay(S.out.as<uint4>(), chunks, 1, S.slots_i.as<int>(),
-                              S.slots_i.as<int>() + 2, S.slots_l.as<int64_t>(), 1,
-                              S.labels.as<int64_t>(), S.hidx.as<int64_t>(), S.hval.as<int32_t>(), R,
-                              signd, 1, nullptr, st, S.mins.as<uint8_t>(), cap_min);
+        tk_launch_heap_replay(j, st);
     }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(indices, S.hidx.p, (size_t)R * 8, hipMemcpyDeviceToHost, st));
@@ -405,7 +416,7 @@ extern "C" int tk_codes_query(tk_codes *c, int64_t n, const uint64_t *tables, in
     bool fresh_heap = !labels && R <= TK_PAIR_MAX_R && (size_t)c->M * 16 <= 32 * 1024;
     for (int i = 0; i < R && fresh_heap; i++) fresh_heap = indices[i] == -1 && vals[i] == (signd ? 127 : 255);
     const bool fresh = fresh_heap && chunks >= 4096 && R <= 64;
-    if (fresh_heap && !fresh && chunks * 16 <= 0xffffff) {
+    if (fresh_heap && !fresh && tk_positions_fit(chunks)) {
         // A fresh heap of up to 513 entries over a shorter array (DistanceTable.top of one query over a few thousand to a
         // million rows, examples/example.py: 16 000 rows, R = 2 k + 10 = 30): table in through pinned memory, the scan, the
         // wave-per-query replay with the heap in registers (heap.hip: heap_replay_pair_kernel, position entries — positions
@@ -427,9 +438,8 @@ extern "C" int tk_codes_query(tk_codes *c, int64_t n, const uint64_t *tables, in
         HIPCHECK(hipMemcpyAsync(c->slots_l.p, psl + 4, sizeof(int64_t), hipMemcpyHostToDevice, st));
         tk_launch_scan_flat(c->tiled.as<uint4>(), chunks, c->M, c->tables.as<uint4>(), 1,
                             c->out.as<uint4>(), chunks, c->mins.as<uint8_t>(), cap_min, signd, order, st);
-        if (tk_launch_heap_replay_pair(c->out.as<uint4>(), chunks, 1, c->mins.as<uint8_t>(), cap_min, c->slots_i.as<int>(),
-                                       c->slots_i.as<int>() + 2, c->slots_l.as<int64_t>(), 1, nullptr, pidx, pval, R, signd,
-                                       1, nullptr, 0, st))
+        const TkReplayJob j = flat_replay_job(*c, chunks, cap_min, nullptr, pidx, pval, R, signd);
+        if (tk_launch_heap_replay_pair(j, nullptr, 0, st))
             return fail(TK_ERR_HIP, "heap_replay_pair_kernel launch failed");
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipStreamSynchronize(st));
@@ -488,10 +498,8 @@ extern "C" int tk_codes_query(tk_codes *c, int64_t n, const uint64_t *tables, in
     // the scan also writes each block's minimum: the replay walks 1024 blocks per step on them
     tk_launch_scan_flat(c->tiled.as<uint4>(), chunks, c->M, c->tables.as<uint4>(), 1,
                         c->out.as<uint4>(), chunks, c->mins.as<uint8_t>(), cap_min, signd, order, st);
-    tk_launch_heap_replay(c->out.as<uint4>(), chunks, 1, c->slots_i.as<int>(),
-                          c->slots_i.as<int>() + 2, c->slots_l.as<int64_t>(), 1,
-                          c->labels.as<int64_t>(), c->hidx.as<int64_t>(), c->hval.as<int32_t>(), R,
-                          signd, 1, nullptr, st, c->mins.as<uint8_t>(), cap_min);
+    tk_launch_heap_replay(flat_replay_job(*c, chunks, cap_min, c->labels.as<int64_t>(), c->hidx.as<int64_t>(),
+                                          c->hval.as<int32_t>(), R, signd), st);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(indices, c->hidx.p, (size_t)R * 8, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(vals, c->hval.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));

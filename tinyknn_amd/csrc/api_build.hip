@@ -582,7 +582,7 @@ extern "C" int tk_index_top_centers(tk_index *ix, const float *q, const void *q_
     Work &w = ix->works[0];
     const int M = ix->M;
     const size_t esz = q_pq_is_f64 ? 8 : 4;
-    const bool lanes = ix->heap_mode == 0 && ix->center_chunks * 16 <= 0xffffff && p.rescore <= TK_LANES_MAX_R;
+    const bool lanes = ix->heap_mode == 0 && tk_positions_fit(ix->center_chunks) && p.rescore <= TK_LANES_MAX_R;
     const bool lazy = lanes && ix->center_chunks >= 1024;
     const int hc = (int)(ix->center_chunks / 64 < 16 ? 16 : ix->center_chunks / 64);     // exact head, in chunks
     bool flat_plain = lanes && ix->plain_mode != 1 && plain_env_on() && tk_plain_fits(M) && ix->flat_plain_ok &&
@@ -629,12 +629,13 @@ extern "C" int tk_index_top_centers(tk_index *ix, const float *q, const void *q_
             Prof pf;
             return coarse_replay_probes(ix, w, ix->q.as<float>(), m, p, w.probes.as<int64_t>(), nullptr, pf);
         }
-        if (tk_launch_heap_replay_lanes(w.cdist.as<uint4>(), ix->center_chunks, m, ix->cslots_i.as<int>(),
-                                        ix->cslots_i.as<int>() + 2, ix->cslots_l.as<int64_t>(), 1, nullptr,
-                                        w.cheap_idx.as<int64_t>(), w.cheap_val.as<int32_t>(), p.rescore, 1, 1,
-                                        plain ? w.repeat_flag.as<unsigned char>() : nullptr, w.cmins.as<uint8_t>(),
-                                        p.ccap_min, nullptr, nullptr, plain ? w.plain0.as<int>() : nullptr,
-                                        plain ? w.qlim.as<int>() : nullptr, lazy ? 1 : 0))
+        TkLanesOpts o;
+        o.lazy = lazy ? 1 : 0;
+        if (plain) {
+            o.skip = w.repeat_flag.as<unsigned char>();
+            o.check = {w.plain0.as<int>(), w.qlim.as<int>()};
+        }
+        if (tk_launch_heap_replay_lanes(centre_replay_job(ix, w, m, p), o, nullptr))
             return fail(TK_ERR_HIP, "hipFuncSetAttribute(LDS size) failed");
         tk_launch_rescore(ix->q.as<float>(), 0, ix->d, ix->active_centers.p, 0, ix->n_lists,
                           w.cheap_idx.as<int64_t>(), p.rescore, m, p.kc, 0, w.probes.as<int64_t>(), nullptr, nullptr,

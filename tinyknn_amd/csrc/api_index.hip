@@ -349,7 +349,13 @@ bool twin_replay(const tk_index *ix, const Plan &p)
 {
     return !ix->ids_unique && ix->twin_w > 0 && ix->opt_replay_twin == 1 && ix->heap_mode == 0 &&
            (!ix->twin_unverified || ix->twin_vouched) &&
-           ix->total_ids < (1ll << 31) && p.cap * 16 <= 0xffffff && tk_lanes_twin_fits(p.R, p.S, ix->n_lists);
+           ix->total_ids < (1ll << 31) && tk_positions_fit(p.cap) && tk_lanes_twin_fits(p.R, p.S, ix->n_lists);
+}
+
+// the lane replay with the duplicate test on int32 labels fits (labels that repeat, no twin table)
+static bool dedupe_lanes_fit(const tk_index *ix, const Plan &p)
+{
+    return ix->have_ids32 && tk_lanes_dedupe_fits(p.R, p.S) && ix->total_ids < (1ll << 31);
 }
 
 // the wave-per-query replay with the heap in registers (heap.hip: heap_replay_pair_kernel): small batches — ONE query
@@ -375,7 +381,7 @@ static bool plain_possible(const tk_index *ix, const Plan &p)
 {
     if (ix->plain_mode == 1 || !plain_env_on() || ix->sharded || p.S < 2 || !tk_plain_fits(ix->M)) return false;
     // (heap_mode 3: the register heap makes the lemma's check as the lane kernel does)
-    if ((ix->heap_mode != 0 && !(ix->heap_mode == 3 && p.R <= TK_PAIR_MAX_R)) || ix->scan_mode == 1 || p.cap * 16 > 0xffffff)
+    if ((ix->heap_mode != 0 && !(ix->heap_mode == 3 && p.R <= TK_PAIR_MAX_R)) || ix->scan_mode == 1 || !tk_positions_fit(p.cap))
         return false;
     if (ix->ids_unique) return p.R <= TK_LANES_MAX_R;
     // repeating labels with the TWIN form of the lane replay: as with distinct labels
@@ -385,7 +391,7 @@ static bool plain_possible(const tk_index *ix, const Plan &p)
     // beside it only stretches that replay — same box, glove-like build_probes = 2: 1.33 ms per batch
     // on the exact kernel, 1.55 ms with the plain path (profiles/r03/ab_build_probes2.txt).  Only on
     // request (mode 2), which is how the tests reach this branch.
-    return ix->plain_mode == 2 && ix->have_ids32 && tk_lanes_dedupe_fits(p.R, p.S) && ix->total_ids < (1ll << 31);
+    return ix->plain_mode == 2 && dedupe_lanes_fit(ix, p);
 }
 
 // The plain path is exact for every query, but a FLAGGED query is scanned twice and replayed
@@ -752,6 +758,32 @@ void launch_coarse_scan(tk_index *ix, Work &w, int64_t nq, const Plan &p, hipStr
                             w.cmins.as<uint8_t>(), p.ccap_min, 1, ix->order, st);
 }
 
+// the replay over the coded centres of queries [0, nq): ONE slot that every query shares, positions as labels
+TkReplayJob centre_replay_job(const tk_index *ix, Work &w, int64_t nq, const Plan &p)
+{
+    TkReplayJob j;
+    j.dist = w.cdist.as<uint4>(); j.cap = ix->center_chunks; j.nq = nq;
+    j.mins = w.cmins.as<uint8_t>(); j.cap_min = p.ccap_min;
+    j.slot_prefix = ix->cslots_i.as<int>(); j.slot_n = ix->cslots_i.as<int>() + 2;
+    j.slot_label_off = ix->cslots_l.as<int64_t>(); j.S = 1; j.slots_uniform = 1;
+    j.heap_idx = w.cheap_idx.as<int64_t>(); j.heap_val = w.cheap_val.as<int32_t>(); j.R = p.rescore; j.signd = 1;
+    return j;
+}
+
+// the register heap's duplicate test on one register per slot (every label below 0xffffff; TK_OPT_LABELS24)
+static int pair_labels24(const tk_index *ix) { return ix->labels24 && ix->opt_labels24 ? TK_PAIR_LABELS24 : 0; }
+// packed entries (lane, register-heap and packed replays) for rows of `chunks` chunks; heap_mode 1: the general kernel
+static bool packed_ok(const tk_index *ix, int64_t chunks) { return ix->heap_mode != 1 && tk_positions_fit(chunks); }
+
+// the general kernel from fresh heaps, block by block (its 1024-block steps on the minima: the query_pq paths only)
+static void replay_general(const TkReplayJob &j, hipStream_t st)
+{
+    TkReplayJob g = j;
+    g.mins = nullptr; g.cap_min = 0;
+    tk_launch_heap_fill(g.heap_idx, g.heap_val, g.nq * g.R, 127, st);
+    tk_launch_heap_replay(g, st);
+}
+
 // 2b. rest of the coarse stage: heap replay over the coded centres, probe lists, per-slot
 // descriptors.  `pair_count`: per-list (query, slot) pair counters for the list-major scan
 // (or NULL); with `owner` only the lists owned by `me` are counted (list-sharded index).
@@ -762,35 +794,18 @@ int coarse_replay_probes(tk_index *ix, Work &w, const float *q_dev, int64_t nq, 
 {
     TRY(pf.mark(st));
     // positions of one list against a fresh heap are distinct labels: lane-per-query
-    const bool fast_c = ix->heap_mode != 1 && ix->center_chunks * 16 <= 0xffffff;
+    const TkReplayJob j = centre_replay_job(ix, w, nq, p);
+    const bool fast_c = packed_ok(ix, ix->center_chunks);
     const bool lanes_c = fast_c && ix->heap_mode == 0 && p.rescore <= TK_LANES_MAX_R;
-    if (fast_c && pair_replay(ix, nq, p.rescore)) {
-        tk_launch_heap_replay_pair(w.cdist.as<uint4>(), ix->center_chunks, nq, w.cmins.as<uint8_t>(), p.ccap_min,
-                                   ix->cslots_i.as<int>(), ix->cslots_i.as<int>() + 2, ix->cslots_l.as<int64_t>(), 1,
-                                   nullptr, w.cheap_idx.as<int64_t>(), w.cheap_val.as<int32_t>(), p.rescore, 1, 1,
-                                   nullptr, 0, st);
-    } else if (fast_c && !lanes_c) {
-        tk_launch_heap_replay_packed(w.cdist.as<uint4>(), ix->center_chunks, nq,
-                                     ix->cslots_i.as<int>(), ix->cslots_i.as<int>() + 2,
-                                     ix->cslots_l.as<int64_t>(), 1, nullptr,
-                                     w.cheap_idx.as<int64_t>(), w.cheap_val.as<int32_t>(),
-                                     p.rescore, 1, 1, nullptr, 0, 0, st);
-    } else if (lanes_c) {
-        if (tk_launch_heap_replay_lanes(w.cdist.as<uint4>(), ix->center_chunks, nq,
-                                        ix->cslots_i.as<int>(), ix->cslots_i.as<int>() + 2,
-                                        ix->cslots_l.as<int64_t>(), 1, nullptr,
-                                        w.cheap_idx.as<int64_t>(), w.cheap_val.as<int32_t>(),
-                                        p.rescore, 1, 1, nullptr, w.cmins.as<uint8_t>(),
-                                        p.ccap_min, nullptr, st))
+    if (fast_c && pair_replay(ix, nq, p.rescore))
+        tk_launch_heap_replay_pair(j, nullptr, 0, st);
+    else if (fast_c && !lanes_c)
+        tk_launch_heap_replay_packed(j, nullptr, TK_RUN_UNFLAGGED, /*dedupe=*/false, st);
+    else if (lanes_c) {
+        if (tk_launch_heap_replay_lanes(j, TkLanesOpts(), st))
             return fail(TK_ERR_HIP, "hipFuncSetAttribute(LDS size) failed");
-    } else {
-        tk_launch_heap_fill(w.cheap_idx.as<int64_t>(), w.cheap_val.as<int32_t>(),
-                            nq * p.rescore, 127, st);
-        tk_launch_heap_replay(w.cdist.as<uint4>(), ix->center_chunks, nq,
-                              ix->cslots_i.as<int>(), ix->cslots_i.as<int>() + 2,
-                              ix->cslots_l.as<int64_t>(), 1, nullptr, w.cheap_idx.as<int64_t>(),
-                              w.cheap_val.as<int32_t>(), p.rescore, 1, 1, nullptr, st);
-    }
+    } else
+        replay_general(j, st);
     TRY(pf.mark(st));
     const int fused = tk_launch_rescore(q_dev, 0, ix->d, ix->active_centers.p, 0, ix->n_lists,
                                         w.cheap_idx.as<int64_t>(), p.rescore, nq, p.kc, 0, probes_out, nullptr, st,
@@ -900,11 +915,6 @@ int stage_coarse_rest(tk_index *ix, Work &w, const float *q_dev, int64_t nq, con
     return TK_OK;
 }
 
-// Stages 3b-4: the heap replay over the distance rows of queries [q0, q0 + nq) of the
-// batch's slot arrays (dist/mins/heaps: `nq` rows starting at row 0), then the exact
-// rescoring.  q_dev: row 0 = query q0.
-// the queries the lane replay flagged (bound above the table's limit at the first plain block:
-// plain_scan.hip): every probed list again with the exact kernel, then the replay again
 // the flagged count is on its way to the page-locked word: the event the state machine polls behind
 static void plain_verdict_event(tk_index *ix, Work &w, int64_t nq, hipStream_t st)
 {
@@ -925,8 +935,9 @@ static void apply_allow(Work &w, int64_t q0, int64_t nq, const Plan &p, const tk
                              allow->bits.as<uint16_t>(), 1, only, st);
 }
 
-// list_built: the lane replay compiled the list of flagged queries itself (tk_launch_heap_replay_lanes' flag_list); the
-// count then reaches the host through the packed kernel behind the re-scan (plain_verdict_event there)
+// The queries the replay flagged (bound above the table's limit at the first plain block, plain_scan.hip): every probed
+// list again with the exact kernel.  list_built: the replay listed them itself (TkPlainCheck::flag_list); the count then
+// reaches the host through the replay behind the re-scan (replay_flagged_tail)
 static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, hipStream_t st,
                            const tk_allow *allow, bool list_built = false)
 {
@@ -948,38 +959,70 @@ static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const 
 // One wave per query either way; heaps of up to 129 entries take the register heap (a flagged query of the 100M x 128
 // index is ~1 300 inserts over 6 250 blocks: the packed kernel's LDS heap with its label scan per insert made ONE such
 // query a 1.2 ms tail behind a 1.9 ms replay of the other 9 999, profiles/r06/c5_flagged_tail.txt)
-static void replay_flagged_tail(tk_index *ix, Work &w, int64_t nq, const Plan &p, const int *slot_prefix, const int *slot_n,
-                                const int64_t *slot_loff, unsigned char *repeat_flag, hipStream_t st)
+static void replay_flagged_tail(tk_index *ix, Work &w, const TkReplayJob &j, unsigned char *flags, hipStream_t st)
 {
-    if (p.R <= TK_PAIR_MAX_R && (ix->heap_mode == 0 || ix->heap_mode == 3) && ix->opt_pair_nq > 0) {
-        (void)tk_launch_heap_replay_pair(w.dist.as<uint4>(), p.cap, nq, w.mins.as<uint8_t>(), p.cap_min, slot_prefix, slot_n,
-                                         slot_loff, p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
-                                         w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, (ix->labels24 && ix->opt_labels24) ? 2 : 0, st, nullptr,
-                                         nullptr, nullptr, 1, w.flag_list.as<int>(), w.flag_host);
+    if (j.R <= TK_PAIR_MAX_R && (ix->heap_mode == 0 || ix->heap_mode == 3) && ix->opt_pair_nq > 0) {
+        (void)tk_launch_heap_replay_pair(j, flags, pair_labels24(ix), st, TkPlainCheck(), /*only_flagged=*/true,
+                                         w.flag_list.as<int>(), w.flag_host);
         return;
     }
-    tk_launch_heap_replay_packed(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n, slot_loff,
-                                 p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
-                                 w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, -1, 1, st,
-                                 w.flag_list.as<int>(), w.flag_host);
+    tk_launch_heap_replay_packed(j, flags, TK_RUN_FLAGGED, /*dedupe=*/true, st, w.flag_list.as<int>(), w.flag_host);
 }
 
-int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
-                      const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain,
-                      TkSecond q2, TkSecond out2, int *plain_flag, const tk_allow *allow)
+// the replay over the probed lists of queries [q0, q0 + nq) of the batch (dist / mins / heaps: `nq` rows from row 0)
+static TkReplayJob list_replay_job(const tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p)
 {
-    const int *slot_exact = plain ? w.plain0.as<int>() + q0 : nullptr;     // (first plain chunk per query)
-    const int *qlim = plain ? w.qlim.as<int>() + q0 : nullptr;
-    const int *slot_prefix = w.slot_prefix.as<int>() + q0 * (p.S + 1);
-    const int *slot_n = w.slot_n.as<int>() + q0 * p.S;
-    const int64_t *slot_loff = w.slot_loff.as<int64_t>() + q0 * p.S;
-    unsigned char *repeat_flag = w.repeat_flag.as<unsigned char>() + q0;
+    TkReplayJob j;
+    j.dist = w.dist.as<uint4>(); j.cap = p.cap; j.nq = nq;
+    j.mins = w.mins.as<uint8_t>(); j.cap_min = p.cap_min;
+    j.slot_prefix = w.slot_prefix.as<int>() + q0 * (p.S + 1); j.slot_n = w.slot_n.as<int>() + q0 * p.S;
+    j.slot_label_off = w.slot_loff.as<int64_t>() + q0 * p.S; j.S = p.S; j.R = p.R; j.signd = 1;
+    j.labels = ix->ids.as<int64_t>(); j.heap_idx = w.heap_idx.as<int64_t>(); j.heap_val = w.heap_val.as<int32_t>();
+    return j;
+}
+
+// The forms of a batch's heap replay (heap.hip).  Every form but General starts from fresh heaps on packed entries.
+enum class Replay {
+    Pair,            // register heap, one query per wave (pair_replay: small batches, heap_mode 3)
+    Lanes,           // lane per query, distinct labels
+    PackedDistinct,  // packed wave kernel, distinct labels (heap_mode 2, heaps above TK_LANES_MAX_R)
+    LanesTwin,       // lane per query, labels that repeat: the duplicate test from the twin table
+    LanesDedupe,     // lane per query, labels that repeat: the duplicate test on int32 labels
+    Packed,          // packed wave kernel, the duplicate test for every query
+    General,         // general wave kernel (heap_mode 1, or rows too long for position entries)
+};
+
+// An unsharded `plain` batch is never PackedDistinct: plain_possible takes distinct labels only at heap_mode 0 with
+// R <= TK_LANES_MAX_R (Lanes) or heap_mode 3 with R <= TK_PAIR_MAX_R (Pair), and both settings flush pending batches.
+static Replay replay_form(const tk_index *ix, int64_t nq, const Plan &p)
+{
+    if (!packed_ok(ix, p.cap)) return Replay::General;
+    if (pair_replay(ix, nq, p.R)) return Replay::Pair;
+    if (ix->ids_unique) return ix->heap_mode == 0 && p.R <= TK_LANES_MAX_R ? Replay::Lanes : Replay::PackedDistinct;
+    if (twin_replay(ix, p)) return Replay::LanesTwin;
+    if (ix->heap_mode == 0 && dedupe_lanes_fit(ix, p)) return Replay::LanesDedupe;
+    return Replay::Packed;
+}
+
+// Stages 3b-4: the heap replay over the distance rows of queries [q0, q0 + nq) of the
+// batch's slot arrays (dist/mins/heaps: `nq` rows starting at row 0), then the exact
+// rescoring.  q_dev: row 0 = query q0.
+int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
+               const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain,
+               TkSecond q2, TkSecond out2, int *plain_flag, const tk_allow *allow)
+{
+    const TkReplayJob j = list_replay_job(ix, w, q0, nq, p);
+    unsigned char *flags = w.repeat_flag.as<unsigned char>() + q0;
+    // behind the plain kernel: the lemma's check per query (first plain chunk, limit), and the list of the queries the
+    // replay leaves for the exact re-scan — none on a list-sharded rank (plain_flag: the codes are elsewhere)
+    TkPlainCheck check;
+    if (plain) check = {w.plain0.as<int>() + q0, w.qlim.as<int>() + q0, plain_flag ? nullptr : w.flag_list.as<int>()};
     apply_allow(w, q0, nq, p, allow, st);
     // heaps start fresh here, so packed entries apply.  Distinct labels: one query per
     // lane (or per wave for big heaps), and the few queries whose probe list wrapped a -1
     // (a list may then be scanned twice) re-run with the duplicate test.  Repeating labels
     // (build n_probes >= 2): the packed wave kernel with the duplicate test for everybody.
-    const bool packed_ok = ix->heap_mode != 1 && p.cap * 16 <= 0xffffff;
+    const Replay form = replay_form(ix, nq, p);
     // Lists far longer than the heap (100M x 128: a query's ten lists hold 6 250 blocks, its heap 111 entries):
     // staging every block through LDS is what the replay then costs (16 row-per-lane loads + 16 LDS writes per
     // segment and lane), while only the few blocks whose minimum passes the bound are ever looked at — the
@@ -991,122 +1034,73 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     const double blocks_per_query = (double)p.S * (double)ix->total_chunks / (double)ix->n_lists;
     const int lazy = ix->opt_replay_lazy >= 0 ? ix->opt_replay_lazy
                                               : (blocks_per_query >= (twin_replay(ix, p) ? 40.0 : 8.0) * p.R);
-    if (packed_ok && pair_replay(ix, nq, p.R)) {
+    // 1. the main replay
+    switch (form) {
+    case Replay::Pair:
         // one wave per query, heap in registers: position entries where labels are distinct (the queries whose probe
         // list names a list twice: the duplicate test on labels, as every query of an index whose labels repeat).
         // Behind the plain kernel: the lemma's check per query, as the lane kernel makes it (it does not depend on how the
-        // duplicate test is made: below the limit the plain values ARE the reference's); the queries that fail it and
-        // those flagged beforehand are scanned again exactly and replayed by the packed kernel with the duplicate test —
-        // or, on a list-sharded rank (plain_flag: the codes are elsewhere), raise the batch's flag word
-        if (tk_launch_heap_replay_pair(w.dist.as<uint4>(), p.cap, nq, w.mins.as<uint8_t>(), p.cap_min, slot_prefix, slot_n,
-                                       slot_loff, p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
-                                       w.heap_val.as<int32_t>(), p.R, 1, 0, (plain || ix->ids_unique) ? repeat_flag : nullptr,
-                                       (ix->ids_unique ? 0 : 1) | ((ix->labels24 && ix->opt_labels24) ? 2 : 0), st, slot_exact, qlim,
-                                       plain && !plain_flag ? w.flag_list.as<int>() : nullptr))
+        // duplicate test is made: below the limit the plain values ARE the reference's)
+        if (tk_launch_heap_replay_pair(j, (plain || ix->ids_unique) ? flags : nullptr,
+                                       (ix->ids_unique ? 0 : TK_PAIR_DEDUPE_ALL) | pair_labels24(ix), st, check))
             return fail(TK_ERR_HIP, "hipMemsetAsync(flag list) failed");
-        if (plain && plain_flag) {
-            tk_launch_shard_flag_plain(repeat_flag, nq, plain_flag, st);
-            tk_launch_heap_replay_packed(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n, slot_loff,
-                                         p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
-                                         w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, 1, 1, st);
-        } else if (plain) {
-            rescan_flagged(ix, w, q0, nq, p, st, allow, true);
-            replay_flagged_tail(ix, w, nq, p, slot_prefix, slot_n, slot_loff, repeat_flag, st);
-            plain_verdict_event(ix, w, nq, st);
-        }
-    } else if (packed_ok && ix->ids_unique) {
-        const bool lanes = ix->heap_mode == 0 && p.R <= TK_LANES_MAX_R;
-        if (!lanes)
-            tk_launch_heap_replay_packed(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n,
-                                         slot_loff, p.S, ix->ids.as<int64_t>(),
-                                         w.heap_idx.as<int64_t>(), w.heap_val.as<int32_t>(), p.R,
-                                         1, 0, repeat_flag, 0, 0, st);
-        else if (tk_launch_heap_replay_lanes(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n,
-                                             slot_loff, p.S, ix->ids.as<int64_t>(),
-                                             w.heap_idx.as<int64_t>(), w.heap_val.as<int32_t>(),
-                                             p.R, 1, 0, repeat_flag, w.mins.as<uint8_t>(),
-                                             p.cap_min, nullptr, st, slot_exact, qlim, lazy,
-                                             ix->opt_replay_count ? ix->replay_counters.as<unsigned long long>() : nullptr,
-                                             nullptr, lanes && plain && !plain_flag ? w.flag_list.as<int>() : nullptr))
-            return fail(TK_ERR_HIP, "hipFuncSetAttribute(LDS size) failed");
-        if (plain && plain_flag) {
-            tk_launch_shard_flag_plain(repeat_flag, nq, plain_flag, st);
-        } else if (plain && lanes) {
-            // flag 2 = the lane replay's "bound above the limit at the first plain block", flag 1 = a probe list that
-            // names a list twice: exact re-scan of both kinds (the lane replay listed them), then ONE launch of the
-            // packed kernel with the duplicate test from fresh heaps (where labels are distinct the test never fires)
-            rescan_flagged(ix, w, q0, nq, p, st, allow, true);
-            replay_flagged_tail(ix, w, nq, p, slot_prefix, slot_n, slot_loff, repeat_flag, st);
-            plain_verdict_event(ix, w, nq, st);
-        } else if (plain) {
-            rescan_flagged(ix, w, q0, nq, p, st, allow);
-            tk_launch_heap_replay_packed(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n, slot_loff,
-                                         p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
-                                         w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, 2, 0, st);
-        }
-        if (!(plain && lanes && !plain_flag))
-        tk_launch_heap_replay_packed(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n, slot_loff,
-                                     p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
-                                     w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, 1, 1, st);
-    } else if (packed_ok && twin_replay(ix, p)) {
-        // repeating labels, every copy of a label with ONE value (IVF.build(n_probes >= 2)): one query per lane,
-        // position entries, `insert`'s duplicate test decided from the twin table (heap.hip, TWIN form).  The
-        // queries that probe a list twice (repeat_flag 1) and, with `plain`, those the lemma's check flags (2)
-        // go to the packed kernel with the reference's scan of the labels
+        break;
+    case Replay::Lanes:
+    case Replay::LanesTwin:
+    case Replay::LanesDedupe: {
+        TkLanesOpts o;
         TkTwins tw;
-        tw.list = ix->twin_list.as<int32_t>();
-        tw.off = ix->twin_off.as<int32_t>();
-        tw.w = ix->twin_w;
-        // (a list-sharded index replays its home queries: the batch's probe lists are the scan stage's)
-        tw.probes = (ix->sharded && w.shard_probes ? w.shard_probes : w.probes.as<int64_t>()) + q0 * p.S;
-        tw.bm_words = tk_lanes_twin_bm_words(ix->n_lists);
-        if (tk_launch_heap_replay_lanes(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n,
-                                        slot_loff, p.S, ix->ids.as<int64_t>(),
-                                        w.heap_idx.as<int64_t>(), w.heap_val.as<int32_t>(), p.R, 1,
-                                        0, repeat_flag, w.mins.as<uint8_t>(), p.cap_min, nullptr, st,
-                                        slot_exact, qlim, lazy,
-                                        ix->opt_replay_count ? ix->replay_counters.as<unsigned long long>() : nullptr,
-                                        &tw, plain && !plain_flag ? w.flag_list.as<int>() : nullptr))
-            return fail(TK_ERR_HIP, "hipFuncSetAttribute(LDS size) failed");
-        if (plain && plain_flag) {
-            tk_launch_shard_flag_plain(repeat_flag, nq, plain_flag, st);
-            tk_launch_heap_replay_packed(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n, slot_loff,
-                                         p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
-                                         w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, 1, 1, st);
-        } else if (plain) {         // (flags 1 and 2 alike: re-scan, one launch of the packed kernel)
-            rescan_flagged(ix, w, q0, nq, p, st, allow, true);
-            replay_flagged_tail(ix, w, nq, p, slot_prefix, slot_n, slot_loff, repeat_flag, st);
-            plain_verdict_event(ix, w, nq, st);
+        o.check = check;
+        if (form == Replay::LanesDedupe) {      // (the queries it flags are listed behind it: rescan_flagged)
+            o.skip = plain ? flags : nullptr;
+            o.labels32 = ix->ids32.as<int32_t>();
+            o.check.flag_list = nullptr;
         } else {
-            tk_launch_heap_replay_packed(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n, slot_loff,
-                                         p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
-                                         w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, 1, 1, st);
+            o.skip = flags;
+            o.lazy = lazy;
+            o.counters = ix->opt_replay_count ? ix->replay_counters.as<unsigned long long>() : nullptr;
         }
-    } else if (packed_ok && ix->have_ids32 && ix->heap_mode == 0 && tk_lanes_dedupe_fits(p.R, p.S) &&
-               ix->total_ids < (1ll << 31)) {
-        // repeating labels that fit int32: one query per lane with the duplicate test
-        // (plain: the queries whose probe list wrapped are left to the packed kernel below too)
-        if (tk_launch_heap_replay_lanes(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n,
-                                        slot_loff, p.S, ix->ids.as<int64_t>(),
-                                        w.heap_idx.as<int64_t>(), w.heap_val.as<int32_t>(), p.R, 1,
-                                        0, plain ? repeat_flag : nullptr, w.mins.as<uint8_t>(), p.cap_min,
-                                        ix->ids32.as<int32_t>(), st, slot_exact, qlim))
+        if (form == Replay::LanesTwin) {
+            // every copy of a label with ONE value (IVF.build(n_probes >= 2)): position entries, `insert`'s duplicate
+            // test decided from the twin table (heap.hip, TWIN form)
+            tw.list = ix->twin_list.as<int32_t>();
+            tw.off = ix->twin_off.as<int32_t>();
+            tw.w = ix->twin_w;
+            // (a list-sharded index replays its home queries: the batch's probe lists are the scan stage's)
+            tw.probes = (ix->sharded && w.shard_probes ? w.shard_probes : w.probes.as<int64_t>()) + q0 * p.S;
+            tw.bm_words = tk_lanes_twin_bm_words(ix->n_lists);
+            o.twins = &tw;
+        }
+        if (tk_launch_heap_replay_lanes(j, o, st))
             return fail(TK_ERR_HIP, "hipFuncSetAttribute(LDS size) failed");
-        if (plain) {
-            rescan_flagged(ix, w, q0, nq, p, st, allow);
-            tk_launch_heap_replay_packed(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n, slot_loff,
-                                         p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
-                                         w.heap_val.as<int32_t>(), p.R, 1, 0, repeat_flag, 1, 1, st);
-        }
-    } else if (packed_ok) {
-        tk_launch_heap_replay_packed(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n, slot_loff,
-                                     p.S, ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
-                                     w.heap_val.as<int32_t>(), p.R, 1, 0, nullptr, 0, 1, st);
-    } else {
-        tk_launch_heap_fill(w.heap_idx.as<int64_t>(), w.heap_val.as<int32_t>(), nq * p.R, 127, st);
-        tk_launch_heap_replay(w.dist.as<uint4>(), p.cap, nq, slot_prefix, slot_n, slot_loff, p.S,
-                              ix->ids.as<int64_t>(), w.heap_idx.as<int64_t>(),
-                              w.heap_val.as<int32_t>(), p.R, 1, 0, nullptr, st);
+        break;
+    }
+    case Replay::PackedDistinct:
+        tk_launch_heap_replay_packed(j, flags, TK_RUN_UNFLAGGED, /*dedupe=*/false, st);
+        break;
+    case Replay::Packed:
+        tk_launch_heap_replay_packed(j, nullptr, TK_RUN_UNFLAGGED, /*dedupe=*/true, st);
+        break;
+    case Replay::General:
+        replay_general(j, st);
+        break;
+    }
+    // 2. the queries it left: flag 1 (the probe list names a list twice) to the packed kernel with the duplicate test; with
+    // `plain`, flag 2 (the lemma's check failed) too, after an exact re-scan — or, on a list-sharded rank, the flag word
+    const bool listed = form == Replay::Pair || form == Replay::Lanes || form == Replay::LanesTwin;
+    const auto replay_wrapped = [&] { tk_launch_heap_replay_packed(j, flags, TK_RUN_WRAPPED, /*dedupe=*/true, st); };
+    if (plain && form == Replay::LanesDedupe) {
+        rescan_flagged(ix, w, q0, nq, p, st, allow);
+        replay_wrapped();
+    } else if (plain && plain_flag && (listed || form == Replay::PackedDistinct)) {
+        tk_launch_shard_flag_plain(flags, nq, plain_flag, st);
+        replay_wrapped();
+    } else if (plain && listed) {
+        rescan_flagged(ix, w, q0, nq, p, st, allow, true);
+        replay_flagged_tail(ix, w, j, flags, st);
+        plain_verdict_event(ix, w, nq, st);
+    } else if (!plain && (form == Replay::Lanes || form == Replay::LanesTwin || form == Replay::PackedDistinct)) {
+        replay_wrapped();
     }
     TRY(pf.mark(st));
     // 4. strip sentinels, exact rescoring                   ivf.py:154-163
@@ -1942,7 +1936,7 @@ extern "C" int tk_index_set_scan_mode(tk_index *ix, int mode)
 {
     IXLOCK(ix);
     ARGCHECK(ix, "null index");
-    ARGCHECK(mode >= 0 && mode <= 3, "mode");
+    ARGCHECK(mode >= 0 && mode <= 2, "mode");
     TRY(flush_pending(ix));
     ix->scan_mode = mode;
     return TK_OK;
@@ -1952,7 +1946,7 @@ extern "C" int tk_index_set_plain_scan(tk_index *ix, int mode)
 {
     IXLOCK(ix);
     ARGCHECK(ix, "null index");
-    ARGCHECK(mode >= 0 && mode <= 3, "mode");
+    ARGCHECK(mode >= 0 && mode <= 2, "mode");
     TRY(flush_pending(ix));
     ix->plain_mode = mode;
     ix->plain_state = PLAIN_PROBE;

@@ -326,6 +326,8 @@ int plain_blocks();
 int shard_plain_blocks();
 void launch_coarse_scan(tk_index *ix, Work &w, int64_t nq, const Plan &p, hipStream_t st,
                         const uint4 *tables = nullptr);
+// the replay over the coded centres of queries [0, nq) (one slot every query shares, positions as labels)
+TkReplayJob centre_replay_job(const tk_index *ix, Work &w, int64_t nq, const Plan &p);
 int coarse_replay_probes(tk_index *ix, Work &w, const float *q_dev, int64_t nq, const Plan &p,
                          int64_t *probes_out, hipStream_t st, Prof &pf, TkSecond q2 = TkSecond(),
                          const TkSlotsOut *slots = nullptr, int *slots_written = nullptr);

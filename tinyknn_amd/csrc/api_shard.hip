@@ -209,7 +209,7 @@ static bool shard_one_phase_possible(const tk_index *ix, const Plan &p, int64_t 
 {
     const int64_t tail = (int64_t)ix->world * capacity - ix->max_list_chunks;
     return shard_plain_possible(ix, p) && (ix->ids_unique || twin_replay(ix, p)) && tail >= 0 && p.R <= TK_LANES_MAX_R &&
-           ix->heap_mode == 0 && p.cap * 16 <= 0xffffff;
+           ix->heap_mode == 0 && tk_positions_fit(p.cap);
 }
 
 // ---- ... and with ONE byte per query exchanged first, for data on which the check at home would fail ----

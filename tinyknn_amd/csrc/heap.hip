@@ -266,26 +266,22 @@ __global__ __launch_bounds__(64 * TK_HEAP_WAVES) void heap_replay_kernel(
     }
 }
 
-void tk_launch_heap_replay(const uint4 *dist, int64_t cap, int64_t nq, const int *slot_prefix,
-                           const int *slot_n, const int64_t *slot_label_off, int S,
-                           const int64_t *labels, int64_t *heap_idx, int32_t *heap_val, int R,
-                           int signd, int slots_uniform, const unsigned char *only_flagged,
-                           hipStream_t s, const uint8_t *mins, int64_t cap_min)
+void tk_launch_heap_replay(const TkReplayJob &j, hipStream_t s)
 {
-    if (nq == 0 || R == 0) return;
-    const size_t wstride = ((size_t)R * 12 + 15) & ~(size_t)15;
+    if (j.nq == 0 || j.R == 0) return;
+    const size_t wstride = ((size_t)j.R * 12 + 15) & ~(size_t)15;
     int waves = (int)(64 * 1024 / wstride);   // large heaps: fewer query-waves per workgroup
     waves = waves < 1 ? 1 : (waves > TK_HEAP_WAVES ? TK_HEAP_WAVES : waves);
     size_t lds = wstride * waves;
-    dim3 grid((unsigned)((nq + waves - 1) / waves)), block(64 * waves);
-    if (signd)
-        hipLaunchKernelGGL(heap_replay_kernel<true>, grid, block, lds, s, dist, cap, slot_prefix,
-                           slot_n, slot_label_off, S, labels, heap_idx, heap_val, R, slots_uniform,
-                           only_flagged, nq, mins, cap_min);
+    dim3 grid((unsigned)((j.nq + waves - 1) / waves)), block(64 * waves);
+    if (j.signd)
+        hipLaunchKernelGGL(heap_replay_kernel<true>, grid, block, lds, s, j.dist, j.cap, j.slot_prefix,
+                           j.slot_n, j.slot_label_off, j.S, j.labels, j.heap_idx, j.heap_val, j.R, j.slots_uniform,
+                           /*only_flagged=*/(const unsigned char *)nullptr, j.nq, j.mins, j.cap_min);
     else
-        hipLaunchKernelGGL(heap_replay_kernel<false>, grid, block, lds, s, dist, cap, slot_prefix,
-                           slot_n, slot_label_off, S, labels, heap_idx, heap_val, R, slots_uniform,
-                           only_flagged, nq, mins, cap_min);
+        hipLaunchKernelGGL(heap_replay_kernel<false>, grid, block, lds, s, j.dist, j.cap, j.slot_prefix,
+                           j.slot_n, j.slot_label_off, j.S, j.labels, j.heap_idx, j.heap_val, j.R, j.slots_uniform,
+                           /*only_flagged=*/(const unsigned char *)nullptr, j.nq, j.mins, j.cap_min);
 }
 
 // ---------------------------------------------------------------------------
@@ -1347,23 +1343,20 @@ __global__ __launch_bounds__(64 * TK_HEAP_WAVES) void heap_replay_packed_kernel(
     }
 }
 
-void tk_launch_heap_replay_packed(const uint4 *dist, int64_t cap, int64_t nq, const int *slot_prefix,
-                                  const int *slot_n, const int64_t *slot_label_off, int S,
-                                  const int64_t *labels, int64_t *heap_idx, int32_t *heap_val,
-                                  int R, int signd, int slots_uniform, const unsigned char *flags,
-                                  int run_if, int dedupe, hipStream_t s, const int *flag_list, int *host_count)
+void tk_launch_heap_replay_packed(const TkReplayJob &j, const unsigned char *flags, int run_if, bool dedupe,
+                                  hipStream_t s, const int *flag_list, int *host_count)
 {
-    if (nq == 0 || R == 0) return;
-    const size_t wstride = dedupe ? (((size_t)R * 12 + 15) & ~(size_t)15) : (size_t)R * 4;
+    if (j.nq == 0 || j.R == 0) return;
+    const size_t wstride = dedupe ? (((size_t)j.R * 12 + 15) & ~(size_t)15) : (size_t)j.R * 4;
     int waves = (int)(64 * 1024 / wstride);
     waves = waves < 1 ? 1 : (waves > TK_HEAP_WAVES ? TK_HEAP_WAVES : waves);
     size_t lds = wstride * waves;
-    dim3 grid((unsigned)((nq + waves - 1) / waves)), block(64 * waves);
-#define TK_LAUNCH(S_, D_)                                                                        \
-    hipLaunchKernelGGL((heap_replay_packed_kernel<S_, D_>), grid, block, lds, s, dist, cap,      \
-                       slot_prefix, slot_n, slot_label_off, S, labels, heap_idx, heap_val, R,    \
-                       slots_uniform, flags, run_if, nq, flag_list, host_count)
-    if (signd) { if (dedupe) TK_LAUNCH(true, true); else TK_LAUNCH(true, false); }
+    dim3 grid((unsigned)((j.nq + waves - 1) / waves)), block(64 * waves);
+#define TK_LAUNCH(S_, D_)                                                                              \
+    hipLaunchKernelGGL((heap_replay_packed_kernel<S_, D_>), grid, block, lds, s, j.dist, j.cap,        \
+                       j.slot_prefix, j.slot_n, j.slot_label_off, j.S, j.labels, j.heap_idx, j.heap_val, \
+                       j.R, j.slots_uniform, flags, run_if, j.nq, flag_list, host_count)
+    if (j.signd) { if (dedupe) TK_LAUNCH(true, true); else TK_LAUNCH(true, false); }
     else { if (dedupe) TK_LAUNCH(false, true); else TK_LAUNCH(false, false); }
 #undef TK_LAUNCH
 }
@@ -1393,19 +1386,17 @@ int tk_lanes_dedupe_fits(int R, int S)
     return R <= TK_LANES_MAX_R_DEDUPE && tk_lanes_fixed_lds(R, S, 1) + 16384 <= 160 * 1024;
 }
 
-int tk_launch_heap_replay_lanes(const uint4 *dist, int64_t cap, int64_t nq, const int *slot_prefix,
-                                const int *slot_n, const int64_t *slot_label_off, int S,
-                                const int64_t *labels, int64_t *heap_idx, int32_t *heap_val, int R,
-                                int signd, int slots_uniform, unsigned char *skip,
-                                const uint8_t *mins, int64_t cap_min, const int32_t *labels32,
-                                hipStream_t s, const int *plain0, const int *qlim, int lazy,
-                                unsigned long long *counters, const TkTwins *twins, int *flag_list)
+int tk_launch_heap_replay_lanes(const TkReplayJob &j, const TkLanesOpts &o, hipStream_t s)
 {
+    const int64_t nq = j.nq;
+    const int R = j.R, S = j.S;
     if (nq == 0 || R == 0) return 0;
-    if (!plain0 || !qlim || !skip || !signd) plain0 = qlim = nullptr;
-    const int dedupe = labels32 != nullptr;
-    const bool twin = !dedupe && twins && twins->w > 0 && twins->list && twins->off && twins->probes && !slots_uniform;
-    const TkTwins tw = twin ? *twins : TkTwins();
+    TkPlainCheck c = o.check;
+    if (!c.plain0 || !c.qlim || !o.skip || !j.signd) c.plain0 = c.qlim = nullptr;
+    const int dedupe = o.labels32 != nullptr;
+    const TkTwins *t = o.twins;
+    const TkTwins tw = !dedupe && t && t->w > 0 && t->list && t->off && t->probes && !j.slots_uniform ? *t : TkTwins();
+    const bool twin = tw.w > 0;
     // Queries per wave: 64, or 32 with the duplicate test — a 64-query wave then needs 140+ KB of
     // LDS at R = 111: one workgroup per CU, and the two replay kernels of the pipelined mode (2 x 157
     // workgroups on 256 CUs) waited for each other's CUs (1.6 ms alone became 2.9 ms in the
@@ -1417,7 +1408,7 @@ int tk_launch_heap_replay_lanes(const uint4 *dist, int64_t cap, int64_t nq, cons
     // heap columns (+ label slots) + one staged segment (16 blocks x LW lanes x 16 B; the next one
     // waits in registers), scaled to the columns in use
     // (staging rows: none when LAZY, TK_LANES_SEG blocks without a duplicate test, 16 otherwise)
-    const size_t st_rows = dedupe ? (size_t)16384 : lazy ? 0 : twin ? (size_t)16384 : (size_t)1024 * TK_LANES_SEG;
+    const size_t st_rows = dedupe ? (size_t)16384 : o.lazy ? 0 : twin ? (size_t)16384 : (size_t)1024 * TK_LANES_SEG;
     const size_t lds = twin ? tk_lanes_twin_lds(R, S, tw.bm_words) + st_rows
                             : tk_lanes_fixed_lds(R, S, dedupe) * LWr / 64 + st_rows * LWr / 64;
     static bool attr_set = false;
@@ -1441,12 +1432,12 @@ int tk_launch_heap_replay_lanes(const uint4 *dist, int64_t cap, int64_t nq, cons
     {   // padding rows out of the way first (the kernels below no longer test `pos < n`)
         const int64_t items = nq * S;
         const unsigned pg = (unsigned)((items + 255) / 256);
-        if (items > 0 && signd)
-            hipLaunchKernelGGL(pad_fix_kernel<true>, dim3(pg), dim3(256), 0, s, (uint4 *)dist, cap, nq,
-                               slot_prefix, slot_n, S, slots_uniform, (uint8_t *)mins, cap_min, flag_list);
+        if (items > 0 && j.signd)
+            hipLaunchKernelGGL(pad_fix_kernel<true>, dim3(pg), dim3(256), 0, s, (uint4 *)j.dist, j.cap, nq,
+                               j.slot_prefix, j.slot_n, S, j.slots_uniform, (uint8_t *)j.mins, j.cap_min, c.flag_list);
         else if (items > 0)
-            hipLaunchKernelGGL(pad_fix_kernel<false>, dim3(pg), dim3(256), 0, s, (uint4 *)dist, cap, nq,
-                               slot_prefix, slot_n, S, slots_uniform, (uint8_t *)mins, cap_min, flag_list);
+            hipLaunchKernelGGL(pad_fix_kernel<false>, dim3(pg), dim3(256), 0, s, (uint4 *)j.dist, j.cap, nq,
+                               j.slot_prefix, j.slot_n, S, j.slots_uniform, (uint8_t *)j.mins, j.cap_min, c.flag_list);
     }
     // one query-wave per workgroup (multi-wave workgroups are placed only when a whole CU has room,
     // which next to the persistent scan kernels means at their launch boundaries)
@@ -1454,31 +1445,18 @@ int tk_launch_heap_replay_lanes(const uint4 *dist, int64_t cap, int64_t nq, cons
     const int64_t n_waves = (nq + LWr - 1) / LWr;
     dim3 grid((unsigned)n_waves);
     const int prio = 3;         // s_setprio of the replay waves: they share SIMDs with issue-bound scan waves
-#define TK_LAUNCH3(S_, D_, L_)                                                                    \
-    hipLaunchKernelGGL((heap_replay_lanes_kernel<S_, D_, L_>), grid, dim3(64), lds, s, dist, cap, nq,  \
-                       slot_prefix, slot_n, slot_label_off, S, labels, heap_idx, heap_val, R,     \
-                       slots_uniform, skip, 1, mins, cap_min, labels32, counters, prio, wave_lds,  \
-                       plain0, qlim, tw, flag_list)
-    if (dedupe) { if (signd) TK_LAUNCH3(true, true, 32); else TK_LAUNCH3(false, true, 32); }
+#define TK_LAUNCH(...)                                                                                          \
+    hipLaunchKernelGGL((heap_replay_lanes_kernel<__VA_ARGS__>), grid, dim3(64), lds, s, j.dist, j.cap, nq,            \
+                       j.slot_prefix, j.slot_n, j.slot_label_off, S, j.labels, j.heap_idx, j.heap_val, R,             \
+                       j.slots_uniform, o.skip, /*nbuf=*/1, j.mins, j.cap_min, o.labels32, o.counters, prio, wave_lds, \
+                       c.plain0, c.qlim, tw, c.flag_list)
+    if (dedupe) { if (j.signd) TK_LAUNCH(true, true, 32); else TK_LAUNCH(false, true, 32); }
     else if (twin) {
-#define TK_LAUNCH_TWIN(S_, Z_)                                                                    \
-    hipLaunchKernelGGL((heap_replay_lanes_kernel<S_, false, 64, Z_, true>), grid, dim3(64), lds, s, dist, cap, nq, \
-                       slot_prefix, slot_n, slot_label_off, S, labels, heap_idx, heap_val, R,     \
-                       slots_uniform, skip, 1, mins, cap_min, labels32, counters, prio, wave_lds,  \
-                       plain0, qlim, tw, flag_list)
-        if (signd) { if (lazy) TK_LAUNCH_TWIN(true, true); else TK_LAUNCH_TWIN(true, false); }
-        else { if (lazy) TK_LAUNCH_TWIN(false, true); else TK_LAUNCH_TWIN(false, false); }
-#undef TK_LAUNCH_TWIN
-    } else if (lazy) {
-#define TK_LAUNCH_LAZY(S_)                                                                        \
-    hipLaunchKernelGGL((heap_replay_lanes_kernel<S_, false, 64, true>), grid, dim3(64), lds, s, dist, cap, nq, \
-                       slot_prefix, slot_n, slot_label_off, S, labels, heap_idx, heap_val, R,     \
-                       slots_uniform, skip, 1, mins, cap_min, labels32, counters, prio, wave_lds,  \
-                       plain0, qlim, tw, flag_list)
-        if (signd) TK_LAUNCH_LAZY(true); else TK_LAUNCH_LAZY(false);
-#undef TK_LAUNCH_LAZY
-    } else { if (signd) TK_LAUNCH3(true, false, 64); else TK_LAUNCH3(false, false, 64); }
-#undef TK_LAUNCH3
+        if (j.signd) { if (o.lazy) TK_LAUNCH(true, false, 64, true, true); else TK_LAUNCH(true, false, 64, false, true); }
+        else { if (o.lazy) TK_LAUNCH(false, false, 64, true, true); else TK_LAUNCH(false, false, 64, false, true); }
+    } else if (o.lazy) { if (j.signd) TK_LAUNCH(true, false, 64, true); else TK_LAUNCH(false, false, 64, true); }
+    else { if (j.signd) TK_LAUNCH(true, false, 64); else TK_LAUNCH(false, false, 64); }
+#undef TK_LAUNCH
     return 0;
 }
 
@@ -2043,26 +2021,24 @@ __global__ __launch_bounds__(64) void heap_replay_pair_kernel(
     }
 }
 
-// cap * 16 <= 0xffffff (position entries) is the caller's to check where labels are distinct.  plain0 / qlim (+ flags): both
-// or none (signed tables only); flag_list (optional: the failing queries listed for a re-scan) has its count zeroed here,
-// on the stream, in front of the kernel.  only_flagged: replay only the queries with flags[q] != 0 (the tail behind a lane
-// replay: queries it flagged, re-scanned exactly meanwhile) — with the duplicate test; count_src / host_count: count_src[0]
-// is copied to the page-locked *host_count (the flagged count the host polls).
-int tk_launch_heap_replay_pair(const uint4 *dist, int64_t cap, int64_t nq, const uint8_t *mins, int64_t cap_min,
-                               const int *slot_prefix, const int *slot_n, const int64_t *slot_label_off, int S,
-                               const int64_t *labels, int64_t *heap_idx, int32_t *heap_val, int R, int signd,
-                               int slots_uniform, unsigned char *flags, int dedupe_all, hipStream_t s,
-                               const int *plain0, const int *qlim, int *flag_list, int only_flagged,
-                               const int *count_src, int *host_count)
+// tk_positions_fit(cap) (position entries) is the caller's to check where labels are distinct.  The check needs flags and
+// signed tables (otherwise none is made); its flag_list (the failing queries listed for a re-scan) has its count zeroed
+// here, on the stream, in front of the kernel.  only_flagged: the tail behind a lane replay — queries it flagged,
+// re-scanned exactly meanwhile; count_src / host_count: the flagged count the host polls.
+int tk_launch_heap_replay_pair(const TkReplayJob &j, unsigned char *flags, int dedupe_all, hipStream_t s,
+                               const TkPlainCheck &check, bool only_flagged, const int *count_src, int *host_count)
 {
-    if (nq == 0 || R == 0) return 0;
-    if (!plain0 || !qlim || !flags || !signd) plain0 = qlim = nullptr, flag_list = nullptr;
-    if (flag_list && hipMemsetAsync(flag_list, 0, 4, s) != hipSuccess) return -1;
-#define TK_LAUNCH_PAIR(S_, G_)                                                                                           \
-    hipLaunchKernelGGL((heap_replay_pair_kernel<S_, G_>), dim3((unsigned)nq), dim3(64), 0, s, dist, cap, mins, cap_min,  \
-                       slot_prefix, slot_n, slot_label_off, S, labels, heap_idx, heap_val, R, slots_uniform, flags,     \
-                       dedupe_all, nq, plain0, qlim, flag_list, only_flagged, count_src, host_count)
+    if (j.nq == 0 || j.R == 0) return 0;
+    TkPlainCheck c = check;
+    if (!c.plain0 || !c.qlim || !flags || !j.signd) c = TkPlainCheck();
+    if (c.flag_list && hipMemsetAsync(c.flag_list, 0, 4, s) != hipSuccess) return -1;
+#define TK_LAUNCH_PAIR(S_, G_)                                                                                         \
+    hipLaunchKernelGGL((heap_replay_pair_kernel<S_, G_>), dim3((unsigned)j.nq), dim3(64), 0, s, j.dist, j.cap, j.mins, \
+                       j.cap_min, j.slot_prefix, j.slot_n, j.slot_label_off, j.S, j.labels, j.heap_idx, j.heap_val,   \
+                       j.R, j.slots_uniform, flags, dedupe_all, j.nq, c.plain0, c.qlim, c.flag_list,                  \
+                       (int)only_flagged, count_src, host_count)
     // two nodes per lane up to 129 entries, four up to 257 (n_probes <= 24 at k = 10), eight up to 513 (n_probes <= 50)
+    const int R = j.R, signd = j.signd;
     if (R <= 129) { if (signd) TK_LAUNCH_PAIR(true, 1); else TK_LAUNCH_PAIR(false, 1); }
     else if (R <= 257) { if (signd) TK_LAUNCH_PAIR(true, 2); else TK_LAUNCH_PAIR(false, 2); }
     else if (R <= TK_PAIR_MAX_R) { if (signd) TK_LAUNCH_PAIR(true, 4); else TK_LAUNCH_PAIR(false, 4); }

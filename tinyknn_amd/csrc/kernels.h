@@ -138,19 +138,48 @@ void tk_launch_scan_units(const uint4 *codes, int M, const uint4 *tables, int64_
                           uint4 *dist, int64_t cap, uint8_t *mins, int64_t min_stride, int signd,
                           int order, int n_blocks, hipStream_t s, int form = 0);
 
-// Exact replay of the reference's sequential heap over precomputed distances.
-// One wave per query.  slot_n: true rows per slot; slot_label_off: offset into
-// `labels` or -1 (label = position).  heap_idx/heap_val: (nq, R) in/out.
-// slots_uniform: the slot arrays hold ONE row that every query uses.
-// only_flagged (nq bytes or NULL): replay only the flagged queries, each from a
-// fresh heap (the second pass behind tk_launch_heap_replay_lanes).
-void tk_launch_heap_replay(const uint4 *dist, int64_t cap, int64_t nq, const int *slot_prefix,
-                           const int *slot_n, const int64_t *slot_label_off, int S,
-                           const int64_t *labels, int64_t *heap_idx, int32_t *heap_val, int R,
-                           int signd, int slots_uniform, const unsigned char *only_flagged,
-                           hipStream_t s, const uint8_t *mins = nullptr, int64_t cap_min = 0);
-// mins (optional): the scan's per-block minima, (nq, cap_min) bytes, cap_min a multiple of 16:
-// slots that start at a multiple of 16 blocks are then walked 1024 blocks per step
+// ---- heap replays: the reference's sequential heap (_fast_pq_256.pyx:73-123) over precomputed distances ----
+// Position entries (value8 << 24 | flat position24) hold every code of a distance row of `chunks` chunks
+static inline bool tk_positions_fit(int64_t chunks) { return chunks * 16 <= 0xffffff; }
+
+// What every replay form reads and writes.  dist: (nq, cap) uint4; mins (or NULL): the scan's per-block minima, (nq,
+// cap_min) bytes, cap_min a multiple of 16.  Slot s of query q: flat chunks slot_prefix[q][s..s+1] of its row, slot_n[q][s]
+// true rows, labels[slot_label_off[q][s] + row] (-1: label = position); slots_uniform: ONE row of slots for every query.
+// heap_idx / heap_val: (nq, R) in/out.  signd: signed tables (int8 distances).
+struct TkReplayJob {
+    const uint4 *dist = nullptr;
+    int64_t cap = 0, nq = 0;
+    const uint8_t *mins = nullptr;
+    int64_t cap_min = 0;
+    const int *slot_prefix = nullptr, *slot_n = nullptr;
+    const int64_t *slot_label_off = nullptr;
+    int S = 0, slots_uniform = 0;
+    const int64_t *labels = nullptr;
+    int64_t *heap_idx = nullptr;
+    int32_t *heap_val = nullptr;
+    int R = 0, signd = 0;
+};
+
+// The per-query check of plain_scan.hip's lemma behind a plain scan (signed tables): the blocks from flat chunk plain0[q]
+// on carry clamp(plain sums); a query whose bound at its first such block is above qlim[q] is flagged, to be re-scanned
+// exactly and replayed again.  plain0 / qlim: nq ints each, or NULL.  flag_list (nq + 1 ints, or NULL): [0] = how many
+// queries the replay leaves to the kernels behind it (flagged before it, or by the check), then their numbers in any
+// order — tk_launch_scan_probes' `only`
+struct TkPlainCheck {
+    const int *plain0 = nullptr, *qlim = nullptr;
+    int *flag_list = nullptr;
+};
+
+// Per-query flags of a batch (nq bytes): 1 = the probe list names a list twice (rescore.hip), so `insert`'s duplicate
+// test can fire — or, from the lane replay with labels32, the lemma's check failed; 2 = the check failed (the other
+// replays).  run_if of the packed replay: the queries it takes (flags NULL: every query).
+#define TK_RUN_UNFLAGGED 0
+#define TK_RUN_WRAPPED 1
+#define TK_RUN_FLAGGED (-1)     // every query with a non-zero flag
+
+// The general form: one wave per query, any heap (heap_idx / heap_val as given).  With j.mins, slots that start at a
+// multiple of 16 blocks are walked 1024 blocks per step.
+void tk_launch_heap_replay(const TkReplayJob &j, hipStream_t s);
 
 // one query, a FRESH heap of R <= 64 entries, rows far longer than it: one workgroup — head of h blocks
 // (a multiple of 16) replayed with the heap in registers, the later blocks whose minimum is below the
@@ -168,12 +197,9 @@ struct TkTwins {
     int bm_words = 0;                 // tk_lanes_twin_bm_words(n_lists): dwords of the per-query list bitmap, 0 = none
 };
 
-// Lane-per-query form of the same replay: 64 queries per wave.  Preconditions
-// (checked by the caller): heaps start fresh (-1 / 127|255), no label can repeat
-// among a query's lists (so `insert`'s duplicate test cannot fire), R*256 B of LDS
-// <= 160 KiB, cap*16 < 2^24 codes per query.  Writes (nq, R) heaps.  Returns 0.
-// skip (nq bytes or NULL): queries to leave untouched.  mins: (nq, cap_min) per-block
-// minima written by the scan kernels, cap_min a multiple of 16.
+// Lane-per-query form: 64 queries per wave.  Preconditions (checked by the caller): heaps start fresh
+// (-1 / 127|255), no label can repeat among a query's lists (so `insert`'s duplicate test cannot fire),
+// R*256 B of LDS <= 160 KiB, tk_positions_fit(cap).  Writes (nq, R) heaps.  Needs j.mins.
 #define TK_LANES_MAX_R 574
 // with labels32 (labels may repeat: duplicate test on 32-bit label slots + a two-choice hash
 // set of the labels in the heap, 64 KiB) the LDS budget is (2R+2)*256 + 64 KiB + 16 KiB + the
@@ -182,46 +208,37 @@ struct TkTwins {
 int tk_lanes_dedupe_fits(int R, int S);     // ... and the slot table of S probed lists fits too
 int tk_lanes_twin_bm_words(int64_t n_lists);
 int tk_lanes_twin_fits(int R, int S, int64_t n_lists);   // the TWIN form: heap columns + slot table + probe list + list bitmap
-// plain0 / qlim (both nq ints, or NULL): the blocks from flat chunk plain0[q] on carry clamp(plain
-// sums) (plain_scan.hip); a query whose bound at its first such block is above qlim[q] gets
-// skip[q] = 1 written (skip must then be writable) and is to be re-scanned exactly and replayed again.
-int tk_launch_heap_replay_lanes(const uint4 *dist, int64_t cap, int64_t nq, const int *slot_prefix,
-                                const int *slot_n, const int64_t *slot_label_off, int S,
-                                const int64_t *labels, int64_t *heap_idx, int32_t *heap_val, int R,
-                                int signd, int slots_uniform, unsigned char *skip,
-                                const uint8_t *mins, int64_t cap_min, const int32_t *labels32,
-                                hipStream_t s, const int *plain0 = nullptr, const int *qlim = nullptr,
-                                int lazy = 0, unsigned long long *counters = nullptr,
-                                const TkTwins *twins = nullptr, int *flag_list = nullptr);
-// flag_list (nq + 1 ints, or NULL): [0] = how many queries this replay leaves to the kernels behind it (flagged in
-// `skip` before it, or by its own check), then their numbers in any order — tk_launch_scan_probes' `only`
-// lazy: blocks are fetched only where their minimum passes (rows far longer than the heap; distinct labels)
-// twins (labels32 == NULL): labels may repeat, every label's copies carry ONE value, and the duplicate test is
-// decided from the twin table (heap.hip, TWIN form); `skip` must flag the queries that probe a list twice
+struct TkLanesOpts {
+    unsigned char *skip = nullptr;          // (nq bytes) queries to leave untouched; the check flags its failures here
+    const int32_t *labels32 = nullptr;      // labels that may repeat, as int32: the duplicate test (32 queries per wave)
+    TkPlainCheck check;                     // applies only with `skip` and signed tables
+    int lazy = 0;                           // blocks fetched only where their minimum passes (rows far longer than R)
+    unsigned long long *counters = nullptr; // TK_OPT_REPLAY_COUNT
+    // (labels32 == NULL) labels may repeat, every label's copies carry ONE value, and the duplicate test is decided from
+    // the twin table (heap.hip, TWIN form); `skip` must flag the queries that probe a list twice
+    const TkTwins *twins = nullptr;
+};
+int tk_launch_heap_replay_lanes(const TkReplayJob &j, const TkLanesOpts &o, hipStream_t s);   // non-zero: no LDS attribute
 
-// Wave-per-query replay on packed 32-bit entries from FRESH heaps (R*4 B of LDS, or
-// R*12 with `dedupe`: int64 labels per slot + the reference's duplicate-label test,
-// for labels that can repeat).  flags/run_if: only queries with flags[q] == run_if
-// (flags may be NULL).  cap*16 < 2^24 (no dedupe) / R < 2^24.
 // Wave-per-query replay with the heap in registers, two / four / eight nodes per lane for heaps of up to 129 / 257 / 513
-// entries (heap.hip): R <= TK_PAIR_MAX_R, fresh heaps;
-// position entries where labels are distinct (cap * 16 <= 0xffffff), the reference's duplicate test on (value, label)
+// entries (heap.hip): R <= TK_PAIR_MAX_R, fresh heaps, j.mins;
+// position entries where labels are distinct (tk_positions_fit(cap)), the reference's duplicate test on (value, label)
 // entries for the queries with flags[q] != 0 or for every query (dedupe_all).  The kernel of one query per call.
-// plain0 / qlim / flag_list: the per-query check of plain_scan.hip's lemma, as tk_launch_heap_replay_lanes makes it.
+// check: as the lane replay makes it, in `flags`.  only_flagged: only the queries with flags[q] != 0, with the duplicate
+// test; count_src[0] is copied to the page-locked *host_count.  Non-zero: the list's count not zeroed, or R too large.
 #define TK_PAIR_MAX_R 513
-int tk_launch_heap_replay_pair(const uint4 *dist, int64_t cap, int64_t nq, const uint8_t *mins, int64_t cap_min,
-                               const int *slot_prefix, const int *slot_n, const int64_t *slot_label_off, int S,
-                               const int64_t *labels, int64_t *heap_idx, int32_t *heap_val, int R, int signd,
-                               int slots_uniform, unsigned char *flags, int dedupe_all, hipStream_t s,
-                               const int *plain0 = nullptr, const int *qlim = nullptr, int *flag_list = nullptr,
-                               int only_flagged = 0, const int *count_src = nullptr, int *host_count = nullptr);
-void tk_launch_heap_replay_packed(const uint4 *dist, int64_t cap, int64_t nq, const int *slot_prefix,
-                                  const int *slot_n, const int64_t *slot_label_off, int S,
-                                  const int64_t *labels, int64_t *heap_idx, int32_t *heap_val,
-                                  int R, int signd, int slots_uniform, const unsigned char *flags,
-                                  int run_if, int dedupe, hipStream_t s, const int *flag_list = nullptr,
-                                  int *host_count = nullptr);
-// run_if < 0: every query with a non-zero flag.  flag_list + host_count (page-locked): *host_count = flag_list[0]
+#define TK_PAIR_DEDUPE_ALL 1    // dedupe_all: every query takes the duplicate test (labels repeat in the index)
+#define TK_PAIR_LABELS24 2      // ... on value8 << 24 | label24 entries (every label of the index below 0xffffff)
+int tk_launch_heap_replay_pair(const TkReplayJob &j, unsigned char *flags, int dedupe_all, hipStream_t s,
+                               const TkPlainCheck &check = TkPlainCheck(), bool only_flagged = false,
+                               const int *count_src = nullptr, int *host_count = nullptr);
+
+// Wave-per-query replay on packed 32-bit entries from FRESH heaps (R*4 B of LDS, or R*12 with `dedupe`: int64 labels
+// per slot + the reference's duplicate-label test, for labels that can repeat).  flags / run_if: only the queries
+// run_if selects (TK_RUN_*; flags may be NULL).  tk_positions_fit(cap) (no dedupe) / R < 2^24.
+// flag_list + host_count (page-locked): *host_count = flag_list[0]
+void tk_launch_heap_replay_packed(const TkReplayJob &j, const unsigned char *flags, int run_if, bool dedupe,
+                                  hipStream_t s, const int *flag_list = nullptr, int *host_count = nullptr);
 
 void tk_launch_heap_fill(int64_t *heap_idx, int32_t *heap_val, int64_t count, int32_t v,
                          hipStream_t s);
