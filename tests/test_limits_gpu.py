@@ -67,6 +67,35 @@ def test_sharded_batch_larger_than_131072_is_refused(small):
     e.dev.close()
 
 
+def test_sharded_scan_rest_needs_the_slots_last_scan_to_be_scan_first(small):
+    """tk_index_shard_scan_rest_dev continues tk_index_shard_scan_first_dev of its slot and nothing else: with no
+    scan before it, or with another scan after the first phase, it is refused before it launches anything."""
+    import torch
+    from tinyknn_amd.multi_gpu import _HipShardEngine, shard_capacity, shard_lists
+    g, ivf = small
+    k, n_probes = 10, 5
+    owner = shard_lists(g["list_sizes"], 1)
+    e = _HipShardEngine(ivf, owner, 0, 1, 1)
+    assert e.plain_ok(k, n_probes, None)
+    qn = torch.from_numpy(np.ascontiguousarray(g["qn"], dtype=np.float32)).cuda()
+    qp = torch.from_numpy(np.ascontiguousarray(g["qpq"])).cuda()
+    nq = qn.shape[0]
+    capacity = shard_capacity(g["list_sizes"], owner, 1, nq, n_probes)
+    send = torch.zeros(capacity * 16, dtype=torch.uint8, device="cuda")
+    flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+    bound = torch.zeros(nq, dtype=torch.uint8, device="cuda")
+    with pytest.raises(AssertionError, match="scan_first_dev of this slot"):
+        e.scan_rest(0, qn, k, n_probes, None, capacity, send, bound)
+    e.scan_first(0, qn, qp, k, n_probes, None, capacity, send, flag, bound)
+    e.scan(0, qn, qp, k, n_probes, None, capacity, send, flag)
+    with pytest.raises(AssertionError, match="scan_first_dev of this slot"):
+        e.scan_rest(0, qn, k, n_probes, None, capacity, send, bound)
+    e.scan_first(0, qn, qp, k, n_probes, None, capacity, send, flag, bound)
+    e.scan_rest(0, qn, k, n_probes, None, capacity, send, bound)
+    torch.cuda.synchronize()
+    e.dev.close()
+
+
 def test_fast_mode_refuses_angular_beyond_128_dims():
     from tinyknn_amd import IVF, FastPQ, _lib
     rng = np.random.RandomState(0)

@@ -680,7 +680,7 @@ TkScanJob coarse_job(const tk_index *ix, const Work &w, const Plan &p)
     return j;
 }
 
-static TkScanJob list_job(const tk_index *ix, const Work &w, const Plan &p)
+TkScanJob list_job(const tk_index *ix, const Work &w, const Plan &p)
 {
     TkScanJob j;
     j.codes = ix->codes.as<uint4>();
@@ -698,7 +698,7 @@ static TkScanJob list_job(const tk_index *ix, const Work &w, const Plan &p)
     return j;
 }
 
-static TkScanJob plain_job(const tk_index *ix, const Work &w, const Plan &p)
+TkScanJob plain_job(const tk_index *ix, const Work &w, const Plan &p)
 {
     TkScanJob j = list_job(ix, w, p);
     j.unit_prefix = w.p_unit_prefix.as<int>();
@@ -720,10 +720,9 @@ static int head_rows(const tk_index *ix, const Plan &p)
     return (ix->ids_unique ? 2 : 4) * p.R;
 }
 // head pairs: the first ceil(head_rows / 16) chunks of the first probed list of a query in head mode
-static int head_chunks(const tk_index *ix, const Plan &p) { return (head_rows(ix, p) + 15) >> 4; }
-int head_chunks_of(const tk_index *ix, const Plan &p) { return head_chunks(ix, p); }
+int head_chunks(const tk_index *ix, const Plan &p) { return (head_rows(ix, p) + 15) >> 4; }
 
-static TkScanJob head_job(const tk_index *ix, const Work &w, const Plan &p)
+TkScanJob head_job(const tk_index *ix, const Work &w, const Plan &p)
 {
     TkScanJob j = list_job(ix, w, p);
     j.unit_prefix = w.h_unit_prefix.as<int>();
@@ -853,6 +852,25 @@ void coarse_slots(tk_index *ix, Work &w, const int64_t *probes, int64_t nq, cons
                          so.plain0, so.pair_count3);
 }
 
+TkPairSet exact_pairs(const Work &w)
+{
+    return TkPairSet{w.u_count.as<int>(), w.u_cursor.as<int>(), w.u_pair_off.as<int>(),
+                     w.u_unit_prefix.as<int>(), w.u_pair_q.as<int>(), w.u_pair_f0.as<int>()};
+}
+
+TkPairSet plain_pairs(const tk_index *ix, const Work &w, int64_t nq, const Plan &p)
+{
+    return TkPairSet{w.p_count.as<int>(), w.p_cursor.as<int>(), w.p_pair_off.as<int>(),
+                     w.p_unit_prefix.as<int>(), w.p_pair_q.as<int>(), w.p_pair_f0.as<int>(),
+                     w.p_unit_desc.as<int>(), plain_k(ix, nq, p)};
+}
+
+TkPairSet head_pairs(const Work &w)
+{
+    return TkPairSet{w.h_count.as<int>(), w.h_cursor.as<int>(), w.h_pair_off.as<int>(),
+                     w.h_unit_prefix.as<int>(), w.h_pair_q.as<int>(), w.h_pair_f0.as<int>()};
+}
+
 // the pair lists of a batch: one set for the exact list-major kernel, with `plain` a second one
 // (the slots behind slot_exact[q]) for the plain kernel
 static void unit_pairs(tk_index *ix, Work &w, int64_t nq, const Plan &p, bool plain, hipStream_t st)
@@ -866,15 +884,9 @@ static void unit_pairs(tk_index *ix, Work &w, int64_t nq, const Plan &p, bool pl
                              nq * p.S + 4 * ix->n_lists, st);
         return;
     }
-    TkPairSet ex{w.u_count.as<int>(), w.u_cursor.as<int>(), w.u_pair_off.as<int>(),
-                 w.u_unit_prefix.as<int>(), w.u_pair_q.as<int>(), w.u_pair_f0.as<int>()};
-    TkPairSet pl{w.p_count.as<int>(), w.p_cursor.as<int>(), w.p_pair_off.as<int>(),
-                 w.p_unit_prefix.as<int>(), w.p_pair_q.as<int>(), w.p_pair_f0.as<int>(),
-                 w.p_unit_desc.as<int>(), plain_k(ix, nq, p)};
-    TkPairSet hd{w.h_count.as<int>(), w.h_cursor.as<int>(), w.h_pair_off.as<int>(),
-                 w.h_unit_prefix.as<int>(), w.h_pair_q.as<int>(), w.h_pair_f0.as<int>()};
     tk_launch_unit_pairs2(nq, w.probes.as<int64_t>(), p.S, ix->n_lists, ix->list_chunk_off.as<int64_t>(),
-                          w.slot_prefix.as<int>(), w.slot_exact.as<int>(), ex, pl, hd, head_chunks(ix, p), st);
+                          w.slot_prefix.as<int>(), w.slot_exact.as<int>(), exact_pairs(w),
+                          plain_pairs(ix, w, nq, p), head_pairs(w), head_chunks(ix, p), st);
 }
 
 int stage_coarse_rest(tk_index *ix, Work &w, const float *q_dev, int64_t nq, const Plan &p,

@@ -89,6 +89,15 @@ struct DevBuf {
         }                                                                                      \
     } while (0)
 
+// what a list-sharded scan call left in its slot (api_shard.hip; every scan entry point sets it)
+enum class ShardState {
+    None,           // no scan yet, or the last one stopped on an error
+    Exact,         // exact rows in the send buffer
+    OnePhase,       // tk_index_shard_scan_plain_dev's rows: the home replay checks the lemma
+    HeadOwed,       // tk_index_shard_scan_head_dev ran: _scan_plain_dev(bound_dev) is owed
+    RestOwed,       // tk_index_shard_scan_first_dev ran: _scan_rest_dev is owed
+};
+
 // buffers of ONE batch in flight
 struct Work {
     DevBuf tables, shift, scale, cdist, cheap_idx, cheap_val, probes, slot_prefix, slot_chunk0,
@@ -110,11 +119,7 @@ struct Work {
     // list-sharded batch: what tk_index_shard_scan_dev left for the filtered exchange
     const int64_t *shard_probes = nullptr;
     int64_t shard_nq = 0, shard_capacity = 0;
-    // list-sharded batch whose tables were built by the queries' HOME ranks and all-gathered by the caller
-    // (tk_index_shard_coarse_home_dev / tk_index_shard_set_tables_dev): the gathered rows, in the caller's buffer
-    bool shard_first = false;       // tk_index_shard_scan_first_dev ran: _rest_dev is owed
-    bool shard_plain = false;       // tk_index_shard_scan_plain_dev filled the send buffer: the home replay checks the lemma
-    bool shard_head = false;        // tk_index_shard_scan_head_dev ran: _scan_plain_dev(bound_dev) is owed
+    ShardState shard_state = ShardState::None;     // what the slot's last list-sharded scan call left
     // pipelined mode (depth > 1): hand-offs between the caller's stream and a latency stream
     hipEvent_t tables_done = nullptr, coarse_scanned = nullptr, front_done = nullptr,
                scanned = nullptr, done = nullptr;
@@ -342,4 +347,12 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
                const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain = false,
                TkSecond q2 = TkSecond(), TkSecond out2 = TkSecond(), int *plain_flag = nullptr,
                const tk_allow *allow = nullptr);
-int head_chunks_of(const tk_index *ix, const Plan &p);    // chunks of a first probed list the exact kernel keeps (head mode)
+int head_chunks(const tk_index *ix, const Plan &p);    // chunks of a first probed list the exact kernel keeps (head mode)
+// the workspace's three pair sets: whole lists exact / plain tiles / heads
+TkPairSet exact_pairs(const Work &w);
+TkPairSet plain_pairs(const tk_index *ix, const Work &w, int64_t nq, const Plan &p);
+TkPairSet head_pairs(const Work &w);
+// the list scans' jobs over those sets, into the workspace's distance rows
+TkScanJob list_job(const tk_index *ix, const Work &w, const Plan &p);
+TkScanJob plain_job(const tk_index *ix, const Work &w, const Plan &p);
+TkScanJob head_job(const tk_index *ix, const Work &w, const Plan &p);

@@ -46,18 +46,47 @@ static int reserve_shard(tk_index *ix, Work &w, int64_t nq, int64_t qh, const Pl
     return TK_OK;
 }
 
-static int shard_args(tk_index *ix, int slot, int64_t nq, int64_t capacity, const Plan &p,
-                      int64_t &qh)
+// the slot's last scan (tk_index_shard_scan_dev or another form) was of this nq and capacity
+static bool scan_left(const Work &w, int64_t nq, int64_t capacity)
 {
+    return w.shard_probes && w.shard_nq == nq && w.shard_capacity == capacity;
+}
+
+// What every tk_index_shard_* call of a batch starts from
+struct ShardCall {
+    Plan p;
+    int64_t qh = 0;         // home queries per rank: ceil(nq / world)
+    Work *w = nullptr;      // the slot's workspace
+    hipStream_t st = nullptr;
+};
+
+// needs_scan: the call reads what tk_index_shard_scan_dev (or another scan form) left in this slot
+static int shard_call(tk_index *ix, int slot, int64_t nq, int k, int n_probes, int pass_1, int64_t capacity,
+                      void *stream, ShardCall &c, bool needs_scan = false)
+{
+    const Plan &p = c.p;
+    TRY(make_plan(ix, k, n_probes, pass_1, c.p));
     ARGCHECK(ix->sharded, "not a list-sharded index (tk_index_set_lists_shard)");
     ARGCHECK(slot >= 0 && slot < ix->depth, "slot must be < the pipeline depth");
     ARGCHECK(nq >= 1 && nq <= MAX_SHARD_BATCH, "1 <= nq <= 131072 per sharded batch");
     ARGCHECK(capacity >= 1 && capacity * ix->world < (1ll << 31), "capacity");
-    qh = (nq + ix->world - 1) / ix->world;
+    c.qh = (nq + ix->world - 1) / ix->world;
     ARGCHECK((double)nq * p.S / 4 * ix->max_list_chunks + (double)ix->total_chunks < 2.0e9,
              "too many scan units for one batch");
-    ARGCHECK((double)qh * p.cap * 17.0 < 16.0e9, "distance rows of the home queries exceed 16 GB");
+    ARGCHECK((double)c.qh * p.cap * 17.0 < 16.0e9, "distance rows of the home queries exceed 16 GB");
+    c.w = &ix->works[(size_t)slot];
+    c.st = (hipStream_t)stream;
+    ARGCHECK(!needs_scan || scan_left(*c.w, nq, capacity),
+             "tk_index_shard_scan_dev of this slot (same nq and capacity) comes first");
     return TK_OK;
+}
+
+// this rank's home queries [q0, q0 + nqh) of a batch of nq; returns nqh (0 where the batch ends before them)
+static int64_t home_range(const tk_index *ix, int64_t nq, int64_t qh, int64_t *q0)
+{
+    *q0 = (int64_t)ix->rank * qh;
+    const int64_t n = nq - *q0;
+    return n < 0 ? 0 : (n > qh ? qh : n);
 }
 
 static bool shard_plain_possible(const tk_index *ix, const Plan &p)
@@ -96,46 +125,157 @@ static int reserve_shard_plain(tk_index *ix, Work &w, int64_t nq, const Plan &p)
 // Coarse stage sharded by HOME rank: tables for all nq queries (every rank scores segments of
 // every query), coarse scan + replay + rescoring only for this rank's ceil(nq/world) home
 // queries; the caller all-gathers the probe lists and hands them to tk_index_shard_scan_dev.
-static int shard_coarse_impl(tk_index *ix, int slot, const float *q_dev, const void *q_pq_dev, int q_pq_is_f64,
-                             int64_t nq, int k, int n_probes, int pass_1, int64_t *probes_home_dev, void *stream)
-{
-    Plan p;
-    TRY(make_plan(ix, k, n_probes, pass_1, p));
-    int64_t qh = 0;
-    TRY(shard_args(ix, slot, nq, 1, p, qh));
-    ARGCHECK(probes_home_dev, "probes buffer");
-    Work &w = ix->works[(size_t)slot];
-    hipStream_t st = (hipStream_t)stream;
-    TRY(reserve_shard(ix, w, nq, qh, p));
-    Prof pf;
-    // (the limits C of all nq tables ride in the table launch's shadow where a plain form may follow)
-    const bool limits = shard_plain_possible(ix, p);
-    if (limits) TRY(reserve_shard_plain(ix, w, nq, p));
-    const int64_t q0 = (int64_t)ix->rank * qh;
-    int64_t nqh = nq - q0;
-    nqh = nqh < 0 ? 0 : (nqh > qh ? qh : nqh);
-    TRY(stage_tables(ix, w, q_pq_dev, q_pq_is_f64, nq, st, pf, limits));
-    // rows past nq: list 0 (never read by a consumer; defined for the all-gather)
-    HIPCHECK(hipMemsetAsync(probes_home_dev, 0, (size_t)qh * p.kc * 8, st));
-    if (nqh > 0) {
-        if (coarse_units(ix, nqh))     // identity pairs of the home range (stage_tables wrote those of all nq)
-            tk_launch_identity_pairs(nqh, (int)ix->center_chunks, w.c_pair_off.as<int>(),
-                                     w.c_unit_prefix.as<int>(), w.c_pair_q.as<int>(),
-                                     w.c_pair_f0.as<int>(), st);
-        launch_coarse_scan(ix, w, nqh, p, st, w.tables.as<uint4>() + q0 * ix->M);
-        TRY(coarse_replay_probes(ix, w, q_dev + q0 * ix->d, nqh, p, probes_home_dev, st, pf));
-    }
-    HIPCHECK(hipGetLastError());
-    return TK_OK;
-}
-
 extern "C" int tk_index_shard_coarse_dev(tk_index *ix, int slot, const float *q_dev,
                                          const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k,
                                          int n_probes, int pass_1, int64_t *probes_home_dev,
                                          void *stream)
 {
     IXLOCK(ix);
-    return shard_coarse_impl(ix, slot, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, probes_home_dev, stream);
+    ShardCall c;
+    TRY(shard_call(ix, slot, nq, k, n_probes, pass_1, 1, stream, c));
+    ARGCHECK(probes_home_dev, "probes buffer");
+    Work &w = *c.w;
+    const Plan &p = c.p;
+    TRY(reserve_shard(ix, w, nq, c.qh, p));
+    Prof pf;
+    // (the limits C of all nq tables ride in the table launch's shadow where a plain form may follow)
+    const bool limits = shard_plain_possible(ix, p);
+    if (limits) TRY(reserve_shard_plain(ix, w, nq, p));
+    int64_t q0 = 0;
+    const int64_t nqh = home_range(ix, nq, c.qh, &q0);
+    TRY(stage_tables(ix, w, q_pq_dev, q_pq_is_f64, nq, c.st, pf, limits));
+    // rows past nq: list 0 (never read by a consumer; defined for the all-gather)
+    HIPCHECK(hipMemsetAsync(probes_home_dev, 0, (size_t)c.qh * p.kc * 8, c.st));
+    if (nqh > 0) {
+        if (coarse_units(ix, nqh))     // identity pairs of the home range (stage_tables wrote those of all nq)
+            tk_launch_identity_pairs(nqh, (int)ix->center_chunks, w.c_pair_off.as<int>(),
+                                     w.c_unit_prefix.as<int>(), w.c_pair_q.as<int>(),
+                                     w.c_pair_f0.as<int>(), c.st);
+        launch_coarse_scan(ix, w, nqh, p, c.st, w.tables.as<uint4>() + q0 * ix->M);
+        TRY(coarse_replay_probes(ix, w, q_dev + q0 * ix->d, nqh, p, probes_home_dev, c.st, pf));
+    }
+    HIPCHECK(hipGetLastError());
+    return TK_OK;
+}
+
+// ---- the scan forms ----
+// Exact: tk_index_shard_scan_dev.  Head: tk_index_shard_scan_head_dev.  OnePhase / OnePhaseBehindHead:
+// tk_index_shard_scan_plain_dev without / with the head call's bounds.  First: tk_index_shard_scan_first_dev.
+// scan_prologue runs what they share before their own scans; they differ there only as form_steps says.
+enum class ShardForm { Exact, Head, OnePhase, OnePhaseBehindHead, First };
+enum class TableLimits { None, WithTables, AfterCoarse };    // the tables' limits C, where the coarse stage is replicated
+
+struct FormSteps {
+    bool plain;             // reserve_shard_plain
+    bool count_exact;       // the slot descriptors count this rank's pairs per list (u_count)
+    bool slots_plain;       // ... split at every query's slot_exact (one-phase forms)
+    TableLimits limits;
+};
+
+static FormSteps form_steps(ShardForm f)
+{
+    switch (f) {
+    case ShardForm::Exact: return {false, true, false, TableLimits::None};
+    // (Head and First count the first slots they score with kernels of their own)
+    case ShardForm::Head: return {true, false, false, TableLimits::WithTables};
+    case ShardForm::OnePhase: return {true, true, true, TableLimits::WithTables};
+    // (the head call left tables, limits, probe lists and positions)
+    case ShardForm::OnePhaseBehindHead: return {true, true, true, TableLimits::None};
+    // (the limits C of all nq tables in a launch of their own behind the replicated coarse stage;
+    //  tk_index_shard_coarse_dev computed them beside its tables)
+    case ShardForm::First: return {true, false, false, TableLimits::AfterCoarse};
+    }
+    return {};
+}
+
+// The reserves, the probe lists (gathered from the home ranks, derived by a replicated coarse stage, or those
+// of the head call) and the positions of the segments in the send buffer.  -> probes: the batch's probe lists.
+// A call that fails on the way leaves the slot owing nothing.
+static int scan_prologue(tk_index *ix, const ShardCall &c, ShardForm form, const float *q_dev,
+                         const void *q_pq_dev, int q_pq_is_f64, int64_t nq, const int64_t *probes_all_dev,
+                         int64_t capacity, int *flag_dev, const uint8_t *bound_dev, const int64_t *&probes)
+{
+    Work &w = *c.w;
+    const Plan &p = c.p;
+    const FormSteps f = form_steps(form);
+    w.shard_state = ShardState::None;
+    TRY(reserve_shard(ix, w, nq, c.qh, p));
+    if (f.plain) TRY(reserve_shard_plain(ix, w, nq, p));
+    TRY(w.smins.ensure((size_t)ix->world * capacity + 16));
+    TRY(w.usage.ensure((size_t)ix->world * 2 * 8));
+    const int *owner = ix->owner.as<int>();
+    int *pair_count = f.count_exact ? w.u_count.as<int>() : nullptr;
+    if (form == ShardForm::OnePhaseBehindHead) {
+        // queries whose bound after the head is above their table's limit leave the plain path (all
+        // their lists exact) — the rest is the one-phase scan, which now cannot fail its check at home
+        probes = w.shard_probes;
+        tk_launch_shard_mask_limits(bound_dev, nq, w.qlim.as<int>(), c.st);
+        coarse_slots(ix, w, probes, nq, p, pair_count, owner, ix->rank, c.st, f.slots_plain);
+        return TK_OK;
+    }
+    probes = probes_all_dev;
+    if (probes) {
+        // the tables of this slot (with their limits where a plain form may follow) were built by
+        // tk_index_shard_coarse_dev; the probe lists of all queries arrive gathered from their home ranks
+        coarse_slots(ix, w, probes, nq, p, pair_count, owner, ix->rank, c.st, f.slots_plain);
+    } else {
+        // replicated coarse stage: every rank derives every probe list itself
+        Prof pf;
+        TRY(stage_tables(ix, w, q_pq_dev, q_pq_is_f64, nq, c.st, pf, f.limits == TableLimits::WithTables));
+        launch_coarse_scan(ix, w, nq, p, c.st);
+        TRY(stage_coarse_rest(ix, w, q_dev, nq, p, pair_count, owner, ix->rank, c.st, pf, f.slots_plain));
+        probes = w.probes.as<int64_t>();
+        if (f.limits == TableLimits::AfterCoarse)
+            tk_launch_table_limits(tables_of(w), ix->M, ix->order, nq, w.qlim.as<int>(), c.st, ix->opt_plain_limit);
+    }
+    const int64_t n1 = nq * p.S + (int64_t)ix->world * c.qh * p.S + 1;
+    ARGCHECK(n1 < (1ll << 31), "too many (query, list) entries for one sharded batch");
+    TRY(w.pos_lens.ensure((size_t)n1 * 8));
+    TRY(w.pos_off.ensure((size_t)n1 * 8));
+    size_t tmp_bytes = 0;
+    ARGCHECK(tk_scan_exclusive64(nullptr, &tmp_bytes, w.pos_lens.as<long long>(),
+                                 w.pos_off.as<long long>(), n1, c.st) == 0,
+             "hipcub scan (size query) failed");
+    TRY(w.scan_tmp.ensure(tmp_bytes + 16));
+    if (tk_launch_shard_positions(probes, w.slot_prefix.as<int>(), p.S, nq, ix->n_lists, owner,
+                                  ix->rank, ix->world, c.qh, capacity, w.spos.as<int>(),
+                                  w.rpos.as<int>(), flag_dev, w.usage.as<long long>(),
+                                  w.pos_lens.as<long long>(), w.pos_off.as<long long>(),
+                                  w.scan_tmp.p, tmp_bytes, c.st))
+        return fail(TK_ERR_HIP, "hipcub scan failed");
+    return TK_OK;
+}
+
+// what a scan call leaves in its slot for the calls of the batch behind it
+static void scan_done(Work &w, const int64_t *probes, int64_t nq, int64_t capacity, ShardState state)
+{
+    w.shard_probes = probes;
+    w.shard_nq = nq;
+    w.shard_capacity = capacity;
+    w.shard_state = state;
+}
+
+// list_job / plain_job / head_job retargeted at the send buffer the way exact_to_send scores: this rank's code
+// storage, row stride 0, the minima in smins
+static TkScanJob to_send(TkScanJob j, const tk_index *ix, const Work &w, void *send_dev)
+{
+    j.list_chunk_off = ix->local_chunk_off.as<int64_t>();
+    j.dist = (uint4 *)send_dev;
+    j.cap = 0;
+    j.mins = w.smins.as<uint8_t>();
+    j.min_stride = 0;
+    return j;
+}
+
+// the exact kernel over the pair set `ex` (u_*): the owned segments are scored straight into the send buffer
+// (row stride 0, the record's offset is the segment's position); the minima are rebuilt by the receiver
+static void exact_to_send(const tk_index *ix, const ShardCall &c, int64_t nq, void *send_dev)
+{
+    const Work &w = *c.w;
+    tk_launch_scan_units(ix->codes.as<uint4>(), ix->M, tables_of(w), nq, c.p.S, ix->n_lists,
+                         ix->local_chunk_off.as<int64_t>(), w.u_pair_off.as<int>(),
+                         w.u_unit_prefix.as<int>(), w.u_pair_q.as<int>(), w.u_pair_f0.as<int>(),
+                         (uint4 *)send_dev, 0, w.smins.as<uint8_t>(), 0, 1, ix->order, 768, c.st);
 }
 
 extern "C" int tk_index_shard_scan_dev(tk_index *ix, int slot, const float *q_dev,
@@ -144,63 +284,23 @@ extern "C" int tk_index_shard_scan_dev(tk_index *ix, int slot, const float *q_de
                                        int64_t capacity, void *send_dev, int *flag_dev, void *stream)
 {
     IXLOCK(ix);
-    Plan p;
-    TRY(make_plan(ix, k, n_probes, pass_1, p));
-    int64_t qh = 0;
-    TRY(shard_args(ix, slot, nq, capacity, p, qh));
+    ShardCall c;
+    TRY(shard_call(ix, slot, nq, k, n_probes, pass_1, capacity, stream, c));
     ARGCHECK(send_dev && flag_dev, "send/flag buffers");
-    Work &w = ix->works[(size_t)slot];
-    hipStream_t st = (hipStream_t)stream;
-    TRY(reserve_shard(ix, w, nq, qh, p));
-    TRY(w.smins.ensure((size_t)ix->world * capacity + 16));
-    TRY(w.usage.ensure((size_t)ix->world * 2 * 8));
-    Prof pf;
+    Work &w = *c.w;
+    const Plan &p = c.p;
     const int *owner = ix->owner.as<int>();
-    const int64_t *probes = probes_all_dev;
-    if (probes) {
-        // the tables of this slot were built by tk_index_shard_coarse_dev; the probe lists of
-        // all queries arrive gathered from their home ranks
-        coarse_slots(ix, w, probes, nq, p, w.u_count.as<int>(), owner, ix->rank, st);
-    } else {
-        // replicated coarse stage: every rank derives every probe list itself
-        TRY(stage_tables(ix, w, q_pq_dev, q_pq_is_f64, nq, st, pf));
-        launch_coarse_scan(ix, w, nq, p, st);
-        TRY(stage_coarse_rest(ix, w, q_dev, nq, p, w.u_count.as<int>(), owner, ix->rank, st, pf));
-        probes = w.probes.as<int64_t>();
-    }
-    {
-        const int64_t n1 = nq * p.S + (int64_t)ix->world * qh * p.S + 1;
-        ARGCHECK(n1 < (1ll << 31), "too many (query, list) entries for one sharded batch");
-        TRY(w.pos_lens.ensure((size_t)n1 * 8));
-        TRY(w.pos_off.ensure((size_t)n1 * 8));
-        size_t tmp_bytes = 0;
-        ARGCHECK(tk_scan_exclusive64(nullptr, &tmp_bytes, w.pos_lens.as<long long>(),
-                                     w.pos_off.as<long long>(), n1, st) == 0,
-                 "hipcub scan (size query) failed");
-        TRY(w.scan_tmp.ensure(tmp_bytes + 16));
-        if (tk_launch_shard_positions(probes, w.slot_prefix.as<int>(), p.S, nq, ix->n_lists, owner,
-                                      ix->rank, ix->world, qh, capacity, w.spos.as<int>(),
-                                      w.rpos.as<int>(), flag_dev, w.usage.as<long long>(),
-                                      w.pos_lens.as<long long>(), w.pos_off.as<long long>(),
-                                      w.scan_tmp.p, tmp_bytes, st))
-            return fail(TK_ERR_HIP, "hipcub scan failed");
-    }
+    const int64_t *probes = nullptr;
+    TRY(scan_prologue(ix, c, ShardForm::Exact, q_dev, q_pq_dev, q_pq_is_f64, nq, probes_all_dev, capacity,
+                      flag_dev, nullptr, probes));
     tk_launch_pairs_scan(w.u_count.as<int>(), ix->local_chunk_off.as<int64_t>(), ix->n_lists,
                          w.u_pair_off.as<int>(), w.u_unit_prefix.as<int>(), w.u_cursor.as<int>(),
-                         w.u_pair_q.as<int>(), st);
+                         w.u_pair_q.as<int>(), c.st);
     tk_launch_shard_pairs_fill(probes, p.S, nq, ix->n_lists, owner, ix->rank,
                                w.spos.as<int>(), w.u_pair_off.as<int>(), w.u_cursor.as<int>(),
-                               w.u_pair_q.as<int>(), w.u_pair_f0.as<int>(), st);
-    // the owned segments are scored straight into the send buffer (row stride 0, the
-    // record's offset is the segment's position); the minima are rebuilt by the receiver
-    tk_launch_scan_units(ix->codes.as<uint4>(), ix->M, tables_of(w), nq, p.S, ix->n_lists,
-                         ix->local_chunk_off.as<int64_t>(), w.u_pair_off.as<int>(),
-                         w.u_unit_prefix.as<int>(), w.u_pair_q.as<int>(), w.u_pair_f0.as<int>(),
-                         (uint4 *)send_dev, 0, w.smins.as<uint8_t>(), 0, 1, ix->order, 768, st);
-    w.shard_probes = probes;
-    w.shard_nq = nq;
-    w.shard_capacity = capacity;
-    w.shard_plain = false;
+                               w.u_pair_q.as<int>(), w.u_pair_f0.as<int>(), c.st);
+    exact_to_send(ix, c, nq, send_dev);
+    scan_done(w, probes, nq, capacity, ShardState::Exact);
     HIPCHECK(hipGetLastError());
     return TK_OK;
 }
@@ -231,92 +331,39 @@ extern "C" int tk_index_shard_scan_head_dev(tk_index *ix, int slot, const float 
                                             uint8_t *bound_dev, void *stream)
 {
     IXLOCK(ix);
-    Plan p;
-    TRY(make_plan(ix, k, n_probes, pass_1, p));
-    int64_t qh = 0;
-    TRY(shard_args(ix, slot, nq, capacity, p, qh));
+    ShardCall c;
+    TRY(shard_call(ix, slot, nq, k, n_probes, pass_1, capacity, stream, c));
     ARGCHECK(send_dev && flag_dev && bound_dev, "send/flag/bound buffers");
-    Work &w = ix->works[(size_t)slot];
-    hipStream_t st = (hipStream_t)stream;
+    Work &w = *c.w;
+    const Plan &p = c.p;
     if (!shard_one_phase_possible(ix, p, capacity)) {
-        HIPCHECK(hipMemsetAsync(bound_dev, 0xff, (size_t)nq, st));
+        HIPCHECK(hipMemsetAsync(bound_dev, 0xff, (size_t)nq, c.st));
         TRY(tk_index_shard_scan_dev(ix, slot, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1,
                                     probes_all_dev, capacity, send_dev, flag_dev, stream));
-        w.shard_head = true;
+        w.shard_state = ShardState::HeadOwed;
         return TK_OK;
     }
-    TRY(reserve_shard(ix, w, nq, qh, p));
-    TRY(reserve_shard_plain(ix, w, nq, p));
-    TRY(w.smins.ensure((size_t)ix->world * capacity + 16));
-    TRY(w.usage.ensure((size_t)ix->world * 2 * 8));
-    Prof pf;
     const int *owner = ix->owner.as<int>();
-    const int64_t *probes = probes_all_dev;
-    if (probes) {
-        coarse_slots(ix, w, probes, nq, p, nullptr, owner, ix->rank, st);
-    } else {
-        TRY(stage_tables(ix, w, q_pq_dev, q_pq_is_f64, nq, st, pf, true));
-        launch_coarse_scan(ix, w, nq, p, st);
-        TRY(stage_coarse_rest(ix, w, q_dev, nq, p, nullptr, owner, ix->rank, st, pf));
-        probes = w.probes.as<int64_t>();
-    }
-    {
-        const int64_t n1 = nq * p.S + (int64_t)ix->world * qh * p.S + 1;
-        ARGCHECK(n1 < (1ll << 31), "too many (query, list) entries for one sharded batch");
-        TRY(w.pos_lens.ensure((size_t)n1 * 8));
-        TRY(w.pos_off.ensure((size_t)n1 * 8));
-        size_t tmp_bytes = 0;
-        ARGCHECK(tk_scan_exclusive64(nullptr, &tmp_bytes, w.pos_lens.as<long long>(),
-                                     w.pos_off.as<long long>(), n1, st) == 0,
-                 "hipcub scan (size query) failed");
-        TRY(w.scan_tmp.ensure(tmp_bytes + 16));
-        if (tk_launch_shard_positions(probes, w.slot_prefix.as<int>(), p.S, nq, ix->n_lists, owner,
-                                      ix->rank, ix->world, qh, capacity, w.spos.as<int>(),
-                                      w.rpos.as<int>(), flag_dev, w.usage.as<long long>(),
-                                      w.pos_lens.as<long long>(), w.pos_off.as<long long>(),
-                                      w.scan_tmp.p, tmp_bytes, st))
-            return fail(TK_ERR_HIP, "hipcub scan failed");
-    }
+    const int64_t *probes = nullptr;
+    TRY(scan_prologue(ix, c, ShardForm::Head, q_dev, q_pq_dev, q_pq_is_f64, nq, probes_all_dev, capacity,
+                      flag_dev, nullptr, probes));
     // heads of the first slots this rank owns: exact, straight into the send buffer
-    const int64_t *lco = ix->local_chunk_off.as<int64_t>();
-    const int hc = head_chunks_of(ix, p);
-    TkPairSet ex{w.u_count.as<int>(), w.u_cursor.as<int>(), w.u_pair_off.as<int>(),
-                 w.u_unit_prefix.as<int>(), w.u_pair_q.as<int>(), w.u_pair_f0.as<int>()};
-    TkPairSet pl{w.p_count.as<int>(), w.p_cursor.as<int>(), w.p_pair_off.as<int>(),
-                 w.p_unit_prefix.as<int>(), w.p_pair_q.as<int>(), w.p_pair_f0.as<int>(),
-                 w.p_unit_desc.as<int>(), plain_k(ix, nq, p)};
-    TkPairSet hd{w.h_count.as<int>(), w.h_cursor.as<int>(), w.h_pair_off.as<int>(),
-                 w.h_unit_prefix.as<int>(), w.h_pair_q.as<int>(), w.h_pair_f0.as<int>()};
-    tk_launch_shard_count_first(probes, p.S, nq, ix->n_lists, owner, ix->rank, w.h_count.as<int>(), st);
-    tk_launch_pairs_scan3(ex, pl, hd, lco, ix->n_lists, hc, st);      // (sets 0 and 1 are empty here)
+    const int hc = head_chunks(ix, p);
+    tk_launch_shard_count_first(probes, p.S, nq, ix->n_lists, owner, ix->rank, w.h_count.as<int>(), c.st);
+    tk_launch_pairs_scan3(exact_pairs(w), plain_pairs(ix, w, nq, p), head_pairs(w), ix->local_chunk_off.as<int64_t>(),
+                          ix->n_lists, hc, c.st);      // (sets 0 and 1 are empty here)
     tk_launch_shard_pairs_fill(probes, p.S, nq, ix->n_lists, owner, ix->rank, w.spos.as<int>(),
                                w.h_pair_off.as<int>(), w.h_cursor.as<int>(), w.h_pair_q.as<int>(),
-                               w.h_pair_f0.as<int>(), st, 0, 1);
-    TkScanJob hj, none;
+                               w.h_pair_f0.as<int>(), c.st, 0, 1);
+    const TkScanJob hj = to_send(head_job(ix, w, p), ix, w, send_dev);
+    TkScanJob none;
     memset(&none, 0, sizeof none);
-    hj.codes = ix->codes.as<uint4>();
-    hj.tables = tables_of(w);
-    hj.list_chunk_off = lco;
-    hj.n_lists = (int)ix->n_lists;
-    hj.unit_prefix = w.h_unit_prefix.as<int>();
-    hj.pair_off = w.h_pair_off.as<int>();
-    hj.pair_q = w.h_pair_q.as<int>();
-    hj.pair_f0 = w.h_pair_f0.as<int>();
-    hj.dist = (uint4 *)send_dev;
-    hj.cap = 0;
-    hj.mins = w.smins.as<uint8_t>();
-    hj.min_stride = 0;
-    hj.max_chunks = hc;
-    tk_launch_scan_units2(none, none, ix->M, ix->order, 512, st, &hj, 0);
+    tk_launch_scan_units2(none, none, ix->M, ix->order, 512, c.st, &hj, 0);
     // the bound after those heads, by value (ivf.py:137-152 over the list's first rows)
     tk_launch_shard_first_bound(probes, w.slot_prefix.as<int>(), w.slot_n.as<int>(), p.S, nq, ix->n_lists,
                                 owner, ix->rank, w.spos.as<int>(), (const uint4 *)send_dev,
-                                w.smins.as<uint8_t>(), p.R, bound_dev, st, hc);
-    w.shard_probes = probes;
-    w.shard_nq = nq;
-    w.shard_capacity = capacity;
-    w.shard_plain = false;
-    w.shard_head = true;
+                                w.smins.as<uint8_t>(), p.R, bound_dev, c.st, hc);
+    scan_done(w, probes, nq, capacity, ShardState::HeadOwed);
     HIPCHECK(hipGetLastError());
     return TK_OK;
 }
@@ -343,113 +390,42 @@ extern "C" int tk_index_shard_scan_plain_dev(tk_index *ix, int slot, const float
                                              const uint8_t *bound_dev, void *stream)
 {
     IXLOCK(ix);
-    Plan p;
-    TRY(make_plan(ix, k, n_probes, pass_1, p));
-    int64_t qh = 0;
-    TRY(shard_args(ix, slot, nq, capacity, p, qh));
+    ShardCall c;
+    TRY(shard_call(ix, slot, nq, k, n_probes, pass_1, capacity, stream, c));
     ARGCHECK(send_dev && flag_dev, "send/flag buffers");
-    const int64_t tail = (int64_t)ix->world * capacity - ix->max_list_chunks;      // (>= 0 where the form applies)
-    Work &w = ix->works[(size_t)slot];
+    Work &w = *c.w;
+    const Plan &p = c.p;
     if (!shard_one_phase_possible(ix, p, capacity)) {
         // (behind tk_index_shard_scan_head_dev, which then was tk_index_shard_scan_dev itself: nothing is owed)
-        if (bound_dev && w.shard_head) {
-            w.shard_head = false;
+        if (bound_dev && w.shard_state == ShardState::HeadOwed) {
+            w.shard_state = ShardState::Exact;
             return TK_OK;
         }
         return tk_index_shard_scan_dev(ix, slot, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1,
                                        probes_all_dev, capacity, send_dev, flag_dev, stream);
     }
-    hipStream_t st = (hipStream_t)stream;
     const bool behind_head = bound_dev != nullptr;
-    ARGCHECK(!behind_head || (w.shard_head && w.shard_probes && w.shard_nq == nq && w.shard_capacity == capacity),
+    ARGCHECK(!behind_head || (w.shard_state == ShardState::HeadOwed && scan_left(w, nq, capacity)),
              "bound_dev: tk_index_shard_scan_head_dev of this slot (same nq and capacity) comes first");
-    w.shard_head = false;
-    TRY(reserve_shard(ix, w, nq, qh, p));
-    TRY(reserve_shard_plain(ix, w, nq, p));
-    TRY(w.smins.ensure((size_t)ix->world * capacity + 16));
-    TRY(w.usage.ensure((size_t)ix->world * 2 * 8));
-    Prof pf;
-    const int *owner = ix->owner.as<int>();
-    const int64_t *probes = probes_all_dev;
-    if (behind_head) {
-        // the head call left tables, limits, probe lists and positions; queries whose bound after the head
-        // is above their table's limit leave the plain path (all their lists exact) — the rest is the
-        // one-phase scan, which now cannot fail its check at home
-        probes = w.shard_probes;
-        tk_launch_shard_mask_limits(bound_dev, nq, w.qlim.as<int>(), st);
-        coarse_slots(ix, w, probes, nq, p, w.u_count.as<int>(), owner, ix->rank, st, true);
-    } else if (probes) {
-        // tables and their limits: tk_index_shard_coarse_dev; the probe lists arrive gathered
-        coarse_slots(ix, w, probes, nq, p, w.u_count.as<int>(), owner, ix->rank, st, true);
-    } else {
-        TRY(stage_tables(ix, w, q_pq_dev, q_pq_is_f64, nq, st, pf, true));
-        launch_coarse_scan(ix, w, nq, p, st);
-        TRY(stage_coarse_rest(ix, w, q_dev, nq, p, w.u_count.as<int>(), owner, ix->rank, st, pf, true));
-        probes = w.probes.as<int64_t>();
-    }
-    if (!behind_head) {
-        const int64_t n1 = nq * p.S + (int64_t)ix->world * qh * p.S + 1;
-        ARGCHECK(n1 < (1ll << 31), "too many (query, list) entries for one sharded batch");
-        TRY(w.pos_lens.ensure((size_t)n1 * 8));
-        TRY(w.pos_off.ensure((size_t)n1 * 8));
-        size_t tmp_bytes = 0;
-        ARGCHECK(tk_scan_exclusive64(nullptr, &tmp_bytes, w.pos_lens.as<long long>(),
-                                     w.pos_off.as<long long>(), n1, st) == 0,
-                 "hipcub scan (size query) failed");
-        TRY(w.scan_tmp.ensure(tmp_bytes + 16));
-        if (tk_launch_shard_positions(probes, w.slot_prefix.as<int>(), p.S, nq, ix->n_lists, owner,
-                                      ix->rank, ix->world, qh, capacity, w.spos.as<int>(),
-                                      w.rpos.as<int>(), flag_dev, w.usage.as<long long>(),
-                                      w.pos_lens.as<long long>(), w.pos_off.as<long long>(),
-                                      w.scan_tmp.p, tmp_bytes, st))
-            return fail(TK_ERR_HIP, "hipcub scan failed");
-    }
+    const int64_t *probes = nullptr;
+    TRY(scan_prologue(ix, c, behind_head ? ShardForm::OnePhaseBehindHead : ShardForm::OnePhase, q_dev, q_pq_dev,
+                      q_pq_is_f64, nq, probes_all_dev, capacity, flag_dev, bound_dev, probes));
     // three pair sets over the lists this rank owns (whole lists exact / plain tiles / heads), the
     // records' row offsets = positions in the send buffer
-    const int64_t *lco = ix->local_chunk_off.as<int64_t>();
-    TkPairSet ex{w.u_count.as<int>(), w.u_cursor.as<int>(), w.u_pair_off.as<int>(),
-                 w.u_unit_prefix.as<int>(), w.u_pair_q.as<int>(), w.u_pair_f0.as<int>()};
-    TkPairSet pl{w.p_count.as<int>(), w.p_cursor.as<int>(), w.p_pair_off.as<int>(),
-                 w.p_unit_prefix.as<int>(), w.p_pair_q.as<int>(), w.p_pair_f0.as<int>(),
-                 w.p_unit_desc.as<int>(), plain_k(ix, nq, p)};
-    TkPairSet hd{w.h_count.as<int>(), w.h_cursor.as<int>(), w.h_pair_off.as<int>(),
-                 w.h_unit_prefix.as<int>(), w.h_pair_q.as<int>(), w.h_pair_f0.as<int>()};
-    const int hc = head_chunks_of(ix, p);
-    tk_launch_unit_pairs2(nq, probes, p.S, ix->n_lists, lco, w.slot_prefix.as<int>(), w.slot_exact.as<int>(),
-                          ex, pl, hd, hc, st, w.spos.as<int>(), owner, ix->rank, (int)tail);
-    TkScanJob lj;
-    lj.codes = ix->codes.as<uint4>();
-    lj.tables = tables_of(w);
-    lj.list_chunk_off = lco;
-    lj.n_lists = (int)ix->n_lists;
-    lj.unit_prefix = w.u_unit_prefix.as<int>();
-    lj.pair_off = w.u_pair_off.as<int>();
-    lj.pair_q = w.u_pair_q.as<int>();
-    lj.pair_f0 = w.u_pair_f0.as<int>();
-    lj.dist = (uint4 *)send_dev;
-    lj.cap = 0;
-    lj.mins = w.smins.as<uint8_t>();
-    lj.min_stride = 0;
-    TkScanJob pj = lj, hj = lj, none;
+    const int64_t tail = (int64_t)ix->world * capacity - ix->max_list_chunks;      // (>= 0 where the form applies)
+    tk_launch_unit_pairs2(nq, probes, p.S, ix->n_lists, ix->local_chunk_off.as<int64_t>(), w.slot_prefix.as<int>(),
+                          w.slot_exact.as<int>(), exact_pairs(w), plain_pairs(ix, w, nq, p), head_pairs(w),
+                          head_chunks(ix, p), c.st, w.spos.as<int>(), ix->owner.as<int>(), ix->rank, (int)tail);
+    const TkScanJob lj = to_send(list_job(ix, w, p), ix, w, send_dev);
+    const TkScanJob pj = to_send(plain_job(ix, w, p), ix, w, send_dev);
+    const TkScanJob hj = to_send(head_job(ix, w, p), ix, w, send_dev);
+    TkScanJob none;
     memset(&none, 0, sizeof none);
-    pj.unit_prefix = w.p_unit_prefix.as<int>();
-    pj.pair_off = w.p_pair_off.as<int>();
-    pj.pair_q = w.p_pair_q.as<int>();
-    pj.pair_f0 = w.p_pair_f0.as<int>();
-    pj.unit_desc4 = w.p_unit_desc.as<int>();
-    hj.unit_prefix = w.h_unit_prefix.as<int>();
-    hj.pair_off = w.h_pair_off.as<int>();
-    hj.pair_q = w.h_pair_q.as<int>();
-    hj.pair_f0 = w.h_pair_f0.as<int>();
-    hj.max_chunks = hc;
     // (plain first: the exact kernel then overwrites the head chunks of the lists in head mode)
-    if (tk_launch_scan_plain(pj, ix->M, ix->order, shard_plain_blocks(), st))
+    if (tk_launch_scan_plain(pj, ix->M, ix->order, shard_plain_blocks(), c.st))
         return fail(TK_ERR_HIP, "scan_plain_kernel: LDS attribute / unsupported M");
-    tk_launch_scan_units2(lj, none, ix->M, ix->order, 768, st, &hj, ix->opt_scan_form);
-    w.shard_probes = probes;
-    w.shard_nq = nq;
-    w.shard_capacity = capacity;
-    w.shard_plain = true;
+    tk_launch_scan_units2(lj, none, ix->M, ix->order, 768, c.st, &hj, ix->opt_scan_form);
+    scan_done(w, probes, nq, capacity, ShardState::OnePhase);
     HIPCHECK(hipGetLastError());
     return TK_OK;
 }
@@ -487,70 +463,30 @@ extern "C" int tk_index_shard_scan_first_dev(tk_index *ix, int slot, const float
                                              uint8_t *bound_dev, void *stream)
 {
     IXLOCK(ix);
-    Plan p;
-    TRY(make_plan(ix, k, n_probes, pass_1, p));
-    int64_t qh = 0;
-    TRY(shard_args(ix, slot, nq, capacity, p, qh));
+    ShardCall c;
+    TRY(shard_call(ix, slot, nq, k, n_probes, pass_1, capacity, stream, c));
     ARGCHECK(send_dev && flag_dev && bound_dev, "send/flag/bound buffers");
-    ARGCHECK(shard_plain_possible(ix, p), "tk_index_shard_plain says no: use tk_index_shard_scan_dev");
-    Work &w = ix->works[(size_t)slot];
-    hipStream_t st = (hipStream_t)stream;
-    TRY(reserve_shard(ix, w, nq, qh, p));
-    TRY(reserve_shard_plain(ix, w, nq, p));
-    TRY(w.smins.ensure((size_t)ix->world * capacity + 16));
-    TRY(w.usage.ensure((size_t)ix->world * 2 * 8));
-    Prof pf;
+    ARGCHECK(shard_plain_possible(ix, c.p), "tk_index_shard_plain says no: use tk_index_shard_scan_dev");
+    Work &w = *c.w;
+    const Plan &p = c.p;
     const int *owner = ix->owner.as<int>();
-    const int64_t *probes = probes_all_dev;
-    if (probes) {
-        coarse_slots(ix, w, probes, nq, p, nullptr, owner, ix->rank, st);
-    } else {
-        TRY(stage_tables(ix, w, q_pq_dev, q_pq_is_f64, nq, st, pf));
-        launch_coarse_scan(ix, w, nq, p, st);
-        TRY(stage_coarse_rest(ix, w, q_dev, nq, p, nullptr, owner, ix->rank, st, pf));
-        probes = w.probes.as<int64_t>();
-    }
-    // the limits C of all nq tables (tk_index_shard_coarse_dev computed them beside its tables)
-    if (!probes_all_dev)
-        tk_launch_table_limits(tables_of(w), ix->M, ix->order, nq, w.qlim.as<int>(), st, ix->opt_plain_limit);
-    {
-        const int64_t n1 = nq * p.S + (int64_t)ix->world * qh * p.S + 1;
-        ARGCHECK(n1 < (1ll << 31), "too many (query, list) entries for one sharded batch");
-        TRY(w.pos_lens.ensure((size_t)n1 * 8));
-        TRY(w.pos_off.ensure((size_t)n1 * 8));
-        size_t tmp_bytes = 0;
-        ARGCHECK(tk_scan_exclusive64(nullptr, &tmp_bytes, w.pos_lens.as<long long>(),
-                                     w.pos_off.as<long long>(), n1, st) == 0,
-                 "hipcub scan (size query) failed");
-        TRY(w.scan_tmp.ensure(tmp_bytes + 16));
-        if (tk_launch_shard_positions(probes, w.slot_prefix.as<int>(), p.S, nq, ix->n_lists, owner,
-                                      ix->rank, ix->world, qh, capacity, w.spos.as<int>(),
-                                      w.rpos.as<int>(), flag_dev, w.usage.as<long long>(),
-                                      w.pos_lens.as<long long>(), w.pos_off.as<long long>(),
-                                      w.scan_tmp.p, tmp_bytes, st))
-            return fail(TK_ERR_HIP, "hipcub scan failed");
-    }
+    const int64_t *probes = nullptr;
+    TRY(scan_prologue(ix, c, ShardForm::First, q_dev, q_pq_dev, q_pq_is_f64, nq, probes_all_dev, capacity,
+                      flag_dev, nullptr, probes));
     // first slots: exact, straight into the send buffer
-    tk_launch_shard_count_first(probes, p.S, nq, ix->n_lists, owner, ix->rank, w.u_count.as<int>(), st);
+    tk_launch_shard_count_first(probes, p.S, nq, ix->n_lists, owner, ix->rank, w.u_count.as<int>(), c.st);
     tk_launch_pairs_scan(w.u_count.as<int>(), ix->local_chunk_off.as<int64_t>(), ix->n_lists,
                          w.u_pair_off.as<int>(), w.u_unit_prefix.as<int>(), w.u_cursor.as<int>(),
-                         w.u_pair_q.as<int>(), st);
+                         w.u_pair_q.as<int>(), c.st);
     tk_launch_shard_pairs_fill(probes, p.S, nq, ix->n_lists, owner, ix->rank, w.spos.as<int>(),
                                w.u_pair_off.as<int>(), w.u_cursor.as<int>(), w.u_pair_q.as<int>(),
-                               w.u_pair_f0.as<int>(), st, 0, 1);
-    tk_launch_scan_units(ix->codes.as<uint4>(), ix->M, tables_of(w), nq, p.S, ix->n_lists,
-                         ix->local_chunk_off.as<int64_t>(), w.u_pair_off.as<int>(),
-                         w.u_unit_prefix.as<int>(), w.u_pair_q.as<int>(), w.u_pair_f0.as<int>(),
-                         (uint4 *)send_dev, 0, w.smins.as<uint8_t>(), 0, 1, ix->order, 768, st);
-    w.shard_probes = probes;
-    w.shard_nq = nq;
-    w.shard_capacity = capacity;
-    w.shard_plain = false;
-    w.shard_first = true;
+                               w.u_pair_f0.as<int>(), c.st, 0, 1);
+    exact_to_send(ix, c, nq, send_dev);
+    scan_done(w, probes, nq, capacity, ShardState::RestOwed);
     // B1 of the queries whose first list lies here (ivf.py:137-152 over that list alone, by value)
     tk_launch_shard_first_bound(probes, w.slot_prefix.as<int>(), w.slot_n.as<int>(), p.S, nq,
                                 ix->n_lists, owner, ix->rank, w.spos.as<int>(), (const uint4 *)send_dev,
-                                w.smins.as<uint8_t>(), p.R, bound_dev, st);
+                                w.smins.as<uint8_t>(), p.R, bound_dev, c.st);
     HIPCHECK(hipGetLastError());
     return TK_OK;
 }
@@ -560,17 +496,16 @@ extern "C" int tk_index_shard_scan_rest_dev(tk_index *ix, int slot, int64_t nq, 
                                             const uint8_t *bound_dev, void *stream)
 {
     IXLOCK(ix);
-    Plan p;
-    TRY(make_plan(ix, k, n_probes, pass_1, p));
-    int64_t qh = 0;
-    TRY(shard_args(ix, slot, nq, capacity, p, qh));
+    ShardCall c;
+    TRY(shard_call(ix, slot, nq, k, n_probes, pass_1, capacity, stream, c));
     ARGCHECK(send_dev && bound_dev, "send/bound buffers");
-    Work &w = ix->works[(size_t)slot];
-    ARGCHECK(w.shard_first && w.shard_probes && w.shard_nq == nq && w.shard_capacity == capacity,
+    Work &w = *c.w;
+    const Plan &p = c.p;
+    ARGCHECK(w.shard_state == ShardState::RestOwed && scan_left(w, nq, capacity),
              "tk_index_shard_scan_first_dev of this slot (same nq and capacity) comes first");
-    w.shard_first = false;
-    hipStream_t st = (hipStream_t)stream;
+    w.shard_state = ShardState::None;
     const int *owner = ix->owner.as<int>();
+    const int64_t *lco = ix->local_chunk_off.as<int64_t>();
     const int64_t *probes = w.shard_probes;
     // a segment that overflowed its region is scored by the plain kernel to the tail of the
     // buffer (the batch is repeated anyway): the longest list must fit there
@@ -578,43 +513,21 @@ extern "C" int tk_index_shard_scan_rest_dev(tk_index *ix, int slot, int64_t nq, 
     const int allow = tail >= 0 ? 1 : 0;
     tk_launch_shard_count_rest(probes, p.S, nq, ix->n_lists, owner, ix->rank, bound_dev,
                                w.qlim.as<int>(), allow, w.plain_q.as<uint8_t>(), w.u_count.as<int>(),
-                               w.p_count.as<int>(), st);
-    TkPairSet ex{w.u_count.as<int>(), w.u_cursor.as<int>(), w.u_pair_off.as<int>(),
-                 w.u_unit_prefix.as<int>(), w.u_pair_q.as<int>(), w.u_pair_f0.as<int>()};
-    TkPairSet pl{w.p_count.as<int>(), w.p_cursor.as<int>(), w.p_pair_off.as<int>(),
-                 w.p_unit_prefix.as<int>(), w.p_pair_q.as<int>(), w.p_pair_f0.as<int>(),
-                 w.p_unit_desc.as<int>(), plain_k(ix, nq, p)};
-    TkPairSet hd{w.h_count.as<int>(), w.h_cursor.as<int>(), w.h_pair_off.as<int>(),
-                 w.h_unit_prefix.as<int>(), w.h_pair_q.as<int>(), w.h_pair_f0.as<int>()};   // (stays empty)
-    tk_launch_pairs_scan3(ex, pl, hd, ix->local_chunk_off.as<int64_t>(), ix->n_lists, 0, st);
-    tk_launch_plain_desc(pl, ix->local_chunk_off.as<int64_t>(), ix->n_lists, st);
+                               w.p_count.as<int>(), c.st);
+    const TkPairSet pl = plain_pairs(ix, w, nq, p);
+    tk_launch_pairs_scan3(exact_pairs(w), pl, head_pairs(w), lco, ix->n_lists, 0, c.st);   // (the head set stays empty)
+    tk_launch_plain_desc(pl, lco, ix->n_lists, c.st);
     tk_launch_shard_pairs_fill(probes, p.S, nq, ix->n_lists, owner, ix->rank, w.spos.as<int>(),
                                w.u_pair_off.as<int>(), w.u_cursor.as<int>(), w.u_pair_q.as<int>(),
-                               w.u_pair_f0.as<int>(), st, 1, p.S, w.plain_q.as<uint8_t>(), 0);
+                               w.u_pair_f0.as<int>(), c.st, 1, p.S, w.plain_q.as<uint8_t>(), 0);
     tk_launch_shard_pairs_fill(probes, p.S, nq, ix->n_lists, owner, ix->rank, w.spos.as<int>(),
                                w.p_pair_off.as<int>(), w.p_cursor.as<int>(), w.p_pair_q.as<int>(),
-                               w.p_pair_f0.as<int>(), st, 1, p.S, w.plain_q.as<uint8_t>(), 1,
+                               w.p_pair_f0.as<int>(), c.st, 1, p.S, w.plain_q.as<uint8_t>(), 1,
                                (int)(tail > 0 ? tail : 0));
-    TkScanJob pj;
-    pj.codes = ix->codes.as<uint4>();
-    pj.tables = tables_of(w);
-    pj.list_chunk_off = ix->local_chunk_off.as<int64_t>();
-    pj.n_lists = (int)ix->n_lists;
-    pj.unit_prefix = w.p_unit_prefix.as<int>();
-    pj.pair_off = w.p_pair_off.as<int>();
-    pj.pair_q = w.p_pair_q.as<int>();
-    pj.pair_f0 = w.p_pair_f0.as<int>();
-    pj.unit_desc4 = w.p_unit_desc.as<int>();
-    pj.dist = (uint4 *)send_dev;
-    pj.cap = 0;
-    pj.mins = w.smins.as<uint8_t>();
-    pj.min_stride = 0;
-    if (tk_launch_scan_plain(pj, ix->M, ix->order, shard_plain_blocks(), st))
+    if (tk_launch_scan_plain(to_send(plain_job(ix, w, p), ix, w, send_dev), ix->M, ix->order, shard_plain_blocks(), c.st))
         return fail(TK_ERR_HIP, "scan_plain_kernel: LDS attribute / unsupported M");
-    tk_launch_scan_units(ix->codes.as<uint4>(), ix->M, tables_of(w), nq, p.S, ix->n_lists,
-                         ix->local_chunk_off.as<int64_t>(), w.u_pair_off.as<int>(),
-                         w.u_unit_prefix.as<int>(), w.u_pair_q.as<int>(), w.u_pair_f0.as<int>(),
-                         (uint4 *)send_dev, 0, w.smins.as<uint8_t>(), 0, 1, ix->order, 768, st);
+    exact_to_send(ix, c, nq, send_dev);
+    w.shard_state = ShardState::Exact;
     HIPCHECK(hipGetLastError());
     return TK_OK;
 }
@@ -629,7 +542,7 @@ extern "C" int tk_index_shard_plain_stats(tk_index *ix, int slot, int64_t *out4)
     ARGCHECK(slot >= 0 && slot < ix->depth, "slot must be < the pipeline depth");
     Work &w = ix->works[(size_t)slot];
     for (int i = 0; i < 4; i++) out4[i] = 0;
-    if (!w.p_pair_off.p || !w.plain_q.p || !w.shard_probes || w.shard_first) return TK_OK;
+    if (!w.p_pair_off.p || !w.plain_q.p || !w.shard_probes || w.shard_state == ShardState::RestOwed) return TK_OK;
     HIPCHECK(hipDeviceSynchronize());
     const int64_t L = ix->n_lists;
     int v[3] = {0, 0, 0};
@@ -675,66 +588,18 @@ extern "C" int tk_index_shard_usage(tk_index *ix, int slot, int64_t *max_stream_
 // [all-to-all of the counts and of the records] -> finish_filtered.  `scan_dev` is the buffer
 // tk_index_shard_scan_dev of the same slot filled (it stays on the rank), with the same nq,
 // k, n_probes, pass_1 and capacity; the probe lists handed to that call must still be alive.
-static int filtered_args(tk_index *ix, Work &w, int64_t nq, int64_t capacity)
-{
-    ARGCHECK(w.shard_probes && w.shard_nq == nq && w.shard_capacity == capacity,
-             "tk_index_shard_scan_dev of this slot (same nq and capacity) comes first");
-    return TK_OK;
-}
-
 extern "C" int tk_index_shard_bound_dev(tk_index *ix, int slot, int64_t nq, int k, int n_probes,
                                         int pass_1, int64_t capacity, const void *scan_dev,
                                         uint8_t *bound_dev, void *stream)
 {
     IXLOCK(ix);
-    Plan p;
-    TRY(make_plan(ix, k, n_probes, pass_1, p));
-    int64_t qh = 0;
-    TRY(shard_args(ix, slot, nq, capacity, p, qh));
+    ShardCall c;
+    TRY(shard_call(ix, slot, nq, k, n_probes, pass_1, capacity, stream, c, true));
     ARGCHECK(scan_dev && bound_dev, "scan/bound buffers");
-    Work &w = ix->works[(size_t)slot];
-    TRY(filtered_args(ix, w, nq, capacity));
-    tk_launch_shard_first_bound(w.shard_probes, w.slot_prefix.as<int>(), w.slot_n.as<int>(), p.S, nq,
+    Work &w = *c.w;
+    tk_launch_shard_first_bound(w.shard_probes, w.slot_prefix.as<int>(), w.slot_n.as<int>(), c.p.S, nq,
                                 ix->n_lists, ix->owner.as<int>(), ix->rank, w.spos.as<int>(),
-                                (const uint4 *)scan_dev, w.smins.as<uint8_t>(), p.R, bound_dev,
-                                (hipStream_t)stream);
-    HIPCHECK(hipGetLastError());
-    return TK_OK;
-}
-
-static int shard_filter_impl(tk_index *ix, int slot, int64_t nq, int k, int n_probes,
-                             int pass_1, int64_t capacity, const void *scan_dev,
-                             const uint8_t *bound_dev, int32_t *counts_dev,
-                             int32_t *records_dev, int64_t region, int *flag_dev, int64_t *acc_dev,
-                             void *stream)
-{
-    Plan p;
-    TRY(make_plan(ix, k, n_probes, pass_1, p));
-    int64_t qh = 0;
-    TRY(shard_args(ix, slot, nq, capacity, p, qh));
-    ARGCHECK(scan_dev && bound_dev && counts_dev && records_dev, "scan/bound/counts/records buffers");
-    Work &w = ix->works[(size_t)slot];
-    TRY(filtered_args(ix, w, nq, capacity));
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t np1 = nq * p.S + 1;
-    ARGCHECK(np1 < (1ll << 31), "too many (query, list) pairs");
-    TRY(w.pair_cnt.ensure((size_t)np1 * 4));
-    TRY(w.pair_off.ensure((size_t)np1 * 4));
-    size_t tmp_bytes = 0;
-    ARGCHECK(tk_scan_exclusive(nullptr, &tmp_bytes, w.pair_cnt.as<int>(), w.pair_off.as<int>(), np1,
-                               st) == 0, "hipcub scan (size query) failed");
-    TRY(w.scan_tmp.ensure(tmp_bytes + 16));
-    TRY(w.tally.ensure((size_t)ix->world * 256 * 4));
-    HIPCHECK(hipMemsetAsync(w.tally.p, 0, (size_t)ix->world * 256 * 4, st));
-    HIPCHECK(hipMemsetAsync(counts_dev, 0, (size_t)ix->world * 3 * 4, st));
-    HIPCHECK(hipMemsetAsync(w.pair_cnt.as<int>() + (np1 - 1), 0, 4, st));
-    if (tk_launch_shard_filter(w.shard_probes, w.slot_prefix.as<int>(), p.S, nq, ix->n_lists,
-                               ix->owner.as<int>(), ix->rank, ix->world, qh, p.cap,
-                               w.spos.as<int>(), (const uint4 *)scan_dev, w.smins.as<uint8_t>(),
-                               bound_dev, w.pair_cnt.as<int>(), w.pair_off.as<int>(), w.scan_tmp.p,
-                               tmp_bytes, w.tally.as<int>(), counts_dev, records_dev, st, (int)region,
-                               flag_dev, (long long *)acc_dev))
-        return fail(TK_ERR_HIP, "hipcub scan failed");
+                                (const uint4 *)scan_dev, w.smins.as<uint8_t>(), c.p.R, bound_dev, c.st);
     HIPCHECK(hipGetLastError());
     return TK_OK;
 }
@@ -758,39 +623,34 @@ extern "C" int tk_index_shard_filter_dev(tk_index *ix, int slot, int64_t nq, int
     ARGCHECK(ix && ix->sharded, "not a list-sharded index");
     ARGCHECK(region_records == 0 || (region_records >= 1 && region_records * ix->world < (1ll << 31) && flag_dev),
              "region_records (x world must stay below 2^31) / flag buffer");
-    if (region_records == 0)
-        return shard_filter_impl(ix, slot, nq, k, n_probes, pass_1, capacity, scan_dev, bound_dev, counts_dev,
-                                 records_dev, 0, nullptr, nullptr, stream);
-    return shard_filter_impl(ix, slot, nq, k, n_probes, pass_1, capacity, scan_dev, bound_dev, counts_dev,
-                             records_dev, region_records, flag_dev, acc_dev, stream);
-}
-
-static int shard_finish_filtered_impl(tk_index *ix, int slot, const float *q_dev,
-                                      int64_t nq, int k, int n_probes, int pass_1,
-                                      const int32_t *records_dev, int64_t n_records,
-                                      const int32_t *counts_recv_dev, int64_t region,
-                                      int64_t *out_ids_home_dev, int *flag_dev, void *stream)
-{
-    Plan p;
-    TRY(make_plan(ix, k, n_probes, pass_1, p));
-    int64_t qh = 0;
-    TRY(shard_args(ix, slot, nq, 1, p, qh));
-    ARGCHECK(out_ids_home_dev && flag_dev && n_records >= 0 && (records_dev || n_records == 0),
-             "records/out/flag buffers");
-    Work &w = ix->works[(size_t)slot];
-    ARGCHECK(w.shard_probes && w.shard_nq == nq, "tk_index_shard_scan_dev of this slot comes first");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t q0 = (int64_t)ix->rank * qh;
-    int64_t nqh = nq - q0;
-    nqh = nqh < 0 ? 0 : (nqh > qh ? qh : nqh);
-    HIPCHECK(hipMemsetAsync(out_ids_home_dev, 0xff, (size_t)qh * k * 8, st));   // -1 rows
-    if (nqh > 0) {
-        tk_launch_shard_expand(records_dev, n_records, w.slot_prefix.as<int>() + q0 * (p.S + 1), p.S,
-                               nqh, w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min,
-                               flag_dev, st, counts_recv_dev, (int)region);
-        Prof pf;
-        TRY(stage_back(ix, w, q_dev + q0 * ix->d, q0, nqh, k, p, out_ids_home_dev, st, pf));
+    if (region_records == 0) {      // (the compact form neither flags nor accumulates)
+        flag_dev = nullptr;
+        acc_dev = nullptr;
     }
+    ShardCall c;
+    TRY(shard_call(ix, slot, nq, k, n_probes, pass_1, capacity, stream, c, true));
+    ARGCHECK(scan_dev && bound_dev && counts_dev && records_dev, "scan/bound/counts/records buffers");
+    Work &w = *c.w;
+    const Plan &p = c.p;
+    const int64_t np1 = nq * p.S + 1;
+    ARGCHECK(np1 < (1ll << 31), "too many (query, list) pairs");
+    TRY(w.pair_cnt.ensure((size_t)np1 * 4));
+    TRY(w.pair_off.ensure((size_t)np1 * 4));
+    size_t tmp_bytes = 0;
+    ARGCHECK(tk_scan_exclusive(nullptr, &tmp_bytes, w.pair_cnt.as<int>(), w.pair_off.as<int>(), np1,
+                               c.st) == 0, "hipcub scan (size query) failed");
+    TRY(w.scan_tmp.ensure(tmp_bytes + 16));
+    TRY(w.tally.ensure((size_t)ix->world * 256 * 4));
+    HIPCHECK(hipMemsetAsync(w.tally.p, 0, (size_t)ix->world * 256 * 4, c.st));
+    HIPCHECK(hipMemsetAsync(counts_dev, 0, (size_t)ix->world * 3 * 4, c.st));
+    HIPCHECK(hipMemsetAsync(w.pair_cnt.as<int>() + (np1 - 1), 0, 4, c.st));
+    if (tk_launch_shard_filter(w.shard_probes, w.slot_prefix.as<int>(), p.S, nq, ix->n_lists,
+                               ix->owner.as<int>(), ix->rank, ix->world, c.qh, p.cap,
+                               w.spos.as<int>(), (const uint4 *)scan_dev, w.smins.as<uint8_t>(),
+                               bound_dev, w.pair_cnt.as<int>(), w.pair_off.as<int>(), w.scan_tmp.p,
+                               tmp_bytes, w.tally.as<int>(), counts_dev, records_dev, c.st, (int)region_records,
+                               flag_dev, (long long *)acc_dev))
+        return fail(TK_ERR_HIP, "hipcub scan failed");
     HIPCHECK(hipGetLastError());
     return TK_OK;
 }
@@ -808,13 +668,31 @@ extern "C" int tk_index_shard_finish_filtered_dev(tk_index *ix, int slot, const 
 {
     IXLOCK(ix);
     ARGCHECK(ix && ix->sharded, "not a list-sharded index");
-    if (!counts_recv_dev)
-        return shard_finish_filtered_impl(ix, slot, q_dev, nq, k, n_probes, pass_1, records_dev, n_records,
-                                          nullptr, 0, out_ids_home_dev, flag_dev, stream);
-    ARGCHECK(region_records >= 1 && region_records * ix->world < (1ll << 31), "counts / region_records");
-    return shard_finish_filtered_impl(ix, slot, q_dev, nq, k, n_probes, pass_1, records_dev,
-                                      region_records * ix->world, counts_recv_dev, region_records,
-                                      out_ids_home_dev, flag_dev, stream);
+    int64_t region = 0;
+    if (counts_recv_dev) {
+        ARGCHECK(region_records >= 1 && region_records * ix->world < (1ll << 31), "counts / region_records");
+        region = region_records;
+        n_records = region_records * ix->world;
+    }
+    ShardCall c;
+    TRY(shard_call(ix, slot, nq, k, n_probes, pass_1, 1, stream, c));
+    ARGCHECK(out_ids_home_dev && flag_dev && n_records >= 0 && (records_dev || n_records == 0),
+             "records/out/flag buffers");
+    Work &w = *c.w;
+    const Plan &p = c.p;
+    ARGCHECK(w.shard_probes && w.shard_nq == nq, "tk_index_shard_scan_dev of this slot comes first");
+    int64_t q0 = 0;
+    const int64_t nqh = home_range(ix, nq, c.qh, &q0);
+    HIPCHECK(hipMemsetAsync(out_ids_home_dev, 0xff, (size_t)c.qh * k * 8, c.st));   // -1 rows
+    if (nqh > 0) {
+        tk_launch_shard_expand(records_dev, n_records, w.slot_prefix.as<int>() + q0 * (p.S + 1), p.S,
+                               nqh, w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min,
+                               flag_dev, c.st, counts_recv_dev, (int)region);
+        Prof pf;
+        TRY(stage_back(ix, w, q_dev + q0 * ix->d, q0, nqh, k, p, out_ids_home_dev, c.st, pf));
+    }
+    HIPCHECK(hipGetLastError());
+    return TK_OK;
 }
 
 extern "C" int tk_index_shard_finish_dev(tk_index *ix, int slot, const float *q_dev, int64_t nq,
@@ -823,26 +701,24 @@ extern "C" int tk_index_shard_finish_dev(tk_index *ix, int slot, const float *q_
                                          int *flag_dev, void *stream)
 {
     IXLOCK(ix);
-    Plan p;
-    TRY(make_plan(ix, k, n_probes, pass_1, p));
-    int64_t qh = 0;
-    TRY(shard_args(ix, slot, nq, capacity, p, qh));
+    ShardCall c;
+    TRY(shard_call(ix, slot, nq, k, n_probes, pass_1, capacity, stream, c));
     ARGCHECK(recv_dev && out_ids_home_dev, "recv/out buffers");
-    Work &w = ix->works[(size_t)slot];
-    ARGCHECK(!w.shard_plain || flag_dev, "the one-phase plain scan needs the batch's flag word at the finish");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t q0 = (int64_t)ix->rank * qh;
-    int64_t nqh = nq - q0;
-    nqh = nqh < 0 ? 0 : (nqh > qh ? qh : nqh);
-    HIPCHECK(hipMemsetAsync(out_ids_home_dev, 0xff, (size_t)qh * k * 8, st));   // -1 rows
+    Work &w = *c.w;
+    const Plan &p = c.p;
+    const bool one_phase = w.shard_state == ShardState::OnePhase;
+    ARGCHECK(!one_phase || flag_dev, "the one-phase plain scan needs the batch's flag word at the finish");
+    int64_t q0 = 0;
+    const int64_t nqh = home_range(ix, nq, c.qh, &q0);
+    HIPCHECK(hipMemsetAsync(out_ids_home_dev, 0xff, (size_t)c.qh * k * 8, c.st));   // -1 rows
     if (nqh > 0) {
         tk_launch_shard_unpack((const uint4 *)recv_dev, w.rpos.as<int>(),
                                w.slot_prefix.as<int>() + q0 * (p.S + 1), p.S, nqh,
-                               w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, 1, st);
+                               w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, 1, c.st);
         Prof pf;
         // (one-phase plain scan: the replay checks the lemma per home query and flags the batch)
-        TRY(stage_back(ix, w, q_dev + q0 * ix->d, q0, nqh, k, p, out_ids_home_dev, st, pf, w.shard_plain,
-                       TkSecond(), TkSecond(), w.shard_plain ? flag_dev : nullptr));
+        TRY(stage_back(ix, w, q_dev + q0 * ix->d, q0, nqh, k, p, out_ids_home_dev, c.st, pf, one_phase,
+                       TkSecond(), TkSecond(), one_phase ? flag_dev : nullptr));
     }
 
     HIPCHECK(hipGetLastError());

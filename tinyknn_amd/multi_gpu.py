@@ -143,6 +143,23 @@ def shard_positions(probes, chunks, owner, world, capacity):
     return src, pos
 
 
+def _stream():
+    """The current torch stream's handle, as the C ABI takes it."""
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _ptr(t):
+    """Device address of tensor `t`, or None."""
+    return None if t is None else t.data_ptr()
+
+
+def _f64(t):
+    """Is tensor `t` float64 (the C ABI's q_pq_is_f64)?"""
+    import torch
+    return t.dtype == torch.float64
+
+
 class _HipShardEngine:
     """scan / finish on the MI355X (torch tensors carry the device buffers)."""
 
@@ -160,109 +177,74 @@ class _HipShardEngine:
         self.device = "cuda"
 
     def coarse(self, slot, qn, qp, k, n_probes, pass_1, probes_home):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
-        self.dev.shard_coarse_dev(slot, qn.data_ptr(), qp.data_ptr(), qp.dtype == torch.float64,
-                                  qn.shape[0], k, n_probes, pass_1, probes_home.data_ptr(), stream=st)
-
-    @property
-    def table_bytes(self):
-        return self.dev.M * 16
+        self.dev.shard_coarse_dev(slot, qn.data_ptr(), qp.data_ptr(), _f64(qp), qn.shape[0], k, n_probes, pass_1,
+                                  probes_home.data_ptr(), stream=_stream())
 
     def scan(self, slot, qn, qp, k, n_probes, pass_1, capacity, send, flag, probes_all=None):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
-        self.dev.shard_scan_dev(slot, qn.data_ptr(), qp.data_ptr(), qp.dtype == torch.float64,
-                                qn.shape[0], k, n_probes, pass_1, capacity, send.data_ptr(),
-                                flag.data_ptr(), stream=st,
-                                probes_all_ptr=None if probes_all is None else probes_all.data_ptr())
+        self.dev.shard_scan_dev(slot, qn.data_ptr(), qp.data_ptr(), _f64(qp), qn.shape[0], k, n_probes, pass_1,
+                                capacity, send.data_ptr(), flag.data_ptr(), stream=_stream(),
+                                probes_all_ptr=_ptr(probes_all))
 
     # the scan in two phases, the second on the matrix cores (tk_index_shard_scan_first_dev / _rest_dev)
     def plain_ok(self, k, n_probes, pass_1):
         return self.dev.shard_plain(k, n_probes, pass_1)
 
     def scan_first(self, slot, qn, qp, k, n_probes, pass_1, capacity, send, flag, bound, probes_all=None):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
-        self.dev.shard_scan_first_dev(slot, qn.data_ptr(), qp.data_ptr(), qp.dtype == torch.float64,
-                                      qn.shape[0], k, n_probes, pass_1, capacity, send.data_ptr(),
-                                      flag.data_ptr(), bound.data_ptr(), stream=st,
-                                      probes_all_ptr=None if probes_all is None else probes_all.data_ptr())
+        self.dev.shard_scan_first_dev(slot, qn.data_ptr(), qp.data_ptr(), _f64(qp), qn.shape[0], k, n_probes,
+                                      pass_1, capacity, send.data_ptr(), flag.data_ptr(), bound.data_ptr(),
+                                      stream=_stream(), probes_all_ptr=_ptr(probes_all))
 
     def scan_rest(self, slot, qn, k, n_probes, pass_1, capacity, send, bound):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
         self.dev.shard_scan_rest_dev(slot, qn.shape[0], k, n_probes, pass_1, capacity, send.data_ptr(),
-                                     bound.data_ptr(), stream=st)
+                                     bound.data_ptr(), stream=_stream())
 
     # ... in ONE phase, heads exactly and the rest on the matrix cores, checked by the home replay
     # (tk_index_shard_scan_plain_dev)
     def scan_plain(self, slot, qn, qp, k, n_probes, pass_1, capacity, send, flag, probes_all=None, bound=None):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
-        self.dev.shard_scan_plain_dev(slot, qn.data_ptr(), qp.data_ptr(), qp.dtype == torch.float64,
-                                      qn.shape[0], k, n_probes, pass_1, capacity, send.data_ptr(),
-                                      flag.data_ptr(), stream=st,
-                                      probes_all_ptr=None if probes_all is None else probes_all.data_ptr(),
-                                      bound_ptr=None if bound is None else bound.data_ptr())
+        self.dev.shard_scan_plain_dev(slot, qn.data_ptr(), qp.data_ptr(), _f64(qp), qn.shape[0], k, n_probes,
+                                      pass_1, capacity, send.data_ptr(), flag.data_ptr(), stream=_stream(),
+                                      probes_all_ptr=_ptr(probes_all), bound_ptr=_ptr(bound))
 
     # ... behind one byte per query: heads of the first lists + the bound after them (tk_index_shard_scan_head_dev)
     def scan_head(self, slot, qn, qp, k, n_probes, pass_1, capacity, send, flag, bound, probes_all=None):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
-        self.dev.shard_scan_head_dev(slot, qn.data_ptr(), qp.data_ptr(), qp.dtype == torch.float64,
-                                     qn.shape[0], k, n_probes, pass_1, capacity, send.data_ptr(),
-                                     flag.data_ptr(), bound.data_ptr(), stream=st,
-                                     probes_all_ptr=None if probes_all is None else probes_all.data_ptr())
+        self.dev.shard_scan_head_dev(slot, qn.data_ptr(), qp.data_ptr(), _f64(qp), qn.shape[0], k, n_probes,
+                                     pass_1, capacity, send.data_ptr(), flag.data_ptr(), bound.data_ptr(),
+                                     stream=_stream(), probes_all_ptr=_ptr(probes_all))
 
     def finish(self, slot, qn, k, n_probes, pass_1, capacity, recv, out_home, flag=None):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
         self.dev.shard_finish_dev(slot, qn.data_ptr(), qn.shape[0], k, n_probes, pass_1, capacity,
-                                  recv.data_ptr(), out_home.data_ptr(), stream=st,
-                                  flag_ptr=None if flag is None else flag.data_ptr())
+                                  recv.data_ptr(), out_home.data_ptr(), stream=_stream(), flag_ptr=_ptr(flag))
 
     def usage(self, slot):
         return self.dev.shard_usage(slot)
 
     # filtered exchange (tk_index_shard_bound_dev / _filter_dev / _finish_filtered_dev)
     def bound(self, slot, qn, k, n_probes, pass_1, capacity, scan_buf, bound):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
         self.dev.shard_bound_dev(slot, qn.shape[0], k, n_probes, pass_1, capacity,
-                                 scan_buf.data_ptr(), bound.data_ptr(), stream=st)
+                                 scan_buf.data_ptr(), bound.data_ptr(), stream=_stream())
 
     def filter(self, slot, qn, k, n_probes, pass_1, capacity, scan_buf, bound, counts, records):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
         self.dev.shard_filter_dev(slot, qn.shape[0], k, n_probes, pass_1, capacity,
                                   scan_buf.data_ptr(), bound.data_ptr(), counts.data_ptr(),
-                                  records.data_ptr(), stream=st)
+                                  records.data_ptr(), stream=_stream())
 
     def finish_filtered(self, slot, qn, k, n_probes, pass_1, records, n_records, out_home, flag):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
         self.dev.shard_finish_filtered_dev(slot, qn.data_ptr(), qn.shape[0], k, n_probes, pass_1,
                                            records.data_ptr(), n_records, out_home.data_ptr(),
-                                           flag.data_ptr(), stream=st)
-
+                                           flag.data_ptr(), stream=_stream())
 
     # ... without the host synchronisation: fixed regions, counts read on the device
     def filter_regions(self, slot, qn, k, n_probes, pass_1, capacity, scan_buf, bound, counts, records,
                        region, flag, acc=None):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
         self.dev.shard_filter_regions_dev(slot, qn.shape[0], k, n_probes, pass_1, capacity,
                                           scan_buf.data_ptr(), bound.data_ptr(), counts.data_ptr(),
                                           records.data_ptr(), region, flag.data_ptr(),
-                                          acc_ptr=None if acc is None else acc.data_ptr(), stream=st)
+                                          acc_ptr=_ptr(acc), stream=_stream())
 
     def finish_regions(self, slot, qn, k, n_probes, pass_1, records, counts_recv, region, out_home, flag):
-        import torch
-        st = torch.cuda.current_stream().cuda_stream
         self.dev.shard_finish_regions_dev(slot, qn.data_ptr(), qn.shape[0], k, n_probes, pass_1,
                                           records.data_ptr(), counts_recv.data_ptr(), region,
-                                          out_home.data_ptr(), flag.data_ptr(), stream=st)
+                                          out_home.data_ptr(), flag.data_ptr(), stream=_stream())
 
 
 class ListShardedIndex:
