@@ -10,8 +10,17 @@ queries through the whole device pipeline (tables, coarse stage, list scan, exac
 heap replay, exact rescoring).  Queries are resident in HBM, already normalised as
 the reference's host code does (ivf.py:125-127), when the timed region starts.
 
-    python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5            # the headline alone
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full     # + every other leg and the detail record
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run fits and builds the index, warms up, times the --steps steps, writes --dump-outputs, computes the recall
+and prints ONE JSON line (roofline and stage times from the timed region's own events).  --full adds what takes runs
+of its own: the raw-stream, hipGraph, host-boundary and fast-front-end rates, the isolated stages, the rocprofv3 child
+runs, the HBM-scale leg, the CPU baseline with its row-by-row parity, query1, the replay / rescore roofs, the sweep,
+the rank-share leg and the one-rank list-sharded rehearsal; it prints the detail record (`# bench_detail ...`, and a
+file) in front of the line.  Neither reads what an earlier run left: caches live in a directory of the run
+(--cache-dir names a lasting one).
 
 N > 1: `value` is the LIST-SHARDED index (north_star's split): inverted
 lists partitioned by cluster id over the ranks, ONE shared batch of --nq queries per
@@ -187,9 +196,13 @@ def _json_safe(x):
     return x
 
 
-def emit(line, detail_file=None):
-    """Detail first (file + a prefixed stdout line), then the compact line as the LAST line of stdout."""
+def emit(line, detail_file=None, detail=True):
+    """Detail first (file + a prefixed stdout line), then the compact line as the LAST line of stdout.  detail=False
+    (a plain run): the compact line alone."""
     full = _json_safe(line)
+    if not detail:
+        print(json.dumps(compact_line(full), allow_nan=False), flush=True)
+        return
     path = detail_file or os.path.join(ROOT, "gpurun_out", "bench", "bench_detail.json")
     shown = None
     try:
@@ -236,9 +249,32 @@ def save_atomic(path, write):
             pass
 
 
+_PRIVATE_CACHE = []
+
+
+def private_cache_dir():
+    """A cache directory of this run alone, removed when it ends (drop_private_cache)."""
+    import atexit
+    import tempfile
+    path = tempfile.mkdtemp(prefix="tinyknn_bench_")
+    _PRIVATE_CACHE.append(path)
+    atexit.register(drop_private_cache)
+    return path
+
+
+def drop_private_cache():
+    """Remove the private cache directory; also called in front of os._exit, which skips atexit."""
+    import shutil
+    while _PRIVATE_CACHE:
+        shutil.rmtree(_PRIVATE_CACHE.pop(), ignore_errors=True)
+
+
 def synth_cached(args):
     """synth() of the run's data set, kept as a .npy beside the index cache: the profiler child runs and the sweep's
-    second build over the same rows load it instead of drawing 118M normals again (7 s each)."""
+    second build over the same rows load it instead of drawing 118M normals again (7 s each).  No cache directory
+    (args.cache_dir None): synth() alone, nothing read or written."""
+    if args.cache_dir is None:
+        return synth(args.n, 0, args.d, args.seed, kind=args.data)
     path = os.path.join(args.cache_dir, f"tinyknn_bench_rows_n{args.n}_d{args.d}_s{args.seed}_{args.data}.npy")
     cent = np.random.RandomState(args.seed).randn(300, args.d)      # synth()'s first draw
     if os.path.exists(path):
@@ -314,19 +350,19 @@ def load_real(args):
 
 
 def build_index(args, device, X=None):
-    """Fit + build with the product's host code; cached on local disk because the
-    driver runs N = 1, 2, 4, 8 back to back on one box."""
+    """Fit + build with the product's host code; kept in args.cache_dir (when there is one) for the child runs, the
+    other ranks and later runs that name the same directory."""
     from tinyknn_amd import IVF, FastPQ
     from tinyknn_amd.fast_pq import TransformedData
     src = args.data if X is None else os.path.basename(args.data_file)
     tag = f"n{args.n}_d{args.d}_c{args.n_clusters}_s{args.seed}_b{args.build_probes}_{args.metric}_{src}_c32"
-    cache = os.path.join(args.cache_dir, f"tinyknn_bench_{tag}.npz")
+    cache = None if args.cache_dir is None else os.path.join(args.cache_dir, f"tinyknn_bench_{tag}.npz")
     cent = None
     if X is None:
         X, cent = synth_cached(args)
     ang = args.metric == "angular"
     ivf = IVF(args.metric, args.n_clusters, FastPQ(2))
-    if os.path.exists(cache):
+    if cache is not None and os.path.exists(cache):
         try:
             z = np.load(cache)
             ivf.pq.centers = z["pq_centers"]
@@ -358,6 +394,8 @@ def build_index(args, device, X=None):
     log(f"[bench] fit done in {time.time() - t0:.1f}s")
     ivf.build(X, n_probes=args.build_probes, device=True)   # build.hip: same lists and codes as numpy
     log(f"[bench] build done in {time.time() - t0:.1f}s")
+    if cache is None:
+        return ivf, cent
     L = len(ivf.active_centers)
     extra = {} if ivf.pq.R is None else {"R": ivf.pq.R}
     save_atomic(cache, lambda f: np.savez(
@@ -409,9 +447,10 @@ def build_index_c5(args, device):
     # the SAME centres and codebook: rank 0 fits first (main() orders the ranks) and leaves the
     # fitted parameters in the cache directory; the other ranks load them.  The BUILD from those
     # parameters is deterministic (seeded generator, stable sort) and runs on every rank.
-    fit_cache = os.path.join(args.cache_dir, f"tinyknn_bench_c5fit_n{args.n}_d{args.d}_c{args.n_clusters}_s{args.seed}"
-                             + (f"_m{micro}_g{sigma}" if micro > 0 else "") + ".npz")
-    if os.path.exists(fit_cache):
+    fit_cache = None if args.cache_dir is None else os.path.join(
+        args.cache_dir, f"tinyknn_bench_c5fit_n{args.n}_d{args.d}_c{args.n_clusters}_s{args.seed}"
+        + (f"_m{micro}_g{sigma}" if micro > 0 else "") + ".npz")
+    if fit_cache is not None and os.path.exists(fit_cache):
         z = np.load(fit_cache)
         ivf.all_centers = z["all_centers"]
         ivf.pq.centers = z["pq_centers"]
@@ -425,12 +464,10 @@ def build_index_c5(args, device):
         fit_pq(ivf.pq, sample[:30000], args.seed)
         del sample
         torch.cuda.empty_cache()
-        try:
-            extra = {} if ivf.pq.R is None else {"R": ivf.pq.R}
-            np.savez(fit_cache, all_centers=ivf.all_centers, pq_centers=ivf.pq.centers,
-                     sqrt_n_blocks=ivf.pq.sqrt_n_blocks, **extra)
-        except OSError as e:
-            log(f"[bench] could not cache the c5 fit: {e}")
+        extra = {} if ivf.pq.R is None else {"R": ivf.pq.R}
+        if fit_cache is not None:
+            save_atomic(fit_cache, lambda f: np.savez(f, all_centers=ivf.all_centers, pq_centers=ivf.pq.centers,
+                                                      sqrt_n_blocks=ivf.pq.sqrt_n_blocks, **extra))
         log(f"[bench] c5 fit done in {time.time() - t0:.1f}s")
     ivf.build_resident(args.n, args.d, args.seed, cent, sigma)
     sz = ivf.list_sizes
@@ -526,7 +563,7 @@ def list_sharded_leg(args, ivf, cent, dev, device, world, rank):
                                                              "identical_rows_vs_replica", "exchange")}
     # the same with ONE step per exchange (fixed Q = --nq queries per exchange: SURVEY 8e's definition
     # of strong scaling), beside the coalesced figure above
-    if co > 1:
+    if args.full and co > 1:
         idx.exchange = kinds[0]
         idx.coalesce = 1
         r1 = _list_sharded_run(args, idx, device, world, rank, qn_t, qp_t, want, 1, kinds[0])
@@ -536,7 +573,7 @@ def list_sharded_leg(args, ivf, cent, dev, device, world, rank):
     res["streams"] = ("by role: front (coarse stages, probe all-gather) / scan (every scan, in order) / two replay "
                       "streams (exchange, replay, rescoring, id gather)" if idx._roles is not None and kinds[0] == "dense"
                       else "one stream per batch in flight")
-    if world == 1 and args.rank_share > 1 and getattr(ivf, "pq_transformed_points", 0) is not None:
+    if args.full and world == 1 and args.rank_share > 1 and getattr(ivf, "pq_transformed_points", 0) is not None:
         # (a resident index was sharded IN PLACE by the leg above: main() runs its rank share first)
         del idx
         torch.cuda.empty_cache()
@@ -1325,7 +1362,10 @@ def main():
                     help="queries timed on the CPU oracle (one core, ~10 s at the default) and compared row by row: the "
                          "distinct batches of the timed region, then more batches of the same generator")
     ap.add_argument("--recall-sample", type=int, default=1000)
-    ap.add_argument("--cache-dir", default=os.environ.get("TMPDIR", "/tmp"))
+    ap.add_argument("--cache-dir", default=None,
+                    help="keep the synthetic rows and the built index here, and load them from here when they are "
+                         "there (default: none for a plain run; --full and N > 1: a private directory of this run, "
+                         "shared with its ranks and child runs, removed at exit)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL)")
     ap.add_argument("--build-probes", type=int, default=1, help="lists per point (ivf.py:53)")
@@ -1417,6 +1457,13 @@ def main():
     ap.add_argument("--query-file", default=None, help=".npy of queries for --data-file (else its last --nq rows)")
     ap.add_argument("--a", type=float, default=1.0,
                     help="--data-file: n_clusters = int(a * sqrt(n)) unless --n-clusters is given (examples/bench.py:73)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: raw stream, isolated stages, hipGraph, host-boundary and "
+                         "fast front-end rates, profiler child runs, HBM-scale leg, CPU baseline and parity with the "
+                         "oracle, query1, replay / rescore roofs, sweep, rank-share and the one-rank list-sharded "
+                         "rehearsal; the detail record beside the result line.  Without it a run sets up, warms up, "
+                         "times --steps steps, computes the recall and prints the result line (N > 1: the "
+                         "list-sharded leg, which is then the headline)")
     args = ap.parse_args()
     if args.workload == "c5":
         dflt = ap.parse_args([])
@@ -1451,6 +1498,13 @@ def main():
 
     from tinyknn_amd import _lib
     _lib.check(_lib.lib().tk_set_device(dev_id))
+    if args.cache_dir is None and (args.full or world > 1):
+        # the other ranks load rank 0's index (the same centres and codebook on every rank), the child runs and the
+        # sweep its rows; nothing of an earlier run is read
+        box = [private_cache_dir() if rank == 0 else None]
+        if world > 1:
+            dist.broadcast_object_list(box, src=0)
+        args.cache_dir = box[0]
 
     # -- index: rank 0 builds (or loads) first so that the cache exists for the others
     if world > 1 and rank != 0:
@@ -1601,30 +1655,31 @@ def main():
     stages, scan_bytes, n_prof = dev.last_profile()
     plain_ms_timed = getattr(dev, "last_plain_kernel_ms", 0.0)      # HIP events around the plain kernel alone
     plain_stats_timed = dev.plain_stats()       # of the last batch of the timed region (a pair of steps when coalescing)
-    raw_leg = None if args.profile_only else raw_stream_leg(args, dev, qs, out_dev, device, world)
+    raw_leg = raw_stream_leg(args, dev, qs, out_dev, device, world) if args.full and not args.profile_only else None
     lap("queries, warm-up, timed region, raw stream leg")
-    # the same kernels with ONE batch in flight (no co-running batches), for reference
-    dev.set_pipeline(1)
-    dev.reserve(args.nq, args.k, args.n_probes)
-    step()
-    torch.cuda.synchronize()     # untimed: first call after the workspace change
-    dev.set_profiling(True)
-    for _ in range(5):
+    iso_stages = iso_bytes = plain_stats = replay_rounds = None
+    if args.full or args.profile_only:
+        # the same kernels with ONE batch in flight (no co-running batches), for reference
+        dev.set_pipeline(1)
+        dev.reserve(args.nq, args.k, args.n_probes)
         step()
-    torch.cuda.synchronize()
-    iso_stages, iso_bytes, _ = dev.last_profile()
-    dev.set_profiling(False)
-    plain_stats = dev.plain_stats()      # of the last batch: tiles, pairs by kernel, queries re-scanned
-    # the list replay's insert rounds of ONE batch (roofline.replay): a device counter, one extra step
-    replay_rounds = None
-    try:
-        dev.set_option(_lib.OPT_REPLAY_COUNT, 1)
-        step()
+        torch.cuda.synchronize()     # untimed: first call after the workspace change
+        dev.set_profiling(True)
+        for _ in range(5):
+            step()
         torch.cuda.synchronize()
-        replay_rounds = dev.replay_stats()
-        dev.set_option(_lib.OPT_REPLAY_COUNT, 0)
-    except Exception as e:      # noqa: BLE001 - measurement plumbing
-        log(f"[bench] replay rounds not counted: {e!r}")
+        iso_stages, iso_bytes, _ = dev.last_profile()
+        dev.set_profiling(False)
+        plain_stats = dev.plain_stats()      # of the last batch: tiles, pairs by kernel, queries re-scanned
+        # the list replay's insert rounds of ONE batch (roofline.replay): a device counter, one extra step
+        try:
+            dev.set_option(_lib.OPT_REPLAY_COUNT, 1)
+            step()
+            torch.cuda.synchronize()
+            replay_rounds = dev.replay_stats()
+            dev.set_option(_lib.OPT_REPLAY_COUNT, 0)
+        except Exception as e:      # noqa: BLE001 - measurement plumbing
+            log(f"[bench] replay rounds not counted: {e!r}")
     if args.profile_only:
         if rank == 0:
             print(json.dumps({"profile_only": True, "ms_per_step": elapsed / K * 1e3,
@@ -1635,99 +1690,100 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
-    # BASELINE configs[3]: a hipGraph-captured batch.  (a) one batch, one batch in flight, captured
-    # once and replayed; (b) the PIPELINED mode as one graph: `gsteps` consecutive steps (the rotating
-    # batches) + the join, captured on a side stream — the index's internal streams fork from it
-    # through the events the calls record and are joined again by tk_index_join — and replayed.
-    graph = None
-    try:
-        if world > 1:      # RCCL's watchdog thread touches the device during a global-mode capture
-            raise RuntimeError("skipped at N > 1")
-        g = torch.cuda.CUDAGraph()
-        gout = torch.full((args.nq, args.k), -1, dtype=torch.int64, device=device)
-        with torch.cuda.graph(g):
-            dev.query_batch_dev(q_dev.data_ptr(), qp_dev.data_ptr(), qp_is_f64, args.nq, args.k,
-                                args.n_probes, gout.data_ptr(),
-                                stream=torch.cuda.current_stream().cuda_stream)
-        g.replay()
-        torch.cuda.synchronize()
-        tg = time.perf_counter()
-        for _ in range(20):
-            g.replay()
-        torch.cuda.synchronize()
-        tg = (time.perf_counter() - tg) / 20
-        graph = {"one_batch_in_flight": {"ms_per_replay": tg * 1e3, "queries_per_s": args.nq / tg,
-                                         "identical_to_stream_launch": bool((gout.cpu().numpy() == out_dev.cpu().numpy()).all())}}
-        del g
-        # (b)
-        gsteps = args.graph_steps
-        dev.set_profiling(False)
-        dev.set_pipeline(args.pipeline)
-        dev.reserve(args.nq, args.k, args.n_probes)
-        gouts = [torch.full((args.nq, args.k), -1, dtype=torch.int64, device=device) for _ in range(N_BATCHES)]
-
-        def gstep(i, st):
-            bb = batches[i % N_BATCHES]
-            dev.query_batch_dev(bb["q_dev"].data_ptr(), bb["qp_dev"].data_ptr(), qp_is_f64, args.nq, args.k,
-                                args.n_probes, gouts[i % N_BATCHES].data_ptr(), stream=st)
-
-        side = torch.cuda.Stream()
-        with torch.cuda.stream(side):
-            for i in range(gsteps):      # uncaptured once: workspaces, events and streams exist afterwards
-                gstep(i, side.cuda_stream)
-            dev.join(side.cuda_stream)
-        torch.cuda.synchronize()
-        dev.quiesce()
-        g2 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g2):
-            cs = torch.cuda.current_stream().cuda_stream
-            for i in range(gsteps):
-                gstep(i, cs)
-            dev.join(cs)
-        dev.quiesce()
-        for o in gouts:
-            o.fill_(-1)
-        g2.replay()
-        torch.cuda.synchronize()
-        same = all(bool((gouts[b_].cpu().numpy() == batches[b_]["out"].cpu().numpy()).all()) for b_ in range(N_BATCHES))
-        tg = time.perf_counter()
-        for _ in range(10):
-            g2.replay()
-        torch.cuda.synchronize()
-        tg = (time.perf_counter() - tg) / 10
-        graph.update({"ms_per_replay": tg * 1e3, "steps_per_replay": gsteps, "ms_per_step": tg / gsteps * 1e3,
-                      "queries_per_s": args.nq * gsteps / tg, "batches_in_flight": args.pipeline,
-                      "identical_to_stream_launch": same,
-                      "note": "the pipelined mode captured as ONE hipGraph (%d steps + join; internal streams "
-                              "forked and joined by events inside the capture), replayed; each replay pays the "
-                              "pipeline's fill and drain once" % gsteps})
-        del g2
-        dev.quiesce()
-        dev.set_pipeline(1)
-    except Exception as e:       # capture support is an extra, never the measured path
-        graph = dict(graph or {}, error=repr(e))
+    graph = host_qps = host_ids = fast_ids = fast_qps = None
+    if args.full:
+        # BASELINE configs[3]: a hipGraph-captured batch.  (a) one batch, one batch in flight, captured
+        # once and replayed; (b) the PIPELINED mode as one graph: `gsteps` consecutive steps (the rotating
+        # batches) + the join, captured on a side stream — the index's internal streams fork from it
+        # through the events the calls record and are joined again by tk_index_join — and replayed.
         try:
+            if world > 1:      # RCCL's watchdog thread touches the device during a global-mode capture
+                raise RuntimeError("skipped at N > 1")
+            g = torch.cuda.CUDAGraph()
+            gout = torch.full((args.nq, args.k), -1, dtype=torch.int64, device=device)
+            with torch.cuda.graph(g):
+                dev.query_batch_dev(q_dev.data_ptr(), qp_dev.data_ptr(), qp_is_f64, args.nq, args.k,
+                                    args.n_probes, gout.data_ptr(),
+                                    stream=torch.cuda.current_stream().cuda_stream)
+            g.replay()
+            torch.cuda.synchronize()
+            tg = time.perf_counter()
+            for _ in range(20):
+                g.replay()
+            torch.cuda.synchronize()
+            tg = (time.perf_counter() - tg) / 20
+            graph = {"one_batch_in_flight": {"ms_per_replay": tg * 1e3, "queries_per_s": args.nq / tg,
+                                             "identical_to_stream_launch": bool((gout.cpu().numpy() == out_dev.cpu().numpy()).all())}}
+            del g
+            # (b)
+            gsteps = args.graph_steps
+            dev.set_profiling(False)
+            dev.set_pipeline(args.pipeline)
+            dev.reserve(args.nq, args.k, args.n_probes)
+            gouts = [torch.full((args.nq, args.k), -1, dtype=torch.int64, device=device) for _ in range(N_BATCHES)]
+
+            def gstep(i, st):
+                bb = batches[i % N_BATCHES]
+                dev.query_batch_dev(bb["q_dev"].data_ptr(), bb["qp_dev"].data_ptr(), qp_is_f64, args.nq, args.k,
+                                    args.n_probes, gouts[i % N_BATCHES].data_ptr(), stream=st)
+
+            side = torch.cuda.Stream()
+            with torch.cuda.stream(side):
+                for i in range(gsteps):      # uncaptured once: workspaces, events and streams exist afterwards
+                    gstep(i, side.cuda_stream)
+                dev.join(side.cuda_stream)
+            torch.cuda.synchronize()
+            dev.quiesce()
+            g2 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g2):
+                cs = torch.cuda.current_stream().cuda_stream
+                for i in range(gsteps):
+                    gstep(i, cs)
+                dev.join(cs)
+            dev.quiesce()
+            for o in gouts:
+                o.fill_(-1)
+            g2.replay()
+            torch.cuda.synchronize()
+            same = all(bool((gouts[b_].cpu().numpy() == batches[b_]["out"].cpu().numpy()).all()) for b_ in range(N_BATCHES))
+            tg = time.perf_counter()
+            for _ in range(10):
+                g2.replay()
+            torch.cuda.synchronize()
+            tg = (time.perf_counter() - tg) / 10
+            graph.update({"ms_per_replay": tg * 1e3, "steps_per_replay": gsteps, "ms_per_step": tg / gsteps * 1e3,
+                          "queries_per_s": args.nq * gsteps / tg, "batches_in_flight": args.pipeline,
+                          "identical_to_stream_launch": same,
+                          "note": "the pipelined mode captured as ONE hipGraph (%d steps + join; internal streams "
+                                  "forked and joined by events inside the capture), replayed; each replay pays the "
+                                  "pipeline's fill and drain once" % gsteps})
+            del g2
             dev.quiesce()
             dev.set_pipeline(1)
-        except Exception:
-            pass
-    # the same batch through the HOST-pointer entry point (tk_index_query_batch: H2D of the
-    # queries, the pipeline, D2H of the ids, synchronous) — the PCIe-inclusive rate
-    dev.query_batch(qn, qp, args.k, args.n_probes)
-    th = time.perf_counter()
-    for _ in range(3):
-        host_ids = dev.query_batch(qn, qp, args.k, args.n_probes)
-    host_qps = 3 * args.nq / (time.perf_counter() - th)
-    # the same RAW queries through the device front end ("fast mode": normalisation, padding,
-    # rotation on the GPU instead of numpy's per-query BLAS calls; within 1 ulp, not exact)
-    try:
-        fast_ids = dev.query_batch_raw(qs, args.k, args.n_probes)
+        except Exception as e:       # capture support is an extra, never the measured path
+            graph = dict(graph or {}, error=repr(e))
+            try:
+                dev.quiesce()
+                dev.set_pipeline(1)
+            except Exception:
+                pass
+        # the same batch through the HOST-pointer entry point (tk_index_query_batch: H2D of the
+        # queries, the pipeline, D2H of the ids, synchronous) — the PCIe-inclusive rate
+        dev.query_batch(qn, qp, args.k, args.n_probes)
         th = time.perf_counter()
         for _ in range(3):
+            host_ids = dev.query_batch(qn, qp, args.k, args.n_probes)
+        host_qps = 3 * args.nq / (time.perf_counter() - th)
+        # the same RAW queries through the device front end ("fast mode": normalisation, padding,
+        # rotation on the GPU instead of numpy's per-query BLAS calls; within 1 ulp, not exact)
+        try:
             fast_ids = dev.query_batch_raw(qs, args.k, args.n_probes)
-        fast_qps = 3 * args.nq / (time.perf_counter() - th)
-    except (AssertionError, RuntimeError) as e:     # e.g. angular with d > 128: an extra only
-        fast_ids, fast_qps = None, repr(e)
+            th = time.perf_counter()
+            for _ in range(3):
+                fast_ids = dev.query_batch_raw(qs, args.k, args.n_probes)
+            fast_qps = 3 * args.nq / (time.perf_counter() - th)
+        except (AssertionError, RuntimeError) as e:     # e.g. angular with d > 128: an extra only
+            fast_ids, fast_qps = None, repr(e)
     t = torch.tensor([elapsed], dtype=torch.float64,
                      device=device if args.backend == "nccl" else "cpu")
     if world > 1:
@@ -1741,7 +1797,7 @@ def main():
     # (torch.distributed, backend nccl, world 1), both exchanges, coalesced and fixed-Q — so that the
     # driver's line carries it.  The process group is created only now: RCCL's internal stream would share
     # one of HIP's four hardware queues with the pipelined index during the headline region.
-    shard_w1 = (args.shard == "auto" and world == 1 and not args.data_file and not args.profile_only and
+    shard_w1 = (args.full and args.shard == "auto" and world == 1 and not args.data_file and
                 (args.workload, args.n, args.d, args.n_clusters, args.nq, args.n_probes, args.metric, args.data,
                  args.build_probes) == ("glove", 1183514, 100, 1087, 10000, 10, "angular", "glove-like", 1))
     if rank != 0:
@@ -1772,41 +1828,43 @@ def main():
                                                     "glove-like", 1)
     kstats, kstats_src = None, "not run"
     plain_on_timed = bool(plain_stats_timed and plain_stats_timed.get("plain_units"))
-    if args.traffic == "auto" and (default_wl or args.workload == "c5") and world == 1 and not args.data_file:
+    if args.full and args.traffic == "auto" and (default_wl or args.workload == "c5") and world == 1 and not args.data_file:
         lap("hipgraph leg, stage and isolated timings")
         traffic, traffic_src = measure_traffic(args, plain_on_timed)
         lap("PMC traffic child runs")
         kstats, kstats_src = kernel_stats_child(args, plain_on_timed)
         lap("kernel-stats child run")
     hbm_leg = None
-    if not args.no_hbm_leg and world == 1:
+    if args.full and not args.no_hbm_leg and world == 1:
         try:
             hbm_leg = hbm_scale_leg(device)
         except Exception as e:      # noqa: BLE001 - an extra leg must not lose the line
             hbm_leg = {"error": repr(e)}
 
-    # the box's device-copy bandwidth (read + write), the practical HBM ceiling next to the spec
-    try:
-        src = torch.empty(1 << 28, dtype=torch.float32, device=device)      # 1 GiB
-        dst = torch.empty_like(src)
-        dst.copy_(src)
-        torch.cuda.synchronize()
-        tc0 = time.perf_counter()
-        for _ in range(5):
+    copy_gbps = read_gbps = None
+    if args.full:
+        # the box's device-copy bandwidth (read + write), the practical HBM ceiling next to the spec
+        try:
+            src = torch.empty(1 << 28, dtype=torch.float32, device=device)      # 1 GiB
+            dst = torch.empty_like(src)
             dst.copy_(src)
-        torch.cuda.synchronize()
-        copy_gbps = 5 * 2 * src.numel() * 4 / (time.perf_counter() - tc0) / 1e9
-        # ... and a read-only kernel over 1 GiB (the flat scan's access pattern): the streaming-read
-        # ceiling the HBM-scale scan leg is up against (profiles/r02_read_bw_microbench.txt)
-        del src, dst
-        import ctypes
-        rb = ctypes.c_double(0.0)
-        _lib.check(_lib.lib().tk_measure_read_bandwidth(1 << 30, 10, ctypes.byref(rb)))
-        read_gbps = rb.value
-    except Exception:
-        copy_gbps = read_gbps = None
-    if hbm_leg and "GBps" in hbm_leg and read_gbps:
-        hbm_leg["frac_of_measured_read_only_kernel"] = hbm_leg["GBps"] / read_gbps
+            torch.cuda.synchronize()
+            tc0 = time.perf_counter()
+            for _ in range(5):
+                dst.copy_(src)
+            torch.cuda.synchronize()
+            copy_gbps = 5 * 2 * src.numel() * 4 / (time.perf_counter() - tc0) / 1e9
+            # ... and a read-only kernel over 1 GiB (the flat scan's access pattern): the streaming-read
+            # ceiling the HBM-scale scan leg is up against (profiles/r02_read_bw_microbench.txt)
+            del src, dst
+            import ctypes
+            rb = ctypes.c_double(0.0)
+            _lib.check(_lib.lib().tk_measure_read_bandwidth(1 << 30, 10, ctypes.byref(rb)))
+            read_gbps = rb.value
+        except Exception:
+            copy_gbps = read_gbps = None
+        if hbm_leg and "GBps" in hbm_leg and read_gbps:
+            hbm_leg["frac_of_measured_read_only_kernel"] = hbm_leg["GBps"] / read_gbps
 
     # -- recall against brute force (torch matmul on the GPU: measurement plumbing)
     rs = min(args.recall_sample, args.nq)
@@ -1839,7 +1897,7 @@ def main():
     cpu = None
     parity = None
     query1 = None
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         cs = min(args.cpu_sample, args.nq)
         heap_parity = None
         if args.workload == "c5":
@@ -1980,7 +2038,7 @@ def main():
                 "covers": "ONE batch of %d queries, one batch in flight (a pair of calls runs as one launch of twice the "
                           "waves in about the same time)" % args.nq}
         row_bytes = args.d * 4
-        if row_bytes % 16 == 0 and row_bytes <= 1024 and ivf.data.dtype == np.float32:
+        if args.full and row_bytes % 16 == 0 and row_bytes <= 1024 and ivf.data.dtype == np.float32:
             gb = ctypes_double()
             _lib.check(_lib.lib().tk_measure_gather_bandwidth(int(min(args.n, 4_000_000)) * row_bytes, row_bytes,
                                                               int(args.nq) * R_heap, 20, gb.ref))
@@ -2001,7 +2059,7 @@ def main():
         side_roofs["error"] = repr(e)
 
     sweep = None
-    if args.sweep == "auto" and default_wl and world == 1 and not args.data_file:
+    if args.full and args.sweep == "auto" and default_wl and world == 1 and not args.data_file:
         try:
             sweep = sweep_leg(args, ivf, dev, batches, qp_is_f64, stream, device, cent)
         except Exception as e:      # noqa: BLE001 - an extra leg must not lose the line
@@ -2054,32 +2112,33 @@ def main():
         "raw_in_ids_out": raw_leg,
         "roofline_hbm_scale": hbm_leg,
         "stage_ms": stages,
-        "isolated": {"note": "same batch with one batch in flight (5 steps after the timed region)",
-                     "stage_ms": iso_stages, "ms_per_step": sum(iso_stages.values()),
-                     "scan_stage_algorithmic_GBps": iso_bytes / (iso_stages["scan"] * 1e-3) / 1e9,
-                     "scan_stage_note": "algorithmic bytes (one code byte per (query, code) pair) over the isolated scan "
-                                        "stage; NOT HBM traffic (32 queries share each fetched tile, the code set sits in "
-                                        "L2 / Infinity Cache): no fraction of the HBM peak is formed from it"},
         "hipgraph": graph,
-        "host_boundary": {"queries_per_s": host_qps,
-                          "note": "tk_index_query_batch with host buffers: H2D queries + pipeline + D2H ids, "
-                                  "synchronous, one batch at a time (never `value`)",
-                          "identical_to_device_path": bool((host_ids == got).all()),
-                          "host_prepare_ms_per_batch": t_prep * 1e3,
-                          "host_prepare_note": "ivf.py:125-128 + fast_pq.py:200-204 per query in numpy "
-                                               "(BLAS norm, padding, BLAS GEMV), before any of the rates above"},
-        "fast_front_end": {"queries_per_s": fast_qps,
-                           "note": "raw float32 queries in, ids out (H2D + device normalisation/padding/rotation "
-                                   "+ pipeline + D2H, synchronous); within 1 ulp of the host preparation, not "
-                                   "bit-identical: never `value`",
-                           "rows_identical_to_exact_path": (None if fast_ids is None else
-                                                            int((fast_ids == got).all(axis=1).sum())),
-                           "rows": args.nq},
         "cpu_baseline": cpu,
         "parity_vs_oracle": parity,
         "query1": query1,
         "sweep": sweep,
     }
+    if args.full:
+        line["isolated"] = {"note": "same batch with one batch in flight (5 steps after the timed region)",
+                            "stage_ms": iso_stages, "ms_per_step": sum(iso_stages.values()),
+                            "scan_stage_algorithmic_GBps": iso_bytes / (iso_stages["scan"] * 1e-3) / 1e9,
+                            "scan_stage_note": "algorithmic bytes (one code byte per (query, code) pair) over the isolated "
+                                               "scan stage; NOT HBM traffic (32 queries share each fetched tile, the code "
+                                               "set sits in L2 / Infinity Cache): no fraction of the HBM peak is formed from it"}
+        line["host_boundary"] = {"queries_per_s": host_qps,
+                                 "note": "tk_index_query_batch with host buffers: H2D queries + pipeline + D2H ids, "
+                                         "synchronous, one batch at a time (never `value`)",
+                                 "identical_to_device_path": bool((host_ids == got).all()),
+                                 "host_prepare_ms_per_batch": t_prep * 1e3,
+                                 "host_prepare_note": "ivf.py:125-128 + fast_pq.py:200-204 per query in numpy "
+                                                      "(BLAS norm, padding, BLAS GEMV), before any of the rates above"}
+        line["fast_front_end"] = {"queries_per_s": fast_qps,
+                                  "note": "raw float32 queries in, ids out (H2D + device normalisation/padding/rotation "
+                                          "+ pipeline + D2H, synchronous); within 1 ulp of the host preparation, not "
+                                          "bit-identical: never `value`",
+                                  "rows_identical_to_exact_path": (None if fast_ids is None else
+                                                                   int((fast_ids == got).all(axis=1).sum())),
+                                  "rows": args.nq}
     if isinstance(query1, dict) and "ms_per_query" in query1:
         line["query1_ms_per_query"] = query1["ms_per_query"]      # (scalar: the reference's own protocol on the drop-in call)
     # the other two chains of a batch, next to the scan kernel's entry (and their fractions as top-level scalars)
@@ -2091,7 +2150,7 @@ def main():
         for key in ("replay", "rescore"):
             if side_roofs.get(key) and side_roofs[key].get("frac") is not None:
                 line["roofline_%s_frac" % key] = side_roofs[key]["frac"]
-    if args.workload == "c5" and world == 1 and args.rank_share > 1 and not do_shard:
+    if args.full and args.workload == "c5" and world == 1 and args.rank_share > 1 and not do_shard:
         # configs[4] is the workload north_star shards: one rank's share of a W-rank partition of THIS index
         # (the resident index stays unsharded: the simulated ranks are clone shards that borrow its arrays)
         try:
@@ -2130,7 +2189,8 @@ def main():
 
         def bail():
             line["list_sharded"] = {"error": f"abandoned after {args.shard_limit:.0f}s"}
-            emit(line)
+            emit(line, detail=args.full)
+            drop_private_cache()
             # a GPU process that abandoned a collective never reports success (N = 1: the headline stands)
             os._exit(3 if world > 1 else 0)
 
@@ -2142,7 +2202,8 @@ def main():
         except Exception as e:
             # the other ranks may be waiting in a collective: do not join them again
             line["list_sharded"] = {"error": repr(e)}
-            emit(line)
+            emit(line, detail=args.full)
+            drop_private_cache()
             os._exit(3 if world > 1 else 0)
         wd.cancel()
         if world == 1:
@@ -2182,7 +2243,7 @@ def main():
                                     note="scan launch of the REPLICA region (the sharded leg runs the same "
                                          "kernel on this rank's 1/%d of the (query, list) segments)" % world)
     lap("list-sharded legs")
-    emit(line)
+    emit(line, detail=args.full)
     if world > 1 or dist.is_initialized():
         dist.destroy_process_group()
 

@@ -3,10 +3,10 @@
 R=$PWD
 O=$R/gpurun_out/final
 mkdir -p $O/sweep
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 for depth in 2 1; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt$depth -- python3 $R/bench.py --steps 50 --warmup 5 --no-cpu --shard none --recall-sample 10 --pipeline $depth > $O/kt${depth}_bench.json 2> $O/kt$depth.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt$depth -- python3 $R/bench.py --full --traffic none --steps 50 --warmup 5 --no-cpu --shard none --recall-sample 10 --pipeline $depth > $O/kt${depth}_bench.json 2> $O/kt$depth.err
   f=$(find $O/kt$depth -name "*kernel_stats.csv" | head -1); cp "$f" $O/kernel_stats_pipeline$depth.csv; rm -rf $O/kt$depth
 done
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -48,10 +48,10 @@ json.dump({"kernels": "scan_units_kernel<1,true,3,false> (list scan) + <1,true,3
 PY
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE
 for np_ in 1 5 20 50; do
-  python bench.py --n-probes $np_ --shard none --cpu-sample 1000 > $O/sweep/glove_np$np_.json 2>> $O/sweep.err
+  python bench.py --full --n-probes $np_ --shard none --cpu-sample 1000 > $O/sweep/glove_np$np_.json 2>> $O/sweep.err
 done
 cp $O/bench.json $O/sweep/glove_np10.json
-python bench.py --data sift-like --metric euclidean --d 128 --n 1000000 --n-clusters 1000 --shard none --cpu-sample 2000 > $O/sweep/sift_np10.json 2>> $O/sweep.err
+python bench.py --full --data sift-like --metric euclidean --d 128 --n 1000000 --n-clusters 1000 --shard none --cpu-sample 2000 > $O/sweep/sift_np10.json 2>> $O/sweep.err
 python3 - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/final/sweep/*.json")) + ["gpurun_out/final/kt2_bench.json", "gpurun_out/final/kt1_bench.json"]:

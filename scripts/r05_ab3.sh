@@ -3,7 +3,7 @@
 # scripts/micro/bin/libtinyknn_hip_$THIRD.so); prints the rate and the lane replay's time alone
 R=$PWD; O=$R/gpurun_out/r05b; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-FL="--steps 20 --warmup 5 --sweep none --traffic none --no-hbm-leg --no-cpu --rank-share 0 --shard none --recall-sample 10 $EXTRA"
+FL="--full --steps 20 --warmup 5 --sweep none --traffic none --no-hbm-leg --no-cpu --rank-share 0 --shard none --recall-sample 10 $EXTRA"
 for i in 1 2; do
   for v in old new $THIRD; do
     if [ $v = new ]; then unset TINYKNN_HIP_LIB; else export TINYKNN_HIP_LIB=$R/scripts/micro/bin/libtinyknn_hip_$v.so; fi

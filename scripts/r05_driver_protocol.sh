@@ -1,7 +1,7 @@
 # round 5: the driver's own command, timed, its line kept under gpurun_out/r05b/ (copied to profiles/r05/bench_default.json)
 R=$PWD; O=$R/gpurun_out/r05b; mkdir -p $O
 t0=$(date +%s)
-timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err
 echo "rc=$? seconds=$(( $(date +%s) - t0 ))"; grep "bench\]" $O/bench_default.err | tail -5
 python3 - <<'PY'
 import json

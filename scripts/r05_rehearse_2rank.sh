@@ -5,7 +5,7 @@
 BP=${BP:-1}
 O=gpurun_out/r05b; mkdir -p $O
 timeout -k 10 800 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 \
-   bench.py --gpus 2 --backend gloo --steps 12 --warmup 3 --shard-exchange both --build-probes $BP > $O/two_rank_gloo_b$BP.json 2> $O/two_rank_gloo_b$BP.err
+   bench.py --gpus 2 --full --backend gloo --steps 12 --warmup 3 --shard-exchange both --build-probes $BP > $O/two_rank_gloo_b$BP.json 2> $O/two_rank_gloo_b$BP.err
 echo "rc=$?"
 grep -v amdgpu.ids $O/two_rank_gloo_b$BP.err | tail -4
 python3 - $BP <<'PY'

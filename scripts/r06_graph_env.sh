@@ -1,7 +1,7 @@
 # hipGraph of the pipelined mode under the runtime's remaining knobs (round 5 tried DEBUG_HIP_FORCE_GRAPH_QUEUES 2 / 8,
 # DEBUG_CLR_GRAPH_PACKET_CAPTURE, DEBUG_HIP_GRAPH_BATCH_SIZE, GPU_MAX_HW_QUEUES 4 / 8), and what the executor says it does
 O=gpurun_out/r06; mkdir -p $O
-B="--steps 20 --warmup 5 --sweep none --traffic none --no-hbm-leg --no-cpu --shard none"
+B="--full --steps 20 --warmup 5 --sweep none --traffic none --no-hbm-leg --no-cpu --shard none"
 run() { tag=$1; shift; env "$@" timeout -k 10 300 python bench.py $B > $O/graph_$tag.out 2> $O/graph_$tag.err || { echo "$tag failed"; tail -3 $O/graph_$tag.err; return; }
   python3 - $O/graph_$tag.out $tag <<'PY'
 import json, sys

@@ -1,6 +1,6 @@
 # hipGraph of the pipelined mode captured on 4 (as stream-launched) / 3 / 2 streams: the executor replays on two queues anyway
 O=gpurun_out/r06; mkdir -p $O
-B="--steps 20 --warmup 5 --sweep none --traffic none --no-hbm-leg --no-cpu --shard none"
+B="--full --steps 20 --warmup 5 --sweep none --traffic none --no-hbm-leg --no-cpu --shard none"
 for v in 4 2 3 2; do
   TINYKNN_GRAPH_STREAMS=$v timeout -k 10 300 python bench.py $B > $O/gs_$v.out 2> $O/gs_$v.err || { echo "$v failed"; tail -3 $O/gs_$v.err; continue; }
   python3 - $O/gs_$v.out $v <<'PY'

@@ -1,5 +1,5 @@
 O=gpurun_out/r06; mkdir -p $O
-B="--steps 20 --warmup 5 --sweep none --traffic none --no-hbm-leg --no-cpu --shard none"
+B="--full --steps 20 --warmup 5 --sweep none --traffic none --no-hbm-leg --no-cpu --shard none"
 run() { tag=$1; shift; pl=$1; shift
   env "$@" timeout -k 10 300 python bench.py $B --pipeline $pl > $O/gs2_$tag.out 2> $O/gs2_$tag.err || { echo "$tag failed"; tail -3 $O/gs2_$tag.err; return; }
   python3 - $O/gs2_$tag.out $tag <<'PY'

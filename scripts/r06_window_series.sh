@@ -1,7 +1,7 @@
 # the timed region's windows over a long run (--windows 250: 5 000 steps, ~2 s), three processes in turn: how often and for how long
 # the pipeline sits in its slower phase
 O=gpurun_out/r06; mkdir -p $O
-FLAGS="--steps 20 --warmup 5 --sweep none --traffic none --no-hbm-leg --no-cpu --shard none --windows 250"
+FLAGS="--full --steps 20 --warmup 5 --sweep none --traffic none --no-hbm-leg --no-cpu --shard none --windows 250"
 for r in 1 2 3; do
   timeout -k 10 300 python bench.py $FLAGS > $O/windows_$r.out 2> $O/windows_$r.err || exit 1
   python3 - $O/windows_$r.out <<'PY'

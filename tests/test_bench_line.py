@@ -128,3 +128,35 @@ def test_bench_caches_round_trip(tmp_path):
         raise OSError("disk full")
     bench.save_atomic(str(tmp_path / "x.bin"), boom)
     assert not (tmp_path / "x.bin").exists() and not list(tmp_path.glob("x.bin.*"))
+
+
+def test_plain_run_prints_the_compact_line_alone(tmp_path, monkeypatch):
+    """A run without --full prints its result line and nothing else: no detail line, no detail file."""
+    monkeypatch.chdir(tmp_path)
+    full = canned()
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        bench.emit(full, str(tmp_path / "detail.json"), detail=False)
+    lines = buf.getvalue().splitlines()
+    assert len(lines) == 1
+    check(json.loads(lines[0]), full)
+    assert not list(tmp_path.iterdir())
+
+
+def test_no_cache_dir_reads_and_writes_nothing(tmp_path, monkeypatch):
+    """cache_dir None (a plain run): synth()'s rows, and no file anywhere a later run could pick up."""
+    import argparse
+    import numpy as np
+    monkeypatch.chdir(tmp_path)
+    a = argparse.Namespace(cache_dir=None, n=3000, d=20, seed=10, data="glove-like")
+    X1, c1 = bench.synth_cached(a)
+    X2, c2 = bench.synth(a.n, 0, a.d, a.seed, kind=a.data)
+    assert np.array_equal(X1, X2) and np.array_equal(c1, c2)
+    assert not list(tmp_path.iterdir())
+
+
+def test_private_cache_dir_is_removed():
+    d = bench.private_cache_dir()
+    open(os.path.join(d, "x.npy"), "wb").close()
+    bench.drop_private_cache()
+    assert not os.path.exists(d)
