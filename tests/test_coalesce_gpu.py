@@ -163,3 +163,38 @@ def test_slot_descriptors_by_the_coarse_rescoring_or_by_their_own_kernel(setup, 
         np.testing.assert_array_equal(o.cpu().numpy(), want[a:b])
     dev.set_coalesce(1)
     dev.set_pipeline(1)
+
+
+@pytest.mark.parametrize("depth, coalesce, counts", [
+    (1, 1, [0, 0, 0, 0, 0]),
+    (2, 1, [1, 2, 3, 3, 3]),
+    (2, 2, [1, 2, 3, 4, 5, 6, 7, 6]),
+])
+def test_pending_calls_after_each_call(setup, depth, coalesce, counts):
+    """tk_index_pending after each call: a held call counts, a pair counts as its two calls, and at most three batches
+    wait for their list scan between calls.  None is left after the join; the rows are the oracle's."""
+    from tinyknn_amd import _lib
+    torch, fx = setup
+    ivf, ox, qn, qp = fx["an100"]
+    dev = ivf.device_index()
+    dev.set_pipeline(depth)
+    dev.set_coalesce(coalesce)
+    st = torch.cuda.current_stream().cuda_stream
+    nq = 300
+    want = ox.query_batch(qn[:nq], 10, 5)
+    q_dev, qp_dev = torch.from_numpy(qn[:nq]).cuda(), torch.from_numpy(qp[:nq]).cuda()
+    outs, seen = [], []
+    for _ in counts:
+        o = torch.full((nq, 10), -1, dtype=torch.int64, device="cuda")
+        outs.append(o)
+        dev.query_batch_dev(q_dev.data_ptr(), qp_dev.data_ptr(), False, nq, 10, 5, o.data_ptr(), stream=st)
+        seen.append(_lib.lib().tk_index_pending(dev.handle))
+    dev.join(st)
+    after_join = _lib.lib().tk_index_pending(dev.handle)
+    torch.cuda.synchronize()
+    dev.set_coalesce(1)
+    dev.set_pipeline(1)
+    assert seen == counts
+    assert after_join == 0
+    for o in outs:
+        np.testing.assert_array_equal(o.cpu().numpy(), want)

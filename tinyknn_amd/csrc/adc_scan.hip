@@ -1070,15 +1070,12 @@ static int scan_form_gmax(int M, int &form)
     return g;
 }
 
-void tk_launch_scan_units(const uint4 *codes, int M, const uint4 *tables, int64_t nq, int S,
-                          int64_t n_lists, const int64_t *list_chunk_off, const int *pair_off,
-                          const int *unit_prefix, const int *pair_q, const int *pair_f0,
-                          uint4 *dist, int64_t cap, uint8_t *mins, int64_t min_stride, int signd,
-                          int order, int n_blocks, hipStream_t s, int form)
+void tk_launch_scan_units(const TkScanJob &j, int M, int64_t nq, int S, int signd, int order, int n_blocks,
+                          hipStream_t s, int form)
 {
     if (nq == 0 || S == 0) return;
     const int P = M / 2;
-    const bool coarse = n_lists == 1 && S == 1;
+    const bool coarse = j.n_lists == 1 && S == 1;
     form = form < 0 || form > 2 ? 0 : form;
     const int gmax = scan_form_gmax(M, form);
     const size_t lds = (size_t)4 * gmax * TK_UNIT_Q * M * 16;
@@ -1087,8 +1084,8 @@ void tk_launch_scan_units(const uint4 *codes, int M, const uint4 *tables, int64_
         static bool attr_ = false;                                                               \
         if (F_ != 0 && !attr_) { lds_attr(scan_units_kernel<O, S_, F_, C_>); attr_ = true; }     \
         hipLaunchKernelGGL((scan_units_kernel<O, S_, F_, C_>), dim3(n_blocks), dim3(256), lds, s, \
-                           codes, P, tables, M, list_chunk_off, (int)n_lists, unit_prefix, pair_off, \
-                           pair_q, pair_f0, dist, cap, mins, min_stride, gmax);                      \
+                           j.codes, P, j.tables, M, j.list_chunk_off, j.n_lists, j.unit_prefix,       \
+                           j.pair_off, j.pair_q, j.pair_f0, j.dist, j.cap, j.mins, j.min_stride, gmax);   \
     } while (0)
 #define TK_LAUNCH2(O, S_, C_)                                          \
     do {                                                               \

@@ -366,10 +366,10 @@ extern "C" int tk_codes_estimate_dev(tk_codes *c, const void *tables_dev, int64_
         tk_launch_identity_pairs(nq, (int)c->chunks, c->pair_off.as<int>(),
                                  c->unit_prefix.as<int>(), c->pair_q.as<int>(),
                                  c->pair_f0.as<int>(), st);
-        tk_launch_scan_units(c->tiled.as<uint4>(), c->M, (const uint4 *)tables_dev, nq, 1, 1,
-                             c->chunk_off.as<int64_t>(), c->pair_off.as<int>(),
-                             c->unit_prefix.as<int>(), c->pair_q.as<int>(), c->pair_f0.as<int>(),
-                             (uint4 *)out_dev, c->chunks, nullptr, 0, signd, order, 768, st);
+        const TkScanJob j = {c->tiled.as<uint4>(), (const uint4 *)tables_dev, c->chunk_off.as<int64_t>(), 1,
+                             c->unit_prefix.as<int>(), c->pair_off.as<int>(), c->pair_q.as<int>(),
+                             c->pair_f0.as<int>(), (uint4 *)out_dev, c->chunks, nullptr, 0};     // one list, no minima
+        tk_launch_scan_units(j, c->M, nq, 1, signd, order, 768, st);
     } else {
         tk_launch_scan_flat(c->tiled.as<uint4>(), c->chunks, c->M, (const uint4 *)tables_dev, nq,
                             (uint4 *)out_dev, c->chunks, nullptr, 0, signd, order, st);

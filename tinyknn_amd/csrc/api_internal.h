@@ -4,6 +4,8 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <deque>
+#include <memory>
 #include <mutex>
 #include <stdlib.h>
 #include <string.h>
@@ -241,13 +243,10 @@ struct tk_index {
     uint64_t calls = 0;
     std::vector<hipStream_t> lat_streams;    // `depth` of them (pipelined mode)
     hipEvent_t ev_in = nullptr;              // caller's stream -> a batch's stream
-    std::vector<struct Pending *> pending;   // calls whose list scan is still to be enqueued (<= 2)
+    std::deque<std::unique_ptr<Pending>> pending;   // batches whose list scan is still to be enqueued (up to 3 between calls)
     uint64_t ev_seq = 0;                     // counts the records of tables_done / front_done (pipeline_step's merged wait)
     int coalesce = 1;                        // 2: two consecutive calls run as ONE batch (tk_index_set_coalesce)
-    struct Pending *held = nullptr;          // ... the first of such a pair, its inputs copied, waiting for the second
-    int held_n_probes = 0, held_pass_1 = 0, held_f64 = 0;
-    int64_t held_rows = 0;                   // rows its staging buffers hold
-    hipStream_t held_stt = nullptr, held_caller = nullptr;
+    std::unique_ptr<Pending> held;           // ... the first of such a pair, waiting for the second
     hipStream_t front_stream = nullptr;      // coarse replays + descriptors of all batches, in order
     // profiling: one set of 8 events per recorded batch, read back on demand
     int profiling = 0;

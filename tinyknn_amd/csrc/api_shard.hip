@@ -272,10 +272,7 @@ static TkScanJob to_send(TkScanJob j, const tk_index *ix, const Work &w, void *s
 static void exact_to_send(const tk_index *ix, const ShardCall &c, int64_t nq, void *send_dev)
 {
     const Work &w = *c.w;
-    tk_launch_scan_units(ix->codes.as<uint4>(), ix->M, tables_of(w), nq, c.p.S, ix->n_lists,
-                         ix->local_chunk_off.as<int64_t>(), w.u_pair_off.as<int>(),
-                         w.u_unit_prefix.as<int>(), w.u_pair_q.as<int>(), w.u_pair_f0.as<int>(),
-                         (uint4 *)send_dev, 0, w.smins.as<uint8_t>(), 0, 1, ix->order, 768, c.st);
+    tk_launch_scan_units(to_send(list_job(ix, w, c.p), ix, w, send_dev), ix->M, nq, c.p.S, 1, ix->order, 768, c.st);
 }
 
 extern "C" int tk_index_shard_scan_dev(tk_index *ix, int slot, const float *q_dev,

@@ -132,11 +132,8 @@ void tk_launch_unit_pairs2(int64_t nq, const int64_t *probes, int S, int64_t n_l
 // of one batch and the coarse scan of the next); signed tables
 void tk_launch_scan_units2(const TkScanJob &a, const TkScanJob &b, int M, int order, int n_blocks,
                            hipStream_t s, const TkScanJob *c = nullptr, int form = 0);
-void tk_launch_scan_units(const uint4 *codes, int M, const uint4 *tables, int64_t nq, int S,
-                          int64_t n_lists, const int64_t *list_chunk_off, const int *pair_off,
-                          const int *unit_prefix, const int *pair_q, const int *pair_f0,
-                          uint4 *dist, int64_t cap, uint8_t *mins, int64_t min_stride, int signd,
-                          int order, int n_blocks, hipStream_t s, int form = 0);
+void tk_launch_scan_units(const TkScanJob &j, int M, int64_t nq, int S, int signd, int order, int n_blocks,
+                          hipStream_t s, int form = 0);
 
 // ---- heap replays: the reference's sequential heap (_fast_pq_256.pyx:73-123) over precomputed distances ----
 // Position entries (value8 << 24 | flat position24) hold every code of a distance row of `chunks` chunks
