@@ -405,6 +405,36 @@ int tk_index_export_lists(tk_index *ix, int64_t *list_sizes, uint64_t *codes, in
 int tk_index_export_centers(tk_index *ix, float *active_centers, uint64_t *center_codes);
 int tk_index_read_rows(tk_index *ix, const int64_t *rows, int64_t n, float *out);
 
+/* ---- rows added to a built index, in place (IVF.add) ----------------------------------------
+ * tk_index_add_rows appends n rows with ids N .. N + n - 1 and leaves the index exactly as the
+ * index's own build over (old rows, new rows) would: a row's code and lists do not depend on the
+ * other rows.  Every list keeps its old members at their old positions inside their column
+ * block: with kp lists per row (the build's n_probes) list l's column-j block becomes
+ * old_j ++ new_j, new_j = the new rows whose nearest[:, j] is l in ASCENDING row order (for
+ * kp >= 2 new column-0 members land in the middle of a list, before the old column-1 members,
+ * where group_data_by_indices puts them).  An index made by tk_index_build_dev over N + n rows
+ * is byte-identical; against a host build (numpy's unstable argsort) the order inside a kp = 1
+ * list is unspecified, as there.  Padding rows carry the zero vector's code.
+ *   rows: (n, d) float32, or float64 (rows_is_f64) where the index's vectors are float64; host
+ *     or device memory.  normalise != 0: divided by their norm on the device first (float32).
+ *   nearest (n, kp) int64 centre ids, or NULL: found on the device as tk_index_build_dev finds
+ *     them (all_centers / search_centers / ynorm2 / C as there).
+ *   labels (n, M) uint8 PQ labels, or NULL: encoded on the device as tk_index_build_dev does.
+ *   list_columns (n_lists, kp) int64 members per (list, column) of the old lists, or NULL where the
+ *     index knows them (tk_index_build_dev, an earlier add: tk_index_list_columns).
+ *   C: centres; new rows may activate centres n_lists .. only so that the active ones stay a prefix
+ *     (the build's contract, utils.py:128; else TK_ERR_ARG).  New lists are appended, their centres
+ *     (rows of all_centers) coded by center_codes ((ceil(L'/16), M) uint64 packed, host) or, NULL,
+ *     on the device.  n_active_out: number of lists afterwards.
+ * Batches in flight are completed first; allowed sets made before fail afterwards (a new layout).
+ * A refused or failed call leaves the index as it was.  A list-sharded index is refused.
+ * tk_index_list_columns: *kp = columns known (0: none, a host upload), counts (n_lists, kp). */
+int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64, int64_t n, int kp,
+                      const int64_t *nearest, const uint8_t *labels, const int64_t *list_columns,
+                      int normalise, const float *all_centers, const float *search_centers,
+                      const float *ynorm2, int64_t C, const uint64_t *center_codes, int64_t *n_active_out);
+int tk_index_list_columns(tk_index *ix, int *kp, int64_t *counts);
+
 /* ---- device front end, "fast mode"  -----------------------------------
  * What IVF.query does on the host before the table build (ivf.py:125-128,
  * fast_pq.py:200-204): float32 normalisation for the angular metric, zero padding to dq,

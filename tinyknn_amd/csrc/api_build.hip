@@ -91,6 +91,99 @@ static int encode_rows_dev(tk_index *ix, const float *x, int64_t m, DevBuf &rows
     return TK_OK;
 }
 
+// what tk_launch_assign reads: the search centres transposed (d, C) and their einsum norms
+static int upload_search_centres(DevBuf &yt, DevBuf &yn, const float *search_centers, const float *ynorm2,
+                                 int64_t C, int d)
+{
+    std::vector<float> ytv((size_t)C * d);
+    for (int64_t j = 0; j < C; j++)
+        for (int t = 0; t < d; t++) ytv[(size_t)t * C + j] = search_centers[(size_t)j * d + t];
+    TRY(yt.ensure(ytv.size() * 4));
+    TRY(yn.ensure((size_t)C * 4));
+    HIPCHECK(hipMemcpy(yt.p, ytv.data(), ytv.size() * 4, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(yn.p, ynorm2, (size_t)C * 4, hipMemcpyHostToDevice));
+    return TK_OK;
+}
+
+// the n_probes nearest centres of m float32 rows on the device (ivf.py:85), normalised in place first
+// (ivf.py:78-79) where `normalise`; slabs of 2^20 rows, as the build has always cut them
+static void assign_rows_dev(float *X, int64_t m, int d, int normalise, const DevBuf &yt, const DevBuf &yn,
+                            int64_t C, int kp, int64_t *nearest)
+{
+    const int64_t slab = 1 << 20;
+    for (int64_t o = 0; o < m; o += slab) {
+        const int64_t s = m - o < slab ? m - o : slab;
+        if (normalise) tk_launch_normalise_rows(X + o * d, s, d, X + o * d, 0);
+        tk_launch_assign(X + o * d, s, d, yt.p, yn.p, 0, (int)C, kp, nearest + o * kp, 0);
+    }
+}
+
+// stable sort of T (list, row) pairs by list (L lists): with kp lists per row, the column blocks of
+// the pair arrays keep column 0 before column 1 ... inside every list (utils.py:131-150)
+static int sort_pairs_dev(DevBuf &keys, DevBuf &rows, DevBuf &keys2, DevBuf &rows2, DevBuf &tmp, int64_t T,
+                          int64_t L)
+{
+    int bits = 1;
+    while ((1ll << bits) < L) bits++;
+    TRY(keys2.ensure((size_t)T * 4));
+    TRY(rows2.ensure((size_t)T * 4));
+    size_t tmp_bytes = 0;
+    if (tk_sort_pairs(nullptr, &tmp_bytes, keys.as<int>(), keys2.as<int>(), rows.as<int>(), rows2.as<int>(), T, bits, 0))
+        return fail(TK_ERR_HIP, "radix sort: size query failed");
+    TRY(tmp.ensure(tmp_bytes > 0 ? tmp_bytes : 16));
+    if (tk_sort_pairs(tmp.p, &tmp_bytes, keys.as<int>(), keys2.as<int>(), rows.as<int>(), rows2.as<int>(), T, bits, 0))
+        return fail(TK_ERR_HIP, "radix sort failed");
+    return TK_OK;
+}
+
+// PQ codes of the L active centres (ivf.py:92-96), packed into `codes` as one tiled list of
+// ceil(L / 16) chunks; the code of the zero vector (list padding, fast_pq.py:165) is left at
+// clab + ceil16(L) * M
+static int encode_centres(tk_index *ix, const float *act, int64_t L, DevBuf &rot, DevBuf &crow, DevBuf &clab,
+                          DevBuf &offs, DevBuf &codes, const uint8_t **zero_code)
+{
+    const int d = ix->d, M = ix->M, P = M / 2;
+    const int64_t L16 = (L + 15) / 16 * 16, cc = L16 / 16;
+    TRY(crow.ensure((size_t)(L16 + 16) * d * 4));
+    TRY(clab.ensure((size_t)(L16 + 16) * M));
+    HIPCHECK(hipMemset(crow.p, 0, (size_t)(L16 + 16) * d * 4));
+    if (L > 0) HIPCHECK(hipMemcpy(crow.p, act, (size_t)L * d * 4, hipMemcpyHostToDevice));
+    TRY(encode_rows_dev(ix, crow.as<float>(), L16 + 16, rot, clab.as<uint8_t>()));
+    *zero_code = clab.as<uint8_t>() + (size_t)L16 * M;
+    const size_t bytes = (size_t)tk_tiled_uint4s(cc, P) * 16;
+    TRY(codes.ensure(bytes > 0 ? bytes : 16));
+    HIPCHECK(hipMemset(codes.p, 0, bytes > 0 ? bytes : 16));
+    const int64_t o[5] = {0, cc, 0, L, L};      // chunk offsets, id offsets, size of the one list
+    TRY(offs.ensure(sizeof o));
+    HIPCHECK(hipMemcpy(offs.p, o, sizeof o, hipMemcpyHostToDevice));
+    tk_launch_pack_lists(clab.as<uint8_t>(), M, nullptr, offs.as<int64_t>() + 2, offs.as<int64_t>(),
+                         offs.as<int64_t>() + 4, 1, *zero_code, codes.as<uint4>(), cc, 0);
+    HIPCHECK(hipGetLastError());
+    return TK_OK;
+}
+
+// the coarse stage's descriptors of L coded centres in center_chunks chunks
+static int set_centre_slots(tk_index *ix, int64_t L, int64_t center_chunks)
+{
+    const int64_t cco[2] = {0, center_chunks};
+    const int ci[3] = {0, (int)center_chunks, (int)L};
+    const int64_t cl1[1] = {-1};
+    TRY(ix->c_chunk_off.ensure(sizeof cco));
+    TRY(ix->cslots_i.ensure(sizeof ci));
+    TRY(ix->cslots_l.ensure(sizeof cl1));
+    HIPCHECK(hipMemcpy(ix->c_chunk_off.p, cco, sizeof cco, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(ix->cslots_i.p, ci, sizeof ci, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(ix->cslots_l.p, cl1, sizeof cl1, hipMemcpyHostToDevice));
+    ix->n_lists = L;
+    ix->center_chunks = center_chunks;
+    return TK_OK;
+}
+
+struct BufCleanup {
+    std::vector<DevBuf *> v;
+    ~BufCleanup() { for (DevBuf *b : v) b->release(); }
+};
+
 extern "C" int tk_index_build_dev(tk_index *ix, int normalise, const float *all_centers,
                                   const float *search_centers, const float *ynorm2, int64_t C,
                                   int n_probes, const double *R, int d_pad, int64_t *n_active_out)
@@ -112,53 +205,45 @@ extern "C" int tk_index_build_dev(tk_index *ix, int normalise, const float *all_
     if (R) TRY(upload_rotation(ix, R, d_pad));
     else { ix->rot_t.release(); ix->rot_d_pad = 0; }
     const int64_t slab = 1 << 20;
-    DevBuf yt, yn, near, keys, rows, keys2, rows2, count, remap, labels, rot, tmp, zero, crow, clab;
-    struct Cleanup {
-        std::vector<DevBuf *> v;
-        ~Cleanup() { for (DevBuf *b : v) b->release(); }
-    } cl{{&yt, &yn, &near, &keys, &rows, &keys2, &rows2, &count, &remap, &labels, &rot, &tmp, &zero, &crow, &clab}};
+    DevBuf yt, yn, near, keys, rows, keys2, rows2, count, remap, labels, rot, tmp, crow, clab;
+    BufCleanup cl{{&yt, &yn, &near, &keys, &rows, &keys2, &rows2, &count, &remap, &labels, &rot, &tmp, &crow, &clab}};
     // ---- 1. data = X / |X| (ivf.py:78-79), nearest centre per row (ivf.py:85)
-    {
-        std::vector<float> ytv((size_t)C * d);
-        for (int64_t j = 0; j < C; j++)
-            for (int t = 0; t < d; t++) ytv[(size_t)t * C + j] = search_centers[(size_t)j * d + t];
-        TRY(yt.ensure(ytv.size() * 4));
-        TRY(yn.ensure((size_t)C * 4));
-        HIPCHECK(hipMemcpy(yt.p, ytv.data(), ytv.size() * 4, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(yn.p, ynorm2, (size_t)C * 4, hipMemcpyHostToDevice));
-    }
+    TRY(upload_search_centres(yt, yn, search_centers, ynorm2, C, d));
     const int64_t T = N * kp;           // (list, row) pairs: every row sits in kp lists
     TRY(near.ensure((size_t)slab * kp * 8));
     TRY(keys.ensure((size_t)T * 4));
     TRY(rows.ensure((size_t)T * 4));
-    TRY(count.ensure((size_t)C * 4));
-    HIPCHECK(hipMemset(count.p, 0, (size_t)C * 4));
+    TRY(count.ensure((size_t)C * kp * 4));
+    HIPCHECK(hipMemset(count.p, 0, (size_t)C * kp * 4));
     for (int64_t o = 0; o < N; o += slab) {
         const int64_t m = N - o < slab ? N - o : slab;
-        if (normalise) tk_launch_normalise_rows(X + o * d, m, d, X + o * d, 0);
-        tk_launch_assign(X + o * d, m, d, yt.p, yn.p, 0, (int)C, kp, near.as<int64_t>(), 0);
+        assign_rows_dev(X + o * d, m, d, normalise, yt, yn, C, kp, near.as<int64_t>());
         tk_launch_keys_count(near.as<int64_t>(), m, kp, o, N, keys.as<int>(), rows.as<int>(), count.as<int>(), 0);
         HIPCHECK(hipGetLastError());
     }
     HIPCHECK(hipDeviceSynchronize());
     // ---- 2. active centres (ivf.py:91: all_centers[np.unique(nearest)]) and the CSR offsets
-    std::vector<int> cnt((size_t)C), rm((size_t)C, -1);
-    HIPCHECK(hipMemcpy(cnt.data(), count.p, (size_t)C * 4, hipMemcpyDeviceToHost));
+    std::vector<int> cntc((size_t)C * kp), rm((size_t)C, -1);
+    HIPCHECK(hipMemcpy(cntc.data(), count.p, (size_t)C * kp * 4, hipMemcpyDeviceToHost));
     std::vector<float> act;
-    std::vector<int64_t> sizes;
-    for (int64_t j = 0; j < C; j++)
-        if (cnt[(size_t)j] > 0) {
+    std::vector<int64_t> sizes, cols;
+    for (int64_t j = 0; j < C; j++) {
+        int64_t c = 0;
+        for (int t = 0; t < kp; t++) c += cntc[(size_t)j * kp + t];
+        if (c > 0) {
             rm[(size_t)j] = (int)sizes.size();
-            sizes.push_back(cnt[(size_t)j]);
+            sizes.push_back(c);
+            cols.insert(cols.end(), cntc.begin() + j * kp, cntc.begin() + (j + 1) * kp);
             act.insert(act.end(), all_centers + (size_t)j * d, all_centers + (size_t)(j + 1) * d);
         }
+    }
     const int64_t L = (int64_t)sizes.size();
     {   // the reference groups the rows by RAW centre id into n_active lists and asserts
         // max(index) < n_active (utils.py:128, IVF.build -> group_data_by_indices): it only builds
         // when no empty centre precedes a used one.  Same contract here (the host build asserts too).
         int64_t last = -1;
         for (int64_t j = 0; j < C; j++)
-            if (cnt[(size_t)j] > 0) last = j;
+            if (rm[(size_t)j] >= 0) last = j;
         ARGCHECK(last < L, "a centre that received no row precedes one that did: the reference's "
                            "group_data_by_indices asserts max(index) < n_active (utils.py:128)");
     }
@@ -176,57 +261,22 @@ extern "C" int tk_index_build_dev(tk_index *ix, int normalise, const float *all_
     tk_launch_remap_keys(keys.as<int>(), T, remap.as<int>(), 0);
     // ---- 3. rows grouped by list: stable sort of (list, row); with two lists per row the
     //         column-0 pairs precede the column-1 pairs of every list (utils.py:131-150)
-    int bits = 1;
-    while ((1ll << bits) < L) bits++;
-    TRY(keys2.ensure((size_t)T * 4));
-    TRY(rows2.ensure((size_t)T * 4));
-    size_t tmp_bytes = 0;
-    if (tk_sort_pairs(nullptr, &tmp_bytes, keys.as<int>(), keys2.as<int>(), rows.as<int>(), rows2.as<int>(), T, bits, 0))
-        return fail(TK_ERR_HIP, "radix sort: size query failed");
-    TRY(tmp.ensure(tmp_bytes > 0 ? tmp_bytes : 16));
-    if (tk_sort_pairs(tmp.p, &tmp_bytes, keys.as<int>(), keys2.as<int>(), rows.as<int>(), rows2.as<int>(), T, bits, 0))
-        return fail(TK_ERR_HIP, "radix sort failed");
+    TRY(sort_pairs_dev(keys, rows, keys2, rows2, tmp, T, L));
     HIPCHECK(hipDeviceSynchronize());
     keys.release(); rows.release(); keys2.release(); tmp.release(); near.release();
-    // ---- 4. PQ codes of every row (a row's code does not depend on its list), of the zero
-    //         vector (list padding, fast_pq.py:165) and of the active centres (ivf.py:92-96)
+    // ---- 4. PQ codes of every row (a row's code does not depend on its list)
     TRY(labels.ensure((size_t)N * M));
     for (int64_t o = 0; o < N; o += slab) {
         const int64_t m = N - o < slab ? N - o : slab;
         TRY(encode_rows_dev(ix, X + o * d, m, rot, labels.as<uint8_t>() + (size_t)o * M));
     }
-    const int64_t L16 = (L + 15) / 16 * 16;
-    TRY(crow.ensure((size_t)(L16 + 16) * d * 4));
-    TRY(clab.ensure((size_t)(L16 + 16) * M));
-    HIPCHECK(hipMemset(crow.p, 0, (size_t)(L16 + 16) * d * 4));
-    HIPCHECK(hipMemcpy(crow.p, act.data(), (size_t)L * d * 4, hipMemcpyHostToDevice));
-    TRY(encode_rows_dev(ix, crow.as<float>(), L16 + 16, rot, clab.as<uint8_t>()));
-    const uint8_t *zero_code = clab.as<uint8_t>() + (size_t)L16 * M;     // code of a zero row
-    // ---- 5. the index: centres
+    // ---- 5. the index: centres, their codes and the zero vector's code (list padding)
+    const uint8_t *zero_code = nullptr;
+    TRY(encode_centres(ix, act.data(), L, rot, crow, clab, ix->stage, ix->center_codes, &zero_code));
     TRY(ix->active_centers.ensure((size_t)L * d * 4));
     HIPCHECK(hipMemcpy(ix->active_centers.p, act.data(), (size_t)L * d * 4, hipMemcpyHostToDevice));
-    const int64_t center_chunks = L16 / 16;
+    TRY(set_centre_slots(ix, L, (L + 15) / 16));
     const int P = M / 2;
-    TRY(ix->center_codes.ensure((size_t)tk_tiled_uint4s(center_chunks, P) * 16));
-    HIPCHECK(hipMemset(ix->center_codes.p, 0, (size_t)tk_tiled_uint4s(center_chunks, P) * 16));
-    int64_t cco[2] = {0, center_chunks};
-    int64_t cio[2] = {0, L};
-    int64_t cn[1] = {L};
-    TRY(ix->c_chunk_off.ensure(sizeof cco));
-    HIPCHECK(hipMemcpy(ix->c_chunk_off.p, cco, sizeof cco, hipMemcpyHostToDevice));
-    TRY(ix->stage.ensure(64));
-    HIPCHECK(hipMemcpy(ix->stage.p, cio, sizeof cio, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy((char *)ix->stage.p + 32, cn, sizeof cn, hipMemcpyHostToDevice));
-    tk_launch_pack_lists(clab.as<uint8_t>(), M, nullptr, ix->stage.as<int64_t>(), ix->c_chunk_off.as<int64_t>(),
-                         (const int64_t *)((char *)ix->stage.p + 32), 1, zero_code,
-                         ix->center_codes.as<uint4>(), center_chunks, 0);
-    ix->n_lists = L; ix->center_chunks = center_chunks;
-    int ci[3] = {0, (int)center_chunks, (int)L};
-    int64_t cl1[1] = {-1};
-    TRY(ix->cslots_i.ensure(sizeof ci));
-    TRY(ix->cslots_l.ensure(sizeof cl1));
-    HIPCHECK(hipMemcpy(ix->cslots_i.p, ci, sizeof ci, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ix->cslots_l.p, cl1, sizeof cl1, hipMemcpyHostToDevice));
     // ---- 6. the index: lists
     TRY(ix->list_chunk_off.ensure((size_t)(L + 1) * 8));
     TRY(ix->ids_off.ensure((size_t)(L + 1) * 8));
@@ -258,8 +308,217 @@ extern "C" int tk_index_build_dev(tk_index *ix, int normalise, const float *all_
     ix->max_list_chunks = (int)maxc;
     ix->have_centers = ix->have_lists = ix->have_data = true;
     ix->lists_gen++;
+    ix->list_cols = cols;
+    ix->list_kp = kp;
     TRY(build_twins(ix, N));
     if (n_active_out) *n_active_out = L;
+    return TK_OK;
+}
+
+extern "C" int tk_index_list_columns(tk_index *ix, int *kp, int64_t *counts)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix && ix->have_lists && kp, "an index with its lists");
+    *kp = ix->list_kp;
+    if (counts && ix->list_kp > 0)
+        memcpy(counts, ix->list_cols.data(), ix->list_cols.size() * sizeof(int64_t));
+    return TK_OK;
+}
+
+// New rows merged into the built lists (tinyknn_hip.h).  Everything is validated and built in new buffers
+// first; the index changes only at the end, where nothing can fail any more.
+extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64, int64_t n, int kp,
+                                 const int64_t *nearest, const uint8_t *labels, const int64_t *list_columns,
+                                 int normalise, const float *all_centers, const float *search_centers,
+                                 const float *ynorm2, int64_t C, const uint64_t *center_codes,
+                                 int64_t *n_active_out)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix && ix->have_pq && ix->have_centers && ix->have_lists && ix->have_data, "a complete index");
+    ARGCHECK(!ix->sharded, "a list-sharded index takes no rows");
+    ARGCHECK(n >= 0 && (n == 0 || rows), "rows");
+    ARGCHECK(kp >= 1 && kp <= 9, "kp (lists per row) must be 1 .. 9");
+    ARGCHECK(!rows_is_f64 == !ix->data_is_f64, "rows must have the dtype of the index's vectors");
+    ARGCHECK(ix->total_ids == ix->N * kp, "kp: every stored row sits in kp lists");
+    ARGCHECK(list_columns || ix->list_kp == kp,
+             "list_columns: the index does not know its members per (list, column) (a host upload)");
+    ARGCHECK(C >= ix->n_lists && C >= kp && C < (1ll << 31), "C: the number of centres");
+    ARGCHECK((ix->N + n) * kp < (1ll << 31), "(N + n) * kp < 2^31");
+    const int d = ix->d, M = ix->M, P = M / 2;
+    if (!search_centers) search_centers = all_centers;
+    ARGCHECK(nearest || (all_centers && ynorm2 && !rows_is_f64 && d <= 384 && (!normalise || d <= 128)),
+             "device assignment: all_centers + ynorm2, float32 rows, d <= 384 (128 with normalisation)");
+    ARGCHECK(!normalise || !rows_is_f64, "normalisation on the device: float32 rows");
+    ARGCHECK(labels || !rows_is_f64, "device encoding: float32 rows (else pass labels)");
+    ARGCHECK(16 % ix->dpb == 0, "dims_per_block must divide 16 for the device encoder");
+    if (nearest)
+        for (int64_t i = 0; i < n * kp; i++) ARGCHECK(nearest[i] >= 0 && nearest[i] < C, "nearest: a centre id");
+    if (n_active_out) *n_active_out = ix->n_lists;
+    if (n == 0) return TK_OK;
+    TRY(settle_lists(ix));
+    const int64_t L0 = ix->n_lists, N0 = ix->N, N1 = N0 + n;
+    // ---- the old layout: list sizes and members per column
+    std::vector<int64_t> size0((size_t)L0);
+    HIPCHECK(hipMemcpy(size0.data(), ix->list_n.p, (size_t)L0 * 8, hipMemcpyDeviceToHost));
+    std::vector<int64_t> cols0(list_columns ? list_columns : ix->list_cols.data(),
+                               (list_columns ? list_columns : ix->list_cols.data()) + L0 * kp);
+    for (int64_t l = 0; l < L0; l++) {
+        int64_t s = 0;
+        for (int t = 0; t < kp; t++) {
+            ARGCHECK(cols0[(size_t)(l * kp + t)] >= 0, "list_columns: negative count");
+            s += cols0[(size_t)(l * kp + t)];
+        }
+        ARGCHECK(s == size0[(size_t)l], "list_columns: a list's columns do not add up to its size");
+    }
+    const size_t esz = rows_is_f64 ? 8 : 4;
+    DevBuf grown, yt, yn, near, keys, prow, keys2, rows2, count, lab, rot, tmp, zrow, zlab, crow, clab, coffs,
+        act1, ccodes, codes1, ids1, ids32_1, coff_d, ioff_d, n_d, noff_d, seg_d;
+    BufCleanup cl{{&grown, &yt, &yn, &near, &keys, &prow, &keys2, &rows2, &count, &lab, &rot, &tmp, &zrow, &zlab,
+                   &crow, &clab, &coffs, &act1, &ccodes, &codes1, &ids1, &ids32_1, &coff_d, &ioff_d, &n_d,
+                   &noff_d, &seg_d}};
+    // ---- 1. the rows behind the old ones (a larger buffer where they do not fit: the old one stays intact)
+    void *base = ix->data.p;
+    if ((size_t)N1 * d * esz > ix->data.cap) {
+        TRY(grown.ensure((size_t)N1 * d * esz));
+        HIPCHECK(hipMemcpy(grown.p, ix->data.p, (size_t)N0 * d * esz, hipMemcpyDeviceToDevice));
+        base = grown.p;
+    }
+    void *Xn = (char *)base + (size_t)N0 * d * esz;
+    HIPCHECK(hipMemcpy(Xn, rows, (size_t)n * d * esz, hipMemcpyDefault));
+    // ---- 2. nearest centres (given, or as tk_index_build_dev finds them), pairs per (centre, column)
+    const int64_t T = n * kp;
+    TRY(near.ensure((size_t)T * 8));
+    if (nearest) {
+        HIPCHECK(hipMemcpy(near.p, nearest, (size_t)T * 8, hipMemcpyHostToDevice));
+        if (normalise) tk_launch_normalise_rows((float *)Xn, n, d, (float *)Xn, 0);
+    } else {
+        TRY(upload_search_centres(yt, yn, search_centers, ynorm2, C, d));
+        assign_rows_dev((float *)Xn, n, d, normalise, yt, yn, C, kp, near.as<int64_t>());
+    }
+    TRY(keys.ensure((size_t)T * 4));
+    TRY(prow.ensure((size_t)T * 4));
+    TRY(count.ensure((size_t)C * kp * 4));
+    HIPCHECK(hipMemset(count.p, 0, (size_t)C * kp * 4));
+    tk_launch_keys_count(near.as<int64_t>(), n, kp, 0, n, keys.as<int>(), prow.as<int>(), count.as<int>(), 0);
+    HIPCHECK(hipGetLastError());
+    std::vector<int> cntc((size_t)C * kp);
+    HIPCHECK(hipMemcpy(cntc.data(), count.p, (size_t)C * kp * 4, hipMemcpyDeviceToHost));
+    // ---- 3. the active centres stay a prefix 0 .. L1 - 1 (the build's contract, utils.py:128)
+    int64_t L1 = 0, last = -1;
+    for (int64_t j = 0; j < C; j++) {
+        int64_t c = 0;
+        for (int t = 0; t < kp; t++) c += cntc[(size_t)(j * kp + t)];
+        if (j < L0 || c > 0) {
+            L1++;
+            last = j;
+        }
+    }
+    ARGCHECK(last < L1, "a centre that received no row precedes one that did: the reference's "
+                        "group_data_by_indices asserts max(index) < n_active (utils.py:128)");
+    ARGCHECK(L1 == L0 || all_centers, "new lists: all_centers");
+    // ---- 4. the new layout: list l's column block j = old_j ++ new_j
+    std::vector<int64_t> coff((size_t)L1 + 1, 0), ioff((size_t)L1 + 1, 0), size1((size_t)L1), noff((size_t)L1 + 1, 0),
+        seg((size_t)L1 * kp * 2), cols1((size_t)L1 * kp);
+    int64_t maxc = 0;
+    for (int64_t l = 0; l < L1; l++) {
+        int64_t s = 0, sn = 0;
+        for (int t = 0; t < kp; t++) {
+            const int64_t o = l < L0 ? cols0[(size_t)(l * kp + t)] : 0, nn = cntc[(size_t)(l * kp + t)];
+            seg[(size_t)(l * kp + t) * 2] = o;
+            seg[(size_t)(l * kp + t) * 2 + 1] = nn;
+            cols1[(size_t)(l * kp + t)] = o + nn;
+            s += o + nn;
+            sn += nn;
+        }
+        size1[(size_t)l] = s;
+        const int64_t c = (s + 15) / 16;
+        coff[(size_t)l + 1] = coff[(size_t)l] + c;
+        ioff[(size_t)l + 1] = ioff[(size_t)l] + s;
+        noff[(size_t)l + 1] = noff[(size_t)l] + sn;
+        if (c > maxc) maxc = c;
+    }
+    ARGCHECK(maxc < (1ll << 26), "list too long");
+    const int64_t chunks1 = coff[(size_t)L1], T1 = ioff[(size_t)L1];
+    // ---- 5. new pairs grouped by list (centre ids are list ids: the active set is a prefix)
+    TRY(sort_pairs_dev(keys, prow, keys2, rows2, tmp, T, L1));
+    // ---- 6. codes of the new rows (given, or as the build encodes them), of the zero vector, of new centres
+    TRY(lab.ensure((size_t)n * M));
+    if (labels) {
+        HIPCHECK(hipMemcpy(lab.p, labels, (size_t)n * M, hipMemcpyHostToDevice));
+    } else {
+        const int64_t slab = 1 << 20;
+        for (int64_t o = 0; o < n; o += slab)
+            TRY(encode_rows_dev(ix, (const float *)Xn + o * d, n - o < slab ? n - o : slab, rot,
+                                lab.as<uint8_t>() + (size_t)o * M));
+    }
+    TRY(zrow.ensure((size_t)16 * d * 4));
+    TRY(zlab.ensure((size_t)16 * M));
+    HIPCHECK(hipMemset(zrow.p, 0, (size_t)16 * d * 4));
+    TRY(encode_rows_dev(ix, zrow.as<float>(), 16, rot, zlab.as<uint8_t>()));
+    if (L1 > L0) {
+        TRY(act1.ensure((size_t)L1 * d * 4));
+        HIPCHECK(hipMemcpy(act1.p, all_centers, (size_t)L1 * d * 4, hipMemcpyHostToDevice));
+        if (center_codes) {         // the host's codes (pq.transform(active_centers)), retiled
+            const int64_t cc = (L1 + 15) / 16;
+            TRY(coffs.ensure((size_t)cc * M * 8));
+            TRY(ccodes.ensure((size_t)tk_tiled_uint4s(cc, P) * 16));
+            HIPCHECK(hipMemcpy(coffs.p, center_codes, (size_t)cc * M * 8, hipMemcpyHostToDevice));
+            tk_launch_retile(coffs.as<uint4>(), ccodes.as<uint4>(), cc, P, 0);
+            HIPCHECK(hipGetLastError());
+        } else {
+            const uint8_t *zc = nullptr;
+            TRY(encode_centres(ix, all_centers, L1, rot, crow, clab, coffs, ccodes, &zc));
+        }
+    }
+    // ---- 7. the merged lists
+    TRY(coff_d.ensure((size_t)(L1 + 1) * 8));
+    TRY(ioff_d.ensure((size_t)(L1 + 1) * 8));
+    TRY(n_d.ensure((size_t)L1 * 8));
+    TRY(noff_d.ensure((size_t)(L1 + 1) * 8));
+    TRY(seg_d.ensure(seg.size() * 8));
+    HIPCHECK(hipMemcpy(coff_d.p, coff.data(), coff.size() * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(ioff_d.p, ioff.data(), ioff.size() * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(n_d.p, size1.data(), size1.size() * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(noff_d.p, noff.data(), noff.size() * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(seg_d.p, seg.data(), seg.size() * 8, hipMemcpyHostToDevice));
+    const size_t tiled_bytes = (size_t)tk_tiled_uint4s(chunks1, P) * 16;
+    TRY(codes1.ensure(tiled_bytes));
+    HIPCHECK(hipMemset(codes1.p, 0, tiled_bytes));
+    TRY(ids1.ensure((size_t)T1 * 8));
+    if (kp > 1) TRY(ids32_1.ensure((size_t)T1 * 4));
+    tk_launch_merge_lists(ix->codes.as<uint4>(), ix->list_chunk_off.as<int64_t>(), ix->ids_off.as<int64_t>(),
+                          ix->ids.as<int64_t>(), lab.as<uint8_t>(), M, rows2.as<int>(), noff_d.as<int64_t>(),
+                          seg_d.as<int64_t>(), kp, coff_d.as<int64_t>(), ioff_d.as<int64_t>(), n_d.as<int64_t>(),
+                          (int)L1, zlab.as<uint8_t>(), N0, codes1.as<uint4>(), ids1.as<int64_t>(),
+                          kp > 1 ? ids32_1.as<int32_t>() : nullptr, chunks1, 0);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    // ---- 8. the swap: the old buffers go with the cleanup
+    std::swap(ix->codes, codes1);
+    std::swap(ix->ids, ids1);
+    std::swap(ix->list_chunk_off, coff_d);
+    std::swap(ix->ids_off, ioff_d);
+    std::swap(ix->list_n, n_d);
+    if (kp > 1) std::swap(ix->ids32, ids32_1);
+    else ix->ids32.release();
+    if (grown.p) std::swap(ix->data, grown);
+    if (L1 > L0) {
+        std::swap(ix->active_centers, act1);
+        std::swap(ix->center_codes, ccodes);
+        TRY(set_centre_slots(ix, L1, (L1 + 15) / 16));     // (buffers of a few bytes that already exist)
+    }
+    ix->N = N1;
+    ix->total_chunks = chunks1;
+    ix->total_ids = T1;
+    ix->max_list_chunks = (int)maxc;
+    ix->ids_unique = kp == 1;
+    ix->labels24 = N1 - 1 < 0x00ffffff;
+    ix->have_ids32 = kp > 1;
+    ix->lists_gen++;
+    ix->list_cols = cols1;
+    ix->list_kp = kp;
+    TRY(build_twins(ix, N1));
+    if (n_active_out) *n_active_out = L1;
     return TK_OK;
 }
 

@@ -311,6 +311,8 @@ static int set_lists_impl(tk_index *ix, const int64_t *list_sizes, const uint64_
     ix->max_list_chunks = (int)maxc;
     ix->have_lists = true;
     ix->lists_gen++;
+    ix->list_cols.clear();
+    ix->list_kp = 0;
     {   // labels that repeat: where every row's other copies are (the lane replay's duplicate test)
         int64_t mx = -1, mn = 0;
         for (int64_t i = 0; i < ioff[L]; i++) {
@@ -1696,6 +1698,16 @@ static int settle(tk_index *ix)
     if (ix->plain_state == PLAIN_WAIT) ix->plain_state = PLAIN_PROBE;
     for (Work &w : ix->works) w.busy = false;
     ix->calls = 0;
+    return TK_OK;
+}
+
+int settle_lists(tk_index *ix)
+{
+    TRY(settle(ix));
+    ix->plain_state = PLAIN_PROBE;      // (a verdict on the old layout says nothing about the new one)
+    ix->plain_skip = 0;
+    ix->plain_wait = 0;
+    ix->plain_backoff = 256;
     return TK_OK;
 }
 

@@ -199,6 +199,11 @@ struct tk_index {
     int64_t total_chunks = 0, total_ids = 0;
     int max_list_chunks = 0;
     uint64_t lists_gen = 0;    // counts the times the lists were (re-)set: an allowed set is valid for one layout
+    // members per (list, column of nearest): list l holds its column-0 members first, then column 1's, ...
+    // (group_data_by_indices); known after tk_index_build_dev / tk_index_add_rows (list_kp = columns), not
+    // after a host upload (list_kp = 0: tk_index_add_rows takes them from the caller)
+    std::vector<int64_t> list_cols;
+    int list_kp = 0;
     bool ids_unique = false;   // no label occurs twice => the lane-per-query replay is exact
     int heap_mode = 0;         // 0 auto (pair for small batches, lanes, else packed wave), 1 general wave, 2 packed wave, 3 pair
     int opt_pair_nq = 8192;    // TK_OPT_PAIR_NQ: batches up to this many queries take the wave-per-query register heap
@@ -312,6 +317,8 @@ inline const uint4 *tables_of(const Work &w) { return w.tables.as<uint4>(); }
 
 // ---- api_index.hip, used by the other files
 int flush_pending(tk_index *ix);
+// nothing in flight, the device idle, the automatic plain-scan state back to its first probe: the lists may change
+int settle_lists(tk_index *ix);
 // the twin table of an index whose int32 labels (all in [0, label_bound)) are in place; no table (twin_w = 0) where
 // the labels are distinct, too sparse, or one label has more than 16 copies
 int build_twins(tk_index *ix, int64_t label_bound);

@@ -65,10 +65,10 @@ void tk_launch_synth_rows(float *X, int64_t row0, int64_t n, int d, uint64_t see
 }
 
 // ---------------------------------------------------------------------------
-// nearest (n, kp) int64 of a slab -> sort keys / values + the per-centre histogram.  Column j of
-// the rows goes to block j of the pair arrays (block stride N): group_data_by_indices
-// (utils.py:131-150) appends a list's column-0 members first, then its column-1 members, and a
-// stable sort of the pairs by list keeps exactly that order.
+// nearest (n, kp) int64 of a slab -> sort keys / values + the per-(centre, column) histogram
+// count[centre * kp + j].  Column j of the rows goes to block j of the pair arrays (block stride N):
+// group_data_by_indices (utils.py:131-150) appends a list's column-0 members first, then its
+// column-1 members, and a stable sort of the pairs by list keeps exactly that order.
 __global__ void keys_count_kernel(const int64_t *__restrict__ nearest, int64_t n, int kp, int64_t row0,
                                   int64_t N, int *__restrict__ keys, int *__restrict__ rows,
                                   int *__restrict__ count)
@@ -80,7 +80,7 @@ __global__ void keys_count_kernel(const int64_t *__restrict__ nearest, int64_t n
     const int k = (int)nearest[i];
     keys[(int64_t)j * N + row0 + r] = k;
     rows[(int64_t)j * N + row0 + r] = (int)(row0 + r);
-    atomicAdd(&count[k], 1);
+    atomicAdd(&count[(int64_t)k * kp + j], 1);
 }
 
 void tk_launch_keys_count(const int64_t *nearest, int64_t n, int kp, int64_t row0, int64_t N, int *keys,
@@ -304,6 +304,98 @@ void tk_launch_pack_lists(const uint8_t *labels, int M, const int *rows_sorted, 
     if (items <= 0) return;
     hipLaunchKernelGGL(pack_lists_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, labels, M,
                        rows_sorted, ids_off, chunk_off, list_n, n_lists, zero_code, tiled, total_chunks);
+}
+
+// New rows merged into built lists (tk_index_add_rows): list l's column-j block becomes old_j ++ new_j.
+// seg[(l * kp + j) * 2 + {0, 1}] = (old, new) members of that block; the old ones sit at list positions
+// sum_{j' < j} old_j' of the old layout (old_chunk_off / old_ids_off; lists past the old ones have none),
+// the new ones at sorted-pair positions new_off[l] + sum_{j' < j} new_j' (rows_sorted: new row numbers,
+// grouped by list, column blocks in order, rows ascending — tk_sort_pairs' output).  One thread per
+// (output chunk, block pair), as pack_lists_kernel: output row r of the chunk finds its segment and
+// copies the packed byte of its old position, or packs labels_new[row][2p .. 2p + 1]; nothing old is
+// decoded or re-encoded.  The p == 0 thread of a chunk also writes the chunk's ids (old labels, or
+// n_old + new row) and their int32 copy (ids32 may be NULL).
+__global__ void merge_lists_kernel(const uint4 *__restrict__ old_tiled, const int64_t *__restrict__ old_chunk_off,
+                                   const int64_t *__restrict__ old_ids_off, const int64_t *__restrict__ old_ids,
+                                   const uint8_t *__restrict__ labels_new, int M, const int *__restrict__ rows_sorted,
+                                   const int64_t *__restrict__ new_off, const int64_t *__restrict__ seg, int kp,
+                                   const int64_t *__restrict__ chunk_off, const int64_t *__restrict__ ids_off,
+                                   const int64_t *__restrict__ list_n, int n_lists, const uint8_t *__restrict__ zero_code,
+                                   int64_t n_old, uint4 *__restrict__ tiled, int64_t *__restrict__ ids,
+                                   int32_t *__restrict__ ids32, int64_t total_chunks)
+{
+    const int P = M >> 1;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total_chunks * P) return;
+    const int64_t c = i / P;
+    const int p = (int)(i - c * P);
+    int lo = 0, hi = n_lists;   // chunk_off[lo] <= c < chunk_off[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (chunk_off[mid] <= c) lo = mid; else hi = mid;
+    }
+    const int64_t pos0 = 16 * (c - chunk_off[lo]);
+    const int64_t n_l = list_n[lo];
+    const int64_t *sg = seg + (int64_t)lo * kp * 2;
+    const uint32_t zb = (uint32_t)zero_code[2 * p] | ((uint32_t)zero_code[2 * p + 1] << 4);
+    uint32_t w[4] = {0, 0, 0, 0};
+    int64_t cur_oc = -1;                  // the old chunk held in `cur` (consecutive rows mostly share one)
+    uint4 cur = make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        uint32_t b = zb;
+        const int64_t pos = pos0 + r;
+        if (pos < n_l) {
+            int64_t q = pos, obase = 0, nbase = new_off[lo];
+            int64_t old_pos = -1, new_at = -1;
+            for (int t = 0; t < kp; t++) {
+                const int64_t o = sg[2 * t], nn = sg[2 * t + 1];
+                if (q < o) { old_pos = obase + q; break; }
+                q -= o;
+                if (q < nn) { new_at = nbase + q; break; }
+                q -= nn;
+                obase += o;
+                nbase += nn;
+            }
+            int64_t label = -1;
+            if (old_pos >= 0) {
+                const int64_t oc = old_chunk_off[lo] + (old_pos >> 4);
+                if (oc != cur_oc) {
+                    cur = old_tiled[((oc >> 3) * P + p) * 8 + (oc & 7)];
+                    cur_oc = oc;
+                }
+                const int rr = (int)(old_pos & 15);
+                const uint32_t word = rr < 4 ? cur.x : (rr < 8 ? cur.y : (rr < 12 ? cur.z : cur.w));
+                b = (word >> (8 * (rr & 3))) & 0xffu;
+                if (p == 0) label = old_ids[old_ids_off[lo] + old_pos];
+            } else if (new_at >= 0) {
+                const int64_t row = rows_sorted[new_at];
+                const uint8_t *lab = labels_new + row * M + 2 * p;
+                b = (uint32_t)lab[0] | ((uint32_t)lab[1] << 4);
+                if (p == 0) label = n_old + row;
+            }
+            if (p == 0) {
+                ids[ids_off[lo] + pos] = label;
+                if (ids32) ids32[ids_off[lo] + pos] = (int32_t)label;
+            }
+        }
+        w[r >> 2] |= b << (8 * (r & 3));
+    }
+    tiled[((c >> 3) * P + p) * 8 + (c & 7)] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+void tk_launch_merge_lists(const uint4 *old_tiled, const int64_t *old_chunk_off, const int64_t *old_ids_off,
+                           const int64_t *old_ids, const uint8_t *labels_new, int M, const int *rows_sorted,
+                           const int64_t *new_off, const int64_t *seg, int kp, const int64_t *chunk_off,
+                           const int64_t *ids_off, const int64_t *list_n, int n_lists, const uint8_t *zero_code,
+                           int64_t n_old, uint4 *tiled, int64_t *ids, int32_t *ids32, int64_t total_chunks,
+                           hipStream_t s)
+{
+    const int64_t items = total_chunks * (M / 2);
+    if (items <= 0) return;
+    hipLaunchKernelGGL(merge_lists_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, old_tiled,
+                       old_chunk_off, old_ids_off, old_ids, labels_new, M, rows_sorted, new_off, seg, kp, chunk_off,
+                       ids_off, list_n, n_lists, zero_code, n_old, tiled, ids, ids32, total_chunks);
 }
 
 // rows of a float32 (N, d) matrix gathered by id (rescoring vectors for the checker)

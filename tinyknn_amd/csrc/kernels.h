@@ -422,6 +422,13 @@ void tk_launch_widen_ids(const int *rows, int64_t n, int64_t *ids, hipStream_t s
 void tk_launch_pack_lists(const uint8_t *labels, int M, const int *rows_sorted, const int64_t *ids_off,
                           const int64_t *chunk_off, const int64_t *list_n, int n_lists,
                           const uint8_t *zero_code, uint4 *tiled, int64_t total_chunks, hipStream_t s);
+// built lists + new rows -> the merged lists (tk_index_add_rows; devbuild.hip merge_lists_kernel)
+void tk_launch_merge_lists(const uint4 *old_tiled, const int64_t *old_chunk_off, const int64_t *old_ids_off,
+                           const int64_t *old_ids, const uint8_t *labels_new, int M, const int *rows_sorted,
+                           const int64_t *new_off, const int64_t *seg, int kp, const int64_t *chunk_off,
+                           const int64_t *ids_off, const int64_t *list_n, int n_lists, const uint8_t *zero_code,
+                           int64_t n_old, uint4 *tiled, int64_t *ids, int32_t *ids32, int64_t total_chunks,
+                           hipStream_t s);
 void tk_launch_gather_rows(const float *X, int d, const int64_t *rows, int64_t n, float *out, hipStream_t s);
 void tk_launch_read_only(const void *src, int64_t n_uint4, uint32_t *out, hipStream_t s);
 // n_gather random rows of row_bytes (a multiple of 16, <= 1024) out of n_rows, read as the rescoring kernel reads

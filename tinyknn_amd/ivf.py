@@ -267,6 +267,8 @@ class DeviceIndex:
         data = np.ascontiguousarray(ivf.data, dtype=np.float64 if is64 else np.float32)
         _lib.check(L.tk_index_set_data(self._h, data.ctypes.data, int(is64), data.shape[0],
                                        data.shape[1]))
+        self._f64 = bool(is64)
+        self.N = int(data.shape[0])
         self.code_bytes = int(codes.nbytes)
         self.angular = ivf.metric == "angular"
         self._R = None
@@ -379,6 +381,78 @@ class DeviceIndex:
         _lib.check(_lib.lib().tk_index_read_rows(self._h, _lib.ptr(rows, _lib._i64p), len(rows),
                                                  _lib.ptr(out, _lib._f32p)))
         return out
+
+    def list_columns(self):
+        """(n_lists, kp) int64 members per (list, column of the build's nearest), or None where the index does
+        not know them (a host upload; tk_index_list_columns)."""
+        kp = C.c_int32(0)
+        _lib.check(_lib.lib().tk_index_list_columns(self._h, C.byref(kp), None))
+        if kp.value == 0:
+            return None
+        out = np.zeros((self.n_lists, kp.value), dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_list_columns(self._h, C.byref(kp), out.ctypes.data))
+        return out
+
+    def add(self, rows, kp, nearest=None, labels=None, list_columns=None, normalise=False, all_centers=None,
+            center_codes=None):
+        """Append rows (ids N .. N + n - 1) to the built lists in place (tk_index_add_rows) -> n_lists.
+        nearest (n, kp) / labels (n, M) / list_columns (n_lists, kp): None = found on the device as the
+        device build finds them (all_centers needed) / encoded on the device / the index's own.
+        center_codes: packed codes of all_centers[:n_lists'] where the rows activate new centres (None:
+        coded on the device).  Batches in flight finish first; allowed sets made before stop working."""
+        if self.world != 1 or getattr(self, "_sharded_as", None) is not None or getattr(self, "_source", None):
+            raise RuntimeError("DeviceIndex.add: a list-sharded index takes no rows")
+        if any(getattr(c, "_h", None) for c in getattr(self, "_clones", ())):
+            raise RuntimeError("DeviceIndex.add: shards cloned from this index borrow its arrays; close them first")
+        for st in list(self._streams.values()):     # the internal sessions of query_raw: made again on demand
+            st.close()
+        self._streams = {}
+        if any(getattr(st, "_s", None) for st in self._live_streams):
+            raise RuntimeError("DeviceIndex.add: a stream() session is open on this index; close it first")
+        is64 = self._data_is_f64()
+        rows = np.ascontiguousarray(rows, dtype=np.float64 if is64 else np.float32)
+        if rows.ndim != 2 or rows.shape[1] != self.d:
+            raise AssertionError(f"add: rows must have shape (n, {self.d}), got {rows.shape}")
+        n, kp = rows.shape[0], int(kp)
+        keep = []
+
+        def opt(a, dtype, shape=None):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if shape is not None and a.shape != shape:
+                raise AssertionError(f"add: expected shape {shape}, got {a.shape}")
+            keep.append(a)
+            return a.ctypes.data
+
+        M = self.dq // self.dpb
+        near_p = opt(nearest, np.int64, (n, kp))
+        lab_p = opt(labels, np.uint8, (n, M))
+        cols_p = opt(list_columns, np.int64, (self.n_lists, kp))
+        cc_p = opt(center_codes, np.uint64)
+        A = Y = yn = None
+        C_ = self.n_lists
+        if all_centers is not None:
+            A = np.ascontiguousarray(all_centers, dtype=np.float32)
+            Y = A
+            if self.angular:
+                Y = np.ascontiguousarray(Y / np.linalg.norm(Y, axis=1, keepdims=True))   # utils.py:75
+            yn = np.ascontiguousarray(np.einsum("ij,ij->i", Y, Y))    # utils.py:80
+            C_ = len(A)
+        n_active = C.c_int64(0)
+        _lib.check(_lib.lib().tk_index_add_rows(
+            self._h, rows.ctypes.data, int(is64), n, kp, near_p, lab_p, cols_p, int(bool(normalise)),
+            None if A is None else A.ctypes.data, None if Y is None else Y.ctypes.data,
+            None if yn is None else yn.ctypes.data, C_, cc_p, C.byref(n_active)))
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_info(self._h, _lib.ptr(info, _lib._i64p)))
+        self.n_lists, self.N = int(n_active.value), int(info[6])
+        self.list_sizes = self.export_lists(codes=False, ids=False)[0]
+        self.code_bytes = int(((self.list_sizes + 15) // 16).sum()) * M * 8
+        return self.n_lists
+
+    def _data_is_f64(self):
+        return bool(getattr(self, "_f64", False))
 
     @property
     def handle(self):
@@ -641,6 +715,9 @@ class DeviceIndex:
         c.rank, c.world = int(rank), int(world)
         c._streams = {}
         c._live_streams = weakref.WeakSet()
+        if getattr(self, "_clones", None) is None:
+            self._clones = weakref.WeakSet()
+        self._clones.add(c)
         return c
 
     def shard_usage(self, slot):
@@ -878,6 +955,7 @@ class IVF:
                 nearest = self._nearest_on_device(data, n_probes)
             else:
                 nearest = knn_brute(data, self.all_centers, k=n_probes, metric=self.metric)
+        self._build_device = bool(device)
         with timer(verbose, "PQ Transforming active centers..."):
             self.active_centers = np.ascontiguousarray(
                 self.all_centers[np.unique(nearest)], dtype=np.float32)
@@ -890,6 +968,9 @@ class IVF:
                 groups, self.ids = group_data_by_indices(data, nearest, n_active)
                 for i in range(n_active):
                     self.pq_transformed_points[i] = self.pq.transform(groups[i])
+        # members per (list, column of nearest): where add() puts a new row inside a list
+        self.list_columns = np.stack([np.bincount(nearest[:, j], minlength=n_active)
+                                      for j in range(nearest.shape[1])], axis=1).astype(np.int64)
         return self
 
     def _nearest_on_device(self, data, n_probes):
@@ -942,6 +1023,25 @@ class IVF:
                 return False
         return True
 
+    def _labels_of(self, data, device):
+        """(n, M) uint8 PQ labels of rows: padded, rotated on the host as the reference does (slabs of
+        rows), nearest centroid per block (on the GPU where `device`)."""
+        pq = self.pq
+        dpb = pq.dims_per_block
+        n, d = data.shape
+        pad = (-d) % (dpad * dpb)
+        M = pq.centers.shape[1] // dpb
+        labels = np.empty((n, M), dtype=np.uint8)
+        slab = 1 << 20
+        for o in range(0, n, slab):
+            rows = data[o:o + slab]
+            if pad:
+                rows = np.concatenate([rows, np.zeros((len(rows), pad), rows.dtype)], axis=1)
+            if pq.R is not None:
+                rows = rows @ pq.R.T
+            labels[o:o + slab] = pq.encode_labels(rows, device)
+        return labels
+
     def _encode_lists_on_device(self, data, nearest, n_active):
         """ivf.py:98-102 with ONE pass over the points: a row's code does not depend on the
         list it lands in, so all rows are encoded once (slabs of rows: pad, rotate on the
@@ -951,20 +1051,9 @@ class IVF:
         from ._transform import transform_data
         from .fast_pq import TransformedData
         pq = self.pq
-        dpb = pq.dims_per_block
         n, d = data.shape
-        pad = (-d) % (dpad * dpb)
         dq = pq.centers.shape[1]
-        M = dq // dpb
-        labels = np.empty((n, M), dtype=np.uint8)
-        slab = 1 << 20
-        for o in range(0, n, slab):
-            rows = data[o:o + slab]
-            if pad:
-                rows = np.concatenate([rows, np.zeros((len(rows), pad), rows.dtype)], axis=1)
-            if pq.R is not None:
-                rows = rows @ pq.R.T
-            labels[o:o + slab] = pq.encode_labels(rows, True)
+        labels = self._labels_of(data, True)
         zero = pq.encode_labels(np.zeros((16, dq), dtype=np.float64 if pq.R is not None else data.dtype),
                                 True)[0]
         # grouping as group_data_by_indices does (utils.py:95-162), without copying the vectors
@@ -1007,6 +1096,8 @@ class IVF:
         extra = {} if self.pq.R is None else {"R": self.pq.R}
         if getattr(self, "all_centers", None) is not None:
             extra["all_centers"] = self.all_centers
+        if getattr(self, "list_columns", None) is not None:
+            extra["list_columns"] = self.list_columns
         path = self._npz_path(path)
         np.savez(path, format_version=1, metric=self.metric, n_clusters=self.n_clusters,
                  use_kmeans=int(self.pq.use_kmeans), rotate_dim=-1 if self.pq.rotate_dim is None else int(self.pq.rotate_dim),
@@ -1053,6 +1144,8 @@ class IVF:
             for i in range(len(sizes))]
         ivf.ids = [ids[ioff[i]:ioff[i + 1]] for i in range(len(sizes))]
         ivf.data = z["data"] if data is None else data
+        # (files written before add() existed have no list_columns: add() recovers them)
+        ivf.list_columns = z["list_columns"] if "list_columns" in z else None
         return ivf
 
     def build_resident(self, N, d, seed, centres=None, sigma=1.0, verbose=False, n_probes=1):
@@ -1089,10 +1182,191 @@ class IVF:
         self.active_centers, cc = dev.export_centers()
         self.pq_transformed_centers = TransformedData(L, cc)
         self.list_sizes = dev.list_sizes
+        self.list_columns = dev.list_columns()
         self.data = ResidentData(dev)
         self.ids = self.pq_transformed_points = None
         self._dev = dev
         return self
+
+    # ---- growth ------------------------------------------------------------
+    def add(self, X, verbose=False):
+        """Append the rows of X with ids N .. N + n - 1 (returns self).  The index afterwards is the one its own
+        build would make over (old rows, X): new rows are prepared as the build prepared its rows (dtype of
+        IVF.data, normalisation, padding, rotation, assignment, PQ codes); every list keeps its old members in
+        place, and with n_probes = kp lists per row list l's column-j block becomes old_j ++ new_j (new_j: the
+        new rows whose j-th nearest centre is l, ascending).  An index built by build_resident is then
+        byte-identical to build_resident over all rows; against IVF.build the order inside a list is
+        unspecified for kp = 1, as numpy's argsort leaves it.  Rows that activate centres past the active
+        ones append lists (the centres stay a prefix, or AssertionError as in build).  The device index is
+        updated in place: allowed sets made before fail afterwards.  A refused call changes nothing."""
+        self._require_device_free()
+        X = np.asarray(X)
+        d = self.data.shape[1]
+        if X.ndim != 2 or X.shape[1] != d:
+            raise AssertionError(f"IVF.add: X must have shape (n, {d}), got {X.shape}")
+        if getattr(self, "all_centers", None) is None:
+            raise AssertionError("IVF.add: the index has no all_centers (fit, or a file written with them)")
+        if len(X) == 0:
+            return self
+        if self.pq_transformed_points is None:
+            return self._add_resident(X, verbose)
+        return self._add_host(X, verbose)
+
+    def _require_device_free(self):
+        dev = self._dev
+        if dev is not None and (dev.world != 1 or getattr(dev, "_sharded_as", None) is not None):
+            raise NotImplementedError("IVF.add: this index has been list-sharded in place; adding rows to a "
+                                      "list-sharded index is not supported")
+
+    def _add_resident(self, X, verbose):
+        from .fast_pq import TransformedData
+        dev = self._dev
+        cols = dev.list_columns()
+        with timer(verbose, "Adding rows on the device..."):
+            L = dev.add(np.ascontiguousarray(X, dtype=np.float32), cols.shape[1], normalise=self.metric == "angular",
+                        all_centers=self.all_centers)
+        self.active_centers, cc = dev.export_centers()
+        self.pq_transformed_centers = TransformedData(L, cc)
+        self.list_sizes = dev.list_sizes
+        self.list_columns = dev.list_columns()
+        self.data = ResidentData(dev)
+        return self
+
+    def _lists_per_row(self):
+        cols = getattr(self, "list_columns", None)
+        if cols is not None:
+            return cols.shape[1]
+        stored = sum(0 if isinstance(t, np.ndarray) else t.size for t in self.pq_transformed_points[:len(self.active_centers)])
+        return max(1, stored // max(1, len(self.data)))
+
+    def _list_columns_now(self, kp):
+        """list_columns, recovered for a file written without them: the list sizes (kp = 1), or the build's own
+        assignment over IVF.data (knn_brute, ivf.py:85) counted per column."""
+        cols = getattr(self, "list_columns", None)
+        if cols is None:
+            L = len(self.active_centers)
+            if kp == 1:
+                cols = np.array([[0 if isinstance(t, np.ndarray) else t.size]
+                                 for t in self.pq_transformed_points[:L]], dtype=np.int64).reshape(L, 1)
+            else:
+                near = knn_brute(np.asarray(self.data), self.all_centers, k=kp, metric=self.metric)
+                cols = np.stack([np.bincount(near[:, j], minlength=L) for j in range(kp)], axis=1).astype(np.int64)
+            self.list_columns = cols
+        return cols
+
+    def _add_host(self, X, verbose):
+        from .fast_pq import TransformedData
+        from . import fast_pq as _fp
+        import time
+        device = getattr(self, "_build_device", _fp.device_build)
+        kp = self._lists_per_row()
+        L0 = len(self.active_centers)
+        cols0 = self._list_columns_now(kp)
+        new = np.array(X, dtype=self.data.dtype, copy=True)         # ivf.py:77-79: X's dtype, normalised
+        if self.metric == "angular":
+            new /= np.linalg.norm(new, axis=1, keepdims=True)
+        with timer(verbose, "Computing nearest clusters..."):
+            if device:
+                nearest = self._nearest_on_device(new, kp)
+            else:
+                nearest = knn_brute(new, self.all_centers, k=kp, metric=self.metric)
+            nearest = np.ascontiguousarray(nearest, dtype=np.int64).reshape(len(new), kp)
+        used = np.union1d(np.arange(L0), np.unique(nearest))
+        assert used.max() < len(used), ("a centre that received no row precedes one that did: the reference's "
+                                        "group_data_by_indices asserts max(index) < n_active (utils.py:128)")
+        L1 = len(used)
+        with timer(verbose, "Transforming points..."):
+            labels = self._labels_of(new, device)
+        centers = self.pq_transformed_centers
+        if L1 > L0:
+            active = np.ascontiguousarray(self.all_centers[:L1], dtype=np.float32)
+            centers = self.pq.transform(active, device=device)
+        dev = self._dev
+        self.last_add_ms = {}
+        if dev is not None:
+            t0 = time.perf_counter()
+            dev.add(new, kp, nearest=nearest, labels=labels, list_columns=cols0,
+                    all_centers=self.all_centers if L1 > L0 else None,
+                    center_codes=centers.packed if L1 > L0 else None)
+            t1 = time.perf_counter()
+            sizes, codes, ids = dev.export_lists()
+            coff = np.concatenate([[0], np.cumsum((sizes + 15) // 16)])
+            ioff = np.concatenate([[0], np.cumsum(sizes)])
+            pts = [TransformedData(int(sizes[i]), codes[coff[i]:coff[i + 1]]) if sizes[i] else np.empty((0, X.shape[1]))
+                   for i in range(L1)]
+            idl = [ids[ioff[i]:ioff[i + 1]] for i in range(L1)]
+            cols1 = dev.list_columns()
+            self.last_add_ms = {"device": 1e3 * (t1 - t0), "host": 1e3 * (time.perf_counter() - t1)}
+        else:
+            t1 = time.perf_counter()
+            pts, idl, cols1 = self._splice(new, nearest, labels, cols0, L1)
+            self.last_add_ms = {"device": 0.0, "host": 1e3 * (time.perf_counter() - t1)}
+        if L1 > L0:
+            self.active_centers = active
+            self.pq_transformed_centers = centers
+        self.data = np.concatenate([self.data, new])
+        self.pq_transformed_points = list(self.pq_transformed_points)
+        self.ids = list(self.ids)
+        self.pq_transformed_points += [None] * (L1 - len(self.pq_transformed_points))
+        self.ids += [None] * (L1 - len(self.ids))
+        for i in range(L1):
+            self.pq_transformed_points[i] = pts[i]
+            self.ids[i] = idl[i]
+        self.list_columns = cols1
+        return self
+
+    def _splice(self, new, nearest, labels, cols0, L1):
+        """The lists after add() in numpy: list l's column-j block = old_j ++ (new rows with nearest[:, j] == l,
+        ascending); untouched lists are kept as they are."""
+        from ._transform import transform_data, unpack
+        from .fast_pq import TransformedData
+        N0, kp = len(self.data), nearest.shape[1]
+        L0 = len(cols0)
+        zero = self._zero_label()
+        cols1 = np.zeros((L1, kp), dtype=np.int64)
+        cols1[:L0] = cols0
+        per = [[None] * kp for _ in range(L1)]
+        for j in range(kp):
+            order = np.argsort(nearest[:, j], kind="stable")
+            cnt = np.bincount(nearest[:, j], minlength=L1)
+            cols1[:, j] += cnt
+            starts = np.concatenate([[0], np.cumsum(cnt)])
+            for l in np.nonzero(cnt)[0]:
+                per[l][j] = order[starts[l]:starts[l + 1]]
+        pts, idl = [], []
+        for l in range(L1):
+            old_t = self.pq_transformed_points[l] if l < L0 else None
+            old_ids = np.asarray(self.ids[l], dtype=np.int64) if l < L0 else np.zeros(0, np.int64)
+            if all(p is None for p in per[l]):
+                pts.append(old_t)
+                idl.append(self.ids[l])
+                continue
+            old_n = len(old_ids)
+            old_lab = (unpack(old_t.packed)[:old_n] if old_n else np.zeros((0, labels.shape[1]), np.uint8))
+            lab_parts, id_parts, o = [], [], 0
+            for j in range(kp):
+                oc = int(cols0[l, j]) if l < L0 else 0
+                lab_parts.append(old_lab[o:o + oc])
+                id_parts.append(old_ids[o:o + oc])
+                o += oc
+                if per[l][j] is not None:
+                    lab_parts.append(labels[per[l][j]])
+                    id_parts.append(N0 + per[l][j].astype(np.int64))
+            lab = np.concatenate(lab_parts).astype(np.uint8)
+            n_l = len(lab)
+            padrows = (-n_l) % 16
+            if padrows:
+                lab = np.concatenate([lab, np.repeat(zero[None], padrows, axis=0)])
+            pts.append(TransformedData(n_l, transform_data(lab)))
+            idl.append(np.concatenate(id_parts))
+        return pts, idl, cols1
+
+    def _zero_label(self):
+        """The zero vector's labels (the rows that pad a list to a multiple of 16, fast_pq.py:165)."""
+        from ._transform import unpack
+        z = self.pq.transform(np.zeros((1, self.data.shape[1]), dtype=self.data.dtype),
+                              device=getattr(self, "_build_device", None))
+        return unpack(z.packed)[1]
 
     # ---- queries (GPU) -----------------------------------------------------
     def device_index(self):

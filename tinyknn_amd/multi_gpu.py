@@ -56,6 +56,10 @@ class ReplicaGroup:
             engine = dev.query_batch
         self.engine = engine
 
+    def add(self, X, verbose=False):
+        raise NotImplementedError("ReplicaGroup.add: adding rows to a replicated index is not supported; "
+                                  "add to the IVF, then make the group again")
+
     def query_shard(self, qs, k, n_probes=1, pass_1=None):
         """This rank's slice of the batch: returns (lo, hi, ids (hi-lo, k))."""
         qs = np.array(qs, dtype=np.float32, order="C", copy=True)
@@ -283,6 +287,10 @@ class ListShardedIndex:
 
     `engine`: object with coarse/scan/finish (default: the HIP engine); tests inject a CPU one.
     """
+
+    def add(self, X, verbose=False):
+        raise NotImplementedError("ListShardedIndex.add: adding rows to a list-sharded index is not supported; "
+                                  "add to the IVF before sharding it")
 
     def __init__(self, ivf, group=None, engine=None, depth=1, owner=None, list_sizes=None,
                  coarse="home", coalesce=1, exchange="dense", calibrate=True, force_collectives=None,
