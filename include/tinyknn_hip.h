@@ -435,6 +435,28 @@ int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64, int64_t n
                       const float *ynorm2, int64_t C, const uint64_t *center_codes, int64_t *n_active_out);
 int tk_index_list_columns(tk_index *ix, int *kp, int64_t *counts);
 
+/* ---- rows removed from a built index, in place (IVF.remove) ----------------------------------
+ * tk_index_remove_rows deletes every stored copy of the n rows named by `rows` (int64 row ids in
+ * [0, N), host or device memory; duplicates allowed; ids in range but no longer stored are ignored,
+ * so a second call changes nothing).  Ids stay stable: N and the vectors are untouched (a removed
+ * row's vector stays as dead weight) and a later tk_index_add_rows still appends ids N ..  Every
+ * list keeps its surviving members in their old order: with kp lists per row list l's column-j
+ * block becomes old_j minus the removed rows.  A list that empties stays, with its centre.  The
+ * index afterwards is byte-identical to tk_index_set_lists of the filtered lists (sizes, offsets,
+ * codes with the zero vector's code in the padding rows, ids, their int32 copy, twin table).
+ *   kp, list_columns (n_lists, kp) int64 members per (list, column), or NULL where the index knows
+ *     them (tk_index_build_dev, tk_index_add_rows, an earlier removal: tk_index_list_columns); given
+ *     ones are checked against the list sizes.  Neither: the lists are compacted all the same and
+ *     their columns stay unknown.
+ *   removed_out: stored entries removed (a row stored in kp lists counts kp times), or NULL.
+ * Batches in flight are completed first; allowed sets made before fail afterwards (a new layout)
+ * unless nothing stored was named.  An id outside [0, N) is refused (TK_ERR_ARG), as is a
+ * list-sharded index; a refused or failed call leaves the index as it was.
+ * tk_index_add_rows after a removal: every row still stored must sit in exactly kp lists (checked
+ * on the device where fewer than N * kp entries remain). */
+int tk_index_remove_rows(tk_index *ix, const int64_t *rows, int64_t n, int kp,
+                         const int64_t *list_columns, int64_t *removed_out);
+
 /* ---- device front end, "fast mode"  -----------------------------------
  * What IVF.query does on the host before the table build (ivf.py:125-128,
  * fast_pq.py:200-204): float32 normalisation for the angular metric, zero padding to dq,

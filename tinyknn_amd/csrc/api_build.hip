@@ -325,6 +325,36 @@ extern "C" int tk_index_list_columns(tk_index *ix, int *kp, int64_t *counts)
     return TK_OK;
 }
 
+// What the stored labels say (all must lie in [0, N)): cnt = copies per row; out = {largest row stored, most copies
+// of a row, fewest copies of a stored row, labels outside [0, N)}.  Synchronises the device.
+static int row_copies(tk_index *ix, const int64_t *ids, int64_t T, DevBuf &cnt, DevBuf &out_d, int out[4])
+{
+    const int init[4] = {-1, 0, 0x7fffffff, 0};
+    TRY(cnt.ensure((size_t)ix->N * 4));
+    TRY(out_d.ensure(sizeof init));
+    HIPCHECK(hipMemset(cnt.p, 0, (size_t)ix->N * 4));
+    HIPCHECK(hipMemcpy(out_d.p, init, sizeof init, hipMemcpyHostToDevice));
+    tk_launch_row_copies(ids, T, cnt.as<int>(), ix->N, out_d.as<int>(), 0);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(out, out_d.p, sizeof init, hipMemcpyDeviceToHost));
+    return TK_OK;
+}
+
+// Every stored row sits in exactly kp lists.  Without removals that is total_ids == N * kp; after
+// tk_index_remove_rows (or a host upload of lists saved after one) fewer entries remain, and every row still
+// stored has its kp copies.
+static int rows_sit_in(tk_index *ix, int kp, bool *ok)
+{
+    *ok = ix->total_ids == ix->N * kp;
+    if (*ok || ix->total_ids > ix->N * kp || ix->total_ids % kp != 0) return TK_OK;
+    DevBuf cnt, out_d;
+    BufCleanup cl{{&cnt, &out_d}};
+    int out[4];
+    TRY(row_copies(ix, ix->ids.as<int64_t>(), ix->total_ids, cnt, out_d, out));
+    *ok = out[3] == 0 && (ix->total_ids == 0 || (out[1] == kp && out[2] == kp));
+    return TK_OK;
+}
+
 // New rows merged into the built lists (tinyknn_hip.h).  Everything is validated and built in new buffers
 // first; the index changes only at the end, where nothing can fail any more.
 extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64, int64_t n, int kp,
@@ -339,7 +369,11 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
     ARGCHECK(n >= 0 && (n == 0 || rows), "rows");
     ARGCHECK(kp >= 1 && kp <= 9, "kp (lists per row) must be 1 .. 9");
     ARGCHECK(!rows_is_f64 == !ix->data_is_f64, "rows must have the dtype of the index's vectors");
-    ARGCHECK(ix->total_ids == ix->N * kp, "kp: every stored row sits in kp lists");
+    {
+        bool sit = false;
+        TRY(rows_sit_in(ix, kp, &sit));
+        ARGCHECK(sit, "kp: every stored row sits in kp lists");
+    }
     ARGCHECK(list_columns || ix->list_kp == kp,
              "list_columns: the index does not know its members per (list, column) (a host upload)");
     ARGCHECK(C >= ix->n_lists && C >= kp && C < (1ll << 31), "C: the number of centres");
@@ -519,6 +553,154 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
     ix->list_kp = kp;
     TRY(build_twins(ix, N1));
     if (n_active_out) *n_active_out = L1;
+    return TK_OK;
+}
+
+// Rows deleted from the built lists (tinyknn_hip.h).  Checks first, the new lists in new buffers, the swap last.
+extern "C" int tk_index_remove_rows(tk_index *ix, const int64_t *rows, int64_t n, int kp,
+                                    const int64_t *list_columns, int64_t *removed_out)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix && ix->have_pq && ix->have_centers && ix->have_lists && ix->have_data, "a complete index");
+    ARGCHECK(!ix->sharded, "a list-sharded index removes no rows");
+    ARGCHECK(n >= 0 && (n == 0 || rows), "rows");
+    ARGCHECK(kp >= 1 && kp <= 9, "kp (lists per row) must be 1 .. 9");
+    ARGCHECK(list_columns || ix->list_kp == 0 || ix->list_kp == kp,
+             "kp: the index knows its members per (list, column) for another number of columns");
+    ARGCHECK(ix->N < (1ll << 31) && ix->total_ids < (1ll << 31), "N and the stored entries < 2^31");
+    ARGCHECK(16 % ix->dpb == 0, "dims_per_block must divide 16 for the device encoder");
+    if (removed_out) *removed_out = 0;
+    std::vector<int64_t> rv((size_t)n);
+    if (n > 0) HIPCHECK(hipMemcpy(rv.data(), rows, (size_t)n * 8, hipMemcpyDefault));
+    for (int64_t i = 0; i < n; i++) ARGCHECK(rv[(size_t)i] >= 0 && rv[(size_t)i] < ix->N, "rows: an id outside [0, N)");
+    const int64_t L = ix->n_lists, T0 = ix->total_ids, N = ix->N;
+    // ---- the old layout: list sizes, offsets, members per column (where known)
+    std::vector<int64_t> size0((size_t)L), ioff0((size_t)L + 1);
+    HIPCHECK(hipMemcpy(size0.data(), ix->list_n.p, (size_t)L * 8, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(ioff0.data(), ix->ids_off.p, (size_t)(L + 1) * 8, hipMemcpyDeviceToHost));
+    const int64_t *cols_src = list_columns ? list_columns : (ix->list_kp == kp ? ix->list_cols.data() : nullptr);
+    const int cw = cols_src ? kp : 1;     // boundaries per list: its column blocks, or the list alone
+    std::vector<int64_t> cols0(cols_src ? cols_src : size0.data(), (cols_src ? cols_src : size0.data()) + L * cw);
+    for (int64_t l = 0; l < L; l++) {
+        int64_t s = 0;
+        for (int t = 0; t < cw; t++) {
+            ARGCHECK(cols0[(size_t)(l * cw + t)] >= 0, "list_columns: negative count");
+            s += cols0[(size_t)(l * cw + t)];
+        }
+        ARGCHECK(s == size0[(size_t)l], "list_columns: a list's columns do not add up to its size");
+    }
+    if (n == 0) return TK_OK;
+    TRY(settle_lists(ix));
+    DevBuf rows_d, dead, keep, scan, tmp, bad, pos_d, gat, src, rot, zrow, zlab, codes1, ids1, ids32_1, coff_d, ioff_d,
+        n_d, cnt, summ;
+    BufCleanup cl{{&rows_d, &dead, &keep, &scan, &tmp, &bad, &pos_d, &gat, &src, &rot, &zrow, &zlab, &codes1, &ids1,
+                   &ids32_1, &coff_d, &ioff_d, &n_d, &cnt, &summ}};
+    // ---- 1. the dead rows, keep / drop per stored entry, its exclusive scan (new positions)
+    TRY(rows_d.ensure((size_t)n * 8));
+    HIPCHECK(hipMemcpy(rows_d.p, rv.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    TRY(dead.ensure((size_t)N));
+    HIPCHECK(hipMemset(dead.p, 0, (size_t)N));
+    TRY(bad.ensure(4));
+    HIPCHECK(hipMemset(bad.p, 0, 4));
+    TRY(keep.ensure((size_t)(T0 + 1) * 8));
+    TRY(scan.ensure((size_t)(T0 + 1) * 8));
+    tk_launch_mark_rows(rows_d.as<int64_t>(), n, dead.as<uint8_t>(), 0);
+    tk_launch_keep_flags(ix->ids.as<int64_t>(), T0, dead.as<uint8_t>(), N, keep.as<long long>(), bad.as<int>(), 0);
+    HIPCHECK(hipGetLastError());
+    size_t tmp_bytes = 0;
+    if (tk_scan_exclusive64(nullptr, &tmp_bytes, nullptr, nullptr, T0 + 1, 0))
+        return fail(TK_ERR_HIP, "scan: size query failed");
+    TRY(tmp.ensure(tmp_bytes));
+    if (tk_scan_exclusive64(tmp.p, &tmp_bytes, keep.as<long long>(), scan.as<long long>(), T0 + 1, 0))
+        return fail(TK_ERR_HIP, "scan failed");
+    // ---- 2. the scan at the (list, column) boundaries: new sizes, offsets and columns
+    std::vector<int64_t> bpos((size_t)(L * cw + 1)), g(bpos.size());
+    for (int64_t l = 0; l < L; l++) {
+        int64_t o = ioff0[(size_t)l];
+        for (int t = 0; t < cw; t++) {
+            bpos[(size_t)(l * cw + t)] = o;
+            o += cols0[(size_t)(l * cw + t)];
+        }
+    }
+    bpos.back() = T0;
+    TRY(pos_d.ensure(bpos.size() * 8));
+    TRY(gat.ensure(bpos.size() * 8));
+    HIPCHECK(hipMemcpy(pos_d.p, bpos.data(), bpos.size() * 8, hipMemcpyHostToDevice));
+    tk_launch_gather_scan(scan.as<long long>(), pos_d.as<int64_t>(), (int64_t)bpos.size(), gat.as<int64_t>(), 0);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(g.data(), gat.p, g.size() * 8, hipMemcpyDeviceToHost));
+    int bad_h = 0;
+    HIPCHECK(hipMemcpy(&bad_h, bad.p, 4, hipMemcpyDeviceToHost));
+    ARGCHECK(!bad_h, "the index holds labels outside [0, N): its rows cannot be named");
+    const int64_t T1 = g.back();
+    if (T1 == T0) return TK_OK;     // nothing stored was named: the index stays exactly as it is
+    std::vector<int64_t> coff((size_t)L + 1, 0), ioff((size_t)L + 1, 0), size1((size_t)L), cols1((size_t)(L * cw));
+    int64_t maxc = 0;
+    for (int64_t l = 0; l < L; l++) {
+        for (int t = 0; t < cw; t++) cols1[(size_t)(l * cw + t)] = g[(size_t)(l * cw + t) + 1] - g[(size_t)(l * cw + t)];
+        const int64_t s = g[(size_t)(l + 1) * cw] - g[(size_t)l * cw], c = (s + 15) / 16;
+        size1[(size_t)l] = s;
+        coff[(size_t)l + 1] = coff[(size_t)l] + c;
+        ioff[(size_t)l + 1] = ioff[(size_t)l] + s;
+        if (c > maxc) maxc = c;
+    }
+    const int64_t chunks1 = coff[(size_t)L];
+    // ---- 3. the old position of every kept entry; the zero vector's code (list padding)
+    TRY(src.ensure((size_t)(T1 > 0 ? T1 : 1) * 4));
+    tk_launch_scatter_kept(keep.as<long long>(), scan.as<long long>(), T0, src.as<int>(), 0);
+    HIPCHECK(hipGetLastError());
+    TRY(zrow.ensure((size_t)16 * ix->d * 4));
+    TRY(zlab.ensure((size_t)16 * ix->M));
+    HIPCHECK(hipMemset(zrow.p, 0, (size_t)16 * ix->d * 4));
+    TRY(encode_rows_dev(ix, zrow.as<float>(), 16, rot, zlab.as<uint8_t>()));
+    // ---- 4. the compacted lists
+    TRY(coff_d.ensure((size_t)(L + 1) * 8));
+    TRY(ioff_d.ensure((size_t)(L + 1) * 8));
+    TRY(n_d.ensure((size_t)L * 8));
+    HIPCHECK(hipMemcpy(coff_d.p, coff.data(), coff.size() * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(ioff_d.p, ioff.data(), ioff.size() * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(n_d.p, size1.data(), size1.size() * 8, hipMemcpyHostToDevice));
+    const size_t tiled_bytes = (size_t)tk_tiled_uint4s(chunks1, ix->M / 2) * 16;
+    TRY(codes1.ensure(tiled_bytes > 0 ? tiled_bytes : 16));
+    HIPCHECK(hipMemset(codes1.p, 0, tiled_bytes > 0 ? tiled_bytes : 16));
+    TRY(ids1.ensure((size_t)(T1 > 0 ? T1 : 1) * 8));
+    const bool want32 = ix->have_ids32 && T1 > 0;
+    if (want32) TRY(ids32_1.ensure((size_t)T1 * 4));
+    tk_launch_compact_lists(ix->codes.as<uint4>(), ix->list_chunk_off.as<int64_t>(), ix->ids_off.as<int64_t>(),
+                            ix->ids.as<int64_t>(), src.as<int>(), ix->M, coff_d.as<int64_t>(), ioff_d.as<int64_t>(),
+                            n_d.as<int64_t>(), (int)L, zlab.as<uint8_t>(), codes1.as<uint4>(), ids1.as<int64_t>(),
+                            want32 ? ids32_1.as<int32_t>() : nullptr, chunks1, 0);
+    HIPCHECK(hipGetLastError());
+    // ---- 5. what tk_index_set_lists derives from the labels: distinct?  the largest?
+    int cs[4];
+    TRY(row_copies(ix, ids1.as<int64_t>(), T1, cnt, summ, cs));
+    HIPCHECK(hipDeviceSynchronize());
+    const bool unique = cs[1] <= 1;
+    // ---- 6. the swap: the old buffers go with the cleanup
+    std::swap(ix->codes, codes1);
+    std::swap(ix->ids, ids1);
+    std::swap(ix->list_chunk_off, coff_d);
+    std::swap(ix->ids_off, ioff_d);
+    std::swap(ix->list_n, n_d);
+    if (want32 && !unique) std::swap(ix->ids32, ids32_1);
+    else ix->ids32.release();
+    ix->total_chunks = chunks1;
+    ix->total_ids = T1;
+    ix->max_list_chunks = (int)maxc;
+    ix->ids_unique = unique;
+    ix->have_ids32 = want32 && !unique;
+    ix->labels24 = cs[0] < 0x00ffffff;
+    ix->lists_gen++;
+    if (cols_src) {
+        ix->list_cols = cols1;
+        ix->list_kp = kp;
+    } else {
+        ix->list_cols.clear();
+        ix->list_kp = 0;
+    }
+    // (the labels' bound as tk_index_set_lists takes it: the same twin table as an upload of these lists)
+    TRY(build_twins(ix, (int64_t)cs[0] + 1));
+    if (removed_out) *removed_out = T0 - T1;
     return TK_OK;
 }
 

@@ -398,6 +398,180 @@ void tk_launch_merge_lists(const uint4 *old_tiled, const int64_t *old_chunk_off,
                        ids_off, list_n, n_lists, zero_code, n_old, tiled, ids, ids32, total_chunks);
 }
 
+// ---------------------------------------------------------------------------
+// Rows removed from built lists (tk_index_remove_rows).  The rows (checked in [0, N) on the host) become a byte
+// map over the row ids; every stored entry is flagged keep / drop; the exclusive scan of the flags gives a kept
+// entry its new position (lists and entries keep their order), src[] maps it back; compact_lists_kernel writes the
+// new tiled array.  Nothing is decoded or re-encoded.
+__global__ void mark_rows_kernel(const int64_t *__restrict__ rows, int64_t n, uint8_t *__restrict__ dead)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dead[rows[i]] = 1;     // (duplicates write the same byte)
+}
+
+// keep[i] = 1 for a stored entry whose row stays, 0 for one removed; keep[T] = 0, so that the exclusive scan's
+// element T is the number kept.  A label outside [0, N) sets *bad (no row id can name it).
+__global__ void keep_flags_kernel(const int64_t *__restrict__ ids, int64_t T, const uint8_t *__restrict__ dead,
+                                  int64_t N, long long *__restrict__ keep, int *__restrict__ bad)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > T) return;
+    long long k = 0;
+    if (i < T) {
+        const int64_t id = ids[i];
+        if (id >= 0 && id < N) k = dead[id] ? 0 : 1;
+        else { k = 1; *bad = 1; }
+    }
+    keep[i] = k;
+}
+
+void tk_launch_mark_rows(const int64_t *rows, int64_t n, uint8_t *dead, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(mark_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rows, n, dead);
+}
+
+void tk_launch_keep_flags(const int64_t *ids, int64_t T, const uint8_t *dead, int64_t N, long long *keep, int *bad,
+                          hipStream_t s)
+{
+    hipLaunchKernelGGL(keep_flags_kernel, dim3((unsigned)((T + 1 + 255) / 256)), dim3(256), 0, s, ids, T, dead, N,
+                       keep, bad);
+}
+
+// src[scan[i]] = i for every kept entry: the old position of every new one
+__global__ void scatter_kept_kernel(const long long *__restrict__ keep, const long long *__restrict__ scan, int64_t T,
+                                    int *__restrict__ src)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < T && keep[i]) src[scan[i]] = (int)i;
+}
+
+// out[j] = scan[pos[j]]: the new positions of the (list, column) boundaries
+__global__ void gather_scan_kernel(const long long *__restrict__ scan, const int64_t *__restrict__ pos, int64_t m,
+                                   int64_t *__restrict__ out)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < m) out[j] = scan[pos[j]];
+}
+
+void tk_launch_scatter_kept(const long long *keep, const long long *scan, int64_t T, int *src, hipStream_t s)
+{
+    if (T <= 0) return;
+    hipLaunchKernelGGL(scatter_kept_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, keep, scan, T, src);
+}
+
+void tk_launch_gather_scan(const long long *scan, const int64_t *pos, int64_t m, int64_t *out, hipStream_t s)
+{
+    if (m <= 0) return;
+    hipLaunchKernelGGL(gather_scan_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, scan, pos, m, out);
+}
+
+// The compacted lists: one thread per (output chunk, block pair), as merge_lists_kernel.  Output row r of the chunk
+// (list position pos, global position g) copies the packed byte of its old position src[g] (in the same list: the
+// scan keeps list boundaries); rows past the list's end take the zero vector's code.  The p == 0 thread of a chunk
+// also writes the chunk's ids and their int32 copy (ids32 may be NULL).
+__global__ void compact_lists_kernel(const uint4 *__restrict__ old_tiled, const int64_t *__restrict__ old_chunk_off,
+                                     const int64_t *__restrict__ old_ids_off, const int64_t *__restrict__ old_ids,
+                                     const int *__restrict__ src, int M, const int64_t *__restrict__ chunk_off,
+                                     const int64_t *__restrict__ ids_off, const int64_t *__restrict__ list_n,
+                                     int n_lists, const uint8_t *__restrict__ zero_code, uint4 *__restrict__ tiled,
+                                     int64_t *__restrict__ ids, int32_t *__restrict__ ids32, int64_t total_chunks)
+{
+    const int P = M >> 1;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total_chunks * P) return;
+    const int64_t c = i / P;
+    const int p = (int)(i - c * P);
+    int lo = 0, hi = n_lists;   // chunk_off[lo] <= c < chunk_off[lo + 1] (empty lists are stepped over)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (chunk_off[mid] <= c) lo = mid; else hi = mid;
+    }
+    const int64_t pos0 = 16 * (c - chunk_off[lo]);
+    const int64_t n_l = list_n[lo], g0 = ids_off[lo], og0 = old_ids_off[lo], oc0 = old_chunk_off[lo];
+    const uint32_t zb = (uint32_t)zero_code[2 * p] | ((uint32_t)zero_code[2 * p + 1] << 4);
+    uint32_t w[4] = {0, 0, 0, 0};
+    int64_t cur_oc = -1;                  // the old chunk held in `cur` (consecutive rows mostly share one)
+    uint4 cur = make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        uint32_t b = zb;
+        const int64_t pos = pos0 + r;
+        if (pos < n_l) {
+            const int64_t og = src[g0 + pos];
+            const int64_t old_pos = og - og0;
+            const int64_t oc = oc0 + (old_pos >> 4);
+            if (oc != cur_oc) {
+                cur = old_tiled[((oc >> 3) * P + p) * 8 + (oc & 7)];
+                cur_oc = oc;
+            }
+            const int rr = (int)(old_pos & 15);
+            const uint32_t word = rr < 4 ? cur.x : (rr < 8 ? cur.y : (rr < 12 ? cur.z : cur.w));
+            b = (word >> (8 * (rr & 3))) & 0xffu;
+            if (p == 0) {
+                const int64_t label = old_ids[og];
+                ids[g0 + pos] = label;
+                if (ids32) ids32[g0 + pos] = (int32_t)label;
+            }
+        }
+        w[r >> 2] |= b << (8 * (r & 3));
+    }
+    tiled[((c >> 3) * P + p) * 8 + (c & 7)] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+void tk_launch_compact_lists(const uint4 *old_tiled, const int64_t *old_chunk_off, const int64_t *old_ids_off,
+                             const int64_t *old_ids, const int *src, int M, const int64_t *chunk_off,
+                             const int64_t *ids_off, const int64_t *list_n, int n_lists, const uint8_t *zero_code,
+                             uint4 *tiled, int64_t *ids, int32_t *ids32, int64_t total_chunks, hipStream_t s)
+{
+    const int64_t items = total_chunks * (M / 2);
+    if (items <= 0) return;
+    hipLaunchKernelGGL(compact_lists_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, old_tiled,
+                       old_chunk_off, old_ids_off, old_ids, src, M, chunk_off, ids_off, list_n, n_lists, zero_code,
+                       tiled, ids, ids32, total_chunks);
+}
+
+// Copies per row of the stored labels: cnt[row] += 1 per entry (cnt: N ints, zeroed); a label outside [0, N) is
+// counted in *outside instead.
+__global__ void row_copies_kernel(const int64_t *__restrict__ ids, int64_t T, int64_t N, int *__restrict__ cnt,
+                                  int *__restrict__ outside)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T) return;
+    const int64_t id = ids[i];
+    if (id >= 0 && id < N) atomicAdd(&cnt[id], 1);
+    else atomicAdd(outside, 1);
+}
+
+// out[0] = the largest row with a copy (-1: none), out[1] = the most copies of a row, out[2] = the fewest copies of
+// a stored row (out[0 .. 2]: {-1, 0, INT_MAX} on entry).  One atomic per wave.
+__global__ void copies_summary_kernel(const int *__restrict__ cnt, int64_t N, int *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = i < N ? cnt[i] : 0;
+    int hi_row = c > 0 ? (int)i : -1, most = c, fewest = c > 0 ? c : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        hi_row = max(hi_row, __shfl_xor(hi_row, o, 64));
+        most = max(most, __shfl_xor(most, o, 64));
+        fewest = min(fewest, __shfl_xor(fewest, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (hi_row >= 0) atomicMax(&out[0], hi_row);
+        if (most > 0) atomicMax(&out[1], most);
+        if (fewest != 0x7fffffff) atomicMin(&out[2], fewest);
+    }
+}
+
+void tk_launch_row_copies(const int64_t *ids, int64_t T, int *cnt, int64_t N, int *out, hipStream_t s)
+{
+    if (T > 0)
+        hipLaunchKernelGGL(row_copies_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, ids, T, N, cnt,
+                           out + 3);
+    if (N > 0)
+        hipLaunchKernelGGL(copies_summary_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, cnt, N, out);
+}
+
 // rows of a float32 (N, d) matrix gathered by id (rescoring vectors for the checker)
 __global__ void gather_rows_kernel(const float *__restrict__ X, int d, const int64_t *__restrict__ rows,
                                    int64_t n, float *__restrict__ out)

@@ -429,6 +429,21 @@ void tk_launch_merge_lists(const uint4 *old_tiled, const int64_t *old_chunk_off,
                            const int64_t *ids_off, const int64_t *list_n, int n_lists, const uint8_t *zero_code,
                            int64_t n_old, uint4 *tiled, int64_t *ids, int32_t *ids32, int64_t total_chunks,
                            hipStream_t s);
+// built lists - removed rows -> the compacted lists (tk_index_remove_rows; devbuild.hip compact_lists_kernel):
+// dead byte map over the rows, keep flags (T + 1 of them; *bad = 1 for a label outside [0, N)), the kept entries'
+// old positions (src[scan[i]] = i), the scan at the (list, column) boundaries, the compaction
+void tk_launch_mark_rows(const int64_t *rows, int64_t n, uint8_t *dead, hipStream_t s);
+void tk_launch_keep_flags(const int64_t *ids, int64_t T, const uint8_t *dead, int64_t N, long long *keep, int *bad,
+                          hipStream_t s);
+void tk_launch_scatter_kept(const long long *keep, const long long *scan, int64_t T, int *src, hipStream_t s);
+void tk_launch_gather_scan(const long long *scan, const int64_t *pos, int64_t m, int64_t *out, hipStream_t s);
+void tk_launch_compact_lists(const uint4 *old_tiled, const int64_t *old_chunk_off, const int64_t *old_ids_off,
+                             const int64_t *old_ids, const int *src, int M, const int64_t *chunk_off,
+                             const int64_t *ids_off, const int64_t *list_n, int n_lists, const uint8_t *zero_code,
+                             uint4 *tiled, int64_t *ids, int32_t *ids32, int64_t total_chunks, hipStream_t s);
+// copies per row of T labels into cnt (N ints, zeroed); out = {largest row stored, most copies, fewest copies of a
+// stored row, labels outside [0, N)}, {-1, 0, INT_MAX, 0} on entry
+void tk_launch_row_copies(const int64_t *ids, int64_t T, int *cnt, int64_t N, int *out, hipStream_t s);
 void tk_launch_gather_rows(const float *X, int d, const int64_t *rows, int64_t n, float *out, hipStream_t s);
 void tk_launch_read_only(const void *src, int64_t n_uint4, uint32_t *out, hipStream_t s);
 // n_gather random rows of row_bytes (a multiple of 16, <= 1024) out of n_rows, read as the rescoring kernel reads

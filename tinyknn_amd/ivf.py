@@ -111,6 +111,22 @@ class ResidentData:
         return self._dev.read_rows(rows).reshape(rows.shape + (self.shape[1],))
 
 
+def removal_rows(ids_or_mask, N):
+    """int64 row ids of remove()'s argument: a bool mask of length N, or a 1-d integer array of ids in [0, N)
+    (duplicates allowed)."""
+    a = np.asarray(ids_or_mask)
+    if a.dtype == np.bool_:
+        if a.shape != (N,):
+            raise ValueError(f"remove: a bool mask must have shape ({N},), got {a.shape}")
+        return np.ascontiguousarray(np.flatnonzero(a), dtype=np.int64)
+    if a.ndim == 1 and (a.size == 0 or np.issubdtype(a.dtype, np.integer)):
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        if a.size and (a.min() < 0 or a.max() >= N):
+            raise ValueError(f"remove: row ids must lie in [0, {N})")
+        return a
+    raise TypeError("remove: a bool mask of length N or a 1-d integer array of row ids")
+
+
 def _copies_carry_one_code(ivf, n_lists):
     """Rows with equal ids lie in different lists and carry equal codes — what IVF.build's lists have by construction
     (ivf.py:77-102) and what the lane replay's TWIN form rests on (heap.hip).  The library checks it on the device
@@ -400,15 +416,7 @@ class DeviceIndex:
         device build finds them (all_centers needed) / encoded on the device / the index's own.
         center_codes: packed codes of all_centers[:n_lists'] where the rows activate new centres (None:
         coded on the device).  Batches in flight finish first; allowed sets made before stop working."""
-        if self.world != 1 or getattr(self, "_sharded_as", None) is not None or getattr(self, "_source", None):
-            raise RuntimeError("DeviceIndex.add: a list-sharded index takes no rows")
-        if any(getattr(c, "_h", None) for c in getattr(self, "_clones", ())):
-            raise RuntimeError("DeviceIndex.add: shards cloned from this index borrow its arrays; close them first")
-        for st in list(self._streams.values()):     # the internal sessions of query_raw: made again on demand
-            st.close()
-        self._streams = {}
-        if any(getattr(st, "_s", None) for st in self._live_streams):
-            raise RuntimeError("DeviceIndex.add: a stream() session is open on this index; close it first")
+        self._lists_may_change("add", "takes no rows")
         is64 = self._data_is_f64()
         rows = np.ascontiguousarray(rows, dtype=np.float64 if is64 else np.float32)
         if rows.ndim != 2 or rows.shape[1] != self.d:
@@ -450,6 +458,45 @@ class DeviceIndex:
         self.list_sizes = self.export_lists(codes=False, ids=False)[0]
         self.code_bytes = int(((self.list_sizes + 15) // 16).sum()) * M * 8
         return self.n_lists
+
+    def _lists_may_change(self, what, sharded):
+        """The refusals of add / remove: a list-sharded index or its clones, an open stream() session (the internal
+        sessions of query_raw are closed: made again on demand)."""
+        if self.world != 1 or getattr(self, "_sharded_as", None) is not None or getattr(self, "_source", None):
+            raise RuntimeError(f"DeviceIndex.{what}: a list-sharded index {sharded}")
+        if any(getattr(c, "_h", None) for c in getattr(self, "_clones", ())):
+            raise RuntimeError(f"DeviceIndex.{what}: shards cloned from this index borrow its arrays; close them first")
+        for st in list(self._streams.values()):
+            st.close()
+        self._streams = {}
+        if any(getattr(st, "_s", None) for st in self._live_streams):
+            raise RuntimeError(f"DeviceIndex.{what}: a stream() session is open on this index; close it first")
+
+    def remove(self, ids_or_mask, list_columns=None):
+        """Delete every stored copy of the rows named by ids_or_mask (row ids in [0, N), duplicates allowed, or a
+        bool mask of length N) in place (tk_index_remove_rows) -> stored entries removed.  Surviving entries keep
+        their order; ids, N and the vectors stay; emptied lists stay.  list_columns (n_lists, kp): the members per
+        (list, column) where the index does not know them (a host upload; None: compacted all the same, the columns
+        stay unknown).  Batches in flight finish first; allowed sets made before stop working (unless nothing
+        stored was named)."""
+        self._lists_may_change("remove", "removes no rows")
+        rows = removal_rows(ids_or_mask, self.N)
+        cols_p, keep, kp = None, None, 1
+        if list_columns is not None:
+            keep = np.ascontiguousarray(list_columns, dtype=np.int64)
+            if keep.ndim != 2 or keep.shape[0] != self.n_lists:
+                raise AssertionError(f"remove: list_columns must have shape ({self.n_lists}, kp), got {keep.shape}")
+            cols_p, kp = keep.ctypes.data, keep.shape[1]
+        else:
+            known = C.c_int32(0)
+            _lib.check(_lib.lib().tk_index_list_columns(self._h, C.byref(known), None))
+            kp = max(1, known.value)
+        removed = C.c_int64(0)
+        _lib.check(_lib.lib().tk_index_remove_rows(self._h, rows.ctypes.data, len(rows), kp, cols_p,
+                                                   C.byref(removed)))
+        self.list_sizes = self.export_lists(codes=False, ids=False)[0]
+        self.code_bytes = int(((self.list_sizes + 15) // 16).sum()) * (self.dq // self.dpb) * 8
+        return int(removed.value)
 
     def _data_is_f64(self):
         return bool(getattr(self, "_f64", False))
@@ -1212,10 +1259,10 @@ class IVF:
             return self._add_resident(X, verbose)
         return self._add_host(X, verbose)
 
-    def _require_device_free(self):
+    def _require_device_free(self, what="add", doing="adding rows to"):
         dev = self._dev
         if dev is not None and (dev.world != 1 or getattr(dev, "_sharded_as", None) is not None):
-            raise NotImplementedError("IVF.add: this index has been list-sharded in place; adding rows to a "
+            raise NotImplementedError(f"IVF.{what}: this index has been list-sharded in place; {doing} a "
                                       "list-sharded index is not supported")
 
     def _add_resident(self, X, verbose):
@@ -1359,6 +1406,104 @@ class IVF:
                 lab = np.concatenate([lab, np.repeat(zero[None], padrows, axis=0)])
             pts.append(TransformedData(n_l, transform_data(lab)))
             idl.append(np.concatenate(id_parts))
+        return pts, idl, cols1
+
+    # ---- removal -----------------------------------------------------------
+    def remove(self, ids_or_mask, verbose=False):
+        """Delete every stored copy of the rows named by ids_or_mask (row ids, duplicates allowed, or a bool mask of
+        length N) from the lists (returns self).  Ids are stable: IVF.data keeps every row (a removed row's vector
+        stays as dead weight) and a later add() still appends ids N ..  Every list keeps its surviving members in
+        their old order: list l's column-j block becomes old_j minus the removed rows (list_columns follows).  A
+        list that empties stays, with its centre.  Ids in range but no longer stored are ignored; an id outside
+        [0, N) raises and changes nothing.  The result is the index over the lists filtered so — not what
+        allowed= the survivors gives on the old index (the reference's heap bound is taken per 16-row block, and
+        compaction moves the blocks).  The device index is updated in place: allowed sets made before fail."""
+        self._require_device_free("remove", "removing rows from")
+        rows = removal_rows(ids_or_mask, len(self.data))
+        if len(rows) == 0:
+            return self
+        if self.pq_transformed_points is None:
+            return self._remove_resident(rows, verbose)
+        return self._remove_host(rows, verbose)
+
+    def _remove_resident(self, rows, verbose):
+        import time
+        dev = self._dev
+        t0 = time.perf_counter()
+        with timer(verbose, "Removing rows on the device..."):
+            dev.remove(rows)
+        self.last_remove_ms = {"device": 1e3 * (time.perf_counter() - t0), "host": 0.0}
+        self.list_sizes = dev.list_sizes
+        self.list_columns = dev.list_columns()
+        return self
+
+    def _remove_host(self, rows, verbose):
+        from .fast_pq import TransformedData
+        import time
+        kp = self._lists_per_row()
+        cols0 = self._list_columns_now(kp)      # (before: their recovery from IVF.data assumes every row stored)
+        dead = np.zeros(len(self.data), dtype=bool)
+        dead[rows] = True
+        L, d = len(self.active_centers), self.data.shape[1]
+        dev = self._dev
+        if dev is not None:
+            t0 = time.perf_counter()
+            with timer(verbose, "Removing rows on the device..."):
+                removed = dev.remove(rows, list_columns=cols0)
+            t1 = time.perf_counter()
+            if removed == 0:                      # nothing stored was named: nothing changed
+                self.last_remove_ms = {"device": 1e3 * (t1 - t0), "host": 0.0}
+                return self
+            sizes, codes, ids = dev.export_lists()
+            coff = np.concatenate([[0], np.cumsum((sizes + 15) // 16)])
+            ioff = np.concatenate([[0], np.cumsum(sizes)])
+            pts = [TransformedData(int(sizes[i]), codes[coff[i]:coff[i + 1]]) if sizes[i] else np.empty((0, d))
+                   for i in range(L)]
+            idl = [ids[ioff[i]:ioff[i + 1]] for i in range(L)]
+            cols1 = dev.list_columns()
+            self.last_remove_ms = {"device": 1e3 * (t1 - t0), "host": 1e3 * (time.perf_counter() - t1)}
+        else:
+            t1 = time.perf_counter()
+            pts, idl, cols1 = self._filter_lists(dead, cols0)
+            self.last_remove_ms = {"device": 0.0, "host": 1e3 * (time.perf_counter() - t1)}
+        self.pq_transformed_points = list(self.pq_transformed_points)
+        self.ids = list(self.ids)
+        for i in range(L):
+            self.pq_transformed_points[i] = pts[i]
+            self.ids[i] = idl[i]
+        self.list_columns = cols1
+        return self
+
+    def _filter_lists(self, dead, cols0):
+        """The lists after remove() in numpy: every list's surviving entries in their old order (each column block
+        shrinks in place), repacked with the zero vector's code in the padding rows; untouched lists are kept."""
+        from ._transform import transform_data, unpack
+        from .fast_pq import TransformedData
+        L, kp = cols0.shape
+        d = self.data.shape[1]
+        zero = self._zero_label()
+        cols1 = np.array(cols0, dtype=np.int64, copy=True)
+        pts, idl = [], []
+        for l in range(L):
+            t = self.pq_transformed_points[l]
+            n_l = 0 if isinstance(t, np.ndarray) else t.size
+            ids = np.asarray(self.ids[l])[:n_l]
+            keep = ~dead[ids.astype(np.int64)]
+            if keep.all():
+                pts.append(t)
+                idl.append(self.ids[l])
+                continue
+            cols1[l] = np.bincount(np.repeat(np.arange(kp), cols0[l])[keep], minlength=kp)
+            n1 = int(keep.sum())
+            idl.append(ids[keep])
+            if n1 == 0:
+                pts.append(np.empty((0, d)))      # as FastPQ.transform of no rows (fast_pq.py:162-163)
+                continue
+            lab = unpack(t.packed)[:n_l][keep]
+            padrows = (-n1) % 16
+            if padrows:
+                lab = np.concatenate([lab, np.repeat(zero[None], padrows, axis=0)])
+            pts.append(TransformedData(n1, transform_data(np.ascontiguousarray(lab, dtype=np.uint8))))
         return pts, idl, cols1
 
     def _zero_label(self):

@@ -60,6 +60,10 @@ class ReplicaGroup:
         raise NotImplementedError("ReplicaGroup.add: adding rows to a replicated index is not supported; "
                                   "add to the IVF, then make the group again")
 
+    def remove(self, ids_or_mask, verbose=False):
+        raise NotImplementedError("ReplicaGroup.remove: removing rows from a replicated index is not supported; "
+                                  "remove from the IVF, then make the group again")
+
     def query_shard(self, qs, k, n_probes=1, pass_1=None):
         """This rank's slice of the batch: returns (lo, hi, ids (hi-lo, k))."""
         qs = np.array(qs, dtype=np.float32, order="C", copy=True)
@@ -291,6 +295,10 @@ class ListShardedIndex:
     def add(self, X, verbose=False):
         raise NotImplementedError("ListShardedIndex.add: adding rows to a list-sharded index is not supported; "
                                   "add to the IVF before sharding it")
+
+    def remove(self, ids_or_mask, verbose=False):
+        raise NotImplementedError("ListShardedIndex.remove: removing rows from a list-sharded index is not "
+                                  "supported; remove from the IVF before sharding it")
 
     def __init__(self, ivf, group=None, engine=None, depth=1, owner=None, list_sizes=None,
                  coarse="home", coalesce=1, exchange="dense", calibrate=True, force_collectives=None,
