@@ -171,6 +171,10 @@ int tk_index_set_data(tk_index *ix, const void *data, int data_is_f64, int64_t N
  * q_pq: their padded / rotated form; out_ids: (nq, k) int64, -1 beyond n. */
 int tk_index_top_centers(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq,
                          int k, int64_t *out_ids);
+/* The same, and out_dist: (nq, k) float32, the exact squared distance beside each id (knn_brute1's
+ * values, the ones the ids are ranked by; +inf beside a -1). */
+int tk_index_top_centers_dist(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq,
+                              int k, int64_t *out_ids, float *out_dist);
 
 /* Largest batch the workspace is currently sized for grows on demand; this call
  * pre-sizes it (so that tk_index_query_batch_dev never allocates, e.g. under
@@ -546,6 +550,25 @@ int tk_index_query_batch_dev_allow(tk_index *ix, const tk_allow *allow, const fl
                                    const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k, int n_probes,
                                    int pass_1, int64_t *out_ids_dev, int64_t *out_ids_pinned,
                                    void *done_event, void *stream);
+/* Ids and their distances.  out_dist[i, j] is the exact squared Euclidean distance between stored row
+ * out_ids[i, j] of tk_index_set_data's vectors and query row q[i], summed as knn_brute1 does (utils.py:89-92:
+ * einsum("ij,ij->i", diff, diff) of diff = data[id] - q) — the value the rescoring ranks by.  Element type:
+ * float32, or float64 after tk_index_set_data(..., data_is_f64 = 1) (numpy's promotion of `Y - x`); +inf
+ * beside every -1.  The ids are those of the ids-only call, bit for bit.  Where a query had more than k
+ * candidates its row is in rescored order (distances non-decreasing); where it had k or fewer the ids keep
+ * heap order (ivf.py:158-159) and each still gets its distance, so such a row need not be sorted.
+ * allow: an allowed set, or NULL for every row.  tk_index_query_batch_dist: host buffers, as
+ * tk_index_query_batch without the debug outputs.  tk_index_query_batch_dev_dist: device buffers, as
+ * tk_index_query_batch_dev_ex without the pinned copy — sub-batches, the pipelined mode and pairs of calls
+ * (a pair may join a call that wants distances with one that does not: each writes only its own buffers);
+ * out_dist_dev belongs to the library, as out_ids_dev does, until done_event or tk_index_join. */
+int tk_index_query_batch_dist(tk_index *ix, const tk_allow *allow, const float *q, const void *q_pq,
+                              int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                              int64_t *out_ids, void *out_dist);
+int tk_index_query_batch_dev_dist(tk_index *ix, const tk_allow *allow, const float *q_dev,
+                                  const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k, int n_probes,
+                                  int pass_1, int64_t *out_ids_dev, void *out_dist_dev, void *done_event,
+                                  void *stream);
 /* hipStream_t on which to copy a batch's inputs in (pipelined mode: the index's front stream,
  * where the batch's first kernel runs; NULL: use the stream the batch is enqueued on) */
 void *tk_index_input_stream(tk_index *ix);

@@ -123,6 +123,8 @@ SIGNATURES = {
     "tk_index_list_columns": (C.c_int, [C.c_void_p, _i32p, C.c_void_p]),
     "tk_index_remove_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, _i64p]),
     "tk_index_top_centers": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int, _i64p]),
+    "tk_index_top_centers_dist": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int, _i64p,
+                                            _f32p]),
     "tk_index_set_data": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int]),
     "tk_index_reserve": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int]),
     "tk_index_query_batch": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int,
@@ -151,6 +153,11 @@ SIGNATURES = {
     "tk_index_query_batch_dev_allow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                  C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]),
+    "tk_index_query_batch_dist": (C.c_int, [C.c_void_p, C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64,
+                                            C.c_int, C.c_int, C.c_int, _i64p, C.c_void_p]),
+    "tk_index_query_batch_dev_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
     "tk_index_pending": (C.c_int, [C.c_void_p]),
     "tk_index_input_stream": (C.c_void_p, [C.c_void_p]),
     "tk_index_info": (C.c_int, [C.c_void_p, _i64p]),

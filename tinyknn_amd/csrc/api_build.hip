@@ -1002,10 +1002,10 @@ extern "C" int tk_index_knn_brute(tk_index *ix, const float *q, int64_t nq, int 
 // first plain block <= C) and fetches only the blocks whose minimum passes its bound (LAZY).  A chunk
 // of queries in which any query fails the check is answered again by the exact kernel alone, and an
 // index on which more than 1 % fail (rows without structure) stays on the exact kernel.
-extern "C" int tk_index_top_centers(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64,
-                                    int64_t nq, int k, int64_t *out_ids)
+// out_dist (or NULL): the float32 exact squared distances beside the ids (+inf beside a -1 of the padding)
+static int top_centers(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
+                       int64_t *out_ids, float *out_dist)
 {
-    IXLOCK(ix);
     ARGCHECK(ix && ix->have_pq && ix->have_centers, "set_pq and set_centers first");
     ARGCHECK(nq >= 0 && k >= 1 && (nq == 0 || (q && q_pq && out_ids)), "buffers / sizes");
     if (nq == 0) return TK_OK;
@@ -1023,6 +1023,11 @@ extern "C" int tk_index_top_centers(tk_index *ix, const float *q, const void *q_
     Work &w = ix->works[0];
     const int M = ix->M;
     const size_t esz = q_pq_is_f64 ? 8 : 4;
+    struct ScopedBuf : DevBuf {
+        ~ScopedBuf() { release(); }
+    } dbuf;             // (freed on every return)
+    if (out_dist) TRY(dbuf.ensure((size_t)chunk * p.kc * 4));
+    float *dist = out_dist ? dbuf.as<float>() : nullptr;
     const bool lanes = ix->heap_mode == 0 && tk_positions_fit(ix->center_chunks) && p.rescore <= TK_LANES_MAX_R;
     const bool lazy = lanes && ix->center_chunks >= 1024;
     const int hc = (int)(ix->center_chunks / 64 < 16 ? 16 : ix->center_chunks / 64);     // exact head, in chunks
@@ -1068,7 +1073,8 @@ extern "C" int tk_index_top_centers(tk_index *ix, const float *q, const void *q_
     auto replay_rescore = [&](int64_t m, bool plain) -> int {
         if (!lanes) {
             Prof pf;
-            return coarse_replay_probes(ix, w, ix->q.as<float>(), m, p, w.probes.as<int64_t>(), nullptr, pf);
+            return coarse_replay_probes(ix, w, ix->q.as<float>(), m, p, w.probes.as<int64_t>(), nullptr, pf, TkSecond(),
+                                        nullptr, nullptr, dist);
         }
         TkLanesOpts o;
         o.lazy = lazy ? 1 : 0;
@@ -1080,7 +1086,7 @@ extern "C" int tk_index_top_centers(tk_index *ix, const float *q, const void *q_
             return fail(TK_ERR_HIP, "hipFuncSetAttribute(LDS size) failed");
         tk_launch_rescore(ix->q.as<float>(), 0, ix->d, ix->active_centers.p, 0, ix->n_lists,
                           w.cheap_idx.as<int64_t>(), p.rescore, m, p.kc, 0, w.probes.as<int64_t>(), nullptr, nullptr,
-                          ix->opt_rescore_form);
+                          ix->opt_rescore_form, TkSecond(), TkSecond(), nullptr, dist);
         return TK_OK;
     };
     for (int64_t o = 0; o < nq; o += chunk) {
@@ -1126,13 +1132,36 @@ extern "C" int tk_index_top_centers(tk_index *ix, const float *q, const void *q_
         }
         if (p.kc == k) {
             HIPCHECK(hipMemcpy(out_ids + o * k, w.probes.p, (size_t)m * k * 8, hipMemcpyDeviceToHost));
-        } else {    // fewer rows than k: rows of kc ids into rows of k, padded with -1
+            if (out_dist) HIPCHECK(hipMemcpy(out_dist + o * k, dist, (size_t)m * k * 4, hipMemcpyDeviceToHost));
+        } else {    // fewer rows than k: rows of kc ids into rows of k, padded with -1 (+inf)
             std::vector<int64_t> tmp((size_t)m * p.kc);
             HIPCHECK(hipMemcpy(tmp.data(), w.probes.p, tmp.size() * 8, hipMemcpyDeviceToHost));
             for (int64_t i = 0; i < m; i++)
                 for (int t = 0; t < k; t++)
                     out_ids[(o + i) * k + t] = t < p.kc ? tmp[(size_t)i * p.kc + t] : -1;
+            if (out_dist) {
+                std::vector<float> tmpd((size_t)m * p.kc);
+                HIPCHECK(hipMemcpy(tmpd.data(), dist, tmpd.size() * 4, hipMemcpyDeviceToHost));
+                for (int64_t i = 0; i < m; i++)
+                    for (int t = 0; t < k; t++)
+                        out_dist[(o + i) * k + t] = t < p.kc ? tmpd[(size_t)i * p.kc + t] : HUGE_VALF;
+            }
         }
     }
     return TK_OK;
+}
+
+extern "C" int tk_index_top_centers(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64,
+                                    int64_t nq, int k, int64_t *out_ids)
+{
+    IXLOCK(ix);
+    return top_centers(ix, q, q_pq, q_pq_is_f64, nq, k, out_ids, nullptr);
+}
+
+extern "C" int tk_index_top_centers_dist(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64,
+                                         int64_t nq, int k, int64_t *out_ids, float *out_dist)
+{
+    IXLOCK(ix);
+    ARGCHECK(nq <= 0 || out_dist, "buffers / sizes");
+    return top_centers(ix, q, q_pq, q_pq_is_f64, nq, k, out_ids, out_dist);
 }

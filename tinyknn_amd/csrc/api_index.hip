@@ -18,6 +18,7 @@ struct Pending {
         int64_t *host_out;          // pinned host copy of the ids, enqueued behind the rescoring (or NULL)
         bool host_out_kernel;       // ... written by copy_words_kernel instead of the copy engine
         hipEvent_t user_ev;         // recorded behind that copy (or NULL)
+        void *dist_dev = nullptr;   // the rescoring's distances beside out_dev (or NULL: ids only)
     } subs[2];
     int n_subs = 1;
     Work *w;
@@ -48,12 +49,15 @@ struct Pending {
         int64_t *out;
         int64_t nq;
         TkSecond q2, qpq2, out2;
+        void *dist;                 // each call's distances (or NULL), as its ids
+        TkSecond dist2;
     };
     Rows rows() const
     {
         const Sub &a = subs[0], &b = subs[1];
-        if (n_subs == 1) return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq, {}, {}, {}};
-        return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq + b.nq, {b.q_dev, a.nq}, {b.qpq_dev, a.nq}, {b.out_dev, a.nq}};
+        if (n_subs == 1) return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq, {}, {}, {}, a.dist_dev, {}};
+        return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq + b.nq, {b.q_dev, a.nq}, {b.qpq_dev, a.nq}, {b.out_dev, a.nq},
+                    a.dist_dev, {b.dist_dev, a.nq}};
     }
 };
 
@@ -834,7 +838,7 @@ static void replay_general(const TkReplayJob &j, hipStream_t st)
 // `probes_out`: (nq, kc) int64, the probe lists (ivf.py:131) — w.probes, or a caller's buffer.
 int coarse_replay_probes(tk_index *ix, Work &w, const float *q_dev, int64_t nq, const Plan &p,
                                 int64_t *probes_out, hipStream_t st, Prof &pf, TkSecond q2,
-                                const TkSlotsOut *slots, int *slots_written)
+                                const TkSlotsOut *slots, int *slots_written, float *dist)
 {
     TRY(pf.mark(st));
     // positions of one list against a fresh heap are distinct labels: lane-per-query
@@ -853,7 +857,7 @@ int coarse_replay_probes(tk_index *ix, Work &w, const float *q_dev, int64_t nq, 
     TRY(pf.mark(st));
     const int fused = tk_launch_rescore(q_dev, 0, ix->d, ix->active_centers.p, 0, ix->n_lists,
                                         w.cheap_idx.as<int64_t>(), p.rescore, nq, p.kc, 0, probes_out, nullptr, st,
-                                        ix->opt_rescore_form, q2, TkSecond(), slots);
+                                        ix->opt_rescore_form, q2, TkSecond(), slots, dist);
     if (slots_written) *slots_written = fused;
     return TK_OK;
 }
@@ -1066,7 +1070,7 @@ static Replay replay_form(const tk_index *ix, int64_t nq, const Plan &p)
 // rescoring.  q_dev: row 0 = query q0.
 int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
                const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain,
-               TkSecond q2, TkSecond out2, int *plain_flag, const tk_allow *allow)
+               TkSecond q2, TkSecond out2, int *plain_flag, const tk_allow *allow, void *dist_dev, TkSecond dist2)
 {
     const TkReplayJob j = list_replay_job(ix, w, q0, nq, p);
     unsigned char *flags = w.repeat_flag.as<unsigned char>() + q0;
@@ -1162,7 +1166,7 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     TRY(pf.mark(st));
     // 4. strip sentinels, exact rescoring                   ivf.py:154-163
     tk_launch_rescore(q_dev, 0, ix->d, ix->data.p, ix->data_is_f64, ix->N, w.heap_idx.as<int64_t>(), p.R, nq, k, 1,
-                      out_dev, nullptr, st, ix->opt_rescore_form, q2, out2);
+                      out_dev, nullptr, st, ix->opt_rescore_form, q2, out2, nullptr, dist_dev, dist2);
     TRY(pf.mark(st));
     return TK_OK;
 }
@@ -1254,7 +1258,8 @@ static void launch_probes(tk_index *ix, const Pending &b, hipStream_t st)
 static int batch_back(tk_index *ix, Pending &b, hipStream_t st)
 {
     const Pending::Rows r = b.rows();
-    TRY(stage_back(ix, *b.w, r.q, 0, r.nq, b.k, b.p, r.out, st, b.pf, b.plain, r.q2, r.out2, nullptr, b.allow));
+    TRY(stage_back(ix, *b.w, r.q, 0, r.nq, b.k, b.p, r.out, st, b.pf, b.plain, r.q2, r.out2, nullptr, b.allow, r.dist,
+                   r.dist2));
     for (int i = 0; i < b.n_subs; i++) {
         const Pending::Sub &u = b.subs[i];
         if (u.host_out && u.host_out_kernel)
@@ -1572,7 +1577,7 @@ static int coalesce_call(tk_index *ix, Pending &b)
 static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_pq_dev,
                                 int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
                                 int64_t *out_ids_dev, int64_t *out_ids_pinned, hipEvent_t done_ev,
-                                void *stream, const tk_allow *allow = nullptr)
+                                void *stream, const tk_allow *allow = nullptr, void *out_dist_dev = nullptr)
 {
     Plan p;
     TRY(make_plan(ix, k, n_probes, pass_1, p));
@@ -1601,7 +1606,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     //  profiles/r04/bench_full_first.json)
     if (ix->depth > 1 && ix->coalesce == 2 && (ix->ids_unique || twin_replay(ix, p)) && nq >= 1 && nq <= ms) {
         Pending b(ix, p, k, n_probes, pass_1, q_pq_is_f64, allow, caller,
-                  {q_dev, q_pq_dev, out_ids_dev, nq, out_ids_pinned, ix->host_out_kernel, done_ev});
+                  {q_dev, q_pq_dev, out_ids_dev, nq, out_ids_pinned, ix->host_out_kernel, done_ev, out_dist_dev});
         return coalesce_call(ix, b);
     }
     TRY(launch_held(ix));
@@ -1609,11 +1614,13 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     // not 22 500 + 7 500 — the small rest fell below the list-major scan's threshold and took the query-major kernel)
     const int64_t parts = nq > ms ? (nq + ms - 1) / ms : 1;
     const int64_t part = (nq + parts - 1) / parts;
+    const size_t dsz = ix->data_is_f64 ? 8 : 4;         // the rescoring's type (the queries are float32)
     for (int64_t o = 0; o < nq; o += part) {
         const int64_t sub = nq - o < part ? nq - o : part;
         Pending b(ix, p, k, n_probes, pass_1, q_pq_is_f64, allow, caller,
                   {q_dev + o * ix->d, (const char *)q_pq_dev + (size_t)o * ix->dq * esz, out_ids_dev + o * k, sub,
-                   out_ids_pinned, ix->host_out_kernel, done_ev});
+                   out_ids_pinned, ix->host_out_kernel, done_ev,
+                   out_dist_dev ? (char *)out_dist_dev + (size_t)o * k * dsz : nullptr});
         if (ix->depth == 1) {
             ix->calls++;
             TRY(run_batch_inline(ix, b));
@@ -1767,7 +1774,7 @@ extern "C" int tk_index_quiesce(tk_index *ix)
 
 static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
                             int n_probes, int pass_1, int64_t *out_ids, int64_t *out_probes, int64_t *out_heap_idx,
-                            int32_t *out_heap_val, const tk_allow *allow)
+                            int32_t *out_heap_val, const tk_allow *allow, void *out_dist = nullptr)
 {
     IXLOCK(ix);
     Plan p;
@@ -1779,17 +1786,26 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     TRY(ix->q.ensure((size_t)nq * ix->d * 4));
     TRY(ix->qpq.ensure((size_t)nq * ix->dq * esz));
-    DevBuf outbuf;  // separate from the sub-batch `out` workspace
+    DevBuf outbuf, distbuf;  // separate from the sub-batch `out` workspace
+    const size_t dist_bytes = (size_t)nq * k * (ix->data_is_f64 ? 8 : 4);
     TRY(outbuf.ensure((size_t)nq * k * 8));
+    if (out_dist) {
+        const int e = distbuf.ensure(dist_bytes);
+        if (e != TK_OK) {
+            outbuf.release();
+            return e;
+        }
+    }
     HIPCHECK(hipMemcpy(ix->q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(ix->qpq.p, q_pq, (size_t)nq * ix->dq * esz, hipMemcpyHostToDevice));
     int r = query_batch_dev_impl(ix, ix->q.as<float>(), ix->qpq.p, q_pq_is_f64, nq, k, n_probes, pass_1,
-                                 outbuf.as<int64_t>(), nullptr, nullptr, nullptr, allow);
+                                 outbuf.as<int64_t>(), nullptr, nullptr, nullptr, allow, out_dist ? distbuf.p : nullptr);
     if (r == TK_OK) r = flush_pending(ix);
     const Work &lw = ix->works[(ix->calls + ix->works.size() - 1) % ix->works.size()];   // last used
     if (r == TK_OK) {
         hipError_t e = hipDeviceSynchronize();
         if (e == hipSuccess) e = hipMemcpy(out_ids, outbuf.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out_dist) e = hipMemcpy(out_dist, distbuf.p, dist_bytes, hipMemcpyDeviceToHost);
         if (e == hipSuccess && out_probes)
             e = hipMemcpy(out_probes, lw.probes.p, (size_t)nq * p.kc * 8, hipMemcpyDeviceToHost);
         if (e == hipSuccess && out_heap_idx)
@@ -1799,6 +1815,7 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
         if (e != hipSuccess) r = fail(TK_ERR_HIP, hipGetErrorString(e));
     }
     outbuf.release();
+    distbuf.release();
     return r;
 }
 
@@ -1832,6 +1849,27 @@ extern "C" int tk_index_query_batch_dev_allow(tk_index *ix, const tk_allow *allo
     if (!allow) return fail(TK_ERR_ARG, "bad argument: null allowed set");
     return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev,
                                 out_ids_pinned, (hipEvent_t)done_event, stream, allow);
+}
+
+// ids and the rescoring's exact squared distances (allow: NULL = every row) — tinyknn_hip.h
+extern "C" int tk_index_query_batch_dist(tk_index *ix, const tk_allow *allow, const float *q, const void *q_pq,
+                                         int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                                         int64_t *out_ids, void *out_dist)
+{
+    if (!out_dist && nq > 0) return fail(TK_ERR_ARG, "bad argument: null distance buffer");
+    return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, nullptr, nullptr, nullptr,
+                            allow, out_dist);
+}
+
+extern "C" int tk_index_query_batch_dev_dist(tk_index *ix, const tk_allow *allow, const float *q_dev,
+                                             const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k, int n_probes,
+                                             int pass_1, int64_t *out_ids_dev, void *out_dist_dev, void *done_event,
+                                             void *stream)
+{
+    IXLOCK(ix);
+    if (!out_dist_dev && nq > 0) return fail(TK_ERR_ARG, "bad argument: null distance buffer");
+    return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
+                                (hipEvent_t)done_event, stream, allow, out_dist_dev);
 }
 
 extern "C" int tk_index_set_heap_mode(tk_index *ix, int mode)

@@ -339,9 +339,10 @@ void launch_coarse_scan(tk_index *ix, Work &w, int64_t nq, const Plan &p, hipStr
                         const uint4 *tables = nullptr);
 // the replay over the coded centres of queries [0, nq) (one slot every query shares, positions as labels)
 TkReplayJob centre_replay_job(const tk_index *ix, Work &w, int64_t nq, const Plan &p);
+// dist (or NULL): the probes' exact float32 distances beside probes_out (FlatTop; the IVF coarse stage asks for none)
 int coarse_replay_probes(tk_index *ix, Work &w, const float *q_dev, int64_t nq, const Plan &p,
                          int64_t *probes_out, hipStream_t st, Prof &pf, TkSecond q2 = TkSecond(),
-                         const TkSlotsOut *slots = nullptr, int *slots_written = nullptr);
+                         const TkSlotsOut *slots = nullptr, int *slots_written = nullptr, float *dist = nullptr);
 void coarse_slots(tk_index *ix, Work &w, const int64_t *probes, int64_t nq, const Plan &p,
                   int *pair_count, const int *owner, int me, hipStream_t st, bool plain = false);
 int stage_coarse_rest(tk_index *ix, Work &w, const float *q_dev, int64_t nq, const Plan &p,
@@ -349,10 +350,11 @@ int stage_coarse_rest(tk_index *ix, Work &w, const float *q_dev, int64_t nq, con
                       bool plain = false, TkSecond q2 = TkSecond());
 // plain_flag (list-sharded home rank): queries the plain path's lemma does not cover raise bit 4 of
 // *plain_flag instead of being scanned again (the codes are on other ranks: the batch is repeated)
+// dist_dev / dist2 (or NULL): the rescoring's distances beside out_dev / out2 (tk_launch_rescore's dist / dist2)
 int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
                const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain = false,
                TkSecond q2 = TkSecond(), TkSecond out2 = TkSecond(), int *plain_flag = nullptr,
-               const tk_allow *allow = nullptr);
+               const tk_allow *allow = nullptr, void *dist_dev = nullptr, TkSecond dist2 = TkSecond());
 int head_chunks(const tk_index *ix, const Plan &p);    // chunks of a first probed list the exact kernel keeps (head mode)
 // the workspace's three pair sets: whole lists exact / plain tiles / heads
 TkPairSet exact_pairs(const Work &w);

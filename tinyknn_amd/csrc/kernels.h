@@ -304,11 +304,16 @@ struct TkSlotsOut {
 };
 // `slots`: a copy of the structure in DEVICE memory (17 pointers as kernel arguments would sit in scalar
 // registers for the whole kernel).  Returns 1 if it was given AND written by the rescoring kernel
-// (float32 operands staged through LDS, k <= 64), else 0: the caller then launches tk_launch_make_slots
+// (float32 operands staged through LDS, k <= 64, no distances), else 0: the caller then launches tk_launch_make_slots
+// dist (or NULL): (nq, k) squared distances beside `out` — of the type the arithmetic is done in (float64 if q or rows
+// is float64, else float32), +inf beside a -1; rows the heap order keeps (<= k candidates) get theirs too.  dist2.b:
+// the second call's own buffer (its rows from out2.n_a on; NULL: that call wants none).  With either, the
+// distance-writing forms of the kernels run and `slots` is ignored.
 int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int rows_is_f64,
                       int64_t n_rows, const int64_t *cand, int R, int64_t nq, int k, int strip,
                       int64_t *out, int *out_count, hipStream_t s, int form = 2, TkSecond q2 = TkSecond(),
-                      TkSecond out2 = TkSecond(), const TkSlotsOut *slots = nullptr);
+                      TkSecond out2 = TkSecond(), const TkSlotsOut *slots = nullptr, void *dist = nullptr,
+                      TkSecond dist2 = TkSecond());
 
 // probes (nq, kc) list ids -> per-slot scan descriptors; pair_count (n_lists, zeroed, or
 // NULL) receives the number of (query, slot) pairs per list — with `owner` (n_lists ranks,

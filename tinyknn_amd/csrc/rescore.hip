@@ -66,16 +66,17 @@ __device__ __forceinline__ T sqdist_row(const TY *__restrict__ y, const T *xs, i
 }
 
 // LDS: cand[R] (int64) | dist[R] (T) | x[d] (T)
-template <typename T, typename TY, typename TX>
-__global__ __launch_bounds__(128) void rescore_kernel(const TX *__restrict__ q, int d,
-                                                      const TY *__restrict__ rows,
-                                                      int64_t n_rows,
-                                                      const int64_t *__restrict__ cand, int R,
-                                                      int k, int strip, int64_t *__restrict__ out,
-                                                      int *__restrict__ out_count, const TX *__restrict__ q_b,
-                                                      int64_t q_na, int64_t *__restrict__ out_b, int64_t out_na)
+// DIST: also write the distance of every id written to out_d (second call of a pair: out_d_b; either may be NULL),
+// +inf beside a -1; where the heap holds <= k ids (no rescoring) their rows are read for it.  The ids-only kernels
+// below are this body with DIST = false, unchanged.
+template <typename T, typename TY, typename TX, bool DIST>
+__device__ __forceinline__ void rescore_body(unsigned char *smem, const TX *__restrict__ q, int d,
+                                             const TY *__restrict__ rows, int64_t n_rows,
+                                             const int64_t *__restrict__ cand, int R, int k, int strip,
+                                             int64_t *__restrict__ out, int *__restrict__ out_count,
+                                             const TX *__restrict__ q_b, int64_t q_na, int64_t *__restrict__ out_b,
+                                             int64_t out_na, T *__restrict__ out_d, T *__restrict__ out_d_b)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int64_t *cs = (int64_t *)smem;
     T *ds = (T *)(smem + (size_t)R * 8);
     T *xs = ds + R;
@@ -102,10 +103,23 @@ __global__ __launch_bounds__(128) void rescore_kernel(const TX *__restrict__ q, 
     }
     __syncthreads();
     const int nc = s_count;
-    int64_t *o = (out_b && qi >= out_na) ? out_b + (qi - out_na) * k : out + qi * k;
+    const bool second = out_b && qi >= out_na;
+    int64_t *o = second ? out_b + (qi - out_na) * k : out + qi * k;
+    T *od = nullptr;
+    if (DIST) od = second ? (out_d_b ? out_d_b + (qi - out_na) * k : nullptr) : (out_d ? out_d + qi * k : nullptr);
     if (nc <= k) {  // ivf.py:158-159 / fast_pq.py:307-308: heap order, no rescoring
         for (int t = tid; t < k; t += blockDim.x) o[t] = t < nc ? cs[t] : -1;
         if (tid == 0 && out_count) out_count[qi] = nc;
+        if (DIST && od)
+            for (int t = tid; t < k; t += blockDim.x) {
+                T dv = (T)__builtin_huge_valf();
+                if (t < nc) {
+                    int64_t id = cs[t];
+                    if (id < 0) id += n_rows;
+                    dv = sqdist_row<T, TY>(rows + id * (int64_t)d, xs, d);
+                }
+                od[t] = dv;
+            }
         return;
     }
     for (int t = tid; t < nc; t += blockDim.x) {
@@ -123,9 +137,40 @@ __global__ __launch_bounds__(128) void rescore_kernel(const TX *__restrict__ q, 
             const T du = ds[u];
             rank += (du < dv) || (du == dv && u < t);
         }
-        if (rank < k) o[rank] = cs[t];
+        if (rank < k) {
+            o[rank] = cs[t];
+            if (DIST && od) od[rank] = dv;
+        }
     }
     if (tid == 0 && out_count) out_count[qi] = k;
+}
+
+template <typename T, typename TY, typename TX>
+__global__ __launch_bounds__(128) void rescore_kernel(const TX *__restrict__ q, int d,
+                                                      const TY *__restrict__ rows,
+                                                      int64_t n_rows,
+                                                      const int64_t *__restrict__ cand, int R,
+                                                      int k, int strip, int64_t *__restrict__ out,
+                                                      int *__restrict__ out_count, const TX *__restrict__ q_b,
+                                                      int64_t q_na, int64_t *__restrict__ out_b, int64_t out_na)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rescore_body<T, TY, TX, false>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, q_b, q_na, out_b,
+                                   out_na, nullptr, nullptr);
+}
+
+template <typename T, typename TY, typename TX>
+__global__ __launch_bounds__(128) void rescore_dist_kernel(const TX *__restrict__ q, int d,
+                                                           const TY *__restrict__ rows, int64_t n_rows,
+                                                           const int64_t *__restrict__ cand, int R, int k, int strip,
+                                                           int64_t *__restrict__ out, int *__restrict__ out_count,
+                                                           const TX *__restrict__ q_b, int64_t q_na,
+                                                           int64_t *__restrict__ out_b, int64_t out_na,
+                                                           T *__restrict__ out_d, T *__restrict__ out_d_b)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rescore_body<T, TY, TX, true>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, q_b, q_na, out_b,
+                                  out_na, out_d, out_d_b);
 }
 
 // sqdist_row<float, float> for a row held in LDS as 16-byte pieces (explicit 128-bit reads: with
@@ -231,19 +276,18 @@ __device__ __forceinline__ void slots_epilogue(const TkSlotsOut &so, int64_t qi,
 // stride is an odd number of 16-byte pieces (conflict-free ds_read_b128), and each lane then
 // runs the identical summation (sqdist_row: numpy's order) on its row from LDS.
 // LDS: cand[R] (int64) | dist[R] | x[d] | tile[64 + 1 spare][stride]
-template <int TILE>
-__global__ __launch_bounds__(64) void rescore_staged_kernel(const float *__restrict__ q, int d,
-                                                            const float *__restrict__ rows,
-                                                            int64_t n_rows,
-                                                            const int64_t *__restrict__ cand, int R,
-                                                            int k, int strip, int64_t *__restrict__ out,
-                                                            int *__restrict__ out_count, int stride4,
-                                                            const float *__restrict__ q_b, int64_t q_na,
-                                                            int64_t *__restrict__ out_b, int64_t out_na,
-                                                            const TkSlotsOut *__restrict__ so_dev)
+// DIST as rescore_body (the short-heap branch reads its rows with sqdist_row: the same summation as sqdist_row_lds)
+template <int TILE, bool DIST>
+__device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const float *__restrict__ q, int d,
+                                                    const float *__restrict__ rows, int64_t n_rows,
+                                                    const int64_t *__restrict__ cand, int R, int k, int strip,
+                                                    int64_t *__restrict__ out, int *__restrict__ out_count,
+                                                    int stride4, const float *__restrict__ q_b, int64_t q_na,
+                                                    int64_t *__restrict__ out_b, int64_t out_na,
+                                                    const TkSlotsOut *__restrict__ so_dev, float *__restrict__ out_d,
+                                                    float *__restrict__ out_d_b)
 {
     const bool have_slots = so_dev != nullptr;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int64_t *cs = (int64_t *)smem;
     float *ds = (float *)(smem + (((size_t)R * 8 + 15) & ~(size_t)15));
     float *xs = ds + ((R + 3) & ~3);
@@ -265,10 +309,23 @@ __global__ __launch_bounds__(64) void rescore_staged_kernel(const float *__restr
         nc += __builtin_popcountll(m);
     }
     __syncthreads();
-    int64_t *o = (out_b && qi >= out_na) ? out_b + (qi - out_na) * k : out + qi * k;
+    const bool second = out_b && qi >= out_na;
+    int64_t *o = second ? out_b + (qi - out_na) * k : out + qi * k;
+    float *od = nullptr;
+    if (DIST) od = second ? (out_d_b ? out_d_b + (qi - out_na) * k : nullptr) : (out_d ? out_d + qi * k : nullptr);
     if (nc <= k) {  // ivf.py:158-159 / fast_pq.py:307-308: heap order, no rescoring
         for (int t = tid; t < k; t += 64) o[t] = t < nc ? cs[t] : -1;
         if (tid == 0 && out_count) out_count[qi] = nc;
+        if (DIST && od)
+            for (int t = tid; t < k; t += 64) {
+                float dv = __builtin_huge_valf();
+                if (t < nc) {
+                    int64_t id = cs[t];
+                    if (id < 0) id += n_rows;
+                    dv = sqdist_row<float, float>(rows + id * (int64_t)d, xs, d);
+                }
+                od[t] = dv;
+            }
         if (have_slots) slots_epilogue(*so_dev, qi, k, tid, tid < nc ? cs[tid < k ? tid : 0] : -1);
         return;
     }
@@ -312,6 +369,7 @@ __global__ __launch_bounds__(64) void rescore_staged_kernel(const float *__restr
         }
         if (rank < k) {
             o[rank] = cs[t];
+            if (DIST && od) od[rank] = dv;
             if (have_slots) ps[rank] = cs[t];
         }
     }
@@ -322,12 +380,47 @@ __global__ __launch_bounds__(64) void rescore_staged_kernel(const float *__restr
     }
 }
 
+template <int TILE>
+__global__ __launch_bounds__(64) void rescore_staged_kernel(const float *__restrict__ q, int d,
+                                                            const float *__restrict__ rows,
+                                                            int64_t n_rows,
+                                                            const int64_t *__restrict__ cand, int R,
+                                                            int k, int strip, int64_t *__restrict__ out,
+                                                            int *__restrict__ out_count, int stride4,
+                                                            const float *__restrict__ q_b, int64_t q_na,
+                                                            int64_t *__restrict__ out_b, int64_t out_na,
+                                                            const TkSlotsOut *__restrict__ so_dev)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rescore_staged_body<TILE, false>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride4, q_b, q_na,
+                                     out_b, out_na, so_dev, nullptr, nullptr);
+}
+
+// (no descriptors: the coarse stage, which writes them, asks for no distances)
+template <int TILE>
+__global__ __launch_bounds__(64) void rescore_staged_dist_kernel(const float *__restrict__ q, int d,
+                                                                 const float *__restrict__ rows, int64_t n_rows,
+                                                                 const int64_t *__restrict__ cand, int R, int k,
+                                                                 int strip, int64_t *__restrict__ out,
+                                                                 int *__restrict__ out_count, int stride4,
+                                                                 const float *__restrict__ q_b, int64_t q_na,
+                                                                 int64_t *__restrict__ out_b, int64_t out_na,
+                                                                 float *__restrict__ out_d, float *__restrict__ out_d_b)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rescore_staged_body<TILE, true>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride4, q_b, q_na,
+                                    out_b, out_na, nullptr, out_d, out_d_b);
+}
+
 int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int rows_is_f64,
                       int64_t n_rows, const int64_t *cand, int R, int64_t nq, int k, int strip,
                       int64_t *out, int *out_count, hipStream_t s, int form, TkSecond q2, TkSecond out2,
-                      const TkSlotsOut *slots)
+                      const TkSlotsOut *slots, void *dist, TkSecond dist2)
 {
     if (nq == 0 || k == 0) return 0;
+    const bool want_d = dist != nullptr || dist2.b != nullptr;
+    if (want_d) slots = nullptr;                // (the descriptors' caller asks for no distances)
+    void *dist_b = out2.b ? const_cast<void *>(dist2.b) : nullptr;     // (rows of the second call: out2.n_a on)
     const bool dbl = q_is_f64 || rows_is_f64;   // numpy promotes `Y - x` to float64
     size_t lds = (size_t)R * 8 + ((size_t)R + d) * (dbl ? 8 : 4) + 16;
     // one wave is enough for the coarse stage's 2 * n_probes + 10 candidates: the second wave of
@@ -353,6 +446,19 @@ int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int 
                             (size_t)(((R + 3) & ~3) + ((d + 3) & ~3)) * 4 + (size_t)(tile_rows + 1) * stride4 * 16 +
                             (fuse ? (size_t)k * 8 : 0);
         if (slds <= 64 * 1024) {
+            if (want_d) {
+                if (tile_rows == 32)
+                    hipLaunchKernelGGL(rescore_staged_dist_kernel<32>, grid, dim3(64), slds, s, (const float *)q, d,
+                                       (const float *)rows, n_rows, cand, R, k, strip, out, out_count, stride4,
+                                       (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, (float *)dist,
+                                       (float *)dist_b);
+                else
+                    hipLaunchKernelGGL(rescore_staged_dist_kernel<64>, grid, dim3(64), slds, s, (const float *)q, d,
+                                       (const float *)rows, n_rows, cand, R, k, strip, out, out_count, stride4,
+                                       (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, (float *)dist,
+                                       (float *)dist_b);
+                return 0;
+            }
             if (tile_rows == 32)
                 hipLaunchKernelGGL(rescore_staged_kernel<32>, grid, dim3(64), slds, s, (const float *)q, d,
                                    (const float *)rows, n_rows, cand, R, k, strip, out, out_count, stride4,
@@ -363,6 +469,27 @@ int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int 
                                    (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, so);
             return fuse ? 1 : 0;
         }
+    }
+    if (want_d) {
+        if (!dbl)
+            hipLaunchKernelGGL((rescore_dist_kernel<float, float, float>), grid, block, lds, s, (const float *)q, d,
+                               (const float *)rows, n_rows, cand, R, k, strip, out, out_count, (const float *)q2.b,
+                               q2.n_a, (int64_t *)out2.b, out2.n_a, (float *)dist, (float *)dist_b);
+        else if (rows_is_f64 && q_is_f64)
+            hipLaunchKernelGGL((rescore_dist_kernel<double, double, double>), grid, block, lds, s, (const double *)q,
+                               d, (const double *)rows, n_rows, cand, R, k, strip, out, out_count,
+                               (const double *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, (double *)dist,
+                               (double *)dist_b);
+        else if (rows_is_f64)
+            hipLaunchKernelGGL((rescore_dist_kernel<double, double, float>), grid, block, lds, s, (const float *)q, d,
+                               (const double *)rows, n_rows, cand, R, k, strip, out, out_count, (const float *)q2.b,
+                               q2.n_a, (int64_t *)out2.b, out2.n_a, (double *)dist, (double *)dist_b);
+        else
+            hipLaunchKernelGGL((rescore_dist_kernel<double, float, double>), grid, block, lds, s, (const double *)q,
+                               d, (const float *)rows, n_rows, cand, R, k, strip, out, out_count,
+                               (const double *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, (double *)dist,
+                               (double *)dist_b);
+        return 0;
     }
     if (!dbl)
         hipLaunchKernelGGL((rescore_kernel<float, float, float>), grid, block, lds, s,

@@ -251,8 +251,10 @@ class FlatTop:
         _lib.check(L.tk_index_set_centers(self._h, _lib.ptr(data, _lib._f32p), true_n, self.d,
                                           _lib.ptr(packed, _lib._u64p), packed.shape[0]))
 
-    def top(self, qs, k=1):
-        """(nq, d) float32 queries -> (nq, min(k, n)) int64 row ids."""
+    def top(self, qs, k=1, *, return_distances=False):
+        """(nq, d) float32 queries -> (nq, min(k, n)) int64 row ids.
+        return_distances: (ids, dists) — beside each id its exact float32 squared distance, the value
+        knn_brute1 ranked it by (tk_index_top_centers_dist)."""
         qs = np.ascontiguousarray(qs, dtype=np.float32)
         assert qs.ndim == 2 and qs.shape[1] == self.d
         k = min(int(k), self.n)
@@ -266,6 +268,12 @@ class FlatTop:
             qp = np.stack([self.pq._pq_query(q) for q in qs]) if len(qs) else np.zeros((0, 1), np.float32)
         qp = np.ascontiguousarray(qp)
         out = np.full((len(qs), k), -1, dtype=np.int64)
+        if return_distances:
+            dist = np.full((len(qs), k), np.inf, dtype=np.float32)
+            _lib.check(_lib.lib().tk_index_top_centers_dist(
+                self._h, _lib.ptr(qs, _lib._f32p), qp.ctypes.data, int(qp.dtype != np.float32), len(qs), k,
+                _lib.ptr(out, _lib._i64p), _lib.ptr(dist, _lib._f32p)))
+            return out, dist
         _lib.check(_lib.lib().tk_index_top_centers(
             self._h, _lib.ptr(qs, _lib._f32p), qp.ctypes.data, int(qp.dtype != np.float32), len(qs), k,
             _lib.ptr(out, _lib._i64p)))

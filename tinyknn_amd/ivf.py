@@ -582,10 +582,16 @@ class DeviceIndex:
         except Exception:
             pass
 
-    def query_batch(self, qn, q_pq, k, n_probes, pass_1=None, debug=False, *, allowed=None):
+    def query_batch(self, qn, q_pq, k, n_probes, pass_1=None, debug=False, *, allowed=None, return_distances=False):
         """qn: (nq, d) float32 normalised queries; q_pq: (nq, dq) table-build queries.
         allowed: None, or the rows the queries may return — an AllowSet (allow()), a bool mask of length N or row
-        ids (tk_index_query_batch_allow: the reference's `insert` only for those labels)."""
+        ids (tk_index_query_batch_allow: the reference's `insert` only for those labels).
+        return_distances: (ids, dists) — the same ids, and beside each the exact squared distance the rescoring
+        ranked it by (tk_index_query_batch_dist): float32, float64 for float64 vectors, +inf beside -1."""
+        if return_distances:
+            if debug:
+                raise ValueError("query_batch: debug=True cannot be combined with return_distances=True")
+            return self._query_batch_dist(qn, q_pq, k, n_probes, pass_1, allowed)
         if allowed is not None:
             return self._query_batch_allow(qn, q_pq, k, n_probes, pass_1, debug, allowed)
         qn = np.ascontiguousarray(qn, dtype=np.float32)
@@ -652,6 +658,24 @@ class DeviceIndex:
             return out, dict(probes=probes, heap_idx=hidx, heap_val=hval)
         return out
 
+    def _query_batch_dist(self, qn, q_pq, k, n_probes, pass_1, allowed):
+        aset, temp = self._allow_of(allowed) if allowed is not None else (None, False)
+        try:
+            qn = np.ascontiguousarray(qn, dtype=np.float32)
+            is64 = q_pq.dtype != np.float32
+            q_pq = np.ascontiguousarray(q_pq, dtype=np.float64 if is64 else np.float32)
+            nq = qn.shape[0]
+            assert qn.shape[1] == self.d and q_pq.shape == (nq, self.dq)
+            out = np.full((nq, k), -1, dtype=np.int64)
+            dist = np.full((nq, k), np.inf, dtype=np.float64 if self._data_is_f64() else np.float32)
+            _lib.check(_lib.lib().tk_index_query_batch_dist(
+                self._h, None if aset is None else aset.handle, _lib.ptr(qn, _lib._f32p), q_pq.ctypes.data,
+                int(is64), nq, int(k), int(n_probes), int(pass_1 or 0), _lib.ptr(out, _lib._i64p), dist.ctypes.data))
+        finally:
+            if temp:
+                aset.close()
+        return out, dist
+
     def query_batch_raw(self, qs, k, n_probes, pass_1=None):
         """Fast mode: raw float32 queries, normalisation / padding / rotation on the device
         (tk_index_prepare_dev: within 1 ulp of the host's BLAS results, not bit-identical)."""
@@ -674,7 +698,7 @@ class DeviceIndex:
         return out
 
     def query_batch_dev(self, qn_ptr, qpq_ptr, qpq_is_f64, nq, k, n_probes, out_ptr,
-                        pass_1=None, stream=0, done_event=None, *, allowed=None):
+                        pass_1=None, stream=0, done_event=None, *, allowed=None, dist_ptr=None):
         """Device pointers in, device pointer out, enqueued on `stream` (no sync).
         done_event: a hipEvent_t (integer handle) recorded behind the batch's last kernel, on
         whichever internal stream that runs (tk_index_query_batch_dev_ex).
@@ -683,7 +707,21 @@ class DeviceIndex:
         staging copy): all three buffers belong to the library until join() — or the call's
         done_event — as include/tinyknn_hip.h says for tk_index_set_pipeline.
         allowed: None or an AllowSet of this index (allow()), which must stay open until the call has run
-        (tk_index_query_batch_dev_allow)."""
+        (tk_index_query_batch_dev_allow).
+        dist_ptr: None, or a device buffer of nq * k distances (float32; float64 for float64 vectors) that receives
+        the rescoring's exact squared distances beside the ids, complete when out_ptr's ids are
+        (tk_index_query_batch_dev_dist)."""
+        if dist_ptr is not None:
+            aset = None
+            if allowed is not None:
+                if not isinstance(allowed, AllowSet):
+                    raise TypeError("query_batch_dev: allowed= takes a prepared set (DeviceIndex.allow / IVF.allow)")
+                aset, _ = self._allow_of(allowed)
+            _lib.check(_lib.lib().tk_index_query_batch_dev_dist(
+                self._h, None if aset is None else aset.handle, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k),
+                int(n_probes), int(pass_1 or 0), out_ptr, dist_ptr,
+                None if done_event is None else C.c_void_p(int(done_event)), stream))
+            return
         if allowed is not None:
             if not isinstance(allowed, AllowSet):
                 raise TypeError("query_batch_dev: allowed= takes a prepared set (DeviceIndex.allow / IVF.allow)")
@@ -1550,31 +1588,46 @@ class IVF:
         device, reused across calls; .close() frees it, len() = allowed stored rows."""
         return self._unsharded_device_index().allow(ids_or_mask)
 
-    def query(self, q, k, n_probes=1, pass_1=None, *, allowed=None):
+    def query(self, q, k, n_probes=1, pass_1=None, *, allowed=None, return_distances=False):
         """Top-k ids for one query.  reference: ivf.py:106-163
         allowed: the rows it may return (a bool mask of length N, row ids, or allow()'s set) — the reference's
-        query with `insert` only for those labels."""
+        query with `insert` only for those labels.
+        return_distances: (ids, dists) of the same length — the exact squared distance of each id to the
+        (normalised) query, as the rescoring computed it."""
         q = np.ascontiguousarray(q, dtype=np.float32)
         assert self.data.shape[1] == q.shape[0]
         qn, qp = self._prepare(q[None, :])
-        out = self._unsharded_device_index().query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed)[0]
+        dev = self._unsharded_device_index()
+        if return_distances:
+            ids, dist = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, return_distances=True)
+            out, dist = ids[0], dist[0]
+            if out[-1] == -1:
+                keep = out != -1
+                return out[keep], dist[keep]
+            return out, dist
+        out = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed)[0]
         return out[out != -1] if out[-1] == -1 else out
 
-    def query_batch(self, qs, k, n_probes=1, pass_1=None, fast=False, *, allowed=None):
+    def query_batch(self, qs, k, n_probes=1, pass_1=None, fast=False, *, allowed=None, return_distances=False):
         """(nq, d) queries -> (nq, k) int64 ids, rows padded with -1 when the
         reference would return fewer than k ids.  (The reference's README shows a
         2-d `ivf.query(queries, ...)` that its code does not support; this is that
         call.)  fast=True: normalisation, padding and rotation run on the device instead
         of numpy's per-query BLAS calls (35 ms per 10 000 queries on the host) — within
-        1 ulp of them, so a rare id can differ from the reference's; the default is exact."""
+        1 ulp of them, so a rare id can differ from the reference's; the default is exact.
+        return_distances: ((nq, k) ids, (nq, k) exact squared distances), INTEGRATION.md §2f."""
+        if return_distances and fast:
+            raise NotImplementedError("IVF.query_batch: fast=True with return_distances=True is not supported; "
+                                      "use the exact default (fast=False)")
         self._unsharded_device_index()
-        if allowed is not None:
+        if allowed is not None or return_distances:
             if fast:
                 raise NotImplementedError("IVF.query_batch: fast=True with allowed= is not supported; "
                                           "use the exact default (fast=False)")
             qs = np.array(qs, dtype=np.float32, order="C", copy=True)
             qn, qp = self._prepare(qs)
-            return self.device_index().query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed)
+            return self.device_index().query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed,
+                                                   return_distances=return_distances)
         if fast:
             return self.device_index().query_batch_raw(qs, k, n_probes, pass_1)
         R = self.pq.R
