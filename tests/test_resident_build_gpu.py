@@ -263,3 +263,30 @@ def test_reduced_c5_lists_far_longer_than_the_heap(oracle, tmp_path):
             np.testing.assert_array_equal(o.cpu().numpy(), want)
         dev.set_pipeline(1)
     dev.close()
+
+
+def test_allowed_sets_on_a_resident_index():
+    """IVF.allow on an index built in HBM: the set is made, answers as the mask it was made from, returns allowed
+    rows only, and goes when the device index is closed (a resident index once lacked the registry of its sets)."""
+    from tinyknn_amd import IVF, FastPQ
+    from tinyknn_amd.ivf import AllowSet
+    n, d, nq, seed = 20000, 64, 120, 9
+    cent = np.random.RandomState(4).randn(20, d).astype(np.float32)
+    ivf = IVF("euclidean", 30, FastPQ(2))
+    ivf.fit(synth_rows(5000, d, seed, cent, 0.8))
+    ivf.build_resident(n, d, seed, cent, 0.8)
+    dev = ivf.device_index()
+    mask = np.random.RandomState(5).rand(n) < 0.3
+    aset = ivf.allow(mask)
+    assert isinstance(aset, AllowSet) and len(aset) == int(mask.sum())       # (one list per row)
+    qn, qp = ivf._prepare(synth_rows(nq, d, seed + 1, cent, 0.8))
+    for n_probes in (1, 6):
+        with_set = dev.query_batch(qn, qp, 10, n_probes, allowed=aset)
+        np.testing.assert_array_equal(with_set, dev.query_batch(qn, qp, 10, n_probes, allowed=mask))
+        assert (with_set >= 0).any() and mask[with_set[with_set >= 0]].all()
+        np.testing.assert_array_equal(ivf.query_batch(synth_rows(nq, d, seed + 1, cent, 0.8), 10, n_probes, allowed=aset),
+                                      with_set)
+    dev.close()
+    assert aset._h is None
+    with pytest.raises(ValueError, match="closed"):
+        aset.handle

@@ -247,15 +247,8 @@ extern "C" int tk_index_build_dev(tk_index *ix, int normalise, const float *all_
         ARGCHECK(last < L, "a centre that received no row precedes one that did: the reference's "
                            "group_data_by_indices asserts max(index) < n_active (utils.py:128)");
     }
-    std::vector<int64_t> coff((size_t)L + 1, 0), ioff((size_t)L + 1, 0);
-    int64_t maxc = 0;
-    for (int64_t i = 0; i < L; i++) {
-        const int64_t c = (sizes[(size_t)i] + 15) / 16;
-        coff[(size_t)i + 1] = coff[(size_t)i] + c;
-        ioff[(size_t)i + 1] = ioff[(size_t)i] + sizes[(size_t)i];
-        if (c > maxc) maxc = c;
-    }
-    ARGCHECK(maxc < (1ll << 26), "list too long");
+    ListLayout lay;
+    TRY(lay.set_sizes(sizes.data(), L));
     TRY(remap.ensure((size_t)C * 4));
     HIPCHECK(hipMemcpy(remap.p, rm.data(), (size_t)C * 4, hipMemcpyHostToDevice));
     tk_launch_remap_keys(keys.as<int>(), T, remap.as<int>(), 0);
@@ -278,39 +271,27 @@ extern "C" int tk_index_build_dev(tk_index *ix, int normalise, const float *all_
     TRY(set_centre_slots(ix, L, (L + 15) / 16));
     const int P = M / 2;
     // ---- 6. the index: lists
-    TRY(ix->list_chunk_off.ensure((size_t)(L + 1) * 8));
-    TRY(ix->ids_off.ensure((size_t)(L + 1) * 8));
-    TRY(ix->list_n.ensure((size_t)L * 8));
-    TRY(ix->ids.ensure((size_t)T * 8));
-    HIPCHECK(hipMemcpy(ix->list_chunk_off.p, coff.data(), (size_t)(L + 1) * 8, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ix->ids_off.p, ioff.data(), (size_t)(L + 1) * 8, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ix->list_n.p, sizes.data(), (size_t)L * 8, hipMemcpyHostToDevice));
-    const size_t tiled_bytes = (size_t)tk_tiled_uint4s(coff[(size_t)L], P) * 16;
-    TRY(ix->codes.ensure(tiled_bytes));
-    HIPCHECK(hipMemset(ix->codes.p, 0, tiled_bytes));
-    tk_launch_pack_lists(labels.as<uint8_t>(), M, rows2.as<int>(), ix->ids_off.as<int64_t>(),
-                         ix->list_chunk_off.as<int64_t>(), ix->list_n.as<int64_t>(), (int)L, zero_code,
-                         ix->codes.as<uint4>(), coff[(size_t)L], 0);
-    tk_launch_widen_ids(rows2.as<int>(), T, ix->ids.as<int64_t>(), 0);
+    TRY(lay.ids.ensure((size_t)T * 8));
+    const size_t tiled_bytes = (size_t)tk_tiled_uint4s(lay.total_chunks, P) * 16;
+    TRY(lay.codes.ensure(tiled_bytes));
+    HIPCHECK(hipMemset(lay.codes.p, 0, tiled_bytes));
+    tk_launch_pack_lists(labels.as<uint8_t>(), M, rows2.as<int>(), lay.ids_off.as<int64_t>(),
+                         lay.list_chunk_off.as<int64_t>(), lay.list_n.as<int64_t>(), (int)L, zero_code,
+                         lay.codes.as<uint4>(), lay.total_chunks, 0);
+    tk_launch_widen_ids(rows2.as<int>(), T, lay.ids.as<int64_t>(), 0);
     HIPCHECK(hipGetLastError());
-    ix->ids_unique = kp == 1;       // one list per row: no label can repeat
-    ix->labels24 = ix->N < 0x00ffffff;      // (labels are row numbers)
-    ix->have_ids32 = false;
     if (kp > 1) {                   // the lane replay's duplicate test reads the labels as int32
-        TRY(ix->ids32.ensure((size_t)T * 4));
-        HIPCHECK(hipMemcpyAsync(ix->ids32.p, rows2.p, (size_t)T * 4, hipMemcpyDeviceToDevice, 0));
-        ix->have_ids32 = true;
+        TRY(lay.ids32.ensure((size_t)T * 4));
+        HIPCHECK(hipMemcpyAsync(lay.ids32.p, rows2.p, (size_t)T * 4, hipMemcpyDeviceToDevice, 0));
+        lay.have_ids32 = true;
     }
     HIPCHECK(hipDeviceSynchronize());
-    ix->sharded = false; ix->rank = 0; ix->world = 1;
-    ix->total_chunks = coff[(size_t)L];
-    ix->total_ids = T;
-    ix->max_list_chunks = (int)maxc;
-    ix->have_centers = ix->have_lists = ix->have_data = true;
-    ix->lists_gen++;
-    ix->list_cols = cols;
-    ix->list_kp = kp;
-    TRY(build_twins(ix, N));
+    lay.ids_unique = kp == 1;       // one list per row: no label can repeat
+    lay.max_label = N - 1;          // (labels are row numbers)
+    lay.list_cols = cols;
+    lay.kp = kp;
+    ix->have_centers = ix->have_data = true;
+    TRY(install_lists(ix, lay));
     if (n_active_out) *n_active_out = L;
     return TK_OK;
 }
@@ -406,10 +387,10 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
     }
     const size_t esz = rows_is_f64 ? 8 : 4;
     DevBuf grown, yt, yn, near, keys, prow, keys2, rows2, count, lab, rot, tmp, zrow, zlab, crow, clab, coffs,
-        act1, ccodes, codes1, ids1, ids32_1, coff_d, ioff_d, n_d, noff_d, seg_d;
+        act1, ccodes, noff_d, seg_d;
     BufCleanup cl{{&grown, &yt, &yn, &near, &keys, &prow, &keys2, &rows2, &count, &lab, &rot, &tmp, &zrow, &zlab,
-                   &crow, &clab, &coffs, &act1, &ccodes, &codes1, &ids1, &ids32_1, &coff_d, &ioff_d, &n_d,
-                   &noff_d, &seg_d}};
+                   &crow, &clab, &coffs, &act1, &ccodes, &noff_d, &seg_d}};
+    ListLayout lay;
     // ---- 1. the rows behind the old ones (a larger buffer where they do not fit: the old one stays intact)
     void *base = ix->data.p;
     if ((size_t)N1 * d * esz > ix->data.cap) {
@@ -451,9 +432,7 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
                         "group_data_by_indices asserts max(index) < n_active (utils.py:128)");
     ARGCHECK(L1 == L0 || all_centers, "new lists: all_centers");
     // ---- 4. the new layout: list l's column block j = old_j ++ new_j
-    std::vector<int64_t> coff((size_t)L1 + 1, 0), ioff((size_t)L1 + 1, 0), size1((size_t)L1), noff((size_t)L1 + 1, 0),
-        seg((size_t)L1 * kp * 2), cols1((size_t)L1 * kp);
-    int64_t maxc = 0;
+    std::vector<int64_t> size1((size_t)L1), noff((size_t)L1 + 1, 0), seg((size_t)L1 * kp * 2), cols1((size_t)L1 * kp);
     for (int64_t l = 0; l < L1; l++) {
         int64_t s = 0, sn = 0;
         for (int t = 0; t < kp; t++) {
@@ -465,14 +444,10 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
             sn += nn;
         }
         size1[(size_t)l] = s;
-        const int64_t c = (s + 15) / 16;
-        coff[(size_t)l + 1] = coff[(size_t)l] + c;
-        ioff[(size_t)l + 1] = ioff[(size_t)l] + s;
         noff[(size_t)l + 1] = noff[(size_t)l] + sn;
-        if (c > maxc) maxc = c;
     }
-    ARGCHECK(maxc < (1ll << 26), "list too long");
-    const int64_t chunks1 = coff[(size_t)L1], T1 = ioff[(size_t)L1];
+    TRY(lay.set_sizes(size1.data(), L1));
+    const int64_t chunks1 = lay.total_chunks, T1 = lay.total_ids;
     // ---- 5. new pairs grouped by list (centre ids are list ids: the active set is a prefix)
     TRY(sort_pairs_dev(keys, prow, keys2, rows2, tmp, T, L1));
     // ---- 6. codes of the new rows (given, or as the build encodes them), of the zero vector, of new centres
@@ -505,36 +480,28 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
         }
     }
     // ---- 7. the merged lists
-    TRY(coff_d.ensure((size_t)(L1 + 1) * 8));
-    TRY(ioff_d.ensure((size_t)(L1 + 1) * 8));
-    TRY(n_d.ensure((size_t)L1 * 8));
     TRY(noff_d.ensure((size_t)(L1 + 1) * 8));
     TRY(seg_d.ensure(seg.size() * 8));
-    HIPCHECK(hipMemcpy(coff_d.p, coff.data(), coff.size() * 8, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ioff_d.p, ioff.data(), ioff.size() * 8, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(n_d.p, size1.data(), size1.size() * 8, hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(noff_d.p, noff.data(), noff.size() * 8, hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(seg_d.p, seg.data(), seg.size() * 8, hipMemcpyHostToDevice));
     const size_t tiled_bytes = (size_t)tk_tiled_uint4s(chunks1, P) * 16;
-    TRY(codes1.ensure(tiled_bytes));
-    HIPCHECK(hipMemset(codes1.p, 0, tiled_bytes));
-    TRY(ids1.ensure((size_t)T1 * 8));
-    if (kp > 1) TRY(ids32_1.ensure((size_t)T1 * 4));
+    TRY(lay.codes.ensure(tiled_bytes));
+    HIPCHECK(hipMemset(lay.codes.p, 0, tiled_bytes));
+    TRY(lay.ids.ensure((size_t)T1 * 8));
+    lay.have_ids32 = kp > 1;
+    if (lay.have_ids32) TRY(lay.ids32.ensure((size_t)T1 * 4));
     tk_launch_merge_lists(ix->codes.as<uint4>(), ix->list_chunk_off.as<int64_t>(), ix->ids_off.as<int64_t>(),
                           ix->ids.as<int64_t>(), lab.as<uint8_t>(), M, rows2.as<int>(), noff_d.as<int64_t>(),
-                          seg_d.as<int64_t>(), kp, coff_d.as<int64_t>(), ioff_d.as<int64_t>(), n_d.as<int64_t>(),
-                          (int)L1, zlab.as<uint8_t>(), N0, codes1.as<uint4>(), ids1.as<int64_t>(),
-                          kp > 1 ? ids32_1.as<int32_t>() : nullptr, chunks1, 0);
+                          seg_d.as<int64_t>(), kp, lay.list_chunk_off.as<int64_t>(), lay.ids_off.as<int64_t>(),
+                          lay.list_n.as<int64_t>(), (int)L1, zlab.as<uint8_t>(), N0, lay.codes.as<uint4>(),
+                          lay.ids.as<int64_t>(), lay.have_ids32 ? lay.ids32.as<int32_t>() : nullptr, chunks1, 0);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
-    // ---- 8. the swap: the old buffers go with the cleanup
-    std::swap(ix->codes, codes1);
-    std::swap(ix->ids, ids1);
-    std::swap(ix->list_chunk_off, coff_d);
-    std::swap(ix->ids_off, ioff_d);
-    std::swap(ix->list_n, n_d);
-    if (kp > 1) std::swap(ix->ids32, ids32_1);
-    else ix->ids32.release();
+    lay.ids_unique = kp == 1;
+    lay.max_label = N1 - 1;
+    lay.list_cols = cols1;
+    lay.kp = kp;
+    // ---- 8. the swap: the old buffers go with the cleanup and the layout
     if (grown.p) std::swap(ix->data, grown);
     if (L1 > L0) {
         std::swap(ix->active_centers, act1);
@@ -542,16 +509,7 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
         TRY(set_centre_slots(ix, L1, (L1 + 15) / 16));     // (buffers of a few bytes that already exist)
     }
     ix->N = N1;
-    ix->total_chunks = chunks1;
-    ix->total_ids = T1;
-    ix->max_list_chunks = (int)maxc;
-    ix->ids_unique = kp == 1;
-    ix->labels24 = N1 - 1 < 0x00ffffff;
-    ix->have_ids32 = kp > 1;
-    ix->lists_gen++;
-    ix->list_cols = cols1;
-    ix->list_kp = kp;
-    TRY(build_twins(ix, N1));
+    TRY(install_lists(ix, lay));
     if (n_active_out) *n_active_out = L1;
     return TK_OK;
 }
@@ -591,10 +549,9 @@ extern "C" int tk_index_remove_rows(tk_index *ix, const int64_t *rows, int64_t n
     }
     if (n == 0) return TK_OK;
     TRY(settle_lists(ix));
-    DevBuf rows_d, dead, keep, scan, tmp, bad, pos_d, gat, src, rot, zrow, zlab, codes1, ids1, ids32_1, coff_d, ioff_d,
-        n_d, cnt, summ;
-    BufCleanup cl{{&rows_d, &dead, &keep, &scan, &tmp, &bad, &pos_d, &gat, &src, &rot, &zrow, &zlab, &codes1, &ids1,
-                   &ids32_1, &coff_d, &ioff_d, &n_d, &cnt, &summ}};
+    DevBuf rows_d, dead, keep, scan, tmp, bad, pos_d, gat, src, rot, zrow, zlab, cnt, summ;
+    BufCleanup cl{{&rows_d, &dead, &keep, &scan, &tmp, &bad, &pos_d, &gat, &src, &rot, &zrow, &zlab, &cnt, &summ}};
+    ListLayout lay;
     // ---- 1. the dead rows, keep / drop per stored entry, its exclusive scan (new positions)
     TRY(rows_d.ensure((size_t)n * 8));
     HIPCHECK(hipMemcpy(rows_d.p, rv.data(), (size_t)n * 8, hipMemcpyHostToDevice));
@@ -634,17 +591,11 @@ extern "C" int tk_index_remove_rows(tk_index *ix, const int64_t *rows, int64_t n
     ARGCHECK(!bad_h, "the index holds labels outside [0, N): its rows cannot be named");
     const int64_t T1 = g.back();
     if (T1 == T0) return TK_OK;     // nothing stored was named: the index stays exactly as it is
-    std::vector<int64_t> coff((size_t)L + 1, 0), ioff((size_t)L + 1, 0), size1((size_t)L), cols1((size_t)(L * cw));
-    int64_t maxc = 0;
+    std::vector<int64_t> size1((size_t)L), cols1((size_t)(L * cw));
     for (int64_t l = 0; l < L; l++) {
         for (int t = 0; t < cw; t++) cols1[(size_t)(l * cw + t)] = g[(size_t)(l * cw + t) + 1] - g[(size_t)(l * cw + t)];
-        const int64_t s = g[(size_t)(l + 1) * cw] - g[(size_t)l * cw], c = (s + 15) / 16;
-        size1[(size_t)l] = s;
-        coff[(size_t)l + 1] = coff[(size_t)l] + c;
-        ioff[(size_t)l + 1] = ioff[(size_t)l] + s;
-        if (c > maxc) maxc = c;
+        size1[(size_t)l] = g[(size_t)(l + 1) * cw] - g[(size_t)l * cw];
     }
-    const int64_t chunks1 = coff[(size_t)L];
     // ---- 3. the old position of every kept entry; the zero vector's code (list padding)
     TRY(src.ensure((size_t)(T1 > 0 ? T1 : 1) * 4));
     tk_launch_scatter_kept(keep.as<long long>(), scan.as<long long>(), T0, src.as<int>(), 0);
@@ -653,53 +604,35 @@ extern "C" int tk_index_remove_rows(tk_index *ix, const int64_t *rows, int64_t n
     TRY(zlab.ensure((size_t)16 * ix->M));
     HIPCHECK(hipMemset(zrow.p, 0, (size_t)16 * ix->d * 4));
     TRY(encode_rows_dev(ix, zrow.as<float>(), 16, rot, zlab.as<uint8_t>()));
-    // ---- 4. the compacted lists
-    TRY(coff_d.ensure((size_t)(L + 1) * 8));
-    TRY(ioff_d.ensure((size_t)(L + 1) * 8));
-    TRY(n_d.ensure((size_t)L * 8));
-    HIPCHECK(hipMemcpy(coff_d.p, coff.data(), coff.size() * 8, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ioff_d.p, ioff.data(), ioff.size() * 8, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(n_d.p, size1.data(), size1.size() * 8, hipMemcpyHostToDevice));
+    // ---- 4. the compacted lists (their small arrays are allocated while the kernels above run)
+    TRY(lay.set_sizes(size1.data(), L));
+    const int64_t chunks1 = lay.total_chunks;
     const size_t tiled_bytes = (size_t)tk_tiled_uint4s(chunks1, ix->M / 2) * 16;
-    TRY(codes1.ensure(tiled_bytes > 0 ? tiled_bytes : 16));
-    HIPCHECK(hipMemset(codes1.p, 0, tiled_bytes > 0 ? tiled_bytes : 16));
-    TRY(ids1.ensure((size_t)(T1 > 0 ? T1 : 1) * 8));
+    TRY(lay.codes.ensure(tiled_bytes > 0 ? tiled_bytes : 16));
+    HIPCHECK(hipMemset(lay.codes.p, 0, tiled_bytes > 0 ? tiled_bytes : 16));
+    TRY(lay.ids.ensure((size_t)(T1 > 0 ? T1 : 1) * 8));
     const bool want32 = ix->have_ids32 && T1 > 0;
-    if (want32) TRY(ids32_1.ensure((size_t)T1 * 4));
+    if (want32) TRY(lay.ids32.ensure((size_t)T1 * 4));
     tk_launch_compact_lists(ix->codes.as<uint4>(), ix->list_chunk_off.as<int64_t>(), ix->ids_off.as<int64_t>(),
-                            ix->ids.as<int64_t>(), src.as<int>(), ix->M, coff_d.as<int64_t>(), ioff_d.as<int64_t>(),
-                            n_d.as<int64_t>(), (int)L, zlab.as<uint8_t>(), codes1.as<uint4>(), ids1.as<int64_t>(),
-                            want32 ? ids32_1.as<int32_t>() : nullptr, chunks1, 0);
+                            ix->ids.as<int64_t>(), src.as<int>(), ix->M, lay.list_chunk_off.as<int64_t>(),
+                            lay.ids_off.as<int64_t>(), lay.list_n.as<int64_t>(), (int)L, zlab.as<uint8_t>(),
+                            lay.codes.as<uint4>(), lay.ids.as<int64_t>(), want32 ? lay.ids32.as<int32_t>() : nullptr,
+                            chunks1, 0);
     HIPCHECK(hipGetLastError());
     // ---- 5. what tk_index_set_lists derives from the labels: distinct?  the largest?
     int cs[4];
-    TRY(row_copies(ix, ids1.as<int64_t>(), T1, cnt, summ, cs));
+    TRY(row_copies(ix, lay.ids.as<int64_t>(), T1, cnt, summ, cs));
     HIPCHECK(hipDeviceSynchronize());
-    const bool unique = cs[1] <= 1;
-    // ---- 6. the swap: the old buffers go with the cleanup
-    std::swap(ix->codes, codes1);
-    std::swap(ix->ids, ids1);
-    std::swap(ix->list_chunk_off, coff_d);
-    std::swap(ix->ids_off, ioff_d);
-    std::swap(ix->list_n, n_d);
-    if (want32 && !unique) std::swap(ix->ids32, ids32_1);
-    else ix->ids32.release();
-    ix->total_chunks = chunks1;
-    ix->total_ids = T1;
-    ix->max_list_chunks = (int)maxc;
-    ix->ids_unique = unique;
-    ix->have_ids32 = want32 && !unique;
-    ix->labels24 = cs[0] < 0x00ffffff;
-    ix->lists_gen++;
+    lay.ids_unique = cs[1] <= 1;
+    lay.have_ids32 = want32 && !lay.ids_unique;
+    // (the largest label as tk_index_set_lists finds it: the same twin table as an upload of these lists)
+    lay.max_label = cs[0];
     if (cols_src) {
-        ix->list_cols = cols1;
-        ix->list_kp = kp;
-    } else {
-        ix->list_cols.clear();
-        ix->list_kp = 0;
+        lay.list_cols = cols1;
+        lay.kp = kp;
     }
-    // (the labels' bound as tk_index_set_lists takes it: the same twin table as an upload of these lists)
-    TRY(build_twins(ix, (int64_t)cs[0] + 1));
+    // ---- 6. the swap: the old buffers go with the layout
+    TRY(install_lists(ix, lay));
     if (removed_out) *removed_out = T0 - T1;
     return TK_OK;
 }

@@ -201,7 +201,7 @@ static int build_twins_try(tk_index *ix, int64_t label_bound, TwinScratch &t)
     return TK_OK;
 }
 
-int build_twins(tk_index *ix, int64_t label_bound)
+static int build_twins(tk_index *ix, int64_t label_bound)
 {
     ix->twin_w = 0;
     ix->twin_unverified = false;
@@ -223,6 +223,38 @@ int build_twins(tk_index *ix, int64_t label_bound)
     return TK_OK;
 }
 
+// (api_internal.h) every field that derives from the lists is set here and nowhere else
+int install_lists(tk_index *ix, ListLayout &lay)
+{
+    std::swap(ix->codes, lay.codes);
+    std::swap(ix->ids, lay.ids);
+    std::swap(ix->list_chunk_off, lay.list_chunk_off);
+    std::swap(ix->ids_off, lay.ids_off);
+    std::swap(ix->list_n, lay.list_n);
+    std::swap(ix->ids32, lay.ids32);
+    if (!lay.have_ids32) ix->ids32.release();
+    // only an upload makes a list-sharded index (tk_index_add_rows / _remove_rows refuse one in their first lines)
+    ix->sharded = lay.sharded;
+    ix->rank = lay.sharded ? lay.rank : 0;
+    ix->world = lay.sharded ? lay.world : 1;
+    if (lay.sharded) {
+        std::swap(ix->owner, lay.owner);
+        std::swap(ix->local_chunk_off, lay.local_chunk_off);
+    }
+    ix->total_chunks = lay.total_chunks;
+    ix->total_ids = lay.total_ids;
+    ix->max_list_chunks = (int)lay.max_list_chunks;
+    ix->ids_unique = lay.ids_unique;
+    ix->have_ids32 = lay.have_ids32;
+    ix->labels24 = lay.max_label < 0x00ffffff;
+    ix->list_cols.swap(lay.list_cols);
+    ix->list_kp = ix->list_cols.empty() ? 0 : lay.kp;
+    ix->have_lists = true;
+    ix->lists_gen++;
+    // labels that repeat: where every row's other copies are (the lane replay's duplicate test)
+    return build_twins(ix, lay.max_label + 1);
+}
+
 extern "C" int tk_index_twin_table(tk_index *ix, int64_t *rows, int *w, int32_t *list_out, int32_t *off_out)
 {
     IXLOCK(ix);
@@ -242,91 +274,58 @@ static int set_lists_impl(tk_index *ix, const int64_t *list_sizes, const uint64_
 {
     ARGCHECK(ix && ix->have_centers, "set_centers first");
     const int64_t L = ix->n_lists;
-    std::vector<int64_t> coff(L + 1, 0), ioff(L + 1, 0), loff(L + 1, 0);
-    int64_t maxc = 0;
+    std::vector<int64_t> loff(L + 1, 0);       // the chunks this rank stores
     for (int64_t i = 0; i < L; i++) {
         ARGCHECK(list_sizes[i] >= 0, "negative list size");
         ARGCHECK(!owner || (owner[i] >= 0 && owner[i] < world), "owner out of range");
-        int64_t c = (list_sizes[i] + 15) / 16;
-        coff[i + 1] = coff[i] + c;
-        loff[i + 1] = loff[i] + ((!owner || owner[i] == rank) ? c : 0);
-        ioff[i + 1] = ioff[i] + list_sizes[i];
-        if (c > maxc) maxc = c;
+        loff[i + 1] = loff[i] + ((!owner || owner[i] == rank) ? (list_sizes[i] + 15) / 16 : 0);
     }
-    ARGCHECK(maxc < (1ll << 26), "list too long");
+    ListLayout lay;
+    TRY(lay.set_sizes(list_sizes, L));
     // are the labels pairwise distinct?  (IVF.build(n_probes=1): every point in one list)
-    {
-        bool uniq = true;
-        const int64_t T = ioff[L];
-        int64_t mn = 0, mx = -1;
-        for (int64_t i = 0; i < T; i++) {
-            if (i == 0 || ids[i] < mn) mn = ids[i];
-            if (i == 0 || ids[i] > mx) mx = ids[i];
-        }
-        if (T > 0 && mn >= 0 && mx < 64 * T + 1024) {
-            std::vector<uint64_t> seen((size_t)(mx / 64 + 1), 0);
-            for (int64_t i = 0; i < T && uniq; i++) {
-                uint64_t bit = 1ull << (ids[i] & 63);
-                if (seen[(size_t)(ids[i] >> 6)] & bit) uniq = false;
-                seen[(size_t)(ids[i] >> 6)] |= bit;
-            }
-        } else if (T > 0) {
-            std::vector<int64_t> tmp(ids, ids + T);
-            std::sort(tmp.begin(), tmp.end());
-            for (int64_t i = 1; i < T && uniq; i++) uniq = tmp[i] != tmp[i - 1];
-            if (mn < 0) uniq = false;  // a label -1 would match the heap's sentinel
-        }
-        ix->ids_unique = uniq;
+    bool uniq = true;
+    const int64_t T = lay.total_ids;
+    int64_t mn = 0, mx = -1;
+    for (int64_t i = 0; i < T; i++) {
+        if (i == 0 || ids[i] < mn) mn = ids[i];
+        if (i == 0 || ids[i] > mx) mx = ids[i];
     }
-    TRY(upload_tiled(ix->codes, ix->stage, codes, loff[L], ix->M));
-    ix->sharded = owner != nullptr;
-    ix->rank = owner ? rank : 0;
-    ix->world = owner ? world : 1;
+    if (T > 0 && mn >= 0 && mx < 64 * T + 1024) {
+        std::vector<uint64_t> seen((size_t)(mx / 64 + 1), 0);
+        for (int64_t i = 0; i < T && uniq; i++) {
+            uint64_t bit = 1ull << (ids[i] & 63);
+            if (seen[(size_t)(ids[i] >> 6)] & bit) uniq = false;
+            seen[(size_t)(ids[i] >> 6)] |= bit;
+        }
+    } else if (T > 0) {
+        std::vector<int64_t> tmp(ids, ids + T);
+        std::sort(tmp.begin(), tmp.end());
+        for (int64_t i = 1; i < T && uniq; i++) uniq = tmp[i] != tmp[i - 1];
+        if (mn < 0) uniq = false;  // a label -1 would match the heap's sentinel
+    }
+    TRY(upload_tiled(lay.codes, ix->stage, codes, loff[L], ix->M));
+    lay.sharded = owner != nullptr;
     if (owner) {
-        TRY(ix->owner.ensure((size_t)L * 4));
-        TRY(ix->local_chunk_off.ensure((size_t)(L + 1) * 8));
-        HIPCHECK(hipMemcpy(ix->owner.p, owner, (size_t)L * 4, hipMemcpyHostToDevice));
-        HIPCHECK(hipMemcpy(ix->local_chunk_off.p, loff.data(), (size_t)(L + 1) * 8,
-                           hipMemcpyHostToDevice));
+        lay.rank = rank;
+        lay.world = world;
+        TRY(lay.owner.ensure((size_t)L * 4));
+        TRY(lay.local_chunk_off.ensure((size_t)(L + 1) * 8));
+        HIPCHECK(hipMemcpy(lay.owner.p, owner, (size_t)L * 4, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(lay.local_chunk_off.p, loff.data(), (size_t)(L + 1) * 8, hipMemcpyHostToDevice));
     }
-    TRY(ix->list_chunk_off.ensure((size_t)(L + 1) * 8));
-    TRY(ix->ids_off.ensure((size_t)(L + 1) * 8));
-    TRY(ix->list_n.ensure((size_t)L * 8));
-    TRY(ix->ids.ensure((size_t)(ioff[L] > 0 ? ioff[L] : 1) * 8));
-    HIPCHECK(hipMemcpy(ix->list_chunk_off.p, coff.data(), (size_t)(L + 1) * 8, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ix->ids_off.p, ioff.data(), (size_t)(L + 1) * 8, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ix->list_n.p, list_sizes, (size_t)L * 8, hipMemcpyHostToDevice));
-    if (ioff[L] > 0)
-        HIPCHECK(hipMemcpy(ix->ids.p, ids, (size_t)ioff[L] * 8, hipMemcpyHostToDevice));
-    {   // int32 copy of the labels for the lane kernel's duplicate test
-        bool fits = true;
-        for (int64_t i = 0; i < ioff[L] && fits; i++) fits = ids[i] >= 0 && ids[i] < 0x7fffffff;
-        ix->have_ids32 = false;
-        if (fits && ioff[L] > 0 && !ix->ids_unique) {
-            std::vector<int32_t> tmp((size_t)ioff[L]);
-            for (int64_t i = 0; i < ioff[L]; i++) tmp[(size_t)i] = (int32_t)ids[i];
-            TRY(ix->ids32.ensure(tmp.size() * 4));
-            HIPCHECK(hipMemcpy(ix->ids32.p, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
-            ix->have_ids32 = true;
-        }
+    TRY(lay.ids.ensure((size_t)(T > 0 ? T : 1) * 8));
+    if (T > 0) HIPCHECK(hipMemcpy(lay.ids.p, ids, (size_t)T * 8, hipMemcpyHostToDevice));
+    // int32 copy of the labels for the lane kernel's duplicate test
+    if (T > 0 && !uniq && mn >= 0 && mx < 0x7fffffff) {
+        std::vector<int32_t> tmp((size_t)T);
+        for (int64_t i = 0; i < T; i++) tmp[(size_t)i] = (int32_t)ids[i];
+        TRY(lay.ids32.ensure(tmp.size() * 4));
+        HIPCHECK(hipMemcpy(lay.ids32.p, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
+        lay.have_ids32 = true;
     }
-    ix->total_chunks = coff[L];
-    ix->total_ids = ioff[L];
-    ix->max_list_chunks = (int)maxc;
-    ix->have_lists = true;
-    ix->lists_gen++;
-    ix->list_cols.clear();
-    ix->list_kp = 0;
-    {   // labels that repeat: where every row's other copies are (the lane replay's duplicate test)
-        int64_t mx = -1, mn = 0;
-        for (int64_t i = 0; i < ioff[L]; i++) {
-            mx = ids[i] > mx ? ids[i] : mx;
-            mn = ids[i] < mn ? ids[i] : mn;
-        }
-        ix->labels24 = mn >= 0 && mx < 0x00ffffff;
-        TRY(build_twins(ix, mx + 1));
-    }
-    return TK_OK;
+    lay.ids_unique = uniq;
+    lay.max_label = mn < 0 ? NO_LABEL_BOUND : mx;
+    return install_lists(ix, lay);
 }
 
 extern "C" int tk_index_set_lists(tk_index *ix, const int64_t *list_sizes, const uint64_t *codes,

@@ -272,6 +272,51 @@ struct tk_allow {
     int64_t stored = 0;        // stored rows of the layout
     uint64_t lists_gen = 0;    // tk_index::lists_gen when it was made
 };
+// A finished layout of the inverted lists on its way into an index (install_lists): the device arrays in the index's
+// formats and what the host knows about them.  What it still holds when it goes — the index's old arrays after
+// install_lists, its own after a call that failed before — is released with it.
+static const int64_t NO_LABEL_BOUND = 1ll << 62;    // max_label of a layout with a negative label: no compact label form applies
+struct ListLayout {
+    DevBuf codes, ids, list_chunk_off, ids_off, list_n;
+    DevBuf ids32;               // the labels as int32 where have_ids32 (they repeat, and all fit)
+    bool have_ids32 = false;
+    int64_t total_chunks = 0, total_ids = 0, max_list_chunks = 0;
+    int64_t max_label = -1;     // the largest label (-1: no stored entry)
+    bool ids_unique = false;    // no label occurs twice
+    std::vector<int64_t> list_cols;     // members per (list, column), kp columns; empty: unknown
+    int kp = 0;
+    // a rank's upload of the lists it owns (tk_index_set_lists_shard): every list's owner, this rank's chunk offsets
+    bool sharded = false;
+    int rank = 0, world = 1;
+    DevBuf owner, local_chunk_off;
+    // the CSR arrays of L lists of these sizes (16 rows to a chunk) and the totals they give
+    int set_sizes(const int64_t *sizes, int64_t L)
+    {
+        std::vector<int64_t> coff((size_t)L + 1, 0), ioff((size_t)L + 1, 0);
+        for (int64_t i = 0; i < L; i++) {
+            const int64_t c = (sizes[i] + 15) / 16;
+            coff[(size_t)i + 1] = coff[(size_t)i] + c;
+            ioff[(size_t)i + 1] = ioff[(size_t)i] + sizes[i];
+            if (c > max_list_chunks) max_list_chunks = c;
+        }
+        ARGCHECK(max_list_chunks < (1ll << 26), "list too long");
+        total_chunks = coff[(size_t)L];
+        total_ids = ioff[(size_t)L];
+        TRY(list_chunk_off.ensure((size_t)(L + 1) * 8));
+        TRY(ids_off.ensure((size_t)(L + 1) * 8));
+        TRY(list_n.ensure((size_t)(L > 0 ? L : 1) * 8));
+        HIPCHECK(hipMemcpy(list_chunk_off.p, coff.data(), (size_t)(L + 1) * 8, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(ids_off.p, ioff.data(), (size_t)(L + 1) * 8, hipMemcpyHostToDevice));
+        if (L > 0) HIPCHECK(hipMemcpy(list_n.p, sizes, (size_t)L * 8, hipMemcpyHostToDevice));
+        return TK_OK;
+    }
+    ListLayout() = default;
+    ListLayout(const ListLayout &) = delete;
+    ~ListLayout()
+    {
+        for (DevBuf *b : {&codes, &ids, &list_chunk_off, &ids_off, &list_n, &ids32, &owner, &local_chunk_off}) b->release();
+    }
+};
 // the set a batch applies: NULL where the set allows every stored row (no kernel at all)
 const tk_allow *allow_effective(const tk_allow *a);
 struct Plan {
@@ -319,9 +364,12 @@ inline const uint4 *tables_of(const Work &w) { return w.tables.as<uint4>(); }
 int flush_pending(tk_index *ix);
 // nothing in flight, the device idle, the automatic plain-scan state back to its first probe: the lists may change
 int settle_lists(tk_index *ix);
-// the twin table of an index whose int32 labels (all in [0, label_bound)) are in place; no table (twin_w = 0) where
-// the labels are distinct, too sparse, or one label has more than 16 copies
-int build_twins(tk_index *ix, int64_t label_bound);
+// THE place where an index takes a new set of lists.  The arrays are swapped in (the old ones leave with `lay`), every
+// field derived from the layout is set, allowed sets made for the old layout stop working (lists_gen), the twin table
+// (twins.hip; none where the labels are distinct, too sparse, or one label has more than 16 copies) is made again.
+// Nothing fails once the swap has begun — a twin table that cannot be made is no table — so a caller that did its
+// checks and allocations first changes the index entirely or not at all.
+int install_lists(tk_index *ix, ListLayout &lay);
 bool twin_replay(const tk_index *ix, const struct Plan &p);
 int make_plan(const tk_index *ix, int k, int n_probes, int pass_1, Plan &p);
 bool plain_env_on();

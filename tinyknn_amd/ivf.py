@@ -7,12 +7,16 @@ kernel pipeline of libtinyknn_hip.so: distance tables -> coarse scan + heap +
 rescoring -> probed-list scan -> exact heap replay -> exact rescoring.
 """
 import ctypes as C
+import time
+import warnings
 import weakref
 
 import numpy as np
 
 from . import _front, _lib
-from .fast_pq import FastPQ, avx, dpad
+from . import fast_pq as _fp
+from ._transform import transform_data, unpack
+from .fast_pq import FastPQ, TransformedData, avx, dpad
 from .utils import group_data_by_indices, knn_brute, timer
 
 
@@ -111,20 +115,56 @@ class ResidentData:
         return self._dev.read_rows(rows).reshape(rows.shape + (self.shape[1],))
 
 
-def removal_rows(ids_or_mask, N):
-    """int64 row ids of remove()'s argument: a bool mask of length N, or a 1-d integer array of ids in [0, N)
-    (duplicates allowed)."""
-    a = np.asarray(ids_or_mask)
+def _mask_or_ids(arg, N, what, takes):
+    """(True, the bool mask of length N) or (False, the int64 row ids, all in [0, N), duplicates allowed) that `arg` is;
+    `what` and `takes` word the refusals."""
+    a = np.asarray(arg)
     if a.dtype == np.bool_:
         if a.shape != (N,):
-            raise ValueError(f"remove: a bool mask must have shape ({N},), got {a.shape}")
-        return np.ascontiguousarray(np.flatnonzero(a), dtype=np.int64)
+            raise ValueError(f"{what}: a bool mask must have shape ({N},), got {a.shape}")
+        return True, a
     if a.ndim == 1 and (a.size == 0 or np.issubdtype(a.dtype, np.integer)):
         a = np.ascontiguousarray(a, dtype=np.int64)
         if a.size and (a.min() < 0 or a.max() >= N):
-            raise ValueError(f"remove: row ids must lie in [0, {N})")
-        return a
-    raise TypeError("remove: a bool mask of length N or a 1-d integer array of row ids")
+            raise ValueError(f"{what}: row ids must lie in [0, {N})")
+        return False, a
+    raise TypeError(f"{what}: {takes}")
+
+
+def removal_rows(ids_or_mask, N):
+    """int64 row ids of remove()'s argument: a bool mask of length N, or a 1-d integer array of ids in [0, N)
+    (duplicates allowed)."""
+    is_mask, a = _mask_or_ids(ids_or_mask, N, "remove", "a bool mask of length N or a 1-d integer array of row ids")
+    return np.ascontiguousarray(np.flatnonzero(a), dtype=np.int64) if is_mask else a
+
+
+def _stored(t):
+    """Stored rows of one list's codes: a TransformedData, or the raw empty array FastPQ.transform returns for no rows."""
+    return 0 if isinstance(t, np.ndarray) else t.size
+
+
+def _split_lists(sizes, codes, ids, d):
+    """Lists concatenated list-major (save's and export_lists' form) as per-list objects -> (codes per list as
+    FastPQ.transform gives them for vectors of d dimensions, ids per list)."""
+    coff = np.concatenate([[0], np.cumsum((sizes + 15) // 16)])
+    ioff = np.concatenate([[0], np.cumsum(sizes)])
+    pts = [TransformedData(int(sizes[i]), codes[coff[i]:coff[i + 1]]) if sizes[i] else np.empty((0, d))
+           for i in range(len(sizes))]
+    return pts, [ids[ioff[i]:ioff[i + 1]] for i in range(len(sizes))]
+
+
+def _pack_labels(lab, zero):
+    """One list's codes from its rows' labels (n, M): the rows that pad it to a multiple of 16 carry the code of the
+    zero vector, as pad2 + transform give them (fast_pq.py:165)."""
+    n = len(lab)
+    if n % 16:
+        lab = np.concatenate([lab, np.repeat(zero[None], (-n) % 16, axis=0)])
+    return TransformedData(n, transform_data(np.ascontiguousarray(lab, dtype=np.uint8)))
+
+
+def _dev_is_sharded(dev):
+    """Has this device index been list-sharded (uploaded as a rank's shard, or sharded in place)?"""
+    return dev.world != 1 or getattr(dev, "_sharded_as", None) is not None
 
 
 def _copies_carry_one_code(ivf, n_lists):
@@ -139,7 +179,7 @@ def _copies_carry_one_code(ivf, n_lists):
     mult = None
     for i in range(n_lists):
         td = ivf.pq_transformed_points[i]
-        if isinstance(td, np.ndarray) or td.size == 0:
+        if _stored(td) == 0:
             continue
         pk = np.ascontiguousarray(td.packed, dtype=np.uint64)              # (chunks, M): per chunk M / 2 groups of 16 bytes
         P = pk.shape[1] // 2
@@ -187,19 +227,13 @@ class AllowSet:
     @staticmethod
     def mask_of(ids_or_mask, N):
         """uint8 (N,) mask of a bool mask of length N or of an array of row ids in [0, N)"""
-        a = np.asarray(ids_or_mask)
-        if a.dtype == np.bool_:
-            if a.shape != (N,):
-                raise ValueError(f"allowed: a bool mask must have shape ({N},), got {a.shape}")
+        is_mask, a = _mask_or_ids(ids_or_mask, N, "allowed",
+                                  "a bool mask of length N, a 1-d integer array of row ids, or an AllowSet")
+        if is_mask:
             return np.ascontiguousarray(a, dtype=np.uint8)
-        if a.ndim == 1 and (a.size == 0 or np.issubdtype(a.dtype, np.integer)):
-            a = a.astype(np.int64, copy=False)
-            if a.size and (a.min() < 0 or a.max() >= N):
-                raise ValueError(f"allowed: row ids must lie in [0, {N})")
-            mask = np.zeros(N, dtype=np.uint8)
-            mask[a] = 1
-            return mask
-        raise TypeError("allowed: a bool mask of length N, a 1-d integer array of row ids, or an AllowSet")
+        mask = np.zeros(N, dtype=np.uint8)
+        mask[a] = 1
+        return mask
 
     @property
     def handle(self):
@@ -226,11 +260,36 @@ class AllowSet:
 class DeviceIndex:
     """HBM-resident copy of a built IVF (C ABI: tk_index_*)."""
 
+    # What an index has however it was made (__init__, resident, clone_shard): these, the containers of _new_state,
+    # and the shape its maker sets (dq, dpb, d, n_lists, N, angular, rank, world).
+    _h = None               # the library's handle; None once closed
+    _R = None               # the PQ's rotation (float64), for the streaming sessions
+    _f64 = False            # float64 vectors (rescored in float64)
+    _sharded_as = None      # (owner, rank, world) once shard_resident made this index a rank's shard in place
+    _source = None          # clone_shard: the index whose arrays this one borrows
+    _clones = ()            # ... and the shards cloned from this one
+    data_ptr = None         # resident: the device address of the vectors
+    list_sizes = None
+    code_bytes = 0
+
+    def _new_state(self):
+        """the containers every instance owns"""
+        self._streams = {}                          # query_raw's sessions, per k
+        self._live_streams = weakref.WeakSet()      # every open session, the callers' included
+        self._live_allows = weakref.WeakSet()
+        self._clones = weakref.WeakSet()
+
+    @property
+    def M(self):
+        """PQ blocks = bytes per code"""
+        return self.dq // self.dpb
+
     def __init__(self, ivf, owner=None, rank=0, world=1):
         """owner (n_lists,) int32 + rank/world: list-sharded index — only the codes of the
         lists with owner[l] == rank are uploaded (tinyknn_hip.h, tk_index_set_lists_shard)."""
         L = _lib.lib()
         pq = ivf.pq
+        self._new_state()
         self._h = L.tk_index_create()
         if not self._h:
             raise _lib.TinyKnnHipError(L.tk_last_error().decode() or "tk_index_create failed")
@@ -249,20 +308,18 @@ class DeviceIndex:
         cpacked = np.ascontiguousarray(cpacked, dtype=np.uint64)
         _lib.check(L.tk_index_set_centers(self._h, _lib.ptr(ac, _lib._f32p), self.n_lists, self.d,
                                           _lib.ptr(cpacked, _lib._u64p), cpacked.shape[0]))
-        M = self.dq // self.dpb
         sizes, packed, ids = [], [], []
         for i in range(self.n_lists):
             td = ivf.pq_transformed_points[i]
-            if isinstance(td, np.ndarray):      # FastPQ.transform(empty) returns the raw array
-                sizes.append(0)
+            sizes.append(_stored(td))
+            if sizes[-1] == 0:
                 continue
-            sizes.append(td.size)
             if owner is None or owner[i] == rank:
                 packed.append(np.ascontiguousarray(td.packed, dtype=np.uint64))
             ids.append(np.asarray(ivf.ids[i], dtype=np.int64)[:td.size])
         sizes = np.array(sizes, dtype=np.int64)
         codes = (np.ascontiguousarray(np.concatenate(packed)) if packed
-                 else np.zeros((1, M), dtype=np.uint64))
+                 else np.zeros((1, self.M), dtype=np.uint64))
         allids = (np.ascontiguousarray(np.concatenate(ids)) if ids else np.zeros(1, np.int64))
         self.list_sizes = sizes
         self.rank, self.world = int(rank), int(world)
@@ -287,10 +344,6 @@ class DeviceIndex:
         self.N = int(data.shape[0])
         self.code_bytes = int(codes.nbytes)
         self.angular = ivf.metric == "angular"
-        self._R = None
-        self._streams = {}
-        self._live_streams = weakref.WeakSet()
-        self._live_allows = weakref.WeakSet()
         if pq.R is not None:    # fast mode (device front end) needs the rotation on the device
             R = np.ascontiguousarray(pq.R, dtype=np.float64)
             _lib.check(L.tk_index_set_rotation(self._h, R.ctypes.data, R.shape[1]))
@@ -307,6 +360,7 @@ class DeviceIndex:
         L = _lib.lib()
         pq = ivf.pq
         self = cls.__new__(cls)
+        self._new_state()
         self._h = L.tk_index_create()
         if not self._h:
             raise _lib.TinyKnnHipError(L.tk_last_error().decode() or "tk_index_create failed")
@@ -322,10 +376,6 @@ class DeviceIndex:
         self.rank, self.world = 0, 1
         self.angular = ivf.metric == "angular"
         self._R = None if pq.R is None else np.ascontiguousarray(pq.R, dtype=np.float64)
-        self._streams = {}
-        self._live_streams = weakref.WeakSet()
-        self.list_sizes = None
-        self.code_bytes = 0
         return self
 
     def synth_data(self, seed, centres=None, sigma=1.0, row0=0, n=None):
@@ -339,11 +389,7 @@ class DeviceIndex:
 
     def build_dev(self, all_centers, n_probes=1):
         """IVF.build(n_probes=1 or 2) on the resident vectors (tk_index_build_dev) -> n_active."""
-        A = np.ascontiguousarray(all_centers, dtype=np.float32)
-        Y = A
-        if self.angular:
-            Y = np.ascontiguousarray(Y / np.linalg.norm(Y, axis=1, keepdims=True))   # utils.py:75
-        ynorm2 = np.ascontiguousarray(np.einsum("ij,ij->i", Y, Y))    # utils.py:80
+        A, Y, ynorm2 = self._search_centres(all_centers)
         n_active = C.c_int64(0)
         R = self._R
         _lib.check(_lib.lib().tk_index_build_dev(
@@ -351,16 +397,31 @@ class DeviceIndex:
             _lib.ptr(ynorm2, _lib._f32p), len(Y), int(n_probes),
             None if R is None else R.ctypes.data, 0 if R is None else R.shape[1], C.byref(n_active)))
         self.n_lists = int(n_active.value)
-        self.list_sizes = self.export_lists(codes=False, ids=False)[0]
-        self.code_bytes = int(((self.list_sizes + 15) // 16).sum()) * (self.dq // self.dpb) * 8
+        self._refresh_lists()
         return self.n_lists
+
+    def _search_centres(self, all_centers):
+        """(all_centers as float32, the centres the assignment searches — normalised for angular —, their squared norms)"""
+        A = np.ascontiguousarray(all_centers, dtype=np.float32)
+        Y = A
+        if self.angular:
+            Y = np.ascontiguousarray(Y / np.linalg.norm(Y, axis=1, keepdims=True))   # utils.py:75
+        return A, Y, np.ascontiguousarray(np.einsum("ij,ij->i", Y, Y))    # utils.py:80
+
+    def _refresh_lists(self):
+        """The host's view of lists that changed on the device: N, the list sizes, the bytes of their codes."""
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_info(self._h, _lib.ptr(info, _lib._i64p)))
+        self.N = int(info[6])
+        self.list_sizes = self.export_lists(codes=False, ids=False)[0]
+        self.code_bytes = int(((self.list_sizes + 15) // 16).sum()) * self.M * 8
 
     def shard_resident(self, owner, rank, world):
         """This complete index becomes rank `rank`'s shard of a list-sharded index, in place
         (tk_index_shard_resident): only the codes of the lists it owns stay in HBM."""
         own = np.ascontiguousarray(owner, dtype=np.int32)
         assert own.shape == (self.n_lists,)
-        prev = getattr(self, "_sharded_as", None)
+        prev = self._sharded_as
         if prev is not None:        # a second ListShardedIndex on the same IVF: same partition only
             if prev[1:] == (int(rank), int(world)) and np.array_equal(prev[0], own):
                 return
@@ -375,8 +436,7 @@ class DeviceIndex:
         L = _lib.lib()
         sizes = np.zeros(self.n_lists, dtype=np.int64)
         _lib.check(L.tk_index_export_lists(self._h, sizes.ctypes.data, None, None))
-        M = self.dq // self.dpb
-        pk = np.zeros((int(((sizes + 15) // 16).sum()), M), dtype=np.uint64) if codes else None
+        pk = np.zeros((int(((sizes + 15) // 16).sum()), self.M), dtype=np.uint64) if codes else None
         lab = np.zeros(int(sizes.sum()), dtype=np.int64) if ids else None
         if codes or ids:
             _lib.check(L.tk_index_export_lists(self._h, None, None if pk is None else pk.ctypes.data,
@@ -386,7 +446,7 @@ class DeviceIndex:
     def export_centers(self):
         """(active_centers (n_lists, d) float32, their packed codes) (tk_index_export_centers)."""
         ac = np.zeros((self.n_lists, self.d), dtype=np.float32)
-        cc = np.zeros(((self.n_lists + 15) // 16, self.dq // self.dpb), dtype=np.uint64)
+        cc = np.zeros(((self.n_lists + 15) // 16, self.M), dtype=np.uint64)
         _lib.check(_lib.lib().tk_index_export_centers(self._h, ac.ctypes.data, cc.ctypes.data))
         return ac, cc
 
@@ -417,7 +477,7 @@ class DeviceIndex:
         center_codes: packed codes of all_centers[:n_lists'] where the rows activate new centres (None:
         coded on the device).  Batches in flight finish first; allowed sets made before stop working."""
         self._lists_may_change("add", "takes no rows")
-        is64 = self._data_is_f64()
+        is64 = self._f64
         rows = np.ascontiguousarray(rows, dtype=np.float64 if is64 else np.float32)
         if rows.ndim != 2 or rows.shape[1] != self.d:
             raise AssertionError(f"add: rows must have shape (n, {self.d}), got {rows.shape}")
@@ -433,38 +493,30 @@ class DeviceIndex:
             keep.append(a)
             return a.ctypes.data
 
-        M = self.dq // self.dpb
         near_p = opt(nearest, np.int64, (n, kp))
-        lab_p = opt(labels, np.uint8, (n, M))
+        lab_p = opt(labels, np.uint8, (n, self.M))
         cols_p = opt(list_columns, np.int64, (self.n_lists, kp))
         cc_p = opt(center_codes, np.uint64)
         A = Y = yn = None
         C_ = self.n_lists
         if all_centers is not None:
-            A = np.ascontiguousarray(all_centers, dtype=np.float32)
-            Y = A
-            if self.angular:
-                Y = np.ascontiguousarray(Y / np.linalg.norm(Y, axis=1, keepdims=True))   # utils.py:75
-            yn = np.ascontiguousarray(np.einsum("ij,ij->i", Y, Y))    # utils.py:80
+            A, Y, yn = self._search_centres(all_centers)
             C_ = len(A)
         n_active = C.c_int64(0)
         _lib.check(_lib.lib().tk_index_add_rows(
             self._h, rows.ctypes.data, int(is64), n, kp, near_p, lab_p, cols_p, int(bool(normalise)),
             None if A is None else A.ctypes.data, None if Y is None else Y.ctypes.data,
             None if yn is None else yn.ctypes.data, C_, cc_p, C.byref(n_active)))
-        info = np.zeros(8, dtype=np.int64)
-        _lib.check(_lib.lib().tk_index_info(self._h, _lib.ptr(info, _lib._i64p)))
-        self.n_lists, self.N = int(n_active.value), int(info[6])
-        self.list_sizes = self.export_lists(codes=False, ids=False)[0]
-        self.code_bytes = int(((self.list_sizes + 15) // 16).sum()) * M * 8
+        self.n_lists = int(n_active.value)
+        self._refresh_lists()
         return self.n_lists
 
     def _lists_may_change(self, what, sharded):
         """The refusals of add / remove: a list-sharded index or its clones, an open stream() session (the internal
         sessions of query_raw are closed: made again on demand)."""
-        if self.world != 1 or getattr(self, "_sharded_as", None) is not None or getattr(self, "_source", None):
+        if _dev_is_sharded(self) or self._source is not None:
             raise RuntimeError(f"DeviceIndex.{what}: a list-sharded index {sharded}")
-        if any(getattr(c, "_h", None) for c in getattr(self, "_clones", ())):
+        if any(c._h for c in self._clones):
             raise RuntimeError(f"DeviceIndex.{what}: shards cloned from this index borrow its arrays; close them first")
         for st in list(self._streams.values()):
             st.close()
@@ -494,12 +546,8 @@ class DeviceIndex:
         removed = C.c_int64(0)
         _lib.check(_lib.lib().tk_index_remove_rows(self._h, rows.ctypes.data, len(rows), kp, cols_p,
                                                    C.byref(removed)))
-        self.list_sizes = self.export_lists(codes=False, ids=False)[0]
-        self.code_bytes = int(((self.list_sizes + 15) // 16).sum()) * (self.dq // self.dpb) * 8
+        self._refresh_lists()
         return int(removed.value)
-
-    def _data_is_f64(self):
-        return bool(getattr(self, "_f64", False))
 
     @property
     def handle(self):
@@ -585,96 +633,63 @@ class DeviceIndex:
     def query_batch(self, qn, q_pq, k, n_probes, pass_1=None, debug=False, *, allowed=None, return_distances=False):
         """qn: (nq, d) float32 normalised queries; q_pq: (nq, dq) table-build queries.
         allowed: None, or the rows the queries may return — an AllowSet (allow()), a bool mask of length N or row
-        ids (tk_index_query_batch_allow: the reference's `insert` only for those labels).
+        ids (the library's _allow entry point: the reference's `insert` only for those labels).
         return_distances: (ids, dists) — the same ids, and beside each the exact squared distance the rescoring
-        ranked it by (tk_index_query_batch_dist): float32, float64 for float64 vectors, +inf beside -1."""
-        if return_distances:
-            if debug:
-                raise ValueError("query_batch: debug=True cannot be combined with return_distances=True")
-            return self._query_batch_dist(qn, q_pq, k, n_probes, pass_1, allowed)
-        if allowed is not None:
-            return self._query_batch_allow(qn, q_pq, k, n_probes, pass_1, debug, allowed)
+        ranked it by (the library's _dist entry point): float32, float64 for float64 vectors, +inf beside -1."""
+        if return_distances and debug:
+            raise ValueError("query_batch: debug=True cannot be combined with return_distances=True")
         qn = np.ascontiguousarray(qn, dtype=np.float32)
         is64 = q_pq.dtype != np.float32
         q_pq = np.ascontiguousarray(q_pq, dtype=np.float64 if is64 else np.float32)
         nq = qn.shape[0]
         assert qn.shape[1] == self.d and q_pq.shape == (nq, self.dq)
         out = np.full((nq, k), -1, dtype=np.int64)
-        # the session pads unrotated queries on the device: only for q_pq = pad1(qn)
-        plain = is64 or (np.array_equal(q_pq[:, :self.d], qn) and not q_pq[:, self.d:].any())
-        if not debug and nq > 0 and plain and _front.bind():
-            # prepared rows through the streaming session (pinned staging, async copies)
-            st = self._cached_stream(nq, k, n_probes, pass_1)
-            for o in range(0, nq, st.max_nq):
-                st.submit_prepared(qn[o:o + st.max_nq],
-                                   q_pq[o:o + st.max_nq] if is64 else None, out[o:o + st.max_nq])
-            st.drain()
-            return out
-        R = pass_1 if pass_1 else (n_probes + 1) * k + 1
-        probes = hidx = hval = None
+        if allowed is None and not return_distances and not debug and nq > 0:
+            # the session pads unrotated queries on the device: only for q_pq = pad1(qn)
+            plain = is64 or (np.array_equal(q_pq[:, :self.d], qn) and not q_pq[:, self.d:].any())
+            if plain and _front.bind():
+                # prepared rows through the streaming session (pinned staging, async copies)
+                st = self._cached_stream(nq, k, n_probes, pass_1)
+                for o in range(0, nq, st.max_nq):
+                    st.submit_prepared(qn[o:o + st.max_nq],
+                                       q_pq[o:o + st.max_nq] if is64 else None, out[o:o + st.max_nq])
+                st.drain()
+                return out
+        dist = probes = hidx = hval = None
+        if return_distances:
+            dist = np.full((nq, k), np.inf, dtype=np.float64 if self._f64 else np.float32)
         if debug:
+            R = pass_1 if pass_1 else (n_probes + 1) * k + 1
             probes = np.zeros((nq, min(n_probes, self.n_lists)), dtype=np.int64)
             hidx = np.zeros((nq, R), dtype=np.int64)
             hval = np.zeros((nq, R), dtype=np.int32)
-        _lib.check(_lib.lib().tk_index_query_batch(
-            self._h, _lib.ptr(qn, _lib._f32p), q_pq.ctypes.data, int(is64), nq, int(k),
-            int(n_probes), int(pass_1 or 0), _lib.ptr(out, _lib._i64p),
-            None if probes is None else _lib.ptr(probes, _lib._i64p),
-            None if hidx is None else _lib.ptr(hidx, _lib._i64p),
-            None if hval is None else _lib.ptr(hval, _lib._i32p)))
-        if debug:
-            return out, dict(probes=probes, heap_idx=hidx, heap_val=hval)
-        return out
-
-    def _query_batch_allow(self, qn, q_pq, k, n_probes, pass_1, debug, allowed):
-        aset, temp = self._allow_of(allowed)
+        L, knobs = _lib.lib(), (int(k), int(n_probes), int(pass_1 or 0))
+        aset, temp = (None, False) if allowed is None else self._allow_of(allowed)
         try:
-            qn = np.ascontiguousarray(qn, dtype=np.float32)
-            is64 = q_pq.dtype != np.float32
-            q_pq = np.ascontiguousarray(q_pq, dtype=np.float64 if is64 else np.float32)
-            nq = qn.shape[0]
-            assert qn.shape[1] == self.d and q_pq.shape == (nq, self.dq)
-            out = np.full((nq, k), -1, dtype=np.int64)
-            R = pass_1 if pass_1 else (n_probes + 1) * k + 1
-            probes = hidx = hval = None
-            if debug:
-                probes = np.zeros((nq, min(n_probes, self.n_lists)), dtype=np.int64)
-                hidx = np.zeros((nq, R), dtype=np.int64)
-                hval = np.zeros((nq, R), dtype=np.int32)
-            # (one sub-batch at a time keeps the debug outputs of every row)
-            step = nq if not debug else max(1, self.max_sub_batch(k, n_probes, pass_1))
-            for o in range(0, nq, max(step, 1)):
+            if return_distances:
+                _lib.check(L.tk_index_query_batch_dist(
+                    self._h, None if aset is None else aset.handle, _lib.ptr(qn, _lib._f32p), q_pq.ctypes.data,
+                    int(is64), nq, *knobs, _lib.ptr(out, _lib._i64p), dist.ctypes.data))
+                return out, dist
+            # (with a set, one sub-batch at a time keeps the debug outputs of every row)
+            step = max(1, self.max_sub_batch(k, n_probes, pass_1)) if debug and aset is not None else max(1, nq)
+            for o in range(0, nq if aset is not None else 1, step):
                 e = min(nq, o + step)
-                _lib.check(_lib.lib().tk_index_query_batch_allow(
-                    self._h, aset.handle, _lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o,
-                    int(k), int(n_probes), int(pass_1 or 0), _lib.ptr(out[o:e], _lib._i64p),
-                    None if probes is None else _lib.ptr(probes[o:e], _lib._i64p),
-                    None if hidx is None else _lib.ptr(hidx[o:e], _lib._i64p),
-                    None if hval is None else _lib.ptr(hval[o:e], _lib._i32p)))
+                args = (_lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o, *knobs,
+                        _lib.ptr(out[o:e], _lib._i64p),
+                        None if probes is None else _lib.ptr(probes[o:e], _lib._i64p),
+                        None if hidx is None else _lib.ptr(hidx[o:e], _lib._i64p),
+                        None if hval is None else _lib.ptr(hval[o:e], _lib._i32p))
+                if aset is None:
+                    _lib.check(L.tk_index_query_batch(self._h, *args))
+                else:
+                    _lib.check(L.tk_index_query_batch_allow(self._h, aset.handle, *args))
         finally:
             if temp:
                 aset.close()
         if debug:
             return out, dict(probes=probes, heap_idx=hidx, heap_val=hval)
         return out
-
-    def _query_batch_dist(self, qn, q_pq, k, n_probes, pass_1, allowed):
-        aset, temp = self._allow_of(allowed) if allowed is not None else (None, False)
-        try:
-            qn = np.ascontiguousarray(qn, dtype=np.float32)
-            is64 = q_pq.dtype != np.float32
-            q_pq = np.ascontiguousarray(q_pq, dtype=np.float64 if is64 else np.float32)
-            nq = qn.shape[0]
-            assert qn.shape[1] == self.d and q_pq.shape == (nq, self.dq)
-            out = np.full((nq, k), -1, dtype=np.int64)
-            dist = np.full((nq, k), np.inf, dtype=np.float64 if self._data_is_f64() else np.float32)
-            _lib.check(_lib.lib().tk_index_query_batch_dist(
-                self._h, None if aset is None else aset.handle, _lib.ptr(qn, _lib._f32p), q_pq.ctypes.data,
-                int(is64), nq, int(k), int(n_probes), int(pass_1 or 0), _lib.ptr(out, _lib._i64p), dist.ctypes.data))
-        finally:
-            if temp:
-                aset.close()
-        return out, dist
 
     def query_batch_raw(self, qs, k, n_probes, pass_1=None):
         """Fast mode: raw float32 queries, normalisation / padding / rotation on the device
@@ -711,33 +726,24 @@ class DeviceIndex:
         dist_ptr: None, or a device buffer of nq * k distances (float32; float64 for float64 vectors) that receives
         the rescoring's exact squared distances beside the ids, complete when out_ptr's ids are
         (tk_index_query_batch_dev_dist)."""
-        if dist_ptr is not None:
-            aset = None
-            if allowed is not None:
-                if not isinstance(allowed, AllowSet):
-                    raise TypeError("query_batch_dev: allowed= takes a prepared set (DeviceIndex.allow / IVF.allow)")
-                aset, _ = self._allow_of(allowed)
-            _lib.check(_lib.lib().tk_index_query_batch_dev_dist(
-                self._h, None if aset is None else aset.handle, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k),
-                int(n_probes), int(pass_1 or 0), out_ptr, dist_ptr,
-                None if done_event is None else C.c_void_p(int(done_event)), stream))
-            return
         if allowed is not None:
             if not isinstance(allowed, AllowSet):
                 raise TypeError("query_batch_dev: allowed= takes a prepared set (DeviceIndex.allow / IVF.allow)")
-            aset, _ = self._allow_of(allowed)
-            _lib.check(_lib.lib().tk_index_query_batch_dev_allow(
-                self._h, aset.handle, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes),
-                int(pass_1 or 0), out_ptr, None, None if done_event is None else C.c_void_p(int(done_event)), stream))
-            return
-        if done_event is None:
-            _lib.check(_lib.lib().tk_index_query_batch_dev(
-                self._h, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes),
-                int(pass_1 or 0), out_ptr, stream))
-        else:
-            _lib.check(_lib.lib().tk_index_query_batch_dev_ex(
-                self._h, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes),
-                int(pass_1 or 0), out_ptr, None, C.c_void_p(int(done_event)), stream))
+            allowed = self._allow_of(allowed)[0].handle
+        L, ev = _lib.lib(), None if done_event is None else C.c_void_p(int(done_event))
+        if dist_ptr is not None:
+            rc = L.tk_index_query_batch_dev_dist(
+                self._h, allowed, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes), int(pass_1 or 0),
+                out_ptr, dist_ptr, ev, stream)
+        elif allowed is not None:
+            rc = L.tk_index_query_batch_dev_allow(
+                self._h, allowed, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes), int(pass_1 or 0),
+                out_ptr, None, ev, stream)
+        else:       # (NULL pinned buffer; with a NULL event this is the library's plain _dev call)
+            rc = L.tk_index_query_batch_dev_ex(
+                self._h, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes), int(pass_1 or 0),
+                out_ptr, None, ev, stream)
+        _lib.check(rc)
 
     def shard_coarse_dev(self, slot, qn_ptr, qpq_ptr, qpq_is_f64, nq, k, n_probes, pass_1,
                          probes_home_ptr, stream=0):
@@ -792,24 +798,19 @@ class DeviceIndex:
         if not h:
             raise _lib.TinyKnnHipError(_lib.lib().tk_last_error().decode() or "tk_index_clone_shard failed")
         c = DeviceIndex.__new__(DeviceIndex)
+        c._new_state()
         c._h = h
         c._source = self            # keeps the lender alive
-        for a in ("dq", "dpb", "n_lists", "d", "list_sizes", "angular", "_R", "code_bytes"):
-            setattr(c, a, getattr(self, a, None))
-        c.N = getattr(self, "N", None)
+        c.dq, c.dpb, c.d, c.n_lists, c.N, c.angular = self.dq, self.dpb, self.d, self.n_lists, self.N, self.angular
+        c._R, c._f64, c.list_sizes, c.code_bytes = self._R, self._f64, self.list_sizes, self.code_bytes
         c.rank, c.world = int(rank), int(world)
-        c._streams = {}
-        c._live_streams = weakref.WeakSet()
-        if getattr(self, "_clones", None) is None:
-            self._clones = weakref.WeakSet()
         self._clones.add(c)
         return c
 
     def shard_usage(self, slot):
         """Longest stream (uint4) of the slot's last shard_scan_dev (tk_index_shard_usage; syncs)."""
-        import ctypes
-        v = ctypes.c_int64(0)
-        _lib.check(_lib.lib().tk_index_shard_usage(self._h, int(slot), ctypes.byref(v)))
+        v = C.c_int64(0)
+        _lib.check(_lib.lib().tk_index_shard_usage(self._h, int(slot), C.byref(v)))
         return int(v.value)
 
     def shard_bound_dev(self, slot, nq, k, n_probes, pass_1, capacity, scan_ptr, bound_ptr, stream=0):
@@ -913,9 +914,8 @@ class DeviceIndex:
     def set_option(self, option, value):
         """Per-index A/B and test options (tk_index_set_option): _lib.OPT_PAIR_NQ (batches of up to this many queries
         replay their heaps one query per wave, heap in registers: 8192 one batch at a time, at most 4096 per launch pipelined),
-        _lib.OPT_LABELS24, _lib.OPT_SCAN_FORM,
-        _lib.OPT_RESCORE_FORM, _lib.OPT_PLAIN_LIMIT, _lib.OPT_REPLAY_LAZY, _lib.OPT_REPLAY_COUNT,
-        _lib.OPT_REPLAY_TWIN."""
+        _lib.OPT_LABELS24, _lib.OPT_SCAN_FORM, _lib.OPT_RESCORE_FORM, _lib.OPT_PLAIN_LIMIT, _lib.OPT_REPLAY_LAZY,
+        _lib.OPT_REPLAY_COUNT, _lib.OPT_REPLAY_TWIN, _lib.OPT_TWIN_VOUCH (include/tinyknn_hip.h describes each)."""
         _lib.check(_lib.lib().tk_index_set_option(self._h, int(option), int(value)))
 
     def set_coalesce(self, n):
@@ -976,6 +976,11 @@ class DeviceIndex:
 class IVF:
     """reference: ivf.py:8-163"""
 
+    # (class-level: an IVF pickled before these existed still reads them)
+    all_centers = None      # fit's coarse centres
+    list_columns = None     # (n_lists, kp) members per (list, column of the build's nearest); None: not recorded
+    _build_device = None    # did build() search on the GPU?  None: not built here (fast_pq.device_build decides)
+
     def __init__(self, metric, n_clusters, pq=None):
         assert metric in ["euclidean", "angular"]
         self.metric = metric
@@ -1029,7 +1034,6 @@ class IVF:
         the rotation GEMM, grouping, packing) is the same host code."""
         assert n_probes <= self.n_clusters, (
             f"Can't assign points to {n_probes} clusters, as index only has {self.n_clusters}")
-        from . import fast_pq as _fp
         device = _fp.device_build if device is None else device
         self._dev = None
         self.data = data = X.copy()
@@ -1088,7 +1092,6 @@ class IVF:
             # is an implementation detail of its argselect (x86-simd-sort on AVX-512; other on AVX2, ARM,
             # older numpy).  Column order decides list order (group_data_by_indices appends column by
             # column): where this host's numpy orders differently, numpy's answer is the reference's.
-            import warnings
             warnings.warn("tinyknn_amd: numpy.argpartition on this host does not return the first k ascending "
                           "(k = %d); list assignment falls back to numpy's knn_brute" % n_probes)
             return knn_brute(data, self.all_centers, k=n_probes, metric=self.metric)
@@ -1133,8 +1136,6 @@ class IVF:
         host as the reference does, nearest centroids on the GPU) and the per-list arrays
         are gathered from the labels; the rows that pad a list to a multiple of 16 carry the
         code of the zero vector, as pad2 + transform give them (fast_pq.py:165)."""
-        from ._transform import transform_data
-        from .fast_pq import TransformedData
         pq = self.pq
         n, d = data.shape
         dq = pq.centers.shape[1]
@@ -1158,11 +1159,7 @@ class IVF:
             if len(sel) == 0:
                 self.pq_transformed_points[i] = np.empty((0, d))     # fast_pq.py:162-163
                 continue
-            lab = labels[sel]
-            padrows = (-len(sel)) % 16
-            if padrows:
-                lab = np.concatenate([lab, np.repeat(zero[None], padrows, axis=0)])
-            self.pq_transformed_points[i] = TransformedData(len(sel), transform_data(lab))
+            self.pq_transformed_points[i] = _pack_labels(labels[sel], zero)
 
     # ---- persistence ---------------------------------------------------------
     # The reference pickles (pq, ivf) (examples/bench.py:88-103); that works here too
@@ -1175,13 +1172,13 @@ class IVF:
         L = len(self.active_centers)
         M = self.pq.centers.shape[1] // self.pq.dims_per_block
         tds = [self.pq_transformed_points[i] for i in range(L)]
-        sizes = np.array([0 if isinstance(t, np.ndarray) else t.size for t in tds], dtype=np.int64)
-        codes = [t.packed for t in tds if not isinstance(t, np.ndarray)]
+        sizes = np.array([_stored(t) for t in tds], dtype=np.int64)
+        codes = [t.packed for t in tds if _stored(t)]
         ids = [np.asarray(self.ids[i], dtype=np.int64)[:sizes[i]] for i in range(L)]
         extra = {} if self.pq.R is None else {"R": self.pq.R}
-        if getattr(self, "all_centers", None) is not None:
+        if self.all_centers is not None:
             extra["all_centers"] = self.all_centers
-        if getattr(self, "list_columns", None) is not None:
+        if self.list_columns is not None:
             extra["list_columns"] = self.list_columns
         path = self._npz_path(path)
         np.savez(path, format_version=1, metric=self.metric, n_clusters=self.n_clusters,
@@ -1204,7 +1201,6 @@ class IVF:
     def load(cls, path, data=None):
         """Inverse of save.  `data`: the rescoring vectors if the file was written without them
         being wanted twice (pass the array to avoid keeping two copies)."""
-        from .fast_pq import TransformedData
         z = np.load(cls._npz_path(path), allow_pickle=False)
         assert int(z["format_version"]) == 1
         pq = FastPQ(int(z["dims_per_block"]),
@@ -1219,15 +1215,8 @@ class IVF:
             ivf.all_centers = z["all_centers"]
         ivf.active_centers = z["active_centers"]
         ivf.pq_transformed_centers = TransformedData(int(z["center_size"]), z["center_codes"])
-        sizes = z["list_sizes"]
-        coff = np.concatenate([[0], np.cumsum((sizes + 15) // 16)])
-        ioff = np.concatenate([[0], np.cumsum(sizes)])
-        codes, ids = z["list_codes"], z["ids"]
-        d = ivf.active_centers.shape[1]
-        ivf.pq_transformed_points = [
-            TransformedData(int(sizes[i]), codes[coff[i]:coff[i + 1]]) if sizes[i] else np.empty((0, d))
-            for i in range(len(sizes))]
-        ivf.ids = [ids[ioff[i]:ioff[i + 1]] for i in range(len(sizes))]
+        ivf.pq_transformed_points, ivf.ids = _split_lists(z["list_sizes"], z["list_codes"], z["ids"],
+                                                          ivf.active_centers.shape[1])
         ivf.data = z["data"] if data is None else data
         # (files written before add() existed have no list_columns: add() recovers them)
         ivf.list_columns = z["list_columns"] if "list_columns" in z else None
@@ -1244,8 +1233,7 @@ class IVF:
         from IVF.build's where that flips a nearest centroid.  Afterwards: active_centers,
         pq_transformed_centers and list_sizes on the host; data / ids / codes stay in HBM
         (device_index().export_lists() / read_rows() fetch them for a checker)."""
-        from .fast_pq import TransformedData
-        assert self.pq.centers is not None and getattr(self, "all_centers", None) is not None
+        assert self.pq.centers is not None and self.all_centers is not None
         with timer(verbose, "Generating vectors in HBM..."):
             dev = DeviceIndex.resident(self, N, d)
             dev.synth_data(seed, centres, sigma)
@@ -1289,7 +1277,7 @@ class IVF:
         d = self.data.shape[1]
         if X.ndim != 2 or X.shape[1] != d:
             raise AssertionError(f"IVF.add: X must have shape (n, {d}), got {X.shape}")
-        if getattr(self, "all_centers", None) is None:
+        if self.all_centers is None:
             raise AssertionError("IVF.add: the index has no all_centers (fit, or a file written with them)")
         if len(X) == 0:
             return self
@@ -1298,13 +1286,11 @@ class IVF:
         return self._add_host(X, verbose)
 
     def _require_device_free(self, what="add", doing="adding rows to"):
-        dev = self._dev
-        if dev is not None and (dev.world != 1 or getattr(dev, "_sharded_as", None) is not None):
+        if self._dev is not None and _dev_is_sharded(self._dev):
             raise NotImplementedError(f"IVF.{what}: this index has been list-sharded in place; {doing} a "
                                       "list-sharded index is not supported")
 
     def _add_resident(self, X, verbose):
-        from .fast_pq import TransformedData
         dev = self._dev
         cols = dev.list_columns()
         with timer(verbose, "Adding rows on the device..."):
@@ -1318,21 +1304,19 @@ class IVF:
         return self
 
     def _lists_per_row(self):
-        cols = getattr(self, "list_columns", None)
-        if cols is not None:
-            return cols.shape[1]
-        stored = sum(0 if isinstance(t, np.ndarray) else t.size for t in self.pq_transformed_points[:len(self.active_centers)])
+        if self.list_columns is not None:
+            return self.list_columns.shape[1]
+        stored = sum(_stored(t) for t in self.pq_transformed_points[:len(self.active_centers)])
         return max(1, stored // max(1, len(self.data)))
 
     def _list_columns_now(self, kp):
         """list_columns, recovered for a file written without them: the list sizes (kp = 1), or the build's own
         assignment over IVF.data (knn_brute, ivf.py:85) counted per column."""
-        cols = getattr(self, "list_columns", None)
+        cols = self.list_columns
         if cols is None:
             L = len(self.active_centers)
             if kp == 1:
-                cols = np.array([[0 if isinstance(t, np.ndarray) else t.size]
-                                 for t in self.pq_transformed_points[:L]], dtype=np.int64).reshape(L, 1)
+                cols = np.array([_stored(t) for t in self.pq_transformed_points[:L]], dtype=np.int64).reshape(L, 1)
             else:
                 near = knn_brute(np.asarray(self.data), self.all_centers, k=kp, metric=self.metric)
                 cols = np.stack([np.bincount(near[:, j], minlength=L) for j in range(kp)], axis=1).astype(np.int64)
@@ -1340,10 +1324,7 @@ class IVF:
         return cols
 
     def _add_host(self, X, verbose):
-        from .fast_pq import TransformedData
-        from . import fast_pq as _fp
-        import time
-        device = getattr(self, "_build_device", _fp.device_build)
+        device = _fp.device_build if self._build_device is None else self._build_device
         kp = self._lists_per_row()
         L0 = len(self.active_centers)
         cols0 = self._list_columns_now(kp)
@@ -1366,45 +1347,50 @@ class IVF:
         if L1 > L0:
             active = np.ascontiguousarray(self.all_centers[:L1], dtype=np.float32)
             centers = self.pq.transform(active, device=device)
-        dev = self._dev
-        self.last_add_ms = {}
-        if dev is not None:
-            t0 = time.perf_counter()
+
+        def on_device(dev):
             dev.add(new, kp, nearest=nearest, labels=labels, list_columns=cols0,
                     all_centers=self.all_centers if L1 > L0 else None,
                     center_codes=centers.packed if L1 > L0 else None)
-            t1 = time.perf_counter()
-            sizes, codes, ids = dev.export_lists()
-            coff = np.concatenate([[0], np.cumsum((sizes + 15) // 16)])
-            ioff = np.concatenate([[0], np.cumsum(sizes)])
-            pts = [TransformedData(int(sizes[i]), codes[coff[i]:coff[i + 1]]) if sizes[i] else np.empty((0, X.shape[1]))
-                   for i in range(L1)]
-            idl = [ids[ioff[i]:ioff[i + 1]] for i in range(L1)]
-            cols1 = dev.list_columns()
-            self.last_add_ms = {"device": 1e3 * (t1 - t0), "host": 1e3 * (time.perf_counter() - t1)}
-        else:
-            t1 = time.perf_counter()
-            pts, idl, cols1 = self._splice(new, nearest, labels, cols0, L1)
-            self.last_add_ms = {"device": 0.0, "host": 1e3 * (time.perf_counter() - t1)}
+            return True
+
+        self._change_lists("add", on_device, lambda: self._splice(new, nearest, labels, cols0, L1))
         if L1 > L0:
             self.active_centers = active
             self.pq_transformed_centers = centers
         self.data = np.concatenate([self.data, new])
-        self.pq_transformed_points = list(self.pq_transformed_points)
-        self.ids = list(self.ids)
-        self.pq_transformed_points += [None] * (L1 - len(self.pq_transformed_points))
-        self.ids += [None] * (L1 - len(self.ids))
-        for i in range(L1):
-            self.pq_transformed_points[i] = pts[i]
-            self.ids[i] = idl[i]
-        self.list_columns = cols1
         return self
+
+    def _change_lists(self, what, on_device, in_numpy):
+        """The second half of add / remove on a host-built index.  With a device index the change is made there
+        (on_device(dev) -> did the lists change?) and mirrored back; without one in_numpy() -> (codes per list, ids
+        per list, list_columns).  Leaves the timings in last_<what>_ms and the lists in self."""
+        dev, t0 = self._dev, time.perf_counter()
+        if dev is not None:
+            changed = on_device(dev)
+            t1 = time.perf_counter()
+            if changed:
+                pts, idl = _split_lists(*dev.export_lists(), self.data.shape[1])
+                cols = dev.list_columns()
+            ms = {"device": 1e3 * (t1 - t0), "host": 1e3 * (time.perf_counter() - t1) if changed else 0.0}
+        else:
+            changed = True
+            pts, idl, cols = in_numpy()
+            ms = {"device": 0.0, "host": 1e3 * (time.perf_counter() - t0)}
+        setattr(self, f"last_{what}_ms", ms)
+        if changed:
+            self._install_lists(pts, idl, cols)
+
+    def _install_lists(self, pts, idl, cols):
+        """The codes and ids of lists 0 .. len(pts) - 1 (lists past the old active ones are new) and the members per
+        (list, column) become the index's."""
+        self.pq_transformed_points = pts + list(self.pq_transformed_points[len(pts):])
+        self.ids = idl + list(self.ids[len(idl):])
+        self.list_columns = cols
 
     def _splice(self, new, nearest, labels, cols0, L1):
         """The lists after add() in numpy: list l's column-j block = old_j ++ (new rows with nearest[:, j] == l,
         ascending); untouched lists are kept as they are."""
-        from ._transform import transform_data, unpack
-        from .fast_pq import TransformedData
         N0, kp = len(self.data), nearest.shape[1]
         L0 = len(cols0)
         zero = self._zero_label()
@@ -1437,12 +1423,7 @@ class IVF:
                 if per[l][j] is not None:
                     lab_parts.append(labels[per[l][j]])
                     id_parts.append(N0 + per[l][j].astype(np.int64))
-            lab = np.concatenate(lab_parts).astype(np.uint8)
-            n_l = len(lab)
-            padrows = (-n_l) % 16
-            if padrows:
-                lab = np.concatenate([lab, np.repeat(zero[None], padrows, axis=0)])
-            pts.append(TransformedData(n_l, transform_data(lab)))
+            pts.append(_pack_labels(np.concatenate(lab_parts), zero))
             idl.append(np.concatenate(id_parts))
         return pts, idl, cols1
 
@@ -1465,7 +1446,6 @@ class IVF:
         return self._remove_host(rows, verbose)
 
     def _remove_resident(self, rows, verbose):
-        import time
         dev = self._dev
         t0 = time.perf_counter()
         with timer(verbose, "Removing rows on the device..."):
@@ -1476,47 +1456,21 @@ class IVF:
         return self
 
     def _remove_host(self, rows, verbose):
-        from .fast_pq import TransformedData
-        import time
         kp = self._lists_per_row()
         cols0 = self._list_columns_now(kp)      # (before: their recovery from IVF.data assumes every row stored)
         dead = np.zeros(len(self.data), dtype=bool)
         dead[rows] = True
-        L, d = len(self.active_centers), self.data.shape[1]
-        dev = self._dev
-        if dev is not None:
-            t0 = time.perf_counter()
+
+        def on_device(dev):
             with timer(verbose, "Removing rows on the device..."):
-                removed = dev.remove(rows, list_columns=cols0)
-            t1 = time.perf_counter()
-            if removed == 0:                      # nothing stored was named: nothing changed
-                self.last_remove_ms = {"device": 1e3 * (t1 - t0), "host": 0.0}
-                return self
-            sizes, codes, ids = dev.export_lists()
-            coff = np.concatenate([[0], np.cumsum((sizes + 15) // 16)])
-            ioff = np.concatenate([[0], np.cumsum(sizes)])
-            pts = [TransformedData(int(sizes[i]), codes[coff[i]:coff[i + 1]]) if sizes[i] else np.empty((0, d))
-                   for i in range(L)]
-            idl = [ids[ioff[i]:ioff[i + 1]] for i in range(L)]
-            cols1 = dev.list_columns()
-            self.last_remove_ms = {"device": 1e3 * (t1 - t0), "host": 1e3 * (time.perf_counter() - t1)}
-        else:
-            t1 = time.perf_counter()
-            pts, idl, cols1 = self._filter_lists(dead, cols0)
-            self.last_remove_ms = {"device": 0.0, "host": 1e3 * (time.perf_counter() - t1)}
-        self.pq_transformed_points = list(self.pq_transformed_points)
-        self.ids = list(self.ids)
-        for i in range(L):
-            self.pq_transformed_points[i] = pts[i]
-            self.ids[i] = idl[i]
-        self.list_columns = cols1
+                return dev.remove(rows, list_columns=cols0) > 0     # (0: nothing stored was named, nothing changed)
+
+        self._change_lists("remove", on_device, lambda: self._filter_lists(dead, cols0))
         return self
 
     def _filter_lists(self, dead, cols0):
         """The lists after remove() in numpy: every list's surviving entries in their old order (each column block
         shrinks in place), repacked with the zero vector's code in the padding rows; untouched lists are kept."""
-        from ._transform import transform_data, unpack
-        from .fast_pq import TransformedData
         L, kp = cols0.shape
         d = self.data.shape[1]
         zero = self._zero_label()
@@ -1524,7 +1478,7 @@ class IVF:
         pts, idl = [], []
         for l in range(L):
             t = self.pq_transformed_points[l]
-            n_l = 0 if isinstance(t, np.ndarray) else t.size
+            n_l = _stored(t)
             ids = np.asarray(self.ids[l])[:n_l]
             keep = ~dead[ids.astype(np.int64)]
             if keep.all():
@@ -1537,18 +1491,12 @@ class IVF:
             if n1 == 0:
                 pts.append(np.empty((0, d)))      # as FastPQ.transform of no rows (fast_pq.py:162-163)
                 continue
-            lab = unpack(t.packed)[:n_l][keep]
-            padrows = (-n1) % 16
-            if padrows:
-                lab = np.concatenate([lab, np.repeat(zero[None], padrows, axis=0)])
-            pts.append(TransformedData(n1, transform_data(np.ascontiguousarray(lab, dtype=np.uint8))))
+            pts.append(_pack_labels(unpack(t.packed)[:n_l][keep], zero))
         return pts, idl, cols1
 
     def _zero_label(self):
         """The zero vector's labels (the rows that pad a list to a multiple of 16, fast_pq.py:165)."""
-        from ._transform import unpack
-        z = self.pq.transform(np.zeros((1, self.data.shape[1]), dtype=self.data.dtype),
-                              device=getattr(self, "_build_device", None))
+        z = self.pq.transform(np.zeros((1, self.data.shape[1]), dtype=self.data.dtype), device=self._build_device)
         return unpack(z.packed)[1]
 
     # ---- queries (GPU) -----------------------------------------------------
@@ -1559,7 +1507,7 @@ class IVF:
 
     def _unsharded_device_index(self):
         dev = self.device_index()
-        if dev.world != 1 or getattr(dev, "_sharded_as", None) is not None:
+        if _dev_is_sharded(dev):
             raise RuntimeError("this IVF's device index has been list-sharded in place (ListShardedIndex on an "
                                f"index built in HBM: rank {dev.rank} of {dev.world}); query it through the "
                                "ListShardedIndex")
