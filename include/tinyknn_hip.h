@@ -466,9 +466,13 @@ int tk_index_remove_rows(tk_index *ix, const int64_t *rows, int64_t n, int kp,
  * fast_pq.py:200-204): float32 normalisation for the angular metric, zero padding to dq,
  * rotation by R.  NOT bit-identical to the host path, which is the default everywhere:
  * numpy normalises with a BLAS dot and rotates with a BLAS GEMV whose summation orders are
- * not restated.  Here the norm is numpy's pairwise float32 sum and the rotation a float64
- * FMA chain; both results are within 1 ulp of the host's, and the ids differ only where
- * that flips a quantised table entry or a rescoring tie (measured in DESIGN.md).
+ * not restated.  Here the norm is numpy's pairwise float32 sum (bit for bit
+ * x / np.linalg.norm(x, axis=1)) and the rotation a float64 FMA chain over ascending t.
+ * Measured against the host's: a normalised element is at most 4 float32 ulp
+ * away (74 % identical, 22 % one ulp); a rotated one differs by at most 7.5 * 2^-53 * sum_t
+ * |x_t R_jt| — a few float64 ulp of an ordinary output (median 2), thousands where the sum
+ * cancels to a small value.  The ids differ only where that flips a quantised table entry or
+ * a rescoring tie.
  * tk_index_set_rotation: R (dq, d_pad) float64 row-major = FastPQ.R, or NULL (no rotation).
  * tk_index_prepare_dev: q_raw_dev (nq, d) float32 -> qn_dev (nq, d) float32 (normalised if
  * `angular`, else a copy; may alias q_raw_dev) and q_pq_dev (nq, dq) float64 when a rotation
@@ -608,7 +612,13 @@ void tk_stream_destroy(tk_stream *s);
  * the k smallest in ascending (part, row) order (numpy's argpartition leaves the order of
  * the first k, and the choice among exact ties at the k-th value, unspecified).
  * q: (nq, d) float32 host, already normalised for the angular metric like IVF.data;
- * out_ids: (nq, k) int64 host.  float32 vectors, d <= 128. */
+ * out_ids: (nq, k) int64 host.  float32 vectors, d <= 128, 1 <= k <= min(1024, N), N < 2^31.
+ * The rows are scanned in segments whose length follows from k (2^20 rows for k <= 16, 2^17 for
+ * k = 100, 2^14 for k = 1024; the rule is in brute.hip), each adding to a list of 8192 candidates
+ * per query.  Refused (TK_ERR_HIP, "candidate list overflow", no ids written): a query for which
+ * one segment holds more than 8192 rows within its running k-th distance, i.e. rows tied at
+ * that distance (thousands of duplicates) or near rows stored together so densely that one
+ * segment holds more than 4 times its share of them.  A list is never cut silently. */
 int tk_index_knn_brute(tk_index *ix, const float *q, int64_t nq, int k, int64_t *out_ids);
 
 /* ---- list-sharded index over `world` ranks, one process per GPU --------

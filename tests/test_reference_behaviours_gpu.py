@@ -157,8 +157,8 @@ def test_saved_and_pickled_index_answers_identically(tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("tag", ["an100", "eu128", "eu20"])
 def test_fast_front_end_close_to_exact(tag):
-    """Device normalisation / padding / rotation (fast=True) against the exact host path: the
-    prepared queries agree to 1 ulp-level tolerances and nearly all result rows are equal."""
+    """Device normalisation / padding / rotation (fast=True) against the exact host path: nearly all
+    result rows are equal.  (The prepared queries themselves: tests/test_fast_front_end_gpu.py.)"""
     from conftest import golden
     from test_hip_parity import ivf_from_fixture
     g = golden(f"g6_ivf_{tag}.npz")

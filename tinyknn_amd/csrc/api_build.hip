@@ -918,7 +918,7 @@ extern "C" int tk_index_knn_brute(tk_index *ix, const float *q, int64_t nq, int 
     HIPCHECK(hipDeviceSynchronize());
     int ov = 0;
     HIPCHECK(hipMemcpy(&ov, overflow, 4, hipMemcpyDeviceToHost));
-    if (ov) return fail(TK_ERR_HIP, "knn_brute: candidate list overflow (a 2^20-row segment holds more than 8192 rows within the running k-th distance)");
+    if (ov) return fail(TK_ERR_HIP, "knn_brute: candidate list overflow (one segment of rows holds more than 8192 rows within a query's running k-th distance: tied or stored together)");
     HIPCHECK(hipMemcpy(out_ids, ix->br_out.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
     return TK_OK;
 }

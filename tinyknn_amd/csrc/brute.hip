@@ -10,11 +10,22 @@
 //   pass A  part values of `ns` rows of Y taken at a constant stride over the whole matrix
 //           (not its first rows: cluster-ordered data would give a useless bound) -> (nq, ns)
 //   sort    per query: k-th smallest of them = tau_q           (bitonic sort in LDS)
-//   pass B  the rows of Y in segments of 2^20: every (part, j) with part <= tau_q is appended
-//           to the query's candidate list (atomic counter, capacity `cap`); after each
-//           segment the list is sorted, cut to its k best and tau_q tightened to the k-th of
-//           them, so a segment adds about k * 2^20 / max(ns, rows seen) entries whatever N is
+//   pass B  the rows of Y in segments of `seg` rows: every (part, j) with part <= tau_q is
+//           appended to the query's candidate list (atomic counter, capacity `cap`); after
+//           each segment the list is sorted, cut to its k best and tau_q tightened to the k-th
+//           of them, so a segment adds about k * seg / max(ns, rows seen) entries whatever N is
 //   result  the k best after the last segment, by (part, j) ascending.  Ties: lower j first.
+// Segment length (brute_segment).  tau_q is the k-th smallest of ns sampled rows, so of
+// `seg` rows about k * seg / ns lie within it.  That count is an order statistic's: its
+// relative spread is 1 / sqrt(k), and rows that are not in random order (a query's cluster
+// stored together) raise a segment's share further.  seg is therefore the largest power of two
+// with k * seg / ns <= cap / 4, a factor 4 below the capacity, and never more than 2^20:
+//   seg = min(2^20, 2^floor(log2(cap * ns / (4 k))))
+// With ns = cap = 8192 that is 2^20 for k <= 16, 2^17 for k = 100 and 2^14 for k = 1024.
+// A list that overflows all the same is reported (`overflow`) and the call fails; it is never
+// cut silently.  That remains for more than `cap` rows of one segment within tau_q: exact ties
+// (duplicated rows), or a query whose near rows are stored together so that one segment holds
+// more than 4 times its share of them.
 // One workgroup = 4 waves = 128 query rows against 32 rows of Y at a time; the Y tile (32
 // consecutive rows = one contiguous block of memory) is fetched once per workgroup into LDS
 // in MFMA operand order, double-buffered.
@@ -216,6 +227,15 @@ __global__ void sample_rows_kernel(const float *__restrict__ Y, int d, int64_t n
     out[i] = Y[r * stride * d + (i - r * d)];
 }
 
+// rows per segment of pass B: the largest power of two with k * seg / ns <= cap / 4, at most 2^20
+static int64_t brute_segment(int k, int64_t ns, int cap)
+{
+    const int64_t most = (int64_t)cap * ns / (4 * (int64_t)k);
+    int64_t seg = 32;
+    while (seg < (1 << 20) && 2 * seg <= most) seg <<= 1;
+    return seg;
+}
+
 // X (nq, d), Y (N, d) float32 on the device, d <= 128, N < 2^31; out (nq, k) int64.
 // Work buffers are the caller's: ynorm2 (N), vals (nq * ns), tau (nq), cand (nq * cap) u64,
 // count (nq) int, overflow (1) int, sample (ns * (d + 1)) floats.
@@ -259,7 +279,7 @@ int tk_launch_knn_brute(const float *X, int64_t nq, int d, const float *Y, int64
                        vals, ns, nullptr, 0, nullptr, k, tau, nullptr, nullptr);
     (void)hipMemsetAsync(count, 0, (size_t)nq * 4, s);
     (void)hipMemsetAsync(overflow, 0, 4, s);
-    const int64_t seg = 1 << 20;
+    const int64_t seg = brute_segment(k, ns, cap);
     for (int64_t s0 = 0; s0 < N; s0 += seg) {
         const int64_t m = N - s0 < seg ? N - s0 : seg;
         hipLaunchKernelGGL(brute_tiles_kernel<1>, dim3(qt, splits(m)), dim3(256), tile_lds, s, X, nq, d,

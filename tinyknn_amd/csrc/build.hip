@@ -550,7 +550,10 @@ void tk_launch_assign(const float *X, int64_t n, int d, const void *Yt, const vo
 // the table build (ivf.py:125-128, fast_pq.py:200-204).  NOT bit-identical to the host path:
 // numpy normalises a query with a BLAS dot and rotates it with a BLAS GEMV, whose summation
 // orders are not restated; here the norm is numpy's pairwise float32 sum (the order of
-// np.linalg.norm(axis=1)) and the rotation a float64 FMA chain over k ascending.
+// np.linalg.norm(axis=1)) and the rotation a float64 FMA chain over k ascending.  Measured
+// against the host's: normalised elements at most 4 float32 ulp apart, rotated
+// ones at most 7.5 * 2^-53 * sum_t |x_t R_jt| (not "1 ulp": where that sum cancels, thousands
+// of ulp of the small result).
 // One workgroup of 64 lanes per query; Rt is R transposed (d_pad, dq) so that lane j reads
 // consecutive addresses.
 __global__ __launch_bounds__(64) void rotate_rows_kernel(const float *__restrict__ X, int64_t n,

@@ -693,7 +693,8 @@ class DeviceIndex:
 
     def query_batch_raw(self, qs, k, n_probes, pass_1=None):
         """Fast mode: raw float32 queries, normalisation / padding / rotation on the device
-        (tk_index_prepare_dev: within 1 ulp of the host's BLAS results, not bit-identical)."""
+        (tk_index_prepare_dev: not bit-identical to the host's BLAS results — normalised rows within 4 float32
+        ulp of them, rotated ones within 7.5 * 2^-53 * sum |x_t R_jt|; measured)."""
         qs = np.ascontiguousarray(qs, dtype=np.float32)
         assert qs.shape[1] == self.d
         out = np.full((qs.shape[0], k), -1, dtype=np.int64)
@@ -1562,7 +1563,8 @@ class IVF:
         2-d `ivf.query(queries, ...)` that its code does not support; this is that
         call.)  fast=True: normalisation, padding and rotation run on the device instead
         of numpy's per-query BLAS calls (35 ms per 10 000 queries on the host) — within
-        1 ulp of them, so a rare id can differ from the reference's; the default is exact.
+        4 float32 ulp of their normalised rows, so a rare id can differ from the
+        reference's; the default is exact.
         return_distances: ((nq, k) ids, (nq, k) exact squared distances), INTEGRATION.md §2f."""
         if return_distances and fast:
             raise NotImplementedError("IVF.query_batch: fast=True with return_distances=True is not supported; "
