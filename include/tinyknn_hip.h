@@ -158,9 +158,25 @@ int tk_index_set_centers(tk_index *ix, const float *active_centers, int64_t n_li
  * ids (sum size,) labels. */
 int tk_index_set_lists(tk_index *ix, const int64_t *list_sizes, const uint64_t *codes,
                        const int64_t *ids);
-/* IVF.data: the (normalised) vectors used for rescoring, float32 or float64 as the
- * caller's X was (ivf.py:77-79 keeps X's dtype)  */
-int tk_index_set_data(tk_index *ix, const void *data, int data_is_f64, int64_t N, int d);
+/* IVF.data: the (normalised) vectors used for rescoring.  dtype: TK_DATA_F32 (0) or TK_DATA_F64 (1) as the
+ * caller's X was (ivf.py:77-79 keeps X's dtype), or TK_DATA_F16 (2): `data` points at N * d IEEE halfs (the
+ * caller rounded its float32 vectors: round-to-nearest-even, subnormals kept, every half finite) and the index
+ * stores 2 bytes per element.  A half index answers, bit for bit, what the float32 index holding float(half(x))
+ * answers: the final rescoring widens each stored value and sums in float32 (distances are float32); lists,
+ * codes, probes and heaps do not read the vectors.
+ * tk_index_narrow_data: the float32 vectors an index already holds in HBM (tk_index_alloc_data +
+ *   tk_index_build_dev, or a float32 upload) become halfs, in a new buffer (the float32 one is freed: 1.5 x the
+ *   float32 size for the length of the call).  A check pass runs first: a value whose half is not finite
+ *   (|x| >= 65520, inf, NaN) is TK_ERR_ARG naming the first such row, and the index stays as it was.  A half
+ *   index: TK_OK, nothing done.  Refused (TK_ERR_ARG): float64 vectors; a cloned shard (its vectors are
+ *   borrowed) and an index that shards were cloned from (they are lent).  Batches in flight finish first.
+ * tk_index_store: the dtype code of the index's vectors (TK_DATA_*), or -1 with no vectors set. */
+#define TK_DATA_F32 0
+#define TK_DATA_F64 1
+#define TK_DATA_F16 2
+int tk_index_set_data(tk_index *ix, const void *data, int dtype, int64_t N, int d);
+int tk_index_narrow_data(tk_index *ix);
+int tk_index_store(tk_index *ix);
 
 /* _FastDistanceTable.top(transformed_data, data, k) (fast_pq.py:284-312) for a batch of queries
  * against the rows the index holds as its centres — tk_index_set_pq + tk_index_set_centers(rows,
@@ -396,7 +412,7 @@ int tk_scan_exclusive_host(const void *in_host, void *out_host, int64_t n, int i
  * tk_index_export_lists / _centers / tk_index_read_rows: what a built index holds, back on
  *   the host in the reference's formats (list_sizes (n_lists,), packed codes (sum
  *   ceil(size/16), M) uint64, ids (sum size,); active centres and their packed codes; rows of
- *   IVF.data by id) — any output may be NULL. */
+ *   IVF.data by id; float32 vectors, or half vectors widened) — any output may be NULL. */
 float *tk_index_alloc_data(tk_index *ix, int64_t N, int d);
 int tk_index_synth_data(tk_index *ix, int64_t row0, int64_t n, uint64_t seed, const float *centres,
                         int n_centres, float sigma);
@@ -421,6 +437,10 @@ int tk_index_read_rows(tk_index *ix, const int64_t *rows, int64_t n, float *out)
  * list is unspecified, as there.  Padding rows carry the zero vector's code.
  *   rows: (n, d) float32, or float64 (rows_is_f64) where the index's vectors are float64; host
  *     or device memory.  normalise != 0: divided by their norm on the device first (float32).
+ *     An index of half vectors (TK_DATA_F16) takes float32 rows: they are normalised, assigned and coded
+ *     from their float32 values in a staging buffer (lists and codes are the float32 index's), checked
+ *     (a value whose half is not finite: TK_ERR_ARG naming the row, nothing changed) and only then
+ *     appended to the stored vectors rounded to half.
  *   nearest (n, kp) int64 centre ids, or NULL: found on the device as tk_index_build_dev finds
  *     them (all_centers / search_centers / ynorm2 / C as there).
  *   labels (n, M) uint8 PQ labels, or NULL: encoded on the device as tk_index_build_dev does.
@@ -557,7 +577,7 @@ int tk_index_query_batch_dev_allow(tk_index *ix, const tk_allow *allow, const fl
 /* Ids and their distances.  out_dist[i, j] is the exact squared Euclidean distance between stored row
  * out_ids[i, j] of tk_index_set_data's vectors and query row q[i], summed as knn_brute1 does (utils.py:89-92:
  * einsum("ij,ij->i", diff, diff) of diff = data[id] - q) — the value the rescoring ranks by.  Element type:
- * float32, or float64 after tk_index_set_data(..., data_is_f64 = 1) (numpy's promotion of `Y - x`); +inf
+ * float32, or float64 after tk_index_set_data(..., TK_DATA_F64) (numpy's promotion of `Y - x`); +inf
  * beside every -1.  The ids are those of the ids-only call, bit for bit.  Where a query had more than k
  * candidates its row is in rescored order (distances non-decreasing); where it had k or fewer the ids keep
  * heap order (ivf.py:158-159) and each still gets its distance, so such a row need not be sorted.

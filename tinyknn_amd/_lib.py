@@ -10,6 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 ORDER_SSE, ORDER_AVX = 0, 1
+DATA_F32, DATA_F64, DATA_F16 = 0, 1, 2      # TK_DATA_*: the dtype codes of tk_index_set_data / tk_index_store
 
 
 class TinyKnnHipError(RuntimeError):
@@ -126,6 +127,8 @@ SIGNATURES = {
     "tk_index_top_centers_dist": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int, _i64p,
                                             _f32p]),
     "tk_index_set_data": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int]),
+    "tk_index_narrow_data": (C.c_int, [C.c_void_p]),
+    "tk_index_store": (C.c_int, [C.c_void_p]),
     "tk_index_reserve": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int]),
     "tk_index_query_batch": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int,
                                        C.c_int, C.c_int, _i64p, _i64p, _i64p, _i32p]),

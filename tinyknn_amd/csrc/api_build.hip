@@ -25,7 +25,7 @@ extern "C" float *tk_index_alloc_data(tk_index *ix, int64_t N, int d)
     if (ix->data.ensure((size_t)N * d * 4) != TK_OK) return nullptr;
     ix->N = N;
     ix->d = d;
-    ix->data_is_f64 = 0;
+    ix->data_dtype = TK_DATA_F32;
     ix->have_data = ix->have_centers = ix->have_lists = false;   // until tk_index_build_dev
     return ix->data.as<float>();
 }
@@ -45,6 +45,7 @@ extern "C" int tk_index_synth_data(tk_index *ix, int64_t row0, int64_t n, uint64
 {
     IXLOCK(ix);
     ARGCHECK(ix && ix->data.p && ix->N > 0, "tk_index_alloc_data first");
+    ARGCHECK(ix->data_dtype == TK_DATA_F32, "float32 vectors (before tk_index_narrow_data)");
     ARGCHECK(row0 >= 0 && n >= 0 && row0 + n <= ix->N, "row range");
     const float *cd = nullptr;
     TRY(synth_centres(ix->stage, centres, n_centres, ix->d, &cd));
@@ -193,6 +194,7 @@ extern "C" int tk_index_build_dev(tk_index *ix, int normalise, const float *all_
     ARGCHECK(n_probes >= 1 && n_probes <= 9 && n_probes <= C, "n_probes must be 1 .. 9");
     const int kp = n_probes;
     ARGCHECK(ix && ix->have_pq && ix->data.p && ix->N > 0, "set_pq and tk_index_alloc_data first");
+    ARGCHECK(ix->data_dtype == TK_DATA_F32, "the build reads float32 vectors (tk_index_narrow_data comes after it)");
     ARGCHECK(all_centers && ynorm2 && C >= 1 && C < (1ll << 31), "centres");
     ARGCHECK(ix->N * kp < (1ll << 31), "N * n_probes < 2^31");
     ARGCHECK(ix->d <= 384 && (!normalise || ix->d <= 128), "d <= 384 (128 with normalisation)");
@@ -296,6 +298,29 @@ extern "C" int tk_index_build_dev(tk_index *ix, int normalise, const float *all_
     return TK_OK;
 }
 
+// float32 vectors in HBM -> halfs (tinyknn_hip.h): checked first, converted into a new buffer, swapped last
+extern "C" int tk_index_narrow_data(tk_index *ix)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix && ix->have_data && ix->data.p, "an index with its vectors");
+    if (ix->data_dtype == TK_DATA_F16) return TK_OK;
+    ARGCHECK(ix->data_dtype == TK_DATA_F32, "float64 vectors are rescored in float64: no half storage");
+    ARGCHECK(!ix->data.borrowed, "a cloned shard borrows its vectors");
+    ARGCHECK(!ix->data_lent, "shards cloned from this index borrow its vectors");
+    TRY(flush_pending(ix));
+    HIPCHECK(hipDeviceSynchronize());
+    DevBuf flag, half;
+    BufCleanup cl{{&flag, &half}};
+    TRY(check_half_rows(ix->data.as<float>(), ix->N, ix->d, 0, flag));
+    TRY(half.ensure((size_t)ix->N * ix->d * 2));
+    tk_launch_narrow_rows(ix->data.as<float>(), ix->N, ix->d, half.p, 0);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    std::swap(ix->data, half);          // (the float32 buffer leaves with the cleanup)
+    ix->data_dtype = TK_DATA_F16;
+    return TK_OK;
+}
+
 extern "C" int tk_index_list_columns(tk_index *ix, int *kp, int64_t *counts)
 {
     IXLOCK(ix);
@@ -349,7 +374,9 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
     ARGCHECK(!ix->sharded, "a list-sharded index takes no rows");
     ARGCHECK(n >= 0 && (n == 0 || rows), "rows");
     ARGCHECK(kp >= 1 && kp <= 9, "kp (lists per row) must be 1 .. 9");
-    ARGCHECK(!rows_is_f64 == !ix->data_is_f64, "rows must have the dtype of the index's vectors");
+    ARGCHECK(!rows_is_f64 == (ix->data_dtype != TK_DATA_F64),
+             "float64 rows only for an index of float64 vectors (float32 rows for float32 and half vectors)");
+    const bool half = ix->data_dtype == TK_DATA_F16;
     {
         bool sit = false;
         TRY(rows_sit_in(ix, kp, &sit));
@@ -385,10 +412,10 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
         }
         ARGCHECK(s == size0[(size_t)l], "list_columns: a list's columns do not add up to its size");
     }
-    const size_t esz = rows_is_f64 ? 8 : 4;
-    DevBuf grown, yt, yn, near, keys, prow, keys2, rows2, count, lab, rot, tmp, zrow, zlab, crow, clab, coffs,
+    const size_t esz = data_esz(ix->data_dtype);      // of a stored element; the rows come as float32 / float64
+    DevBuf xstage, hflag, grown, yt, yn, near, keys, prow, keys2, rows2, count, lab, rot, tmp, zrow, zlab, crow, clab, coffs,
         act1, ccodes, noff_d, seg_d;
-    BufCleanup cl{{&grown, &yt, &yn, &near, &keys, &prow, &keys2, &rows2, &count, &lab, &rot, &tmp, &zrow, &zlab,
+    BufCleanup cl{{&xstage, &hflag, &grown, &yt, &yn, &near, &keys, &prow, &keys2, &rows2, &count, &lab, &rot, &tmp, &zrow, &zlab,
                    &crow, &clab, &coffs, &act1, &ccodes, &noff_d, &seg_d}};
     ListLayout lay;
     // ---- 1. the rows behind the old ones (a larger buffer where they do not fit: the old one stays intact)
@@ -398,8 +425,14 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
         HIPCHECK(hipMemcpy(grown.p, ix->data.p, (size_t)N0 * d * esz, hipMemcpyDeviceToDevice));
         base = grown.p;
     }
-    void *Xn = (char *)base + (size_t)N0 * d * esz;
-    HIPCHECK(hipMemcpy(Xn, rows, (size_t)n * d * esz, hipMemcpyDefault));
+    // (half vectors: the rows are prepared as float32 in a buffer of their own and narrowed into the tail last)
+    void *tail = (char *)base + (size_t)N0 * d * esz;
+    void *Xn = tail;
+    if (half) {
+        TRY(xstage.ensure((size_t)n * d * 4));
+        Xn = xstage.p;
+    }
+    HIPCHECK(hipMemcpy(Xn, rows, (size_t)n * d * (rows_is_f64 ? 8 : 4), hipMemcpyDefault));
     // ---- 2. nearest centres (given, or as tk_index_build_dev finds them), pairs per (centre, column)
     const int64_t T = n * kp;
     TRY(near.ensure((size_t)T * 8));
@@ -478,6 +511,11 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
             const uint8_t *zc = nullptr;
             TRY(encode_centres(ix, all_centers, L1, rot, crow, clab, coffs, ccodes, &zc));
         }
+    }
+    if (half) {         // what the vectors will hold: every half finite, or nothing changes
+        TRY(check_half_rows((const float *)Xn, n, d, N0, hflag));
+        tk_launch_narrow_rows((const float *)Xn, n, d, tail, 0);
+        HIPCHECK(hipGetLastError());
     }
     // ---- 7. the merged lists
     TRY(noff_d.ensure((size_t)(L1 + 1) * 8));
@@ -718,7 +756,8 @@ extern "C" tk_index *tk_index_clone_shard(tk_index *src, const int32_t *owner, i
     ix->rot_t.borrow(src->rot_t);
     ix->rot_d_pad = src->rot_d_pad;
     ix->data.borrow(src->data);
-    ix->N = src->N; ix->data_is_f64 = src->data_is_f64;
+    ix->N = src->N; ix->data_dtype = src->data_dtype;
+    src->data_lent = true;
     ix->have_pq = ix->have_centers = ix->have_lists = ix->have_data = true;
     ix->plain_mode = src->plain_mode;
     // this rank's codes
@@ -794,11 +833,11 @@ extern "C" int tk_index_export_centers(tk_index *ix, float *active_centers, uint
     return TK_OK;
 }
 
-// rows of IVF.data by id (float32 vectors), e.g. the candidates a checker wants to rescore
+// rows of IVF.data by id (float32 vectors, or half vectors widened), e.g. the candidates a checker wants to rescore
 extern "C" int tk_index_read_rows(tk_index *ix, const int64_t *rows, int64_t n, float *out)
 {
     IXLOCK(ix);
-    ARGCHECK(ix && ix->have_data && !ix->data_is_f64, "an index with float32 vectors");
+    ARGCHECK(ix && ix->have_data && ix->data_dtype != TK_DATA_F64, "an index with float32 or half vectors");
     ARGCHECK(n >= 0 && (n == 0 || (rows && out)), "buffers");
     for (int64_t i = 0; i < n; i++) ARGCHECK(rows[i] >= 0 && rows[i] < ix->N, "row id out of range");
     if (n == 0) return TK_OK;
@@ -808,7 +847,10 @@ extern "C" int tk_index_read_rows(tk_index *ix, const int64_t *rows, int64_t n, 
     if (rc == TK_OK) {
         hipError_t e = hipMemcpy(r.p, rows, (size_t)n * 8, hipMemcpyHostToDevice);
         if (e == hipSuccess) {
-            tk_launch_gather_rows(ix->data.as<float>(), ix->d, r.as<int64_t>(), n, o.as<float>(), 0);
+            if (ix->data_dtype == TK_DATA_F16)
+                tk_launch_gather_rows_half(ix->data.p, ix->d, r.as<int64_t>(), n, o.as<float>(), 0);
+            else
+                tk_launch_gather_rows(ix->data.as<float>(), ix->d, r.as<int64_t>(), n, o.as<float>(), 0);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpy(out, o.p, (size_t)n * ix->d * 4, hipMemcpyDeviceToHost);
@@ -889,7 +931,9 @@ extern "C" int tk_index_knn_brute(tk_index *ix, const float *q, int64_t nq, int 
 {
     IXLOCK(ix);
     ARGCHECK(ix && ix->have_data, "set_data first");
-    ARGCHECK(!ix->data_is_f64, "float32 vectors only");
+    ARGCHECK(ix->data_dtype != TK_DATA_F64, "float32 vectors only");
+    ARGCHECK(ix->data_dtype != TK_DATA_F16, "knn_brute is the ground truth on float32 vectors: this index stores "
+                                            "them as half (store=\"float16\"); ask a float32 index");
     ARGCHECK(ix->d <= 128, "d <= 128");
     ARGCHECK(nq >= 0 && q && out_ids, "buffers");
     ARGCHECK(k >= 1 && k <= 1024 && k <= ix->N, "1 <= k <= min(1024, N)");

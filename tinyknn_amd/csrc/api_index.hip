@@ -345,19 +345,41 @@ extern "C" int tk_index_set_lists_shard(tk_index *ix, const int64_t *list_sizes,
     return set_lists_impl(ix, list_sizes, codes_owned, ids, owner, rank, world);
 }
 
-extern "C" int tk_index_set_data(tk_index *ix, const void *data, int data_is_f64, int64_t N,
-                                 int d)
+extern "C" int tk_index_set_data(tk_index *ix, const void *data, int dtype, int64_t N, int d)
 {
     IXLOCK(ix);
     ARGCHECK(ix && ix->have_centers, "set_centers first");
     ARGCHECK(d == ix->d, "data dimension differs from the centres'");
     ARGCHECK(N >= 1, "N");
-    const size_t esz = data_is_f64 ? 8 : 4;
+    ARGCHECK(dtype == TK_DATA_F32 || dtype == TK_DATA_F64 || dtype == TK_DATA_F16, "dtype: TK_DATA_F32 / _F64 / _F16");
+    const size_t esz = data_esz(dtype);
     TRY(ix->data.ensure((size_t)N * d * esz));
     HIPCHECK(hipMemcpy(ix->data.p, data, (size_t)N * d * esz, hipMemcpyHostToDevice));
     ix->N = N;
-    ix->data_is_f64 = data_is_f64;
+    ix->data_dtype = dtype;
     ix->have_data = true;
+    return TK_OK;
+}
+
+extern "C" int tk_index_store(tk_index *ix)
+{
+    IXLOCK(ix);
+    return ix && ix->have_data ? ix->data_dtype : -1;
+}
+
+// the first row of n float32 rows (device) with a value whose half is not finite -> TK_ERR_ARG naming row0 + it
+int check_half_rows(const float *X, int64_t n, int d, int64_t row0, DevBuf &flag)
+{
+    const unsigned long long none = ~0ull;
+    unsigned long long bad = none;
+    TRY(flag.ensure(8));
+    HIPCHECK(hipMemcpy(flag.p, &none, 8, hipMemcpyHostToDevice));
+    tk_launch_check_half(X, n, d, flag.as<unsigned long long>(), 0);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(&bad, flag.p, 8, hipMemcpyDeviceToHost));
+    if (bad != none)
+        return fail(TK_ERR_ARG, "bad argument: half storage: row " + std::to_string(row0 + (int64_t)bad) +
+                                    " holds a value whose half is not finite (|x| >= 65520, inf or NaN)");
     return TK_OK;
 }
 
@@ -372,7 +394,8 @@ int make_plan(const tk_index *ix, int k, int n_probes, int pass_1, Plan &p)
     int64_t R = pass_1 > 0 ? pass_1 : (int64_t)(n_probes + 1) * k + 1;         // ivf.py:135-136
     ARGCHECK(R * 12 + 16 <= 64 * 1024 && rescore * 12 + 16 <= 64 * 1024,
              "heap larger than 64 KiB of LDS (pass_1 <= 5460)");
-    ARGCHECK(R * (ix->data_is_f64 ? 16 : 12) + (int64_t)ix->d * (ix->data_is_f64 ? 8 : 4) + 16 <= 64 * 1024,
+    const bool f64 = ix->data_dtype == TK_DATA_F64;    // (half vectors are summed in float32: the float32 sizes)
+    ARGCHECK(R * (f64 ? 16 : 12) + (int64_t)ix->d * (f64 ? 8 : 4) + 16 <= 64 * 1024,
              "rescoring tile larger than 64 KiB of LDS");
     p.kc = (int)kc; p.rescore = (int)rescore; p.R = (int)R; p.S = (int)kc;
     p.cap = (int64_t)kc * ix->max_list_chunks;
@@ -1164,7 +1187,7 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     }
     TRY(pf.mark(st));
     // 4. strip sentinels, exact rescoring                   ivf.py:154-163
-    tk_launch_rescore(q_dev, 0, ix->d, ix->data.p, ix->data_is_f64, ix->N, w.heap_idx.as<int64_t>(), p.R, nq, k, 1,
+    tk_launch_rescore(q_dev, 0, ix->d, ix->data.p, ix->data_dtype, ix->N, w.heap_idx.as<int64_t>(), p.R, nq, k, 1,
                       out_dev, nullptr, st, ix->opt_rescore_form, q2, out2, nullptr, dist_dev, dist2);
     TRY(pf.mark(st));
     return TK_OK;
@@ -1613,7 +1636,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     // not 22 500 + 7 500 — the small rest fell below the list-major scan's threshold and took the query-major kernel)
     const int64_t parts = nq > ms ? (nq + ms - 1) / ms : 1;
     const int64_t part = (nq + parts - 1) / parts;
-    const size_t dsz = ix->data_is_f64 ? 8 : 4;         // the rescoring's type (the queries are float32)
+    const size_t dsz = ix->data_dtype == TK_DATA_F64 ? 8 : 4;         // the rescoring's type (the queries are float32)
     for (int64_t o = 0; o < nq; o += part) {
         const int64_t sub = nq - o < part ? nq - o : part;
         Pending b(ix, p, k, n_probes, pass_1, q_pq_is_f64, allow, caller,
@@ -1786,7 +1809,7 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
     TRY(ix->q.ensure((size_t)nq * ix->d * 4));
     TRY(ix->qpq.ensure((size_t)nq * ix->dq * esz));
     DevBuf outbuf, distbuf;  // separate from the sub-batch `out` workspace
-    const size_t dist_bytes = (size_t)nq * k * (ix->data_is_f64 ? 8 : 4);
+    const size_t dist_bytes = (size_t)nq * k * (ix->data_dtype == TK_DATA_F64 ? 8 : 4);
     TRY(outbuf.ensure((size_t)nq * k * 8));
     if (out_dist) {
         const int e = distbuf.ensure(dist_bytes);

@@ -220,7 +220,8 @@ struct tk_index {
     // vectors
     DevBuf data;
     int64_t N = 0;
-    int data_is_f64 = 0;
+    int data_dtype = 0;        // TK_DATA_F32 / TK_DATA_F64 / TK_DATA_F16
+    bool data_lent = false;    // shards were cloned from this index: they borrow its arrays
     // index-static descriptors of the coarse stage, staging buffers of the host API
     DevBuf cslots_i, cslots_l, c_chunk_off, q, qpq, stage;
     int scan_mode = 0;         // 0 auto, 1 query-major kernel, 2 list-major (units) kernel
@@ -361,6 +362,9 @@ struct Prof {
 inline const uint4 *tables_of(const Work &w) { return w.tables.as<uint4>(); }
 
 // ---- api_index.hip, used by the other files
+static inline size_t data_esz(int dtype) { return dtype == TK_DATA_F64 ? 8 : (dtype == TK_DATA_F16 ? 2 : 4); }
+// TK_OK, or TK_ERR_ARG naming row0 + the first of n float32 rows (device) with a value whose half is not finite
+int check_half_rows(const float *X, int64_t n, int d, int64_t row0, DevBuf &flag);
 int flush_pending(tk_index *ix);
 // nothing in flight, the device idle, the automatic plain-scan state back to its first probe: the lists may change
 int settle_lists(tk_index *ix);

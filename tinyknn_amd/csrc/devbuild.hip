@@ -589,6 +589,65 @@ void tk_launch_gather_rows(const float *X, int d, const int64_t *rows, int64_t n
                        n, out);
 }
 
+// ... and of vectors stored as IEEE half (TK_DATA_F16), widened (exact)
+__global__ void gather_rows_half_kernel(const _Float16 *__restrict__ X, int d, const int64_t *__restrict__ rows,
+                                        int64_t n, float *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * d) return;
+    const int64_t r = i / d;
+    out[i] = (float)X[rows[r] * d + (i - r * d)];
+}
+
+void tk_launch_gather_rows_half(const void *X, int d, const int64_t *rows, int64_t n, float *out, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(gather_rows_half_kernel, dim3((unsigned)((n * d + 255) / 256)), dim3(256), 0, s,
+                       (const _Float16 *)X, d, rows, n, out);
+}
+
+// Half storage of float32 rows.  The check pass: *first_bad (set to INT64_MAX by the caller) = the first row
+// holding a value whose half is not finite — |x| >= 65520 rounds to infinity under round-to-nearest-even
+// (65504 is the largest half, 65520 the tie above it, which goes to the even side: infinity), and so do inf
+// and NaN fail `|x| < 65520`.
+__global__ __launch_bounds__(256) void check_half_kernel(const float *__restrict__ X, int64_t n, int d,
+                                                         unsigned long long *__restrict__ first_bad)
+{
+    const int64_t total = n * d, stride = (int64_t)gridDim.x * blockDim.x;
+    unsigned long long bad = ~0ull;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride)
+        if (!(__builtin_fabsf(X[i]) < 65520.0f)) {
+            const unsigned long long r = (unsigned long long)(i / d);
+            if (r < bad) bad = r;
+        }
+    if (bad != ~0ull) atomicMin(first_bad, bad);
+}
+
+void tk_launch_check_half(const float *X, int64_t n, int d, unsigned long long *first_bad, hipStream_t s)
+{
+    if (n <= 0) return;
+    const int64_t total = n * d;
+    const unsigned blocks = (unsigned)(total / 256 + 1 < 4096 ? total / 256 + 1 : 4096);
+    hipLaunchKernelGGL(check_half_kernel, dim3(blocks), dim3(256), 0, s, X, n, d, first_bad);
+}
+
+// The conversion: round-to-nearest-even, subnormal halves kept (the hardware's v_cvt_f16_f32 in its default
+// mode: what numpy's astype(float16) gives for every value that passed the check).
+__global__ __launch_bounds__(256) void narrow_rows_kernel(const float *__restrict__ X, int64_t total,
+                                                          _Float16 *__restrict__ out)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) out[i] = (_Float16)X[i];
+}
+
+void tk_launch_narrow_rows(const float *X, int64_t n, int d, void *out, hipStream_t s)
+{
+    if (n <= 0) return;
+    const int64_t total = n * d;
+    const unsigned blocks = (unsigned)(total / 256 + 1 < 8192 ? total / 256 + 1 : 8192);
+    hipLaunchKernelGGL(narrow_rows_kernel, dim3(blocks), dim3(256), 0, s, X, total, (_Float16 *)out);
+}
+
 // chunks of the lists a rank owns, copied from the whole index's tiled code array into the
 // rank's own (compact) tiled array: local chunk cl of list l = global chunk coff[l] + cl - loff[l]
 __global__ void compact_tiled_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, int P,

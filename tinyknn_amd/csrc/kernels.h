@@ -309,7 +309,7 @@ struct TkSlotsOut {
 // is float64, else float32), +inf beside a -1; rows the heap order keeps (<= k candidates) get theirs too.  dist2.b:
 // the second call's own buffer (its rows from out2.n_a on; NULL: that call wants none).  With either, the
 // distance-writing forms of the kernels run and `slots` is ignored.
-int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int rows_is_f64,
+int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int rows_dtype,
                       int64_t n_rows, const int64_t *cand, int R, int64_t nq, int k, int strip,
                       int64_t *out, int *out_count, hipStream_t s, int form = 2, TkSecond q2 = TkSecond(),
                       TkSecond out2 = TkSecond(), const TkSlotsOut *slots = nullptr, void *dist = nullptr,
@@ -450,6 +450,12 @@ void tk_launch_compact_lists(const uint4 *old_tiled, const int64_t *old_chunk_of
 // stored row, labels outside [0, N)}, {-1, 0, INT_MAX, 0} on entry
 void tk_launch_row_copies(const int64_t *ids, int64_t T, int *cnt, int64_t N, int *out, hipStream_t s);
 void tk_launch_gather_rows(const float *X, int d, const int64_t *rows, int64_t n, float *out, hipStream_t s);
+// the same for vectors stored as IEEE half (TK_DATA_F16): out = the rows widened
+void tk_launch_gather_rows_half(const void *X, int d, const int64_t *rows, int64_t n, float *out, hipStream_t s);
+// half storage of float32 rows (n, d) on the device: *first_bad (preset to ~0) = the first row with a value whose
+// half is not finite (|x| >= 65520, inf, NaN); `out` = the rows as halfs, round-to-nearest-even, subnormals kept
+void tk_launch_check_half(const float *X, int64_t n, int d, unsigned long long *first_bad, hipStream_t s);
+void tk_launch_narrow_rows(const float *X, int64_t n, int d, void *out, hipStream_t s);
 void tk_launch_read_only(const void *src, int64_t n_uint4, uint32_t *out, hipStream_t s);
 // n_gather random rows of row_bytes (a multiple of 16, <= 1024) out of n_rows, read as the rescoring kernel reads
 void tk_launch_gather_rows(const void *src, int64_t n_rows, int row_bytes, int64_t n_gather, uint32_t *out, hipStream_t s);

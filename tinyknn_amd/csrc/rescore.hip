@@ -412,7 +412,262 @@ __global__ __launch_bounds__(64) void rescore_staged_dist_kernel(const float *__
                                     out_b, out_na, nullptr, out_d, out_d_b);
 }
 
-int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int rows_is_f64,
+// ---------------------------------------------------------------------------
+// Vectors stored as IEEE half (TK_DATA_F16), float32 queries, float32 sums: the result is what the float32
+// kernels above give on the rows float(half(x)).  Rows are d halfs, so the unit of the stream is an 8-byte
+// piece of 4 halfs (d % 4 == 0; GloVe's 200-byte rows have no whole number of 16-byte pieces) and everything
+// else keeps the float32 kernel's geometry: lanes_per_row = the power of two >= d / 4, (rr, pc), sixteen loads
+// in flight per lane.  The tile stays in half (half the float32 tile's LDS) and is widened where it is summed.
+// A lane reads its row with ds_read_b64: the lane groups are {0-31}, {32-63} and a piece covers two of the 64
+// banks, so lane t's piece j sits on bank pair (t * stride8 + j) mod 32 — distinct over 32 lanes exactly when
+// the row stride is an ODD number of 8-byte pieces.
+// sqdist_row<float, float> after float(y) for a row held in LDS as 8-byte pieces of 4 halfs: same operations
+// in the same order (un-fused, four lane-accumulators, groups folded 3,2,1,0, pairwise horizontal add).
+__device__ __forceinline__ void widen4(const uint2 p, float *o)
+{
+    typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+    const half2_t lo = __builtin_bit_cast(half2_t, p.x), hi = __builtin_bit_cast(half2_t, p.y);
+    o[0] = (float)lo.x; o[1] = (float)lo.y; o[2] = (float)hi.x; o[3] = (float)hi.y;
+}
+
+__device__ __forceinline__ float sqdist_row_lds_half(const uint2 *__restrict__ y2, const float *xs, int d)
+{
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    int i = 0;
+    for (; d - i >= 16; i += 16) {
+        float yv[16];
+        widen4(y2[(i >> 2)], yv);
+        widen4(y2[(i >> 2) + 1], yv + 4);
+        widen4(y2[(i >> 2) + 2], yv + 8);
+        widen4(y2[(i >> 2) + 3], yv + 12);
+        float df[16];
+#pragma unroll
+        for (int t = 0; t < 16; t++) df[t] = yv[t] - xs[i + t];
+#pragma unroll
+        for (int l = 0; l < 4; l++) {
+            float ab3 = df[12 + l] * df[12 + l] + acc[l];
+            float ab2 = df[8 + l] * df[8 + l] + ab3;
+            float ab1 = df[4 + l] * df[4 + l] + ab2;
+            acc[l] = df[l] * df[l] + ab1;
+        }
+    }
+    for (; i < d; i += 4) {          // d % 4 == 0: whole vectors only
+        float yv[4];
+        widen4(y2[i >> 2], yv);
+#pragma unroll
+        for (int l = 0; l < 4; l++) {
+            const float df = yv[l] - xs[i + l];
+            acc[l] = df * df + acc[l];
+        }
+    }
+    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+}
+
+// LDS: cand[R] (int64) | dist[R] | x[d] | tile[TILE + 1 spare][stride8] (8-byte pieces)
+// DIST, the pair arguments and the descriptors' hook as rescore_staged_body (the final stage passes no slots).
+template <int TILE, bool DIST>
+__device__ __forceinline__ void rescore_staged_half_body(unsigned char *smem, const float *__restrict__ q, int d,
+                                                         const _Float16 *__restrict__ rows, int64_t n_rows,
+                                                         const int64_t *__restrict__ cand, int R, int k, int strip,
+                                                         int64_t *__restrict__ out, int *__restrict__ out_count,
+                                                         int stride8, const float *__restrict__ q_b, int64_t q_na,
+                                                         int64_t *__restrict__ out_b, int64_t out_na,
+                                                         const TkSlotsOut *__restrict__ so_dev,
+                                                         float *__restrict__ out_d, float *__restrict__ out_d_b)
+{
+    const bool have_slots = so_dev != nullptr;
+    int64_t *cs = (int64_t *)smem;
+    float *ds = (float *)(smem + (((size_t)R * 8 + 15) & ~(size_t)15));
+    float *xs = ds + ((R + 3) & ~3);
+    uint2 *tile = (uint2 *)(xs + ((d + 3) & ~3));        // 16-byte aligned
+    const int tid = threadIdx.x;
+    const int64_t qi = blockIdx.x;
+    const int64_t *c = cand + qi * R;
+    const float *qrow = (q_b && qi >= q_na) ? q_b + (qi - q_na) * d : q + qi * d;   // second call of a pair
+    for (int t = tid; t < d; t += 64) xs[t] = qrow[t];
+    // ordered compaction of the candidate ids (ivf.py:154-155 drops -1)
+    int nc = 0;
+    for (int t0 = 0; t0 < R; t0 += 64) {
+        const int t = t0 + tid;
+        const int64_t id = t < R ? c[t] : -1;
+        const bool keep = t < R && (!strip || id != -1);
+        const uint64_t m = __builtin_amdgcn_ballot_w64(keep);
+        const int before = __builtin_popcountll(m & ((1ull << tid) - 1ull));
+        if (keep) cs[nc + before] = id;
+        nc += __builtin_popcountll(m);
+    }
+    __syncthreads();
+    const bool second = out_b && qi >= out_na;
+    int64_t *o = second ? out_b + (qi - out_na) * k : out + qi * k;
+    float *od = nullptr;
+    if (DIST) od = second ? (out_d_b ? out_d_b + (qi - out_na) * k : nullptr) : (out_d ? out_d + qi * k : nullptr);
+    if (nc <= k) {  // ivf.py:158-159 / fast_pq.py:307-308: heap order, no rescoring
+        for (int t = tid; t < k; t += 64) o[t] = t < nc ? cs[t] : -1;
+        if (tid == 0 && out_count) out_count[qi] = nc;
+        if (DIST && od)
+            for (int t = tid; t < k; t += 64) {
+                float dv = __builtin_huge_valf();
+                if (t < nc) {
+                    int64_t id = cs[t];
+                    if (id < 0) id += n_rows;
+                    dv = sqdist_row<float, _Float16>(rows + id * (int64_t)d, xs, d);
+                }
+                od[t] = dv;
+            }
+        if (have_slots) slots_epilogue(*so_dev, qi, k, tid, tid < nc ? cs[tid < k ? tid : 0] : -1);
+        return;
+    }
+    const int d4 = d >> 2;                   // 8-byte pieces per row
+    const int lpr_log = d4 <= 16 ? 4 : (d4 <= 32 ? 5 : 6);
+    const int rr = tid >> lpr_log, pc = tid & ((1 << lpr_log) - 1), rpi = 64 >> lpr_log;
+    for (int t0 = 0; t0 < nc; t0 += TILE) {
+        const int nt = nc - t0 < TILE ? nc - t0 : TILE;
+        if (pc < d4)
+            for (int r0 = rr; r0 < nt; r0 += 16 * rpi) {
+                // sixteen loads in flight per lane before the first LDS store waits for one
+                uint2 v[16];
+#pragma unroll
+                for (int u = 0; u < 16; u++) {
+                    const int r = r0 + u * rpi;
+                    int64_t id = cs[t0 + (r < nt ? r : nt - 1)];
+                    if (id < 0) id += n_rows;  // numpy fancy indexing with a negative index
+                    v[u] = ((const uint2 *)(rows + id * (int64_t)d))[pc];
+                }
+                // unconditional stores (rows past the tile go to the spare row), as in the float32 kernel
+#pragma unroll
+                for (int u = 0; u < 16; u++) {
+                    const int r = r0 + u * rpi;
+                    tile[(r < nt ? r : TILE) * stride8 + pc] = v[u];
+                }
+            }
+        __syncthreads();
+        if (tid < nt) ds[t0 + tid] = sqdist_row_lds_half(tile + tid * stride8, xs, d);
+        __syncthreads();
+    }
+    int64_t *ps = (int64_t *)(tile + (((TILE + 1) * stride8 + 1) & ~1));     // have_slots: the k results in order
+    for (int t = tid; t < nc; t += 64) {
+        const float dv = ds[t];
+        int rank = 0;
+        for (int u = 0; u < nc; u++) {
+            const float du = ds[u];
+            rank += (du < dv) || (du == dv && u < t);
+        }
+        if (rank < k) {
+            o[rank] = cs[t];
+            if (DIST && od) od[rank] = dv;
+            if (have_slots) ps[rank] = cs[t];
+        }
+    }
+    if (tid == 0 && out_count) out_count[qi] = k;
+    if (have_slots) {
+        __syncthreads();
+        slots_epilogue(*so_dev, qi, k, tid, tid < k ? ps[tid] : -1);
+    }
+}
+
+template <int TILE>
+__global__ __launch_bounds__(64) void rescore_staged_half_kernel(const float *__restrict__ q, int d,
+                                                                 const _Float16 *__restrict__ rows, int64_t n_rows,
+                                                                 const int64_t *__restrict__ cand, int R, int k,
+                                                                 int strip, int64_t *__restrict__ out,
+                                                                 int *__restrict__ out_count, int stride8,
+                                                                 const float *__restrict__ q_b, int64_t q_na,
+                                                                 int64_t *__restrict__ out_b, int64_t out_na,
+                                                                 const TkSlotsOut *__restrict__ so_dev)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rescore_staged_half_body<TILE, false>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride8, q_b,
+                                          q_na, out_b, out_na, so_dev, nullptr, nullptr);
+}
+
+template <int TILE>
+__global__ __launch_bounds__(64) void rescore_staged_half_distances_kernel(const float *__restrict__ q, int d,
+                                                                      const _Float16 *__restrict__ rows,
+                                                                      int64_t n_rows, const int64_t *__restrict__ cand,
+                                                                      int R, int k, int strip,
+                                                                      int64_t *__restrict__ out,
+                                                                      int *__restrict__ out_count, int stride8,
+                                                                      const float *__restrict__ q_b, int64_t q_na,
+                                                                      int64_t *__restrict__ out_b, int64_t out_na,
+                                                                      float *__restrict__ out_d,
+                                                                      float *__restrict__ out_d_b)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rescore_staged_half_body<TILE, true>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride8, q_b,
+                                         q_na, out_b, out_na, nullptr, out_d, out_d_b);
+}
+
+// the lane-per-row kernel's distance-writing form on half rows: rescore_body<float, _Float16, float, true>, as
+// rescore_dist_kernel<float, _Float16, float> would be (the distance forms of the half kernels carry "distances"
+// in their names: the resource test of the float32 / float64 ones counts the names that hold "dist_kernel")
+__global__ __launch_bounds__(128) void rescore_half_distances_kernel(const float *__restrict__ q, int d,
+                                                                     const _Float16 *__restrict__ rows, int64_t n_rows,
+                                                                     const int64_t *__restrict__ cand, int R, int k,
+                                                                     int strip, int64_t *__restrict__ out,
+                                                                     int *__restrict__ out_count,
+                                                                     const float *__restrict__ q_b, int64_t q_na,
+                                                                     int64_t *__restrict__ out_b, int64_t out_na,
+                                                                     float *__restrict__ out_d,
+                                                                     float *__restrict__ out_d_b)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rescore_body<float, _Float16, float, true>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, q_b, q_na,
+                                               out_b, out_na, out_d, out_d_b);
+}
+
+// half vectors (float32 queries): the staged kernels where they apply (as for float32: d % 4 == 0, d <= 256,
+// R <= 256, form 1 / 2), else the lane-per-row kernels on _Float16 rows
+static int launch_rescore_half(const float *q, int d, const _Float16 *rows, int64_t n_rows, const int64_t *cand, int R,
+                               int64_t nq, int k, int strip, int64_t *out, int *out_count, hipStream_t s, int form,
+                               TkSecond q2, TkSecond out2, const TkSlotsOut *slots, float *dist, float *dist_b,
+                               bool want_d)
+{
+    dim3 grid((unsigned)nq), block(R <= 64 ? 64 : 128);
+    const int staged = form < 0 || form > 2 ? 2 : form;
+    if (staged && d % 4 == 0 && d <= 256 && R <= 256) {
+        const int stride8 = (d / 4) | 1;                      // odd number of 8-byte pieces
+        const int tile_rows = staged == 2 ? 32 : 64;
+        const bool fuse = slots != nullptr && k <= 64;
+        const TkSlotsOut *so = fuse ? slots : nullptr;
+        const size_t slds = (((size_t)R * 8 + 15) & ~(size_t)15) +
+                            (size_t)(((R + 3) & ~3) + ((d + 3) & ~3)) * 4 +
+                            (size_t)(((tile_rows + 1) * stride8 + 1) & ~1) * 8 + (fuse ? (size_t)k * 8 : 0);
+        if (slds <= 64 * 1024) {
+            if (want_d) {
+                if (tile_rows == 32)
+                    hipLaunchKernelGGL(rescore_staged_half_distances_kernel<32>, grid, dim3(64), slds, s, q, d, rows, n_rows,
+                                       cand, R, k, strip, out, out_count, stride8, (const float *)q2.b, q2.n_a,
+                                       (int64_t *)out2.b, out2.n_a, dist, dist_b);
+                else
+                    hipLaunchKernelGGL(rescore_staged_half_distances_kernel<64>, grid, dim3(64), slds, s, q, d, rows, n_rows,
+                                       cand, R, k, strip, out, out_count, stride8, (const float *)q2.b, q2.n_a,
+                                       (int64_t *)out2.b, out2.n_a, dist, dist_b);
+                return 0;
+            }
+            if (tile_rows == 32)
+                hipLaunchKernelGGL(rescore_staged_half_kernel<32>, grid, dim3(64), slds, s, q, d, rows, n_rows, cand, R,
+                                   k, strip, out, out_count, stride8, (const float *)q2.b, q2.n_a, (int64_t *)out2.b,
+                                   out2.n_a, so);
+            else
+                hipLaunchKernelGGL(rescore_staged_half_kernel<64>, grid, dim3(64), slds, s, q, d, rows, n_rows, cand, R,
+                                   k, strip, out, out_count, stride8, (const float *)q2.b, q2.n_a, (int64_t *)out2.b,
+                                   out2.n_a, so);
+            return fuse ? 1 : 0;
+        }
+    }
+    const size_t lds = (size_t)R * 8 + ((size_t)R + d) * 4 + 16;
+    if (want_d)
+        hipLaunchKernelGGL(rescore_half_distances_kernel, grid, block, lds, s, q, d, rows, n_rows, cand, R, k, strip,
+                           out, out_count, (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, dist, dist_b);
+    else
+        hipLaunchKernelGGL((rescore_kernel<float, _Float16, float>), grid, block, lds, s, q, d, rows, n_rows, cand, R,
+                           k, strip, out, out_count, (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a);
+    return 0;
+}
+
+// rows_dtype: TK_DATA_F32 / TK_DATA_F64 / TK_DATA_F16 (the coarse stage and tk_bottom_k pass 0 / 1)
+int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int rows_dtype,
+
                       int64_t n_rows, const int64_t *cand, int R, int64_t nq, int k, int strip,
                       int64_t *out, int *out_count, hipStream_t s, int form, TkSecond q2, TkSecond out2,
                       const TkSlotsOut *slots, void *dist, TkSecond dist2)
@@ -421,6 +676,12 @@ int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int 
     const bool want_d = dist != nullptr || dist2.b != nullptr;
     if (want_d) slots = nullptr;                // (the descriptors' caller asks for no distances)
     void *dist_b = out2.b ? const_cast<void *>(dist2.b) : nullptr;     // (rows of the second call: out2.n_a on)
+    if (rows_dtype == 2) {                      // half vectors: float32 queries only (the index's final stage)
+        if (q_is_f64) return -1;
+        return launch_rescore_half((const float *)q, d, (const _Float16 *)rows, n_rows, cand, R, nq, k, strip, out,
+                                   out_count, s, form, q2, out2, slots, (float *)dist, (float *)dist_b, want_d);
+    }
+    const int rows_is_f64 = rows_dtype == 1;
     const bool dbl = q_is_f64 || rows_is_f64;   // numpy promotes `Y - x` to float64
     size_t lds = (size_t)R * 8 + ((size_t)R + d) * (dbl ? 8 : 4) + 16;
     // one wave is enough for the coarse stage's 2 * n_probes + 10 candidates: the second wave of

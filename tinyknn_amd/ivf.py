@@ -98,14 +98,55 @@ class QueryStream:
             pass
 
 
+STORES = (None, "float32", "float16")
+_STORE_NAMES = {_lib.DATA_F32: "float32", _lib.DATA_F64: "float64", _lib.DATA_F16: "float16"}
+
+
+def check_store(store):
+    """The `store=` argument: None (the vectors as they are today: the caller's dtype), "float32" (the same,
+    said out loud) or "float16" (the device copy of the rescoring vectors in IEEE half)."""
+    if store not in STORES:
+        raise ValueError(f"store must be one of {STORES}, got {store!r}")
+    return store
+
+
+def half_rows(X, what, row0=0):
+    """X (float32) rounded to IEEE half as the device stores it: numpy's astype (round-to-nearest-even,
+    subnormals kept).  ValueError naming the first row with a value whose half is not finite (|x| >= 65520,
+    inf, NaN), or for float64 vectors — those callers asked for float64 rescoring."""
+    X = np.asarray(X)
+    if X.dtype != np.float32:
+        raise ValueError(f"{what}: store=\"float16\" takes float32 vectors, got {X.dtype} "
+                         "(float64 vectors are rescored in float64)")
+    bad = ~(np.abs(X) < np.float32(65520.0))
+    if bad.any():
+        row = int(np.argmax(bad.reshape(len(X), -1).any(axis=1)))
+        raise ValueError(f"{what}: half storage: row {row0 + row} holds a value whose half is not finite "
+                         "(|x| >= 65520, inf or NaN)")
+    with np.errstate(over="ignore"):
+        return np.ascontiguousarray(X).astype(np.float16)
+
+
+def _half_refusal(call, *args):
+    """The library's refusal of a row whose half is not finite (TK_ERR_ARG) as the ValueError the host checks raise."""
+    try:
+        return _lib.check(call(*args))
+    except AssertionError as e:
+        if "half is not finite" in str(e):
+            raise ValueError(str(e)) from None
+        raise
+
+
 class ResidentData:
     """Stands where IVF.data stood when the vectors live in HBM only (IVF.build_resident):
-    shape, dtype and rows by id (tk_index_read_rows)."""
+    shape, dtype and rows by id (tk_index_read_rows).  dtype stays float32 for a half store (`store`):
+    rows come back widened."""
 
     def __init__(self, dev):
         self._dev = dev
         self.shape = (dev.N, dev.d)
         self.dtype = np.dtype(np.float32)
+        self.store = dev.store
 
     def __len__(self):
         return self.shape[0]
@@ -284,10 +325,14 @@ class DeviceIndex:
         """PQ blocks = bytes per code"""
         return self.dq // self.dpb
 
-    def __init__(self, ivf, owner=None, rank=0, world=1):
+    def __init__(self, ivf, owner=None, rank=0, world=1, store=None):
         """owner (n_lists,) int32 + rank/world: list-sharded index — only the codes of the
-        lists with owner[l] == rank are uploaded (tinyknn_hip.h, tk_index_set_lists_shard)."""
+        lists with owner[l] == rank are uploaded (tinyknn_hip.h, tk_index_set_lists_shard).
+        store: None = ivf.store; "float16": the vectors are rounded to half here and only the halfs are
+        uploaded (ValueError for a value whose half is not finite, or float64 vectors)."""
         L = _lib.lib()
+        store = check_store(store) or getattr(ivf, "store", None)
+        half = half_rows(ivf.data, "DeviceIndex") if store == "float16" else None      # (refused before anything is made)
         pq = ivf.pq
         self._new_state()
         self._h = L.tk_index_create()
@@ -337,9 +382,13 @@ class DeviceIndex:
         # IVF.data keeps the dtype of the X passed to build (ivf.py:77); float64 vectors
         # are rescored in float64 like numpy would
         is64 = ivf.data.dtype != np.float32
-        data = np.ascontiguousarray(ivf.data, dtype=np.float64 if is64 else np.float32)
-        _lib.check(L.tk_index_set_data(self._h, data.ctypes.data, int(is64), data.shape[0],
-                                       data.shape[1]))
+        if half is not None:
+            data = half
+            _lib.check(L.tk_index_set_data(self._h, data.ctypes.data, _lib.DATA_F16, data.shape[0], data.shape[1]))
+        else:
+            data = np.ascontiguousarray(ivf.data, dtype=np.float64 if is64 else np.float32)
+            _lib.check(L.tk_index_set_data(self._h, data.ctypes.data, int(is64), data.shape[0],
+                                           data.shape[1]))
         self._f64 = bool(is64)
         self.N = int(data.shape[0])
         self.code_bytes = int(codes.nbytes)
@@ -377,6 +426,22 @@ class DeviceIndex:
         self.angular = ivf.metric == "angular"
         self._R = None if pq.R is None else np.ascontiguousarray(pq.R, dtype=np.float64)
         return self
+
+    @property
+    def store(self):
+        """How the rescoring vectors sit in HBM: "float32", "float64" or "float16" (tk_index_store)."""
+        return _STORE_NAMES.get(_lib.lib().tk_index_store(self._h))
+
+    @property
+    def vector_bytes(self):
+        """Bytes of the rescoring vectors in HBM: N * d * the stored element's size."""
+        return self.N * self.d * {"float64": 8, "float16": 2}.get(self.store, 4)
+
+    def narrow(self):
+        """The float32 vectors this index holds in HBM become halfs (tk_index_narrow_data): checked first
+        (ValueError naming the first row with a value whose half is not finite; the index stays float32),
+        converted into a new buffer, the float32 one freed.  Nothing to do on a half index."""
+        _half_refusal(_lib.lib().tk_index_narrow_data, self._h)
 
     def synth_data(self, seed, centres=None, sigma=1.0, row0=0, n=None):
         """rows [row0, row0 + n) = centres[c(row)] + sigma * N(0, 1) from the seeded
@@ -451,7 +516,7 @@ class DeviceIndex:
         return ac, cc
 
     def read_rows(self, rows):
-        """IVF.data[rows] for float32 vectors held in HBM (tk_index_read_rows)."""
+        """IVF.data[rows] for float32 vectors held in HBM, or half vectors widened (tk_index_read_rows)."""
         rows = np.ascontiguousarray(rows, dtype=np.int64).ravel()
         out = np.zeros((len(rows), self.d), dtype=np.float32)
         _lib.check(_lib.lib().tk_index_read_rows(self._h, _lib.ptr(rows, _lib._i64p), len(rows),
@@ -475,7 +540,9 @@ class DeviceIndex:
         nearest (n, kp) / labels (n, M) / list_columns (n_lists, kp): None = found on the device as the
         device build finds them (all_centers needed) / encoded on the device / the index's own.
         center_codes: packed codes of all_centers[:n_lists'] where the rows activate new centres (None:
-        coded on the device).  Batches in flight finish first; allowed sets made before stop working."""
+        coded on the device).  Batches in flight finish first; allowed sets made before stop working.
+        A half index takes float32 rows: assigned and coded from their float32 values, stored rounded
+        (ValueError for a row whose half is not finite: nothing changes)."""
         self._lists_may_change("add", "takes no rows")
         is64 = self._f64
         rows = np.ascontiguousarray(rows, dtype=np.float64 if is64 else np.float32)
@@ -503,10 +570,11 @@ class DeviceIndex:
             A, Y, yn = self._search_centres(all_centers)
             C_ = len(A)
         n_active = C.c_int64(0)
-        _lib.check(_lib.lib().tk_index_add_rows(
+        _half_refusal(
+            _lib.lib().tk_index_add_rows,
             self._h, rows.ctypes.data, int(is64), n, kp, near_p, lab_p, cols_p, int(bool(normalise)),
             None if A is None else A.ctypes.data, None if Y is None else Y.ctypes.data,
-            None if yn is None else yn.ctypes.data, C_, cc_p, C.byref(n_active)))
+            None if yn is None else yn.ctypes.data, C_, cc_p, C.byref(n_active))
         self.n_lists = int(n_active.value)
         self._refresh_lists()
         return self.n_lists
@@ -705,7 +773,8 @@ class DeviceIndex:
 
     def knn_brute(self, qn, k):
         """Exact k nearest rows of IVF.data for normalised queries (ground truth of recall;
-        tk_index_knn_brute: f32 MFMA, numpy's distances bit for bit), ascending."""
+        tk_index_knn_brute: f32 MFMA, numpy's distances bit for bit), ascending.  Float32 vectors only:
+        refused on a float64 and on a half index."""
         qn = np.ascontiguousarray(qn, dtype=np.float32)
         assert qn.shape[1] == self.d
         out = np.empty((qn.shape[0], k), dtype=np.int64)
@@ -981,6 +1050,7 @@ class IVF:
     all_centers = None      # fit's coarse centres
     list_columns = None     # (n_lists, kp) members per (list, column of the build's nearest); None: not recorded
     _build_device = None    # did build() search on the GPU?  None: not built here (fast_pq.device_build decides)
+    store = None            # how the device keeps the rescoring vectors: None / "float32" / "float16" (build's store=)
 
     def __init__(self, metric, n_clusters, pq=None):
         assert metric in ["euclidean", "angular"]
@@ -1027,8 +1097,11 @@ class IVF:
             self.pq.fit(X, verbose=verbose)
         return self
 
-    def build(self, X, n_probes=2, verbose=False, device=None):
+    def build(self, X, n_probes=2, verbose=False, device=None, store=None):
         """Assign every point to its n_probes nearest centres and encode the lists.
+        store="float16": the DEVICE copy of the rescoring vectors is kept in IEEE half (summed in float32;
+        INTEGRATION.md §2g) — IVF.data, the lists and the codes are what store=None gives.  ValueError, before
+        anything changes, for float64 X or a value whose half is not finite.
         reference: ivf.py:53-104.  device=True (default: fast_pq.device_build): the two
         searches — nearest centres per point, nearest centroid per block — run on the GPU
         (build.hip) and give the lists and codes numpy gives; everything else (normalisation,
@@ -1036,10 +1109,17 @@ class IVF:
         assert n_probes <= self.n_clusters, (
             f"Can't assign points to {n_probes} clusters, as index only has {self.n_clusters}")
         device = _fp.device_build if device is None else device
-        self._dev = None
-        self.data = data = X.copy()
+        check_store(store)
+        if store == "float16" and np.asarray(X).dtype != np.float32:
+            half_rows(X, "IVF.build")                   # (raises: float64 vectors)
+        data = X.copy()
         if self.metric == "angular":
             data /= np.linalg.norm(data, axis=1, keepdims=True)
+        if store == "float16":
+            half_rows(data, "IVF.build")                # the refusals only: the rounding happens at upload
+        self._dev = None
+        self.data = data
+        self.store = store
         with timer(verbose, "Computing nearest clusters..."):
             if device:
                 nearest = self._nearest_on_device(data, n_probes)
@@ -1181,6 +1261,8 @@ class IVF:
             extra["all_centers"] = self.all_centers
         if self.list_columns is not None:
             extra["list_columns"] = self.list_columns
+        if self.store is not None:          # (the vectors are written unrounded: the upload rounds again, same bits)
+            extra["store"] = self.store
         path = self._npz_path(path)
         np.savez(path, format_version=1, metric=self.metric, n_clusters=self.n_clusters,
                  use_kmeans=int(self.pq.use_kmeans), rotate_dim=-1 if self.pq.rotate_dim is None else int(self.pq.rotate_dim),
@@ -1221,9 +1303,10 @@ class IVF:
         ivf.data = z["data"] if data is None else data
         # (files written before add() existed have no list_columns: add() recovers them)
         ivf.list_columns = z["list_columns"] if "list_columns" in z else None
+        ivf.store = check_store(str(z["store"])) if "store" in z else None     # (files written before store= existed)
         return ivf
 
-    def build_resident(self, N, d, seed, centres=None, sigma=1.0, verbose=False, n_probes=1):
+    def build_resident(self, N, d, seed, centres=None, sigma=1.0, verbose=False, n_probes=1, store=None):
         """IVF.build(X, n_probes=1 or 2) (ivf.py:53-104) for N synthetic float32 vectors that are
         generated IN HBM (seeded, devbuild.hip) and never visit the host — the way the
         100M x 128 configuration is assembled.  Needs all_centers and a
@@ -1233,8 +1316,11 @@ class IVF:
         the device front end's float64 FMA chain, not numpy's DGEMM, so a code can differ
         from IVF.build's where that flips a nearest centroid.  Afterwards: active_centers,
         pq_transformed_centers and list_sizes on the host; data / ids / codes stay in HBM
-        (device_index().export_lists() / read_rows() fetch them for a checker)."""
+        (device_index().export_lists() / read_rows() fetch them for a checker).
+        store="float16": after the build (which reads the float32 rows) the vectors are narrowed to half in
+        HBM (DeviceIndex.narrow: ValueError for a value whose half is not finite)."""
         assert self.pq.centers is not None and self.all_centers is not None
+        check_store(store)
         with timer(verbose, "Generating vectors in HBM..."):
             dev = DeviceIndex.resident(self, N, d)
             dev.synth_data(seed, centres, sigma)
@@ -1253,6 +1339,9 @@ class IVF:
                                    "n_probes <= 2 or on the host (IVF.build)" % n_probes)
         with timer(verbose, "Building lists on the device..."):
             L = dev.build_dev(self.all_centers, n_probes)
+        if store == "float16":
+            dev.narrow()
+        self.store = store
         self.active_centers, cc = dev.export_centers()
         self.pq_transformed_centers = TransformedData(L, cc)
         self.list_sizes = dev.list_sizes
@@ -1332,6 +1421,8 @@ class IVF:
         new = np.array(X, dtype=self.data.dtype, copy=True)         # ivf.py:77-79: X's dtype, normalised
         if self.metric == "angular":
             new /= np.linalg.norm(new, axis=1, keepdims=True)
+        if self.store == "float16":         # (the refusal, before anything changes; the device rounds its copy)
+            half_rows(new, "IVF.add", row0=len(self.data))
         with timer(verbose, "Computing nearest clusters..."):
             if device:
                 nearest = self._nearest_on_device(new, kp)
