@@ -3,13 +3,12 @@ the combinations they do not support before any device work, and the distance-wr
 the staged kernel's register budget, without scratch (read from the compiler, as test_kernel_resources does)."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from kernel_usage import have_hipcc, kernel_usage
 
 ENTRY_POINTS = {
     "tk_index_query_batch_dist": 11,
@@ -62,26 +61,10 @@ def test_out_of_scope_calls_do_not_take_the_option():
         assert "return_distances" not in names and not (code.co_flags & 0x08), f.__qualname__
 
 
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-         "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", "-o", os.devnull]
-
-
 def test_distance_kernels_resources():
-    if not shutil.which(HIPCC) and not os.path.exists(HIPCC):
+    if not have_hipcc():
         pytest.skip("hipcc not found")
-    r = subprocess.run([HIPCC] + FLAGS + ["rescore.hip"], cwd=os.path.join(ROOT, "tinyknn_amd", "csrc"),
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = usage.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    usage = kernel_usage("rescore.hip")
     staged = {k: v for k, v in usage.items() if "rescore_staged_dist_kernelILi32EE" in k}
     assert staged, sorted(usage)
     for name, u in staged.items():

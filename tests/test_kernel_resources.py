@@ -7,17 +7,12 @@ GloVe-shaped batch launches, zero scratch and the occupancy the design counts on
 """
 import os
 import re
-import shutil
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tinyknn_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-         "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", "-o", os.devnull]
+from kernel_usage import CSRC, HIPCC, have_hipcc, kernel_usage
 
 # (file, substring of the mangled name) -> (max VGPRs, min waves/SIMD)
 PINNED = {
@@ -69,29 +64,13 @@ SGPR_SPILLS_OK = {"heap_replay_lanes_kernelILb1ELb1ELi32ELb0ELb0EE": 48, "heap_r
                   "heap_replay_pair_kernelILb1ELi4EE": 96, "heap_replay_pair_kernelILb0ELi4EE": 96}
 
 
-def _usage(fname):
-    r = subprocess.run([HIPCC] + FLAGS + [fname], cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = {}
-    cur = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return out
-
-
 @pytest.fixture(scope="module")
 def usage():
-    if not shutil.which(HIPCC) and not os.path.exists(HIPCC):
+    if not have_hipcc():
         pytest.skip("hipcc not found")
     files = sorted({f for f, _ in PINNED} | set(NO_SCRATCH_FILES))
     with ThreadPoolExecutor(max_workers=4) as ex:
-        return dict(zip(files, ex.map(_usage, files)))
+        return dict(zip(files, ex.map(kernel_usage, files)))
 
 
 @pytest.mark.parametrize("key", sorted(PINNED))
@@ -122,7 +101,7 @@ def test_no_kernel_of_the_hot_files_uses_scratch(usage):
 def test_twin_replay_parks_its_sgprs_outside_the_loops():
     """The TWIN form of the lane replay reports SGPR spills: kernel arguments that are only needed behind the replay
     loop.  They must stay there — no v_readlane / v_writelane in any basic block of a loop (read off the ISA)."""
-    if not shutil.which(HIPCC) and not os.path.exists(HIPCC):
+    if not have_hipcc():
         pytest.skip("hipcc not found")
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:

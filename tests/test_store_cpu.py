@@ -4,11 +4,11 @@ and the register budget of the half rescoring kernel."""
 import os
 import pickle
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+from kernel_usage import have_hipcc, kernel_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -152,28 +152,12 @@ def test_header_declares_and_the_bindings_know_the_new_entries():
         assert getattr(lib, name).argtypes is not None
 
 
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-         "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", "-o", os.devnull]
-
-
 def test_half_rescoring_kernels_meet_the_float32_kernel_s_budget():
     """The default instantiation of the half staged kernel under its float32 sibling's pin (<= 128 VGPRs, >= 4 waves
     per SIMD, zero scratch, no spills); every half kernel of rescore.hip without scratch or spills."""
-    if not shutil.which(HIPCC) and not os.path.exists(HIPCC):
+    if not have_hipcc():
         pytest.skip("hipcc not found")
-    r = subprocess.run([HIPCC] + FLAGS + ["rescore.hip"], cwd=os.path.join(ROOT, "tinyknn_amd", "csrc"),
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = usage.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    usage = kernel_usage("rescore.hip")
     pinned = {k: v for k, v in usage.items() if "rescore_staged_half_kernelILi32EE" in k}
     assert len(pinned) == 1, sorted(usage)
     for name, u in pinned.items():

@@ -252,6 +252,41 @@ def test_rescore_forms_heap_modes_and_allowed_sets_on_one_index(tk, oracle):
             aset.close()
 
 
+@pytest.mark.parametrize("d", [256, 132])
+def test_rows_of_more_than_32_pieces_under_every_rescore_form(tk, oracle, d):
+    """Rows of 33 ... 64 pieces spread over 64 lanes in the staged kernels (32 for every narrower row).  d = 256: 64
+    pieces, every lane busy; the float32 tile of 64 rows is (64 + 1) * 65 * 16 = 67 600 bytes, beyond the 64 KB of a
+    workgroup, so form 1 on float32 rows falls through to the lane-per-row kernel while the half tile (33 800
+    bytes) stays staged.  d = 132: 33 pieces, the first size with 64 lanes per row, 31 of them idle.  The half
+    index against the oracle on the rounded rows; float32 indexes on the rounded rows (the twin) and on the
+    unrounded ones against the oracle on theirs."""
+    from tinyknn_amd import _lib
+    ivf, qn, qp = _synth(tk, d, 9000, 150, "euclidean", 300)
+    data_r = rounded(ivf.data)
+    assert not np.array_equal(data_r, ivf.data)
+    plain = twin(ivf)
+    plain.data = ivf.data
+    for index, data, store in ((ivf, data_r, "float16"), (twin(ivf), data_r, "float32"), (plain, ivf.data, "float32")):
+        ox = oracle_index(oracle, index, data)
+        dev = index.device_index()
+        assert dev.store == store
+        for n_probes in (1, 5):
+            want = ox.query_batch(qn, 10, n_probes)
+            wd = exact_distances(oracle, qn, data, want)
+            got = []
+            for form in (0, 1, 2):
+                dev.set_option(_lib.OPT_RESCORE_FORM, form)
+                ids, dist = dev.query_batch(qn, qp, 10, n_probes, return_distances=True)
+                np.testing.assert_array_equal(ids, want, err_msg=f"{store} form {form} p{n_probes}")
+                assert same_bits(dist, wd), (store, form, n_probes)
+                np.testing.assert_array_equal(dev.query_batch(qn, qp, 10, n_probes), want)
+                got.append((ids, dist))
+            for ids, dist in got[1:]:
+                np.testing.assert_array_equal(ids, got[0][0])
+                assert same_bits(dist, got[0][1])
+        dev.set_option(_lib.OPT_RESCORE_FORM, 2)
+
+
 # ---- pipelined pairs, the stream session, a captured graph ------------------------------------------------------
 @pytest.fixture(scope="module")
 def big(tk):

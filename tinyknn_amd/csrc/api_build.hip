@@ -847,10 +847,7 @@ extern "C" int tk_index_read_rows(tk_index *ix, const int64_t *rows, int64_t n, 
     if (rc == TK_OK) {
         hipError_t e = hipMemcpy(r.p, rows, (size_t)n * 8, hipMemcpyHostToDevice);
         if (e == hipSuccess) {
-            if (ix->data_dtype == TK_DATA_F16)
-                tk_launch_gather_rows_half(ix->data.p, ix->d, r.as<int64_t>(), n, o.as<float>(), 0);
-            else
-                tk_launch_gather_rows(ix->data.as<float>(), ix->d, r.as<int64_t>(), n, o.as<float>(), 0);
+            tk_launch_gather_rows(ix->data.p, ix->data_dtype, ix->d, r.as<int64_t>(), n, o.as<float>(), 0);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpy(out, o.p, (size_t)n * ix->d * 4, hipMemcpyDeviceToHost);

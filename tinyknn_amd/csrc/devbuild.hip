@@ -572,26 +572,11 @@ void tk_launch_row_copies(const int64_t *ids, int64_t T, int *cnt, int64_t N, in
         hipLaunchKernelGGL(copies_summary_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, cnt, N, out);
 }
 
-// rows of a float32 (N, d) matrix gathered by id (rescoring vectors for the checker)
-__global__ void gather_rows_kernel(const float *__restrict__ X, int d, const int64_t *__restrict__ rows,
-                                   int64_t n, float *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n * d) return;
-    const int64_t r = i / d;
-    out[i] = X[rows[r] * d + (i - r * d)];
-}
-
-void tk_launch_gather_rows(const float *X, int d, const int64_t *rows, int64_t n, float *out, hipStream_t s)
-{
-    if (n <= 0) return;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n * d + 255) / 256)), dim3(256), 0, s, X, d, rows,
-                       n, out);
-}
-
-// ... and of vectors stored as IEEE half (TK_DATA_F16), widened (exact)
-__global__ void gather_rows_half_kernel(const _Float16 *__restrict__ X, int d, const int64_t *__restrict__ rows,
-                                        int64_t n, float *__restrict__ out)
+// rows of an (N, d) matrix gathered by id as float32 (rescoring vectors for the checker): float32 vectors, or
+// vectors stored as IEEE half, widened (exact)
+template <typename TY>
+__global__ void gather_rows_kernel(const TY *__restrict__ X, int d, const int64_t *__restrict__ rows, int64_t n,
+                                   float *__restrict__ out)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * d) return;
@@ -599,11 +584,15 @@ __global__ void gather_rows_half_kernel(const _Float16 *__restrict__ X, int d, c
     out[i] = (float)X[rows[r] * d + (i - r * d)];
 }
 
-void tk_launch_gather_rows_half(const void *X, int d, const int64_t *rows, int64_t n, float *out, hipStream_t s)
+void tk_launch_gather_rows(const void *X, int data_dtype, int d, const int64_t *rows, int64_t n, float *out,
+                           hipStream_t s)
 {
     if (n <= 0) return;
-    hipLaunchKernelGGL(gather_rows_half_kernel, dim3((unsigned)((n * d + 255) / 256)), dim3(256), 0, s,
-                       (const _Float16 *)X, d, rows, n, out);
+    const dim3 grid((unsigned)((n * d + 255) / 256)), block(256);
+    if (data_dtype == 2)
+        hipLaunchKernelGGL(gather_rows_kernel<_Float16>, grid, block, 0, s, (const _Float16 *)X, d, rows, n, out);
+    else
+        hipLaunchKernelGGL(gather_rows_kernel<float>, grid, block, 0, s, (const float *)X, d, rows, n, out);
 }
 
 // Half storage of float32 rows.  The check pass: *first_bad (set to INT64_MAX by the caller) = the first row

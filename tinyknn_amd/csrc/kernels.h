@@ -449,9 +449,9 @@ void tk_launch_compact_lists(const uint4 *old_tiled, const int64_t *old_chunk_of
 // copies per row of T labels into cnt (N ints, zeroed); out = {largest row stored, most copies, fewest copies of a
 // stored row, labels outside [0, N)}, {-1, 0, INT_MAX, 0} on entry
 void tk_launch_row_copies(const int64_t *ids, int64_t T, int *cnt, int64_t N, int *out, hipStream_t s);
-void tk_launch_gather_rows(const float *X, int d, const int64_t *rows, int64_t n, float *out, hipStream_t s);
-// the same for vectors stored as IEEE half (TK_DATA_F16): out = the rows widened
-void tk_launch_gather_rows_half(const void *X, int d, const int64_t *rows, int64_t n, float *out, hipStream_t s);
+// n rows of X (N, d) by id as float32; data_dtype: TK_DATA_F32, or TK_DATA_F16 (IEEE half, widened)
+void tk_launch_gather_rows(const void *X, int data_dtype, int d, const int64_t *rows, int64_t n, float *out,
+                           hipStream_t s);
 // half storage of float32 rows (n, d) on the device: *first_bad (preset to ~0) = the first row with a value whose
 // half is not finite (|x| >= 65520, inf, NaN); `out` = the rows as halfs, round-to-nearest-even, subnormals kept
 void tk_launch_check_half(const float *X, int64_t n, int d, unsigned long long *first_bad, hipStream_t s);

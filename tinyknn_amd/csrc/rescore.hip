@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
 #include "kernels.h"
 
 // (tried: nontemporal loads of the candidate rows, so that they would not evict the scan
@@ -173,16 +174,37 @@ __global__ __launch_bounds__(128) void rescore_dist_kernel(const TX *__restrict_
                                   out_na, out_d, out_d_b);
 }
 
-// sqdist_row<float, float> for a row held in LDS as 16-byte pieces (explicit 128-bit reads: with
-// an odd piece stride the 64 lanes' reads are conflict-free; 32-bit reads of the same layout
-// would collide four ways).  Same operations in the same order.
-__device__ __forceinline__ float sqdist_row_lds(const float4 *__restrict__ y4, const float *xs, int d)
+// A staged row travels and rests as pieces of four elements: 16 bytes of float32, 8 bytes of IEEE half (GloVe's
+// 200-byte half rows have no whole number of 16-byte pieces).
+template <typename TY> struct RowPiece;
+template <> struct RowPiece<float> { typedef float4 type; };
+template <> struct RowPiece<_Float16> { typedef uint2 type; };
+
+__device__ __forceinline__ void unpack4(const float4 p, float *o)
+{
+    o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = p.w;
+}
+
+__device__ __forceinline__ void unpack4(const uint2 p, float *o)    // float(half): exact
+{
+    typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+    const half2_t lo = __builtin_bit_cast(half2_t, p.x), hi = __builtin_bit_cast(half2_t, p.y);
+    o[0] = (float)lo.x; o[1] = (float)lo.y; o[2] = (float)hi.x; o[3] = (float)hi.y;
+}
+
+// sqdist_row<float, float> (after float(y) for half rows) for a row held in LDS as pieces P, read whole: same
+// operations in the same order (un-fused, four lane-accumulators, groups folded 3,2,1,0, pairwise horizontal add).
+template <typename P>
+__device__ __forceinline__ float sqdist_row_lds(const P *__restrict__ y, const float *xs, int d)
 {
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     int i = 0;
     for (; d - i >= 16; i += 16) {
-        const float4 a = y4[(i >> 2)], b = y4[(i >> 2) + 1], c = y4[(i >> 2) + 2], e = y4[(i >> 2) + 3];
-        const float yv[16] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, e.x, e.y, e.z, e.w};
+        float yv[16];
+        unpack4(y[(i >> 2)], yv);
+        unpack4(y[(i >> 2) + 1], yv + 4);
+        unpack4(y[(i >> 2) + 2], yv + 8);
+        unpack4(y[(i >> 2) + 3], yv + 12);
         float df[16];
 #pragma unroll
         for (int t = 0; t < 16; t++) df[t] = yv[t] - xs[i + t];
@@ -195,8 +217,8 @@ __device__ __forceinline__ float sqdist_row_lds(const float4 *__restrict__ y4, c
         }
     }
     for (; i < d; i += 4) {          // d % 4 == 0: whole vectors only
-        const float4 a = y4[i >> 2];
-        const float yv[4] = {a.x, a.y, a.z, a.w};
+        float yv[4];
+        unpack4(y[i >> 2], yv);
 #pragma unroll
         for (int l = 0; l < 4; l++) {
             const float df = yv[l] - xs[i + l];
@@ -267,31 +289,36 @@ __device__ __forceinline__ void slots_epilogue(const TkSlotsOut &so, int64_t qi,
     if (lane == 0 && so.repeat_flag) so.repeat_flag[qi] = wrapped;
 }
 
-// The same for float32 vectors and queries with d % 4 == 0, rows staged through LDS: in the
-// kernel above a lane walks its own row, so every load instruction of a wave touches 64
-// different lines — 2775 line visits per query at R = 111, d = 100 — and that address traffic
-// is what this kernel costs the scan kernels it runs beside (profiles/r02_scan_grid.md).  Here
-// the wave reads 64 candidate rows as one stream of 16-byte pieces, consecutive lanes =
-// consecutive pieces of a row (4 lines per 400-byte row), drops them into a tile whose row
-// stride is an odd number of 16-byte pieces (conflict-free ds_read_b128), and each lane then
-// runs the identical summation (sqdist_row: numpy's order) on its row from LDS.
-// LDS: cand[R] (int64) | dist[R] | x[d] | tile[64 + 1 spare][stride]
+// rescore_body for float32 sums (float32 queries; rows TY = float, or _Float16: the result is what the float32
+// rows float(half(x)) give) with d % 4 == 0, rows staged through LDS: in the kernel above a lane walks its own
+// row, so every load instruction of a wave touches 64 different lines — 2775 line visits per query at R = 111,
+// d = 100 — and that address traffic is what it costs the scan kernels it runs beside
+// (profiles/r02_scan_grid.md).  Here the wave reads TILE candidate rows as one stream of pieces (RowPiece),
+// consecutive lanes = consecutive pieces of a row (4 lines per 400-byte row), drops them into a tile, and each
+// lane then runs the identical summation (sqdist_row: numpy's order) on its row from LDS.  A half tile stays in
+// half (half the float32 tile's LDS) and is widened where it is summed.
+// The row stride of the tile is an ODD number of pieces, which makes a lane's whole-piece reads conflict-free:
+// 16-byte pieces are read with ds_read_b128 (32-bit reads of the same layout would collide four ways); 8-byte
+// pieces with ds_read_b64, whose lane groups are {0-31}, {32-63}: a piece covers two of the 64 banks, so lane t's
+// piece j sits on bank pair (t * stride + j) mod 32 — distinct over 32 lanes exactly when the stride is odd.
+// LDS: cand[R] (int64) | dist[R] | x[d] | tile[TILE + 1 spare][stride] | have_slots: the k results (int64)
 // DIST as rescore_body (the short-heap branch reads its rows with sqdist_row: the same summation as sqdist_row_lds)
-template <int TILE, bool DIST>
+template <typename TY, int TILE, bool DIST>
 __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const float *__restrict__ q, int d,
-                                                    const float *__restrict__ rows, int64_t n_rows,
+                                                    const TY *__restrict__ rows, int64_t n_rows,
                                                     const int64_t *__restrict__ cand, int R, int k, int strip,
                                                     int64_t *__restrict__ out, int *__restrict__ out_count,
-                                                    int stride4, const float *__restrict__ q_b, int64_t q_na,
+                                                    int stride, const float *__restrict__ q_b, int64_t q_na,
                                                     int64_t *__restrict__ out_b, int64_t out_na,
                                                     const TkSlotsOut *__restrict__ so_dev, float *__restrict__ out_d,
                                                     float *__restrict__ out_d_b)
 {
+    typedef typename RowPiece<TY>::type P;
     const bool have_slots = so_dev != nullptr;
     int64_t *cs = (int64_t *)smem;
     float *ds = (float *)(smem + (((size_t)R * 8 + 15) & ~(size_t)15));
     float *xs = ds + ((R + 3) & ~3);
-    float4 *tile = (float4 *)(xs + ((d + 3) & ~3));      // 16-byte aligned
+    P *tile = (P *)(xs + ((d + 3) & ~3));                // 16-byte aligned
     const int tid = threadIdx.x;
     const int64_t qi = blockIdx.x;
     const int64_t *c = cand + qi * R;
@@ -322,14 +349,14 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
                 if (t < nc) {
                     int64_t id = cs[t];
                     if (id < 0) id += n_rows;
-                    dv = sqdist_row<float, float>(rows + id * (int64_t)d, xs, d);
+                    dv = sqdist_row<float, TY>(rows + id * (int64_t)d, xs, d);
                 }
                 od[t] = dv;
             }
         if (have_slots) slots_epilogue(*so_dev, qi, k, tid, tid < nc ? cs[tid < k ? tid : 0] : -1);
         return;
     }
-    const int d4 = d >> 2;
+    const int d4 = d >> 2;                   // pieces per row
     // lanes_per_row = the power of two >= d4 (16, 32 or 64): a load instruction covers
     // 64 / lanes_per_row whole rows, lane (rr, pc) fetches piece pc of its row
     const int lpr_log = d4 <= 16 ? 4 : (d4 <= 32 ? 5 : 6);
@@ -339,27 +366,29 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
         if (pc < d4)
             for (int r0 = rr; r0 < nt; r0 += 16 * rpi) {
                 // sixteen loads in flight per lane before the first LDS store waits for one
-                float4 v[16];
+                P v[16];
 #pragma unroll
                 for (int u = 0; u < 16; u++) {
                     const int r = r0 + u * rpi;
                     int64_t id = cs[t0 + (r < nt ? r : nt - 1)];
                     if (id < 0) id += n_rows;  // numpy fancy indexing with a negative index
-                    v[u] = ((const float4 *)(rows + id * (int64_t)d))[pc];
+                    v[u] = ((const P *)(rows + id * (int64_t)d))[pc];
                 }
                 // unconditional stores (rows past the tile go to a spare row): a branch here
                 // lets the compiler sink each load next to its store, one exposed latency apiece
 #pragma unroll
                 for (int u = 0; u < 16; u++) {
                     const int r = r0 + u * rpi;
-                    tile[(r < nt ? r : TILE) * stride4 + pc] = v[u];
+                    tile[(r < nt ? r : TILE) * stride + pc] = v[u];
                 }
             }
         __syncthreads();
-        if (tid < nt) ds[t0 + tid] = sqdist_row_lds(tile + tid * stride4, xs, d);
+        if (tid < nt) ds[t0 + tid] = sqdist_row_lds(tile + tid * stride, xs, d);
         __syncthreads();
     }
-    int64_t *ps = (int64_t *)(tile + (TILE + 1) * stride4);      // have_slots: the k results in order
+    // have_slots: the k results in order, behind the tile rounded up to 16 bytes
+    constexpr int PER16 = 16 / (int)sizeof(P);
+    int64_t *ps = (int64_t *)(tile + (((TILE + 1) * stride + PER16 - 1) & ~(PER16 - 1)));
     for (int t = tid; t < nc; t += 64) {
         const float dv = ds[t];
         int rank = 0;
@@ -380,6 +409,9 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
     }
 }
 
+// The kernels of the body, under the names the resource tests pin and profiles/ records.  (The distance forms on
+// half rows carry "distances" in their names: the resource test of the float32 / float64 ones counts the names that
+// hold "dist_kernel".  They take no descriptors: the coarse stage, which writes them, asks for no distances.)
 template <int TILE>
 __global__ __launch_bounds__(64) void rescore_staged_kernel(const float *__restrict__ q, int d,
                                                             const float *__restrict__ rows,
@@ -392,11 +424,10 @@ __global__ __launch_bounds__(64) void rescore_staged_kernel(const float *__restr
                                                             const TkSlotsOut *__restrict__ so_dev)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    rescore_staged_body<TILE, false>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride4, q_b, q_na,
-                                     out_b, out_na, so_dev, nullptr, nullptr);
+    rescore_staged_body<float, TILE, false>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride4, q_b,
+                                            q_na, out_b, out_na, so_dev, nullptr, nullptr);
 }
 
-// (no descriptors: the coarse stage, which writes them, asks for no distances)
 template <int TILE>
 __global__ __launch_bounds__(64) void rescore_staged_dist_kernel(const float *__restrict__ q, int d,
                                                                  const float *__restrict__ rows, int64_t n_rows,
@@ -408,161 +439,8 @@ __global__ __launch_bounds__(64) void rescore_staged_dist_kernel(const float *__
                                                                  float *__restrict__ out_d, float *__restrict__ out_d_b)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    rescore_staged_body<TILE, true>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride4, q_b, q_na,
-                                    out_b, out_na, nullptr, out_d, out_d_b);
-}
-
-// ---------------------------------------------------------------------------
-// Vectors stored as IEEE half (TK_DATA_F16), float32 queries, float32 sums: the result is what the float32
-// kernels above give on the rows float(half(x)).  Rows are d halfs, so the unit of the stream is an 8-byte
-// piece of 4 halfs (d % 4 == 0; GloVe's 200-byte rows have no whole number of 16-byte pieces) and everything
-// else keeps the float32 kernel's geometry: lanes_per_row = the power of two >= d / 4, (rr, pc), sixteen loads
-// in flight per lane.  The tile stays in half (half the float32 tile's LDS) and is widened where it is summed.
-// A lane reads its row with ds_read_b64: the lane groups are {0-31}, {32-63} and a piece covers two of the 64
-// banks, so lane t's piece j sits on bank pair (t * stride8 + j) mod 32 — distinct over 32 lanes exactly when
-// the row stride is an ODD number of 8-byte pieces.
-// sqdist_row<float, float> after float(y) for a row held in LDS as 8-byte pieces of 4 halfs: same operations
-// in the same order (un-fused, four lane-accumulators, groups folded 3,2,1,0, pairwise horizontal add).
-__device__ __forceinline__ void widen4(const uint2 p, float *o)
-{
-    typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-    const half2_t lo = __builtin_bit_cast(half2_t, p.x), hi = __builtin_bit_cast(half2_t, p.y);
-    o[0] = (float)lo.x; o[1] = (float)lo.y; o[2] = (float)hi.x; o[3] = (float)hi.y;
-}
-
-__device__ __forceinline__ float sqdist_row_lds_half(const uint2 *__restrict__ y2, const float *xs, int d)
-{
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    int i = 0;
-    for (; d - i >= 16; i += 16) {
-        float yv[16];
-        widen4(y2[(i >> 2)], yv);
-        widen4(y2[(i >> 2) + 1], yv + 4);
-        widen4(y2[(i >> 2) + 2], yv + 8);
-        widen4(y2[(i >> 2) + 3], yv + 12);
-        float df[16];
-#pragma unroll
-        for (int t = 0; t < 16; t++) df[t] = yv[t] - xs[i + t];
-#pragma unroll
-        for (int l = 0; l < 4; l++) {
-            float ab3 = df[12 + l] * df[12 + l] + acc[l];
-            float ab2 = df[8 + l] * df[8 + l] + ab3;
-            float ab1 = df[4 + l] * df[4 + l] + ab2;
-            acc[l] = df[l] * df[l] + ab1;
-        }
-    }
-    for (; i < d; i += 4) {          // d % 4 == 0: whole vectors only
-        float yv[4];
-        widen4(y2[i >> 2], yv);
-#pragma unroll
-        for (int l = 0; l < 4; l++) {
-            const float df = yv[l] - xs[i + l];
-            acc[l] = df * df + acc[l];
-        }
-    }
-    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
-}
-
-// LDS: cand[R] (int64) | dist[R] | x[d] | tile[TILE + 1 spare][stride8] (8-byte pieces)
-// DIST, the pair arguments and the descriptors' hook as rescore_staged_body (the final stage passes no slots).
-template <int TILE, bool DIST>
-__device__ __forceinline__ void rescore_staged_half_body(unsigned char *smem, const float *__restrict__ q, int d,
-                                                         const _Float16 *__restrict__ rows, int64_t n_rows,
-                                                         const int64_t *__restrict__ cand, int R, int k, int strip,
-                                                         int64_t *__restrict__ out, int *__restrict__ out_count,
-                                                         int stride8, const float *__restrict__ q_b, int64_t q_na,
-                                                         int64_t *__restrict__ out_b, int64_t out_na,
-                                                         const TkSlotsOut *__restrict__ so_dev,
-                                                         float *__restrict__ out_d, float *__restrict__ out_d_b)
-{
-    const bool have_slots = so_dev != nullptr;
-    int64_t *cs = (int64_t *)smem;
-    float *ds = (float *)(smem + (((size_t)R * 8 + 15) & ~(size_t)15));
-    float *xs = ds + ((R + 3) & ~3);
-    uint2 *tile = (uint2 *)(xs + ((d + 3) & ~3));        // 16-byte aligned
-    const int tid = threadIdx.x;
-    const int64_t qi = blockIdx.x;
-    const int64_t *c = cand + qi * R;
-    const float *qrow = (q_b && qi >= q_na) ? q_b + (qi - q_na) * d : q + qi * d;   // second call of a pair
-    for (int t = tid; t < d; t += 64) xs[t] = qrow[t];
-    // ordered compaction of the candidate ids (ivf.py:154-155 drops -1)
-    int nc = 0;
-    for (int t0 = 0; t0 < R; t0 += 64) {
-        const int t = t0 + tid;
-        const int64_t id = t < R ? c[t] : -1;
-        const bool keep = t < R && (!strip || id != -1);
-        const uint64_t m = __builtin_amdgcn_ballot_w64(keep);
-        const int before = __builtin_popcountll(m & ((1ull << tid) - 1ull));
-        if (keep) cs[nc + before] = id;
-        nc += __builtin_popcountll(m);
-    }
-    __syncthreads();
-    const bool second = out_b && qi >= out_na;
-    int64_t *o = second ? out_b + (qi - out_na) * k : out + qi * k;
-    float *od = nullptr;
-    if (DIST) od = second ? (out_d_b ? out_d_b + (qi - out_na) * k : nullptr) : (out_d ? out_d + qi * k : nullptr);
-    if (nc <= k) {  // ivf.py:158-159 / fast_pq.py:307-308: heap order, no rescoring
-        for (int t = tid; t < k; t += 64) o[t] = t < nc ? cs[t] : -1;
-        if (tid == 0 && out_count) out_count[qi] = nc;
-        if (DIST && od)
-            for (int t = tid; t < k; t += 64) {
-                float dv = __builtin_huge_valf();
-                if (t < nc) {
-                    int64_t id = cs[t];
-                    if (id < 0) id += n_rows;
-                    dv = sqdist_row<float, _Float16>(rows + id * (int64_t)d, xs, d);
-                }
-                od[t] = dv;
-            }
-        if (have_slots) slots_epilogue(*so_dev, qi, k, tid, tid < nc ? cs[tid < k ? tid : 0] : -1);
-        return;
-    }
-    const int d4 = d >> 2;                   // 8-byte pieces per row
-    const int lpr_log = d4 <= 16 ? 4 : (d4 <= 32 ? 5 : 6);
-    const int rr = tid >> lpr_log, pc = tid & ((1 << lpr_log) - 1), rpi = 64 >> lpr_log;
-    for (int t0 = 0; t0 < nc; t0 += TILE) {
-        const int nt = nc - t0 < TILE ? nc - t0 : TILE;
-        if (pc < d4)
-            for (int r0 = rr; r0 < nt; r0 += 16 * rpi) {
-                // sixteen loads in flight per lane before the first LDS store waits for one
-                uint2 v[16];
-#pragma unroll
-                for (int u = 0; u < 16; u++) {
-                    const int r = r0 + u * rpi;
-                    int64_t id = cs[t0 + (r < nt ? r : nt - 1)];
-                    if (id < 0) id += n_rows;  // numpy fancy indexing with a negative index
-                    v[u] = ((const uint2 *)(rows + id * (int64_t)d))[pc];
-                }
-                // unconditional stores (rows past the tile go to the spare row), as in the float32 kernel
-#pragma unroll
-                for (int u = 0; u < 16; u++) {
-                    const int r = r0 + u * rpi;
-                    tile[(r < nt ? r : TILE) * stride8 + pc] = v[u];
-                }
-            }
-        __syncthreads();
-        if (tid < nt) ds[t0 + tid] = sqdist_row_lds_half(tile + tid * stride8, xs, d);
-        __syncthreads();
-    }
-    int64_t *ps = (int64_t *)(tile + (((TILE + 1) * stride8 + 1) & ~1));     // have_slots: the k results in order
-    for (int t = tid; t < nc; t += 64) {
-        const float dv = ds[t];
-        int rank = 0;
-        for (int u = 0; u < nc; u++) {
-            const float du = ds[u];
-            rank += (du < dv) || (du == dv && u < t);
-        }
-        if (rank < k) {
-            o[rank] = cs[t];
-            if (DIST && od) od[rank] = dv;
-            if (have_slots) ps[rank] = cs[t];
-        }
-    }
-    if (tid == 0 && out_count) out_count[qi] = k;
-    if (have_slots) {
-        __syncthreads();
-        slots_epilogue(*so_dev, qi, k, tid, tid < k ? ps[tid] : -1);
-    }
+    rescore_staged_body<float, TILE, true>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride4, q_b,
+                                           q_na, out_b, out_na, nullptr, out_d, out_d_b);
 }
 
 template <int TILE>
@@ -576,8 +454,8 @@ __global__ __launch_bounds__(64) void rescore_staged_half_kernel(const float *__
                                                                  const TkSlotsOut *__restrict__ so_dev)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    rescore_staged_half_body<TILE, false>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride8, q_b,
-                                          q_na, out_b, out_na, so_dev, nullptr, nullptr);
+    rescore_staged_body<_Float16, TILE, false>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride8,
+                                               q_b, q_na, out_b, out_na, so_dev, nullptr, nullptr);
 }
 
 template <int TILE>
@@ -593,13 +471,12 @@ __global__ __launch_bounds__(64) void rescore_staged_half_distances_kernel(const
                                                                       float *__restrict__ out_d_b)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    rescore_staged_half_body<TILE, true>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride8, q_b,
-                                         q_na, out_b, out_na, nullptr, out_d, out_d_b);
+    rescore_staged_body<_Float16, TILE, true>(smem, q, d, rows, n_rows, cand, R, k, strip, out, out_count, stride8,
+                                              q_b, q_na, out_b, out_na, nullptr, out_d, out_d_b);
 }
 
 // the lane-per-row kernel's distance-writing form on half rows: rescore_body<float, _Float16, float, true>, as
-// rescore_dist_kernel<float, _Float16, float> would be (the distance forms of the half kernels carry "distances"
-// in their names: the resource test of the float32 / float64 ones counts the names that hold "dist_kernel")
+// rescore_dist_kernel<float, _Float16, float> would be
 __global__ __launch_bounds__(128) void rescore_half_distances_kernel(const float *__restrict__ q, int d,
                                                                      const _Float16 *__restrict__ rows, int64_t n_rows,
                                                                      const int64_t *__restrict__ cand, int R, int k,
@@ -615,59 +492,103 @@ __global__ __launch_bounds__(128) void rescore_half_distances_kernel(const float
                                                out_b, out_na, out_d, out_d_b);
 }
 
-// half vectors (float32 queries): the staged kernels where they apply (as for float32: d % 4 == 0, d <= 256,
-// R <= 256, form 1 / 2), else the lane-per-row kernels on _Float16 rows
-static int launch_rescore_half(const float *q, int d, const _Float16 *rows, int64_t n_rows, const int64_t *cand, int R,
-                               int64_t nq, int k, int strip, int64_t *out, int *out_count, hipStream_t s, int form,
-                               TkSecond q2, TkSecond out2, const TkSlotsOut *slots, float *dist, float *dist_b,
-                               bool want_d)
+// ---- host side -------------------------------------------------------------------------------------------------
+// One call as tk_launch_rescore received it; a launcher casts the pointers to the types it was chosen for.
+struct RescoreCall {
+    const void *q, *rows;
+    int d, R, k, strip;
+    int64_t n_rows, nq;
+    const int64_t *cand;
+    int64_t *out;
+    int *out_count;
+    hipStream_t s;
+    TkSecond q2, out2;
+    void *dist, *dist_b;    // want_d: where the distances go (either may be null)
+    bool want_d;
+};
+
+// the kernels by row type
+template <int TILE> static auto staged_ids_kernel(const float *) { return rescore_staged_kernel<TILE>; }
+template <int TILE> static auto staged_ids_kernel(const _Float16 *) { return rescore_staged_half_kernel<TILE>; }
+template <int TILE> static auto staged_dist_kernel(const float *) { return rescore_staged_dist_kernel<TILE>; }
+template <int TILE> static auto staged_dist_kernel(const _Float16 *) { return rescore_staged_half_distances_kernel<TILE>; }
+
+template <typename T, typename TY, typename TX> static auto rows_dist_kernel()
 {
-    dim3 grid((unsigned)nq), block(R <= 64 ? 64 : 128);
+    if constexpr (std::is_same<TY, _Float16>::value) return rescore_half_distances_kernel;
+    else return rescore_dist_kernel<T, TY, TX>;
+}
+
+// every lane walks its own row: sums in T, rows TY, queries TX
+template <typename T, typename TY, typename TX>
+static void launch_rows(const RescoreCall &c)
+{
+    // one wave is enough for the coarse stage's 2 * n_probes + 10 candidates: the second wave of
+    // a 128-thread workgroup only waited at the barriers and took a wave slot beside the scan
+    const dim3 grid((unsigned)c.nq), block(c.R <= 64 ? 64 : 128);
+    const size_t lds = (size_t)c.R * 8 + ((size_t)c.R + c.d) * sizeof(T) + 16;
+    const TX *q = (const TX *)c.q, *q_b = (const TX *)c.q2.b;
+    const TY *rows = (const TY *)c.rows;
+    if (c.want_d)
+        hipLaunchKernelGGL((rows_dist_kernel<T, TY, TX>()), grid, block, lds, c.s, q, c.d, rows, c.n_rows, c.cand, c.R,
+                           c.k, c.strip, c.out, c.out_count, q_b, c.q2.n_a, (int64_t *)c.out2.b, c.out2.n_a,
+                           (T *)c.dist, (T *)c.dist_b);
+    else
+        hipLaunchKernelGGL((rescore_kernel<T, TY, TX>), grid, block, lds, c.s, q, c.d, rows, c.n_rows, c.cand, c.R,
+                           c.k, c.strip, c.out, c.out_count, q_b, c.q2.n_a, (int64_t *)c.out2.b, c.out2.n_a);
+}
+
+template <typename TY, int TILE>
+static void launch_staged_tile(const RescoreCall &c, size_t lds, int stride, const TkSlotsOut *so)
+{
+    const dim3 grid((unsigned)c.nq), block(64);
+    const float *q = (const float *)c.q, *q_b = (const float *)c.q2.b;
+    const TY *rows = (const TY *)c.rows;
+    if (c.want_d)
+        hipLaunchKernelGGL(staged_dist_kernel<TILE>(rows), grid, block, lds, c.s, q, c.d, rows, c.n_rows, c.cand, c.R,
+                           c.k, c.strip, c.out, c.out_count, stride, q_b, c.q2.n_a, (int64_t *)c.out2.b, c.out2.n_a,
+                           (float *)c.dist, (float *)c.dist_b);
+    else
+        hipLaunchKernelGGL(staged_ids_kernel<TILE>(rows), grid, block, lds, c.s, q, c.d, rows, c.n_rows, c.cand, c.R,
+                           c.k, c.strip, c.out, c.out_count, stride, q_b, c.q2.n_a, (int64_t *)c.out2.b, c.out2.n_a,
+                           so);
+}
+
+// float32 sums on rows TY (float32 queries): returns 1 when the descriptors were written too, else 0.
+// Rows staged through LDS in tiles of 32 (form 2, DEFAULT) / 64 (form 1) rows, or every lane
+// walking its own row (form 0); tk_index_set_option(TK_OPT_RESCORE_FORM).  Round 2
+// (profiles/r02_scan_grid.md): the 32-row form was the fastest alone (0.118 ms per 10 000
+// queries against 0.135) but lost in the pipeline — its workgroups (15-29 KB of LDS) were
+// placed late next to the exact scan's persistent grid: 0.68-0.70 ms per batch against 0.656.
+// Round 3, next to the plain kernel (two 58 KB workgroups per CU leave 44 KB): 0.495 ms per
+// batch against 0.543 (profiles/r03/ab_pipeline_knobs.txt) — the 64 lines a wave touches per
+// load in mode 0 were costing the scans beside it more than its own time.
+template <typename TY>
+static int launch_float_sums(const RescoreCall &c, int form, const TkSlotsOut *slots)
+{
     const int staged = form < 0 || form > 2 ? 2 : form;
-    if (staged && d % 4 == 0 && d <= 256 && R <= 256) {
-        const int stride8 = (d / 4) | 1;                      // odd number of 8-byte pieces
+    // (heaps beyond 256 entries: a 64-lane workgroup walks 16+ tiles one after the other — n_probes 50,
+    //  R = 511: 3.18 M queries/s staged against 3.85 M with the 128-lane lane-per-row kernel)
+    if (staged && c.d % 4 == 0 && c.d <= 256 && c.R <= 256) {
+        const int stride = (c.d / 4) | 1;                       // odd number of pieces
         const int tile_rows = staged == 2 ? 32 : 64;
-        const bool fuse = slots != nullptr && k <= 64;
-        const TkSlotsOut *so = fuse ? slots : nullptr;
-        const size_t slds = (((size_t)R * 8 + 15) & ~(size_t)15) +
-                            (size_t)(((R + 3) & ~3) + ((d + 3) & ~3)) * 4 +
-                            (size_t)(((tile_rows + 1) * stride8 + 1) & ~1) * 8 + (fuse ? (size_t)k * 8 : 0);
-        if (slds <= 64 * 1024) {
-            if (want_d) {
-                if (tile_rows == 32)
-                    hipLaunchKernelGGL(rescore_staged_half_distances_kernel<32>, grid, dim3(64), slds, s, q, d, rows, n_rows,
-                                       cand, R, k, strip, out, out_count, stride8, (const float *)q2.b, q2.n_a,
-                                       (int64_t *)out2.b, out2.n_a, dist, dist_b);
-                else
-                    hipLaunchKernelGGL(rescore_staged_half_distances_kernel<64>, grid, dim3(64), slds, s, q, d, rows, n_rows,
-                                       cand, R, k, strip, out, out_count, stride8, (const float *)q2.b, q2.n_a,
-                                       (int64_t *)out2.b, out2.n_a, dist, dist_b);
-                return 0;
-            }
-            if (tile_rows == 32)
-                hipLaunchKernelGGL(rescore_staged_half_kernel<32>, grid, dim3(64), slds, s, q, d, rows, n_rows, cand, R,
-                                   k, strip, out, out_count, stride8, (const float *)q2.b, q2.n_a, (int64_t *)out2.b,
-                                   out2.n_a, so);
-            else
-                hipLaunchKernelGGL(rescore_staged_half_kernel<64>, grid, dim3(64), slds, s, q, d, rows, n_rows, cand, R,
-                                   k, strip, out, out_count, stride8, (const float *)q2.b, q2.n_a, (int64_t *)out2.b,
-                                   out2.n_a, so);
+        const bool fuse = slots != nullptr && c.k <= 64;        // (slots: a DEVICE copy of the structure)
+        const size_t tile_bytes = (size_t)(tile_rows + 1) * stride * sizeof(typename RowPiece<TY>::type);
+        const size_t lds = (((size_t)c.R * 8 + 15) & ~(size_t)15) +
+                           (size_t)(((c.R + 3) & ~3) + ((c.d + 3) & ~3)) * 4 + ((tile_bytes + 15) & ~(size_t)15) +
+                           (fuse ? (size_t)c.k * 8 : 0);
+        if (lds <= 64 * 1024) {
+            if (tile_rows == 32) launch_staged_tile<TY, 32>(c, lds, stride, fuse ? slots : nullptr);
+            else launch_staged_tile<TY, 64>(c, lds, stride, fuse ? slots : nullptr);
             return fuse ? 1 : 0;
         }
     }
-    const size_t lds = (size_t)R * 8 + ((size_t)R + d) * 4 + 16;
-    if (want_d)
-        hipLaunchKernelGGL(rescore_half_distances_kernel, grid, block, lds, s, q, d, rows, n_rows, cand, R, k, strip,
-                           out, out_count, (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, dist, dist_b);
-    else
-        hipLaunchKernelGGL((rescore_kernel<float, _Float16, float>), grid, block, lds, s, q, d, rows, n_rows, cand, R,
-                           k, strip, out, out_count, (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a);
+    launch_rows<float, TY, float>(c);
     return 0;
 }
 
 // rows_dtype: TK_DATA_F32 / TK_DATA_F64 / TK_DATA_F16 (the coarse stage and tk_bottom_k pass 0 / 1)
 int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int rows_dtype,
-
                       int64_t n_rows, const int64_t *cand, int R, int64_t nq, int k, int strip,
                       int64_t *out, int *out_count, hipStream_t s, int form, TkSecond q2, TkSecond out2,
                       const TkSlotsOut *slots, void *dist, TkSecond dist2)
@@ -676,98 +597,15 @@ int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int 
     const bool want_d = dist != nullptr || dist2.b != nullptr;
     if (want_d) slots = nullptr;                // (the descriptors' caller asks for no distances)
     void *dist_b = out2.b ? const_cast<void *>(dist2.b) : nullptr;     // (rows of the second call: out2.n_a on)
-    if (rows_dtype == 2) {                      // half vectors: float32 queries only (the index's final stage)
-        if (q_is_f64) return -1;
-        return launch_rescore_half((const float *)q, d, (const _Float16 *)rows, n_rows, cand, R, nq, k, strip, out,
-                                   out_count, s, form, q2, out2, slots, (float *)dist, (float *)dist_b, want_d);
-    }
+    const RescoreCall c = {q, rows, d, R, k, strip, n_rows, nq, cand, out, out_count, s, q2, out2, dist, dist_b, want_d};
+    if (rows_dtype == 2)                        // half vectors: float32 queries only (the index's final stage)
+        return q_is_f64 ? -1 : launch_float_sums<_Float16>(c, form, slots);
     const int rows_is_f64 = rows_dtype == 1;
-    const bool dbl = q_is_f64 || rows_is_f64;   // numpy promotes `Y - x` to float64
-    size_t lds = (size_t)R * 8 + ((size_t)R + d) * (dbl ? 8 : 4) + 16;
-    // one wave is enough for the coarse stage's 2 * n_probes + 10 candidates: the second wave of
-    // a 128-thread workgroup only waited at the barriers and took a wave slot beside the scan
-    dim3 grid((unsigned)nq), block(R <= 64 ? 64 : 128);
-    // Rows staged through LDS in tiles of 32 (form 2, DEFAULT) / 64 (form 1) rows, or every lane
-    // walking its own row (form 0); tk_index_set_option(TK_OPT_RESCORE_FORM).  Round 2
-    // (profiles/r02_scan_grid.md): the 32-row form was the fastest alone (0.118 ms per 10 000
-    // queries against 0.135) but lost in the pipeline — its workgroups (15-29 KB of LDS) were
-    // placed late next to the exact scan's persistent grid: 0.68-0.70 ms per batch against 0.656.
-    // Round 3, next to the plain kernel (two 58 KB workgroups per CU leave 44 KB): 0.495 ms per
-    // batch against 0.543 (profiles/r03/ab_pipeline_knobs.txt) — the 64 lines a wave touches per
-    // load in mode 0 were costing the scans beside it more than its own time.
-    const int staged = form < 0 || form > 2 ? 2 : form;
-    // (heaps beyond 256 entries: a 64-lane workgroup walks 16+ tiles one after the other — n_probes 50,
-    //  R = 511: 3.18 M queries/s staged against 3.85 M with the 128-lane lane-per-row kernel)
-    if (!dbl && staged && d % 4 == 0 && d <= 256 && R <= 256 ) {
-        const int stride4 = (d / 4) | 1;                      // odd number of 16-byte pieces
-        const int tile_rows = staged == 2 ? 32 : 64;
-        const bool fuse = slots != nullptr && k <= 64;
-        const TkSlotsOut *so = fuse ? slots : nullptr;      // (a DEVICE copy of the structure)
-        const size_t slds = (((size_t)R * 8 + 15) & ~(size_t)15) +
-                            (size_t)(((R + 3) & ~3) + ((d + 3) & ~3)) * 4 + (size_t)(tile_rows + 1) * stride4 * 16 +
-                            (fuse ? (size_t)k * 8 : 0);
-        if (slds <= 64 * 1024) {
-            if (want_d) {
-                if (tile_rows == 32)
-                    hipLaunchKernelGGL(rescore_staged_dist_kernel<32>, grid, dim3(64), slds, s, (const float *)q, d,
-                                       (const float *)rows, n_rows, cand, R, k, strip, out, out_count, stride4,
-                                       (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, (float *)dist,
-                                       (float *)dist_b);
-                else
-                    hipLaunchKernelGGL(rescore_staged_dist_kernel<64>, grid, dim3(64), slds, s, (const float *)q, d,
-                                       (const float *)rows, n_rows, cand, R, k, strip, out, out_count, stride4,
-                                       (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, (float *)dist,
-                                       (float *)dist_b);
-                return 0;
-            }
-            if (tile_rows == 32)
-                hipLaunchKernelGGL(rescore_staged_kernel<32>, grid, dim3(64), slds, s, (const float *)q, d,
-                                   (const float *)rows, n_rows, cand, R, k, strip, out, out_count, stride4,
-                                   (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, so);
-            else
-                hipLaunchKernelGGL(rescore_staged_kernel<64>, grid, dim3(64), slds, s, (const float *)q, d,
-                                   (const float *)rows, n_rows, cand, R, k, strip, out, out_count, stride4,
-                                   (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, so);
-            return fuse ? 1 : 0;
-        }
-    }
-    if (want_d) {
-        if (!dbl)
-            hipLaunchKernelGGL((rescore_dist_kernel<float, float, float>), grid, block, lds, s, (const float *)q, d,
-                               (const float *)rows, n_rows, cand, R, k, strip, out, out_count, (const float *)q2.b,
-                               q2.n_a, (int64_t *)out2.b, out2.n_a, (float *)dist, (float *)dist_b);
-        else if (rows_is_f64 && q_is_f64)
-            hipLaunchKernelGGL((rescore_dist_kernel<double, double, double>), grid, block, lds, s, (const double *)q,
-                               d, (const double *)rows, n_rows, cand, R, k, strip, out, out_count,
-                               (const double *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, (double *)dist,
-                               (double *)dist_b);
-        else if (rows_is_f64)
-            hipLaunchKernelGGL((rescore_dist_kernel<double, double, float>), grid, block, lds, s, (const float *)q, d,
-                               (const double *)rows, n_rows, cand, R, k, strip, out, out_count, (const float *)q2.b,
-                               q2.n_a, (int64_t *)out2.b, out2.n_a, (double *)dist, (double *)dist_b);
-        else
-            hipLaunchKernelGGL((rescore_dist_kernel<double, float, double>), grid, block, lds, s, (const double *)q,
-                               d, (const float *)rows, n_rows, cand, R, k, strip, out, out_count,
-                               (const double *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a, (double *)dist,
-                               (double *)dist_b);
-        return 0;
-    }
-    if (!dbl)
-        hipLaunchKernelGGL((rescore_kernel<float, float, float>), grid, block, lds, s,
-                           (const float *)q, d, (const float *)rows, n_rows, cand, R, k, strip, out,
-                           out_count, (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a);
-    else if (rows_is_f64 && q_is_f64)
-        hipLaunchKernelGGL((rescore_kernel<double, double, double>), grid, block, lds, s,
-                           (const double *)q, d, (const double *)rows, n_rows, cand, R, k, strip,
-                           out, out_count, (const double *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a);
-    else if (rows_is_f64)
-        hipLaunchKernelGGL((rescore_kernel<double, double, float>), grid, block, lds, s,
-                           (const float *)q, d, (const double *)rows, n_rows, cand, R, k, strip, out,
-                           out_count, (const float *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a);
-    else
-        hipLaunchKernelGGL((rescore_kernel<double, float, double>), grid, block, lds, s,
-                           (const double *)q, d, (const float *)rows, n_rows, cand, R, k, strip, out,
-                           out_count, (const double *)q2.b, q2.n_a, (int64_t *)out2.b, out2.n_a);
+    if (!q_is_f64 && !rows_is_f64) return launch_float_sums<float>(c, form, slots);
+    // numpy promotes `Y - x` to float64
+    if (rows_is_f64 && q_is_f64) launch_rows<double, double, double>(c);
+    else if (rows_is_f64) launch_rows<double, double, float>(c);
+    else launch_rows<double, float, double>(c);
     return 0;
 }
 
