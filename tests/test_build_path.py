@@ -4,6 +4,7 @@ reference produced (golden IVF fixtures) and (b) numpy itself on the shapes the 
 import numpy as np
 import pytest
 
+import build_shapes as B
 from conftest import G6_TAGS, golden, split_lists
 
 
@@ -111,3 +112,54 @@ def test_assign_vs_numpy(oracle, metric, y64, k):
         part = np.einsum("ij,ij->i", xc, xc)[:, None] + yn[None] - 2 * xc @ Yn.T
         want[i:i + 100] = np.argpartition(part, k, axis=1)[:, :k]
     np.testing.assert_array_equal(oracle.assign(X, Y, k, metric), want)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The shape table of build_shapes.py: the oracle equals numpy at every width, centre count and k the device is
+# compared with the oracle at (tests/test_build_gpu.py), so that device == oracle there means device == numpy.
+#
+# d = 1 and d = 2 are left out of the numpy comparison: at d = 1 angular every normalised value is +-1, every
+# distance ties, and about half the rows differ (which of the tied centres numpy's argselect returns is its own
+# affair); at d = 1 and d = 2 euclidean random float32 rows still produced an exact tie in isolated rows.  From
+# d = 3 on, random rows are tie-free and the oracle's answer is numpy's in every row.
+_NUMPY_ASSIGN = [(c, i) for c, i in zip(B.ASSIGN_CASES, B.ASSIGN_IDS) if c.ties is None and c.d >= 3]
+
+
+@pytest.mark.parametrize("case", [c for c, _ in _NUMPY_ASSIGN], ids=[i for _, i in _NUMPY_ASSIGN])
+def test_assign_table_vs_numpy(oracle, case):
+    """Whole 100-row chunks (knn_brute's own, utils.py:81-85), tie-free random rows: equal in every row."""
+    from tinyknn_amd.utils import knn_brute
+    X, Y = B.assign_inputs(case, whole_chunks=True)
+    assert len(X) % 100 == 0
+    metric = B.oracle_metric(case)
+    np.testing.assert_array_equal(oracle.assign(X, Y, case.k, metric), knn_brute(X, Y, k=case.k, metric=metric))
+
+
+def _labels_same_up_to_exact_ties(centers, dpb, X, la, lb):
+    """tests/test_build_gpu.py's _same_up_to_exact_ties on labels: the cap is a condition, not a tolerance — every
+    differing label must be an exact tie of the minimum in numpy's own `part`."""
+    bad = np.argwhere(la != lb)
+    assert len(bad) <= 1e-5 * la.size + 2
+    for i, m in bad:
+        lo = i - i % 100                                  # the chunk numpy scored the row in
+        xc = X[lo:lo + 100, m * dpb:(m + 1) * dpb]
+        code = centers[:, m * dpb:(m + 1) * dpb]
+        part = (np.einsum("ij,ij->i", xc, xc)[:, None] + np.einsum("ij,ij->i", code, code)[None]
+                - 2 * xc @ code.T)[i - lo]
+        assert part[la[i, m]] == part[lb[i, m]] == part.min()
+
+
+_NUMPY_ENCODE = [(c, i) for c, i in zip(B.ENCODE_CASES, B.ENCODE_IDS) if not c.ties]
+
+
+@pytest.mark.parametrize("case", [c for c, _ in _NUMPY_ENCODE], ids=[i for _, i in _NUMPY_ENCODE])
+def test_encode_table_vs_numpy(oracle, case):
+    """oracle.encode_pq == FastPQ.encode_labels on the host (knn_brute per block, fast_pq.py:174-181) on the
+    random cases of the table; the tie cases have no numpy answer to compare with (its AVX-512 argselect need
+    not return the first of tied entries)."""
+    from tinyknn_amd import FastPQ
+    centers, X = B.encode_inputs(case)
+    pq = FastPQ(case.dpb)
+    pq.centers = centers
+    want = pq.encode_labels(X, device=False)
+    _labels_same_up_to_exact_ties(centers, case.dpb, X, oracle.encode_pq(centers, case.dpb, X), want)
