@@ -251,6 +251,8 @@ int tk_index_join(tk_index *ix, void *stream);
  * every call its own batch.  ivf.py:106-163 answers one query per call; the batch forms here and
  * everything about their scheduling are this library's. */
 int tk_index_set_coalesce(tk_index *ix, int n);
+/* what tk_index_set_coalesce was last given (1 or 2); the pipeline depth is info8[5] of tk_index_info */
+int tk_index_coalesce(tk_index *ix);
 /* hipGraph of the pipelined mode: tk_index_quiesce (device-synchronising; forgets the completion
  * events of earlier calls), then capture on a non-NULL stream any number of
  * tk_index_query_batch_dev calls followed by tk_index_join on that stream.  The internal streams
@@ -593,6 +595,48 @@ int tk_index_query_batch_dev_dist(tk_index *ix, const tk_allow *allow, const flo
                                   const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k, int n_probes,
                                   int pass_1, int64_t *out_ids_dev, void *out_dist_dev, void *done_event,
                                   void *stream);
+/* One excluded row per query, and stored rows as queries (k-NN graphs, de-duplication, "more like this row").
+ * exclude[i] = e: query i returns what IVF.query (ivf.py:106-163) returns when `insert` in query_pq runs only
+ * for labels != e — the allowed set "every row but e", with everything else the reference's as for allowed sets
+ * above; bit for bit that guarded reference.  e = -1: nothing excluded for that query.  On the device every stored
+ * copy of e in a probed list takes the heap's empty value in the query's distance row, where the allowed set's
+ * pass runs (behind the list scans and every exact re-scan, in front of every replay; never on the coarse stage).
+ * The copies are found in a row-position table: 4 (N + 2) + 4 T bytes for N rows and T stored entries (plus
+ * the allocator's eighth of slack: 0.8 GB at 100M rows stored once, 1.2 GB stored twice), made from the
+ * device-resident labels by the first call that passes an exclude array, once per layout of the lists (again after
+ * tk_index_set_lists, _add_rows, _remove_rows; that call synchronises the device, so make it outside a stream
+ * capture), freed with the index.  Calls without an array never make it.  T and N must be below 2^31.
+ * tk_index_query_batch_ex2 / _dev_ex2: tk_index_query_batch / _dev_ex with everything at once; allow, exclude,
+ * out_dist and the debug outputs may each be NULL.  The host call checks exclude (an entry outside [-1, N):
+ * TK_ERR_ARG, nothing run) and passes an array of only -1 on as none.  The device call does not read exclude_dev
+ * on the host: an entry outside [0, N) there excludes nothing.  exclude_dev (int64, nq entries) belongs to the
+ * library until done_event or tk_index_join, like the other buffers.  Not for list-sharded indexes.
+ * Sub-batches, the pipelined mode and pairs of calls as the _dist call; ANY two calls that could pair without an
+ * exclude array still pair with one, on either side (each half reads its own array or none).  An excluding call
+ * takes the scan an unrestricted call takes (the automatic plain-scan state counts its verdicts).
+ * tk_index_gather_queries_dev: qn_dev[i] = float32(data[rows_dev[i]]) — a copy of float32 vectors, half
+ * vectors widened, float64 vectors rounded to nearest even — NOT normalised again, and q_pq_dev as
+ * tk_index_prepare_dev makes it from qn_dev (padded; rotated with the device's float64 FMA chain where a rotation
+ * is set: float64 iff rotated).  rows_dev: int64 entries in [0, N), the caller's promise.  Enqueued on `stream`.
+ * tk_index_gather_queries: the same with host buffers (rows checked), for inspection and tests.
+ * tk_index_query_rows: rows on the host in (checked: outside [0, N) is TK_ERR_ARG), gather + _ex2 in library
+ * buffers; exclude_self != 0: exclude = rows.  A row that was removed is still a vector: nothing is masked for it.
+ * tk_index_row_table: info4 = {table exists for the current lists, its bytes, times one was made, its entries}. */
+int tk_index_query_batch_ex2(tk_index *ix, const tk_allow *allow, const int64_t *exclude, const float *q,
+                             const void *q_pq, int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                             int64_t *out_ids, void *out_dist, int64_t *out_probes, int64_t *out_heap_idx,
+                             int32_t *out_heap_val);
+int tk_index_query_batch_dev_ex2(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
+                                 const float *q_dev, const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k,
+                                 int n_probes, int pass_1, int64_t *out_ids_dev, void *out_dist_dev,
+                                 void *done_event, void *stream);
+int tk_index_gather_queries_dev(tk_index *ix, const int64_t *rows_dev, int64_t nq, float *qn_dev,
+                                void *q_pq_dev, void *stream);
+int tk_index_gather_queries(tk_index *ix, const int64_t *rows, int64_t nq, float *qn, void *q_pq);
+int tk_index_query_rows(tk_index *ix, const tk_allow *allow, const int64_t *rows, int64_t nq, int exclude_self,
+                        int k, int n_probes, int pass_1, int64_t *out_ids, void *out_dist, int64_t *out_probes,
+                        int64_t *out_heap_idx, int32_t *out_heap_val);
+int tk_index_row_table(tk_index *ix, int64_t *info4);
 /* hipStream_t on which to copy a batch's inputs in (pipelined mode: the index's front stream,
  * where the batch's first kernel runs; NULL: use the stream the batch is enqueued on) */
 void *tk_index_input_stream(tk_index *ix);

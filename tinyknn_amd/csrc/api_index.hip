@@ -19,6 +19,7 @@ struct Pending {
         bool host_out_kernel;       // ... written by copy_words_kernel instead of the copy engine
         hipEvent_t user_ev;         // recorded behind that copy (or NULL)
         void *dist_dev = nullptr;   // the rescoring's distances beside out_dev (or NULL: ids only)
+        const int64_t *exclude = nullptr;   // one row per query that the query may not return (or NULL), rows.hip
     } subs[2];
     int n_subs = 1;
     Work *w;
@@ -51,13 +52,15 @@ struct Pending {
         TkSecond q2, qpq2, out2;
         void *dist;                 // each call's distances (or NULL), as its ids
         TkSecond dist2;
+        const int64_t *exclude;     // each call's excluded rows (or NULL)
+        TkSecond exclude2;
     };
     Rows rows() const
     {
         const Sub &a = subs[0], &b = subs[1];
-        if (n_subs == 1) return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq, {}, {}, {}, a.dist_dev, {}};
+        if (n_subs == 1) return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq, {}, {}, {}, a.dist_dev, {}, a.exclude, {}};
         return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq + b.nq, {b.q_dev, a.nq}, {b.qpq_dev, a.nq}, {b.out_dev, a.nq},
-                    a.dist_dev, {b.dist_dev, a.nq}};
+                    a.dist_dev, {b.dist_dev, a.nq}, a.exclude, {b.exclude, a.nq}};
     }
 };
 
@@ -87,7 +90,7 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->cslots_l, &ix->c_chunk_off, &ix->q, &ix->qpq, &ix->stage, &ix->owner,
                       &ix->local_chunk_off, &ix->rot_t, &ix->br_ynorm, &ix->br_vals, &ix->br_tau,
                       &ix->br_cand, &ix->br_count, &ix->br_out, &ix->br_q, &ix->br_sample, &ix->replay_counters,
-                      &ix->twin_list, &ix->twin_off};
+                      &ix->twin_list, &ix->twin_off, &ix->row_pos_off, &ix->row_pos};
     for (DevBuf *b : bufs) b->release();
     for (Work &w : ix->works) w.release();
     // (the internal streams belong to the process: shared_streams below)
@@ -1018,11 +1021,24 @@ static void apply_allow(Work &w, int64_t q0, int64_t nq, const Plan &p, const tk
                              allow->bits.as<uint16_t>(), 1, only, st);
 }
 
+// One excluded row per query (rows.hip), where apply_allow runs and with its offsets; exclude / exclude2: the batch's
+// rows from row 0 (the pass adds q0).  exclude2.n_a > 0: a pair, whose second call's rows start there (exclude2.b NULL: they mask nothing)
+static void apply_exclude(const tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, const int64_t *exclude,
+                          TkSecond exclude2, hipStream_t st, const int *only = nullptr)
+{
+    if (!exclude && !exclude2.b) return;
+    TkRowPos tab;
+    tab.pos_off = ix->row_pos_off.as<int>(); tab.pos = ix->row_pos.as<int>(); tab.N = ix->N; tab.T = ix->total_ids;
+    tk_launch_exclude_pass(w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, nq,
+                           w.slot_prefix.as<int>() + q0 * (p.S + 1), w.slot_n.as<int>() + q0 * p.S,
+                           w.slot_loff.as<int64_t>() + q0 * p.S, p.S, tab, exclude, exclude2, q0, only, st);
+}
+
 // The queries the replay flagged (bound above the table's limit at the first plain block, plain_scan.hip): every probed
 // list again with the exact kernel.  list_built: the replay listed them itself (TkPlainCheck::flag_list); the count then
 // reaches the host through the replay behind the re-scan (replay_flagged_tail)
 static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, hipStream_t st,
-                           const tk_allow *allow, bool list_built = false)
+                           const tk_allow *allow, const int64_t *exclude, TkSecond exclude2, bool list_built = false)
 {
     int *list = w.flag_list.as<int>();
     if (!list_built) {
@@ -1034,6 +1050,7 @@ static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const 
                           p.S, (int)p.cap, w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, 1,
                           ix->order, st, list);
     apply_allow(w, q0, nq, p, allow, st, list);
+    apply_exclude(ix, w, q0, nq, p, exclude, exclude2, st, list);
 }
 
 // The tail behind a lane (or register-heap) replay that rode with the plain kernel: the queries it flagged — the lemma's
@@ -1092,7 +1109,8 @@ static Replay replay_form(const tk_index *ix, int64_t nq, const Plan &p)
 // rescoring.  q_dev: row 0 = query q0.
 int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
                const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain,
-               TkSecond q2, TkSecond out2, int *plain_flag, const tk_allow *allow, void *dist_dev, TkSecond dist2)
+               TkSecond q2, TkSecond out2, int *plain_flag, const tk_allow *allow, void *dist_dev, TkSecond dist2,
+               const int64_t *exclude, TkSecond exclude2)
 {
     const TkReplayJob j = list_replay_job(ix, w, q0, nq, p);
     unsigned char *flags = w.repeat_flag.as<unsigned char>() + q0;
@@ -1101,6 +1119,7 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     TkPlainCheck check;
     if (plain) check = {w.plain0.as<int>() + q0, w.qlim.as<int>() + q0, plain_flag ? nullptr : w.flag_list.as<int>()};
     apply_allow(w, q0, nq, p, allow, st);
+    apply_exclude(ix, w, q0, nq, p, exclude, exclude2, st);
     // heaps start fresh here, so packed entries apply.  Distinct labels: one query per
     // lane (or per wave for big heaps), and the few queries whose probe list wrapped a -1
     // (a list may then be scanned twice) re-run with the duplicate test.  Repeating labels
@@ -1173,13 +1192,13 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     const bool listed = form == Replay::Pair || form == Replay::Lanes || form == Replay::LanesTwin;
     const auto replay_wrapped = [&] { tk_launch_heap_replay_packed(j, flags, TK_RUN_WRAPPED, /*dedupe=*/true, st); };
     if (plain && form == Replay::LanesDedupe) {
-        rescan_flagged(ix, w, q0, nq, p, st, allow);
+        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2);
         replay_wrapped();
     } else if (plain && plain_flag && (listed || form == Replay::PackedDistinct)) {
         tk_launch_shard_flag_plain(flags, nq, plain_flag, st);
         replay_wrapped();
     } else if (plain && listed) {
-        rescan_flagged(ix, w, q0, nq, p, st, allow, true);
+        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2, true);
         replay_flagged_tail(ix, w, j, flags, st);
         plain_verdict_event(ix, w, nq, st);
     } else if (!plain && (form == Replay::Lanes || form == Replay::LanesTwin || form == Replay::PackedDistinct)) {
@@ -1281,7 +1300,7 @@ static int batch_back(tk_index *ix, Pending &b, hipStream_t st)
 {
     const Pending::Rows r = b.rows();
     TRY(stage_back(ix, *b.w, r.q, 0, r.nq, b.k, b.p, r.out, st, b.pf, b.plain, r.q2, r.out2, nullptr, b.allow, r.dist,
-                   r.dist2));
+                   r.dist2, r.exclude, r.exclude2));
     for (int i = 0; i < b.n_subs; i++) {
         const Pending::Sub &u = b.subs[i];
         if (u.host_out && u.host_out_kernel)
@@ -1599,7 +1618,8 @@ static int coalesce_call(tk_index *ix, Pending &b)
 static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_pq_dev,
                                 int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
                                 int64_t *out_ids_dev, int64_t *out_ids_pinned, hipEvent_t done_ev,
-                                void *stream, const tk_allow *allow = nullptr, void *out_dist_dev = nullptr)
+                                void *stream, const tk_allow *allow = nullptr, void *out_dist_dev = nullptr,
+                                const int64_t *exclude_dev = nullptr)
 {
     Plan p;
     TRY(make_plan(ix, k, n_probes, pass_1, p));
@@ -1618,6 +1638,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
                         cs != hipStreamCaptureStatusNone;
         (void)hipGetLastError();
     }
+    if (exclude_dev && nq > 0) TRY(row_pos_ensure(ix));     // (the first excluding call of a layout: rows.hip)
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     const int64_t ms = sub_batch(p);
     ARGCHECK(!(out_ids_pinned || done_ev) || (nq >= 1 && nq <= ms),
@@ -1628,7 +1649,8 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     //  profiles/r04/bench_full_first.json)
     if (ix->depth > 1 && ix->coalesce == 2 && (ix->ids_unique || twin_replay(ix, p)) && nq >= 1 && nq <= ms) {
         Pending b(ix, p, k, n_probes, pass_1, q_pq_is_f64, allow, caller,
-                  {q_dev, q_pq_dev, out_ids_dev, nq, out_ids_pinned, ix->host_out_kernel, done_ev, out_dist_dev});
+                  {q_dev, q_pq_dev, out_ids_dev, nq, out_ids_pinned, ix->host_out_kernel, done_ev, out_dist_dev,
+                   exclude_dev});
         return coalesce_call(ix, b);
     }
     TRY(launch_held(ix));
@@ -1642,7 +1664,8 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
         Pending b(ix, p, k, n_probes, pass_1, q_pq_is_f64, allow, caller,
                   {q_dev + o * ix->d, (const char *)q_pq_dev + (size_t)o * ix->dq * esz, out_ids_dev + o * k, sub,
                    out_ids_pinned, ix->host_out_kernel, done_ev,
-                   out_dist_dev ? (char *)out_dist_dev + (size_t)o * k * dsz : nullptr});
+                   out_dist_dev ? (char *)out_dist_dev + (size_t)o * k * dsz : nullptr,
+                   exclude_dev ? exclude_dev + o : nullptr});     // (a part's rows of the CALL's array)
         if (ix->depth == 1) {
             ix->calls++;
             TRY(run_batch_inline(ix, b));
@@ -1794,34 +1817,64 @@ extern "C" int tk_index_quiesce(tk_index *ix)
     return TK_OK;
 }
 
+// a call's own device buffers, freed however it leaves
+struct BufRelease {
+    std::vector<DevBuf *> bufs;
+    ~BufRelease()
+    {
+        for (DevBuf *b : bufs) b->release();
+    }
+};
+
 static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
                             int n_probes, int pass_1, int64_t *out_ids, int64_t *out_probes, int64_t *out_heap_idx,
-                            int32_t *out_heap_val, const tk_allow *allow, void *out_dist = nullptr)
+                            int32_t *out_heap_val, const tk_allow *allow, void *out_dist = nullptr,
+                            const int64_t *exclude = nullptr, const int64_t *rows = nullptr)
 {
     IXLOCK(ix);
     Plan p;
     TRY(make_plan(ix, k, n_probes, pass_1, p));
     ARGCHECK(nq >= 0, "nq");
     if (nq == 0) return TK_OK;
+    if (exclude || rows) ARGCHECK(!ix->sharded, "list-sharded index: excluded rows / stored rows as queries are not supported");
+    // rows: the queries are the stored rows named (tk_index_query_rows) — gathered below, q / q_pq unused
+    if (rows) {
+        ARGCHECK(ix->have_data, "set_data first");
+        for (int64_t i = 0; i < nq; i++) ARGCHECK(rows[i] >= 0 && rows[i] < ix->N, "row id out of range");
+    }
+    // exclude: validated here, and dropped where no entry excludes anything (no table, no pass)
+    bool excludes = false;
+    if (exclude)
+        for (int64_t i = 0; i < nq; i++) {
+            ARGCHECK(exclude[i] >= -1 && exclude[i] < ix->N, "exclude: entries must lie in [-1, N)");
+            excludes = excludes || exclude[i] >= 0;
+        }
+    if (!excludes) exclude = nullptr;
     ARGCHECK(!(out_probes || out_heap_idx || out_heap_val) || nq <= sub_batch(p),
              "debug outputs need the batch to fit one sub-batch");
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     TRY(ix->q.ensure((size_t)nq * ix->d * 4));
     TRY(ix->qpq.ensure((size_t)nq * ix->dq * esz));
-    DevBuf outbuf, distbuf;  // separate from the sub-batch `out` workspace
+    DevBuf outbuf, distbuf, exbuf, rowbuf;  // separate from the sub-batch `out` workspace
+    BufRelease rel{{&outbuf, &distbuf, &exbuf, &rowbuf}};
     const size_t dist_bytes = (size_t)nq * k * (ix->data_dtype == TK_DATA_F64 ? 8 : 4);
     TRY(outbuf.ensure((size_t)nq * k * 8));
-    if (out_dist) {
-        const int e = distbuf.ensure(dist_bytes);
-        if (e != TK_OK) {
-            outbuf.release();
-            return e;
-        }
+    if (out_dist) TRY(distbuf.ensure(dist_bytes));
+    if (exclude) {
+        TRY(exbuf.ensure((size_t)nq * 8));
+        HIPCHECK(hipMemcpy(exbuf.p, exclude, (size_t)nq * 8, hipMemcpyHostToDevice));
     }
-    HIPCHECK(hipMemcpy(ix->q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(ix->qpq.p, q_pq, (size_t)nq * ix->dq * esz, hipMemcpyHostToDevice));
+    if (rows) {
+        TRY(rowbuf.ensure((size_t)nq * 8));
+        HIPCHECK(hipMemcpy(rowbuf.p, rows, (size_t)nq * 8, hipMemcpyHostToDevice));
+        TRY(tk_index_gather_queries_dev(ix, rowbuf.as<int64_t>(), nq, ix->q.as<float>(), ix->qpq.p, nullptr));
+    } else {
+        HIPCHECK(hipMemcpy(ix->q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(ix->qpq.p, q_pq, (size_t)nq * ix->dq * esz, hipMemcpyHostToDevice));
+    }
     int r = query_batch_dev_impl(ix, ix->q.as<float>(), ix->qpq.p, q_pq_is_f64, nq, k, n_probes, pass_1,
-                                 outbuf.as<int64_t>(), nullptr, nullptr, nullptr, allow, out_dist ? distbuf.p : nullptr);
+                                 outbuf.as<int64_t>(), nullptr, nullptr, nullptr, allow, out_dist ? distbuf.p : nullptr,
+                                 exclude ? exbuf.as<int64_t>() : nullptr);
     if (r == TK_OK) r = flush_pending(ix);
     const Work &lw = ix->works[(ix->calls + ix->works.size() - 1) % ix->works.size()];   // last used
     if (r == TK_OK) {
@@ -1836,8 +1889,6 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
             e = hipMemcpy(out_heap_val, lw.heap_val.p, (size_t)nq * p.R * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) r = fail(TK_ERR_HIP, hipGetErrorString(e));
     }
-    outbuf.release();
-    distbuf.release();
     return r;
 }
 
@@ -1892,6 +1943,39 @@ extern "C" int tk_index_query_batch_dev_dist(tk_index *ix, const tk_allow *allow
     if (!out_dist_dev && nq > 0) return fail(TK_ERR_ARG, "bad argument: null distance buffer");
     return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
                                 (hipEvent_t)done_event, stream, allow, out_dist_dev);
+}
+
+// everything at once: an allowed set, one excluded row per query, distances, the debug outputs — any of them NULL
+// (rows.hip, tinyknn_hip.h)
+extern "C" int tk_index_query_batch_ex2(tk_index *ix, const tk_allow *allow, const int64_t *exclude, const float *q,
+                                        const void *q_pq, int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                                        int64_t *out_ids, void *out_dist, int64_t *out_probes, int64_t *out_heap_idx,
+                                        int32_t *out_heap_val)
+{
+    return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
+                            out_heap_val, allow, out_dist, exclude);
+}
+
+extern "C" int tk_index_query_batch_dev_ex2(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
+                                            const float *q_dev, const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k,
+                                            int n_probes, int pass_1, int64_t *out_ids_dev, void *out_dist_dev,
+                                            void *done_event, void *stream)
+{
+    IXLOCK(ix);
+    return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
+                                (hipEvent_t)done_event, stream, allow, out_dist_dev, exclude_dev);
+}
+
+// the stored rows `rows` as queries, each leaving itself out where exclude_self
+extern "C" int tk_index_query_rows(tk_index *ix, const tk_allow *allow, const int64_t *rows, int64_t nq,
+                                   int exclude_self, int k, int n_probes, int pass_1, int64_t *out_ids, void *out_dist,
+                                   int64_t *out_probes, int64_t *out_heap_idx, int32_t *out_heap_val)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix && (nq == 0 || rows), "null index / rows");
+    ARGCHECK(ix->have_pq && ix->have_centers, "set_pq and set_centers first");
+    return query_batch_host(ix, nullptr, nullptr, ix->rot_d_pad > 0, nq, k, n_probes, pass_1, out_ids, out_probes,
+                            out_heap_idx, out_heap_val, allow, out_dist, exclude_self ? rows : nullptr, rows);
 }
 
 extern "C" int tk_index_set_heap_mode(tk_index *ix, int mode)

@@ -199,6 +199,11 @@ struct tk_index {
     int64_t total_chunks = 0, total_ids = 0;
     int max_list_chunks = 0;
     uint64_t lists_gen = 0;    // counts the times the lists were (re-)set: an allowed set is valid for one layout
+    // where every row is stored (rows.hip): made by the first call that names an exclude array, for ONE layout
+    DevBuf row_pos_off, row_pos;
+    bool row_pos_ok = false;
+    uint64_t row_pos_gen = 0;  // lists_gen when it was made
+    int64_t row_pos_builds = 0;
     // members per (list, column of nearest): list l holds its column-0 members first, then column 1's, ...
     // (group_data_by_indices); known after tk_index_build_dev / tk_index_add_rows (list_kp = columns), not
     // after a host upload (list_kp = 0: tk_index_add_rows takes them from the caller)
@@ -406,7 +411,10 @@ int stage_coarse_rest(tk_index *ix, Work &w, const float *q_dev, int64_t nq, con
 int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
                const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain = false,
                TkSecond q2 = TkSecond(), TkSecond out2 = TkSecond(), int *plain_flag = nullptr,
-               const tk_allow *allow = nullptr, void *dist_dev = nullptr, TkSecond dist2 = TkSecond());
+               const tk_allow *allow = nullptr, void *dist_dev = nullptr, TkSecond dist2 = TkSecond(),
+               const int64_t *exclude = nullptr, TkSecond exclude2 = TkSecond());
+// rows.hip: the row-position table of the index's current lists exists (made now if not: synchronises the device)
+int row_pos_ensure(tk_index *ix);
 int head_chunks(const tk_index *ix, const Plan &p);    // chunks of a first probed list the exact kernel keeps (head mode)
 // the workspace's three pair sets: whole lists exact / plain tiles / heads
 TkPairSet exact_pairs(const Work &w);

@@ -572,8 +572,8 @@ void tk_launch_row_copies(const int64_t *ids, int64_t T, int *cnt, int64_t N, in
         hipLaunchKernelGGL(copies_summary_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, cnt, N, out);
 }
 
-// rows of an (N, d) matrix gathered by id as float32 (rescoring vectors for the checker): float32 vectors, or
-// vectors stored as IEEE half, widened (exact)
+// rows of an (N, d) matrix gathered by id as float32 (rescoring vectors for the checker, stored rows as queries):
+// float32 vectors, vectors stored as IEEE half, widened (exact), or float64 vectors rounded to nearest even
 template <typename TY>
 __global__ void gather_rows_kernel(const TY *__restrict__ X, int d, const int64_t *__restrict__ rows, int64_t n,
                                    float *__restrict__ out)
@@ -591,6 +591,8 @@ void tk_launch_gather_rows(const void *X, int data_dtype, int d, const int64_t *
     const dim3 grid((unsigned)((n * d + 255) / 256)), block(256);
     if (data_dtype == 2)
         hipLaunchKernelGGL(gather_rows_kernel<_Float16>, grid, block, 0, s, (const _Float16 *)X, d, rows, n, out);
+    else if (data_dtype == 1)       // (double -> float: round to nearest even, numpy's astype)
+        hipLaunchKernelGGL(gather_rows_kernel<double>, grid, block, 0, s, (const double *)X, d, rows, n, out);
     else
         hipLaunchKernelGGL(gather_rows_kernel<float>, grid, block, 0, s, (const float *)X, d, rows, n, out);
 }

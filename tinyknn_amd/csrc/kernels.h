@@ -449,9 +449,22 @@ void tk_launch_compact_lists(const uint4 *old_tiled, const int64_t *old_chunk_of
 // copies per row of T labels into cnt (N ints, zeroed); out = {largest row stored, most copies, fewest copies of a
 // stored row, labels outside [0, N)}, {-1, 0, INT_MAX, 0} on entry
 void tk_launch_row_copies(const int64_t *ids, int64_t T, int *cnt, int64_t N, int *out, hipStream_t s);
-// n rows of X (N, d) by id as float32; data_dtype: TK_DATA_F32, or TK_DATA_F16 (IEEE half, widened)
+// n rows of X (N, d) by id as float32; data_dtype: TK_DATA_F32, TK_DATA_F16 (IEEE half, widened) or TK_DATA_F64
+// (rounded to nearest even, as numpy's astype)
 void tk_launch_gather_rows(const void *X, int data_dtype, int d, const int64_t *rows, int64_t n, float *out,
                            hipStream_t s);
+// rows.hip: where every row is stored.  pos_off[r .. r + 1]: row r's entries of pos, each an index into the labels
+struct TkRowPos {
+    const int *pos_off = nullptr, *pos = nullptr;
+    int64_t N = 0, T = 0;
+};
+// ... and one excluded row per query: every copy of it in a probed slot takes the empty value (127: signed bytes) in dist, its chunk's
+// byte of mins is recomputed.  Slot arrays, dist / mins rows and `only` as tk_launch_allow_pass; ex_a / ex_b: the
+// excluded rows of the batch's first call (from batch row q0 on the slot arrays start at) and of its second call
+void tk_launch_exclude_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
+                            const int *slot_prefix, const int *slot_n, const int64_t *slot_label_off, int S,
+                            const TkRowPos &tab, const int64_t *ex_a, TkSecond ex_b, int64_t q0, const int *only,
+                            hipStream_t s);
 // half storage of float32 rows (n, d) on the device: *first_bad (preset to ~0) = the first row with a value whose
 // half is not finite (|x| >= 65520, inf, NaN); `out` = the rows as halfs, round-to-nearest-even, subnormals kept
 void tk_launch_check_half(const float *X, int64_t n, int d, unsigned long long *first_bad, hipStream_t s);

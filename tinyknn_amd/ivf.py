@@ -698,8 +698,57 @@ class DeviceIndex:
         except Exception:
             pass
 
-    def query_batch(self, qn, q_pq, k, n_probes, pass_1=None, debug=False, *, allowed=None, return_distances=False):
+    def _exclude_of(self, exclude, nq):
+        """the int64 array an `exclude=` argument is: 1-d, one entry per query, each a row id or -1 (nothing)"""
+        a = np.asarray(exclude)
+        if a.ndim != 1 or not (a.size == 0 or np.issubdtype(a.dtype, np.integer)):
+            raise TypeError("exclude: a 1-d integer array, one row id (or -1) per query")
+        if a.shape[0] != nq:
+            raise ValueError(f"exclude: one entry per query ({nq}), got {a.shape[0]}")
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        if a.size and (a.min() < -1 or a.max() >= self.N):
+            raise ValueError(f"exclude: entries must lie in [-1, {self.N})")
+        return a
+
+    def _query_ex2(self, call, nq, k, n_probes, pass_1, debug, return_distances, allowed, exclude=None):
+        """The library's everything-at-once host calls (tk_index_query_batch_ex2 / tk_index_query_rows) for rows
+        [o, e) at a time: call(o, e, allow handle, exclude, out, dist, probes, heap_idx, heap_val)."""
+        if return_distances and debug:
+            raise ValueError("query_batch: debug=True cannot be combined with return_distances=True")
+        out = np.full((nq, k), -1, dtype=np.int64)
+        dist = probes = hidx = hval = None
+        if return_distances:
+            dist = np.full((nq, k), np.inf, dtype=np.float64 if self._f64 else np.float32)
+        if debug:
+            R = pass_1 if pass_1 else (n_probes + 1) * k + 1
+            probes = np.zeros((nq, min(n_probes, self.n_lists)), dtype=np.int64)
+            hidx = np.zeros((nq, R), dtype=np.int64)
+            hval = np.zeros((nq, R), dtype=np.int32)
+        aset, temp = (None, False) if allowed is None else self._allow_of(allowed)
+        try:
+            # (one sub-batch at a time keeps the debug outputs of every row)
+            step = max(1, self.max_sub_batch(k, n_probes, pass_1)) if debug else max(1, nq)
+            for o in range(0, nq, step):
+                e = min(nq, o + step)
+                _lib.check(call(o, e, None if aset is None else aset.handle,
+                                None if exclude is None else _lib.ptr(exclude[o:e], _lib._i64p),
+                                _lib.ptr(out[o:e], _lib._i64p), None if dist is None else dist[o:e].ctypes.data,
+                                None if probes is None else _lib.ptr(probes[o:e], _lib._i64p),
+                                None if hidx is None else _lib.ptr(hidx[o:e], _lib._i64p),
+                                None if hval is None else _lib.ptr(hval[o:e], _lib._i32p)))
+        finally:
+            if temp:
+                aset.close()
+        if debug:
+            return out, dict(probes=probes, heap_idx=hidx, heap_val=hval)
+        return (out, dist) if return_distances else out
+
+    def query_batch(self, qn, q_pq, k, n_probes, pass_1=None, debug=False, *, allowed=None, return_distances=False,
+                    exclude=None):
         """qn: (nq, d) float32 normalised queries; q_pq: (nq, dq) table-build queries.
+        exclude: None, or a 1-d integer array of length nq: the row each query may not return, -1 for none (the
+        reference's `insert` only for labels != that row); such calls take the library path
+        (tk_index_query_batch_ex2), not the cached streaming session.
         allowed: None, or the rows the queries may return — an AllowSet (allow()), a bool mask of length N or row
         ids (the library's _allow entry point: the reference's `insert` only for those labels).
         return_distances: (ids, dists) — the same ids, and beside each the exact squared distance the rescoring
@@ -711,6 +760,14 @@ class DeviceIndex:
         q_pq = np.ascontiguousarray(q_pq, dtype=np.float64 if is64 else np.float32)
         nq = qn.shape[0]
         assert qn.shape[1] == self.d and q_pq.shape == (nq, self.dq)
+        if exclude is not None:
+            exclude = self._exclude_of(exclude, nq)
+            L, knobs = _lib.lib(), (int(k), int(n_probes), int(pass_1 or 0))
+            return self._query_ex2(
+                lambda o, e, a, ex, out, *rest: L.tk_index_query_batch_ex2(
+                    self._h, a, ex, _lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o, *knobs,
+                    out, *rest),
+                nq, k, n_probes, pass_1, debug, return_distances, allowed, exclude)
         out = np.full((nq, k), -1, dtype=np.int64)
         if allowed is None and not return_distances and not debug and nq > 0:
             # the session pads unrotated queries on the device: only for q_pq = pad1(qn)
@@ -759,6 +816,58 @@ class DeviceIndex:
             return out, dict(probes=probes, heap_idx=hidx, heap_val=hval)
         return out
 
+    def _rows_of(self, rows, what):
+        """int64 row ids in [0, N), duplicates allowed (validated like remove's ids)"""
+        is_mask, a = _mask_or_ids(rows, self.N, what, "a 1-d integer array of row ids")
+        if is_mask:
+            raise TypeError(f"{what}: a 1-d integer array of row ids")
+        return a
+
+    def pipeline_settings(self):
+        """(pipeline depth, coalesce) as the library holds them (tk_index_info, tk_index_coalesce)"""
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_info(self._h, _lib.ptr(info, _lib._i64p)))
+        return int(info[5]), int(_lib.check(_lib.lib().tk_index_coalesce(self._h)))
+
+    def rotated(self):
+        """True where the device holds the PQ's rotation: its q_pq (gather_queries, the fast front end) is float64"""
+        info = np.zeros(8, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_info(self._h, _lib.ptr(info, _lib._i64p)))
+        return bool(info[4] > 0)
+
+    def gather_queries(self, rows):
+        """(qn, q_pq) on the host as the device makes them from the stored rows (tk_index_gather_queries):
+        qn = float32(data[rows]), not normalised again; q_pq = qn padded (float32), or rotated by the device's
+        float64 FMA chain where the PQ has a rotation (float64)."""
+        rows = self._rows_of(rows, "gather_queries")
+        qn = np.zeros((len(rows), self.d), dtype=np.float32)
+        qp = np.zeros((len(rows), self.dq), dtype=np.float64 if self.rotated() else np.float32)
+        _lib.check(_lib.lib().tk_index_gather_queries(self._h, _lib.ptr(rows, _lib._i64p), len(rows),
+                                                      _lib.ptr(qn, _lib._f32p), qp.ctypes.data))
+        return qn, qp
+
+    def gather_queries_dev(self, rows_ptr, nq, qn_ptr, qpq_ptr, stream=0):
+        """Device pointers: nq int64 row ids (in [0, N): not checked) -> qn (nq, d) float32 and q_pq (nq, dq),
+        float64 iff the PQ has a rotation; enqueued on `stream` (tk_index_gather_queries_dev)."""
+        _lib.check(_lib.lib().tk_index_gather_queries_dev(self._h, rows_ptr, int(nq), qn_ptr, qpq_ptr, stream))
+
+    def query_rows(self, rows, k, n_probes, pass_1=None, debug=False, *, exclude_self=True, allowed=None,
+                   return_distances=False):
+        """The neighbours of stored rows (tk_index_query_rows): gather_queries(rows) as the queries, each leaving
+        its own row out where exclude_self.  Outputs as query_batch."""
+        rows = self._rows_of(rows, "query_rows")
+        L, knobs = _lib.lib(), (int(k), int(n_probes), int(pass_1 or 0))
+        return self._query_ex2(
+            lambda o, e, a, ex, *outs: L.tk_index_query_rows(
+                self._h, a, _lib.ptr(rows[o:e], _lib._i64p), e - o, int(bool(exclude_self)), *knobs, *outs),
+            len(rows), k, n_probes, pass_1, debug, return_distances, allowed)
+
+    def row_table(self):
+        """The row-position table behind exclude= (tk_index_row_table): dict(built, bytes, builds, entries)."""
+        o = np.zeros(4, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_row_table(self._h, _lib.ptr(o, _lib._i64p)))
+        return dict(built=bool(o[0]), bytes=int(o[1]), builds=int(o[2]), entries=int(o[3]))
+
     def query_batch_raw(self, qs, k, n_probes, pass_1=None):
         """Fast mode: raw float32 queries, normalisation / padding / rotation on the device
         (tk_index_prepare_dev: not bit-identical to the host's BLAS results — normalised rows within 4 float32
@@ -783,7 +892,7 @@ class DeviceIndex:
         return out
 
     def query_batch_dev(self, qn_ptr, qpq_ptr, qpq_is_f64, nq, k, n_probes, out_ptr,
-                        pass_1=None, stream=0, done_event=None, *, allowed=None, dist_ptr=None):
+                        pass_1=None, stream=0, done_event=None, *, allowed=None, dist_ptr=None, exclude_ptr=None):
         """Device pointers in, device pointer out, enqueued on `stream` (no sync).
         done_event: a hipEvent_t (integer handle) recorded behind the batch's last kernel, on
         whichever internal stream that runs (tk_index_query_batch_dev_ex).
@@ -795,13 +904,19 @@ class DeviceIndex:
         (tk_index_query_batch_dev_allow).
         dist_ptr: None, or a device buffer of nq * k distances (float32; float64 for float64 vectors) that receives
         the rescoring's exact squared distances beside the ids, complete when out_ptr's ids are
-        (tk_index_query_batch_dev_dist)."""
+        (tk_index_query_batch_dev_dist).
+        exclude_ptr: None, or a device buffer of nq int64: the row each query may not return, anything outside [0, N)
+        for none (tk_index_query_batch_dev_ex2); the library's until join() or done_event, like the others."""
         if allowed is not None:
             if not isinstance(allowed, AllowSet):
                 raise TypeError("query_batch_dev: allowed= takes a prepared set (DeviceIndex.allow / IVF.allow)")
             allowed = self._allow_of(allowed)[0].handle
         L, ev = _lib.lib(), None if done_event is None else C.c_void_p(int(done_event))
-        if dist_ptr is not None:
+        if exclude_ptr is not None:
+            rc = L.tk_index_query_batch_dev_ex2(
+                self._h, allowed, exclude_ptr, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes),
+                int(pass_1 or 0), out_ptr, dist_ptr, ev, stream)
+        elif dist_ptr is not None:
             rc = L.tk_index_query_batch_dev_dist(
                 self._h, allowed, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes), int(pass_1 or 0),
                 out_ptr, dist_ptr, ev, stream)
@@ -1628,8 +1743,9 @@ class IVF:
         device, reused across calls; .close() frees it, len() = allowed stored rows."""
         return self._unsharded_device_index().allow(ids_or_mask)
 
-    def query(self, q, k, n_probes=1, pass_1=None, *, allowed=None, return_distances=False):
+    def query(self, q, k, n_probes=1, pass_1=None, *, allowed=None, return_distances=False, exclude=None):
         """Top-k ids for one query.  reference: ivf.py:106-163
+        exclude: a row id the query may not return, or None.
         allowed: the rows it may return (a bool mask of length N, row ids, or allow()'s set) — the reference's
         query with `insert` only for those labels.
         return_distances: (ids, dists) of the same length — the exact squared distance of each id to the
@@ -1638,17 +1754,81 @@ class IVF:
         assert self.data.shape[1] == q.shape[0]
         qn, qp = self._prepare(q[None, :])
         dev = self._unsharded_device_index()
+        if exclude is not None:
+            exclude = np.asarray(exclude).reshape(1)
         if return_distances:
-            ids, dist = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, return_distances=True)
+            ids, dist = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, return_distances=True,
+                                        exclude=exclude)
             out, dist = ids[0], dist[0]
             if out[-1] == -1:
                 keep = out != -1
                 return out[keep], dist[keep]
             return out, dist
-        out = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed)[0]
+        out = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, exclude=exclude)[0]
         return out[out != -1] if out[-1] == -1 else out
 
-    def query_batch(self, qs, k, n_probes=1, pass_1=None, fast=False, *, allowed=None, return_distances=False):
+    def query_rows(self, rows, k, n_probes=1, pass_1=None, *, exclude_self=True, allowed=None,
+                   return_distances=False):
+        """The neighbours of stored rows: (len(rows), k) ids padded with -1 — (ids, dists) with return_distances —
+        of the queries float32(data[rows]), made on the device without a second normalisation.
+        exclude_self: a row's own copies are never inserted, so it is not among its neighbours; its twin with an equal
+        vector is.  rows: ids in [0, N), duplicates allowed (ValueError outside).  A removed row is still a vector:
+        it can be a query row, and nothing is masked for it."""
+        return self._unsharded_device_index().query_rows(rows, k, n_probes, pass_1, exclude_self=exclude_self,
+                                                         allowed=allowed, return_distances=return_distances)
+
+    def knn_graph(self, k, n_probes=1, pass_1=None, *, chunk=10000, return_distances=False):
+        """query_rows over every row, itself left out: (N, k) ids — (ids, dists) with return_distances.  Chunks of
+        `chunk` rows run through the pipelined device calls in pairs (set_pipeline(3), set_coalesce(2)): row ids are
+        generated on the device, results copied back per group of chunks; the settings found are restored."""
+        import torch
+        dev = self._unsharded_device_index()
+        N, d, dq = dev.N, dev.d, dev.dq
+        chunk = int(max(1, min(chunk, dev.max_sub_batch(k, n_probes, pass_1), max(N, 1))))
+        f64q, f64d = dev.rotated(), dev._f64
+        ids = np.full((N, k), -1, dtype=np.int64)
+        dist = np.full((N, k), np.inf, dtype=np.float64 if f64d else np.float32) if return_distances else None
+        depth0, coalesce0 = dev.pipeline_settings()
+        group = 8       # chunks in flight: their buffers are the library's until join()
+        cuda = torch.device("cuda", torch.cuda.current_device())
+        bufs = [dict(rows=torch.empty(chunk, dtype=torch.int64, device=cuda),
+                     qn=torch.empty((chunk, d), dtype=torch.float32, device=cuda),
+                     qp=torch.empty((chunk, dq), dtype=torch.float64 if f64q else torch.float32, device=cuda),
+                     ids=torch.empty((chunk, k), dtype=torch.int64, device=cuda),
+                     dist=torch.empty((chunk, k), dtype=torch.float64 if f64d else torch.float32, device=cuda)
+                     if return_distances else None) for _ in range(min(group, -(-N // chunk)))]
+        try:
+            dev.set_pipeline(3)
+            dev.set_coalesce(2)
+            st = torch.cuda.current_stream().cuda_stream
+            for g0 in range(0, N, group * chunk):
+                spans = []
+                for b in bufs:
+                    o = g0 + len(spans) * chunk
+                    if o >= N:
+                        break
+                    n = min(N, o + chunk) - o
+                    torch.arange(o, o + n, out=b["rows"][:n])
+                    dev.gather_queries_dev(b["rows"].data_ptr(), n, b["qn"].data_ptr(), b["qp"].data_ptr(), st)
+                    dev.query_batch_dev(b["qn"].data_ptr(), b["qp"].data_ptr(), f64q, n, k, n_probes,
+                                        b["ids"].data_ptr(), pass_1, st,
+                                        dist_ptr=None if dist is None else b["dist"].data_ptr(),
+                                        exclude_ptr=b["rows"].data_ptr())
+                    spans.append((o, n))
+                dev.join(st)
+                torch.cuda.current_stream().synchronize()
+                for b, (o, n) in zip(bufs, spans):
+                    ids[o:o + n] = b["ids"][:n].cpu().numpy()
+                    if dist is not None:
+                        dist[o:o + n] = b["dist"][:n].cpu().numpy()
+        finally:
+            dev.join(0)
+            dev.set_pipeline(depth0)
+            dev.set_coalesce(coalesce0)
+        return (ids, dist) if return_distances else ids
+
+    def query_batch(self, qs, k, n_probes=1, pass_1=None, fast=False, *, allowed=None, return_distances=False,
+                    exclude=None):
         """(nq, d) queries -> (nq, k) int64 ids, rows padded with -1 when the
         reference would return fewer than k ids.  (The reference's README shows a
         2-d `ivf.query(queries, ...)` that its code does not support; this is that
@@ -1656,19 +1836,25 @@ class IVF:
         of numpy's per-query BLAS calls (35 ms per 10 000 queries on the host) — within
         4 float32 ulp of their normalised rows, so a rare id can differ from the
         reference's; the default is exact.
-        return_distances: ((nq, k) ids, (nq, k) exact squared distances), INTEGRATION.md §2f."""
+        return_distances: ((nq, k) ids, (nq, k) exact squared distances), INTEGRATION.md §2f.
+        exclude: a 1-d integer array, the row each query may not return or -1; not with fast=True."""
+        if exclude is not None and fast:
+            raise NotImplementedError("IVF.query_batch: fast=True with exclude= is not supported; "
+                                      "use the exact default (fast=False)")
         if return_distances and fast:
             raise NotImplementedError("IVF.query_batch: fast=True with return_distances=True is not supported; "
                                       "use the exact default (fast=False)")
         self._unsharded_device_index()
-        if allowed is not None or return_distances:
+        if allowed is not None or return_distances or exclude is not None:
             if fast:
                 raise NotImplementedError("IVF.query_batch: fast=True with allowed= is not supported; "
                                           "use the exact default (fast=False)")
             qs = np.array(qs, dtype=np.float32, order="C", copy=True)
+            if exclude is not None and np.ndim(exclude) == 1 and len(exclude) != len(qs):
+                raise ValueError(f"exclude: one entry per query ({len(qs)}), got {len(exclude)}")
             qn, qp = self._prepare(qs)
             return self.device_index().query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed,
-                                                   return_distances=return_distances)
+                                                   return_distances=return_distances, exclude=exclude)
         if fast:
             return self.device_index().query_batch_raw(qs, k, n_probes, pass_1)
         R = self.pq.R
