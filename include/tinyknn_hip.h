@@ -637,6 +637,45 @@ int tk_index_query_rows(tk_index *ix, const tk_allow *allow, const int64_t *rows
                         int k, int n_probes, int pass_1, int64_t *out_ids, void *out_dist, int64_t *out_probes,
                         int64_t *out_heap_idx, int32_t *out_heap_val);
 int tk_index_row_table(tk_index *ix, int64_t *info4);
+/* Every query of a batch restricted to its own group of rows (one tenant, language or category per row).
+ * groups[r] in [0, 2^31 - 1) is row r's group.  A query with group g >= 0 returns what IVF.query (ivf.py:106-163)
+ * returns when `insert` in query_pq runs only for labels with groups[label] == g — the allowed set "groups == g",
+ * for that query alone, with everything else the reference's as for allowed sets above; bit for bit that guarded
+ * reference.  g = -1: the query is unrestricted.  A g that no row carries: the query returns no id (a row of -1).
+ * With an allowed set and / or an exclude array as well, `insert` runs only for labels that pass all of them.
+ * tk_index_set_groups: n == N ids on the host (outside [0, 2^31 - 1): TK_ERR_ARG), uploaded once and kept until
+ * they are replaced, cleared (NULL, 0) or the index is destroyed; completes the batches in flight first.
+ * tk_index_groups: the number of rows the groups cover, 0 for none.
+ * On the device the rows of other groups in a probed list take the heap's empty value in the query's distance row,
+ * where the allowed set's pass runs (behind the list scans and every exact re-scan, in front of every replay; never
+ * on the coarse stage).  Their groups are read from a table in list-position order, 64 bytes per stored chunk of 16
+ * rows beside the 4 N bytes by row id (0.4 GB each at 100M rows stored once, plus the allocator's eighth of slack),
+ * made from the device-resident labels by the first call that passes a group array, once per layout of the lists
+ * (again after tk_index_set_lists, _add_rows, _remove_rows and after tk_index_set_groups; that call synchronises
+ * the device, so make it outside a stream capture), freed with the index.  Calls without an array never make it
+ * and launch nothing more than before.
+ * tk_index_query_batch_ex3 / _dev_ex3: _ex2 with one more pointer, group / group_dev (int32, nq entries), which may
+ * be NULL.  The host call checks group (an entry < -1: TK_ERR_ARG, nothing run) and passes an array of only -1 on as
+ * none.  The device call does not read group_dev on the host: an entry < 0 there leaves its query unrestricted.
+ * group_dev belongs to the library until done_event or tk_index_join, like the other buffers.
+ * Refused, nothing run: a group array while no groups are set, or while they cover fewer rows than the index has
+ * (after tk_index_add_rows: TK_ERR_STATE, set them again); a list-sharded index (TK_ERR_ARG).
+ * Sub-batches and the pipelined mode as the _ex2 calls.  A call with a group array is a restricted call: in the
+ * automatic plain-scan mode it takes the exact scan and leaves the automatic state alone, as a call with an allowed
+ * set; two calls pair (tk_index_set_coalesce) only where both pass a group array or neither does.
+ * tk_index_group_table: info4 = {table exists for the current lists, its bytes, times one was made, the bytes of
+ * the groups by row id}. */
+int tk_index_set_groups(tk_index *ix, const int32_t *groups, int64_t n);
+int64_t tk_index_groups(tk_index *ix);
+int tk_index_query_batch_ex3(tk_index *ix, const tk_allow *allow, const int64_t *exclude, const int32_t *group,
+                             const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k, int n_probes,
+                             int pass_1, int64_t *out_ids, void *out_dist, int64_t *out_probes,
+                             int64_t *out_heap_idx, int32_t *out_heap_val);
+int tk_index_query_batch_dev_ex3(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
+                                 const int32_t *group_dev, const float *q_dev, const void *q_pq_dev, int q_pq_is_f64,
+                                 int64_t nq, int k, int n_probes, int pass_1, int64_t *out_ids_dev,
+                                 void *out_dist_dev, void *done_event, void *stream);
+int tk_index_group_table(tk_index *ix, int64_t *info4);
 /* hipStream_t on which to copy a batch's inputs in (pipelined mode: the index's front stream,
  * where the batch's first kernel runs; NULL: use the stream the batch is enqueued on) */
 void *tk_index_input_stream(tk_index *ix);

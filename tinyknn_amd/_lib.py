@@ -171,6 +171,15 @@ SIGNATURES = {
     "tk_index_query_rows": (C.c_int, [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                       _i64p, C.c_void_p, _i64p, _i64p, _i32p]),
     "tk_index_row_table": (C.c_int, [C.c_void_p, _i64p]),
+    "tk_index_set_groups": (C.c_int, [C.c_void_p, _i32p, C.c_int64]),
+    "tk_index_groups": (C.c_int64, [C.c_void_p]),
+    "tk_index_query_batch_ex3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _f32p, C.c_void_p, C.c_int,
+                                           C.c_int64, C.c_int, C.c_int, C.c_int, _i64p, C.c_void_p, _i64p, _i64p,
+                                           _i32p]),
+    "tk_index_query_batch_dev_ex3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    "tk_index_group_table": (C.c_int, [C.c_void_p, _i64p]),
     "tk_index_coalesce": (C.c_int, [C.c_void_p]),
     "tk_index_pending": (C.c_int, [C.c_void_p]),
     "tk_index_input_stream": (C.c_void_p, [C.c_void_p]),

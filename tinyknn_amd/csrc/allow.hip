@@ -16,6 +16,7 @@
 // The set is a bitmap in list-position order: 16 bits per stored chunk, indexed like list_chunk_off (bit r of chunk
 // c = row r of the chunk; the rows that pad a list's last chunk get 0).
 #include "api_internal.h"
+#include "chunk_mask.h"
 
 // One workgroup per list.  Each wave takes 64 consecutive rows of the list (4 chunks): lane j tests row j's label,
 // the wave's ballot holds the 4 chunks' 16-bit masks, lanes 0/16/32/48 write them.  Coalesced reads of the labels.
@@ -48,8 +49,8 @@ __global__ __launch_bounds__(256) void allow_bits_kernel(const int64_t *__restri
 
 // One workgroup per query; threads stride over the query's contiguous chunk range [0, slot_prefix[S]) of dist / mins,
 // the slot prefix in LDS.  A chunk whose 16 bits are all set is not touched; one with none set is written without
-// being read; else its disallowed bytes take the empty value and its minimum byte is recomputed (the replays' LAZY
-// form and the block-minimum skips read it).  only (or NULL): [count, q_0, q_1, ...] — just these queries (the
+// being read; else its disallowed bytes take the empty value and its minimum byte is recomputed (tk_mask_chunk,
+// chunk_mask.h).  only (or NULL): [count, q_0, q_1, ...] — just these queries (the
 // exact re-scan of flagged queries rewrote their rows: rescan_flagged).
 template <bool SIGNED>
 __global__ __launch_bounds__(256) void allow_pass_kernel(uint4 *__restrict__ dist, int64_t cap,
@@ -68,7 +69,6 @@ __global__ __launch_bounds__(256) void allow_pass_kernel(uint4 *__restrict__ dis
     for (int s = threadIdx.x; s <= S; s += blockDim.x) pre[s] = slot_prefix[q * (S + 1) + s];
     __syncthreads();
     const int total = pre[S];
-    const uint32_t fill = SIGNED ? 0x7f7f7f7fu : 0xffffffffu;
     for (int f = threadIdx.x; f < total; f += blockDim.x) {
         int lo = 0, hi = S;     // largest lo with pre[lo] <= f (pre is non-decreasing, pre[0] = 0)
         while (hi - lo > 1) {
@@ -76,31 +76,7 @@ __global__ __launch_bounds__(256) void allow_pass_kernel(uint4 *__restrict__ dis
             if (pre[mid] <= f) lo = mid; else hi = mid;
         }
         const uint32_t b = bits[slot_chunk0[q * S + lo] + (f - pre[lo])];
-        if (b == 0xffffu) continue;
-        uint4 *d = dist + q * cap + f;
-        uint8_t *m = mins + q * cap_min + f;
-        if (b == 0) {
-            *d = make_uint4(fill, fill, fill, fill);
-            *m = (uint8_t)fill;
-            continue;
-        }
-        const uint4 v = *d;
-        uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        int mn = SIGNED ? 127 : 255;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            // nibble j of the row bits -> 0xff in the bytes of the allowed rows
-            const uint32_t keep = (((b >> (4 * j)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
-            w[j] = (w[j] & keep) | (fill & ~keep);
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const uint32_t y = (w[j] >> (8 * t)) & 0xffu;
-                const int x = SIGNED ? (int)(int8_t)y : (int)y;
-                mn = x < mn ? x : mn;
-            }
-        }
-        *d = make_uint4(w[0], w[1], w[2], w[3]);
-        *m = (uint8_t)mn;
+        tk_mask_chunk<SIGNED>(dist + q * cap + f, mins + q * cap_min + f, b);
     }
 }
 

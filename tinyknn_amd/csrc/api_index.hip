@@ -20,6 +20,7 @@ struct Pending {
         hipEvent_t user_ev;         // recorded behind that copy (or NULL)
         void *dist_dev = nullptr;   // the rescoring's distances beside out_dev (or NULL: ids only)
         const int64_t *exclude = nullptr;   // one row per query that the query may not return (or NULL), rows.hip
+        const int32_t *group = nullptr;     // one group per query that the query is restricted to (or NULL), groups.hip
     } subs[2];
     int n_subs = 1;
     Work *w;
@@ -32,7 +33,7 @@ struct Pending {
     bool plain = false;             // probed lists behind the first ones by the plain kernel (plain_scan.hip)
     bool coarse_launched = false;   // its coarse scan has been enqueued
     // a held first call: a second call joins it with the same k, n_probes, pass_1, table dtype, allowed set and
-    // caller's stream `st` (its table build waits on `sf`), within `room` rows in all
+    // caller's stream `st` (its table build waits on `sf`), within `room` rows in all; both name a group array or neither
     int64_t room = 0;
 
     // one call on the next workspace, every stream the caller's (pipe_begin picks the internal ones)
@@ -54,13 +55,16 @@ struct Pending {
         TkSecond dist2;
         const int64_t *exclude;     // each call's excluded rows (or NULL)
         TkSecond exclude2;
+        const int32_t *group;       // each call's groups (or NULL)
+        TkSecond group2;
     };
+    bool grouped() const { return subs[0].group != nullptr; }    // (a pair: both calls or neither, coalesce_call)
     Rows rows() const
     {
         const Sub &a = subs[0], &b = subs[1];
-        if (n_subs == 1) return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq, {}, {}, {}, a.dist_dev, {}, a.exclude, {}};
+        if (n_subs == 1) return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq, {}, {}, {}, a.dist_dev, {}, a.exclude, {}, a.group, {}};
         return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq + b.nq, {b.q_dev, a.nq}, {b.qpq_dev, a.nq}, {b.out_dev, a.nq},
-                    a.dist_dev, {b.dist_dev, a.nq}, a.exclude, {b.exclude, a.nq}};
+                    a.dist_dev, {b.dist_dev, a.nq}, a.exclude, {b.exclude, a.nq}, a.group, {b.group, a.nq}};
     }
 };
 
@@ -90,7 +94,8 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->cslots_l, &ix->c_chunk_off, &ix->q, &ix->qpq, &ix->stage, &ix->owner,
                       &ix->local_chunk_off, &ix->rot_t, &ix->br_ynorm, &ix->br_vals, &ix->br_tau,
                       &ix->br_cand, &ix->br_count, &ix->br_out, &ix->br_q, &ix->br_sample, &ix->replay_counters,
-                      &ix->twin_list, &ix->twin_off, &ix->row_pos_off, &ix->row_pos};
+                      &ix->twin_list, &ix->twin_off, &ix->row_pos_off, &ix->row_pos, &ix->row_group,
+                      &ix->group_table};
     for (DevBuf *b : bufs) b->release();
     for (Work &w : ix->works) w.release();
     // (the internal streams belong to the process: shared_streams below)
@@ -1034,11 +1039,22 @@ static void apply_exclude(const tk_index *ix, Work &w, int64_t q0, int64_t nq, c
                            w.slot_loff.as<int64_t>() + q0 * p.S, p.S, tab, exclude, exclude2, q0, only, st);
 }
 
+// One group per query (groups.hip), where apply_allow runs and with its offsets; group / group2 as exclude / exclude2
+static void apply_groups(const tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, const int32_t *group,
+                         TkSecond group2, hipStream_t st, const int *only = nullptr)
+{
+    if (!group && !group2.b) return;
+    tk_launch_group_pass(w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, nq,
+                         w.slot_prefix.as<int>() + q0 * (p.S + 1), w.slot_chunk0.as<int64_t>() + q0 * p.S, p.S,
+                         ix->group_table.as<int32_t>(), group, group2, q0, 1, only, st);
+}
+
 // The queries the replay flagged (bound above the table's limit at the first plain block, plain_scan.hip): every probed
 // list again with the exact kernel.  list_built: the replay listed them itself (TkPlainCheck::flag_list); the count then
 // reaches the host through the replay behind the re-scan (replay_flagged_tail)
 static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, hipStream_t st,
-                           const tk_allow *allow, const int64_t *exclude, TkSecond exclude2, bool list_built = false)
+                           const tk_allow *allow, const int64_t *exclude, TkSecond exclude2, const int32_t *group,
+                           TkSecond group2, bool list_built = false)
 {
     int *list = w.flag_list.as<int>();
     if (!list_built) {
@@ -1051,6 +1067,7 @@ static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const 
                           ix->order, st, list);
     apply_allow(w, q0, nq, p, allow, st, list);
     apply_exclude(ix, w, q0, nq, p, exclude, exclude2, st, list);
+    apply_groups(ix, w, q0, nq, p, group, group2, st, list);
 }
 
 // The tail behind a lane (or register-heap) replay that rode with the plain kernel: the queries it flagged — the lemma's
@@ -1110,7 +1127,7 @@ static Replay replay_form(const tk_index *ix, int64_t nq, const Plan &p)
 int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
                const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain,
                TkSecond q2, TkSecond out2, int *plain_flag, const tk_allow *allow, void *dist_dev, TkSecond dist2,
-               const int64_t *exclude, TkSecond exclude2)
+               const int64_t *exclude, TkSecond exclude2, const int32_t *group, TkSecond group2)
 {
     const TkReplayJob j = list_replay_job(ix, w, q0, nq, p);
     unsigned char *flags = w.repeat_flag.as<unsigned char>() + q0;
@@ -1120,6 +1137,7 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     if (plain) check = {w.plain0.as<int>() + q0, w.qlim.as<int>() + q0, plain_flag ? nullptr : w.flag_list.as<int>()};
     apply_allow(w, q0, nq, p, allow, st);
     apply_exclude(ix, w, q0, nq, p, exclude, exclude2, st);
+    apply_groups(ix, w, q0, nq, p, group, group2, st);
     // heaps start fresh here, so packed entries apply.  Distinct labels: one query per
     // lane (or per wave for big heaps), and the few queries whose probe list wrapped a -1
     // (a list may then be scanned twice) re-run with the duplicate test.  Repeating labels
@@ -1192,13 +1210,13 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     const bool listed = form == Replay::Pair || form == Replay::Lanes || form == Replay::LanesTwin;
     const auto replay_wrapped = [&] { tk_launch_heap_replay_packed(j, flags, TK_RUN_WRAPPED, /*dedupe=*/true, st); };
     if (plain && form == Replay::LanesDedupe) {
-        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2);
+        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2, group, group2);
         replay_wrapped();
     } else if (plain && plain_flag && (listed || form == Replay::PackedDistinct)) {
         tk_launch_shard_flag_plain(flags, nq, plain_flag, st);
         replay_wrapped();
     } else if (plain && listed) {
-        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2, true);
+        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2, group, group2, true);
         replay_flagged_tail(ix, w, j, flags, st);
         plain_verdict_event(ix, w, nq, st);
     } else if (!plain && (form == Replay::Lanes || form == Replay::LanesTwin || form == Replay::PackedDistinct)) {
@@ -1234,12 +1252,12 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
 //
 // Both depths run a batch through the same stages below; only the streams and the event hand-offs differ.
 
-// A restricted batch (allowed set) in the automatic plain-scan mode takes the exact scan and never touches the
-// state: a selective set flags many queries, and its verdicts would pause the plain path for the unrestricted traffic
-// (DESIGN §3.8).  Modes 1 and 2 hold for every batch.
+// A restricted batch (allowed set, group array) in the automatic plain-scan mode takes the exact scan and never touches
+// the state: a selective restriction flags many queries, and its verdicts would pause the plain path for the
+// unrestricted traffic.  Modes 1 and 2 hold for every batch.
 static bool plain_for(tk_index *ix, const Pending &b)
 {
-    if (b.allow && plain_adaptive(ix)) return false;
+    if ((b.allow || b.grouped()) && plain_adaptive(ix)) return false;
     return plain_now(ix, b.p);
 }
 
@@ -1300,7 +1318,7 @@ static int batch_back(tk_index *ix, Pending &b, hipStream_t st)
 {
     const Pending::Rows r = b.rows();
     TRY(stage_back(ix, *b.w, r.q, 0, r.nq, b.k, b.p, r.out, st, b.pf, b.plain, r.q2, r.out2, nullptr, b.allow, r.dist,
-                   r.dist2, r.exclude, r.exclude2));
+                   r.dist2, r.exclude, r.exclude2, r.group, r.group2));
     for (int i = 0; i < b.n_subs; i++) {
         const Pending::Sub &u = b.subs[i];
         if (u.host_out && u.host_out_kernel)
@@ -1595,7 +1613,8 @@ static int coalesce_call(tk_index *ix, Pending &b)
     if (ix->held) {
         Pending &h = *ix->held;
         const bool joins = h.k == b.k && h.n_probes == b.n_probes && h.pass_1 == b.pass_1 && h.qpq_f64 == b.qpq_f64 &&
-                           h.st == b.st && h.subs[0].nq + call.nq <= h.room && h.allow == b.allow;
+                           h.st == b.st && h.subs[0].nq + call.nq <= h.room && h.allow == b.allow &&
+                           h.grouped() == b.grouped();     // (the two kinds take different scans: plain_for)
         if (joins) {
             if (h.sf != h.st) {            // the second call's inputs: the caller's work so far
                 HIPCHECK(hipEventRecord(ix->ev_in, h.st));
@@ -1619,7 +1638,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
                                 int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
                                 int64_t *out_ids_dev, int64_t *out_ids_pinned, hipEvent_t done_ev,
                                 void *stream, const tk_allow *allow = nullptr, void *out_dist_dev = nullptr,
-                                const int64_t *exclude_dev = nullptr)
+                                const int64_t *exclude_dev = nullptr, const int32_t *group_dev = nullptr)
 {
     Plan p;
     TRY(make_plan(ix, k, n_probes, pass_1, p));
@@ -1639,6 +1658,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
         (void)hipGetLastError();
     }
     if (exclude_dev && nq > 0) TRY(row_pos_ensure(ix));     // (the first excluding call of a layout: rows.hip)
+    if (group_dev && nq > 0) TRY(group_table_ensure(ix));   // (groups set for every row; the first grouped call of a layout: groups.hip)
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     const int64_t ms = sub_batch(p);
     ARGCHECK(!(out_ids_pinned || done_ev) || (nq >= 1 && nq <= ms),
@@ -1650,7 +1670,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     if (ix->depth > 1 && ix->coalesce == 2 && (ix->ids_unique || twin_replay(ix, p)) && nq >= 1 && nq <= ms) {
         Pending b(ix, p, k, n_probes, pass_1, q_pq_is_f64, allow, caller,
                   {q_dev, q_pq_dev, out_ids_dev, nq, out_ids_pinned, ix->host_out_kernel, done_ev, out_dist_dev,
-                   exclude_dev});
+                   exclude_dev, group_dev});
         return coalesce_call(ix, b);
     }
     TRY(launch_held(ix));
@@ -1665,7 +1685,8 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
                   {q_dev + o * ix->d, (const char *)q_pq_dev + (size_t)o * ix->dq * esz, out_ids_dev + o * k, sub,
                    out_ids_pinned, ix->host_out_kernel, done_ev,
                    out_dist_dev ? (char *)out_dist_dev + (size_t)o * k * dsz : nullptr,
-                   exclude_dev ? exclude_dev + o : nullptr});     // (a part's rows of the CALL's array)
+                   exclude_dev ? exclude_dev + o : nullptr,       // (a part's rows of the CALL's arrays)
+                   group_dev ? group_dev + o : nullptr});
         if (ix->depth == 1) {
             ix->calls++;
             TRY(run_batch_inline(ix, b));
@@ -1829,7 +1850,8 @@ struct BufRelease {
 static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
                             int n_probes, int pass_1, int64_t *out_ids, int64_t *out_probes, int64_t *out_heap_idx,
                             int32_t *out_heap_val, const tk_allow *allow, void *out_dist = nullptr,
-                            const int64_t *exclude = nullptr, const int64_t *rows = nullptr)
+                            const int64_t *exclude = nullptr, const int64_t *rows = nullptr,
+                            const int32_t *group = nullptr)
 {
     IXLOCK(ix);
     Plan p;
@@ -1850,19 +1872,32 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
             excludes = excludes || exclude[i] >= 0;
         }
     if (!excludes) exclude = nullptr;
+    // group: the same (an array of only -1 restricts nothing: no table, no pass, the scan an unrestricted call takes)
+    bool groups = false;
+    if (group)
+        for (int64_t i = 0; i < nq; i++) {
+            ARGCHECK(group[i] >= -1, "group: entries must be a group id or -1");
+            groups = groups || group[i] >= 0;
+        }
+    if (!groups) group = nullptr;
+    if (group) ARGCHECK(!ix->sharded, "list-sharded index: row groups are not supported");
     ARGCHECK(!(out_probes || out_heap_idx || out_heap_val) || nq <= sub_batch(p),
              "debug outputs need the batch to fit one sub-batch");
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     TRY(ix->q.ensure((size_t)nq * ix->d * 4));
     TRY(ix->qpq.ensure((size_t)nq * ix->dq * esz));
-    DevBuf outbuf, distbuf, exbuf, rowbuf;  // separate from the sub-batch `out` workspace
-    BufRelease rel{{&outbuf, &distbuf, &exbuf, &rowbuf}};
+    DevBuf outbuf, distbuf, exbuf, rowbuf, grbuf;  // separate from the sub-batch `out` workspace
+    BufRelease rel{{&outbuf, &distbuf, &exbuf, &rowbuf, &grbuf}};
     const size_t dist_bytes = (size_t)nq * k * (ix->data_dtype == TK_DATA_F64 ? 8 : 4);
     TRY(outbuf.ensure((size_t)nq * k * 8));
     if (out_dist) TRY(distbuf.ensure(dist_bytes));
     if (exclude) {
         TRY(exbuf.ensure((size_t)nq * 8));
         HIPCHECK(hipMemcpy(exbuf.p, exclude, (size_t)nq * 8, hipMemcpyHostToDevice));
+    }
+    if (group) {
+        TRY(grbuf.ensure((size_t)nq * 4));
+        HIPCHECK(hipMemcpy(grbuf.p, group, (size_t)nq * 4, hipMemcpyHostToDevice));
     }
     if (rows) {
         TRY(rowbuf.ensure((size_t)nq * 8));
@@ -1874,7 +1909,7 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
     }
     int r = query_batch_dev_impl(ix, ix->q.as<float>(), ix->qpq.p, q_pq_is_f64, nq, k, n_probes, pass_1,
                                  outbuf.as<int64_t>(), nullptr, nullptr, nullptr, allow, out_dist ? distbuf.p : nullptr,
-                                 exclude ? exbuf.as<int64_t>() : nullptr);
+                                 exclude ? exbuf.as<int64_t>() : nullptr, group ? grbuf.as<int32_t>() : nullptr);
     if (r == TK_OK) r = flush_pending(ix);
     const Work &lw = ix->works[(ix->calls + ix->works.size() - 1) % ix->works.size()];   // last used
     if (r == TK_OK) {
@@ -1964,6 +1999,26 @@ extern "C" int tk_index_query_batch_dev_ex2(tk_index *ix, const tk_allow *allow,
     IXLOCK(ix);
     return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
                                 (hipEvent_t)done_event, stream, allow, out_dist_dev, exclude_dev);
+}
+
+// ... and one group per query (groups.hip, tinyknn_hip.h): _ex2 with one more pointer
+extern "C" int tk_index_query_batch_ex3(tk_index *ix, const tk_allow *allow, const int64_t *exclude,
+                                        const int32_t *group, const float *q, const void *q_pq, int q_pq_is_f64,
+                                        int64_t nq, int k, int n_probes, int pass_1, int64_t *out_ids, void *out_dist,
+                                        int64_t *out_probes, int64_t *out_heap_idx, int32_t *out_heap_val)
+{
+    return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
+                            out_heap_val, allow, out_dist, exclude, nullptr, group);
+}
+
+extern "C" int tk_index_query_batch_dev_ex3(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
+                                            const int32_t *group_dev, const float *q_dev, const void *q_pq_dev,
+                                            int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                                            int64_t *out_ids_dev, void *out_dist_dev, void *done_event, void *stream)
+{
+    IXLOCK(ix);
+    return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
+                                (hipEvent_t)done_event, stream, allow, out_dist_dev, exclude_dev, group_dev);
 }
 
 // the stored rows `rows` as queries, each leaving itself out where exclude_self

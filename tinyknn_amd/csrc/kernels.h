@@ -465,6 +465,13 @@ void tk_launch_exclude_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap
                             const int *slot_prefix, const int *slot_n, const int64_t *slot_label_off, int S,
                             const TkRowPos &tab, const int64_t *ex_a, TkSecond ex_b, int64_t q0, const int *only,
                             hipStream_t s);
+// groups.hip: one group per query — the probed rows of another group take the empty value, as the allowed set's pass
+// masks (slot arrays, dist / mins rows, signd and `only` as tk_launch_allow_pass).  table: 16 int32 per stored chunk
+// (list_chunk_off order); g_a / g_b: the groups of the batch's first call (from batch row q0 on the slot arrays start
+// at) and of its second call, each NULL or with entries < 0 for queries that are not restricted
+void tk_launch_group_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
+                          const int *slot_prefix, const int64_t *slot_chunk0, int S, const int32_t *table,
+                          const int32_t *g_a, TkSecond g_b, int64_t q0, int signd, const int *only, hipStream_t s);
 // half storage of float32 rows (n, d) on the device: *first_bad (preset to ~0) = the first row with a value whose
 // half is not finite (|x| >= 65520, inf, NaN); `out` = the rows as halfs, round-to-nearest-even, subnormals kept
 void tk_launch_check_half(const float *X, int64_t n, int d, unsigned long long *first_bad, hipStream_t s);

@@ -179,6 +179,34 @@ def removal_rows(ids_or_mask, N):
     return np.ascontiguousarray(np.flatnonzero(a), dtype=np.int64) if is_mask else a
 
 
+def group_ids(groups, n, what):
+    """The int32 group ids a `groups` argument is: a 1-d integer array of length n, every id in [0, 2**31 - 1)
+    (TypeError for another kind of value, ValueError for another length or an id outside)."""
+    a = np.asarray(groups)
+    if a.ndim != 1 or a.dtype == np.bool_ or not (a.size == 0 or np.issubdtype(a.dtype, np.integer)):
+        raise TypeError(f"{what}: a 1-d integer array, one group id per row")
+    if a.shape[0] != n:
+        raise ValueError(f"{what}: one group id per row ({n}), got {a.shape[0]}")
+    if a.size and (a.min() < 0 or a.max() >= 2**31 - 1):
+        raise ValueError(f"{what}: group ids must lie in [0, 2**31 - 1)")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def query_groups(group, nq):
+    """The int32 array a `group=` argument is: an int for every query, or a 1-d integer array with one entry per
+    query; each a group id or -1 (unrestricted)."""
+    a = np.asarray(group)
+    if a.dtype == np.bool_ or not (a.size == 0 or np.issubdtype(a.dtype, np.integer)) or a.ndim > 1:
+        raise TypeError("group: an int, or a 1-d integer array with one group id (or -1) per query")
+    if a.ndim == 0:
+        a = np.full(nq, a[()])
+    if a.shape[0] != nq:
+        raise ValueError(f"group: one entry per query ({nq}), got {a.shape[0]}")
+    if a.size and (a.min() < -1 or a.max() >= 2**31 - 1):
+        raise ValueError("group: entries must be a group id in [0, 2**31 - 1) or -1")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 def _stored(t):
     """Stored rows of one list's codes: a TransformedData, or the raw empty array FastPQ.transform returns for no rows."""
     return 0 if isinstance(t, np.ndarray) else t.size
@@ -627,6 +655,28 @@ class DeviceIndex:
         self._live_allows.add(a)
         return a
 
+    def set_groups(self, groups):
+        """One group id per row (int, [0, 2**31 - 1)) for the `group=` argument of the query calls, uploaded once
+        (tk_index_set_groups); None clears.  After add() they must be set again for all N rows.  Batches in flight
+        finish first.  Not for a list-sharded index."""
+        if _dev_is_sharded(self) or self._source is not None:
+            raise RuntimeError("DeviceIndex.set_groups: a list-sharded index takes no row groups")
+        if groups is None:
+            _lib.check(_lib.lib().tk_index_set_groups(self._h, None, 0))
+            return
+        g = group_ids(groups, self.N, "set_groups")
+        _lib.check(_lib.lib().tk_index_set_groups(self._h, _lib.ptr(g, _lib._i32p), len(g)))
+
+    def groups_set(self):
+        """The number of rows the device's groups cover, 0 for none (tk_index_groups)."""
+        return int(_lib.check(_lib.lib().tk_index_groups(self._h)))
+
+    def group_table(self):
+        """The group table behind group= (tk_index_group_table): dict(built, bytes, builds, row_bytes)."""
+        o = np.zeros(4, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_group_table(self._h, _lib.ptr(o, _lib._i64p)))
+        return dict(built=bool(o[0]), bytes=int(o[1]), builds=int(o[2]), row_bytes=int(o[3]))
+
     def _allow_of(self, allowed):
         """(set, temporary) for an `allowed=` argument: a prepared set of this index, or a mask / ids made into one"""
         if isinstance(allowed, AllowSet):
@@ -744,8 +794,11 @@ class DeviceIndex:
         return (out, dist) if return_distances else out
 
     def query_batch(self, qn, q_pq, k, n_probes, pass_1=None, debug=False, *, allowed=None, return_distances=False,
-                    exclude=None):
+                    exclude=None, group=None):
         """qn: (nq, d) float32 normalised queries; q_pq: (nq, dq) table-build queries.
+        group: None, an int for every query, or a 1-d integer array of length nq: the group of rows (set_groups) each
+        query may return, -1 for any (the reference's `insert` only for labels of that group); such
+        calls take the library path (tk_index_query_batch_ex3).
         exclude: None, or a 1-d integer array of length nq: the row each query may not return, -1 for none (the
         reference's `insert` only for labels != that row); such calls take the library path
         (tk_index_query_batch_ex2), not the cached streaming session.
@@ -760,14 +813,19 @@ class DeviceIndex:
         q_pq = np.ascontiguousarray(q_pq, dtype=np.float64 if is64 else np.float32)
         nq = qn.shape[0]
         assert qn.shape[1] == self.d and q_pq.shape == (nq, self.dq)
-        if exclude is not None:
-            exclude = self._exclude_of(exclude, nq)
+        if group is not None or exclude is not None:
+            if group is not None:
+                group = query_groups(group, nq)
+            if exclude is not None:
+                exclude = self._exclude_of(exclude, nq)
             L, knobs = _lib.lib(), (int(k), int(n_probes), int(pass_1 or 0))
-            return self._query_ex2(
-                lambda o, e, a, ex, out, *rest: L.tk_index_query_batch_ex2(
-                    self._h, a, ex, _lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o, *knobs,
-                    out, *rest),
-                nq, k, n_probes, pass_1, debug, return_distances, allowed, exclude)
+
+            def call(o, e, a, ex, out, *rest):
+                tail = (_lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o, *knobs, out, *rest)
+                if group is None:
+                    return L.tk_index_query_batch_ex2(self._h, a, ex, *tail)
+                return L.tk_index_query_batch_ex3(self._h, a, ex, group[o:e].ctypes.data, *tail)
+            return self._query_ex2(call, nq, k, n_probes, pass_1, debug, return_distances, allowed, exclude)
         out = np.full((nq, k), -1, dtype=np.int64)
         if allowed is None and not return_distances and not debug and nq > 0:
             # the session pads unrotated queries on the device: only for q_pq = pad1(qn)
@@ -892,7 +950,8 @@ class DeviceIndex:
         return out
 
     def query_batch_dev(self, qn_ptr, qpq_ptr, qpq_is_f64, nq, k, n_probes, out_ptr,
-                        pass_1=None, stream=0, done_event=None, *, allowed=None, dist_ptr=None, exclude_ptr=None):
+                        pass_1=None, stream=0, done_event=None, *, allowed=None, dist_ptr=None, exclude_ptr=None,
+                        group_ptr=None):
         """Device pointers in, device pointer out, enqueued on `stream` (no sync).
         done_event: a hipEvent_t (integer handle) recorded behind the batch's last kernel, on
         whichever internal stream that runs (tk_index_query_batch_dev_ex).
@@ -906,13 +965,19 @@ class DeviceIndex:
         the rescoring's exact squared distances beside the ids, complete when out_ptr's ids are
         (tk_index_query_batch_dev_dist).
         exclude_ptr: None, or a device buffer of nq int64: the row each query may not return, anything outside [0, N)
-        for none (tk_index_query_batch_dev_ex2); the library's until join() or done_event, like the others."""
+        for none (tk_index_query_batch_dev_ex2); the library's until join() or done_event, like the others.
+        group_ptr: None, or a device buffer of nq int32: the group each query is restricted to, any entry < 0 for an
+        unrestricted query (tk_index_query_batch_dev_ex3); the caller's again after join() or done_event."""
         if allowed is not None:
             if not isinstance(allowed, AllowSet):
                 raise TypeError("query_batch_dev: allowed= takes a prepared set (DeviceIndex.allow / IVF.allow)")
             allowed = self._allow_of(allowed)[0].handle
         L, ev = _lib.lib(), None if done_event is None else C.c_void_p(int(done_event))
-        if exclude_ptr is not None:
+        if group_ptr is not None:
+            rc = L.tk_index_query_batch_dev_ex3(
+                self._h, allowed, exclude_ptr, group_ptr, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes),
+                int(pass_1 or 0), out_ptr, dist_ptr, ev, stream)
+        elif exclude_ptr is not None:
             rc = L.tk_index_query_batch_dev_ex2(
                 self._h, allowed, exclude_ptr, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes),
                 int(pass_1 or 0), out_ptr, dist_ptr, ev, stream)
@@ -1166,6 +1231,7 @@ class IVF:
     list_columns = None     # (n_lists, kp) members per (list, column of the build's nearest); None: not recorded
     _build_device = None    # did build() search on the GPU?  None: not built here (fast_pq.device_build decides)
     store = None            # how the device keeps the rescoring vectors: None / "float32" / "float16" (build's store=)
+    groups = None           # set_groups' host copy: (N,) int32 group id per row; None (and no instance attribute): none
 
     def __init__(self, metric, n_clusters, pq=None):
         assert metric in ["euclidean", "angular"]
@@ -1235,6 +1301,7 @@ class IVF:
         self._dev = None
         self.data = data
         self.store = store
+        self.__dict__.pop("groups", None)               # (groups belong to the rows they were set for)
         with timer(verbose, "Computing nearest clusters..."):
             if device:
                 nearest = self._nearest_on_device(data, n_probes)
@@ -1378,6 +1445,8 @@ class IVF:
             extra["list_columns"] = self.list_columns
         if self.store is not None:          # (the vectors are written unrounded: the upload rounds again, same bits)
             extra["store"] = self.store
+        if self.groups is not None:
+            extra["groups"] = self.groups
         path = self._npz_path(path)
         np.savez(path, format_version=1, metric=self.metric, n_clusters=self.n_clusters,
                  use_kmeans=int(self.pq.use_kmeans), rotate_dim=-1 if self.pq.rotate_dim is None else int(self.pq.rotate_dim),
@@ -1419,6 +1488,8 @@ class IVF:
         # (files written before add() existed have no list_columns: add() recovers them)
         ivf.list_columns = z["list_columns"] if "list_columns" in z else None
         ivf.store = check_store(str(z["store"])) if "store" in z else None     # (files written before store= existed)
+        if "groups" in z:
+            ivf.groups = np.ascontiguousarray(z["groups"], dtype=np.int32)
         return ivf
 
     def build_resident(self, N, d, seed, centres=None, sigma=1.0, verbose=False, n_probes=1, store=None):
@@ -1463,12 +1534,14 @@ class IVF:
         self.list_columns = dev.list_columns()
         self.data = ResidentData(dev)
         self.ids = self.pq_transformed_points = None
+        self.__dict__.pop("groups", None)               # (groups belong to the rows they were set for, as in build)
         self._dev = dev
         return self
 
     # ---- growth ------------------------------------------------------------
-    def add(self, X, verbose=False):
-        """Append the rows of X with ids N .. N + n - 1 (returns self).  The index afterwards is the one its own
+    def add(self, X, verbose=False, groups=None):
+        """Append the rows of X with ids N .. N + n - 1 (returns self).  groups: the new rows' group ids, needed (and
+        only taken) where the index has groups (set_groups): ValueError otherwise, before anything changes.  The index afterwards is the one its own
         build would make over (old rows, X): new rows are prepared as the build prepared its rows (dtype of
         IVF.data, normalisation, padding, rotation, assignment, PQ codes); every list keeps its old members in
         place, and with n_probes = kp lists per row list l's column-j block becomes old_j ++ new_j (new_j: the
@@ -1482,13 +1555,25 @@ class IVF:
         d = self.data.shape[1]
         if X.ndim != 2 or X.shape[1] != d:
             raise AssertionError(f"IVF.add: X must have shape (n, {d}), got {X.shape}")
+        if self.groups is None and groups is not None:
+            raise ValueError("IVF.add: groups= on an index without groups (set_groups first)")
+        if self.groups is not None:
+            if groups is None:
+                raise ValueError("IVF.add: this index has groups (set_groups): pass the new rows' with groups=")
+            groups = group_ids(groups, len(X), "IVF.add: groups")
         if self.all_centers is None:
             raise AssertionError("IVF.add: the index has no all_centers (fit, or a file written with them)")
         if len(X) == 0:
             return self
         if self.pq_transformed_points is None:
-            return self._add_resident(X, verbose)
-        return self._add_host(X, verbose)
+            self._add_resident(X, verbose)
+        else:
+            self._add_host(X, verbose)
+        if groups is not None:          # (the device's cover the old rows only: set again for all)
+            self.groups = np.concatenate([self.groups, groups])
+            if self._dev is not None:
+                self._dev.set_groups(self.groups)
+        return self
 
     def _require_device_free(self, what="add", doing="adding rows to"):
         if self._dev is not None and _dev_is_sharded(self._dev):
@@ -1709,8 +1794,25 @@ class IVF:
     # ---- queries (GPU) -----------------------------------------------------
     def device_index(self):
         if self._dev is None:
-            self._dev = DeviceIndex(self)
+            dev = DeviceIndex(self)
+            if self.groups is not None:
+                dev.set_groups(self.groups)
+            self._dev = dev
         return self._dev
+
+    def set_groups(self, groups):
+        """One group id per row — tenant, language, category: a 1-d integer array of length N with ids in
+        [0, 2**31 - 1) — for the `group=` argument of query / query_batch; None clears.  TypeError for
+        another kind of value, ValueError for another length or an id outside.  IVF.groups is the host copy (int32);
+        save / load and pickling carry it."""
+        g = None if groups is None else group_ids(groups, len(self.data), "IVF.set_groups")
+        if self._dev is not None:                # (a list-sharded index raises here, before the host copy changes)
+            self._unsharded_device_index().set_groups(g)
+        if g is None:
+            self.__dict__.pop("groups", None)
+        else:
+            self.groups = g.copy() if g is groups else g
+        return self
 
     def _unsharded_device_index(self):
         dev = self.device_index()
@@ -1743,8 +1845,9 @@ class IVF:
         device, reused across calls; .close() frees it, len() = allowed stored rows."""
         return self._unsharded_device_index().allow(ids_or_mask)
 
-    def query(self, q, k, n_probes=1, pass_1=None, *, allowed=None, return_distances=False, exclude=None):
+    def query(self, q, k, n_probes=1, pass_1=None, *, allowed=None, return_distances=False, exclude=None, group=None):
         """Top-k ids for one query.  reference: ivf.py:106-163
+        group: the group of rows (set_groups) the query may return, -1 or None for any.
         exclude: a row id the query may not return, or None.
         allowed: the rows it may return (a bool mask of length N, row ids, or allow()'s set) — the reference's
         query with `insert` only for those labels.
@@ -1756,15 +1859,17 @@ class IVF:
         dev = self._unsharded_device_index()
         if exclude is not None:
             exclude = np.asarray(exclude).reshape(1)
+        if group is not None:
+            group = np.asarray(group).reshape(1)
         if return_distances:
             ids, dist = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, return_distances=True,
-                                        exclude=exclude)
+                                        exclude=exclude, group=group)
             out, dist = ids[0], dist[0]
             if out[-1] == -1:
                 keep = out != -1
                 return out[keep], dist[keep]
             return out, dist
-        out = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, exclude=exclude)[0]
+        out = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, exclude=exclude, group=group)[0]
         return out[out != -1] if out[-1] == -1 else out
 
     def query_rows(self, rows, k, n_probes=1, pass_1=None, *, exclude_self=True, allowed=None,
@@ -1828,7 +1933,7 @@ class IVF:
         return (ids, dist) if return_distances else ids
 
     def query_batch(self, qs, k, n_probes=1, pass_1=None, fast=False, *, allowed=None, return_distances=False,
-                    exclude=None):
+                    exclude=None, group=None):
         """(nq, d) queries -> (nq, k) int64 ids, rows padded with -1 when the
         reference would return fewer than k ids.  (The reference's README shows a
         2-d `ivf.query(queries, ...)` that its code does not support; this is that
@@ -1837,7 +1942,12 @@ class IVF:
         4 float32 ulp of their normalised rows, so a rare id can differ from the
         reference's; the default is exact.
         return_distances: ((nq, k) ids, (nq, k) exact squared distances), INTEGRATION.md §2f.
-        exclude: a 1-d integer array, the row each query may not return or -1; not with fast=True."""
+        exclude: a 1-d integer array, the row each query may not return or -1; not with fast=True.
+        group: an int for every query, or a 1-d integer array with one entry per query: the group of rows (set_groups)
+        it may return, -1 for any; not with fast=True."""
+        if group is not None and fast:
+            raise NotImplementedError("IVF.query_batch: fast=True with group= is not supported; "
+                                      "use the exact default (fast=False)")
         if exclude is not None and fast:
             raise NotImplementedError("IVF.query_batch: fast=True with exclude= is not supported; "
                                       "use the exact default (fast=False)")
@@ -1845,16 +1955,18 @@ class IVF:
             raise NotImplementedError("IVF.query_batch: fast=True with return_distances=True is not supported; "
                                       "use the exact default (fast=False)")
         self._unsharded_device_index()
-        if allowed is not None or return_distances or exclude is not None:
+        if allowed is not None or return_distances or exclude is not None or group is not None:
             if fast:
                 raise NotImplementedError("IVF.query_batch: fast=True with allowed= is not supported; "
                                           "use the exact default (fast=False)")
             qs = np.array(qs, dtype=np.float32, order="C", copy=True)
             if exclude is not None and np.ndim(exclude) == 1 and len(exclude) != len(qs):
                 raise ValueError(f"exclude: one entry per query ({len(qs)}), got {len(exclude)}")
+            if group is not None:
+                group = query_groups(group, len(qs))
             qn, qp = self._prepare(qs)
             return self.device_index().query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed,
-                                                   return_distances=return_distances, exclude=exclude)
+                                                   return_distances=return_distances, exclude=exclude, group=group)
         if fast:
             return self.device_index().query_batch_raw(qs, k, n_probes, pass_1)
         R = self.pq.R
