@@ -81,7 +81,10 @@ int tk_heap_insert_is(int64_t *indices, int32_t *vals, int R, int64_t i, int32_t
  * sums the mean in that order).  q: (nq, dq) padded (and rotated) queries, float32
  * (q_is_f64 == 0) or float64.  aux0/aux1: signed: sqrt_n_blocks, unused;
  * unsigned: log(n_blocks), sqrt(n_blocks).  Outputs: tables uint8 (nq, M, 16) (the
- * transform_tables byte image), shift (nq,) in q's dtype, scale float64 (nq,). */
+ * transform_tables byte image), shift (nq,) in q's dtype, scale float64 (nq,).
+ * dims_per_block 1 .. 32, at most 512 blocks, in both query types (as tk_index_set_pq).
+ * The unsigned table sums a block's squares as numpy's `.sum(axis=-1)` does: one pairwise
+ * leaf — sequential below 8 elements, 8 accumulators and a tail from 8 on. */
 int tk_build_tables(const float *centers, int dq, int dpb, int f_order, const void *q,
                     int q_is_f64, int64_t nq, double aux0, double aux1, int signd,
                     uint8_t *tables, void *shift, double *scale);
@@ -146,7 +149,8 @@ tk_index *tk_index_create(void);
 void tk_index_destroy(tk_index *ix);
 
 /* FastPQ state: centers (16, dq) float32, dims_per_block, sqrt_n_blocks
- * (fast_pq.py:99-102); f_order as in tk_build_tables; order = TK_ORDER_*. */
+ * (fast_pq.py:99-102); f_order as in tk_build_tables; order = TK_ORDER_*.
+ * dims_per_block 1 .. 32; an even number of blocks, at most 512 (float32 and float64 q_pq). */
 int tk_index_set_pq(tk_index *ix, const float *centers, int dq, int dpb, int f_order,
                     double sqrt_n_blocks, int order);
 /* active_centers (n_lists, d) float32 and their packed codes

@@ -478,7 +478,8 @@ int tko_distance_table_f64(const float *centers, int dq, int dpb, const double *
 }
 
 /* FastPQ.udistance_table (experimental, fast_pq.py:224-252).  np.square then a
- * sum over the last axis (sequential for dims_per_block < 8); shift = min;
+ * sum over the last axis: numpy's pairwise sum of the block's dims_per_block squares, one leaf
+ * (sequential below 8 elements, 8 accumulators and a tail from 8 on); shift = min;
  * scale = 255 / ((max * log(nb)) * sqrt(nb)), left to right as Python evaluates
  * fast_pq.py:248; the caller passes np.log(nb) and np.sqrt(nb) (float64).  The f32 path multiplies in f64 because
  * `scale` is a numpy float64 scalar. */
@@ -488,16 +489,16 @@ int tko_udistance_table_f32(const float *centers, int dq, int dpb, const float *
 {
     int M = dq / dpb;
     float *dists = (float *)malloc(sizeof(float) * 16 * (size_t)M);
-    if (!dists) return -1;
+    float sq[32];                       /* dims_per_block <= 32 */
+    if (!dists || dpb > 32) { free(dists); return -1; }
     float mn = INFINITY, mx = -INFINITY;
     for (int i = 0; i < 16; i++)
         for (int m = 0; m < M; m++) {
-            float s = 0.0f;
             for (int k = 0; k < dpb; k++) {
                 float df = centers[i * (i64)dq + m * dpb + k] - q[m * dpb + k];
-                float sq = df * df;
-                s += sq;
+                sq[k] = df * df;
             }
+            float s = pairwise_f32(sq, dpb);
             dists[i * M + m] = s;
             if (s < mn) mn = s;
         }
@@ -521,16 +522,16 @@ int tko_udistance_table_f64(const float *centers, int dq, int dpb, const double 
 {
     int M = dq / dpb;
     double *dists = (double *)malloc(sizeof(double) * 16 * (size_t)M);
-    if (!dists) return -1;
+    double sq[32];                      /* dims_per_block <= 32 */
+    if (!dists || dpb > 32) { free(dists); return -1; }
     double mn = INFINITY, mx = -INFINITY;
     for (int i = 0; i < 16; i++)
         for (int m = 0; m < M; m++) {
-            double s = 0.0;
             for (int k = 0; k < dpb; k++) {
                 double df = (double)centers[i * (i64)dq + m * dpb + k] - q[m * dpb + k];
-                double sq = df * df;
-                s += sq;
+                sq[k] = df * df;
             }
+            double s = pairwise_f64(sq, dpb);
             dists[i * M + m] = s;
             if (s < mn) mn = s;
         }

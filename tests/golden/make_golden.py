@@ -12,6 +12,7 @@ Two compatibility shims are needed, neither touches reference sources:
   * numpy 2: `numpy.core._methods` alias for fast_pq.py:15.
 
     python tests/golden/make_golden.py            # (re)write tests/golden/*.npz
+    python tests/golden/make_golden.py --only-wide-tables      # only g5w_*.npz
 """
 import os
 import shutil
@@ -70,10 +71,56 @@ def save(name, **arrays):
     print(f"{name}: {os.path.getsize(path) / 1024:.1f} KiB")
 
 
+# ---- G5w: distance tables at widths FastPQ.fit never produces --------------------
+# (M, dims_per_block): wide blocks (einsum's group loop, the pairwise leaf of `.sum(axis=-1)`), and many blocks
+# (a mean over 4096+ entries; C- and F-ordered centres).  The file name of a case is WIDE_TABLES_NAME % (M, dpb).
+WIDE_TABLES = [(M, dpb) for dpb in (8, 16, 32) for M in (4, 12, 36)] + \
+              [(M, dpb) for dpb in (1, 2) for M in (256, 258, 260, 472, 474, 512)]
+WIDE_TABLES_NAME = "g5w_tables_m%d_b%d.npz"
+
+
+def make_wide_tables(tk):
+    """The reference's distance_table / udistance_table for a FastPQ whose codebook is set by hand (random centres,
+    assembled through the (M, 16, dpb) array as fit assembles its own: dims_per_block 1 leaves an F-ordered view),
+    float32 and float64 queries.  25 queries (5 scaled by 0.05) for the wide blocks, 8 (2 scaled) from 256 blocks on:
+    a table is 16 M bytes.  M = 258 and 474 are no multiple of the AVX build's 4-block padding: for those the
+    reference's own SSE padding (fast_pq.py:27, dpad = 2) is set on the imported module."""
+    import tinyknn.fast_pq as rfp
+    dpad0 = rfp.dpad
+    for M, dpb in WIDE_TABLES:
+        rng = np.random.default_rng(M * 37 + dpb)
+        dq = M * dpb
+        pq = tk.FastPQ(dpb)
+        pq.centers = rng.standard_normal((M, 16, dpb)).astype(np.float32).transpose(1, 0, 2).reshape(16, dq)
+        pq.sqrt_n_blocks = np.sqrt(M)
+        assert pq.centers.flags.c_contiguous == (dpb != 1)
+        nq, small = (25, 5) if M < 256 else (8, 2)
+        out = dict(centers=np.ascontiguousarray(pq.centers), f_order=np.int64(dpb == 1),
+                   sqrt_n_blocks=np.float64(pq.sqrt_n_blocks))
+        rfp.dpad = dpad0 if M % dpad0 == 0 else 2
+        try:
+            for tag, dtype in (("f32", np.float32), ("f64", np.float64)):
+                qs = rng.standard_normal((nq, dq)).astype(dtype)
+                qs[:small] *= 0.05
+                out[f"qs_{tag}"] = qs
+                for sign, fn in (("s", pq.distance_table), ("u", pq.udistance_table)):
+                    dts = [fn(q) for q in qs]
+                    assert all(dt.q.dtype == dtype and dt.q.shape == (dq,) for dt in dts)
+                    out[f"tables_{sign}_{tag}"] = np.array([dt.tables for dt in dts])
+                    out[f"shift_{sign}_{tag}"] = np.array([dt.mean for dt in dts])
+                    out[f"scale_{sign}_{tag}"] = np.array([dt.scale for dt in dts])
+                    assert out[f"shift_{sign}_{tag}"].dtype == dtype
+        finally:
+            rfp.dpad = dpad0
+        save(WIDE_TABLES_NAME % (M, dpb), **out)
+
+
 def main():
     only = set(sys.argv[2:]) if len(sys.argv) > 2 and sys.argv[1] == "--only-ivf" else None
     warnings.filterwarnings("ignore")
     tk = import_reference()
+    if sys.argv[1:2] == ["--only-wide-tables"]:
+        return make_wide_tables(tk)
     from tinyknn import _transform as rt
     from tinyknn._fast_pq import estimate_pq_sse, query_pq_sse, init_heap, insert, insert_is
     from tinyknn._fast_pq_avx import estimate_pq_avx, query_pq_avx
@@ -220,6 +267,7 @@ def main():
         out[f"sqrt_n_blocks_{ci}"] = np.float64(pq.sqrt_n_blocks)
     out["meta"] = np.array(meta, dtype=np.int64)
     save("g5_tables.npz", **out)
+    make_wide_tables(tk)
 
     make_ivf(tk, None, query_pq_avx, knn_brute1)
 

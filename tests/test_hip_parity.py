@@ -49,7 +49,7 @@ def test_estimate_golden(tk):
 
 
 @pytest.mark.parametrize("n,M", [(16, 2), (16, 4), (48, 6), (1024, 32), (1040, 52), (16 * 4097, 52),
-                                 (16 * 1000, 32), (16 * 333, 104)])
+                                 (16 * 1000, 32), (16 * 333, 104), (16 * 40, 258), (16 * 40, 512)])
 def test_estimate_vs_oracle(tk, oracle, n, M):
     rng = np.random.default_rng(n * 131 + M)
     codes = rng.integers(0, 16, size=(n, M)).astype(np.uint8)
@@ -237,8 +237,18 @@ def test_distance_tables_golden(tk):
 
 
 @pytest.mark.parametrize("M,dpb,is64", [(52, 2, False), (32, 2, True), (32, 2, False), (100, 1, False),
-                                        (6, 4, True), (200, 2, False), (12, 8, False)])
+                                        (6, 4, True), (200, 2, False), (12, 8, False),
+                                        # einsum's four-vector group loop (16 floats / 8 doubles on) and, unsigned,
+                                        # numpy's 8-accumulator leaf
+                                        (12, 8, True), (12, 16, False), (12, 16, True), (6, 32, False), (6, 32, True),
+                                        # either side of the kernel's M <= 256 paths (the reciprocal for e / M, the
+                                        # unrolled dims_per_block 2 body)
+                                        (256, 2, False), (258, 2, False), (258, 1, True), (260, 2, True),
+                                        # the limits: 472 = the last float64 width within 64 KiB of LDS per wave,
+                                        # 512 = the most blocks an index takes, in both query types
+                                        (472, 2, True), (512, 2, False), (512, 1, False), (512, 2, True)])
 def test_distance_tables_vs_oracle(tk, oracle, M, dpb, is64):
+    """(The oracle itself is held to the reference's tables at the wide and the many-block shapes by test_oracle_tables_cpu.py.)"""
     from tinyknn_amd.fast_pq import build_tables
     rng = np.random.default_rng(M * 7 + dpb)
     dq = M * dpb
@@ -248,8 +258,9 @@ def test_distance_tables_vs_oracle(tk, oracle, M, dpb, is64):
         pq.centers = np.asfortranarray(pq.centers)
     pq.dims_per_block = dpb
     pq.sqrt_n_blocks = np.sqrt(M)
-    qs = rng.standard_normal((200, dq)).astype(np.float64 if is64 else np.float32)
-    qs[:50] *= 0.05
+    nq = 200 if M < 256 else 40
+    qs = rng.standard_normal((nq, dq)).astype(np.float64 if is64 else np.float32)
+    qs[:nq // 4] *= 0.05
     for signed in (True, False):
         tables, shift, scale = build_tables(pq, qs, signed)
         for qi in range(len(qs)):

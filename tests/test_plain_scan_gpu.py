@@ -142,18 +142,20 @@ def test_automatic_mode_pauses_on_data_without_structure(tk):
 
 @pytest.mark.parametrize("d,metric", [(12, "euclidean"), (40, "angular"), (64, "angular"), (72, "euclidean"), (104, "angular")])
 def test_every_register_shape_of_the_plain_kernel(tk, d, metric):
-    """M = d / 2 blocks: 6, 20, 32, 36, 52 -> the guarded forms for P <= 8 / 16 / 26 block pairs and the
-    unguarded ones at P = 16 and P = 26, the latter two also with the table operand read from LDS.  Plain pinned on,
-    list-major: heap arrays (layout included) and ids equal to the exact kernel's, with small and
-    default heaps."""
+    """M blocks of 2 dims, unrotated (d padded to a multiple of 8: 12 -> 16): 8, 20, 32, 36, 52 -> the guarded forms
+    for P <= 8 / 16 / 26 block pairs and the unguarded ones at P = 16 and P = 26, the latter two also with the table
+    operand read from LDS.  Plain pinned on, list-major: heap arrays (layout included) and ids equal to the exact
+    kernel's, with small and default heaps.  (FastPQ(2) alone rotates these inputs down to 64 dims: M = 32 from
+    d = 64 on, and the guarded 26-pair form never ran.)"""
     from tinyknn_amd import IVF, FastPQ
     np.random.seed(d)
     n, nq, n_lists = 30000, 600, 60
     cent = np.random.randn(80, d)
     X = (cent[np.random.randint(80, size=n)] + 0.5 * np.random.randn(n, d)).astype(np.float32)
     qs = (cent[np.random.randint(80, size=nq)] + 0.5 * np.random.randn(nq, d)).astype(np.float32)
-    ivf = IVF(metric, n_lists, FastPQ(2))
+    ivf = IVF(metric, n_lists, FastPQ(2, rotate_dim=None))
     ivf.fit(X[:10000]).build(X, n_probes=1)
+    assert ivf.pq.R is None and ivf.pq.centers.shape[1] // 2 == {12: 8, 40: 20, 64: 32, 72: 36, 104: 52}[d]
     qn, qp = ivf._prepare(qs.copy())
     dev = ivf.device_index()
     dev.set_scan_mode(2)

@@ -230,8 +230,7 @@ extern "C" int tk_build_tables(const float *centers, int dq, int dpb, int f_orde
     ARGCHECK(nq >= 0, "nq");
     const int M = dq / dpb;
     const size_t esz = q_is_f64 ? 8 : 4;
-    ARGCHECK(((size_t)16 * M + 640) * esz <= 64 * 1024 && 16 * M <= 8192,
-             "too many blocks for the LDS table");
+    ARGCHECK(M <= TK_TABLES_MAX_BLOCKS, "too many blocks for the LDS table (at most 512)");
     if (nq == 0) return TK_OK;
     Scratch &S = scratch();
     std::lock_guard<std::mutex> lk(S.mu);
@@ -243,8 +242,9 @@ extern "C" int tk_build_tables(const float *centers, int dq, int dpb, int f_orde
     TRY(S.scale.ensure((size_t)nq * 8));
     HIPCHECK(hipMemcpyAsync(S.centers.p, centers, (size_t)16 * dq * 4, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(S.q.p, q, (size_t)nq * dq * esz, hipMemcpyHostToDevice, st));
-    tk_launch_build_tables(S.centers.as<float>(), dq, dpb, f_order, S.q.p, q_is_f64, nq, aux0, aux1,
-                           signd, S.tabs8.as<uint8_t>(), S.shift.p, S.scale.as<double>(), st);
+    if (tk_launch_build_tables(S.centers.as<float>(), dq, dpb, f_order, S.q.p, q_is_f64, nq, aux0, aux1,
+                               signd, S.tabs8.as<uint8_t>(), S.shift.p, S.scale.as<double>(), st) != 0)
+        return fail(TK_ERR_HIP, "hipFuncSetAttribute(LDS size) failed");
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(tables, S.tabs8.p, (size_t)nq * M * 16, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(shift, S.shift.p, (size_t)nq * esz, hipMemcpyDeviceToHost, st));

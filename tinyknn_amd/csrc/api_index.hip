@@ -111,7 +111,7 @@ extern "C" int tk_index_set_pq(tk_index *ix, const float *centers, int dq, int d
     ARGCHECK(ix, "null index");
     ARGCHECK(dpb >= 1 && dpb <= 32 && dq % dpb == 0, "dq/dpb");
     ARGCHECK((dq / dpb) % 2 == 0, "number of blocks must be even");
-    ARGCHECK(dq / dpb <= 512, "at most 512 blocks");
+    ARGCHECK(dq / dpb <= TK_TABLES_MAX_BLOCKS, "at most 512 blocks");
     ARGCHECK(order == TK_ORDER_SSE || order == TK_ORDER_AVX, "order");
     TRY(ix->pq_centers.ensure((size_t)16 * dq * 4));
     HIPCHECK(hipMemcpy(ix->pq_centers.p, centers, (size_t)16 * dq * 4, hipMemcpyHostToDevice));
@@ -738,9 +738,10 @@ int stage_tables(tk_index *ix, Work &w, const void *qpq_dev, int qpq_f64, int64_
         ex.c_chunks = (int)ix->center_chunks;
         ex.c_nq = nq;
     }
-    tk_launch_build_tables(ix->pq_centers.as<float>(), ix->dq, ix->dpb, ix->f_order, qpq_dev,
-                           qpq_f64, nq, ix->sqrt_nb, 0.0, 1, w.tables.as<uint8_t>() + (size_t)row0 * ix->M * 16, w.shift.p,
-                           w.scale.as<double>(), st, qpq2, &ex);
+    if (tk_launch_build_tables(ix->pq_centers.as<float>(), ix->dq, ix->dpb, ix->f_order, qpq_dev,
+                               qpq_f64, nq, ix->sqrt_nb, 0.0, 1, w.tables.as<uint8_t>() + (size_t)row0 * ix->M * 16, w.shift.p,
+                               w.scale.as<double>(), st, qpq2, &ex) != 0)
+        return fail(TK_ERR_HIP, "hipFuncSetAttribute(LDS size) failed");
     TRY(pf.mark(st));
     return TK_OK;
 }

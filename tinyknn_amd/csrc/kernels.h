@@ -272,10 +272,15 @@ struct TkTablesExtra {
     int c_chunks = 0;
     int64_t c_nq = 0;
 };
-void tk_launch_build_tables(const float *centers, int dq, int dpb, int f_order, const void *q,
-                            int q_is_f64, int64_t nq, double aux0, double aux1, int signd,
-                            uint8_t *tables, void *shift, double *scale, hipStream_t s, TkSecond q2 = TkSecond(),
-                            const TkTablesExtra *extra = nullptr);
+// a wave's LDS region (16 M distances + 64 x 8 accumulators + 128 tree nodes) at the 512 blocks tk_index_set_pq
+// admits, in double: what the double instantiations of build_tables_kernel are allowed to ask for
+#define TK_TABLES_MAX_BLOCKS 512
+#define TK_TABLES_LDS_MAX ((16 * TK_TABLES_MAX_BLOCKS + 64 * 8 + 128) * 8)
+// (0, or -1 where the double kernels could not be allowed their LDS: nothing was launched)
+int tk_launch_build_tables(const float *centers, int dq, int dpb, int f_order, const void *q,
+                           int q_is_f64, int64_t nq, double aux0, double aux1, int signd,
+                           uint8_t *tables, void *shift, double *scale, hipStream_t s, TkSecond q2 = TkSecond(),
+                           const TkTablesExtra *extra = nullptr);
 
 // Exact rescoring + ascending top-k.
 // cand: (nq, R) int64 candidate ids (heap order).  strip: drop -1 entries first

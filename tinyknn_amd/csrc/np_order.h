@@ -73,3 +73,27 @@ __device__ __forceinline__ T einsum_selfdot_fn(F f, int n)
     if (L == 4) return (acc[0] + acc[1]) + (acc[2 % L] + acc[3 % L]);
     return acc[0] + acc[1 % L];
 }
+
+// np.add.reduce over a contiguous run of n <= 128 elements a[k] = f(k) — one leaf of numpy's pairwise sum
+// (loops_utils.h.src, @TYPE@_pairwise_sum): sequential below 8 elements; from 8 on, 8 accumulators over the whole
+// groups of 8, combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the tail added one by one
+template <typename T, typename F>
+__device__ __forceinline__ T pairwise_leaf_fn(F f, int n)
+{
+    if (n < 8) {
+        T res = 0;
+        for (int i = 0; i < n; i++) res += f(i);
+        return res;
+    }
+    T r[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) r[j] = f(j);
+    int i = 8;
+    for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) r[j] += f(i + j);
+    }
+    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; i++) res += f(i);
+    return res;
+}

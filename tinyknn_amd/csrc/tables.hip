@@ -161,13 +161,11 @@ __global__ __launch_bounds__(256) void build_tables_kernel(
             const T *qp = q + m * dpb;
             v = einsum_selfdot_fn<T>([&](int k) { return (T)cp[k] - qp[k]; }, dpb);
         } else {
-            // np.square(centers - q).reshape(16, nb, dpb).sum(-1): sequential adds
-            v = 0;
-            for (int k = 0; k < dpb; k++) {
-                T df = (T)centers[(int64_t)i * dq + m * dpb + k] - q[m * dpb + k];
-                T sq = df * df;
-                v += sq;
-            }
+            // np.square(centers - q).reshape(16, nb, dpb).sum(-1): a block's squares are one leaf of numpy's
+            // pairwise sum (dpb <= 32)
+            const float *cp = centers + (int64_t)i * dq + m * dpb;
+            const T *qp = q + m * dpb;
+            v = pairwise_leaf_fn<T>([&](int k) { const T df = (T)cp[k] - qp[k]; return df * df; }, dpb);
         }
         dists[f_order ? (m * 16 + i) : e] = v;
     }
@@ -304,12 +302,12 @@ __global__ __launch_bounds__(256) void build_tables_kernel(
     }
 }
 
-void tk_launch_build_tables(const float *centers, int dq, int dpb, int f_order, const void *q,
-                            int q_is_f64, int64_t nq, double aux0, double aux1, int signd,
-                            uint8_t *tables, void *shift, double *scale, hipStream_t s, TkSecond q2,
-                            const TkTablesExtra *extra)
+int tk_launch_build_tables(const float *centers, int dq, int dpb, int f_order, const void *q,
+                           int q_is_f64, int64_t nq, double aux0, double aux1, int signd,
+                           uint8_t *tables, void *shift, double *scale, hipStream_t s, TkSecond q2,
+                           const TkTablesExtra *extra)
 {
-    if (nq == 0) return;
+    if (nq == 0) return 0;
     TkTablesExtra ex;
     if (extra) ex = *extra;
     const int M = dq / dpb;
@@ -321,6 +319,17 @@ void tk_launch_build_tables(const float *centers, int dq, int dpb, int f_order, 
     int waves = 64 * 1024 / wave_lds;
     waves = waves < 1 ? 1 : (waves > 4 ? 4 : waves);
     size_t lds = (size_t)waves * wave_lds;
+    // float64 tables of 474 .. 512 blocks: one wave's region is past 64 KiB of dynamic LDS, which a kernel has to be
+    // allowed to ask for (as build.hip, heap.hip and brute.hip do for theirs).  TK_TABLES_LDS_MAX = the region of
+    // TK_TABLES_MAX_BLOCKS blocks in double
+    static bool attr_set = false;
+    if (q_is_f64 && !attr_set) {
+        const void *fns[] = {(const void *)build_tables_kernel<double, true>, (const void *)build_tables_kernel<double, false>};
+        for (const void *f : fns)
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, TK_TABLES_LDS_MAX) != hipSuccess)
+                return -1;
+        attr_set = true;
+    }
     dim3 grid((unsigned)((nq + waves - 1) / waves)), block(64 * waves);
     const int pdpb = dpb;
     if (q_is_f64) {
@@ -345,4 +354,5 @@ void tk_launch_build_tables(const float *centers, int dq, int dpb, int f_order, 
                                (float *)shift, scale, nq, wave_lds, pw,
                                (const float *)q2.b, q2.n_a, ex);
     }
+    return 0;
 }
