@@ -308,6 +308,26 @@ int tk_index_set_plain_scan(tk_index *ix, int mode);
  * re-scan, sum over the plain units of the list's chunk pairs, state of mode 0 (0 probe next,
  * 1 waiting for the probe's count, 2 on, 3 paused), batches left of the pause. */
 int tk_index_plain_stats(tk_index *ix, int64_t *out8);
+/* Which heap replay the last batch enqueued took for its probed lists (read-only, nothing is waited for; with
+ * batches in flight: the last one whose replay has been launched).  out4 = the form (below; -1 before the first
+ * batch), 1 where the lane replay ran lazy (TK_OPT_REPLAY_LAZY), 1 where the register heap ran on value8 << 24 |
+ * label24 entries (TK_OPT_LABELS24), the twin table width the TWIN form used (0 for every other form).  Results
+ * never depend on the form; the tests of one form assert that their batch took it.
+ * It is the form the dispatch CHOSE: the launcher of the lane replay would still drop a twin table that came without
+ * its arrays or with uniform slots (no list replay passes either).  A call that the library splits into sub-batches
+ * reports its last sub-batch alone: a short tail may have taken TK_REPLAY_PAIR where the others did not. */
+#define TK_REPLAY_PAIR 0            /* register heap, one query per wave (small batches, heap mode 3) */
+#define TK_REPLAY_LANES 1           /* lane per query, distinct labels */
+#define TK_REPLAY_PACKED_DISTINCT 2 /* packed wave kernel, distinct labels */
+#define TK_REPLAY_LANES_TWIN 3      /* lane per query, labels that repeat: duplicate test from the twin table */
+#define TK_REPLAY_LANES_DEDUPE 4    /* lane per query, labels that repeat: duplicate test on a hash set of the labels */
+#define TK_REPLAY_PACKED 5          /* packed wave kernel, duplicate test for every query */
+#define TK_REPLAY_GENERAL 6         /* general wave kernel (heap mode 1, rows too long for position entries) */
+int tk_index_last_replay(tk_index *ix, int64_t *out4);
+/* The two buckets (0..63, never equal) in which the lane replay's hash set may keep `label`: four labels per
+ * bucket, four more in a stash, and a lane whose label finds all of them taken falls back to a scan of its heap's
+ * labels.  The kernel's own function (no device needed): what a test draws colliding labels from. */
+int tk_label_buckets(uint32_t label, int *b1, int *b2);
 /* Per-index options (no process-wide state: the reference's entry points carry none either,
  * _fast_pq.pyx:101-307 are nogil and re-entrant).  Results never depend on an option; they exist for
  * A/B measurements and for the tests.

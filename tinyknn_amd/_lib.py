@@ -35,6 +35,9 @@ _f64p = C.POINTER(C.c_double)
 # tk_index_set_option
 OPT_SCAN_FORM, OPT_RESCORE_FORM, OPT_PLAIN_LIMIT, OPT_REPLAY_LAZY, OPT_REPLAY_COUNT, OPT_REPLAY_TWIN, OPT_TWIN_VOUCH = 1, 2, 3, 4, 5, 6, 7
 OPT_PAIR_NQ, OPT_LABELS24 = 8, 9
+# tk_index_last_replay: the forms of a batch's heap replay (TK_REPLAY_*)
+REPLAY_PAIR, REPLAY_LANES, REPLAY_PACKED_DISTINCT, REPLAY_LANES_TWIN, REPLAY_LANES_DEDUPE, REPLAY_PACKED, REPLAY_GENERAL = range(7)
+REPLAY_NAMES = ("pair", "lanes", "packed_distinct", "lanes_twin", "lanes_dedupe", "packed", "general")
 
 SIGNATURES = {
     "tk_last_error": (C.c_char_p, []),
@@ -203,6 +206,8 @@ SIGNATURES = {
     "tk_index_set_plain_scan": (C.c_int, [C.c_void_p, C.c_int]),
     "tk_index_quiesce": (C.c_int, [C.c_void_p]),
     "tk_index_plain_stats": (C.c_int, [C.c_void_p, _i64p]),
+    "tk_index_last_replay": (C.c_int, [C.c_void_p, _i64p]),
+    "tk_label_buckets": (C.c_int, [C.c_uint32, _i32p, _i32p]),
     "tk_index_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "tk_index_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "tk_index_last_profile": (C.c_int, [C.c_void_p, _f32p, _f64p, _i32p]),

@@ -1100,14 +1100,15 @@ static TkReplayJob list_replay_job(const tk_index *ix, Work &w, int64_t q0, int6
 }
 
 // The forms of a batch's heap replay (heap.hip).  Every form but General starts from fresh heaps on packed entries.
+// (tk_index_last_replay reports them: the values are the header's TK_REPLAY_*)
 enum class Replay {
-    Pair,            // register heap, one query per wave (pair_replay: small batches, heap_mode 3)
-    Lanes,           // lane per query, distinct labels
-    PackedDistinct,  // packed wave kernel, distinct labels (heap_mode 2, heaps above TK_LANES_MAX_R)
-    LanesTwin,       // lane per query, labels that repeat: the duplicate test from the twin table
-    LanesDedupe,     // lane per query, labels that repeat: the duplicate test on int32 labels
-    Packed,          // packed wave kernel, the duplicate test for every query
-    General,         // general wave kernel (heap_mode 1, or rows too long for position entries)
+    Pair = TK_REPLAY_PAIR,                      // register heap, one query per wave (pair_replay: small batches, heap_mode 3)
+    Lanes = TK_REPLAY_LANES,                    // lane per query, distinct labels
+    PackedDistinct = TK_REPLAY_PACKED_DISTINCT, // packed wave kernel, distinct labels (heap_mode 2, heaps above TK_LANES_MAX_R)
+    LanesTwin = TK_REPLAY_LANES_TWIN,           // lane per query, labels that repeat: the duplicate test from the twin table
+    LanesDedupe = TK_REPLAY_LANES_DEDUPE,       // lane per query, labels that repeat: the duplicate test on int32 labels
+    Packed = TK_REPLAY_PACKED,                  // packed wave kernel, the duplicate test for every query
+    General = TK_REPLAY_GENERAL,                // general wave kernel (heap_mode 1, or rows too long for position entries)
 };
 
 // An unsharded `plain` batch is never PackedDistinct: plain_possible takes distinct labels only at heap_mode 0 with
@@ -1155,6 +1156,14 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     const double blocks_per_query = (double)p.S * (double)ix->total_chunks / (double)ix->n_lists;
     const int lazy = ix->opt_replay_lazy >= 0 ? ix->opt_replay_lazy
                                               : (blocks_per_query >= (twin_replay(ix, p) ? 40.0 : 8.0) * p.R);
+    // (tk_index_last_replay: what the tests of one form assert before they compare anything)
+    {
+        const bool lanes = form == Replay::Lanes || form == Replay::LanesTwin;
+        ix->last_replay[0] = (int64_t)form;
+        ix->last_replay[1] = lanes && lazy;
+        ix->last_replay[2] = form == Replay::Pair && pair_labels24(ix) != 0;
+        ix->last_replay[3] = form == Replay::LanesTwin ? ix->twin_w : 0;
+    }
     // 1. the main replay
     switch (form) {
     case Replay::Pair:
@@ -2154,6 +2163,26 @@ extern "C" int tk_index_plain_stats(tk_index *ix, int64_t *out8)
         out8[0] = tiles;
         out8[5] = cps;
     }
+    return TK_OK;
+}
+
+// Which replay the LAST batch enqueued took for its probed lists (stage_back; nothing is waited for): out4 = the form
+// (TK_REPLAY_*, -1 before the first batch), lane replay lazy, register heap on label24 entries, twin table width used.
+extern "C" int tk_index_last_replay(tk_index *ix, int64_t *out4)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix && out4, "null index / buffer");
+    for (int i = 0; i < 4; i++) out4[i] = ix->last_replay[i];
+    return TK_OK;
+}
+
+// The two buckets the lane replay's hash set keeps a label in (kernels.h: tk_label_bucket_pair, the one heap.hip's kernel calls)
+extern "C" int tk_label_buckets(uint32_t label, int *b1, int *b2)
+{
+    ARGCHECK(b1 && b2, "null buffer");
+    const TkBucketPair p = tk_label_bucket_pair(label);
+    *b1 = p.b1;
+    *b2 = p.b2;
     return TK_OK;
 }
 

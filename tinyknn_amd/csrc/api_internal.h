@@ -275,6 +275,7 @@ struct tk_index {
     size_t ev_used = 0;            // sets recorded since the last read
     int last_S = 0, last_R = 0, last_work = 0;
     int64_t last_nq = 0;
+    int64_t last_replay[4] = {-1, 0, 0, 0};    // tk_index_last_replay: form, lazy, label24 entries, twin width (stage_back)
 };
 
 // an allowed set (allow.hip): 16 bits per stored chunk in list-position order, for ONE layout of the lists

@@ -996,10 +996,8 @@ __global__ __launch_bounds__(256) void heap_replay_lanes_kernel(
                     // label, the emptier one takes it; a label that finds both full is only kept in
                     // LAB and switches its lane to the full scan (exactness never depends on the
                     // set: LAB always holds every slot's label).
-                    const uint32_t hh = label * 0x9E3779B1u;
-                    const int b1 = (int)(hh >> 26);
-                    int b2 = (int)((hh >> 18) & 63u);
-                    b2 = b2 == b1 ? (b1 ^ 1) : b2;
+                    const TkBucketPair lb = tk_label_bucket_pair(label);
+                    const int b1 = lb.b1, b2 = lb.b2;
                     const uint4 x1 = TB[b1 * LW + lane], x2 = TB[b2 * LW + lane];
                     dup = (x1.x == label) | (x1.y == label) | (x1.z == label) | (x1.w == label) |
                           (x2.x == label) | (x2.y == label) | (x2.z == label) | (x2.w == label) |
@@ -1015,10 +1013,8 @@ __global__ __launch_bounds__(256) void heap_replay_lanes_kernel(
                     const uint32_t gone = TK_LAB(low); // label leaving with the root
                     if (!dup) {
                         if (gone != 0xffffffffu) {     // out of its bucket (if it ever got into one)
-                            const uint32_t gh = gone * 0x9E3779B1u;
-                            const int g1 = (int)(gh >> 26);
-                            int g2 = (int)((gh >> 18) & 63u);
-                            g2 = g2 == g1 ? (g1 ^ 1) : g2;
+                            const TkBucketPair gb = tk_label_bucket_pair(gone);
+                            const int g1 = gb.b1, g2 = gb.b2;
                             const uint4 y1 = TB[g1 * LW + lane], y2 = TB[g2 * LW + lane];
                             const int p1 = y1.x == gone ? 0 : y1.y == gone ? 1 : y1.z == gone ? 2 : y1.w == gone ? 3 : -1;
                             const int p2 = y2.x == gone ? 0 : y2.y == gone ? 1 : y2.z == gone ? 2 : y2.w == gone ? 3 : -1;

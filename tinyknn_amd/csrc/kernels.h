@@ -202,6 +202,18 @@ struct TkTwins {
 // set of the labels in the heap, 64 KiB) the LDS budget is (2R+2)*256 + 64 KiB + 16 KiB + the
 // slot table
 #define TK_LANES_MAX_R_DEDUPE 149
+// ... the hash set's two candidate buckets (of 64, four labels each) of a label: THE definition — the kernel places,
+// finds and removes labels through it, tk_label_buckets exports it (the tests draw their colliding labels from there)
+// (forced inline, the pair by value: the kernel's instructions are then those of the hash written out in place)
+struct TkBucketPair { int b1, b2; };
+__host__ __device__ __forceinline__ TkBucketPair tk_label_bucket_pair(uint32_t label)
+{
+    const uint32_t hh = label * 0x9E3779B1u;
+    const int b1 = (int)(hh >> 26);
+    int b2 = (int)((hh >> 18) & 63u);
+    b2 = b2 == b1 ? (b1 ^ 1) : b2;
+    return TkBucketPair{b1, b2};
+}
 int tk_lanes_dedupe_fits(int R, int S);     // ... and the slot table of S probed lists fits too
 int tk_lanes_twin_bm_words(int64_t n_lists);
 int tk_lanes_twin_fits(int R, int S, int64_t n_lists);   // the TWIN form: heap columns + slot table + probe list + list bitmap

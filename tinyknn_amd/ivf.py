@@ -1186,6 +1186,16 @@ class DeviceIndex:
                     head_pair_records=int(o[3]), flagged_queries=int(o[4]), plain_unit_chunk_pairs=int(o[5]),
                     state=("probe", "wait", "on", "paused")[int(o[6]) & 3], pause_left=int(o[7]))
 
+    def last_replay(self):
+        """Which heap replay the last batch took for its probed lists (tk_index_last_replay; nothing is waited for):
+        form (_lib.REPLAY_*; -1 before the first batch) and its name, lane replay lazy, register heap on label24
+        entries, twin table width used."""
+        o = np.zeros(4, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_last_replay(self._h, _lib.ptr(o, _lib._i64p)))
+        form = int(o[0])
+        return dict(form=form, name=_lib.REPLAY_NAMES[form] if 0 <= form < len(_lib.REPLAY_NAMES) else None,
+                    lazy=int(o[1]), labels24=int(o[2]), twin_w=int(o[3]))
+
     def quiesce(self):
         """Wait for everything enqueued and forget its completion events (before a stream
         capture of the pipelined mode: tinyknn_hip.h, tk_index_quiesce)."""
