@@ -400,8 +400,9 @@ int tk_index_last_profile(tk_index *ix, float *ms8, double *scan_bytes, int *bat
 
 /* measurement plumbing (bench.py): GB/s of a kernel that only reads `bytes` of HBM, every byte
  * once with the flat scan's access pattern — the streaming-read ceiling of the box */
-/* out4 = insert rounds summed over the replay waves, the most rounds one wave ran, waves, 16-block segments walked,
- * since TK_OPT_REPLAY_COUNT was set / the last call (synchronises, zeroes) */
+/* out4 = insert rounds summed over the replay waves, the most rounds one wave ran, waves, and — summed over the
+ * waves — the refills of the per-lane rings (the form without a duplicate test) or the 16-block segments walked
+ * (the others), since TK_OPT_REPLAY_COUNT was set / the last call (synchronises, zeroes) */
 int tk_index_replay_stats(tk_index *ix, int64_t *out4);
 int tk_measure_read_bandwidth(int64_t bytes, int reps, double *gbps);
 /* ... and of a kernel that gathers n_gather random rows of row_bytes (16 .. 1024, a multiple of 16) out of

@@ -1381,7 +1381,7 @@ static int scan_blocks_pipelined(double est_units) { return est_units > 6.0e6 ? 
 // ... and of the plain kernel beside the other batches' kernels: what the pipelined batch runs out of is LDS SPACE
 //  — two paired lane replays, the coarse replay and 512 plain workgroups ask for more than the chip's
 // 41 MB, and whoever comes last waits.  The plain kernel is as fast on 256 workgroups as on 512 there (its waves wait
-// on latencies, not on each other), and with the lane replay's 8-block segments (heap.hip) everything fits: same
+// on latencies, not on each other), and with the lane replay's 8 staging rows per lane (heap.hip) everything fits: same
 // box, headline batch 25.4-25.8 M queries/s against 24.4-24.7 M (320 or 256; 192: 25.0; 512 with 8-block segments:
 // 24.0-25.4, bimodal).  Long launches keep 512: 100M x 128 loses 5 % on 320, build(n_probes=2) 4 %.
 // (256 against 320, seven runs each in turn on one box: 25.5-25.75 M every time against 25.4-25.6 M with one run
@@ -2188,7 +2188,8 @@ extern "C" int tk_label_buckets(uint32_t label, int *b1, int *b2)
 
 // TK_OPT_REPLAY_COUNT: what the lane replays of the probed lists did since the option was set / the last call
 // (synchronises; zeroes the counters): out4 = insert rounds summed over the waves, the most rounds any wave ran
-// (the kernel's critical path: a round is one dependent insert step of a wave), waves, 16-block segments walked.
+// (the kernel's critical path: a round is one dependent insert step of a wave), waves, and summed over the waves the
+// refills of the per-lane rings (form without a duplicate test) or the 16-block segments walked (the other forms).
 extern "C" int tk_index_replay_stats(tk_index *ix, int64_t *out4)
 {
     IXLOCK(ix);

@@ -553,6 +553,21 @@ void tk_launch_flat_top_one(const uint4 *dist, const uint8_t *mins, int chunks, 
 //     load; inside a segment lanes are decoupled: each walks to its next block with
 //     a byte below its bound, then all lanes with a pending candidate perform one
 //     insert together; a bound is refreshed when its block is done;
+//   * (without a duplicate test: !DEDUPE && !TWIN && !LAZY) the lanes do not walk segments in step — a wave that does
+//     pays, per segment, the LARGEST insert count among its 64 lanes: sum over segments of the maximum, 678 rounds per
+//     wave for ~460 inserts per query — but each keeps a RING of staged blocks of its own: a cursor into its row's
+//     block minima, a FIFO over its TK_RING_SLOTS rows ST[slot][lane], up to TK_RING_LOADS blocks in flight in
+//     registers.  Every TK_RING_T rounds (and whenever no lane has a pending row) the wave REFILLS: the blocks
+//     requested at the previous refill drop into the rings, each lane picks its next blocks whose minimum is below
+//     its bound of now and requests them.  A lane without a pending row pops its ring.  Why the heaps are the same:
+//       - a block whose minimum is >= a bound captured earlier is >= the bound at its own start (a bound only
+//         falls): the reference enters it, inserts nothing, and the bound does not move — leaving it out is a no-op;
+//       - the blocks that are staged are replayed in row order, each tested against the bound at its own start (a
+//         lane pops only when its block is done and its bound refreshed) with the same strict `<`, the same
+//         unconditional replace-root insert and the same sift;
+//       - lanes never shared state.
+//     (tests/test_ring_replay_lemma.py checks the first point on the reference's loop; scripts/sim_replay_rounds.py
+//     is the model of the rounds per wave.)
 //   * pad_fix_kernel has set the rows that pad a list's last chunk to the largest
 //     value beforehand (`pos < n`, _fast_pq_256.pyx:111), so there is no row mask
 //     and, with distinct labels, no slot cursor in the loop;
@@ -560,8 +575,14 @@ void tk_launch_flat_top_one(const uint4 *dist, const uint8_t *mins, int chunks, 
 //     tests 16 minima at once and touches only blocks that can contain a hit;
 //   * the top three heap levels (nodes 0..6) are kept in registers;
 //   * labels are resolved from the flat positions once, at the end.
-#ifndef TK_LANES_SEG
-#define TK_LANES_SEG 8      // blocks per staged segment of the lane replay's form without a duplicate test: 16 or 8
+// The form without a duplicate test (distinct labels, and the coarse replay of every index) stages its blocks in a
+// per-lane RING instead of segments the wave walks in step (see the head of heap_replay_lanes_kernel):
+#define TK_RING_SLOTS 8     // staging rows ST[slot][lane] of a lane's ring (the queue of block numbers below holds eight)
+#ifndef TK_RING_T
+#define TK_RING_T 4         // insert rounds between two refills of the rings
+#endif
+#ifndef TK_RING_LOADS
+#define TK_RING_LOADS 4     // blocks a lane requests per refill at most (uint4 registers in flight)
 #endif
 template <bool SIGNED>
 __device__ __forceinline__ int entry_val(uint32_t e)
@@ -718,8 +739,8 @@ __global__ __launch_bounds__(256) void heap_replay_lanes_kernel(
     // DEDUPE: slot table of the lane's query, SE[s][lane] = first flat chunk past slot s,
     // SB[s][lane] = label offset of slot s - 16 * its first flat chunk (label of row r of flat
     // chunk c in slot s = labels32[SB[s] + 16 c + r])
-    // (staging rows: none when LAZY, TK_LANES_SEG blocks without a duplicate test, 16 otherwise)
-    int *SE = (int *)(ST + (DEDUPE ? 16 : LAZY ? 0 : TWIN ? 16 : TK_LANES_SEG) * LW);
+    // (staging rows: none when LAZY, the TK_RING_SLOTS of a lane's ring without a duplicate test, 16 otherwise)
+    int *SE = (int *)(ST + (DEDUPE ? 16 : LAZY ? 0 : TWIN ? 16 : TK_RING_SLOTS) * LW);
     int *SB = SE + (size_t)S * LW;
     // TWIN: the probed lists of the lane's query, four to a uint4: PL[t / 4][lane]
     uint4 *PL = (uint4 *)(SB + (size_t)S * LW);
@@ -772,15 +793,14 @@ __global__ __launch_bounds__(256) void heap_replay_lanes_kernel(
     const int plain0 = (plain0_arr && valid) ? plain0_arr[qc] : 0x7fffffff;
     uint32_t b_plain = SIGNED ? 0x7fu : 0xffu;
     const uint4 *mrow = (const uint4 *)(mins + qc * cap_min);   // per-block minima, 16 per uint4
-    // Blocks per staged segment.  The staging rows are LDS SPACE, which is what the pipelined batch runs out of
-    // (DESIGN §3.6): the form without a duplicate test — every index with distinct labels, and the coarse stage of
-    // all — stages 8 blocks at a time (8 KB per wave instead of 16, 32 prefetch registers instead of 64, 86 VGPRs
-    // instead of 118; the minima still arrive 16 to a load, a pair of segments shares one).  Alone that replay is 9 %
-    // slower (twice the segments, a prefetch eight blocks ahead); with the plain kernel on 256 instead of 512
-    // workgroups beside it the batch's kernels fit the chip's LDS and the headline batch gains 4-5 % (25.4-25.8
-    // against 24.4-24.7 M queries/s, same box).  The TWIN form keeps 16 (replay-bound: 15.5 against 14.9 M).
-    constexpr int SEG = (LAZY || DEDUPE || TWIN) ? 16 : TK_LANES_SEG;
-    int nseg = (total + SEG - 1) / SEG;
+    // Blocks per staged segment (DEDUPE, TWIN, LAZY).  The staging rows are LDS SPACE, which is what the pipelined
+    // batch runs out of: the form without a duplicate test — every index with distinct labels, and the
+    // coarse stage of all — has 8 rows per lane (8 KB per wave instead of 16), as a ring (RING, below the segment
+    // loop's declarations); with the plain kernel on 256 instead of 512 workgroups beside it the batch's kernels fit
+    // the chip's LDS.  The TWIN form keeps 16-block segments (replay-bound: 15.5 against 14.9 M).
+    constexpr bool RING = !LAZY && !DEDUPE && !TWIN;
+    constexpr int SEG = 16;
+    int nseg = RING ? 0 : (total + SEG - 1) / SEG;
     int max_nseg = nseg;
     for (int o = LW / 2; o > 0; o >>= 1) {
         int other = __shfl_xor(max_nseg, o, 64);
@@ -833,7 +853,7 @@ __global__ __launch_bounds__(256) void heap_replay_lanes_kernel(
     uint4 nx[SEG];
     uint4 mins_nx = make_uint4(0, 0, 0, 0);
 #define TK_MINS_ROW16(g_) mrow[(g_) < last_m ? (g_) : (last_m > 0 ? last_m : 0)]
-#define TK_MINS_ROW(g_) TK_MINS_ROW16(SEG == 16 ? (g_) : (g_) >> 1)
+#define TK_MINS_ROW(g_) TK_MINS_ROW16(g_)
 #define TK_FETCH_BLOCKS(g_)                                                       \
     {                                                                             \
         _Pragma("unroll") for (int k = 0; k < SEG; k++) {                         \
@@ -850,13 +870,167 @@ __global__ __launch_bounds__(256) void heap_replay_lanes_kernel(
     // (500 of 6 250 per query at 100M x 128), each was a dependent trip to memory of its own.
     uint4 mins_n2 = make_uint4(0, 0, 0, 0), pre = make_uint4(0, 0, 0, 0), pre_n = make_uint4(0, 0, 0, 0);
     int pre_blk = -1, pre_n_blk = -1;
-    if (max_nseg > 0) {
+    if (!RING && max_nseg > 0) {
         mins_nx = TK_MINS_ROW(0);
         if (LAZY && max_nseg > 1) mins_n2 = TK_MINS_ROW(1);
         if (!LAZY) TK_FETCH_BLOCKS(0)
     }
     int rounds = 0;               // wave-uniform: iterations of the insert loop (each a dependent chain: roofline.replay)
-    for (int g = 0; g < max_nseg; g++) {
+    // `insert` below node j (3..6): children in LDS, branch-free per level — rows R and R+1 hold a value no entry
+    // exceeds, so children beyond the heap (clamped to R) are never taken
+    auto lds_levels = [&](int j, const uint32_t entry, const int v) {
+        bool first = true, go = true;
+        do {
+            const int l = 2 * j + 1;
+            const int lc = l < R ? l : R;
+            const uint32_t el = H[lc * LW + lane];
+            const uint32_t er = H[(lc + 1) * LW + lane];
+            const int vl = entry_val<SIGNED>(el), vr = entry_val<SIGNED>(er);
+            const bool cl = vl > v;                 // vals[l] > nxt_val
+            const int nvv = cl ? vl : v;
+            uint32_t ne = cl ? el : entry;
+            int nxt = cl ? l : j;
+            const bool cr = vr > nvv;               // vals[r] > nxt_val
+            ne = cr ? er : ne;
+            nxt = cr ? l + 1 : nxt;
+            if (first) {
+                h3 = j == 3 ? ne : h3; h4 = j == 4 ? ne : h4;
+                h5 = j == 5 ? ne : h5; h6 = j == 6 ? ne : h6;
+                first = false;
+            } else {
+                H[j * LW + lane] = ne;              // entry itself when nxt == j
+            }
+            go = nxt != j;
+            j = nxt;
+        } while (go);
+    };
+    // `insert`, _fast_pq.pyx:291-307, levels 0-2 (registers).  -> 0: the entry has its place; j = 3..6: the sift goes
+    // on below node j (lds_levels)
+    auto reg_levels = [&](const uint32_t entry, const int v) -> int {
+        // node 0, children 1 and 2
+        const int v1 = entry_val<SIGNED>(h1), v2 = entry_val<SIGNED>(h2);
+        const bool c1 = v1 > v;
+        const int nv = c1 ? v1 : v;
+        const bool c2 = v2 > nv;
+        h0 = c2 ? h2 : (c1 ? h1 : entry);
+        if (!(c1 | c2)) return 0;
+        // node 1 or 2, children (3,4) or (5,6)
+        const uint32_t a = c2 ? h5 : h3, b = c2 ? h6 : h4;
+        const int va = entry_val<SIGNED>(a), vb = entry_val<SIGNED>(b);
+        const bool ca = va > v;
+        const int nv1 = ca ? va : v;
+        const bool cb = vb > nv1;
+        const uint32_t ne1 = cb ? b : (ca ? a : entry);
+        if (c2) h2 = ne1; else h1 = ne1;
+        return (ca | cb) ? (c2 ? 5 : 3) + (cb ? 1 : 0) : 0;
+    };
+    // ---- RING: per-lane ring of staged blocks (the head of the kernel says why the heaps stay the same)
+    int refills = 0;              // wave-uniform: refills of the rings (TK_OPT_REPLAY_COUNT)
+    if constexpr (RING) {
+        const int nwin = (total + 15) >> 4;          // windows of 16 block minima in the lane's row
+        int win = -1;                                // the window the cursor is in
+        uint32_t wmask = 0;                          // its blocks still to pick: minimum below the bound when it was entered
+        uint4 m1 = make_uint4(0, 0, 0, 0), m2 = m1;  // minima of windows win + 1, win + 2, requested ahead
+        // (a wave without any row touches neither its rows nor their minima; a lane without rows beside others
+        // requests block 0 of its own row like them, and never looks at it)
+        const bool wave_rows = __builtin_amdgcn_ballot_w64(nwin > 0) != 0;
+        if (wave_rows) {
+            m1 = TK_MINS_ROW16(0);
+            m2 = TK_MINS_ROW16(1);
+        }
+        int head = 0, nst = 0, nfl = 0;              // ring: slot of the oldest staged block, blocks staged, blocks in flight
+        // block numbers of the staged and in-flight blocks, oldest first: 16-bit steps from the block before (a window
+        // that would put a step past 16 bits stages its first block whatever its minimum: a block nothing passes in)
+        uint64_t qlo = 0, qhi = 0;
+        int last_req = 0;                            // the block requested last
+        uint4 fl[TK_RING_LOADS];                     // blocks in flight: fl[0 .. nfl)
+#pragma unroll
+        for (int k = 0; k < TK_RING_LOADS; k++) fl[k] = make_uint4(0, 0, 0, 0);
+        uint32_t bits = 0;
+        uint4 dd = make_uint4(0, 0, 0, 0);
+        int cur = 0;                                 // the block popped last
+        // One pass of this loop = one refill and up to TK_RING_T rounds behind it.  (The refill is not a branch inside
+        // the round loop: what it requests is used at the head of the next pass and nowhere else, so each load keeps
+        // ONE register from request to ring store, and the only vmcnt wait is in front of the ring stores.)
+        while (wave_rows) {
+            // ---- refill.  The blocks requested by the previous one: into the ring
+            const bool more = nfl > 0 || wmask != 0 || win + 1 < nwin;
+            refills += __builtin_amdgcn_ballot_w64(more) != 0;
+#pragma unroll
+            for (int k = 0; k < TK_RING_LOADS; k++)
+                if (k < nfl) ST[((head + nst + k) & (TK_RING_SLOTS - 1)) * LW + lane] = fl[k];
+            nst += nfl;
+            nfl = 0;
+            // the cursor: at most two windows per refill (their minima are in registers; those requested here arrive
+            // while the rounds up to the next refill run)
+#pragma unroll
+            for (int a = 0; a < 2; a++) {   // (the second step only behind the first: wmask is unchanged otherwise)
+                if (wmask == 0 && win + 1 < nwin) {
+                    win++;
+                    const int kn = total - 16 * win;
+                    wmask = mask_lt16_swar<SIGNED>(a ? m2 : m1, bb) & (kn >= 16 ? 0xffffu : ((1u << kn) - 1u));
+                    if (16 * win - last_req > 0xffe0) wmask |= 1u;
+                }
+            }
+            // pick and request: the next blocks of the window whose minimum passes, into the free slots.  No branch
+            // around a load: every lane requests TK_RING_LOADS blocks and two rows of minima in every refill (a lane
+            // with nothing to pick: the block it requested last)
+            int room = TK_RING_SLOTS - nst;
+            room = room > TK_RING_LOADS ? TK_RING_LOADS : room;
+#pragma unroll
+            for (int k = 0; k < TK_RING_LOADS; k++) {
+                const bool take = k < room && wmask != 0;
+                const int blk = take ? 16 * win + __builtin_ctz(wmask) : last_req;
+                wmask &= take ? wmask - 1 : ~0u;
+                fl[k] = drow[blk < last_blk ? blk : last_blk];
+                const int p = nst + nfl;
+                const uint64_t step = (uint64_t)(uint32_t)(blk - last_req) << (16 * (p & 3));
+                qlo |= take && p < 4 ? step : 0;
+                qhi |= take && p >= 4 ? step : 0;
+                last_req = blk;
+                nfl += take;
+            }
+            m1 = TK_MINS_ROW16(win + 1);
+            m2 = TK_MINS_ROW16(win + 2);
+            // (what is in flight or still in a row: if nothing is, in any lane, the last blocks are in the rings)
+            const bool rest = __builtin_amdgcn_ballot_w64(nfl > 0 || wmask != 0 || win + 1 < nwin) != 0;
+            // ---- rounds
+            bool any = true;
+            for (int t = 0; rest ? t < TK_RING_T : true; t++) {
+                // a lane without a pending row pops its ring until a block has a row below the live bound (its block
+                // is done and its bound refreshed: the bound at the popped block's own start)
+                while (bits == 0 && nst > 0) {
+                    dd = ST[head * LW + lane];
+                    head = (head + 1) & (TK_RING_SLOTS - 1);
+                    nst--;
+                    cur += (int)((uint32_t)qlo & 0xffffu);
+                    qlo = (qlo >> 16) | (qhi << 48);
+                    qhi >>= 16;
+                    bits = mask_lt16_swar<SIGNED>(dd, bb);
+                }
+                any = __builtin_amdgcn_ballot_w64(bits != 0) != 0;
+                if (!any) break;          // every ring is empty: refill at once
+                rounds++;
+                if (bits) {   // one insert per lane with a pending candidate
+                    const int r = __builtin_ctz(bits);
+                    bits &= bits - 1;
+                    const uint32_t w = r < 4 ? dd.x : r < 8 ? dd.y : r < 12 ? dd.z : dd.w;
+                    const uint32_t by = (w >> (8 * (r & 3))) & 0xffu;
+                    const uint32_t entry = (by << 24) | (uint32_t)(16 * cur + r);
+                    const int v = entry_val<SIGNED>(entry);
+                    const int j = reg_levels(entry, v);
+                    if (j) lds_levels(j, entry, v);
+                    if (bits == 0) {  // refresh after the block, :123
+                        bound = h0 >> 24;
+                        bb = bound_bytes<SIGNED>(bound);
+                        b_plain = cur < plain0 ? bound : b_plain;
+                    }
+                }
+            }
+            if (!rest) break;             // no pending row, staged block, request in flight or row left in any lane
+        }
+    }
+    for (int g = 0; !RING && g < max_nseg; g++) {
         if (!LAZY) {
 #pragma unroll
             for (int k = 0; k < SEG; k++) ST[k * LW + lane] = nx[k];
@@ -888,7 +1062,6 @@ __global__ __launch_bounds__(256) void heap_replay_lanes_kernel(
         // blocks whose minimum is below the bound at segment start: a superset of the
         // blocks the reference enters (the bound only decreases)
         uint32_t hit = mask_lt16_swar<SIGNED>(mins_cur, bb);
-        if (SEG == 8) hit = (hit >> (8 * (g & 1))) & 0xffu;       // (this segment's half of the 16 minima)
         hit &= kmax >= SEG ? ((1u << SEG) - 1u) : ((1u << kmax) - 1u);
         uint32_t bits = 0;
         uint4 dd = make_uint4(0, 0, 0, 0);
@@ -941,34 +1114,6 @@ __global__ __launch_bounds__(256) void heap_replay_lanes_kernel(
         // form's next passing block ahead of the insert in the same manner was measured and is not kept (100M x 128:
         // 6.27 M queries/s with, 6.27 without, same box).
         constexpr bool EARLY = TWIN && !LAZY;
-        // `insert` below node j (3..6): children in LDS, branch-free per level — rows R and R+1 hold a value no entry
-        // exceeds, so children beyond the heap (clamped to R) are never taken
-        auto lds_levels = [&](int j, const uint32_t entry, const int v) {
-            bool first = true, go = true;
-            do {
-                const int l = 2 * j + 1;
-                const int lc = l < R ? l : R;
-                const uint32_t el = H[lc * LW + lane];
-                const uint32_t er = H[(lc + 1) * LW + lane];
-                const int vl = entry_val<SIGNED>(el), vr = entry_val<SIGNED>(er);
-                const bool cl = vl > v;                 // vals[l] > nxt_val
-                const int nvv = cl ? vl : v;
-                uint32_t ne = cl ? el : entry;
-                int nxt = cl ? l : j;
-                const bool cr = vr > nvv;               // vals[r] > nxt_val
-                ne = cr ? er : ne;
-                nxt = cr ? l + 1 : nxt;
-                if (first) {
-                    h3 = j == 3 ? ne : h3; h4 = j == 4 ? ne : h4;
-                    h5 = j == 5 ? ne : h5; h6 = j == 6 ? ne : h6;
-                    first = false;
-                } else {
-                    H[j * LW + lane] = ne;              // entry itself when nxt == j
-                }
-                go = nxt != j;
-                j = nxt;
-            } while (go);
-        };
         for (;;) {
             if (!EARLY) {
                 TK_ADVANCE()
@@ -1083,29 +1228,10 @@ __global__ __launch_bounds__(256) void heap_replay_lanes_kernel(
                     const int root = entry_val<SIGNED>(h0);
                     f = root < f ? root : f;
                 }
-                // insert, _fast_pq.pyx:291-307.  Levels 0-2 in registers, the rest in
-                // LDS, branch-free per level: rows R and R+1 hold a value no entry
-                // exceeds, so children beyond the heap (clamped to R) are never taken.
-                if (!dup)
-                {   // node 0, children 1 and 2
-                    const int v1 = entry_val<SIGNED>(h1), v2 = entry_val<SIGNED>(h2);
-                    const bool c1 = v1 > v;
-                    const int nv = c1 ? v1 : v;
-                    const bool c2 = v2 > nv;
-                    h0 = c2 ? h2 : (c1 ? h1 : entry);
-                    if (c1 | c2) {   // node 1 or 2, children (3,4) or (5,6)
-                        const uint32_t a = c2 ? h5 : h3, b = c2 ? h6 : h4;
-                        const int va = entry_val<SIGNED>(a), vb = entry_val<SIGNED>(b);
-                        const bool ca = va > v;
-                        const int nv1 = ca ? va : v;
-                        const bool cb = vb > nv1;
-                        const uint32_t ne1 = cb ? b : (ca ? a : entry);
-                        if (c2) h2 = ne1; else h1 = ne1;
-                        if (ca | cb) {
-                            j = (c2 ? 5 : 3) + (cb ? 1 : 0);
-                            if (!EARLY) lds_levels(j, entry, v);        // (EARLY: behind the look-ahead below)
-                        }
-                    }
+                // insert, _fast_pq.pyx:291-307: levels 0-2 in registers, the rest in LDS
+                if (!dup) {
+                    j = reg_levels(entry, v);
+                    if (j && !EARLY) lds_levels(j, entry, v);           // (EARLY: behind the look-ahead below)
                 }
                 // refresh after the block, :123 (EARLY: the new root is known behind the register levels — the bound
                 // does not wait for the levels below)
@@ -1127,11 +1253,11 @@ __global__ __launch_bounds__(256) void heap_replay_lanes_kernel(
 #undef TK_FETCH_BLOCKS
 #undef TK_MINS_ROW
 #undef TK_MINS_ROW16
-    if (dbg && lane == 0) {       // TK_OPT_REPLAY_COUNT: [0] += rounds, [1] = max rounds of a wave, [2] += waves, [3] += segments
+    if (dbg && lane == 0) {       // TK_OPT_REPLAY_COUNT: [0] += rounds, [1] = max rounds of a wave, [2] += waves, [3] += segments (RING: refills)
         atomicAdd(&dbg[0], (unsigned long long)rounds);
         atomicMax(&dbg[1], (unsigned long long)rounds);
         atomicAdd(&dbg[2], 1ull);
-        atomicAdd(&dbg[3], (unsigned long long)max_nseg);
+        atomicAdd(&dbg[3], (unsigned long long)(RING ? refills : max_nseg));
     }
     // registers back to their heap rows
     if (R > 0) H[0 * LW + lane] = h0;
@@ -1403,8 +1529,8 @@ int tk_launch_heap_replay_lanes(const TkReplayJob &j, const TkLanesOpts &o, hipS
     const int LWr = dedupe ? 32 : 64;
     // heap columns (+ label slots) + one staged segment (16 blocks x LW lanes x 16 B; the next one
     // waits in registers), scaled to the columns in use
-    // (staging rows: none when LAZY, TK_LANES_SEG blocks without a duplicate test, 16 otherwise)
-    const size_t st_rows = dedupe ? (size_t)16384 : o.lazy ? 0 : twin ? (size_t)16384 : (size_t)1024 * TK_LANES_SEG;
+    // (staging rows: none when LAZY, the TK_RING_SLOTS of a lane's ring without a duplicate test, 16 otherwise)
+    const size_t st_rows = dedupe ? (size_t)16384 : o.lazy ? 0 : twin ? (size_t)16384 : (size_t)1024 * TK_RING_SLOTS;
     const size_t lds = twin ? tk_lanes_twin_lds(R, S, tw.bm_words) + st_rows
                             : tk_lanes_fixed_lds(R, S, dedupe) * LWr / 64 + st_rows * LWr / 64;
     static bool attr_set = false;

@@ -1131,7 +1131,8 @@ class DeviceIndex:
     def replay_stats(self):
         """What the lane replays of the probed lists did since set_option(OPT_REPLAY_COUNT, 1) / the last call
         (tk_index_replay_stats; synchronises): insert rounds over all waves, the most one wave ran, waves,
-        16-block segments walked."""
+        and under `segments` the refills of the per-lane rings, summed over the waves (the lane replay without a
+        duplicate test; the forms with one: 16-block segments walked)."""
         o = np.zeros(4, dtype=np.int64)
         _lib.check(_lib.lib().tk_index_replay_stats(self._h, _lib.ptr(o, _lib._i64p)))
         return dict(rounds=int(o[0]), max_rounds_of_a_wave=int(o[1]), waves=int(o[2]), segments=int(o[3]))
