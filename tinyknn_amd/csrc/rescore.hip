@@ -176,56 +176,88 @@ __global__ __launch_bounds__(128) void rescore_dist_kernel(const TX *__restrict_
 
 // A staged row travels and rests as pieces of four elements: 16 bytes of float32, 8 bytes of IEEE half (GloVe's
 // 200-byte half rows have no whole number of 16-byte pieces).
+// (the compiler's own vector types: they can sit behind an LDS-qualified pointer on the host pass too)
+typedef float float2_t __attribute__((ext_vector_type(2)));
+typedef float float4_t __attribute__((ext_vector_type(4)));
+typedef unsigned uint2_t __attribute__((ext_vector_type(2)));
 template <typename TY> struct RowPiece;
-template <> struct RowPiece<float> { typedef float4 type; };
-template <> struct RowPiece<_Float16> { typedef uint2 type; };
+template <> struct RowPiece<float> { typedef float4_t type; };
+template <> struct RowPiece<_Float16> { typedef uint2_t type; };
 
-__device__ __forceinline__ void unpack4(const float4 p, float *o)
-{
-    o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = p.w;
-}
+// The half of a piece that one lane of a pair sums: elements 2s, 2s + 1 — 8 bytes of a float32 piece, 4 of a half one.
+template <typename P> struct HalfPiece;
+template <> struct HalfPiece<float4_t> { typedef float2_t type; };
+template <> struct HalfPiece<uint2_t> { typedef unsigned type; };
 
-__device__ __forceinline__ void unpack4(const uint2 p, float *o)    // float(half): exact
+__device__ __forceinline__ float2_t widen2(const float2_t p) { return p; }
+
+__device__ __forceinline__ float2_t widen2(const unsigned p)    // float(half): exact
 {
     typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-    const half2_t lo = __builtin_bit_cast(half2_t, p.x), hi = __builtin_bit_cast(half2_t, p.y);
-    o[0] = (float)lo.x; o[1] = (float)lo.y; o[2] = (float)hi.x; o[3] = (float)hi.y;
+    const half2_t h = __builtin_bit_cast(half2_t, p);
+    return float2_t{(float)h.x, (float)h.y};
 }
 
-// sqdist_row<float, float> (after float(y) for half rows) for a row held in LDS as pieces P, read whole: same
-// operations in the same order (un-fused, four lane-accumulators, groups folded 3,2,1,0, pairwise horizontal add).
-template <typename P>
-__device__ __forceinline__ float sqdist_row_lds(const P *__restrict__ y, const float *xs, int d)
+// sqdist_row<float, float> (after float(y) for half rows) for a row held in LDS as pieces, summed by TWO lanes: the
+// four lane-accumulators of sqdist_row never meet before the last line, so lane s of the pair carries acc[2s] and
+// acc[2s + 1] as one 2-vector (yp, xp: the row and the query from element 2s on, so piece j is yp[2j] / xp[2j]) and
+// returns their sum, acc[2s] + acc[2s + 1]; the caller adds the partner's.  Per accumulator the operations and their
+// order are sqdist_row's (un-fused subtract, multiply, add; groups of four pieces folded 3,2,1,0; whole pieces in the
+// tail), here two at a time (v_pk_add_f32 / v_pk_mul_f32, which round as the scalar forms do; -ffp-contract=off).
+template <typename H>
+__device__ __forceinline__ float sqdist_row_lds(const H *__restrict__ yp, const float2_t *xp, int d4)
 {
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    int i = 0;
-    for (; d - i >= 16; i += 16) {
-        float yv[16];
-        unpack4(y[(i >> 2)], yv);
-        unpack4(y[(i >> 2) + 1], yv + 4);
-        unpack4(y[(i >> 2) + 2], yv + 8);
-        unpack4(y[(i >> 2) + 3], yv + 12);
-        float df[16];
+    float2_t acc = {0.f, 0.f};
+    int j = 0;
+    for (; d4 - j >= 4; j += 4) {
+        float2_t df[4];
 #pragma unroll
-        for (int t = 0; t < 16; t++) df[t] = yv[t] - xs[i + t];
+        for (int t = 0; t < 4; t++) df[t] = widen2(yp[2 * (j + t)]) - xp[2 * (j + t)];
+        const float2_t ab3 = df[3] * df[3] + acc;
+        const float2_t ab2 = df[2] * df[2] + ab3;
+        const float2_t ab1 = df[1] * df[1] + ab2;
+        acc = df[0] * df[0] + ab1;
+    }
+    for (; j < d4; j++) {            // d % 4 == 0: whole vectors only
+        const float2_t df = widen2(yp[2 * j]) - xp[2 * j];
+        acc = df * df + acc;
+    }
+    return acc.x + acc.y;
+}
+
+// LDS addresses as numbers, and back: what a ds instruction takes, so that a clamp is one v_min on it.
+#define LDS_AT(p) ((unsigned)(size_t)(__attribute__((address_space(3))) const void *)(p))
+#define LDS_PTR(T, a) ((__attribute__((address_space(3))) T *)(size_t)(a))
+// The first address of an unrolled run, hidden from the optimiser (no instruction is emitted): seeing through it, it
+// carries each of the run's sixteen addresses round the enclosing loop in a register of its own, for the loads and
+// again for the stores, and at 134 VGPRs no longer keeps sixteen loads in flight.
+#define OPAQUE(x) asm("" : "+v"(x))
+
+// the value of the neighbouring lane (lane ^ 1): one DPP move, no LDS
+__device__ __forceinline__ float from_pair_lane(float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));
+}
+
+// Strict-count ranks of a lane's NV values dv[] among ds[0 .. nc4) (nc rounded up to 4 with +inf): per value and
+// element one compare and one add.  cnt[j] = #{u : ds[u] < dv[j]} is the final rank of dv[j] when every pair of the nc
+// distances is strictly ordered — and then the counts of all nc values add up to nc (nc - 1) / 2; a pair that is not
+// (equal, +0 / -0, a NaN) adds 0 where an ordered one adds 1, so the sum falls short exactly when there is one.
+template <int NV>
+__device__ __forceinline__ void strict_counts(const float *ds, int nc4, const float *dv, int *cnt)
+{
 #pragma unroll
-        for (int l = 0; l < 4; l++) {
-            float ab3 = df[12 + l] * df[12 + l] + acc[l];
-            float ab2 = df[8 + l] * df[8 + l] + ab3;
-            float ab1 = df[4 + l] * df[4 + l] + ab2;
-            acc[l] = df[l] * df[l] + ab1;
+    for (int j = 0; j < NV; j++) cnt[j] = 0;
+    for (int u = 0; u < nc4; u += 4) {
+        const float4_t du = *(const float4_t *)(ds + u);
+#pragma unroll
+        for (int j = 0; j < NV; j++) {
+            cnt[j] += du.x < dv[j];
+            cnt[j] += du.y < dv[j];
+            cnt[j] += du.z < dv[j];
+            cnt[j] += du.w < dv[j];
         }
     }
-    for (; i < d; i += 4) {          // d % 4 == 0: whole vectors only
-        float yv[4];
-        unpack4(y[i >> 2], yv);
-#pragma unroll
-        for (int l = 0; l < 4; l++) {
-            const float df = yv[l] - xs[i + l];
-            acc[l] = df * df + acc[l];
-        }
-    }
-    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
 }
 
 // make_slots_kernel's work for ONE query by the wave that ranked its probed lists (S <= 64): lane s
@@ -294,14 +326,15 @@ __device__ __forceinline__ void slots_epilogue(const TkSlotsOut &so, int64_t qi,
 // row, so every load instruction of a wave touches 64 different lines — 2775 line visits per query at R = 111,
 // d = 100 — and that address traffic is what it costs the scan kernels it runs beside
 // (profiles/r02_scan_grid.md).  Here the wave reads TILE candidate rows as one stream of pieces (RowPiece),
-// consecutive lanes = consecutive pieces of a row (4 lines per 400-byte row), drops them into a tile, and each
-// lane then runs the identical summation (sqdist_row: numpy's order) on its row from LDS.  A half tile stays in
-// half (half the float32 tile's LDS) and is widened where it is summed.
-// The row stride of the tile is an ODD number of pieces, which makes a lane's whole-piece reads conflict-free:
-// 16-byte pieces are read with ds_read_b128 (32-bit reads of the same layout would collide four ways); 8-byte
-// pieces with ds_read_b64, whose lane groups are {0-31}, {32-63}: a piece covers two of the 64 banks, so lane t's
-// piece j sits on bank pair (t * stride + j) mod 32 — distinct over 32 lanes exactly when the stride is odd.
-// LDS: cand[R] (int64) | dist[R] | x[d] | tile[TILE + 1 spare][stride] | have_slots: the k results (int64)
+// consecutive lanes = consecutive pieces of a row (4 lines per 400-byte row), drops them into a tile, and two
+// lanes per row then run the identical summation (sqdist_row: numpy's order, two of its four accumulators each)
+// from LDS.  A half tile stays in half (half the float32 tile's LDS) and is widened where it is summed.
+// The row stride of the tile is an ODD number of pieces, which makes the half-piece reads of the sum conflict-free
+// (worked out where they are issued).  A candidate's row is resolved ONCE, by the compaction, into a byte offset
+// kept beside its id; the ranking is one walk over the distances with the strict comparison, checked by the sum
+// of the counts, and falls back to the walk that breaks ties by position (strict_counts).
+// LDS: cand[R] (int64) | row offset[R] (int64) | dist[R] | x[d] | tile[TILE + 1 spare][stride] | have_slots: the
+// k results (int64)
 // DIST as rescore_body (the short-heap branch reads its rows with sqdist_row: the same summation as sqdist_row_lds)
 template <typename TY, int TILE, bool DIST>
 __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const float *__restrict__ q, int d,
@@ -314,9 +347,11 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
                                                     float *__restrict__ out_d_b)
 {
     typedef typename RowPiece<TY>::type P;
+    typedef typename HalfPiece<P>::type H;
     const bool have_slots = so_dev != nullptr;
     int64_t *cs = (int64_t *)smem;
-    float *ds = (float *)(smem + (((size_t)R * 8 + 15) & ~(size_t)15));
+    int64_t *ro = cs + R;                                // a kept candidate's row, in bytes from `rows`
+    float *ds = (float *)(smem + (size_t)R * 16);
     float *xs = ds + ((R + 3) & ~3);
     P *tile = (P *)(xs + ((d + 3) & ~3));                // 16-byte aligned
     const int tid = threadIdx.x;
@@ -332,9 +367,15 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
         const bool keep = t < R && (!strip || id != -1);
         const uint64_t m = __builtin_amdgcn_ballot_w64(keep);
         const int before = __builtin_popcountll(m & ((1ull << tid) - 1ull));
-        if (keep) cs[nc + before] = id;
+        if (keep) {
+            cs[nc + before] = id;
+            // numpy fancy indexing with a negative index, resolved once per candidate
+            ro[nc + before] = (id < 0 ? id + n_rows : id) * (int64_t)d * (int64_t)sizeof(TY);
+        }
         nc += __builtin_popcountll(m);
     }
+    // the ranking reads ds[] four at a time: +inf behind the last distance is below no value
+    if (tid < ((-nc) & 3)) ds[nc + tid] = __builtin_huge_valf();
     __syncthreads();
     const bool second = out_b && qi >= out_na;
     int64_t *o = second ? out_b + (qi - out_na) * k : out + qi * k;
@@ -361,45 +402,91 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
     // 64 / lanes_per_row whole rows, lane (rr, pc) fetches piece pc of its row
     const int lpr_log = d4 <= 16 ? 4 : (d4 <= 32 ? 5 : 6);
     const int rr = tid >> lpr_log, pc = tid & ((1 << lpr_log) - 1), rpi = 64 >> lpr_log;
+    // A lane's LDS addresses are plain numbers (LDS_AT: base included), each one add of a wave-uniform multiple of
+    // the step and one min: the row position comes resolved from ro[], so a load costs one LDS read and one 64-bit
+    // add onto the lane's base (piece pc of row 0).
+    const char *const lane_base = (const char *)rows + (size_t)pc * sizeof(P);
+    const unsigned ro_step = rpi * 8, st_step = rpi * stride * (unsigned)sizeof(P);
+    const int half = tid & 1, prow = tid >> 1;           // the sum: lanes 2p, 2p + 1 share row p of 32
+    const float2_t *const xp = (const float2_t *)xs + half;
     for (int t0 = 0; t0 < nc; t0 += TILE) {
         const int nt = nc - t0 < TILE ? nc - t0 : TILE;
         if (pc < d4)
             for (int r0 = rr; r0 < nt; r0 += 16 * rpi) {
-                // sixteen loads in flight per lane before the first LDS store waits for one
+                // sixteen loads in flight per lane before the first LDS store waits for one; rows past the tile
+                // re-read its last row
                 P v[16];
+                unsigned ro_at = LDS_AT(ro + t0 + r0), st_at = LDS_AT(tile + r0 * stride + pc);
+                const unsigned ro_last = LDS_AT(ro + t0 + nt - 1), st_spare = LDS_AT(tile + nt * stride + pc);
+                OPAQUE(ro_at);
+                OPAQUE(st_at);
 #pragma unroll
                 for (int u = 0; u < 16; u++) {
-                    const int r = r0 + u * rpi;
-                    int64_t id = cs[t0 + (r < nt ? r : nt - 1)];
-                    if (id < 0) id += n_rows;  // numpy fancy indexing with a negative index
-                    v[u] = ((const P *)(rows + id * (int64_t)d))[pc];
+                    const unsigned a = ro_at + u * ro_step;
+                    v[u] = *(const P *)(lane_base + *LDS_PTR(const int64_t, a < ro_last ? a : ro_last));
                 }
-                // unconditional stores (rows past the tile go to a spare row): a branch here
-                // lets the compiler sink each load next to its store, one exposed latency apiece
+                // unconditional stores (rows past the tile land in row nt, which is summed by nobody and exists:
+                // the tile has TILE + 1 rows): a branch here lets the compiler sink each load next to its store,
+                // one exposed latency apiece
 #pragma unroll
                 for (int u = 0; u < 16; u++) {
-                    const int r = r0 + u * rpi;
-                    tile[(r < nt ? r : TILE) * stride + pc] = v[u];
+                    const unsigned a = st_at + u * st_step;
+                    *LDS_PTR(P, a < st_spare ? a : st_spare) = v[u];
                 }
             }
         __syncthreads();
-        if (tid < nt) ds[t0 + tid] = sqdist_row_lds(tile + tid * stride, xs, d);
+        // two lanes per row, all 64 at work on a 32-row tile (a 64-row tile goes in two halves).  Banks: lane
+        // (p, s) reads 8 bytes (float32 rows) at dword 4 * (p * stride + j) + 2s — ds_read_b64 serves lanes 0-31
+        // and 32-63 apart, 16 rows each, p * stride distinct mod 16 for an odd stride, so the 32 lanes cover the
+        // 64 banks once; 4 bytes (half rows) at dword 2 * (p * stride + j) + s, p * stride distinct mod 32 over the
+        // 32 rows: 64 lanes, 64 banks.  The query's 2 addresses per read are broadcasts.  No conflicts either way.
+        for (int rb = 0; rb < nt; rb += 32) {
+            const int r = rb + prow;            // (rows nt .. TILE - 1 hold stale pieces: summed, not kept)
+            const float mine = sqdist_row_lds((const H *)(tile + r * stride) + half, xp, d4);
+            const float sum = mine + from_pair_lane(mine);      // (acc[0] + acc[1]) + (acc[2] + acc[3])
+            if (half == 0 && r < nt) ds[t0 + r] = sum;
+        }
         __syncthreads();
     }
     // have_slots: the k results in order, behind the tile rounded up to 16 bytes
     constexpr int PER16 = 16 / (int)sizeof(P);
     int64_t *ps = (int64_t *)(tile + (((TILE + 1) * stride + PER16 - 1) & ~(PER16 - 1)));
-    for (int t = tid; t < nc; t += 64) {
-        const float dv = ds[t];
-        int rank = 0;
-        for (int u = 0; u < nc; u++) {
-            const float du = ds[u];
-            rank += (du < dv) || (du == dv && u < t);
+    // rank by counting: a lane keeps its values (t = tid, tid + 64, ...: at most four, R <= 256) in registers and
+    // walks ds[] once with the strict comparison alone; beyond nc it holds -inf, which nothing is below
+    float dv[4];
+    int cnt[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) dv[j] = tid + 64 * j < nc ? ds[tid + 64 * j] : -__builtin_huge_valf();
+    const int nc4 = (nc + 3) & ~3;
+    if (nc <= 64) { strict_counts<1>(ds, nc4, dv, cnt); cnt[1] = cnt[2] = cnt[3] = 0; }
+    else if (nc <= 128) { strict_counts<2>(ds, nc4, dv, cnt); cnt[2] = cnt[3] = 0; }
+    else strict_counts<4>(ds, nc4, dv, cnt);
+    int total = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) total += __shfl_xor(total, m, 64);
+    if (total == nc * (nc - 1) / 2) {       // every pair strictly ordered: the counts are the ranks
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int t = tid + 64 * j;
+            if (t < nc && cnt[j] < k) {
+                o[cnt[j]] = cs[t];
+                if (DIST && od) od[cnt[j]] = dv[j];
+                if (have_slots) ps[cnt[j]] = cs[t];
+            }
         }
-        if (rank < k) {
-            o[rank] = cs[t];
-            if (DIST && od) od[rank] = dv;
-            if (have_slots) ps[rank] = cs[t];
+    } else {                                // equal distances (or a NaN): ties go to the lower position
+        for (int t = tid; t < nc; t += 64) {
+            const float dvt = ds[t];
+            int rank = 0;
+            for (int u = 0; u < nc; u++) {
+                const float du = ds[u];
+                rank += (du < dvt) || (du == dvt && u < t);
+            }
+            if (rank < k) {
+                o[rank] = cs[t];
+                if (DIST && od) od[rank] = dvt;
+                if (have_slots) ps[rank] = cs[t];
+            }
         }
     }
     if (tid == 0 && out_count) out_count[qi] = k;
@@ -574,7 +661,8 @@ static int launch_float_sums(const RescoreCall &c, int form, const TkSlotsOut *s
         const int tile_rows = staged == 2 ? 32 : 64;
         const bool fuse = slots != nullptr && c.k <= 64;        // (slots: a DEVICE copy of the structure)
         const size_t tile_bytes = (size_t)(tile_rows + 1) * stride * sizeof(typename RowPiece<TY>::type);
-        const size_t lds = (((size_t)c.R * 8 + 15) & ~(size_t)15) +
+        // ids and resolved row offsets (8 bytes each per candidate) | distances | query | tile | fused: the k results
+        const size_t lds = (size_t)c.R * 16 +
                            (size_t)(((c.R + 3) & ~3) + ((c.d + 3) & ~3)) * 4 + ((tile_bytes + 15) & ~(size_t)15) +
                            (fuse ? (size_t)c.k * 8 : 0);
         if (lds <= 64 * 1024) {
