@@ -178,8 +178,21 @@ def test_full_size_every_mode(full):
                         bad = np.flatnonzero((got != w).any(axis=1))
                         assert bad.size == 0, (heap_mode, plain, pair_nq, name, bad[:5])
                         _check(got, gd, w, wd, sets[name])
+        # the limit at -128: every query with a plain list fails the lemma's check, is scanned again exactly and masked
+        # again through the flag list (allow_pass_kernel's `only` branch)
+        dev.set_heap_mode(0)
+        dev.set_plain_scan("always")
+        dev.set_option(_lib.OPT_PAIR_NQ, 4)
+        dev.set_option(_lib.OPT_PLAIN_LIMIT, -128)
+        for name, aset in asets.items():
+            got, gd = dev.query_batch(qn, qp, 10, 10, debug=True, allowed=aset)
+            st = dev.plain_stats()
+            w, wd = want[name]
+            _check(got, gd, w, wd, sets[name])
+            assert st["plain_units"] > 0 and st["flagged_queries"] > 0, (name, st)
     finally:
         dev.set_heap_mode(0); dev.set_plain_scan(True); dev.set_option(_lib.OPT_PAIR_NQ, 4)
+        dev.set_option(_lib.OPT_PLAIN_LIMIT, 0x7fffffff)
         for a in asets.values():
             a.close()
 

@@ -171,12 +171,25 @@ def test_every_replay_form(tk, synthetic, kp):
                     got, gd = dev.query_batch(qn, qp, 10, 10, debug=True, group=group)
                     _same(got, gd, want, wd, (kp, heap_mode, plain, pair_nq))
         _within_groups(got, group, groups)
+        # the limit at -128: every query with a plain list fails the lemma's check, is scanned again exactly and masked
+        # again through the flag list (the passes' `only` branch)
+        dev.set_heap_mode(0)
+        dev.set_plain_scan("always")
+        dev.set_option(_lib.OPT_PLAIN_LIMIT, -128)
+        for pair_nq in (4, 8192):
+            dev.set_option(_lib.OPT_PAIR_NQ, pair_nq)
+            got, gd = dev.query_batch(qn, qp, 10, 10, debug=True, group=group)
+            st = dev.plain_stats()
+            _same(got, gd, want, wd, (kp, "limit -128", pair_nq, st))
+            assert st["plain_units"] > 0 and st["flagged_queries"] > 0, st
         assert dev.group_table()["builds"] == 1
     finally:
         dev.set_heap_mode(0); dev.set_plain_scan(True); dev.set_option(_lib.OPT_PAIR_NQ, 4)
+        dev.set_option(_lib.OPT_PLAIN_LIMIT, 0x7fffffff)
 
 
 def test_with_an_allowed_set_an_excluded_row_and_distances(tk, oracle, synthetic):
+    from tinyknn_amd import _lib
     get, groups, group = synthetic
     ivf, ox, qn, qp, (want, _) = get(1)
     dev = ivf.device_index()
@@ -184,20 +197,28 @@ def test_with_an_allowed_set_an_excluded_row_and_distances(tk, oracle, synthetic
     exclude = want[:, 0].copy()             # every query's best id (or -1) may not come back
     assert (exclude >= 0).sum() > SYN_NQ // 2
     aset = dev.allow(allowed)
-    try:
-        for plain in (False, "always"):
-            dev.set_plain_scan(plain)
+    legs = [(name, kw, grouped_batch(oracle, ox, qn, group, groups, 10, 10, debug=True, **ref))
             for name, kw, ref in (("allowed", dict(allowed=aset), dict(allowed=allowed)),
                                   ("exclude", dict(exclude=exclude), dict(exclude=exclude)),
-                                  ("all three", dict(allowed=aset, exclude=exclude), dict(allowed=allowed, exclude=exclude))):
-                w, wdbg = grouped_batch(oracle, ox, qn, group, groups, 10, 10, debug=True, **ref)
+                                  ("all three", dict(allowed=aset, exclude=exclude), dict(allowed=allowed, exclude=exclude)))]
+    try:
+        # ("forced": pinned on with the limit at -128 — every query with a plain list is flagged, scanned again exactly
+        #  and masked again by all three passes through the flag list)
+        for plain in (False, "always", "forced"):
+            dev.set_plain_scan("always" if plain == "forced" else plain)
+            dev.set_option(_lib.OPT_PLAIN_LIMIT, -128 if plain == "forced" else 0x7fffffff)
+            for name, kw, (w, wdbg) in legs:
                 got, gd = dev.query_batch(qn, qp, 10, 10, debug=True, group=group, **kw)
                 _same(got, gd, w, wdbg, (name, plain))
+                if plain == "forced":
+                    st = dev.plain_stats()
+                    assert st["plain_units"] > 0 and st["flagged_queries"] > 0, (name, st)
                 _within_groups(got, group, groups)
                 if "exclude" in kw:
                     assert not (got == np.where(exclude >= 0, exclude, -2)[:, None]).any()
                 if "allowed" in kw:
                     assert allowed[got[got != -1]].all()
+        dev.set_option(_lib.OPT_PLAIN_LIMIT, 0x7fffffff)
         dev.set_plain_scan(True)
         # distances: the ids of the plain grouped call, each with the rescoring's exact distance
         ids, dist = dev.query_batch(qn, qp, 10, 10, group=group, return_distances=True)
@@ -208,7 +229,30 @@ def test_with_an_allowed_set_an_excluded_row_and_distances(tk, oracle, synthetic
         assert same_bits(dist, exact_distances(oracle, qn, ivf.data, ids))
     finally:
         dev.set_plain_scan(True)
+        dev.set_option(_lib.OPT_PLAIN_LIMIT, 0x7fffffff)
         aset.close()
+    # the index built with n_probes = 2 (labels repeat: the TWIN form): the allow pass alone and all three passes behind
+    # its flagged re-scan
+    ivf2, ox2, qn2, qp2, (want2, _) = get(2)
+    dev2 = ivf2.device_index()
+    exclude2 = want2[:, 0].copy()
+    aset2 = dev2.allow(allowed)
+    try:
+        dev2.set_plain_scan("always")
+        dev2.set_option(_lib.OPT_PLAIN_LIMIT, -128)
+        for name, kw, ref in (("allowed", dict(allowed=aset2), dict(allowed=allowed)),
+                              ("all three", dict(allowed=aset2, exclude=exclude2, group=group),
+                               dict(allowed=allowed, exclude=exclude2))):
+            w2, wd2 = grouped_batch(oracle, ox2, qn2, group if "group" in kw else -1, groups, 10, 10, debug=True, **ref)
+            got, gd = dev2.query_batch(qn2, qp2, 10, 10, debug=True, **kw)
+            st = dev2.plain_stats()
+            _same(got, gd, w2, wd2, (2, name, "forced", st))
+            assert st["plain_units"] > 0 and st["flagged_queries"] > 0, (name, st)
+            assert allowed[got[got != -1]].all()
+    finally:
+        dev2.set_plain_scan(True)
+        dev2.set_option(_lib.OPT_PLAIN_LIMIT, 0x7fffffff)
+        aset2.close()
 
 
 def test_pipelined_pairs_alternating_kinds(tk, oracle, synthetic):

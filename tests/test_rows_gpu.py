@@ -178,8 +178,20 @@ def test_every_replay_form(tk, synthetic, kp):
                     dev.set_option(_lib.OPT_PAIR_NQ, pair_nq)
                     got, gd = dev.query_rows(rows, 10, 10, debug=True)
                     _same(got, gd, want, wd, (kp, heap_mode, plain, pair_nq))
+        # the limit at -128: every query with a plain list fails the lemma's check, is scanned again exactly and masked
+        # again through the flag list (exclude_pass_kernel's `only` branch)
+        dev.set_heap_mode(0)
+        dev.set_plain_scan("always")
+        dev.set_option(_lib.OPT_PLAIN_LIMIT, -128)
+        for pair_nq in (4, 8192):
+            dev.set_option(_lib.OPT_PAIR_NQ, pair_nq)
+            got, gd = dev.query_rows(rows, 10, 10, debug=True)
+            st = dev.plain_stats()
+            _same(got, gd, want, wd, (kp, "limit -128", pair_nq, st))
+            assert st["plain_units"] > 0 and st["flagged_queries"] > 0, st
     finally:
         dev.set_heap_mode(0); dev.set_plain_scan(True); dev.set_option(_lib.OPT_PAIR_NQ, 4)
+        dev.set_option(_lib.OPT_PLAIN_LIMIT, 0x7fffffff)
 
 
 def test_pipelined_pairs_alternating_kinds(tk, oracle, synthetic):
