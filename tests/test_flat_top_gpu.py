@@ -78,7 +78,7 @@ def test_flat_top_long_rows_on_the_matrix_cores(oracle, d, structured):
 def test_query_pq_long_rows_fresh_heap_compacts_candidates(oracle, signd, chunks, n_off, R):
     """Per-query `query_pq` over >= 4096 blocks with a fresh heap of at most 64 entries: one launch
     replays the first ~sqrt(R chunks) blocks with the heap in registers, compacts the later blocks whose
-    minimum is below the bound reached there, and replays those (heap.hip, flat_top_one_kernel).  Same
+    minimum is below the bound reached there, and replays those (heap_flat.hip, flat_top_one_kernel).  Same
     heap arrays as the oracle — with n short of (or beyond) the padded rows, signed and unsigned, heaps
     on either side of the 64-entry limit (R = 65, 2000: the general kernel), and a second call that
     continues from the heap of the first (general kernel)."""

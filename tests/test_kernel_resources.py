@@ -23,9 +23,9 @@ PINNED = {
     ("plain_scan.hip", "scan_plain_wave_kernelILi26ELb1E"): (256, 2),
     ("plain_scan.hip", "scan_plain_wave_kernelILi16ELb1E"): (256, 2),
     # lane-per-query replay, distinct labels, 64 queries per wave
-    ("heap.hip", "heap_replay_lanes_kernelILb1ELb0ELi64ELb0ELb0EE"): (128, 4),
+    ("heap.hip", "heap_replay_lanes_kernelILb1EE"): (128, 4),
     # one query over a long array: one workgroup of 16 waves, heap in registers
-    ("heap.hip", "flat_top_one_kernelILb1EE"): (128, 4),
+    ("heap_flat.hip", "flat_top_one_kernelILb1EE"): (128, 4),
     ("rescore.hip", "rescore_staged_kernelILi32EE"): (128, 4),
     # table build, the head of the front stream's chain: float queries (GloVe-shaped) and the float64
     # form of every ROTATED index (configs[0], [2], [4]) — round 4 shipped the latter with 272 B/lane
@@ -33,30 +33,31 @@ PINNED = {
     ("tables.hip", "build_tables_kernelIfLb1EE"): (128, 4),
     ("tables.hip", "build_tables_kernelIdLb1EE"): (128, 4),
     # the lazy lane replay of long rows (FlatTop, configs[2]) and the wave-per-query replays
-    ("heap.hip", "heap_replay_lanes_kernelILb1ELb0ELi64ELb1ELb0EE"): (80, 4),
+    ("heap.hip", "heap_replay_lanes_seg_kernelILb1ELb0ELi64ELb1ELb0EE"): (80, 4),
     # labels that repeat (IVF.build(n_probes >= 2), the reference's default): the TWIN form, staged and lazy
     # (one wave per SIMD is all a replay gets: 157 - 314 waves on 1024 SIMDs)
-    ("heap.hip", "heap_replay_lanes_kernelILb1ELb0ELi64ELb0ELb1EE"): (144, 3),
-    ("heap.hip", "heap_replay_lanes_kernelILb1ELb0ELi64ELb1ELb1EE"): (96, 4),
+    ("heap.hip", "heap_replay_lanes_seg_kernelILb1ELb0ELi64ELb0ELb1EE"): (144, 3),
+    ("heap.hip", "heap_replay_lanes_seg_kernelILb1ELb0ELi64ELb1ELb1EE"): (96, 4),
     # the register heap (one query per wave; round 6): two / four / eight nodes per lane, no LDS
-    ("heap.hip", "heap_replay_pair_kernelILb1ELi1EE"): (48, 8),
-    ("heap.hip", "heap_replay_pair_kernelILb1ELi2EE"): (64, 7),
-    ("heap.hip", "heap_replay_pair_kernelILb1ELi4EE"): (112, 4),
-    ("heap.hip", "heap_replay_packed_kernelILb1ELb0EE"): (64, 8),
-    ("heap.hip", "heap_replay_packed_kernelILb1ELb1EE"): (64, 8),
+    ("heap_pair.hip", "heap_replay_pair_kernelILb1ELi1EE"): (48, 8),
+    ("heap_pair.hip", "heap_replay_pair_kernelILb1ELi2EE"): (64, 7),
+    ("heap_pair.hip", "heap_replay_pair_kernelILb1ELi4EE"): (112, 4),
+    ("heap_wave.hip", "heap_replay_packed_kernelILb1ELb0EE"): (64, 8),
+    ("heap_wave.hip", "heap_replay_packed_kernelILb1ELb1EE"): (64, 8),
 }
 
 
 # every kernel of these files: no scratch, no VGPR spills (rotated / 100M x 128 / build_probes = 2 indexes
 # launch instantiations the default batch does not)
-NO_SCRATCH_FILES = ("adc_scan.hip", "plain_scan.hip", "tables.hip", "rescore.hip", "heap.hip")
+NO_SCRATCH_FILES = ("adc_scan.hip", "plain_scan.hip", "tables.hip", "rescore.hip", "heap.hip", "heap_wave.hip", "heap_flat.hip",
+                    "heap_pair.hip")
 # SGPR spills tolerated (to VGPR lanes, not memory): the duplicate-test lane replay of build_probes >= 2
 # ... and the SSE-order form of the plain kernel (the reference's non-AVX module order; no BASELINE config)
 # ... and its TWIN form: kernel arguments that are only needed behind the replay loop, parked in VGPR lanes in the
 # prologue and fetched back in the epilogue (no v_readlane / v_writelane inside the loop: read off the ISA)
-SGPR_SPILLS_OK = {"heap_replay_lanes_kernelILb1ELb1ELi32ELb0ELb0EE": 48, "heap_replay_lanes_kernelILb0ELb1ELi32ELb0ELb0EE": 48,
-                  "heap_replay_lanes_kernelILb1ELb0ELi64ELb0ELb1EE": 24, "heap_replay_lanes_kernelILb0ELb0ELi64ELb0ELb1EE": 24,
-                  "heap_replay_lanes_kernelILb1ELb0ELi64ELb1ELb1EE": 24, "heap_replay_lanes_kernelILb0ELb0ELi64ELb1ELb1EE": 24,
+SGPR_SPILLS_OK = {"heap_replay_lanes_seg_kernelILb1ELb1ELi32ELb0ELb0EE": 48, "heap_replay_lanes_seg_kernelILb0ELb1ELi32ELb0ELb0EE": 48,
+                  "heap_replay_lanes_seg_kernelILb1ELb0ELi64ELb0ELb1EE": 24, "heap_replay_lanes_seg_kernelILb0ELb0ELi64ELb0ELb1EE": 24,
+                  "heap_replay_lanes_seg_kernelILb1ELb0ELi64ELb1ELb1EE": 24, "heap_replay_lanes_seg_kernelILb0ELb0ELi64ELb1ELb1EE": 24,
                   "scan_plain_wave_kernelILi26ELb0EE": 16,
                   # the register heap with four / eight nodes per lane (heaps of 130 ... 513 entries): its lane masks (one
                   # per group and role) outnumber the SGPRs; the two-node form of the common heaps (<= 129) has none
@@ -111,7 +112,7 @@ def test_twin_replay_parks_its_sgprs_outside_the_loops():
         assert r.returncode == 0, r.stderr[-2000:]
         asm = open(out).read()
     seen = 0
-    for name in re.findall(r"^(_Z24heap_replay_lanes_kernelILb[01]ELb0ELi64ELb[01]ELb1EE\S*):", asm, flags=re.M):
+    for name in re.findall(r"^(_Z28heap_replay_lanes_seg_kernelILb[01]ELb0ELi64ELb[01]ELb1EE\S*):", asm, flags=re.M):
         body = asm[asm.index("\n" + name + ":"):]
         body = body[:body.index("s_endpgm")]
         in_loop = False

@@ -1,5 +1,5 @@
 """The two-registers-per-lane form of `insert` (_fast_pq.pyx:274-307) that the wave-per-query replay runs for heaps of
-up to 129 entries (heap.hip: pair_heap_insert — IVF.query's heap of (n_probes + 1) k + 1 = 111 entries at the
+up to 129 entries (heap_pair.hip: PairHeapPos / PairHeapLab — IVF.query's heap of (n_probes + 1) k + 1 = 111 entries at the
 reference's bench settings), restated in numpy over 64 "lanes" and checked against the oracle's loop.
 
 Layout: the root is wave-uniform; lane L holds the two CHILDREN of node L — node 2L+1 in slot 0, node 2L+2 in slot 1
@@ -111,7 +111,7 @@ def test_pair_layout_insert_on_falling_and_constant_streams(oracle):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# G groups of node pairs per lane (heap.hip: the same kernel for heaps of up to 128 G + 1 entries — G = 2: 257, the
+# G groups of node pairs per lane (heap_pair.hip: the same kernel for heaps of up to 128 G + 1 entries — G = 2: 257, the
 # heap of n_probes <= 24 at k = 10): lane L, group g holds the children of node t = 64 g + L.  The path is still one
 # ballot per group; a node's ancestors are all below 64 G / 2, i.e. in the lower half of the groups; CE[c] of the
 # chosen child c = 2 t + 1 + right lives in lane c & 63 of group c >> 6 (if c < 64 G).

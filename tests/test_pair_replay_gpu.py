@@ -1,4 +1,4 @@
-"""The wave-per-query heap replay with the heap in registers (heap.hip: heap_replay_pair_kernel) — the kernel behind
+"""The wave-per-query heap replay with the heap in registers (heap_pair.hip: heap_replay_pair_kernel) — the kernel behind
 ONE query per call, which is what the reference's own bench times (examples/bench.py:118-137: `ivf.query(q)` in a
 Python loop), and behind small batches (TK_OPT_PAIR_NQ, product default 8192 one batch at a time).
 

@@ -1,5 +1,5 @@
 """The lane-parallel form of `insert` (_fast_pq.pyx:274-307) that flat_top_one_kernel runs with the heap
-in registers (heap.hip: reg_heap_insert), restated in numpy and checked against the oracle's loop.
+in registers (heap_flat.hip: reg_heap_insert), restated in numpy and checked against the oracle's loop.
 
 Claim: the sift of `insert` follows the heap's MAX-CHILD path (left child on ties), which does not depend
 on the inserted value; values never rise along it, so the nodes the loop passes are the root and the path
@@ -10,7 +10,7 @@ import pytest
 
 
 def insert_by_lanes(idx, val, label, v):
-    """All R 'lanes' at once, as heap.hip does it (no loop over levels)."""
+    """All R 'lanes' at once, as heap_flat.hip does it (no loop over levels)."""
     R = len(val)
     if (idx == label).any():                       # the duplicate test, :284-287
         return

@@ -155,7 +155,7 @@ extern "C" int tk_query_pq(const uint64_t *data, int64_t chunks, int M, int64_t 
     tk_launch_scan_flat(S.tiled.as<uint4>(), chunks, M, S.tables.as<uint4>(), 1, S.out.as<uint4>(),
                         chunks, S.mins.as<uint8_t>(), cap_min, signd, order, st);
     // A FRESH heap of up to 513 entries (init_heap's arrays: the first query_pq of a DistanceTable.top / IVF.query): the
-    // wave-per-query replay with the heap in registers (heap.hip: heap_replay_pair_kernel; position entries without labels,
+    // wave-per-query replay with the heap in registers (heap_pair.hip: heap_replay_pair_kernel; position entries without labels,
     // (value, label64) entries with the reference's duplicate test with them) instead of the general kernel's LDS heap —
     // ~300 instead of ~2 000 cycles per insert.  Same arrays out.
     bool fresh_heap = R <= TK_PAIR_MAX_R && tk_positions_fit(chunks);
@@ -411,7 +411,7 @@ extern "C" int tk_codes_query(tk_codes *c, int64_t n, const uint64_t *tables, in
     TRY(c->mins.ensure((size_t)cap_min));
     // Rows far longer than a FRESH heap of at most 64 entries (top() of one query over a whole data
     // set): one table copy from pinned memory, the scan, ONE launch that replays with the heap in
-    // registers and writes it to pinned memory (heap.hip, flat_top_one_kernel).  The head is
+    // registers and writes it to pinned memory (heap_flat.hip, flat_top_one_kernel).  The head is
     // ~sqrt(R chunks) blocks: about as many again pass its bound.
     bool fresh_heap = !labels && R <= TK_PAIR_MAX_R && (size_t)c->M * 16 <= 32 * 1024;
     for (int i = 0; i < R && fresh_heap; i++) fresh_heap = indices[i] == -1 && vals[i] == (signd ? 127 : 255);
@@ -419,7 +419,7 @@ extern "C" int tk_codes_query(tk_codes *c, int64_t n, const uint64_t *tables, in
     if (fresh_heap && !fresh && tk_positions_fit(chunks)) {
         // A fresh heap of up to 513 entries over a shorter array (DistanceTable.top of one query over a few thousand to a
         // million rows, examples/example.py: 16 000 rows, R = 2 k + 10 = 30): table in through pinned memory, the scan, the
-        // wave-per-query replay with the heap in registers (heap.hip: heap_replay_pair_kernel, position entries — positions
+        // wave-per-query replay with the heap in registers (heap_pair.hip: heap_replay_pair_kernel, position entries — positions
         // ARE the labels here), the heap written straight to pinned memory: 4 operations instead of 11, ~300 instead of
         // ~2 000 cycles per insert.
         if (!c->pin) HIPCHECK(hipHostMalloc(&c->pin, 64 * 1024, hipHostMallocDefault));

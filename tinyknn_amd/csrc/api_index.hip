@@ -442,7 +442,7 @@ static bool dedupe_lanes_fit(const tk_index *ix, const Plan &p)
     return ix->have_ids32 && tk_lanes_dedupe_fits(p.R, p.S) && ix->total_ids < (1ll << 31);
 }
 
-// the wave-per-query replay with the heap in registers (heap.hip: heap_replay_pair_kernel): small batches — ONE query
+// the wave-per-query replay with the heap in registers (heap_pair.hip: heap_replay_pair_kernel): small batches — ONE query
 // per call above all — where the lane kernel would spend a wave's round on a few lanes; heap_mode 3 forces it
 static bool pair_replay(const tk_index *ix, int64_t nq, int R)
 {
@@ -1099,7 +1099,7 @@ static TkReplayJob list_replay_job(const tk_index *ix, Work &w, int64_t q0, int6
     return j;
 }
 
-// The forms of a batch's heap replay (heap.hip).  Every form but General starts from fresh heaps on packed entries.
+// The forms of a batch's heap replay (heap.hip, heap_wave.hip, heap_pair.hip).  Every form but General starts from fresh heaps on packed entries.
 // (tk_index_last_replay reports them: the values are the header's TK_REPLAY_*)
 enum class Replay {
     Pair = TK_REPLAY_PAIR,                      // register heap, one query per wave (pair_replay: small batches, heap_mode 3)

@@ -181,7 +181,7 @@ void tk_launch_heap_replay(const TkReplayJob &j, hipStream_t s);
 // one query, a FRESH heap of R <= 64 entries, rows far longer than it: one workgroup — head of h blocks
 // (a multiple of 16) replayed with the heap in registers, the later blocks whose minimum is below the
 // bound reached there compacted in order, those replayed; the heap goes to out_idx / out_val (which may
-// be pinned host memory).  cdist: chunks uint4, cblock: chunks int + chunks bytes.  See heap.hip
+// be pinned host memory).  cdist: chunks uint4, cblock: chunks int + chunks bytes.  See heap_flat.hip
 void tk_launch_flat_top_one(const uint4 *dist, const uint8_t *mins, int chunks, int h, int64_t n, int R, int signd,
                             uint4 *cdist, int *cblock, int64_t *out_idx, int32_t *out_val, hipStream_t s);
 
@@ -196,11 +196,15 @@ struct TkTwins {
 
 // Lane-per-query form: 64 queries per wave.  Preconditions (checked by the caller): heaps start fresh
 // (-1 / 127|255), no label can repeat among a query's lists (so `insert`'s duplicate test cannot fire),
-// R*256 B of LDS <= 160 KiB, tk_positions_fit(cap).  Writes (nq, R) heaps.  Needs j.mins.
+// R <= TK_LANES_MAX_R, tk_positions_fit(cap).  Writes (nq, R) heaps.  Needs j.mins.
+// The LDS of a query-wave is written down once, in heap.hip (tk_lanes_lds), with static_asserts for what follows.
+// 574: the largest heap whose columns, (R + 2) * 256 B, leave 16 KiB of staging within 160 KiB.  The TWIN form adds its
+// slot table, probe list and list bitmap: tk_lanes_twin_fits, not this limit, is what bounds it (R <= 568 beside one list).
 #define TK_LANES_MAX_R 574
 // with labels32 (labels may repeat: duplicate test on 32-bit label slots + a two-choice hash
 // set of the labels in the heap, 64 KiB) the LDS budget is (2R+2)*256 + 64 KiB + 16 KiB + the
-// slot table
+// slot table.  149 is below where that budget ends (156 beside one list) and fits beside at most 8 probed lists
+// (163 584 B); it is kept as it is because it decides which replay an index gets.  tk_lanes_dedupe_fits applies both.
 #define TK_LANES_MAX_R_DEDUPE 149
 // ... the hash set's two candidate buckets (of 64, four labels each) of a label: THE definition — the kernel places,
 // finds and removes labels through it, tk_label_buckets exports it (the tests draw their colliding labels from there)
@@ -230,7 +234,7 @@ struct TkLanesOpts {
 int tk_launch_heap_replay_lanes(const TkReplayJob &j, const TkLanesOpts &o, hipStream_t s);   // non-zero: no LDS attribute
 
 // Wave-per-query replay with the heap in registers, two / four / eight nodes per lane for heaps of up to 129 / 257 / 513
-// entries (heap.hip): R <= TK_PAIR_MAX_R, fresh heaps, j.mins;
+// entries (heap_pair.hip): R <= TK_PAIR_MAX_R, fresh heaps, j.mins;
 // position entries where labels are distinct (tk_positions_fit(cap)), the reference's duplicate test on (value, label)
 // entries for the queries with flags[q] != 0 or for every query (dedupe_all).  The kernel of one query per call.
 // check: as the lane replay makes it, in `flags`.  only_flagged: only the queries with flags[q] != 0, with the duplicate
