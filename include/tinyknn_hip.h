@@ -508,6 +508,43 @@ int tk_index_list_columns(tk_index *ix, int *kp, int64_t *counts);
 int tk_index_remove_rows(tk_index *ix, const int64_t *rows, int64_t n, int kp,
                          const int64_t *list_columns, int64_t *removed_out);
 
+/* ---- stored rows replaced in a built index, in place, ids kept (IVF.update) -------------------
+ * tk_index_update_rows gives the n rows named by `ids` (int64 row ids in [0, N), pairwise
+ * distinct; host or device memory) the new vectors `rows` (n, d).  The index afterwards is the
+ * one that tk_index_remove_rows(ids) followed by tk_index_add_rows(rows) gives on the same index,
+ * with two differences: the added row N + i carries the label ids[i] in every list, and its
+ * prepared vector sits in row ids[i] of the stored vectors, not behind the old rows.  N and the
+ * size of the vector store do not change.  With kp lists per row list l's column-j block becomes
+ * (old_j minus the rows in ids, old order kept) ++ (the rows i whose nearest[:, j] is l,
+ * ASCENDING i, labelled ids[i]).  A row in ids that was removed earlier is stored again (the hole
+ * is refilled); a row whose nearest list does not change moves to the end of its column block; a
+ * list that empties stays, with its centre; rows that activate centres n_lists .. append lists
+ * under the prefix rule of tk_index_add_rows.  The index is byte-identical to tk_index_set_lists
+ * of those lists (sizes, offsets, codes with the zero vector's code in the padding rows, ids,
+ * their int32 copy, twin table) over the vectors with their rows replaced.
+ *   rows, nearest, labels, list_columns, normalise, all_centers, search_centers, ynorm2, C,
+ *     center_codes, n_active_out: as in tk_index_add_rows — the rows are prepared exactly as there
+ *     (normalisation, assignment, PQ labels; a half store takes float32 rows, assigns and codes
+ *     them from their float32 values and stores them rounded as tk_index_narrow_data rounds).
+ *   removed_out: stored entries of the old versions that went (kp per row that was stored), or NULL.
+ * The lists are rewritten in ONE pass: the old code array is read once and the new one written
+ * once (nothing old is decoded or re-encoded), the vectors are scattered once.
+ * Order inside the call: batches in flight are completed first, on the old lists AND the old
+ * vectors; the rows are staged and prepared in a scratch buffer, never in the live store; the new
+ * lists are built completely in new buffers; only behind the last point that can fail are the
+ * vectors overwritten and the lists swapped.  So a refused or failed call leaves the lists and
+ * the vectors as they were.  Refused (TK_ERR_ARG): an id outside [0, N) or named twice; a row
+ * whose half is not finite on a half store (naming the row of `rows`); what tk_index_add_rows
+ * and tk_index_remove_rows refuse (a list-sharded index, kp against the stored copies, unknown
+ * list_columns, the prefix rule).  Allowed sets made before fail afterwards (a new layout); the
+ * row-position table of exclude= and the group table follow the new layout on their next use.
+ * n == 0 changes nothing. */
+int tk_index_update_rows(tk_index *ix, const int64_t *ids, int64_t n, const void *rows, int rows_is_f64,
+                         int kp, const int64_t *nearest, const uint8_t *labels, const int64_t *list_columns,
+                         int normalise, const float *all_centers, const float *search_centers,
+                         const float *ynorm2, int64_t C, const uint64_t *center_codes,
+                         int64_t *n_active_out, int64_t *removed_out);
+
 /* ---- device front end, "fast mode"  -----------------------------------
  * What IVF.query does on the host before the table build (ivf.py:125-128,
  * fast_pq.py:200-204): float32 normalisation for the angular metric, zero padding to dq,

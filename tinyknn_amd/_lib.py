@@ -126,6 +126,9 @@ SIGNATURES = {
                                     C.c_void_p, _i64p]),
     "tk_index_list_columns": (C.c_int, [C.c_void_p, _i32p, C.c_void_p]),
     "tk_index_remove_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, _i64p]),
+    "tk_index_update_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p, _i64p, _i64p]),
     "tk_index_top_centers": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int, _i64p]),
     "tk_index_top_centers_dist": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int, _i64p,
                                             _f32p]),

@@ -361,6 +361,159 @@ static int rows_sit_in(tk_index *ix, int kp, bool *ok)
     return TK_OK;
 }
 
+// list_columns against the list sizes: cw counts per list, none negative, adding up to the list
+static int check_columns(const std::vector<int64_t> &cols0, const std::vector<int64_t> &size0, int64_t L, int cw)
+{
+    for (int64_t l = 0; l < L; l++) {
+        int64_t s = 0;
+        for (int t = 0; t < cw; t++) {
+            ARGCHECK(cols0[(size_t)(l * cw + t)] >= 0, "list_columns: negative count");
+            s += cols0[(size_t)(l * cw + t)];
+        }
+        ARGCHECK(s == size0[(size_t)l], "list_columns: a list's columns do not add up to its size");
+    }
+    return TK_OK;
+}
+
+// ---- what add and update do with their new rows, in the order they do it
+// The nearest centres of the n rows Xn (device; given, or found as tk_index_build_dev finds them; the rows are
+// normalised in place first where asked), their (centre, row) pairs in keys / prow and the members per
+// (centre, column) in cntc
+static int new_row_pairs(void *Xn, int64_t n, int d, int kp, const int64_t *nearest, int normalise,
+                         const float *search_centers, const float *ynorm2, int64_t C, DevBuf &yt, DevBuf &yn,
+                         DevBuf &near, DevBuf &keys, DevBuf &prow, DevBuf &count, std::vector<int> &cntc)
+{
+    const int64_t T = n * kp;
+    TRY(near.ensure((size_t)T * 8));
+    if (nearest) {
+        HIPCHECK(hipMemcpy(near.p, nearest, (size_t)T * 8, hipMemcpyHostToDevice));
+        if (normalise) tk_launch_normalise_rows((float *)Xn, n, d, (float *)Xn, 0);
+    } else {
+        TRY(upload_search_centres(yt, yn, search_centers, ynorm2, C, d));
+        assign_rows_dev((float *)Xn, n, d, normalise, yt, yn, C, kp, near.as<int64_t>());
+    }
+    TRY(keys.ensure((size_t)T * 4));
+    TRY(prow.ensure((size_t)T * 4));
+    TRY(count.ensure((size_t)C * kp * 4));
+    HIPCHECK(hipMemset(count.p, 0, (size_t)C * kp * 4));
+    tk_launch_keys_count(near.as<int64_t>(), n, kp, 0, n, keys.as<int>(), prow.as<int>(), count.as<int>(), 0);
+    HIPCHECK(hipGetLastError());
+    cntc.resize((size_t)C * kp);
+    HIPCHECK(hipMemcpy(cntc.data(), count.p, (size_t)C * kp * 4, hipMemcpyDeviceToHost));
+    return TK_OK;
+}
+
+// The active centres stay a prefix 0 .. L1 - 1 (the build's contract, utils.py:128): L1 lists once the centres that
+// received a row join the L0 old ones, or -1 where an unused centre would precede a used one
+#define PREFIX_REFUSAL "a centre that received no row precedes one that did: the reference's " \
+                       "group_data_by_indices asserts max(index) < n_active (utils.py:128)"
+static int64_t active_prefix(const std::vector<int> &cntc, int64_t C, int kp, int64_t L0)
+{
+    int64_t L1 = 0, last = -1;
+    for (int64_t j = 0; j < C; j++) {
+        int64_t c = 0;
+        for (int t = 0; t < kp; t++) c += cntc[(size_t)(j * kp + t)];
+        if (j < L0 || c > 0) {
+            L1++;
+            last = j;
+        }
+    }
+    return last < L1 ? L1 : -1;
+}
+
+// PQ labels (n, M) of the new rows in lab: given, or as the build encodes them
+static int new_row_labels(tk_index *ix, const void *Xn, int64_t n, const uint8_t *labels, DevBuf &rot, DevBuf &lab)
+{
+    const int M = ix->M, d = ix->d;
+    TRY(lab.ensure((size_t)n * M));
+    if (labels) {
+        HIPCHECK(hipMemcpy(lab.p, labels, (size_t)n * M, hipMemcpyHostToDevice));
+        return TK_OK;
+    }
+    const int64_t slab = 1 << 20;
+    for (int64_t o = 0; o < n; o += slab)
+        TRY(encode_rows_dev(ix, (const float *)Xn + o * d, n - o < slab ? n - o : slab, rot,
+                            lab.as<uint8_t>() + (size_t)o * M));
+    return TK_OK;
+}
+
+// the zero vector's labels (the rows that pad a list) in zlab
+static int zero_labels_dev(tk_index *ix, DevBuf &rot, DevBuf &zrow, DevBuf &zlab)
+{
+    TRY(zrow.ensure((size_t)16 * ix->d * 4));
+    TRY(zlab.ensure((size_t)16 * ix->M));
+    HIPCHECK(hipMemset(zrow.p, 0, (size_t)16 * ix->d * 4));
+    return encode_rows_dev(ix, zrow.as<float>(), 16, rot, zlab.as<uint8_t>());
+}
+
+// L1 > L0 lists: the centres all_centers[:L1] in act1 and their codes in ccodes — the host's
+// (pq.transform(active_centers)) retiled, or coded on the device
+static int grown_centres(tk_index *ix, const float *all_centers, const uint64_t *center_codes, int64_t L1, DevBuf &rot,
+                         DevBuf &crow, DevBuf &clab, DevBuf &coffs, DevBuf &act1, DevBuf &ccodes)
+{
+    const int d = ix->d, M = ix->M, P = M / 2;
+    TRY(act1.ensure((size_t)L1 * d * 4));
+    HIPCHECK(hipMemcpy(act1.p, all_centers, (size_t)L1 * d * 4, hipMemcpyHostToDevice));
+    if (center_codes) {
+        const int64_t cc = (L1 + 15) / 16;
+        TRY(coffs.ensure((size_t)cc * M * 8));
+        TRY(ccodes.ensure((size_t)tk_tiled_uint4s(cc, P) * 16));
+        HIPCHECK(hipMemcpy(coffs.p, center_codes, (size_t)cc * M * 8, hipMemcpyHostToDevice));
+        tk_launch_retile(coffs.as<uint4>(), ccodes.as<uint4>(), cc, P, 0);
+        HIPCHECK(hipGetLastError());
+        return TK_OK;
+    }
+    const uint8_t *zc = nullptr;
+    return encode_centres(ix, all_centers, L1, rot, crow, clab, coffs, ccodes, &zc);
+}
+
+// The first half of a removal, which update shares: the n rows (device ids, checked in [0, N) by the caller) become
+// a byte map, every stored entry is flagged keep / drop, the exclusive scan of the flags numbers the kept ones
+// (keep, scan: T0 + 1 entries).  g = the scan at the (list, column) boundaries (cw per list, then the end): the kept
+// entries in front of each.  ioff0 / cols0: the old id offsets and members per (list, boundary).
+static int kept_entries(tk_index *ix, const int64_t *rows_d, int64_t n, const std::vector<int64_t> &ioff0,
+                        const std::vector<int64_t> &cols0, int cw, DevBuf &dead, DevBuf &keep, DevBuf &scan,
+                        DevBuf &tmp, DevBuf &bad, DevBuf &pos_d, DevBuf &gat, std::vector<int64_t> &g)
+{
+    const int64_t L = ix->n_lists, T0 = ix->total_ids, N = ix->N;
+    TRY(dead.ensure((size_t)N));
+    HIPCHECK(hipMemset(dead.p, 0, (size_t)N));
+    TRY(bad.ensure(4));
+    HIPCHECK(hipMemset(bad.p, 0, 4));
+    TRY(keep.ensure((size_t)(T0 + 1) * 8));
+    TRY(scan.ensure((size_t)(T0 + 1) * 8));
+    tk_launch_mark_rows(rows_d, n, dead.as<uint8_t>(), 0);
+    tk_launch_keep_flags(ix->ids.as<int64_t>(), T0, dead.as<uint8_t>(), N, keep.as<long long>(), bad.as<int>(), 0);
+    HIPCHECK(hipGetLastError());
+    size_t tmp_bytes = 0;
+    if (tk_scan_exclusive64(nullptr, &tmp_bytes, nullptr, nullptr, T0 + 1, 0))
+        return fail(TK_ERR_HIP, "scan: size query failed");
+    TRY(tmp.ensure(tmp_bytes));
+    if (tk_scan_exclusive64(tmp.p, &tmp_bytes, keep.as<long long>(), scan.as<long long>(), T0 + 1, 0))
+        return fail(TK_ERR_HIP, "scan failed");
+    // the scan at the (list, column) boundaries
+    std::vector<int64_t> bpos((size_t)(L * cw + 1));
+    g.resize(bpos.size());
+    for (int64_t l = 0; l < L; l++) {
+        int64_t o = ioff0[(size_t)l];
+        for (int t = 0; t < cw; t++) {
+            bpos[(size_t)(l * cw + t)] = o;
+            o += cols0[(size_t)(l * cw + t)];
+        }
+    }
+    bpos.back() = T0;
+    TRY(pos_d.ensure(bpos.size() * 8));
+    TRY(gat.ensure(bpos.size() * 8));
+    HIPCHECK(hipMemcpy(pos_d.p, bpos.data(), bpos.size() * 8, hipMemcpyHostToDevice));
+    tk_launch_gather_scan(scan.as<long long>(), pos_d.as<int64_t>(), (int64_t)bpos.size(), gat.as<int64_t>(), 0);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpy(g.data(), gat.p, g.size() * 8, hipMemcpyDeviceToHost));
+    int bad_h = 0;
+    HIPCHECK(hipMemcpy(&bad_h, bad.p, 4, hipMemcpyDeviceToHost));
+    ARGCHECK(!bad_h, "the index holds labels outside [0, N): its rows cannot be named");
+    return TK_OK;
+}
+
 // New rows merged into the built lists (tinyknn_hip.h).  Everything is validated and built in new buffers
 // first; the index changes only at the end, where nothing can fail any more.
 extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64, int64_t n, int kp,
@@ -404,14 +557,7 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
     HIPCHECK(hipMemcpy(size0.data(), ix->list_n.p, (size_t)L0 * 8, hipMemcpyDeviceToHost));
     std::vector<int64_t> cols0(list_columns ? list_columns : ix->list_cols.data(),
                                (list_columns ? list_columns : ix->list_cols.data()) + L0 * kp);
-    for (int64_t l = 0; l < L0; l++) {
-        int64_t s = 0;
-        for (int t = 0; t < kp; t++) {
-            ARGCHECK(cols0[(size_t)(l * kp + t)] >= 0, "list_columns: negative count");
-            s += cols0[(size_t)(l * kp + t)];
-        }
-        ARGCHECK(s == size0[(size_t)l], "list_columns: a list's columns do not add up to its size");
-    }
+    TRY(check_columns(cols0, size0, L0, kp));
     const size_t esz = data_esz(ix->data_dtype);      // of a stored element; the rows come as float32 / float64
     DevBuf xstage, hflag, grown, yt, yn, near, keys, prow, keys2, rows2, count, lab, rot, tmp, zrow, zlab, crow, clab, coffs,
         act1, ccodes, noff_d, seg_d;
@@ -435,34 +581,11 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
     HIPCHECK(hipMemcpy(Xn, rows, (size_t)n * d * (rows_is_f64 ? 8 : 4), hipMemcpyDefault));
     // ---- 2. nearest centres (given, or as tk_index_build_dev finds them), pairs per (centre, column)
     const int64_t T = n * kp;
-    TRY(near.ensure((size_t)T * 8));
-    if (nearest) {
-        HIPCHECK(hipMemcpy(near.p, nearest, (size_t)T * 8, hipMemcpyHostToDevice));
-        if (normalise) tk_launch_normalise_rows((float *)Xn, n, d, (float *)Xn, 0);
-    } else {
-        TRY(upload_search_centres(yt, yn, search_centers, ynorm2, C, d));
-        assign_rows_dev((float *)Xn, n, d, normalise, yt, yn, C, kp, near.as<int64_t>());
-    }
-    TRY(keys.ensure((size_t)T * 4));
-    TRY(prow.ensure((size_t)T * 4));
-    TRY(count.ensure((size_t)C * kp * 4));
-    HIPCHECK(hipMemset(count.p, 0, (size_t)C * kp * 4));
-    tk_launch_keys_count(near.as<int64_t>(), n, kp, 0, n, keys.as<int>(), prow.as<int>(), count.as<int>(), 0);
-    HIPCHECK(hipGetLastError());
-    std::vector<int> cntc((size_t)C * kp);
-    HIPCHECK(hipMemcpy(cntc.data(), count.p, (size_t)C * kp * 4, hipMemcpyDeviceToHost));
+    std::vector<int> cntc;
+    TRY(new_row_pairs(Xn, n, d, kp, nearest, normalise, search_centers, ynorm2, C, yt, yn, near, keys, prow, count, cntc));
     // ---- 3. the active centres stay a prefix 0 .. L1 - 1 (the build's contract, utils.py:128)
-    int64_t L1 = 0, last = -1;
-    for (int64_t j = 0; j < C; j++) {
-        int64_t c = 0;
-        for (int t = 0; t < kp; t++) c += cntc[(size_t)(j * kp + t)];
-        if (j < L0 || c > 0) {
-            L1++;
-            last = j;
-        }
-    }
-    ARGCHECK(last < L1, "a centre that received no row precedes one that did: the reference's "
-                        "group_data_by_indices asserts max(index) < n_active (utils.py:128)");
+    const int64_t L1 = active_prefix(cntc, C, kp, L0);
+    ARGCHECK(L1 >= 0, PREFIX_REFUSAL);
     ARGCHECK(L1 == L0 || all_centers, "new lists: all_centers");
     // ---- 4. the new layout: list l's column block j = old_j ++ new_j
     std::vector<int64_t> size1((size_t)L1), noff((size_t)L1 + 1, 0), seg((size_t)L1 * kp * 2), cols1((size_t)L1 * kp);
@@ -484,34 +607,9 @@ extern "C" int tk_index_add_rows(tk_index *ix, const void *rows, int rows_is_f64
     // ---- 5. new pairs grouped by list (centre ids are list ids: the active set is a prefix)
     TRY(sort_pairs_dev(keys, prow, keys2, rows2, tmp, T, L1));
     // ---- 6. codes of the new rows (given, or as the build encodes them), of the zero vector, of new centres
-    TRY(lab.ensure((size_t)n * M));
-    if (labels) {
-        HIPCHECK(hipMemcpy(lab.p, labels, (size_t)n * M, hipMemcpyHostToDevice));
-    } else {
-        const int64_t slab = 1 << 20;
-        for (int64_t o = 0; o < n; o += slab)
-            TRY(encode_rows_dev(ix, (const float *)Xn + o * d, n - o < slab ? n - o : slab, rot,
-                                lab.as<uint8_t>() + (size_t)o * M));
-    }
-    TRY(zrow.ensure((size_t)16 * d * 4));
-    TRY(zlab.ensure((size_t)16 * M));
-    HIPCHECK(hipMemset(zrow.p, 0, (size_t)16 * d * 4));
-    TRY(encode_rows_dev(ix, zrow.as<float>(), 16, rot, zlab.as<uint8_t>()));
-    if (L1 > L0) {
-        TRY(act1.ensure((size_t)L1 * d * 4));
-        HIPCHECK(hipMemcpy(act1.p, all_centers, (size_t)L1 * d * 4, hipMemcpyHostToDevice));
-        if (center_codes) {         // the host's codes (pq.transform(active_centers)), retiled
-            const int64_t cc = (L1 + 15) / 16;
-            TRY(coffs.ensure((size_t)cc * M * 8));
-            TRY(ccodes.ensure((size_t)tk_tiled_uint4s(cc, P) * 16));
-            HIPCHECK(hipMemcpy(coffs.p, center_codes, (size_t)cc * M * 8, hipMemcpyHostToDevice));
-            tk_launch_retile(coffs.as<uint4>(), ccodes.as<uint4>(), cc, P, 0);
-            HIPCHECK(hipGetLastError());
-        } else {
-            const uint8_t *zc = nullptr;
-            TRY(encode_centres(ix, all_centers, L1, rot, crow, clab, coffs, ccodes, &zc));
-        }
-    }
+    TRY(new_row_labels(ix, Xn, n, labels, rot, lab));
+    TRY(zero_labels_dev(ix, rot, zrow, zlab));
+    if (L1 > L0) TRY(grown_centres(ix, all_centers, center_codes, L1, rot, crow, clab, coffs, act1, ccodes));
     if (half) {         // what the vectors will hold: every half finite, or nothing changes
         TRY(check_half_rows((const float *)Xn, n, d, N0, hflag));
         tk_launch_narrow_rows((const float *)Xn, n, d, tail, 0);
@@ -569,7 +667,7 @@ extern "C" int tk_index_remove_rows(tk_index *ix, const int64_t *rows, int64_t n
     std::vector<int64_t> rv((size_t)n);
     if (n > 0) HIPCHECK(hipMemcpy(rv.data(), rows, (size_t)n * 8, hipMemcpyDefault));
     for (int64_t i = 0; i < n; i++) ARGCHECK(rv[(size_t)i] >= 0 && rv[(size_t)i] < ix->N, "rows: an id outside [0, N)");
-    const int64_t L = ix->n_lists, T0 = ix->total_ids, N = ix->N;
+    const int64_t L = ix->n_lists, T0 = ix->total_ids;
     // ---- the old layout: list sizes, offsets, members per column (where known)
     std::vector<int64_t> size0((size_t)L), ioff0((size_t)L + 1);
     HIPCHECK(hipMemcpy(size0.data(), ix->list_n.p, (size_t)L * 8, hipMemcpyDeviceToHost));
@@ -577,56 +675,18 @@ extern "C" int tk_index_remove_rows(tk_index *ix, const int64_t *rows, int64_t n
     const int64_t *cols_src = list_columns ? list_columns : (ix->list_kp == kp ? ix->list_cols.data() : nullptr);
     const int cw = cols_src ? kp : 1;     // boundaries per list: its column blocks, or the list alone
     std::vector<int64_t> cols0(cols_src ? cols_src : size0.data(), (cols_src ? cols_src : size0.data()) + L * cw);
-    for (int64_t l = 0; l < L; l++) {
-        int64_t s = 0;
-        for (int t = 0; t < cw; t++) {
-            ARGCHECK(cols0[(size_t)(l * cw + t)] >= 0, "list_columns: negative count");
-            s += cols0[(size_t)(l * cw + t)];
-        }
-        ARGCHECK(s == size0[(size_t)l], "list_columns: a list's columns do not add up to its size");
-    }
+    TRY(check_columns(cols0, size0, L, cw));
     if (n == 0) return TK_OK;
     TRY(settle_lists(ix));
     DevBuf rows_d, dead, keep, scan, tmp, bad, pos_d, gat, src, rot, zrow, zlab, cnt, summ;
     BufCleanup cl{{&rows_d, &dead, &keep, &scan, &tmp, &bad, &pos_d, &gat, &src, &rot, &zrow, &zlab, &cnt, &summ}};
     ListLayout lay;
-    // ---- 1. the dead rows, keep / drop per stored entry, its exclusive scan (new positions)
+    // ---- 1. + 2. the dead rows, keep / drop per stored entry, its exclusive scan (new positions), the scan at the
+    //              (list, column) boundaries: new sizes, offsets and columns
     TRY(rows_d.ensure((size_t)n * 8));
     HIPCHECK(hipMemcpy(rows_d.p, rv.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    TRY(dead.ensure((size_t)N));
-    HIPCHECK(hipMemset(dead.p, 0, (size_t)N));
-    TRY(bad.ensure(4));
-    HIPCHECK(hipMemset(bad.p, 0, 4));
-    TRY(keep.ensure((size_t)(T0 + 1) * 8));
-    TRY(scan.ensure((size_t)(T0 + 1) * 8));
-    tk_launch_mark_rows(rows_d.as<int64_t>(), n, dead.as<uint8_t>(), 0);
-    tk_launch_keep_flags(ix->ids.as<int64_t>(), T0, dead.as<uint8_t>(), N, keep.as<long long>(), bad.as<int>(), 0);
-    HIPCHECK(hipGetLastError());
-    size_t tmp_bytes = 0;
-    if (tk_scan_exclusive64(nullptr, &tmp_bytes, nullptr, nullptr, T0 + 1, 0))
-        return fail(TK_ERR_HIP, "scan: size query failed");
-    TRY(tmp.ensure(tmp_bytes));
-    if (tk_scan_exclusive64(tmp.p, &tmp_bytes, keep.as<long long>(), scan.as<long long>(), T0 + 1, 0))
-        return fail(TK_ERR_HIP, "scan failed");
-    // ---- 2. the scan at the (list, column) boundaries: new sizes, offsets and columns
-    std::vector<int64_t> bpos((size_t)(L * cw + 1)), g(bpos.size());
-    for (int64_t l = 0; l < L; l++) {
-        int64_t o = ioff0[(size_t)l];
-        for (int t = 0; t < cw; t++) {
-            bpos[(size_t)(l * cw + t)] = o;
-            o += cols0[(size_t)(l * cw + t)];
-        }
-    }
-    bpos.back() = T0;
-    TRY(pos_d.ensure(bpos.size() * 8));
-    TRY(gat.ensure(bpos.size() * 8));
-    HIPCHECK(hipMemcpy(pos_d.p, bpos.data(), bpos.size() * 8, hipMemcpyHostToDevice));
-    tk_launch_gather_scan(scan.as<long long>(), pos_d.as<int64_t>(), (int64_t)bpos.size(), gat.as<int64_t>(), 0);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpy(g.data(), gat.p, g.size() * 8, hipMemcpyDeviceToHost));
-    int bad_h = 0;
-    HIPCHECK(hipMemcpy(&bad_h, bad.p, 4, hipMemcpyDeviceToHost));
-    ARGCHECK(!bad_h, "the index holds labels outside [0, N): its rows cannot be named");
+    std::vector<int64_t> g;
+    TRY(kept_entries(ix, rows_d.as<int64_t>(), n, ioff0, cols0, cw, dead, keep, scan, tmp, bad, pos_d, gat, g));
     const int64_t T1 = g.back();
     if (T1 == T0) return TK_OK;     // nothing stored was named: the index stays exactly as it is
     std::vector<int64_t> size1((size_t)L), cols1((size_t)(L * cw));
@@ -638,10 +698,7 @@ extern "C" int tk_index_remove_rows(tk_index *ix, const int64_t *rows, int64_t n
     TRY(src.ensure((size_t)(T1 > 0 ? T1 : 1) * 4));
     tk_launch_scatter_kept(keep.as<long long>(), scan.as<long long>(), T0, src.as<int>(), 0);
     HIPCHECK(hipGetLastError());
-    TRY(zrow.ensure((size_t)16 * ix->d * 4));
-    TRY(zlab.ensure((size_t)16 * ix->M));
-    HIPCHECK(hipMemset(zrow.p, 0, (size_t)16 * ix->d * 4));
-    TRY(encode_rows_dev(ix, zrow.as<float>(), 16, rot, zlab.as<uint8_t>()));
+    TRY(zero_labels_dev(ix, rot, zrow, zlab));
     // ---- 4. the compacted lists (their small arrays are allocated while the kernels above run)
     TRY(lay.set_sizes(size1.data(), L));
     const int64_t chunks1 = lay.total_chunks;
@@ -672,6 +729,166 @@ extern "C" int tk_index_remove_rows(tk_index *ix, const int64_t *rows, int64_t n
     // ---- 6. the swap: the old buffers go with the layout
     TRY(install_lists(ix, lay));
     if (removed_out) *removed_out = T0 - T1;
+    return TK_OK;
+}
+
+// Stored rows replaced in place, ids kept (tinyknn_hip.h): tk_index_remove_rows of the ids and tk_index_add_rows of
+// the rows in one pass over the code array, the new entries labelled ids[i] and their vectors written over rows
+// ids[i].  The order matters, because this is the one list change that overwrites live vectors: (1) the checks;
+// (2) settle_lists, so that batches in flight finish on the old lists AND the old vectors (as in add and remove it
+// comes before the call's own device work, which then runs on an idle device); (3) the rows staged in a scratch
+// buffer — never in the live store — and prepared, assigned, coded and (half store) checked there; (4) the new lists
+// built completely in new buffers, what the labels say derived from them (row_copies, as the removal does), the
+// device synchronised; (5) only then, behind the last point that can fail, the scatter into the store and the swap.
+extern "C" int tk_index_update_rows(tk_index *ix, const int64_t *ids, int64_t n, const void *rows, int rows_is_f64,
+                                    int kp, const int64_t *nearest, const uint8_t *labels,
+                                    const int64_t *list_columns, int normalise, const float *all_centers,
+                                    const float *search_centers, const float *ynorm2, int64_t C,
+                                    const uint64_t *center_codes, int64_t *n_active_out, int64_t *removed_out)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix && ix->have_pq && ix->have_centers && ix->have_lists && ix->have_data, "a complete index");
+    ARGCHECK(!ix->sharded, "a list-sharded index replaces no rows");
+    ARGCHECK(n >= 0 && (n == 0 || (rows && ids)), "ids / rows");
+    ARGCHECK(kp >= 1 && kp <= 9, "kp (lists per row) must be 1 .. 9");
+    ARGCHECK(!rows_is_f64 == (ix->data_dtype != TK_DATA_F64),
+             "float64 rows only for an index of float64 vectors (float32 rows for float32 and half vectors)");
+    const bool half = ix->data_dtype == TK_DATA_F16;
+    {
+        bool sit = false;
+        TRY(rows_sit_in(ix, kp, &sit));
+        ARGCHECK(sit, "kp: every stored row sits in kp lists");
+    }
+    ARGCHECK(list_columns || ix->list_kp == kp,
+             "list_columns: the index does not know its members per (list, column) (a host upload)");
+    ARGCHECK(C >= ix->n_lists && C >= kp && C < (1ll << 31), "C: the number of centres");
+    ARGCHECK(ix->N < (1ll << 31) && ix->total_ids < (1ll << 31) && ix->total_ids + n * kp < (1ll << 31),
+             "N and the stored entries (+ n * kp) < 2^31");
+    const int d = ix->d, M = ix->M, P = M / 2;
+    if (!search_centers) search_centers = all_centers;
+    ARGCHECK(nearest || (all_centers && ynorm2 && !rows_is_f64 && d <= 384 && (!normalise || d <= 128)),
+             "device assignment: all_centers + ynorm2, float32 rows, d <= 384 (128 with normalisation)");
+    ARGCHECK(!normalise || !rows_is_f64, "normalisation on the device: float32 rows");
+    ARGCHECK(labels || !rows_is_f64, "device encoding: float32 rows (else pass labels)");
+    ARGCHECK(16 % ix->dpb == 0, "dims_per_block must divide 16 for the device encoder");
+    if (nearest)
+        for (int64_t i = 0; i < n * kp; i++) ARGCHECK(nearest[i] >= 0 && nearest[i] < C, "nearest: a centre id");
+    const int64_t L0 = ix->n_lists, T0 = ix->total_ids, N = ix->N;
+    std::vector<int64_t> idv((size_t)n);
+    if (n > 0) HIPCHECK(hipMemcpy(idv.data(), ids, (size_t)n * 8, hipMemcpyDefault));
+    {
+        std::vector<uint8_t> named((size_t)N, 0);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t r = idv[(size_t)i];
+            ARGCHECK(r >= 0 && r < N, "ids: an id outside [0, N)");
+            ARGCHECK(!named[(size_t)r], "ids: an id named twice");
+            named[(size_t)r] = 1;
+        }
+    }
+    if (n_active_out) *n_active_out = L0;
+    if (removed_out) *removed_out = 0;
+    if (n == 0) return TK_OK;
+    TRY(settle_lists(ix));
+    // ---- the old layout: list sizes, offsets, members per column
+    std::vector<int64_t> size0((size_t)L0), ioff0((size_t)L0 + 1);
+    HIPCHECK(hipMemcpy(size0.data(), ix->list_n.p, (size_t)L0 * 8, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(ioff0.data(), ix->ids_off.p, (size_t)(L0 + 1) * 8, hipMemcpyDeviceToHost));
+    std::vector<int64_t> cols0(list_columns ? list_columns : ix->list_cols.data(),
+                               (list_columns ? list_columns : ix->list_cols.data()) + L0 * kp);
+    TRY(check_columns(cols0, size0, L0, kp));
+    DevBuf xstage, hflag, ids_d, dead, keep, scan, stmp, bad, pos_d, gat, src, yt, yn, near, keys, prow, keys2, rows2, count,
+        lab, rot, tmp, zrow, zlab, crow, clab, coffs, act1, ccodes, noff_d, seg_d, koff_d, cnt, summ;
+    BufCleanup cl{{&xstage, &hflag, &ids_d, &dead, &keep, &scan, &stmp, &bad, &pos_d, &gat, &src, &yt, &yn, &near, &keys, &prow,
+                   &keys2, &rows2, &count, &lab, &rot, &tmp, &zrow, &zlab, &crow, &clab, &coffs, &act1, &ccodes, &noff_d,
+                   &seg_d, &koff_d, &cnt, &summ}};
+    ListLayout lay;
+    // ---- 1. the rows in a scratch buffer; nearest centres, pairs per (centre, column); what a half store will hold
+    TRY(xstage.ensure((size_t)n * d * (rows_is_f64 ? 8 : 4)));
+    void *Xn = xstage.p;
+    HIPCHECK(hipMemcpy(Xn, rows, (size_t)n * d * (rows_is_f64 ? 8 : 4), hipMemcpyDefault));
+    const int64_t T = n * kp;
+    std::vector<int> cntc;
+    TRY(new_row_pairs(Xn, n, d, kp, nearest, normalise, search_centers, ynorm2, C, yt, yn, near, keys, prow, count, cntc));
+    const int64_t L1 = active_prefix(cntc, C, kp, L0);
+    ARGCHECK(L1 >= 0, PREFIX_REFUSAL);
+    ARGCHECK(L1 == L0 || all_centers, "new lists: all_centers");
+    if (half) TRY(check_half_rows((const float *)Xn, n, d, 0, hflag));     // (names the row of `rows`, not an id)
+    // ---- 2. the entries that stay: keep / drop per stored entry, the scan, the old position of every kept one
+    TRY(ids_d.ensure((size_t)n * 8));
+    HIPCHECK(hipMemcpy(ids_d.p, idv.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    std::vector<int64_t> g;
+    TRY(kept_entries(ix, ids_d.as<int64_t>(), n, ioff0, cols0, kp, dead, keep, scan, stmp, bad, pos_d, gat, g));
+    const int64_t Tk = g.back();
+    TRY(src.ensure((size_t)(Tk > 0 ? Tk : 1) * 4));
+    tk_launch_scatter_kept(keep.as<long long>(), scan.as<long long>(), T0, src.as<int>(), 0);
+    HIPCHECK(hipGetLastError());
+    // ---- 3. the new layout: list l's column block j = kept_j ++ new_j
+    std::vector<int64_t> size1((size_t)L1), noff((size_t)L1 + 1, 0), koff((size_t)L1 + 1, Tk), seg((size_t)L1 * kp * 2),
+        cols1((size_t)L1 * kp);
+    for (int64_t l = 0; l < L1; l++) {
+        int64_t s = 0, sn = 0;
+        if (l < L0) koff[(size_t)l] = g[(size_t)(l * kp)];
+        for (int t = 0; t < kp; t++) {
+            const int64_t o = l < L0 ? g[(size_t)(l * kp + t) + 1] - g[(size_t)(l * kp + t)] : 0;
+            const int64_t nn = cntc[(size_t)(l * kp + t)];
+            seg[(size_t)(l * kp + t) * 2] = o;
+            seg[(size_t)(l * kp + t) * 2 + 1] = nn;
+            cols1[(size_t)(l * kp + t)] = o + nn;
+            s += o + nn;
+            sn += nn;
+        }
+        size1[(size_t)l] = s;
+        noff[(size_t)l + 1] = noff[(size_t)l] + sn;
+    }
+    TRY(lay.set_sizes(size1.data(), L1));
+    const int64_t chunks1 = lay.total_chunks, T1 = lay.total_ids;       // (T1 = Tk + n * kp > 0)
+    // ---- 4. new pairs grouped by list; codes of the new rows, of the zero vector, of new centres
+    TRY(sort_pairs_dev(keys, prow, keys2, rows2, tmp, T, L1));
+    TRY(new_row_labels(ix, Xn, n, labels, rot, lab));
+    TRY(zero_labels_dev(ix, rot, zrow, zlab));
+    if (L1 > L0) TRY(grown_centres(ix, all_centers, center_codes, L1, rot, crow, clab, coffs, act1, ccodes));
+    // ---- 5. the new lists: the old code array is read once, the new one written once
+    TRY(noff_d.ensure(noff.size() * 8));
+    TRY(koff_d.ensure(koff.size() * 8));
+    TRY(seg_d.ensure(seg.size() * 8));
+    HIPCHECK(hipMemcpy(noff_d.p, noff.data(), noff.size() * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(koff_d.p, koff.data(), koff.size() * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(seg_d.p, seg.data(), seg.size() * 8, hipMemcpyHostToDevice));
+    const size_t tiled_bytes = (size_t)tk_tiled_uint4s(chunks1, P) * 16;
+    TRY(lay.codes.ensure(tiled_bytes));
+    HIPCHECK(hipMemset(lay.codes.p, 0, tiled_bytes));
+    TRY(lay.ids.ensure((size_t)T1 * 8));
+    const bool want32 = kp > 1 || ix->have_ids32;
+    if (want32) TRY(lay.ids32.ensure((size_t)T1 * 4));
+    tk_launch_replace_lists(ix->codes.as<uint4>(), ix->list_chunk_off.as<int64_t>(), ix->ids_off.as<int64_t>(),
+                            ix->ids.as<int64_t>(), (int)L0, src.as<int>(), koff_d.as<int64_t>(), lab.as<uint8_t>(), M,
+                            rows2.as<int>(), ids_d.as<int64_t>(), noff_d.as<int64_t>(), seg_d.as<int64_t>(), kp,
+                            lay.list_chunk_off.as<int64_t>(), lay.ids_off.as<int64_t>(), lay.list_n.as<int64_t>(), (int)L1,
+                            zlab.as<uint8_t>(), lay.codes.as<uint4>(), lay.ids.as<int64_t>(),
+                            want32 ? lay.ids32.as<int32_t>() : nullptr, chunks1, 0);
+    HIPCHECK(hipGetLastError());
+    // ---- 6. what tk_index_set_lists derives from the labels (as the removal): distinct?  the largest?
+    int cs[4];
+    TRY(row_copies(ix, lay.ids.as<int64_t>(), T1, cnt, summ, cs));
+    HIPCHECK(hipDeviceSynchronize());
+    lay.ids_unique = cs[1] <= 1;
+    lay.have_ids32 = want32 && !lay.ids_unique;
+    lay.max_label = cs[0];
+    lay.list_cols = cols1;
+    lay.kp = kp;
+    // ---- 7. nothing fails from here on (a launch into buffers that exist; set_centre_slots: a few bytes that
+    //         exist): the vectors over the old rows', the swap
+    tk_launch_scatter_rows(Xn, n, d, ids_d.as<int64_t>(), ix->data.p, ix->data_dtype, 0);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());       // (ids_d and the scratch rows leave with this call)
+    if (L1 > L0) {
+        std::swap(ix->active_centers, act1);
+        std::swap(ix->center_codes, ccodes);
+        TRY(set_centre_slots(ix, L1, (L1 + 15) / 16));
+    }
+    TRY(install_lists(ix, lay));
+    if (n_active_out) *n_active_out = L1;
+    if (removed_out) *removed_out = T0 - Tk;
     return TK_OK;
 }
 

@@ -531,6 +531,139 @@ void tk_launch_compact_lists(const uint4 *old_tiled, const int64_t *old_chunk_of
                        tiled, ids, ids32, total_chunks);
 }
 
+// Stored rows replaced in built lists (tk_index_update_rows): the removal's compaction and the addition's merge in
+// one pass.  List l's column-j block becomes (old_j minus the replaced rows, old order kept) ++ new_j.
+// seg[(l * kp + j) * 2 + {0, 1}] = (kept, new) members of that block.  The kept ones are numbered as the removal
+// numbers them — kept entry kept_off[l] + sum_{j' < j} kept_j' + q of the compacted order, whose old global position
+// is src[] (scatter_kept's output; in the same list: the scan keeps list boundaries) — the new ones sit at
+// sorted-pair positions new_off[l] + sum_{j' < j} new_j' (rows_sorted, as merge_lists_kernel reads it).  One thread
+// per (output chunk, block pair): a kept member copies the packed byte and the label of its old position, a new
+// member packs labels_new[row][2p .. 2p + 1] and takes the label new_ids[row]; nothing old is decoded or re-encoded,
+// padding rows take the zero vector's code.  Removed entries leave gaps between the old positions of consecutive
+// kept members: the old chunk held in `cur` is named by cur_oc and fetched again only when the position leaves it, so
+// a chunk is read once per thread however many of its rows went (as in compact_lists_kernel).  Lists past the old
+// ones (l >= n_old_lists) have no kept member and read nothing old.  The p == 0 thread writes ids and ids32.
+__global__ void replace_lists_kernel(const uint4 *__restrict__ old_tiled, const int64_t *__restrict__ old_chunk_off,
+                                     const int64_t *__restrict__ old_ids_off, const int64_t *__restrict__ old_ids,
+                                     int n_old_lists, const int *__restrict__ src, const int64_t *__restrict__ kept_off,
+                                     const uint8_t *__restrict__ labels_new, int M, const int *__restrict__ rows_sorted,
+                                     const int64_t *__restrict__ new_ids, const int64_t *__restrict__ new_off,
+                                     const int64_t *__restrict__ seg, int kp, const int64_t *__restrict__ chunk_off,
+                                     const int64_t *__restrict__ ids_off, const int64_t *__restrict__ list_n,
+                                     int n_lists, const uint8_t *__restrict__ zero_code, uint4 *__restrict__ tiled,
+                                     int64_t *__restrict__ ids, int32_t *__restrict__ ids32, int64_t total_chunks)
+{
+    const int P = M >> 1;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total_chunks * P) return;
+    const int64_t c = i / P;
+    const int p = (int)(i - c * P);
+    int lo = 0, hi = n_lists;   // chunk_off[lo] <= c < chunk_off[lo + 1] (empty lists are stepped over)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (chunk_off[mid] <= c) lo = mid; else hi = mid;
+    }
+    const int64_t pos0 = 16 * (c - chunk_off[lo]);
+    const int64_t n_l = list_n[lo], g0 = ids_off[lo];
+    const bool had = lo < n_old_lists;
+    const int64_t og0 = had ? old_ids_off[lo] : 0, oc0 = had ? old_chunk_off[lo] : 0, k0 = had ? kept_off[lo] : 0;
+    const int64_t *sg = seg + (int64_t)lo * kp * 2;
+    const uint32_t zb = (uint32_t)zero_code[2 * p] | ((uint32_t)zero_code[2 * p + 1] << 4);
+    uint32_t w[4] = {0, 0, 0, 0};
+    int64_t cur_oc = -1;                  // the old chunk held in `cur` (kept neighbours mostly share one, gaps or not)
+    uint4 cur = make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        uint32_t b = zb;
+        const int64_t pos = pos0 + r;
+        if (pos < n_l) {
+            int64_t q = pos, kbase = k0, nbase = new_off[lo];
+            int64_t kept_at = -1, new_at = -1;
+            for (int t = 0; t < kp; t++) {
+                const int64_t o = sg[2 * t], nn = sg[2 * t + 1];
+                if (q < o) { kept_at = kbase + q; break; }
+                q -= o;
+                if (q < nn) { new_at = nbase + q; break; }
+                q -= nn;
+                kbase += o;
+                nbase += nn;
+            }
+            int64_t label = -1;
+            if (kept_at >= 0 && had) {
+                const int64_t og = src[kept_at];
+                const int64_t old_pos = og - og0;
+                const int64_t oc = oc0 + (old_pos >> 4);
+                if (oc != cur_oc) {
+                    cur = old_tiled[((oc >> 3) * P + p) * 8 + (oc & 7)];
+                    cur_oc = oc;
+                }
+                const int rr = (int)(old_pos & 15);
+                const uint32_t word = rr < 4 ? cur.x : (rr < 8 ? cur.y : (rr < 12 ? cur.z : cur.w));
+                b = (word >> (8 * (rr & 3))) & 0xffu;
+                if (p == 0) label = old_ids[og];
+            } else if (new_at >= 0) {
+                const int64_t row = rows_sorted[new_at];
+                const uint8_t *lab = labels_new + row * M + 2 * p;
+                b = (uint32_t)lab[0] | ((uint32_t)lab[1] << 4);
+                if (p == 0) label = new_ids[row];
+            }
+            if (p == 0) {
+                ids[g0 + pos] = label;
+                if (ids32) ids32[g0 + pos] = (int32_t)label;
+            }
+        }
+        w[r >> 2] |= b << (8 * (r & 3));
+    }
+    tiled[((c >> 3) * P + p) * 8 + (c & 7)] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+void tk_launch_replace_lists(const uint4 *old_tiled, const int64_t *old_chunk_off, const int64_t *old_ids_off,
+                             const int64_t *old_ids, int n_old_lists, const int *src, const int64_t *kept_off,
+                             const uint8_t *labels_new, int M, const int *rows_sorted, const int64_t *new_ids,
+                             const int64_t *new_off, const int64_t *seg, int kp, const int64_t *chunk_off,
+                             const int64_t *ids_off, const int64_t *list_n, int n_lists, const uint8_t *zero_code,
+                             uint4 *tiled, int64_t *ids, int32_t *ids32, int64_t total_chunks, hipStream_t s)
+{
+    const int64_t items = total_chunks * (M / 2);
+    if (items <= 0) return;
+    hipLaunchKernelGGL(replace_lists_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, old_tiled,
+                       old_chunk_off, old_ids_off, old_ids, n_old_lists, src, kept_off, labels_new, M, rows_sorted,
+                       new_ids, new_off, seg, kp, chunk_off, ids_off, list_n, n_lists, zero_code, tiled, ids, ids32,
+                       total_chunks);
+}
+
+// The replaced rows' vectors: staged row i (prepared, row-major (n, d)) goes to row new_ids[i] of the store.  One
+// thread per element, consecutive threads along d (a wave writes one row's consecutive elements, or the ends of two);
+// the ids are distinct (checked by the caller), so no two staged rows meet.  TX -> TY: float -> float and
+// double -> double copy; float -> _Float16 is narrow_rows_kernel's conversion (round-to-nearest-even, subnormals kept).
+template <typename TX, typename TY>
+__global__ __launch_bounds__(256) void scatter_rows_kernel(const TX *__restrict__ X, int64_t n, int d,
+                                                           const int64_t *__restrict__ new_ids, TY *__restrict__ data)
+{
+    const int64_t total = n * d, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int64_t r = i / d;
+        data[new_ids[r] * d + (i - r * d)] = (TY)X[i];
+    }
+}
+
+void tk_launch_scatter_rows(const void *X, int64_t n, int d, const int64_t *new_ids, void *data, int data_dtype,
+                            hipStream_t s)
+{
+    if (n <= 0) return;
+    const int64_t total = n * d;
+    const dim3 grid((unsigned)(total / 256 + 1 < 8192 ? total / 256 + 1 : 8192)), block(256);
+    if (data_dtype == 2)
+        hipLaunchKernelGGL((scatter_rows_kernel<float, _Float16>), grid, block, 0, s, (const float *)X, n, d, new_ids,
+                           (_Float16 *)data);
+    else if (data_dtype == 1)
+        hipLaunchKernelGGL((scatter_rows_kernel<double, double>), grid, block, 0, s, (const double *)X, n, d, new_ids,
+                           (double *)data);
+    else
+        hipLaunchKernelGGL((scatter_rows_kernel<float, float>), grid, block, 0, s, (const float *)X, n, d, new_ids,
+                           (float *)data);
+}
+
 // Copies per row of the stored labels: cnt[row] += 1 per entry (cnt: N ints, zeroed); a label outside [0, N) is
 // counted in *outside instead.
 __global__ void row_copies_kernel(const int64_t *__restrict__ ids, int64_t T, int64_t N, int *__restrict__ cnt,

@@ -467,6 +467,20 @@ void tk_launch_compact_lists(const uint4 *old_tiled, const int64_t *old_chunk_of
                              const int64_t *old_ids, const int *src, int M, const int64_t *chunk_off,
                              const int64_t *ids_off, const int64_t *list_n, int n_lists, const uint8_t *zero_code,
                              uint4 *tiled, int64_t *ids, int32_t *ids32, int64_t total_chunks, hipStream_t s);
+// built lists - replaced rows + their new versions -> the new lists in one pass (tk_index_update_rows; devbuild.hip
+// replace_lists_kernel): src / kept_off number the kept entries as the removal does (kept_off[l]: kept entries in
+// front of old list l), labels_new / rows_sorted / new_off / seg describe the new rows as for the merge (seg's first
+// of a pair = KEPT members of the column block), new_ids[row] = the label a new row carries
+void tk_launch_replace_lists(const uint4 *old_tiled, const int64_t *old_chunk_off, const int64_t *old_ids_off,
+                             const int64_t *old_ids, int n_old_lists, const int *src, const int64_t *kept_off,
+                             const uint8_t *labels_new, int M, const int *rows_sorted, const int64_t *new_ids,
+                             const int64_t *new_off, const int64_t *seg, int kp, const int64_t *chunk_off,
+                             const int64_t *ids_off, const int64_t *list_n, int n_lists, const uint8_t *zero_code,
+                             uint4 *tiled, int64_t *ids, int32_t *ids32, int64_t total_chunks, hipStream_t s);
+// staged rows X (n, d) — float32, or float64 where data_dtype is TK_DATA_F64 — written to rows new_ids[i] (distinct,
+// in range) of the stored vectors; TK_DATA_F16: narrowed as tk_launch_narrow_rows narrows
+void tk_launch_scatter_rows(const void *X, int64_t n, int d, const int64_t *new_ids, void *data, int data_dtype,
+                            hipStream_t s);
 // copies per row of T labels into cnt (N ints, zeroed); out = {largest row stored, most copies, fewest copies of a
 // stored row, labels outside [0, N)}, {-1, 0, INT_MAX, 0} on entry
 void tk_launch_row_copies(const int64_t *ids, int64_t T, int *cnt, int64_t N, int *out, hipStream_t s);

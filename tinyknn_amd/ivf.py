@@ -179,6 +179,17 @@ def removal_rows(ids_or_mask, N):
     return np.ascontiguousarray(np.flatnonzero(a), dtype=np.int64) if is_mask else a
 
 
+def update_ids(ids, N):
+    """int64 row ids of update()'s argument: a 1-d integer array of ids in [0, N), pairwise distinct (TypeError for
+    another kind of value — a bool mask names no order —, ValueError for an id outside or named twice)."""
+    is_mask, a = _mask_or_ids(ids, N, "update", "a 1-d integer array of row ids")
+    if is_mask:
+        raise TypeError("update: a 1-d integer array of row ids (a mask does not say which row takes which vector)")
+    if len(np.unique(a)) != len(a):
+        raise ValueError("update: row ids must be pairwise distinct")
+    return a
+
+
 def group_ids(groups, n, what):
     """The int32 group ids a `groups` argument is: a 1-d integer array of length n, every id in [0, 2**31 - 1)
     (TypeError for another kind of value, ValueError for another length or an id outside)."""
@@ -577,6 +588,49 @@ class DeviceIndex:
         if rows.ndim != 2 or rows.shape[1] != self.d:
             raise AssertionError(f"add: rows must have shape (n, {self.d}), got {rows.shape}")
         n, kp = rows.shape[0], int(kp)
+        near_p, lab_p, cols_p, cc_p, A, Y, yn, C_, keep = self._new_row_args("add", n, kp, nearest, labels,
+                                                                           list_columns, all_centers, center_codes)
+        n_active = C.c_int64(0)
+        _half_refusal(
+            _lib.lib().tk_index_add_rows,
+            self._h, rows.ctypes.data, int(is64), n, kp, near_p, lab_p, cols_p, int(bool(normalise)),
+            None if A is None else A.ctypes.data, None if Y is None else Y.ctypes.data,
+            None if yn is None else yn.ctypes.data, C_, cc_p, C.byref(n_active))
+        self.n_lists = int(n_active.value)
+        self._refresh_lists()
+        return self.n_lists
+
+    def update(self, ids, rows, kp, nearest=None, labels=None, list_columns=None, normalise=False, all_centers=None,
+               center_codes=None):
+        """Replace the stored rows `ids` (distinct, in [0, N)) by `rows` (n, d) in place, ids kept
+        (tk_index_update_rows) -> n_lists: remove(ids) and add(rows) in one pass over the code array, the new
+        entries labelled ids[i], their vectors written over rows ids[i]; N and the store's size stay.  The other
+        arguments as in add().  Batches in flight finish first, on the old lists and the old vectors; allowed sets
+        made before stop working.  ValueError for an id outside [0, N) or named twice, or (a half index) a row
+        whose half is not finite; a refused call changes neither the lists nor the vectors."""
+        self._lists_may_change("update", "replaces no rows")
+        ids = update_ids(ids, self.N)
+        is64 = self._f64
+        rows = np.ascontiguousarray(rows, dtype=np.float64 if is64 else np.float32)
+        if rows.ndim != 2 or rows.shape != (len(ids), self.d):
+            raise AssertionError(f"update: rows must have shape ({len(ids)}, {self.d}), got {rows.shape}")
+        n, kp = rows.shape[0], int(kp)
+        near_p, lab_p, cols_p, cc_p, A, Y, yn, C_, keep = self._new_row_args("update", n, kp, nearest, labels,
+                                                                           list_columns, all_centers, center_codes)
+        n_active, removed = C.c_int64(0), C.c_int64(0)
+        _half_refusal(
+            _lib.lib().tk_index_update_rows,
+            self._h, ids.ctypes.data, n, rows.ctypes.data, int(is64), kp, near_p, lab_p, cols_p, int(bool(normalise)),
+            None if A is None else A.ctypes.data, None if Y is None else Y.ctypes.data,
+            None if yn is None else yn.ctypes.data, C_, cc_p, C.byref(n_active), C.byref(removed))
+        self.n_lists = int(n_active.value)
+        self._refresh_lists()
+        return self.n_lists
+
+    def _new_row_args(self, what, n, kp, nearest, labels, list_columns, all_centers, center_codes):
+        """The optional arguments add and update share, as the library takes them: the addresses of nearest (n, kp),
+        labels (n, M), list_columns (n_lists, kp) and center_codes (None: None), the centres (all_centers, the ones
+        the assignment searches, their norms; None: None) and their number, and the arrays to keep alive."""
         keep = []
 
         def opt(a, dtype, shape=None):
@@ -584,7 +638,7 @@ class DeviceIndex:
                 return None
             a = np.ascontiguousarray(a, dtype=dtype)
             if shape is not None and a.shape != shape:
-                raise AssertionError(f"add: expected shape {shape}, got {a.shape}")
+                raise AssertionError(f"{what}: expected shape {shape}, got {a.shape}")
             keep.append(a)
             return a.ctypes.data
 
@@ -597,18 +651,10 @@ class DeviceIndex:
         if all_centers is not None:
             A, Y, yn = self._search_centres(all_centers)
             C_ = len(A)
-        n_active = C.c_int64(0)
-        _half_refusal(
-            _lib.lib().tk_index_add_rows,
-            self._h, rows.ctypes.data, int(is64), n, kp, near_p, lab_p, cols_p, int(bool(normalise)),
-            None if A is None else A.ctypes.data, None if Y is None else Y.ctypes.data,
-            None if yn is None else yn.ctypes.data, C_, cc_p, C.byref(n_active))
-        self.n_lists = int(n_active.value)
-        self._refresh_lists()
-        return self.n_lists
+        return near_p, lab_p, cols_p, cc_p, A, Y, yn, C_, keep
 
     def _lists_may_change(self, what, sharded):
-        """The refusals of add / remove: a list-sharded index or its clones, an open stream() session (the internal
+        """The refusals of add / remove / update: a list-sharded index or its clones, an open stream() session (the internal
         sessions of query_raw are closed: made again on demand)."""
         if _dev_is_sharded(self) or self._source is not None:
             raise RuntimeError(f"DeviceIndex.{what}: a list-sharded index {sharded}")
@@ -1624,7 +1670,12 @@ class IVF:
             self.list_columns = cols
         return cols
 
-    def _add_host(self, X, verbose):
+    def _prepared_rows(self, X, what, row0, verbose):
+        """New rows as the host build prepares its rows (ivf.py:77-102), for add and update on a host-built index ->
+        (rows in IVF.data's dtype, normalised; nearest (n, kp); PQ labels (n, M); the members per (list, column)
+        now; lists afterwards; the active centres and their codes afterwards — the index's own where no list is
+        new).  A half store refuses a row whose half is not finite here, naming row0 + its row, before anything
+        changes (the device rounds its copy)."""
         device = _fp.device_build if self._build_device is None else self._build_device
         kp = self._lists_per_row()
         L0 = len(self.active_centers)
@@ -1632,8 +1683,8 @@ class IVF:
         new = np.array(X, dtype=self.data.dtype, copy=True)         # ivf.py:77-79: X's dtype, normalised
         if self.metric == "angular":
             new /= np.linalg.norm(new, axis=1, keepdims=True)
-        if self.store == "float16":         # (the refusal, before anything changes; the device rounds its copy)
-            half_rows(new, "IVF.add", row0=len(self.data))
+        if self.store == "float16":
+            half_rows(new, f"IVF.{what}", row0=row0)
         with timer(verbose, "Computing nearest clusters..."):
             if device:
                 nearest = self._nearest_on_device(new, kp)
@@ -1646,21 +1697,24 @@ class IVF:
         L1 = len(used)
         with timer(verbose, "Transforming points..."):
             labels = self._labels_of(new, device)
-        centers = self.pq_transformed_centers
+        active, centers = self.active_centers, self.pq_transformed_centers
         if L1 > L0:
             active = np.ascontiguousarray(self.all_centers[:L1], dtype=np.float32)
             centers = self.pq.transform(active, device=device)
+        return new, nearest, labels, cols0, L1, active, centers
+
+    def _add_host(self, X, verbose):
+        new, nearest, labels, cols0, L1, active, centers = self._prepared_rows(X, "add", len(self.data), verbose)
+        kp, grown = nearest.shape[1], L1 > len(self.active_centers)
 
         def on_device(dev):
             dev.add(new, kp, nearest=nearest, labels=labels, list_columns=cols0,
-                    all_centers=self.all_centers if L1 > L0 else None,
-                    center_codes=centers.packed if L1 > L0 else None)
+                    all_centers=self.all_centers if grown else None,
+                    center_codes=centers.packed if grown else None)
             return True
 
         self._change_lists("add", on_device, lambda: self._splice(new, nearest, labels, cols0, L1))
-        if L1 > L0:
-            self.active_centers = active
-            self.pq_transformed_centers = centers
+        self.active_centers, self.pq_transformed_centers = active, centers
         self.data = np.concatenate([self.data, new])
         return self
 
@@ -1691,11 +1745,15 @@ class IVF:
         self.ids = idl + list(self.ids[len(idl):])
         self.list_columns = cols
 
-    def _splice(self, new, nearest, labels, cols0, L1):
+    def _splice(self, new, nearest, labels, cols0, L1, old=None, new_ids=None):
         """The lists after add() in numpy: list l's column-j block = old_j ++ (new rows with nearest[:, j] == l,
-        ascending); untouched lists are kept as they are."""
-        N0, kp = len(self.data), nearest.shape[1]
+        ascending); untouched lists are kept as they are.  old: (codes per list, ids per list) to splice into
+        (None: the index's own); new_ids: the labels the new rows carry (None: N .. N + n - 1)."""
+        kp = nearest.shape[1]
         L0 = len(cols0)
+        old_pts, old_idl = (self.pq_transformed_points, self.ids) if old is None else old
+        if new_ids is None:
+            new_ids = len(self.data) + np.arange(len(new), dtype=np.int64)
         zero = self._zero_label()
         cols1 = np.zeros((L1, kp), dtype=np.int64)
         cols1[:L0] = cols0
@@ -1709,11 +1767,11 @@ class IVF:
                 per[l][j] = order[starts[l]:starts[l + 1]]
         pts, idl = [], []
         for l in range(L1):
-            old_t = self.pq_transformed_points[l] if l < L0 else None
-            old_ids = np.asarray(self.ids[l], dtype=np.int64) if l < L0 else np.zeros(0, np.int64)
+            old_t = old_pts[l] if l < L0 else None
+            old_ids = np.asarray(old_idl[l], dtype=np.int64) if l < L0 else np.zeros(0, np.int64)
             if all(p is None for p in per[l]):
                 pts.append(old_t)
-                idl.append(self.ids[l])
+                idl.append(old_idl[l])
                 continue
             old_n = len(old_ids)
             old_lab = (unpack(old_t.packed)[:old_n] if old_n else np.zeros((0, labels.shape[1]), np.uint8))
@@ -1725,10 +1783,88 @@ class IVF:
                 o += oc
                 if per[l][j] is not None:
                     lab_parts.append(labels[per[l][j]])
-                    id_parts.append(N0 + per[l][j].astype(np.int64))
+                    id_parts.append(new_ids[per[l][j]])
             pts.append(_pack_labels(np.concatenate(lab_parts), zero))
             idl.append(np.concatenate(id_parts))
         return pts, idl, cols1
+
+    # ---- replacement --------------------------------------------------------
+    def update(self, ids, X, verbose=False, groups=None):
+        """Give the stored rows `ids` (n row ids in [0, N), pairwise distinct) the new vectors X (n, d), ids kept
+        (returns self).  The index afterwards is the one that remove(ids) then add(X) gives on the same index, with
+        two differences: the added row N + i carries the label ids[i] in every list, and its prepared vector sits in
+        row ids[i] of IVF.data and of the device store, not behind the old rows — N, len(IVF.data) and the store's
+        size do not change.  The rows are prepared exactly as add prepares them (dtype of IVF.data, normalisation,
+        padding, rotation, assignment, PQ labels; a half store refuses a row whose half is not finite before anything
+        changes).  List l's column-j block becomes (old_j minus the rows in ids, old order kept) ++ (the rows i whose
+        j-th nearest centre is l, ascending i, labelled ids[i]): a row removed earlier is stored again, a row whose
+        nearest list does not change moves to the end of its column block, a list that empties stays with its
+        centre, rows that activate centres past the active ones append lists (the prefix rule and AssertionError of
+        add); list_columns follows.  groups: new group ids for those rows, only taken where the index has groups;
+        without it they keep their groups.  A duplicate or out-of-range id raises ValueError.  The device index is
+        updated in place (one pass over its codes, one scatter into its vectors): batches in flight finish on the
+        old lists and vectors, allowed sets made before fail afterwards.  A refused call changes nothing."""
+        self._require_device_free("update", "replacing rows of")
+        ids = update_ids(ids, len(self.data))
+        X = np.asarray(X)
+        d = self.data.shape[1]
+        if X.ndim != 2 or X.shape != (len(ids), d):
+            raise AssertionError(f"IVF.update: X must have shape ({len(ids)}, {d}), got {X.shape}")
+        if groups is not None:
+            if self.groups is None:
+                raise ValueError("IVF.update: groups= on an index without groups (set_groups first)")
+            groups = group_ids(groups, len(X), "IVF.update: groups")
+        if self.all_centers is None:
+            raise AssertionError("IVF.update: the index has no all_centers (fit, or a file written with them)")
+        if len(ids) == 0:
+            return self
+        if self.pq_transformed_points is None:
+            self._update_resident(ids, X, verbose)
+        else:
+            self._update_host(ids, X, verbose)
+        if groups is not None:
+            self.groups = self.groups.copy()
+            self.groups[ids] = groups
+            if self._dev is not None:
+                self._dev.set_groups(self.groups)
+        return self
+
+    def _update_resident(self, ids, X, verbose):
+        dev = self._dev
+        t0 = time.perf_counter()
+        with timer(verbose, "Replacing rows on the device..."):
+            L = dev.update(ids, np.ascontiguousarray(X, dtype=np.float32), dev.list_columns().shape[1],
+                           normalise=self.metric == "angular", all_centers=self.all_centers)
+        self.last_update_ms = {"device": 1e3 * (time.perf_counter() - t0), "host": 0.0}
+        self.active_centers, cc = dev.export_centers()
+        self.pq_transformed_centers = TransformedData(L, cc)
+        self.list_sizes = dev.list_sizes
+        self.list_columns = dev.list_columns()
+        return self
+
+    def _update_host(self, ids, X, verbose):
+        new, nearest, labels, cols0, L1, active, centers = self._prepared_rows(X, "update", 0, verbose)
+        kp, grown = nearest.shape[1], L1 > len(self.active_centers)
+        if not self.data.flags.writeable:       # (before anything changes: the rows are overwritten in place below)
+            self.data = self.data.copy()
+
+        def on_device(dev):
+            with timer(verbose, "Replacing rows on the device..."):
+                dev.update(ids, new, kp, nearest=nearest, labels=labels, list_columns=cols0,
+                           all_centers=self.all_centers if grown else None,
+                           center_codes=centers.packed if grown else None)
+            return True
+
+        def in_numpy():
+            dead = np.zeros(len(self.data), dtype=bool)
+            dead[ids] = True
+            pts, idl, cols = self._filter_lists(dead, cols0)
+            return self._splice(new, nearest, labels, cols, L1, old=(pts, idl), new_ids=ids)
+
+        self._change_lists("update", on_device, in_numpy)
+        self.active_centers, self.pq_transformed_centers = active, centers
+        self.data[ids] = new
+        return self
 
     # ---- removal -----------------------------------------------------------
     def remove(self, ids_or_mask, verbose=False):

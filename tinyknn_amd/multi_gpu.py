@@ -64,6 +64,10 @@ class ReplicaGroup:
         raise NotImplementedError("ReplicaGroup.remove: removing rows from a replicated index is not supported; "
                                   "remove from the IVF, then make the group again")
 
+    def update(self, ids, X, verbose=False, groups=None):
+        raise NotImplementedError("ReplicaGroup.update: replacing rows of a replicated index is not supported; "
+                                  "update the IVF, then make the group again")
+
     def query_shard(self, qs, k, n_probes=1, pass_1=None):
         """This rank's slice of the batch: returns (lo, hi, ids (hi-lo, k))."""
         qs = np.array(qs, dtype=np.float32, order="C", copy=True)
@@ -299,6 +303,10 @@ class ListShardedIndex:
     def remove(self, ids_or_mask, verbose=False):
         raise NotImplementedError("ListShardedIndex.remove: removing rows from a list-sharded index is not "
                                   "supported; remove from the IVF before sharding it")
+
+    def update(self, ids, X, verbose=False, groups=None):
+        raise NotImplementedError("ListShardedIndex.update: replacing rows of a list-sharded index is not "
+                                  "supported; update the IVF before sharding it")
 
     def __init__(self, ivf, group=None, engine=None, depth=1, owner=None, list_sizes=None,
                  coarse="home", coalesce=1, exchange="dense", calibrate=True, force_collectives=None,
