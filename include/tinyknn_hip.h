@@ -738,6 +738,47 @@ int tk_index_query_batch_dev_ex3(tk_index *ix, const tk_allow *allow, const int6
                                  int64_t nq, int k, int n_probes, int pass_1, int64_t *out_ids_dev,
                                  void *out_dist_dev, void *done_event, void *stream);
 int tk_index_group_table(tk_index *ix, int64_t *info4);
+/* Every query of a batch restricted to the rows that carry its tags (several categories or ACL principals per row).
+ * tags[r] is row r's 64-bit mask: bit t set = the row carries tag t, 64 tags per index, 0 = a row without tags.  A
+ * query carries a mask m, the call one mode: tag_mode 0 ("any") — a row passes iff (tags[r] & m) != 0; tag_mode 1
+ * ("all") — iff (tags[r] & m) == m; another mode: TK_ERR_ARG.  A query with m != 0 returns what IVF.query
+ * (ivf.py:106-163) returns when `insert` in query_pq runs only for labels that pass — that allowed set, for that
+ * query alone, with everything else the reference's as for allowed sets above; bit for bit that guarded reference.
+ * m == 0: the query is unrestricted in both modes.  No row passes: the query returns no id (a row of -1).  With an
+ * allowed set, an exclude array and / or a group array as well, `insert` runs only for labels that pass all of them.
+ * tk_index_set_tags: n == N masks on the host, uploaded once and kept until they are replaced, cleared (NULL, 0) or
+ * the index is destroyed; completes the batches in flight first.
+ * tk_index_tags: the number of rows the tags cover, 0 for none.
+ * On the device the probed rows that do not pass take the heap's empty value in the query's distance row, where the
+ * group pass runs (behind the list scans and every exact re-scan, in front of every replay; never on the coarse
+ * stage).  Their tags are read from a table in list-position order, 128 bytes per stored chunk of 16 rows beside the
+ * 8 N bytes by row id (0.8 GB each at 100M rows stored once, plus the allocator's eighth of slack), made from the
+ * device-resident labels by the first call that passes a tag array, once per layout of the lists (again after
+ * tk_index_set_lists, _add_rows, _remove_rows, _update_rows and after tk_index_set_tags; that call synchronises the
+ * device, so make it outside a stream capture), freed with the index.  Calls without an array never make it and
+ * launch nothing more than before.
+ * tk_index_query_batch_ex4 / _dev_ex4: _ex3 with one more pointer, tags / tags_dev (uint64, nq entries), which may be
+ * NULL, and tag_mode.  The host call passes an array of only zeros on as none.  The device call does not read
+ * tags_dev on the host: an entry of 0 there leaves its query unrestricted.  tags_dev belongs to the library until
+ * done_event or tk_index_join, like the other buffers.  _ex3 is this call without a tag array.
+ * Refused, nothing run: a tag array while no tags are set, or while they cover fewer rows than the index has (after
+ * tk_index_add_rows: TK_ERR_STATE, set them again); a list-sharded index (TK_ERR_ARG).
+ * Sub-batches and the pipelined mode as the _ex3 calls.  A call with a tag array is a restricted call: in the
+ * automatic plain-scan mode it takes the exact scan and leaves the automatic state alone; two calls pair
+ * (tk_index_set_coalesce) only where both pass a tag array with the same mode or neither passes one.
+ * tk_index_tag_table: info4 = {table exists for the current lists, its bytes, times one was made, the bytes of the
+ * tags by row id}. */
+int tk_index_set_tags(tk_index *ix, const uint64_t *tags, int64_t n);
+int64_t tk_index_tags(tk_index *ix);
+int tk_index_query_batch_ex4(tk_index *ix, const tk_allow *allow, const int64_t *exclude, const int32_t *group,
+                             const uint64_t *tags, int tag_mode, const float *q, const void *q_pq, int q_pq_is_f64,
+                             int64_t nq, int k, int n_probes, int pass_1, int64_t *out_ids, void *out_dist,
+                             int64_t *out_probes, int64_t *out_heap_idx, int32_t *out_heap_val);
+int tk_index_query_batch_dev_ex4(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
+                                 const int32_t *group_dev, const uint64_t *tags_dev, int tag_mode, const float *q_dev,
+                                 const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                                 int64_t *out_ids_dev, void *out_dist_dev, void *done_event, void *stream);
+int tk_index_tag_table(tk_index *ix, int64_t *info4);
 /* hipStream_t on which to copy a batch's inputs in (pipelined mode: the index's front stream,
  * where the batch's first kernel runs; NULL: use the stream the batch is enqueued on) */
 void *tk_index_input_stream(tk_index *ix);

@@ -21,6 +21,8 @@ struct Pending {
         void *dist_dev = nullptr;   // the rescoring's distances beside out_dev (or NULL: ids only)
         const int64_t *exclude = nullptr;   // one row per query that the query may not return (or NULL), rows.hip
         const int32_t *group = nullptr;     // one group per query that the query is restricted to (or NULL), groups.hip
+        const uint64_t *tags = nullptr;     // one tag mask per query that the query is restricted by (or NULL), tags.hip
+        int tag_mode = 0;                   // ... 0: a row passes with any of the mask's tags, 1: with all of them
     } subs[2];
     int n_subs = 1;
     Work *w;
@@ -33,7 +35,8 @@ struct Pending {
     bool plain = false;             // probed lists behind the first ones by the plain kernel (plain_scan.hip)
     bool coarse_launched = false;   // its coarse scan has been enqueued
     // a held first call: a second call joins it with the same k, n_probes, pass_1, table dtype, allowed set and
-    // caller's stream `st` (its table build waits on `sf`), within `room` rows in all; both name a group array or neither
+    // caller's stream `st` (its table build waits on `sf`), within `room` rows in all; both name a group array or neither,
+    // and both a tag array with the same mode or neither
     int64_t room = 0;
 
     // one call on the next workspace, every stream the caller's (pipe_begin picks the internal ones)
@@ -57,14 +60,20 @@ struct Pending {
         TkSecond exclude2;
         const int32_t *group;       // each call's groups (or NULL)
         TkSecond group2;
+        const uint64_t *tags;       // each call's tag masks (or NULL)
+        TkSecond tags2;
     };
     bool grouped() const { return subs[0].group != nullptr; }    // (a pair: both calls or neither, coalesce_call)
+    bool tagged() const { return subs[0].tags != nullptr; }      // (a pair: both calls in one mode or neither)
+    int tag_mode() const { return subs[0].tag_mode; }
     Rows rows() const
     {
         const Sub &a = subs[0], &b = subs[1];
-        if (n_subs == 1) return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq, {}, {}, {}, a.dist_dev, {}, a.exclude, {}, a.group, {}};
+        if (n_subs == 1) return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq, {}, {}, {}, a.dist_dev, {}, a.exclude, {}, a.group, {},
+                                     a.tags, {}};
         return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq + b.nq, {b.q_dev, a.nq}, {b.qpq_dev, a.nq}, {b.out_dev, a.nq},
-                    a.dist_dev, {b.dist_dev, a.nq}, a.exclude, {b.exclude, a.nq}, a.group, {b.group, a.nq}};
+                    a.dist_dev, {b.dist_dev, a.nq}, a.exclude, {b.exclude, a.nq}, a.group, {b.group, a.nq},
+                    a.tags, {b.tags, a.nq}};
     }
 };
 
@@ -95,7 +104,7 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->local_chunk_off, &ix->rot_t, &ix->br_ynorm, &ix->br_vals, &ix->br_tau,
                       &ix->br_cand, &ix->br_count, &ix->br_out, &ix->br_q, &ix->br_sample, &ix->replay_counters,
                       &ix->twin_list, &ix->twin_off, &ix->row_pos_off, &ix->row_pos, &ix->row_group,
-                      &ix->group_table};
+                      &ix->group_table, &ix->row_tags, &ix->tag_table};
     for (DevBuf *b : bufs) b->release();
     for (Work &w : ix->works) w.release();
     // (the internal streams belong to the process: shared_streams below)
@@ -1050,12 +1059,23 @@ static void apply_groups(const tk_index *ix, Work &w, int64_t q0, int64_t nq, co
                          ix->group_table.as<int32_t>(), group, group2, q0, 1, only, st);
 }
 
+// One tag mask per query (tags.hip), where apply_groups runs and with its arguments; all: the batch's mode
+static void apply_tags(const tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, const uint64_t *tags,
+                       TkSecond tags2, int all, hipStream_t st, const int *only = nullptr)
+{
+    if (!tags && !tags2.b) return;
+    tk_launch_tag_pass(w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, nq,
+                       w.slot_prefix.as<int>() + q0 * (p.S + 1), w.slot_chunk0.as<int64_t>() + q0 * p.S, p.S,
+                       ix->tag_table.as<uint64_t>(), tags, tags2, all, q0, 1, only, st);
+}
+
 // The queries the replay flagged (bound above the table's limit at the first plain block, plain_scan.hip): every probed
 // list again with the exact kernel.  list_built: the replay listed them itself (TkPlainCheck::flag_list); the count then
 // reaches the host through the replay behind the re-scan (replay_flagged_tail)
 static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, hipStream_t st,
                            const tk_allow *allow, const int64_t *exclude, TkSecond exclude2, const int32_t *group,
-                           TkSecond group2, bool list_built = false)
+                           TkSecond group2, const uint64_t *tags, TkSecond tags2, int tag_mode,
+                           bool list_built = false)
 {
     int *list = w.flag_list.as<int>();
     if (!list_built) {
@@ -1069,6 +1089,7 @@ static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const 
     apply_allow(w, q0, nq, p, allow, st, list);
     apply_exclude(ix, w, q0, nq, p, exclude, exclude2, st, list);
     apply_groups(ix, w, q0, nq, p, group, group2, st, list);
+    apply_tags(ix, w, q0, nq, p, tags, tags2, tag_mode, st, list);
 }
 
 // The tail behind a lane (or register-heap) replay that rode with the plain kernel: the queries it flagged — the lemma's
@@ -1129,7 +1150,8 @@ static Replay replay_form(const tk_index *ix, int64_t nq, const Plan &p)
 int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
                const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain,
                TkSecond q2, TkSecond out2, int *plain_flag, const tk_allow *allow, void *dist_dev, TkSecond dist2,
-               const int64_t *exclude, TkSecond exclude2, const int32_t *group, TkSecond group2)
+               const int64_t *exclude, TkSecond exclude2, const int32_t *group, TkSecond group2,
+               const uint64_t *tags, TkSecond tags2, int tag_mode)
 {
     const TkReplayJob j = list_replay_job(ix, w, q0, nq, p);
     unsigned char *flags = w.repeat_flag.as<unsigned char>() + q0;
@@ -1140,6 +1162,7 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     apply_allow(w, q0, nq, p, allow, st);
     apply_exclude(ix, w, q0, nq, p, exclude, exclude2, st);
     apply_groups(ix, w, q0, nq, p, group, group2, st);
+    apply_tags(ix, w, q0, nq, p, tags, tags2, tag_mode, st);
     // heaps start fresh here, so packed entries apply.  Distinct labels: one query per
     // lane (or per wave for big heaps), and the few queries whose probe list wrapped a -1
     // (a list may then be scanned twice) re-run with the duplicate test.  Repeating labels
@@ -1220,13 +1243,13 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     const bool listed = form == Replay::Pair || form == Replay::Lanes || form == Replay::LanesTwin;
     const auto replay_wrapped = [&] { tk_launch_heap_replay_packed(j, flags, TK_RUN_WRAPPED, /*dedupe=*/true, st); };
     if (plain && form == Replay::LanesDedupe) {
-        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2, group, group2);
+        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2, group, group2, tags, tags2, tag_mode);
         replay_wrapped();
     } else if (plain && plain_flag && (listed || form == Replay::PackedDistinct)) {
         tk_launch_shard_flag_plain(flags, nq, plain_flag, st);
         replay_wrapped();
     } else if (plain && listed) {
-        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2, group, group2, true);
+        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2, group, group2, tags, tags2, tag_mode, true);
         replay_flagged_tail(ix, w, j, flags, st);
         plain_verdict_event(ix, w, nq, st);
     } else if (!plain && (form == Replay::Lanes || form == Replay::LanesTwin || form == Replay::PackedDistinct)) {
@@ -1262,12 +1285,12 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
 //
 // Both depths run a batch through the same stages below; only the streams and the event hand-offs differ.
 
-// A restricted batch (allowed set, group array) in the automatic plain-scan mode takes the exact scan and never touches
+// A restricted batch (allowed set, group array, tag array) in the automatic plain-scan mode takes the exact scan and never touches
 // the state: a selective restriction flags many queries, and its verdicts would pause the plain path for the
 // unrestricted traffic.  Modes 1 and 2 hold for every batch.
 static bool plain_for(tk_index *ix, const Pending &b)
 {
-    if ((b.allow || b.grouped()) && plain_adaptive(ix)) return false;
+    if ((b.allow || b.grouped() || b.tagged()) && plain_adaptive(ix)) return false;
     return plain_now(ix, b.p);
 }
 
@@ -1328,7 +1351,7 @@ static int batch_back(tk_index *ix, Pending &b, hipStream_t st)
 {
     const Pending::Rows r = b.rows();
     TRY(stage_back(ix, *b.w, r.q, 0, r.nq, b.k, b.p, r.out, st, b.pf, b.plain, r.q2, r.out2, nullptr, b.allow, r.dist,
-                   r.dist2, r.exclude, r.exclude2, r.group, r.group2));
+                   r.dist2, r.exclude, r.exclude2, r.group, r.group2, r.tags, r.tags2, b.tag_mode()));
     for (int i = 0; i < b.n_subs; i++) {
         const Pending::Sub &u = b.subs[i];
         if (u.host_out && u.host_out_kernel)
@@ -1624,7 +1647,8 @@ static int coalesce_call(tk_index *ix, Pending &b)
         Pending &h = *ix->held;
         const bool joins = h.k == b.k && h.n_probes == b.n_probes && h.pass_1 == b.pass_1 && h.qpq_f64 == b.qpq_f64 &&
                            h.st == b.st && h.subs[0].nq + call.nq <= h.room && h.allow == b.allow &&
-                           h.grouped() == b.grouped();     // (the two kinds take different scans: plain_for)
+                           h.grouped() == b.grouped() &&   // (the two kinds take different scans: plain_for)
+                           h.tagged() == b.tagged() && (!h.tagged() || h.tag_mode() == b.tag_mode());  // (one mode per launch)
         if (joins) {
             if (h.sf != h.st) {            // the second call's inputs: the caller's work so far
                 HIPCHECK(hipEventRecord(ix->ev_in, h.st));
@@ -1648,12 +1672,15 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
                                 int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
                                 int64_t *out_ids_dev, int64_t *out_ids_pinned, hipEvent_t done_ev,
                                 void *stream, const tk_allow *allow = nullptr, void *out_dist_dev = nullptr,
-                                const int64_t *exclude_dev = nullptr, const int32_t *group_dev = nullptr)
+                                const int64_t *exclude_dev = nullptr, const int32_t *group_dev = nullptr,
+                                const uint64_t *tags_dev = nullptr, int tag_mode = 0)
 {
     Plan p;
     TRY(make_plan(ix, k, n_probes, pass_1, p));
     ARGCHECK(nq >= 0, "nq");
     ARGCHECK(!ix->sharded, "list-sharded index: use tk_index_shard_scan_dev / _finish_dev");
+    ARGCHECK(tag_mode == 0 || tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
+    if (!tags_dev) tag_mode = 0;
     if (allow) {
         ARGCHECK(allow->ix == ix, "the allowed set belongs to another index");
         if (allow->lists_gen != ix->lists_gen)
@@ -1669,6 +1696,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     }
     if (exclude_dev && nq > 0) TRY(row_pos_ensure(ix));     // (the first excluding call of a layout: rows.hip)
     if (group_dev && nq > 0) TRY(group_table_ensure(ix));   // (groups set for every row; the first grouped call of a layout: groups.hip)
+    if (tags_dev && nq > 0) TRY(tag_table_ensure(ix));      // (the same for tags: tags.hip)
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     const int64_t ms = sub_batch(p);
     ARGCHECK(!(out_ids_pinned || done_ev) || (nq >= 1 && nq <= ms),
@@ -1680,7 +1708,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     if (ix->depth > 1 && ix->coalesce == 2 && (ix->ids_unique || twin_replay(ix, p)) && nq >= 1 && nq <= ms) {
         Pending b(ix, p, k, n_probes, pass_1, q_pq_is_f64, allow, caller,
                   {q_dev, q_pq_dev, out_ids_dev, nq, out_ids_pinned, ix->host_out_kernel, done_ev, out_dist_dev,
-                   exclude_dev, group_dev});
+                   exclude_dev, group_dev, tags_dev, tag_mode});
         return coalesce_call(ix, b);
     }
     TRY(launch_held(ix));
@@ -1696,7 +1724,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
                    out_ids_pinned, ix->host_out_kernel, done_ev,
                    out_dist_dev ? (char *)out_dist_dev + (size_t)o * k * dsz : nullptr,
                    exclude_dev ? exclude_dev + o : nullptr,       // (a part's rows of the CALL's arrays)
-                   group_dev ? group_dev + o : nullptr});
+                   group_dev ? group_dev + o : nullptr, tags_dev ? tags_dev + o : nullptr, tag_mode});
         if (ix->depth == 1) {
             ix->calls++;
             TRY(run_batch_inline(ix, b));
@@ -1861,7 +1889,7 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
                             int n_probes, int pass_1, int64_t *out_ids, int64_t *out_probes, int64_t *out_heap_idx,
                             int32_t *out_heap_val, const tk_allow *allow, void *out_dist = nullptr,
                             const int64_t *exclude = nullptr, const int64_t *rows = nullptr,
-                            const int32_t *group = nullptr)
+                            const int32_t *group = nullptr, const uint64_t *tags = nullptr, int tag_mode = 0)
 {
     IXLOCK(ix);
     Plan p;
@@ -1891,13 +1919,20 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
         }
     if (!groups) group = nullptr;
     if (group) ARGCHECK(!ix->sharded, "list-sharded index: row groups are not supported");
+    // tags: the same (an array of only zeros restricts nothing)
+    ARGCHECK(tag_mode == 0 || tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
+    bool tagged = false;
+    if (tags)
+        for (int64_t i = 0; i < nq && !tagged; i++) tagged = tags[i] != 0;
+    if (!tagged) tags = nullptr;
+    if (tags) ARGCHECK(!ix->sharded, "list-sharded index: row tags are not supported");
     ARGCHECK(!(out_probes || out_heap_idx || out_heap_val) || nq <= sub_batch(p),
              "debug outputs need the batch to fit one sub-batch");
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     TRY(ix->q.ensure((size_t)nq * ix->d * 4));
     TRY(ix->qpq.ensure((size_t)nq * ix->dq * esz));
-    DevBuf outbuf, distbuf, exbuf, rowbuf, grbuf;  // separate from the sub-batch `out` workspace
-    BufRelease rel{{&outbuf, &distbuf, &exbuf, &rowbuf, &grbuf}};
+    DevBuf outbuf, distbuf, exbuf, rowbuf, grbuf, tgbuf;  // separate from the sub-batch `out` workspace
+    BufRelease rel{{&outbuf, &distbuf, &exbuf, &rowbuf, &grbuf, &tgbuf}};
     const size_t dist_bytes = (size_t)nq * k * (ix->data_dtype == TK_DATA_F64 ? 8 : 4);
     TRY(outbuf.ensure((size_t)nq * k * 8));
     if (out_dist) TRY(distbuf.ensure(dist_bytes));
@@ -1909,6 +1944,10 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
         TRY(grbuf.ensure((size_t)nq * 4));
         HIPCHECK(hipMemcpy(grbuf.p, group, (size_t)nq * 4, hipMemcpyHostToDevice));
     }
+    if (tags) {
+        TRY(tgbuf.ensure((size_t)nq * 8));
+        HIPCHECK(hipMemcpy(tgbuf.p, tags, (size_t)nq * 8, hipMemcpyHostToDevice));
+    }
     if (rows) {
         TRY(rowbuf.ensure((size_t)nq * 8));
         HIPCHECK(hipMemcpy(rowbuf.p, rows, (size_t)nq * 8, hipMemcpyHostToDevice));
@@ -1919,7 +1958,8 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
     }
     int r = query_batch_dev_impl(ix, ix->q.as<float>(), ix->qpq.p, q_pq_is_f64, nq, k, n_probes, pass_1,
                                  outbuf.as<int64_t>(), nullptr, nullptr, nullptr, allow, out_dist ? distbuf.p : nullptr,
-                                 exclude ? exbuf.as<int64_t>() : nullptr, group ? grbuf.as<int32_t>() : nullptr);
+                                 exclude ? exbuf.as<int64_t>() : nullptr, group ? grbuf.as<int32_t>() : nullptr,
+                                 tags ? tgbuf.as<uint64_t>() : nullptr, tag_mode);
     if (r == TK_OK) r = flush_pending(ix);
     const Work &lw = ix->works[(ix->calls + ix->works.size() - 1) % ix->works.size()];   // last used
     if (r == TK_OK) {
@@ -2029,6 +2069,29 @@ extern "C" int tk_index_query_batch_dev_ex3(tk_index *ix, const tk_allow *allow,
     IXLOCK(ix);
     return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
                                 (hipEvent_t)done_event, stream, allow, out_dist_dev, exclude_dev, group_dev);
+}
+
+// ... and one tag mask per query (tags.hip, tinyknn_hip.h): _ex3 with one more pointer and the call's mode
+extern "C" int tk_index_query_batch_ex4(tk_index *ix, const tk_allow *allow, const int64_t *exclude,
+                                        const int32_t *group, const uint64_t *tags, int tag_mode, const float *q,
+                                        const void *q_pq, int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                                        int64_t *out_ids, void *out_dist, int64_t *out_probes, int64_t *out_heap_idx,
+                                        int32_t *out_heap_val)
+{
+    return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
+                            out_heap_val, allow, out_dist, exclude, nullptr, group, tags, tag_mode);
+}
+
+extern "C" int tk_index_query_batch_dev_ex4(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
+                                            const int32_t *group_dev, const uint64_t *tags_dev, int tag_mode,
+                                            const float *q_dev, const void *q_pq_dev, int q_pq_is_f64, int64_t nq,
+                                            int k, int n_probes, int pass_1, int64_t *out_ids_dev, void *out_dist_dev,
+                                            void *done_event, void *stream)
+{
+    IXLOCK(ix);
+    return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
+                                (hipEvent_t)done_event, stream, allow, out_dist_dev, exclude_dev, group_dev, tags_dev,
+                                tag_mode);
 }
 
 // the stored rows `rows` as queries, each leaving itself out where exclude_self

@@ -211,6 +211,13 @@ struct tk_index {
     bool group_table_ok = false;
     uint64_t group_table_gen = 0;
     int64_t group_table_builds = 0;
+    // a 64-bit tag mask per row (tags.hip): by row id as tk_index_set_tags uploaded them (tags_n of them, 0: none), and
+    // in list-position order — made by the first call that names a tag array, for ONE layout, as the group table
+    DevBuf row_tags, tag_table;
+    int64_t tags_n = 0;
+    bool tag_table_ok = false;
+    uint64_t tag_table_gen = 0;
+    int64_t tag_table_builds = 0;
     // members per (list, column of nearest): list l holds its column-0 members first, then column 1's, ...
     // (group_data_by_indices); known after tk_index_build_dev / tk_index_add_rows (list_kp = columns), not
     // after a host upload (list_kp = 0: tk_index_add_rows takes them from the caller)
@@ -421,12 +428,15 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
                TkSecond q2 = TkSecond(), TkSecond out2 = TkSecond(), int *plain_flag = nullptr,
                const tk_allow *allow = nullptr, void *dist_dev = nullptr, TkSecond dist2 = TkSecond(),
                const int64_t *exclude = nullptr, TkSecond exclude2 = TkSecond(), const int32_t *group = nullptr,
-               TkSecond group2 = TkSecond());
+               TkSecond group2 = TkSecond(), const uint64_t *tags = nullptr, TkSecond tags2 = TkSecond(),
+               int tag_mode = 0);
 // rows.hip: the row-position table of the index's current lists exists (made now if not: synchronises the device)
 int row_pos_ensure(tk_index *ix);
 // groups.hip: groups for every row the index has (else TK_ERR_STATE) and the group table of its current lists (made
 // now if not: synchronises the device)
 int group_table_ensure(tk_index *ix);
+// tags.hip: the same for the tags and the tag table
+int tag_table_ensure(tk_index *ix);
 int head_chunks(const tk_index *ix, const Plan &p);    // chunks of a first probed list the exact kernel keeps (head mode)
 // the workspace's three pair sets: whole lists exact / plain tiles / heads
 TkPairSet exact_pairs(const Work &w);

@@ -507,6 +507,14 @@ void tk_launch_exclude_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap
 void tk_launch_group_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
                           const int *slot_prefix, const int64_t *slot_chunk0, int S, const int32_t *table,
                           const int32_t *g_a, TkSecond g_b, int64_t q0, int signd, const int *only, hipStream_t s);
+// tags.hip: one 64-bit tag mask per query — the probed rows that do not pass it take the empty value, as the group pass
+// masks (every argument it shares with tk_launch_group_pass as there).  table: 16 uint64 per stored chunk; m_a / m_b:
+// the masks of the batch's first and second call, each NULL or with entries of 0 for queries that are not restricted;
+// all: 0 = a row passes with (tags & m) != 0, 1 = with (tags & m) == m, for both calls
+void tk_launch_tag_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
+                        const int *slot_prefix, const int64_t *slot_chunk0, int S, const uint64_t *table,
+                        const uint64_t *m_a, TkSecond m_b, int all, int64_t q0, int signd, const int *only,
+                        hipStream_t s);
 // half storage of float32 rows (n, d) on the device: *first_bad (preset to ~0) = the first row with a value whose
 // half is not finite (|x| >= 65520, inf, NaN); `out` = the rows as halfs, round-to-nearest-even, subnormals kept
 void tk_launch_check_half(const float *X, int64_t n, int d, unsigned long long *first_bad, hipStream_t s);

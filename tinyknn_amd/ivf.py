@@ -218,6 +218,77 @@ def query_groups(group, nq):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _u64(a):
+    """the integer array `a` as uint64 where every value lies in [0, 2**64), else None"""
+    if a.dtype == np.uint64:
+        return np.ascontiguousarray(a)
+    if a.size == 0:
+        return np.zeros(a.shape, dtype=np.uint64)
+    if a.dtype == object:           # (Python ints beyond int64 among smaller ones)
+        if not all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in a.flat):
+            return None
+        if min(a.flat) < 0 or max(a.flat) >= 2**64:
+            return None
+        return np.array([int(v) for v in a.flat], dtype=np.uint64).reshape(a.shape)
+    if a.min() < 0:
+        return None
+    return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def _mask_array(x):
+    """np.asarray(x) — a sequence of Python ints that numpy would make floats of (values on both sides of 2**63) as objects"""
+    a = np.asarray(x)
+    if a.dtype.kind == "f" and not isinstance(x, np.ndarray) and a.ndim == 1 and \
+            all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in x):
+        a = np.asarray(x, dtype=object)
+    return a
+
+
+def tag_masks(tags, n, what):
+    """The uint64 tag masks a `tags` argument is: a 1-d integer array of length n, uint64 or any integer dtype with
+    every value in [0, 2**64) (TypeError for another kind of value, ValueError for another length or a value outside)."""
+    a = _mask_array(tags)
+    integral = a.size == 0 or np.issubdtype(a.dtype, np.integer) or a.dtype == object
+    if a.ndim != 1 or a.dtype == np.bool_ or not integral:
+        raise TypeError(f"{what}: a 1-d integer array, one tag mask per row")
+    if a.shape[0] != n:
+        raise ValueError(f"{what}: one tag mask per row ({n}), got {a.shape[0]}")
+    u = _u64(a)
+    if u is None:
+        if a.dtype == object and not all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+                                         for v in a.flat):
+            raise TypeError(f"{what}: a 1-d integer array, one tag mask per row")
+        raise ValueError(f"{what}: tag masks must lie in [0, 2**64)")
+    return u
+
+
+TAG_MODES = {"any": 0, "all": 1}
+
+
+def tag_mode_of(tags_mode):
+    """0 / 1 for tags_mode "any" / "all" (ValueError for anything else)"""
+    if not isinstance(tags_mode, str) or tags_mode not in TAG_MODES:
+        raise ValueError(f"tags_mode: \"any\" or \"all\", got {tags_mode!r}")
+    return TAG_MODES[tags_mode]
+
+
+def query_tags(tags, nq):
+    """The uint64 array a `tags=` argument is: an int for every query, or a 1-d integer array with one mask per query;
+    each in [0, 2**64), 0 for an unrestricted query."""
+    a = _mask_array(tags)
+    integral = a.size == 0 or np.issubdtype(a.dtype, np.integer) or a.dtype == object
+    if a.dtype == np.bool_ or not integral or a.ndim > 1:
+        raise TypeError("tags: an int, or a 1-d integer array with one tag mask (or 0) per query")
+    if a.ndim == 0:
+        a = np.full(nq, a[()], dtype=a.dtype)
+    if a.shape[0] != nq:
+        raise ValueError(f"tags: one entry per query ({nq}), got {a.shape[0]}")
+    u = _u64(a)
+    if u is None:
+        raise ValueError("tags: entries must be a tag mask in [0, 2**64)")
+    return u
+
+
 def _stored(t):
     """Stored rows of one list's codes: a TransformedData, or the raw empty array FastPQ.transform returns for no rows."""
     return 0 if isinstance(t, np.ndarray) else t.size
@@ -723,6 +794,28 @@ class DeviceIndex:
         _lib.check(_lib.lib().tk_index_group_table(self._h, _lib.ptr(o, _lib._i64p)))
         return dict(built=bool(o[0]), bytes=int(o[1]), builds=int(o[2]), row_bytes=int(o[3]))
 
+    def set_tags(self, tags):
+        """One 64-bit tag mask per row (bit t set: the row carries tag t) for the `tags=` argument of the query
+        calls, uploaded once (tk_index_set_tags); None clears.  After add() they must be set again for all N rows.
+        Batches in flight finish first.  Not for a list-sharded index."""
+        if _dev_is_sharded(self) or self._source is not None:
+            raise RuntimeError("DeviceIndex.set_tags: a list-sharded index takes no row tags")
+        if tags is None:
+            _lib.check(_lib.lib().tk_index_set_tags(self._h, None, 0))
+            return
+        t = tag_masks(tags, self.N, "set_tags")
+        _lib.check(_lib.lib().tk_index_set_tags(self._h, t.ctypes.data, len(t)))
+
+    def tags_set(self):
+        """The number of rows the device's tags cover, 0 for none (tk_index_tags)."""
+        return int(_lib.check(_lib.lib().tk_index_tags(self._h)))
+
+    def tag_table(self):
+        """The tag table behind tags= (tk_index_tag_table): dict(built, bytes, builds, row_bytes)."""
+        o = np.zeros(4, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_tag_table(self._h, _lib.ptr(o, _lib._i64p)))
+        return dict(built=bool(o[0]), bytes=int(o[1]), builds=int(o[2]), row_bytes=int(o[3]))
+
     def _allow_of(self, allowed):
         """(set, temporary) for an `allowed=` argument: a prepared set of this index, or a mask / ids made into one"""
         if isinstance(allowed, AllowSet):
@@ -840,8 +933,12 @@ class DeviceIndex:
         return (out, dist) if return_distances else out
 
     def query_batch(self, qn, q_pq, k, n_probes, pass_1=None, debug=False, *, allowed=None, return_distances=False,
-                    exclude=None, group=None):
+                    exclude=None, group=None, tags=None, tags_mode="any"):
         """qn: (nq, d) float32 normalised queries; q_pq: (nq, dq) table-build queries.
+        tags: None, an int for every query, or a 1-d integer array of length nq: the 64-bit tag mask each query is
+        restricted by, 0 for none; tags_mode "any": a row passes where it carries one of the mask's tags (set_tags),
+        "all": where it carries every one (the reference's `insert` only for labels that pass); such
+        calls take the library path (tk_index_query_batch_ex4).
         group: None, an int for every query, or a 1-d integer array of length nq: the group of rows (set_groups) each
         query may return, -1 for any (the reference's `insert` only for labels of that group); such
         calls take the library path (tk_index_query_batch_ex3).
@@ -859,15 +956,20 @@ class DeviceIndex:
         q_pq = np.ascontiguousarray(q_pq, dtype=np.float64 if is64 else np.float32)
         nq = qn.shape[0]
         assert qn.shape[1] == self.d and q_pq.shape == (nq, self.dq)
-        if group is not None or exclude is not None:
+        if group is not None or exclude is not None or tags is not None:
             if group is not None:
                 group = query_groups(group, nq)
+            if tags is not None:
+                tags, mode = query_tags(tags, nq), tag_mode_of(tags_mode)
             if exclude is not None:
                 exclude = self._exclude_of(exclude, nq)
             L, knobs = _lib.lib(), (int(k), int(n_probes), int(pass_1 or 0))
 
             def call(o, e, a, ex, out, *rest):
                 tail = (_lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o, *knobs, out, *rest)
+                if tags is not None:
+                    return L.tk_index_query_batch_ex4(self._h, a, ex, None if group is None else group[o:e].ctypes.data,
+                                                      tags[o:e].ctypes.data, mode, *tail)
                 if group is None:
                     return L.tk_index_query_batch_ex2(self._h, a, ex, *tail)
                 return L.tk_index_query_batch_ex3(self._h, a, ex, group[o:e].ctypes.data, *tail)
@@ -997,7 +1099,7 @@ class DeviceIndex:
 
     def query_batch_dev(self, qn_ptr, qpq_ptr, qpq_is_f64, nq, k, n_probes, out_ptr,
                         pass_1=None, stream=0, done_event=None, *, allowed=None, dist_ptr=None, exclude_ptr=None,
-                        group_ptr=None):
+                        group_ptr=None, tags_ptr=None, tags_mode="any"):
         """Device pointers in, device pointer out, enqueued on `stream` (no sync).
         done_event: a hipEvent_t (integer handle) recorded behind the batch's last kernel, on
         whichever internal stream that runs (tk_index_query_batch_dev_ex).
@@ -1013,13 +1115,21 @@ class DeviceIndex:
         exclude_ptr: None, or a device buffer of nq int64: the row each query may not return, anything outside [0, N)
         for none (tk_index_query_batch_dev_ex2); the library's until join() or done_event, like the others.
         group_ptr: None, or a device buffer of nq int32: the group each query is restricted to, any entry < 0 for an
-        unrestricted query (tk_index_query_batch_dev_ex3); the caller's again after join() or done_event."""
+        unrestricted query (tk_index_query_batch_dev_ex3); the caller's again after join() or done_event.
+        tags_ptr: None, or a device buffer of nq uint64: the tag mask each query is restricted by under tags_mode
+        ("any" / "all"), an entry of 0 for an unrestricted query (tk_index_query_batch_dev_ex4); the caller's again
+        after join() or done_event."""
         if allowed is not None:
             if not isinstance(allowed, AllowSet):
                 raise TypeError("query_batch_dev: allowed= takes a prepared set (DeviceIndex.allow / IVF.allow)")
             allowed = self._allow_of(allowed)[0].handle
         L, ev = _lib.lib(), None if done_event is None else C.c_void_p(int(done_event))
-        if group_ptr is not None:
+        if tags_ptr is not None:
+            mode = tag_mode_of(tags_mode)
+            rc = L.tk_index_query_batch_dev_ex4(
+                self._h, allowed, exclude_ptr, group_ptr, tags_ptr, mode, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k),
+                int(n_probes), int(pass_1 or 0), out_ptr, dist_ptr, ev, stream)
+        elif group_ptr is not None:
             rc = L.tk_index_query_batch_dev_ex3(
                 self._h, allowed, exclude_ptr, group_ptr, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes),
                 int(pass_1 or 0), out_ptr, dist_ptr, ev, stream)
@@ -1289,6 +1399,7 @@ class IVF:
     _build_device = None    # did build() search on the GPU?  None: not built here (fast_pq.device_build decides)
     store = None            # how the device keeps the rescoring vectors: None / "float32" / "float16" (build's store=)
     groups = None           # set_groups' host copy: (N,) int32 group id per row; None (and no instance attribute): none
+    tags = None             # set_tags' host copy: (N,) uint64 tag mask per row; None (and no instance attribute): none
 
     def __init__(self, metric, n_clusters, pq=None):
         assert metric in ["euclidean", "angular"]
@@ -1359,6 +1470,7 @@ class IVF:
         self.data = data
         self.store = store
         self.__dict__.pop("groups", None)               # (groups belong to the rows they were set for)
+        self.__dict__.pop("tags", None)                 # (tags too)
         with timer(verbose, "Computing nearest clusters..."):
             if device:
                 nearest = self._nearest_on_device(data, n_probes)
@@ -1504,6 +1616,8 @@ class IVF:
             extra["store"] = self.store
         if self.groups is not None:
             extra["groups"] = self.groups
+        if self.tags is not None:
+            extra["tags"] = self.tags
         path = self._npz_path(path)
         np.savez(path, format_version=1, metric=self.metric, n_clusters=self.n_clusters,
                  use_kmeans=int(self.pq.use_kmeans), rotate_dim=-1 if self.pq.rotate_dim is None else int(self.pq.rotate_dim),
@@ -1547,6 +1661,8 @@ class IVF:
         ivf.store = check_store(str(z["store"])) if "store" in z else None     # (files written before store= existed)
         if "groups" in z:
             ivf.groups = np.ascontiguousarray(z["groups"], dtype=np.int32)
+        if "tags" in z:
+            ivf.tags = np.ascontiguousarray(z["tags"], dtype=np.uint64)
         return ivf
 
     def build_resident(self, N, d, seed, centres=None, sigma=1.0, verbose=False, n_probes=1, store=None):
@@ -1592,13 +1708,15 @@ class IVF:
         self.data = ResidentData(dev)
         self.ids = self.pq_transformed_points = None
         self.__dict__.pop("groups", None)               # (groups belong to the rows they were set for, as in build)
+        self.__dict__.pop("tags", None)
         self._dev = dev
         return self
 
     # ---- growth ------------------------------------------------------------
-    def add(self, X, verbose=False, groups=None):
+    def add(self, X, verbose=False, groups=None, tags=None):
         """Append the rows of X with ids N .. N + n - 1 (returns self).  groups: the new rows' group ids, needed (and
-        only taken) where the index has groups (set_groups): ValueError otherwise, before anything changes.  The index afterwards is the one its own
+        only taken) where the index has groups (set_groups): ValueError otherwise, before anything changes.  tags: the
+        new rows' tag masks, by the same rule where the index has tags (set_tags).  The index afterwards is the one its own
         build would make over (old rows, X): new rows are prepared as the build prepared its rows (dtype of
         IVF.data, normalisation, padding, rotation, assignment, PQ codes); every list keeps its old members in
         place, and with n_probes = kp lists per row list l's column-j block becomes old_j ++ new_j (new_j: the
@@ -1618,6 +1736,12 @@ class IVF:
             if groups is None:
                 raise ValueError("IVF.add: this index has groups (set_groups): pass the new rows' with groups=")
             groups = group_ids(groups, len(X), "IVF.add: groups")
+        if self.tags is None and tags is not None:
+            raise ValueError("IVF.add: tags= on an index without tags (set_tags first)")
+        if self.tags is not None:
+            if tags is None:
+                raise ValueError("IVF.add: this index has tags (set_tags): pass the new rows' with tags=")
+            tags = tag_masks(tags, len(X), "IVF.add: tags")
         if self.all_centers is None:
             raise AssertionError("IVF.add: the index has no all_centers (fit, or a file written with them)")
         if len(X) == 0:
@@ -1630,6 +1754,10 @@ class IVF:
             self.groups = np.concatenate([self.groups, groups])
             if self._dev is not None:
                 self._dev.set_groups(self.groups)
+        if tags is not None:
+            self.tags = np.concatenate([self.tags, tags])
+            if self._dev is not None:
+                self._dev.set_tags(self.tags)
         return self
 
     def _require_device_free(self, what="add", doing="adding rows to"):
@@ -1789,7 +1917,7 @@ class IVF:
         return pts, idl, cols1
 
     # ---- replacement --------------------------------------------------------
-    def update(self, ids, X, verbose=False, groups=None):
+    def update(self, ids, X, verbose=False, groups=None, tags=None):
         """Give the stored rows `ids` (n row ids in [0, N), pairwise distinct) the new vectors X (n, d), ids kept
         (returns self).  The index afterwards is the one that remove(ids) then add(X) gives on the same index, with
         two differences: the added row N + i carries the label ids[i] in every list, and its prepared vector sits in
@@ -1801,7 +1929,8 @@ class IVF:
         nearest list does not change moves to the end of its column block, a list that empties stays with its
         centre, rows that activate centres past the active ones append lists (the prefix rule and AssertionError of
         add); list_columns follows.  groups: new group ids for those rows, only taken where the index has groups;
-        without it they keep their groups.  A duplicate or out-of-range id raises ValueError.  The device index is
+        without it they keep their groups; tags: the same for tag masks (set_tags).  A duplicate or out-of-range id raises
+        ValueError.  The device index is
         updated in place (one pass over its codes, one scatter into its vectors): batches in flight finish on the
         old lists and vectors, allowed sets made before fail afterwards.  A refused call changes nothing."""
         self._require_device_free("update", "replacing rows of")
@@ -1814,6 +1943,10 @@ class IVF:
             if self.groups is None:
                 raise ValueError("IVF.update: groups= on an index without groups (set_groups first)")
             groups = group_ids(groups, len(X), "IVF.update: groups")
+        if tags is not None:
+            if self.tags is None:
+                raise ValueError("IVF.update: tags= on an index without tags (set_tags first)")
+            tags = tag_masks(tags, len(X), "IVF.update: tags")
         if self.all_centers is None:
             raise AssertionError("IVF.update: the index has no all_centers (fit, or a file written with them)")
         if len(ids) == 0:
@@ -1827,6 +1960,11 @@ class IVF:
             self.groups[ids] = groups
             if self._dev is not None:
                 self._dev.set_groups(self.groups)
+        if tags is not None:
+            self.tags = self.tags.copy()
+            self.tags[ids] = tags
+            if self._dev is not None:
+                self._dev.set_tags(self.tags)
         return self
 
     def _update_resident(self, ids, X, verbose):
@@ -1944,6 +2082,8 @@ class IVF:
             dev = DeviceIndex(self)
             if self.groups is not None:
                 dev.set_groups(self.groups)
+            if self.tags is not None:
+                dev.set_tags(self.tags)
             self._dev = dev
         return self._dev
 
@@ -1959,6 +2099,20 @@ class IVF:
             self.__dict__.pop("groups", None)
         else:
             self.groups = g.copy() if g is groups else g
+        return self
+
+    def set_tags(self, tags):
+        """One 64-bit tag mask per row — categories, ACL principals: a 1-d integer array of length N, uint64 or any
+        integer dtype with every value in [0, 2**64), bit t set = the row carries tag t, 0 = no tag — for the `tags=`
+        argument of query / query_batch; None clears.  TypeError for another kind of value, ValueError
+        for another length or a value outside.  IVF.tags is the host copy (uint64); save / load and pickling carry it."""
+        t = None if tags is None else tag_masks(tags, len(self.data), "IVF.set_tags")
+        if self._dev is not None:                # (a list-sharded index raises here, before the host copy changes)
+            self._unsharded_device_index().set_tags(t)
+        if t is None:
+            self.__dict__.pop("tags", None)
+        else:
+            self.tags = t.copy() if t is tags or np.shares_memory(t, tags) else t
         return self
 
     def _unsharded_device_index(self):
@@ -1992,8 +2146,11 @@ class IVF:
         device, reused across calls; .close() frees it, len() = allowed stored rows."""
         return self._unsharded_device_index().allow(ids_or_mask)
 
-    def query(self, q, k, n_probes=1, pass_1=None, *, allowed=None, return_distances=False, exclude=None, group=None):
+    def query(self, q, k, n_probes=1, pass_1=None, *, allowed=None, return_distances=False, exclude=None, group=None,
+              tags=None, tags_mode="any"):
         """Top-k ids for one query.  reference: ivf.py:106-163
+        tags: the 64-bit tag mask the query is restricted by under tags_mode — "any": rows that carry one of its tags
+        (set_tags), "all": rows that carry every one; 0 or None for any row.
         group: the group of rows (set_groups) the query may return, -1 or None for any.
         exclude: a row id the query may not return, or None.
         allowed: the rows it may return (a bool mask of length N, row ids, or allow()'s set) — the reference's
@@ -2008,15 +2165,18 @@ class IVF:
             exclude = np.asarray(exclude).reshape(1)
         if group is not None:
             group = np.asarray(group).reshape(1)
+        if tags is not None:
+            tags = np.asarray(tags).reshape(1)
         if return_distances:
             ids, dist = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, return_distances=True,
-                                        exclude=exclude, group=group)
+                                        exclude=exclude, group=group, tags=tags, tags_mode=tags_mode)
             out, dist = ids[0], dist[0]
             if out[-1] == -1:
                 keep = out != -1
                 return out[keep], dist[keep]
             return out, dist
-        out = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, exclude=exclude, group=group)[0]
+        out = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, exclude=exclude, group=group, tags=tags,
+                              tags_mode=tags_mode)[0]
         return out[out != -1] if out[-1] == -1 else out
 
     def query_rows(self, rows, k, n_probes=1, pass_1=None, *, exclude_self=True, allowed=None,
@@ -2080,7 +2240,7 @@ class IVF:
         return (ids, dist) if return_distances else ids
 
     def query_batch(self, qs, k, n_probes=1, pass_1=None, fast=False, *, allowed=None, return_distances=False,
-                    exclude=None, group=None):
+                    exclude=None, group=None, tags=None, tags_mode="any"):
         """(nq, d) queries -> (nq, k) int64 ids, rows padded with -1 when the
         reference would return fewer than k ids.  (The reference's README shows a
         2-d `ivf.query(queries, ...)` that its code does not support; this is that
@@ -2091,7 +2251,15 @@ class IVF:
         return_distances: ((nq, k) ids, (nq, k) exact squared distances), INTEGRATION.md §2f.
         exclude: a 1-d integer array, the row each query may not return or -1; not with fast=True.
         group: an int for every query, or a 1-d integer array with one entry per query: the group of rows (set_groups)
-        it may return, -1 for any; not with fast=True."""
+        it may return, -1 for any; not with fast=True.
+        tags: an int for every query, or a 1-d integer array with one 64-bit mask per query: the tags (set_tags) its
+        rows must carry — one of them with tags_mode "any", every one with "all" — 0 for any row; not
+        with fast=True."""
+        if tags is not None and fast:
+            raise NotImplementedError("IVF.query_batch: fast=True with tags= is not supported; "
+                                      "use the exact default (fast=False)")
+        if tags is not None:
+            tag_mode_of(tags_mode)
         if group is not None and fast:
             raise NotImplementedError("IVF.query_batch: fast=True with group= is not supported; "
                                       "use the exact default (fast=False)")
@@ -2102,7 +2270,7 @@ class IVF:
             raise NotImplementedError("IVF.query_batch: fast=True with return_distances=True is not supported; "
                                       "use the exact default (fast=False)")
         self._unsharded_device_index()
-        if allowed is not None or return_distances or exclude is not None or group is not None:
+        if allowed is not None or return_distances or exclude is not None or group is not None or tags is not None:
             if fast:
                 raise NotImplementedError("IVF.query_batch: fast=True with allowed= is not supported; "
                                           "use the exact default (fast=False)")
@@ -2111,9 +2279,12 @@ class IVF:
                 raise ValueError(f"exclude: one entry per query ({len(qs)}), got {len(exclude)}")
             if group is not None:
                 group = query_groups(group, len(qs))
+            if tags is not None:
+                tags = query_tags(tags, len(qs))
             qn, qp = self._prepare(qs)
             return self.device_index().query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed,
-                                                   return_distances=return_distances, exclude=exclude, group=group)
+                                                   return_distances=return_distances, exclude=exclude, group=group,
+                                                   tags=tags, tags_mode=tags_mode)
         if fast:
             return self.device_index().query_batch_raw(qs, k, n_probes, pass_1)
         R = self.pq.R
