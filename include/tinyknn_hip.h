@@ -900,13 +900,20 @@ int tk_index_shard_finish_dev(tk_index *ix, int slot, const float *q_dev, int64_
  * The same with ONE byte per query exchanged first — for data on which the optimistic form fails (one
  * query in 20 000 of the 100M x 128 index; a sharded batch holds 120 000):
  *   tk_index_shard_scan_head_dev   tables / probe lists / segment positions as tk_index_shard_scan_dev;
- *                                  the HEAD (two heap sizes of rows) of every first probed list this
- *                                  rank owns scored exactly into send_dev; bound_dev[nq] = the bound
- *                                  after it (order key, as tk_index_shard_bound_dev; 255 elsewhere);
+ *                                  the HEAD of every first probed list this rank owns — its first
+ *                                  ceil(2 R / 16) chunks, R the heap size; ceil(4 R / 16) where labels
+ *                                  repeat — scored exactly into send_dev; bound_dev[nq] = the bound
+ *                                  after it (order key, as tk_index_shard_bound_dev; 255 elsewhere).
+ *                                  Where the one-phase form does not apply (see above) this call IS
+ *                                  tk_index_shard_scan_dev, bound_dev is 255 for every query and the
+ *                                  plain call behind it does nothing;
  *   all-reduce(MIN, uint8)         by the caller;
  *   tk_index_shard_scan_plain_dev(bound_dev)
  *                                  the one-phase scan, with every query whose bound is above its table's
- *                                  limit kept on the exact kernel: the check at home cannot fail.
+ *                                  limit kept on the exact kernel: the check at home cannot fail.  (The
+ *                                  call writes "never" over those queries' limits in the slot: a scan
+ *                                  form run behind it on the same slot needs the batch's tables and
+ *                                  limits anew — tk_index_shard_coarse_dev, or a replicated scan call.)
  * Against tk_index_shard_scan_first_dev / _rest_dev, phase 1 scores ~14 chunks per query instead of a
  * whole list, and replays as many. */
 int tk_index_shard_scan_plain_dev(tk_index *ix, int slot, const float *q_dev, const void *q_pq_dev,
@@ -932,7 +939,7 @@ void *tk_shared_stream(int role, int i);
 tk_index *tk_index_clone_shard(tk_index *src, const int32_t *owner, int rank, int world);
 
 /* Longest (source -> home) stream of the slot's last tk_index_shard_scan_dev in uint4, fitted or
- * not: max-reduce it over the ranks and size `capacity` by it (the regions of the dense exchange
+ * not, among the streams THIS rank sends or receives: max-reduce it over the ranks and size `capacity` by it (the regions of the dense exchange
  * travel whole).  Synchronises with the device. */
 int tk_index_shard_usage(tk_index *ix, int slot, int64_t *max_stream_uint4);
 
@@ -999,7 +1006,15 @@ int tk_index_shard_finish_filtered_dev(tk_index *ix, int slot, const float *q_de
  *                                  the queries whose first list this rank owns, 255 elsewhere;
  *   all-reduce(MIN, uint8)         by the caller;
  *   tk_index_shard_scan_rest_dev   the slots behind the first: queries with B1 <= C on the plain
- *                                  kernel, the others on the exact one.  No query is scanned twice,
+ *                                  kernel, the others on the exact one — as are the queries whose
+ *                                  probe list wrapped (a -1 of the coarse heap names the last list)
+ *                                  and, where world * capacity is shorter than the longest list,
+ *                                  all of them (the plain kernel scores a segment that overflowed
+ *                                  its region to the buffer's tail).  The plain kernel's bytes are
+ *                                  clamp(plain sum of the signed table, -128, 127), padding rows of
+ *                                  a list's last chunk included; both kernels write the 16-byte
+ *                                  blocks of this rank's own segments and nothing else unless a
+ *                                  region overflowed.  No query is scanned twice,
  *                                  nothing is repaired afterwards; tk_index_shard_finish_dev / the
  *                                  filtered exchange (with this bound: no tk_index_shard_bound_dev)
  *                                  follow as after tk_index_shard_scan_dev and return the same ids.

@@ -9,12 +9,7 @@ And a replay whose bound is <= C from the first block on is the same replay on e
 import numpy as np
 import pytest
 
-
-def limits(T, avx):
-    neg = np.maximum(0, -T.min(axis=1))
-    chain = ((np.arange(len(T)) >> 1) & 1) if avx else np.zeros(len(T), int)
-    n0, n1 = int(neg[chain == 0].sum()), int(neg[chain == 1].sum())
-    return n0, n1, 127 - n0 - n1
+from shard_cpu_engine import limits     # (N_0, N_1, C): the one statement of the limit, shared with the wire model
 
 
 @pytest.mark.parametrize("order", ["avx", "sse"])
