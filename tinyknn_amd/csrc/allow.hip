@@ -47,11 +47,10 @@ __global__ __launch_bounds__(256) void allow_bits_kernel(const int64_t *__restri
     }
 }
 
-// One workgroup per query; threads stride over the query's contiguous chunk range [0, slot_prefix[S]) of dist / mins,
-// the slot prefix in LDS.  A chunk whose 16 bits are all set is not touched; one with none set is written without
-// being read; else its disallowed bytes take the empty value and its minimum byte is recomputed (tk_mask_chunk,
-// chunk_mask.h).  only (or NULL): [count, q_0, q_1, ...] — just these queries (the
-// exact re-scan of flagged queries rewrote their rows: rescan_flagged).
+// One workgroup per query over the query's probed chunks (tk_mask_probed, chunk_mask.h), a chunk's keep mask its 16
+// bits of the set: a chunk whose bits are all set is not touched; one with none set is written without being read;
+// else its disallowed bytes take the empty value and its minimum byte is recomputed.  only (or NULL): [count, q_0,
+// q_1, ...] — just these queries (tk_pass_query).
 template <bool SIGNED>
 __global__ __launch_bounds__(256) void allow_pass_kernel(uint4 *__restrict__ dist, int64_t cap,
                                                          uint8_t *__restrict__ mins, int64_t cap_min,
@@ -60,24 +59,10 @@ __global__ __launch_bounds__(256) void allow_pass_kernel(uint4 *__restrict__ dis
                                                          const uint16_t *__restrict__ bits,
                                                          const int *__restrict__ only)
 {
-    extern __shared__ int pre[];        // S + 1
-    int64_t q = blockIdx.x;
-    if (only) {
-        if ((int)blockIdx.x >= only[0]) return;
-        q = only[1 + blockIdx.x];
-    }
-    for (int s = threadIdx.x; s <= S; s += blockDim.x) pre[s] = slot_prefix[q * (S + 1) + s];
-    __syncthreads();
-    const int total = pre[S];
-    for (int f = threadIdx.x; f < total; f += blockDim.x) {
-        int lo = 0, hi = S;     // largest lo with pre[lo] <= f (pre is non-decreasing, pre[0] = 0)
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (pre[mid] <= f) lo = mid; else hi = mid;
-        }
-        const uint32_t b = bits[slot_chunk0[q * S + lo] + (f - pre[lo])];
-        tk_mask_chunk<SIGNED>(dist + q * cap + f, mins + q * cap_min + f, b);
-    }
+    int64_t q;
+    if (!tk_pass_query(blockIdx.x, only, q)) return;
+    tk_mask_probed<SIGNED>(dist, cap, mins, cap_min, slot_prefix, slot_chunk0, S, q,
+                           [=](int64_t c) -> uint32_t { return bits[c]; });
 }
 
 void tk_launch_allow_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
@@ -86,12 +71,9 @@ void tk_launch_allow_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_m
 {
     if (nq <= 0) return;
     const size_t lds = (size_t)(S + 1) * 4;
-    if (signd)
-        hipLaunchKernelGGL(allow_pass_kernel<true>, dim3((unsigned)nq), dim3(256), lds, s, dist, cap, mins, cap_min,
-                           slot_prefix, slot_chunk0, S, bits, only);
-    else
-        hipLaunchKernelGGL(allow_pass_kernel<false>, dim3((unsigned)nq), dim3(256), lds, s, dist, cap, mins, cap_min,
-                           slot_prefix, slot_chunk0, S, bits, only);
+    const auto kernel = signd ? allow_pass_kernel<true> : allow_pass_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nq), dim3(256), lds, s, dist, cap, mins, cap_min, slot_prefix, slot_chunk0,
+                       S, bits, only);
 }
 
 const tk_allow *allow_effective(const tk_allow *a)

@@ -19,31 +19,26 @@ struct Pending {
         bool host_out_kernel;       // ... written by copy_words_kernel instead of the copy engine
         hipEvent_t user_ev;         // recorded behind that copy (or NULL)
         void *dist_dev = nullptr;   // the rescoring's distances beside out_dev (or NULL: ids only)
-        const int64_t *exclude = nullptr;   // one row per query that the query may not return (or NULL), rows.hip
-        const int32_t *group = nullptr;     // one group per query that the query is restricted to (or NULL), groups.hip
-        const uint64_t *tags = nullptr;     // one tag mask per query that the query is restricted by (or NULL), tags.hip
-        int tag_mode = 0;                   // ... 0: a row passes with any of the mask's tags, 1: with all of them
+        TkCallRestrict r;           // what the call restricts its answers by
     } subs[2];
     int n_subs = 1;
     Work *w;
     Plan p;
     int k, n_probes, pass_1, qpq_f64;
-    const tk_allow *allow;          // allowed set of the batch (NULL: every row)
     hipStream_t st, sf, sl;         // scans: the caller's stream (+ tables) / coarse replay + descriptors / replay + rescoring
     Prof pf;
     bool units = false;
     bool plain = false;             // probed lists behind the first ones by the plain kernel (plain_scan.hip)
     bool coarse_launched = false;   // its coarse scan has been enqueued
-    // a held first call: a second call joins it with the same k, n_probes, pass_1, table dtype, allowed set and
-    // caller's stream `st` (its table build waits on `sf`), within `room` rows in all; both name a group array or neither,
-    // and both a tag array with the same mode or neither
+    // a held first call: a second call joins it with the same k, n_probes, pass_1, table dtype and caller's stream `st`
+    // (its table build waits on `sf`), within `room` rows in all, and restrictions that join (TkCallRestrict::joins)
     int64_t room = 0;
 
     // one call on the next workspace, every stream the caller's (pipe_begin picks the internal ones)
-    Pending(tk_index *ix, const Plan &p_, int k_, int n_probes_, int pass_1_, int qpq_f64_, const tk_allow *allow_,
-            hipStream_t caller, const Sub &call)
+    Pending(tk_index *ix, const Plan &p_, int k_, int n_probes_, int pass_1_, int qpq_f64_, hipStream_t caller,
+            const Sub &call)
         : subs{call}, w(&ix->works[ix->calls % ix->works.size()]), p(p_), k(k_), n_probes(n_probes_),
-          pass_1(pass_1_), qpq_f64(qpq_f64_), allow(allow_), st(caller), sf(caller), sl(caller)
+          pass_1(pass_1_), qpq_f64(qpq_f64_), st(caller), sf(caller), sl(caller)
     {
     }
 
@@ -56,24 +51,14 @@ struct Pending {
         TkSecond q2, qpq2, out2;
         void *dist;                 // each call's distances (or NULL), as its ids
         TkSecond dist2;
-        const int64_t *exclude;     // each call's excluded rows (or NULL)
-        TkSecond exclude2;
-        const int32_t *group;       // each call's groups (or NULL)
-        TkSecond group2;
-        const uint64_t *tags;       // each call's tag masks (or NULL)
-        TkSecond tags2;
+        TkRestrict r;               // what the batch is restricted by, each call's arrays as its ids
     };
-    bool grouped() const { return subs[0].group != nullptr; }    // (a pair: both calls or neither, coalesce_call)
-    bool tagged() const { return subs[0].tags != nullptr; }      // (a pair: both calls in one mode or neither)
-    int tag_mode() const { return subs[0].tag_mode; }
     Rows rows() const
     {
         const Sub &a = subs[0], &b = subs[1];
-        if (n_subs == 1) return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq, {}, {}, {}, a.dist_dev, {}, a.exclude, {}, a.group, {},
-                                     a.tags, {}};
+        if (n_subs == 1) return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq, {}, {}, {}, a.dist_dev, {}, a.r};
         return Rows{a.q_dev, a.qpq_dev, a.out_dev, a.nq + b.nq, {b.q_dev, a.nq}, {b.qpq_dev, a.nq}, {b.out_dev, a.nq},
-                    a.dist_dev, {b.dist_dev, a.nq}, a.exclude, {b.exclude, a.nq}, a.group, {b.group, a.nq},
-                    a.tags, {b.tags, a.nq}};
+                    a.dist_dev, {b.dist_dev, a.nq}, TkRestrict(a.r, &b.r, a.nq)};
     }
 };
 
@@ -103,8 +88,8 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->cslots_l, &ix->c_chunk_off, &ix->q, &ix->qpq, &ix->stage, &ix->owner,
                       &ix->local_chunk_off, &ix->rot_t, &ix->br_ynorm, &ix->br_vals, &ix->br_tau,
                       &ix->br_cand, &ix->br_count, &ix->br_out, &ix->br_q, &ix->br_sample, &ix->replay_counters,
-                      &ix->twin_list, &ix->twin_off, &ix->row_pos_off, &ix->row_pos, &ix->row_group,
-                      &ix->group_table, &ix->row_tags, &ix->tag_table};
+                      &ix->twin_list, &ix->twin_off, &ix->row_pos_off, &ix->row_pos, &ix->groups.by_row,
+                      &ix->groups.table, &ix->tags.by_row, &ix->tags.table};
     for (DevBuf *b : bufs) b->release();
     for (Work &w : ix->works) w.release();
     // (the internal streams belong to the process: shared_streams below)
@@ -1025,57 +1010,41 @@ static void plain_verdict_event(tk_index *ix, Work &w, int64_t nq, hipStream_t s
     }
 }
 
-// The allowed set over the probed chunks of queries [q0, q0 + nq) (allow.hip) — all of them, or (`only`) those of the
-// flag list: behind the list scans and every re-scan, in front of every replay that reads dist / mins
-static void apply_allow(Work &w, int64_t q0, int64_t nq, const Plan &p, const tk_allow *allow, hipStream_t st,
-                        const int *only = nullptr)
+// What the batch is restricted by, applied to the probed chunks of queries [q0, q0 + nq) — all of them, or (`only`)
+// those of the flag list: behind the list scans and every re-scan, in front of every replay that reads dist / mins.
+// One launch per kind that is set, in this order: the allowed set (allow.hip), the excluded rows (rows.hip), the groups
+// (groups.hip), the tags (tags.hip).  The per-query arrays are the batch's from row 0 (the passes add q0); a pair's
+// second call that names no array masks nothing.
+static void apply_restrictions(const tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, const TkRestrict &r,
+                               hipStream_t st, const int *only = nullptr)
 {
-    if (allow)
-        tk_launch_allow_pass(w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, nq,
-                             w.slot_prefix.as<int>() + q0 * (p.S + 1), w.slot_chunk0.as<int64_t>() + q0 * p.S, p.S,
-                             allow->bits.as<uint16_t>(), 1, only, st);
-}
-
-// One excluded row per query (rows.hip), where apply_allow runs and with its offsets; exclude / exclude2: the batch's
-// rows from row 0 (the pass adds q0).  exclude2.n_a > 0: a pair, whose second call's rows start there (exclude2.b NULL: they mask nothing)
-static void apply_exclude(const tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, const int64_t *exclude,
-                          TkSecond exclude2, hipStream_t st, const int *only = nullptr)
-{
-    if (!exclude && !exclude2.b) return;
-    TkRowPos tab;
-    tab.pos_off = ix->row_pos_off.as<int>(); tab.pos = ix->row_pos.as<int>(); tab.N = ix->N; tab.T = ix->total_ids;
-    tk_launch_exclude_pass(w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, nq,
-                           w.slot_prefix.as<int>() + q0 * (p.S + 1), w.slot_n.as<int>() + q0 * p.S,
-                           w.slot_loff.as<int64_t>() + q0 * p.S, p.S, tab, exclude, exclude2, q0, only, st);
-}
-
-// One group per query (groups.hip), where apply_allow runs and with its offsets; group / group2 as exclude / exclude2
-static void apply_groups(const tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, const int32_t *group,
-                         TkSecond group2, hipStream_t st, const int *only = nullptr)
-{
-    if (!group && !group2.b) return;
-    tk_launch_group_pass(w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, nq,
-                         w.slot_prefix.as<int>() + q0 * (p.S + 1), w.slot_chunk0.as<int64_t>() + q0 * p.S, p.S,
-                         ix->group_table.as<int32_t>(), group, group2, q0, 1, only, st);
-}
-
-// One tag mask per query (tags.hip), where apply_groups runs and with its arguments; all: the batch's mode
-static void apply_tags(const tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, const uint64_t *tags,
-                       TkSecond tags2, int all, hipStream_t st, const int *only = nullptr)
-{
-    if (!tags && !tags2.b) return;
-    tk_launch_tag_pass(w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, nq,
-                       w.slot_prefix.as<int>() + q0 * (p.S + 1), w.slot_chunk0.as<int64_t>() + q0 * p.S, p.S,
-                       ix->tag_table.as<uint64_t>(), tags, tags2, all, q0, 1, only, st);
+    if (!r.any()) return;
+    uint4 *dist = w.dist.as<uint4>();
+    uint8_t *mins = w.mins.as<uint8_t>();
+    const int *prefix = w.slot_prefix.as<int>() + q0 * (p.S + 1);
+    const int64_t *chunk0 = w.slot_chunk0.as<int64_t>() + q0 * p.S;
+    if (r.allow)
+        tk_launch_allow_pass(dist, p.cap, mins, p.cap_min, nq, prefix, chunk0, p.S, r.allow->bits.as<uint16_t>(), 1,
+                             only, st);
+    if (r.excludes()) {
+        TkRowPos tab;
+        tab.pos_off = ix->row_pos_off.as<int>(); tab.pos = ix->row_pos.as<int>(); tab.N = ix->N; tab.T = ix->total_ids;
+        tk_launch_exclude_pass(dist, p.cap, mins, p.cap_min, nq, prefix, w.slot_n.as<int>() + q0 * p.S,
+                               w.slot_loff.as<int64_t>() + q0 * p.S, p.S, tab, r.exclude, r.exclude2, q0, only, st);
+    }
+    if (r.grouped())
+        tk_launch_group_pass(dist, p.cap, mins, p.cap_min, nq, prefix, chunk0, p.S, ix->groups.table.as<int32_t>(),
+                             r.group, r.group2, q0, 1, only, st);
+    if (r.tagged())
+        tk_launch_tag_pass(dist, p.cap, mins, p.cap_min, nq, prefix, chunk0, p.S, ix->tags.table.as<uint64_t>(), r.tags,
+                           r.tags2, r.tag_mode, q0, 1, only, st);
 }
 
 // The queries the replay flagged (bound above the table's limit at the first plain block, plain_scan.hip): every probed
 // list again with the exact kernel.  list_built: the replay listed them itself (TkPlainCheck::flag_list); the count then
 // reaches the host through the replay behind the re-scan (replay_flagged_tail)
 static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, hipStream_t st,
-                           const tk_allow *allow, const int64_t *exclude, TkSecond exclude2, const int32_t *group,
-                           TkSecond group2, const uint64_t *tags, TkSecond tags2, int tag_mode,
-                           bool list_built = false)
+                           const TkRestrict &r, bool list_built = false)
 {
     int *list = w.flag_list.as<int>();
     if (!list_built) {
@@ -1086,10 +1055,7 @@ static void rescan_flagged(tk_index *ix, Work &w, int64_t q0, int64_t nq, const 
                           w.slot_prefix.as<int>() + q0 * (p.S + 1), w.slot_chunk0.as<int64_t>() + q0 * p.S,
                           p.S, (int)p.cap, w.dist.as<uint4>(), p.cap, w.mins.as<uint8_t>(), p.cap_min, 1,
                           ix->order, st, list);
-    apply_allow(w, q0, nq, p, allow, st, list);
-    apply_exclude(ix, w, q0, nq, p, exclude, exclude2, st, list);
-    apply_groups(ix, w, q0, nq, p, group, group2, st, list);
-    apply_tags(ix, w, q0, nq, p, tags, tags2, tag_mode, st, list);
+    apply_restrictions(ix, w, q0, nq, p, r, st, list);
 }
 
 // The tail behind a lane (or register-heap) replay that rode with the plain kernel: the queries it flagged — the lemma's
@@ -1149,9 +1115,7 @@ static Replay replay_form(const tk_index *ix, int64_t nq, const Plan &p)
 // rescoring.  q_dev: row 0 = query q0.
 int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
                const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain,
-               TkSecond q2, TkSecond out2, int *plain_flag, const tk_allow *allow, void *dist_dev, TkSecond dist2,
-               const int64_t *exclude, TkSecond exclude2, const int32_t *group, TkSecond group2,
-               const uint64_t *tags, TkSecond tags2, int tag_mode)
+               TkSecond q2, TkSecond out2, int *plain_flag, const TkRestrict &r, void *dist_dev, TkSecond dist2)
 {
     const TkReplayJob j = list_replay_job(ix, w, q0, nq, p);
     unsigned char *flags = w.repeat_flag.as<unsigned char>() + q0;
@@ -1159,10 +1123,7 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     // replay leaves for the exact re-scan — none on a list-sharded rank (plain_flag: the codes are elsewhere)
     TkPlainCheck check;
     if (plain) check = {w.plain0.as<int>() + q0, w.qlim.as<int>() + q0, plain_flag ? nullptr : w.flag_list.as<int>()};
-    apply_allow(w, q0, nq, p, allow, st);
-    apply_exclude(ix, w, q0, nq, p, exclude, exclude2, st);
-    apply_groups(ix, w, q0, nq, p, group, group2, st);
-    apply_tags(ix, w, q0, nq, p, tags, tags2, tag_mode, st);
+    apply_restrictions(ix, w, q0, nq, p, r, st);
     // heaps start fresh here, so packed entries apply.  Distinct labels: one query per
     // lane (or per wave for big heaps), and the few queries whose probe list wrapped a -1
     // (a list may then be scanned twice) re-run with the duplicate test.  Repeating labels
@@ -1243,13 +1204,13 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     const bool listed = form == Replay::Pair || form == Replay::Lanes || form == Replay::LanesTwin;
     const auto replay_wrapped = [&] { tk_launch_heap_replay_packed(j, flags, TK_RUN_WRAPPED, /*dedupe=*/true, st); };
     if (plain && form == Replay::LanesDedupe) {
-        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2, group, group2, tags, tags2, tag_mode);
+        rescan_flagged(ix, w, q0, nq, p, st, r);
         replay_wrapped();
     } else if (plain && plain_flag && (listed || form == Replay::PackedDistinct)) {
         tk_launch_shard_flag_plain(flags, nq, plain_flag, st);
         replay_wrapped();
     } else if (plain && listed) {
-        rescan_flagged(ix, w, q0, nq, p, st, allow, exclude, exclude2, group, group2, tags, tags2, tag_mode, true);
+        rescan_flagged(ix, w, q0, nq, p, st, r, true);
         replay_flagged_tail(ix, w, j, flags, st);
         plain_verdict_event(ix, w, nq, st);
     } else if (!plain && (form == Replay::Lanes || form == Replay::LanesTwin || form == Replay::PackedDistinct)) {
@@ -1285,12 +1246,12 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
 //
 // Both depths run a batch through the same stages below; only the streams and the event hand-offs differ.
 
-// A restricted batch (allowed set, group array, tag array) in the automatic plain-scan mode takes the exact scan and never touches
+// A restricted batch (TkRestrict::exact_scan) in the automatic plain-scan mode takes the exact scan and never touches
 // the state: a selective restriction flags many queries, and its verdicts would pause the plain path for the
 // unrestricted traffic.  Modes 1 and 2 hold for every batch.
 static bool plain_for(tk_index *ix, const Pending &b)
 {
-    if ((b.allow || b.grouped() || b.tagged()) && plain_adaptive(ix)) return false;
+    if (b.rows().r.exact_scan() && plain_adaptive(ix)) return false;
     return plain_now(ix, b.p);
 }
 
@@ -1350,8 +1311,8 @@ static void launch_probes(tk_index *ix, const Pending &b, hipStream_t st)
 static int batch_back(tk_index *ix, Pending &b, hipStream_t st)
 {
     const Pending::Rows r = b.rows();
-    TRY(stage_back(ix, *b.w, r.q, 0, r.nq, b.k, b.p, r.out, st, b.pf, b.plain, r.q2, r.out2, nullptr, b.allow, r.dist,
-                   r.dist2, r.exclude, r.exclude2, r.group, r.group2, r.tags, r.tags2, b.tag_mode()));
+    TRY(stage_back(ix, *b.w, r.q, 0, r.nq, b.k, b.p, r.out, st, b.pf, b.plain, r.q2, r.out2, nullptr, r.r, r.dist,
+                   r.dist2));
     for (int i = 0; i < b.n_subs; i++) {
         const Pending::Sub &u = b.subs[i];
         if (u.host_out && u.host_out_kernel)
@@ -1646,9 +1607,7 @@ static int coalesce_call(tk_index *ix, Pending &b)
     if (ix->held) {
         Pending &h = *ix->held;
         const bool joins = h.k == b.k && h.n_probes == b.n_probes && h.pass_1 == b.pass_1 && h.qpq_f64 == b.qpq_f64 &&
-                           h.st == b.st && h.subs[0].nq + call.nq <= h.room && h.allow == b.allow &&
-                           h.grouped() == b.grouped() &&   // (the two kinds take different scans: plain_for)
-                           h.tagged() == b.tagged() && (!h.tagged() || h.tag_mode() == b.tag_mode());  // (one mode per launch)
+                           h.st == b.st && h.subs[0].nq + call.nq <= h.room && h.subs[0].r.joins(call.r);
         if (joins) {
             if (h.sf != h.st) {            // the second call's inputs: the caller's work so far
                 HIPCHECK(hipEventRecord(ix->ev_in, h.st));
@@ -1671,21 +1630,19 @@ static int coalesce_call(tk_index *ix, Pending &b)
 static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_pq_dev,
                                 int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
                                 int64_t *out_ids_dev, int64_t *out_ids_pinned, hipEvent_t done_ev,
-                                void *stream, const tk_allow *allow = nullptr, void *out_dist_dev = nullptr,
-                                const int64_t *exclude_dev = nullptr, const int32_t *group_dev = nullptr,
-                                const uint64_t *tags_dev = nullptr, int tag_mode = 0)
+                                void *stream, TkCallRestrict r = TkCallRestrict(), void *out_dist_dev = nullptr)
 {
     Plan p;
     TRY(make_plan(ix, k, n_probes, pass_1, p));
     ARGCHECK(nq >= 0, "nq");
     ARGCHECK(!ix->sharded, "list-sharded index: use tk_index_shard_scan_dev / _finish_dev");
-    ARGCHECK(tag_mode == 0 || tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
-    if (!tags_dev) tag_mode = 0;
-    if (allow) {
-        ARGCHECK(allow->ix == ix, "the allowed set belongs to another index");
-        if (allow->lists_gen != ix->lists_gen)
+    ARGCHECK(r.tag_mode == 0 || r.tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
+    if (!r.tags) r.tag_mode = 0;
+    if (r.allow) {
+        ARGCHECK(r.allow->ix == ix, "the allowed set belongs to another index");
+        if (r.allow->lists_gen != ix->lists_gen)
             return fail(TK_ERR_STATE, "the allowed set was made for an earlier layout of the lists: make it again");
-        allow = allow_effective(allow);
+        r.allow = allow_effective(r.allow);
     }
     hipStream_t caller = (hipStream_t)stream;
     {
@@ -1694,9 +1651,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
                         cs != hipStreamCaptureStatusNone;
         (void)hipGetLastError();
     }
-    if (exclude_dev && nq > 0) TRY(row_pos_ensure(ix));     // (the first excluding call of a layout: rows.hip)
-    if (group_dev && nq > 0) TRY(group_table_ensure(ix));   // (groups set for every row; the first grouped call of a layout: groups.hip)
-    if (tags_dev && nq > 0) TRY(tag_table_ensure(ix));      // (the same for tags: tags.hip)
+    TRY(r.ensure_tables(ix, nq));       // (the first excluding / grouped / tagged call of a layout)
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     const int64_t ms = sub_batch(p);
     ARGCHECK(!(out_ids_pinned || done_ev) || (nq >= 1 && nq <= ms),
@@ -1706,9 +1661,8 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     //  fit the chip in one round of waves: 5.1 M queries/s paired against 7.7 M alone,
     //  profiles/r04/bench_full_first.json)
     if (ix->depth > 1 && ix->coalesce == 2 && (ix->ids_unique || twin_replay(ix, p)) && nq >= 1 && nq <= ms) {
-        Pending b(ix, p, k, n_probes, pass_1, q_pq_is_f64, allow, caller,
-                  {q_dev, q_pq_dev, out_ids_dev, nq, out_ids_pinned, ix->host_out_kernel, done_ev, out_dist_dev,
-                   exclude_dev, group_dev, tags_dev, tag_mode});
+        Pending b(ix, p, k, n_probes, pass_1, q_pq_is_f64, caller,
+                  {q_dev, q_pq_dev, out_ids_dev, nq, out_ids_pinned, ix->host_out_kernel, done_ev, out_dist_dev, r});
         return coalesce_call(ix, b);
     }
     TRY(launch_held(ix));
@@ -1719,12 +1673,11 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     const size_t dsz = ix->data_dtype == TK_DATA_F64 ? 8 : 4;         // the rescoring's type (the queries are float32)
     for (int64_t o = 0; o < nq; o += part) {
         const int64_t sub = nq - o < part ? nq - o : part;
-        Pending b(ix, p, k, n_probes, pass_1, q_pq_is_f64, allow, caller,
+        Pending b(ix, p, k, n_probes, pass_1, q_pq_is_f64, caller,
                   {q_dev + o * ix->d, (const char *)q_pq_dev + (size_t)o * ix->dq * esz, out_ids_dev + o * k, sub,
                    out_ids_pinned, ix->host_out_kernel, done_ev,
                    out_dist_dev ? (char *)out_dist_dev + (size_t)o * k * dsz : nullptr,
-                   exclude_dev ? exclude_dev + o : nullptr,       // (a part's rows of the CALL's arrays)
-                   group_dev ? group_dev + o : nullptr, tags_dev ? tags_dev + o : nullptr, tag_mode});
+                   r.at(o)});       // (a part's rows of the CALL's arrays)
         if (ix->depth == 1) {
             ix->calls++;
             TRY(run_batch_inline(ix, b));
@@ -1887,16 +1840,15 @@ struct BufRelease {
 
 static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
                             int n_probes, int pass_1, int64_t *out_ids, int64_t *out_probes, int64_t *out_heap_idx,
-                            int32_t *out_heap_val, const tk_allow *allow, void *out_dist = nullptr,
-                            const int64_t *exclude = nullptr, const int64_t *rows = nullptr,
-                            const int32_t *group = nullptr, const uint64_t *tags = nullptr, int tag_mode = 0)
+                            int32_t *out_heap_val, TkCallRestrict r = TkCallRestrict(), void *out_dist = nullptr,
+                            const int64_t *rows = nullptr)
 {
     IXLOCK(ix);
     Plan p;
     TRY(make_plan(ix, k, n_probes, pass_1, p));
     ARGCHECK(nq >= 0, "nq");
     if (nq == 0) return TK_OK;
-    if (exclude || rows) ARGCHECK(!ix->sharded, "list-sharded index: excluded rows / stored rows as queries are not supported");
+    if (r.exclude || rows) ARGCHECK(!ix->sharded, "list-sharded index: excluded rows / stored rows as queries are not supported");
     // rows: the queries are the stored rows named (tk_index_query_rows) — gathered below, q / q_pq unused
     if (rows) {
         ARGCHECK(ix->have_data, "set_data first");
@@ -1904,28 +1856,28 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
     }
     // exclude: validated here, and dropped where no entry excludes anything (no table, no pass)
     bool excludes = false;
-    if (exclude)
+    if (r.exclude)
         for (int64_t i = 0; i < nq; i++) {
-            ARGCHECK(exclude[i] >= -1 && exclude[i] < ix->N, "exclude: entries must lie in [-1, N)");
-            excludes = excludes || exclude[i] >= 0;
+            ARGCHECK(r.exclude[i] >= -1 && r.exclude[i] < ix->N, "exclude: entries must lie in [-1, N)");
+            excludes = excludes || r.exclude[i] >= 0;
         }
-    if (!excludes) exclude = nullptr;
+    if (!excludes) r.exclude = nullptr;
     // group: the same (an array of only -1 restricts nothing: no table, no pass, the scan an unrestricted call takes)
     bool groups = false;
-    if (group)
+    if (r.group)
         for (int64_t i = 0; i < nq; i++) {
-            ARGCHECK(group[i] >= -1, "group: entries must be a group id or -1");
-            groups = groups || group[i] >= 0;
+            ARGCHECK(r.group[i] >= -1, "group: entries must be a group id or -1");
+            groups = groups || r.group[i] >= 0;
         }
-    if (!groups) group = nullptr;
-    if (group) ARGCHECK(!ix->sharded, "list-sharded index: row groups are not supported");
+    if (!groups) r.group = nullptr;
+    if (r.group) ARGCHECK(!ix->sharded, "list-sharded index: row groups are not supported");
     // tags: the same (an array of only zeros restricts nothing)
-    ARGCHECK(tag_mode == 0 || tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
+    ARGCHECK(r.tag_mode == 0 || r.tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
     bool tagged = false;
-    if (tags)
-        for (int64_t i = 0; i < nq && !tagged; i++) tagged = tags[i] != 0;
-    if (!tagged) tags = nullptr;
-    if (tags) ARGCHECK(!ix->sharded, "list-sharded index: row tags are not supported");
+    if (r.tags)
+        for (int64_t i = 0; i < nq && !tagged; i++) tagged = r.tags[i] != 0;
+    if (!tagged) r.tags = nullptr;
+    if (r.tags) ARGCHECK(!ix->sharded, "list-sharded index: row tags are not supported");
     ARGCHECK(!(out_probes || out_heap_idx || out_heap_val) || nq <= sub_batch(p),
              "debug outputs need the batch to fit one sub-batch");
     const size_t esz = q_pq_is_f64 ? 8 : 4;
@@ -1933,21 +1885,20 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
     TRY(ix->qpq.ensure((size_t)nq * ix->dq * esz));
     DevBuf outbuf, distbuf, exbuf, rowbuf, grbuf, tgbuf;  // separate from the sub-batch `out` workspace
     BufRelease rel{{&outbuf, &distbuf, &exbuf, &rowbuf, &grbuf, &tgbuf}};
+    // a per-query host array (or NULL) as the device array the call below names
+    const auto upload = [&](auto *&arr, DevBuf &buf) -> int {
+        if (!arr) return TK_OK;
+        TRY(buf.ensure((size_t)nq * sizeof *arr));
+        HIPCHECK(hipMemcpy(buf.p, arr, (size_t)nq * sizeof *arr, hipMemcpyHostToDevice));
+        arr = (std::remove_reference_t<decltype(arr)>)buf.p;
+        return TK_OK;
+    };
     const size_t dist_bytes = (size_t)nq * k * (ix->data_dtype == TK_DATA_F64 ? 8 : 4);
     TRY(outbuf.ensure((size_t)nq * k * 8));
     if (out_dist) TRY(distbuf.ensure(dist_bytes));
-    if (exclude) {
-        TRY(exbuf.ensure((size_t)nq * 8));
-        HIPCHECK(hipMemcpy(exbuf.p, exclude, (size_t)nq * 8, hipMemcpyHostToDevice));
-    }
-    if (group) {
-        TRY(grbuf.ensure((size_t)nq * 4));
-        HIPCHECK(hipMemcpy(grbuf.p, group, (size_t)nq * 4, hipMemcpyHostToDevice));
-    }
-    if (tags) {
-        TRY(tgbuf.ensure((size_t)nq * 8));
-        HIPCHECK(hipMemcpy(tgbuf.p, tags, (size_t)nq * 8, hipMemcpyHostToDevice));
-    }
+    TRY(upload(r.exclude, exbuf));
+    TRY(upload(r.group, grbuf));
+    TRY(upload(r.tags, tgbuf));
     if (rows) {
         TRY(rowbuf.ensure((size_t)nq * 8));
         HIPCHECK(hipMemcpy(rowbuf.p, rows, (size_t)nq * 8, hipMemcpyHostToDevice));
@@ -1956,13 +1907,11 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
         HIPCHECK(hipMemcpy(ix->q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
         HIPCHECK(hipMemcpy(ix->qpq.p, q_pq, (size_t)nq * ix->dq * esz, hipMemcpyHostToDevice));
     }
-    int r = query_batch_dev_impl(ix, ix->q.as<float>(), ix->qpq.p, q_pq_is_f64, nq, k, n_probes, pass_1,
-                                 outbuf.as<int64_t>(), nullptr, nullptr, nullptr, allow, out_dist ? distbuf.p : nullptr,
-                                 exclude ? exbuf.as<int64_t>() : nullptr, group ? grbuf.as<int32_t>() : nullptr,
-                                 tags ? tgbuf.as<uint64_t>() : nullptr, tag_mode);
-    if (r == TK_OK) r = flush_pending(ix);
+    int rc = query_batch_dev_impl(ix, ix->q.as<float>(), ix->qpq.p, q_pq_is_f64, nq, k, n_probes, pass_1,
+                                  outbuf.as<int64_t>(), nullptr, nullptr, nullptr, r, out_dist ? distbuf.p : nullptr);
+    if (rc == TK_OK) rc = flush_pending(ix);
     const Work &lw = ix->works[(ix->calls + ix->works.size() - 1) % ix->works.size()];   // last used
-    if (r == TK_OK) {
+    if (rc == TK_OK) {
         hipError_t e = hipDeviceSynchronize();
         if (e == hipSuccess) e = hipMemcpy(out_ids, outbuf.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost);
         if (e == hipSuccess && out_dist) e = hipMemcpy(out_dist, distbuf.p, dist_bytes, hipMemcpyDeviceToHost);
@@ -1972,9 +1921,9 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
             e = hipMemcpy(out_heap_idx, lw.heap_idx.p, (size_t)nq * p.R * 8, hipMemcpyDeviceToHost);
         if (e == hipSuccess && out_heap_val)
             e = hipMemcpy(out_heap_val, lw.heap_val.p, (size_t)nq * p.R * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = fail(TK_ERR_HIP, hipGetErrorString(e));
+        if (e != hipSuccess) rc = fail(TK_ERR_HIP, hipGetErrorString(e));
     }
-    return r;
+    return rc;
 }
 
 extern "C" int tk_index_query_batch(tk_index *ix, const float *q, const void *q_pq,
@@ -1983,7 +1932,7 @@ extern "C" int tk_index_query_batch(tk_index *ix, const float *q, const void *q_
                                     int32_t *out_heap_val)
 {
     return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
-                            out_heap_val, nullptr);
+                            out_heap_val);
 }
 
 // the restricted calls (allow.hip) — extend IVF.query, ivf.py:106-163: `insert` (_fast_pq_256.pyx:114-118,
@@ -1995,7 +1944,7 @@ extern "C" int tk_index_query_batch_allow(tk_index *ix, const tk_allow *allow, c
 {
     if (!allow) return fail(TK_ERR_ARG, "bad argument: null allowed set");
     return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
-                            out_heap_val, allow);
+                            out_heap_val, {allow});
 }
 
 extern "C" int tk_index_query_batch_dev_allow(tk_index *ix, const tk_allow *allow, const float *q_dev,
@@ -2006,7 +1955,7 @@ extern "C" int tk_index_query_batch_dev_allow(tk_index *ix, const tk_allow *allo
     IXLOCK(ix);
     if (!allow) return fail(TK_ERR_ARG, "bad argument: null allowed set");
     return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev,
-                                out_ids_pinned, (hipEvent_t)done_event, stream, allow);
+                                out_ids_pinned, (hipEvent_t)done_event, stream, {allow});
 }
 
 // ids and the rescoring's exact squared distances (allow: NULL = every row) — tinyknn_hip.h
@@ -2016,7 +1965,7 @@ extern "C" int tk_index_query_batch_dist(tk_index *ix, const tk_allow *allow, co
 {
     if (!out_dist && nq > 0) return fail(TK_ERR_ARG, "bad argument: null distance buffer");
     return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, nullptr, nullptr, nullptr,
-                            allow, out_dist);
+                            {allow}, out_dist);
 }
 
 extern "C" int tk_index_query_batch_dev_dist(tk_index *ix, const tk_allow *allow, const float *q_dev,
@@ -2027,7 +1976,7 @@ extern "C" int tk_index_query_batch_dev_dist(tk_index *ix, const tk_allow *allow
     IXLOCK(ix);
     if (!out_dist_dev && nq > 0) return fail(TK_ERR_ARG, "bad argument: null distance buffer");
     return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
-                                (hipEvent_t)done_event, stream, allow, out_dist_dev);
+                                (hipEvent_t)done_event, stream, {allow}, out_dist_dev);
 }
 
 // everything at once: an allowed set, one excluded row per query, distances, the debug outputs — any of them NULL
@@ -2038,7 +1987,7 @@ extern "C" int tk_index_query_batch_ex2(tk_index *ix, const tk_allow *allow, con
                                         int32_t *out_heap_val)
 {
     return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
-                            out_heap_val, allow, out_dist, exclude);
+                            out_heap_val, {allow, exclude}, out_dist);
 }
 
 extern "C" int tk_index_query_batch_dev_ex2(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
@@ -2048,7 +1997,7 @@ extern "C" int tk_index_query_batch_dev_ex2(tk_index *ix, const tk_allow *allow,
 {
     IXLOCK(ix);
     return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
-                                (hipEvent_t)done_event, stream, allow, out_dist_dev, exclude_dev);
+                                (hipEvent_t)done_event, stream, {allow, exclude_dev}, out_dist_dev);
 }
 
 // ... and one group per query (groups.hip, tinyknn_hip.h): _ex2 with one more pointer
@@ -2058,7 +2007,7 @@ extern "C" int tk_index_query_batch_ex3(tk_index *ix, const tk_allow *allow, con
                                         int64_t *out_probes, int64_t *out_heap_idx, int32_t *out_heap_val)
 {
     return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
-                            out_heap_val, allow, out_dist, exclude, nullptr, group);
+                            out_heap_val, {allow, exclude, group}, out_dist);
 }
 
 extern "C" int tk_index_query_batch_dev_ex3(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
@@ -2068,7 +2017,7 @@ extern "C" int tk_index_query_batch_dev_ex3(tk_index *ix, const tk_allow *allow,
 {
     IXLOCK(ix);
     return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
-                                (hipEvent_t)done_event, stream, allow, out_dist_dev, exclude_dev, group_dev);
+                                (hipEvent_t)done_event, stream, {allow, exclude_dev, group_dev}, out_dist_dev);
 }
 
 // ... and one tag mask per query (tags.hip, tinyknn_hip.h): _ex3 with one more pointer and the call's mode
@@ -2079,7 +2028,7 @@ extern "C" int tk_index_query_batch_ex4(tk_index *ix, const tk_allow *allow, con
                                         int32_t *out_heap_val)
 {
     return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
-                            out_heap_val, allow, out_dist, exclude, nullptr, group, tags, tag_mode);
+                            out_heap_val, {allow, exclude, group, tags, tag_mode}, out_dist);
 }
 
 extern "C" int tk_index_query_batch_dev_ex4(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
@@ -2090,8 +2039,8 @@ extern "C" int tk_index_query_batch_dev_ex4(tk_index *ix, const tk_allow *allow,
 {
     IXLOCK(ix);
     return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
-                                (hipEvent_t)done_event, stream, allow, out_dist_dev, exclude_dev, group_dev, tags_dev,
-                                tag_mode);
+                                (hipEvent_t)done_event, stream, {allow, exclude_dev, group_dev, tags_dev, tag_mode},
+                                out_dist_dev);
 }
 
 // the stored rows `rows` as queries, each leaving itself out where exclude_self
@@ -2103,7 +2052,7 @@ extern "C" int tk_index_query_rows(tk_index *ix, const tk_allow *allow, const in
     ARGCHECK(ix && (nq == 0 || rows), "null index / rows");
     ARGCHECK(ix->have_pq && ix->have_centers, "set_pq and set_centers first");
     return query_batch_host(ix, nullptr, nullptr, ix->rot_d_pad > 0, nq, k, n_probes, pass_1, out_ids, out_probes,
-                            out_heap_idx, out_heap_val, allow, out_dist, exclude_self ? rows : nullptr, rows);
+                            out_heap_idx, out_heap_val, {allow, exclude_self ? rows : nullptr}, out_dist, rows);
 }
 
 extern "C" int tk_index_set_heap_mode(tk_index *ix, int mode)

@@ -164,6 +164,26 @@ struct Work {
     }
 };
 
+// a table made for ONE layout of the lists: whether it exists, the lists_gen it was made for, how often one was made
+struct TkTableState {
+    bool ok = false;
+    uint64_t gen = 0;
+    int64_t builds = 0;
+    bool current(uint64_t lists_gen) const { return ok && gen == lists_gen; }
+    void made(uint64_t lists_gen) { ok = true, gen = lists_gen, builds++; }
+};
+
+// One value per row that queries are restricted by (row_table.hip): by row id as the caller set them (n of them, 0:
+// none), and in list-position order, 16 per stored chunk — made by the first call that names an array of the kind.
+// noun / called / unit: what the kind's error texts name ("group" / "grouped" / "id").
+struct TkRowTable {
+    size_t esz;
+    const char *noun, *called, *unit;
+    DevBuf by_row, table;
+    int64_t n = 0;
+    TkTableState state;
+};
+
 #define IXLOCK(ix_)                                               \
     std::unique_lock<std::recursive_mutex> ixlock_;               \
     if (ix_) ixlock_ = std::unique_lock<std::recursive_mutex>((ix_)->mu)
@@ -201,23 +221,11 @@ struct tk_index {
     uint64_t lists_gen = 0;    // counts the times the lists were (re-)set: an allowed set is valid for one layout
     // where every row is stored (rows.hip): made by the first call that names an exclude array, for ONE layout
     DevBuf row_pos_off, row_pos;
-    bool row_pos_ok = false;
-    uint64_t row_pos_gen = 0;  // lists_gen when it was made
-    int64_t row_pos_builds = 0;
-    // a group id per row (groups.hip): by row id as tk_index_set_groups uploaded them (groups_n of them, 0: none), and in
-    // list-position order — made by the first call that names a group array, for ONE layout, as the table above
-    DevBuf row_group, group_table;
-    int64_t groups_n = 0;
-    bool group_table_ok = false;
-    uint64_t group_table_gen = 0;
-    int64_t group_table_builds = 0;
-    // a 64-bit tag mask per row (tags.hip): by row id as tk_index_set_tags uploaded them (tags_n of them, 0: none), and
-    // in list-position order — made by the first call that names a tag array, for ONE layout, as the group table
-    DevBuf row_tags, tag_table;
-    int64_t tags_n = 0;
-    bool tag_table_ok = false;
-    uint64_t tag_table_gen = 0;
-    int64_t tag_table_builds = 0;
+    TkTableState row_pos_state;
+    // a group id per row (groups.hip) and a 64-bit tag mask per row (tags.hip): by row id as tk_index_set_groups /
+    // tk_index_set_tags uploaded them, and in list-position order — made by the first call that names a group / tag
+    // array, for ONE layout, as the table above
+    TkRowTable groups{4, "group", "grouped", "id"}, tags{8, "tag", "tagged", "mask"};
     // members per (list, column of nearest): list l holds its column-0 members first, then column 1's, ...
     // (group_data_by_indices); known after tk_index_build_dev / tk_index_add_rows (list_kp = columns), not
     // after a host upload (list_kp = 0: tk_index_add_rows takes them from the caller)
@@ -340,6 +348,57 @@ struct ListLayout {
 };
 // the set a batch applies: NULL where the set allows every stored row (no kernel at all)
 const tk_allow *allow_effective(const tk_allow *a);
+
+// What ONE call restricts its answers by, any of it absent: an allowed set (allow.hip), and per query (device arrays,
+// or NULL) a row the query may not return (rows.hip), a group it is restricted to (groups.hip), a tag mask it is
+// restricted by (tags.hip) in the call's tag_mode (0: a row passes with any of the mask's tags, 1: with all of them).
+struct TkCallRestrict {
+    const tk_allow *allow = nullptr;
+    const int64_t *exclude = nullptr;
+    const int32_t *group = nullptr;
+    const uint64_t *tags = nullptr;
+    int tag_mode = 0;
+    // the call's rows from row o on
+    TkCallRestrict at(int64_t o) const
+    {
+        return {allow, exclude ? exclude + o : nullptr, group ? group + o : nullptr, tags ? tags + o : nullptr, tag_mode};
+    }
+    // Join rule: two calls run as one batch (coalesce_call) with the same allowed set, both grouped or neither (the
+    // two kinds take different scans: exact_scan), both tagged in one mode or neither (one mode per launch).
+    bool joins(const TkCallRestrict &o) const
+    {
+        return allow == o.allow && !group == !o.group && !tags == !o.tags && (!tags || tag_mode == o.tag_mode);
+    }
+    // Table rule: what the passes read exists before the call's first launch (each made once per layout of the lists,
+    // synchronising the device; TK_ERR_STATE where the index has no groups / tags for every row).  Defined below.
+    int ensure_tables(tk_index *ix, int64_t nq) const;
+};
+
+// What a BATCH is restricted by: the one call's, or (a pair, joins()) the first call's with the second call's arrays
+// behind them — a TkSecond with b == NULL: the second call's rows are unrestricted in that kind.
+struct TkRestrict {
+    const tk_allow *allow = nullptr;
+    int tag_mode = 0;
+    const int64_t *exclude = nullptr;
+    const int32_t *group = nullptr;
+    const uint64_t *tags = nullptr;
+    TkSecond exclude2, group2, tags2;
+    TkRestrict() = default;
+    // a: the first call; b (or NULL: one call): the second, whose rows start at batch row n_a
+    TkRestrict(const TkCallRestrict &a, const TkCallRestrict *b = nullptr, int64_t n_a = 0)
+        : allow(a.allow), tag_mode(a.tag_mode), exclude(a.exclude), group(a.group), tags(a.tags)
+    {
+        if (b) exclude2 = {b->exclude, n_a}, group2 = {b->group, n_a}, tags2 = {b->tags, n_a};
+    }
+    bool excludes() const { return exclude || exclude2.b; }
+    bool grouped() const { return group || group2.b; }
+    bool tagged() const { return tags || tags2.b; }
+    // Anything set: the batch launches at least one restricting pass
+    bool any() const { return allow || excludes() || grouped() || tagged(); }
+    // Exact-scan rule: a batch with an allowed set, a group array or a tag array takes the exact scan in the automatic
+    // plain-scan mode (plain_for); an excluded row masks a byte or two and does not.
+    bool exact_scan() const { return allow || grouped() || tagged(); }
+};
 struct Plan {
     int kc, rescore, R, S;
     int64_t cap;       // uint4 per query in the distance buffer
@@ -426,17 +485,27 @@ int stage_coarse_rest(tk_index *ix, Work &w, const float *q_dev, int64_t nq, con
 int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq, int k,
                const Plan &p, int64_t *out_dev, hipStream_t st, Prof &pf, bool plain = false,
                TkSecond q2 = TkSecond(), TkSecond out2 = TkSecond(), int *plain_flag = nullptr,
-               const tk_allow *allow = nullptr, void *dist_dev = nullptr, TkSecond dist2 = TkSecond(),
-               const int64_t *exclude = nullptr, TkSecond exclude2 = TkSecond(), const int32_t *group = nullptr,
-               TkSecond group2 = TkSecond(), const uint64_t *tags = nullptr, TkSecond tags2 = TkSecond(),
-               int tag_mode = 0);
+               const TkRestrict &r = TkRestrict(), void *dist_dev = nullptr, TkSecond dist2 = TkSecond());
+// a table of the index's current lists may be made now: there are lists, and no stream capture is under way
+int table_may_build(const tk_index *ix, const char *table, const char *call);
 // rows.hip: the row-position table of the index's current lists exists (made now if not: synchronises the device)
 int row_pos_ensure(tk_index *ix);
-// groups.hip: groups for every row the index has (else TK_ERR_STATE) and the group table of its current lists (made
-// now if not: synchronises the device)
-int group_table_ensure(tk_index *ix);
-// tags.hip: the same for the tags and the tag table
-int tag_table_ensure(tk_index *ix);
+// row_table.hip — set: calls still owed run first, then the values are uploaded (n == N of them; `check`, if any, has
+// the last word on them) or (n == 0) dropped.  ensure: values for every row the index has (else TK_ERR_STATE) and the
+// table of its current lists, made now if not by `launch` (synchronises the device).  info: tk_index_*_table's info4.
+int row_table_set(tk_index *ix, TkRowTable &t, const void *vals, int64_t n,
+                  int (*check)(const void *vals, int64_t n) = nullptr);
+int row_table_ensure(tk_index *ix, TkRowTable &t, void (*launch)(const tk_index *ix));
+int row_table_info(const tk_index *ix, const TkRowTable &t, int64_t *info4);
+int group_table_ensure(tk_index *ix);       // groups.hip
+int tag_table_ensure(tk_index *ix);         // tags.hip
+inline int TkCallRestrict::ensure_tables(tk_index *ix, int64_t nq) const
+{
+    if (exclude && nq > 0) TRY(row_pos_ensure(ix));
+    if (group && nq > 0) TRY(group_table_ensure(ix));
+    if (tags && nq > 0) TRY(tag_table_ensure(ix));
+    return TK_OK;
+}
 int head_chunks(const tk_index *ix, const Plan &p);    // chunks of a first probed list the exact kernel keeps (head mode)
 // the workspace's three pair sets: whole lists exact / plain tiles / heads
 TkPairSet exact_pairs(const Work &w);

@@ -47,9 +47,12 @@ void tk_launch_scan_probes(const uint4 *codes, int M, const uint4 *tables, int64
                            int max_flat_chunks, uint4 *dist, int64_t cap, uint8_t *mins,
                            int64_t min_stride, int signd, int order, hipStream_t s,
                            const int *only = nullptr);
-// allow.hip: the allowed set applied to the probed chunks of a batch — disallowed bytes of dist take the empty value
-// (127 signed, 255 unsigned), touched chunks' minima are recomputed.  bits: 16 per stored chunk (list_chunk_off order);
-// only: NULL (all nq queries) or [count, q_0, ...] (nq = its capacity)
+// The restricting passes (allow.hip here; rows.hip, groups.hip, tags.hip below; device bodies in chunk_mask.h) run over
+// the probed chunks of a batch: the bytes of dist whose rows a query may not return take the empty value (127 signed,
+// 255 unsigned), touched chunks' minima are recomputed.  They share dist / mins rows, the slot arrays, signd, and
+// only: NULL (all nq queries) or [count, q_0, ...] (nq = its capacity).  A per-query array comes as x_a / x_b: the
+// entries of the batch's first call (from batch row q0 on the slot arrays start at) and of its second call, either NULL.
+// allow.hip: an allowed set — bits: 16 per stored chunk (list_chunk_off order)
 void tk_launch_allow_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
                           const int *slot_prefix, const int64_t *slot_chunk0, int S, const uint16_t *bits,
                           int signd, const int *only, hipStream_t s);
@@ -493,24 +496,20 @@ struct TkRowPos {
     const int *pos_off = nullptr, *pos = nullptr;
     int64_t N = 0, T = 0;
 };
-// ... and one excluded row per query: every copy of it in a probed slot takes the empty value (127: signed bytes) in dist, its chunk's
-// byte of mins is recomputed.  Slot arrays, dist / mins rows and `only` as tk_launch_allow_pass; ex_a / ex_b: the
-// excluded rows of the batch's first call (from batch row q0 on the slot arrays start at) and of its second call
+// ... and one excluded row per query: every copy of it in a probed slot is masked (signed bytes only); entries outside
+// [0, N) exclude nothing
 void tk_launch_exclude_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
                             const int *slot_prefix, const int *slot_n, const int64_t *slot_label_off, int S,
                             const TkRowPos &tab, const int64_t *ex_a, TkSecond ex_b, int64_t q0, const int *only,
                             hipStream_t s);
-// groups.hip: one group per query — the probed rows of another group take the empty value, as the allowed set's pass
-// masks (slot arrays, dist / mins rows, signd and `only` as tk_launch_allow_pass).  table: 16 int32 per stored chunk
-// (list_chunk_off order); g_a / g_b: the groups of the batch's first call (from batch row q0 on the slot arrays start
-// at) and of its second call, each NULL or with entries < 0 for queries that are not restricted
+// groups.hip: one group per query — the probed rows of another group are masked.  table: 16 int32 per stored chunk
+// (list_chunk_off order); entries < 0 of g_a / g_b: queries that are not restricted
 void tk_launch_group_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
                           const int *slot_prefix, const int64_t *slot_chunk0, int S, const int32_t *table,
                           const int32_t *g_a, TkSecond g_b, int64_t q0, int signd, const int *only, hipStream_t s);
-// tags.hip: one 64-bit tag mask per query — the probed rows that do not pass it take the empty value, as the group pass
-// masks (every argument it shares with tk_launch_group_pass as there).  table: 16 uint64 per stored chunk; m_a / m_b:
-// the masks of the batch's first and second call, each NULL or with entries of 0 for queries that are not restricted;
-// all: 0 = a row passes with (tags & m) != 0, 1 = with (tags & m) == m, for both calls
+// tags.hip: one 64-bit tag mask per query — the probed rows that do not pass it are masked.  table: 16 uint64 per
+// stored chunk; entries of 0 of m_a / m_b: queries that are not restricted; all: 0 = a row passes with
+// (tags & m) != 0, 1 = with (tags & m) == m, for both calls
 void tk_launch_tag_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
                         const int *slot_prefix, const int64_t *slot_chunk0, int S, const uint64_t *table,
                         const uint64_t *m_a, TkSecond m_b, int all, int64_t q0, int signd, const int *only,

@@ -12,6 +12,7 @@
 // in no particular order.  4 (N + 2) + 4 T bytes: 0.8 GB for 100M rows stored once, 1.2 GB stored twice.  Made from
 // the device-resident labels by the first call that names an exclude array, for one layout of the lists (lists_gen).
 #include "api_internal.h"
+#include "chunk_mask.h"
 
 // cur[1 + r] = first entry of row r on entry (the exclusive scan of the copies per row) and, every copy placed,
 // the first entry of row r + 1: the cursor of a row IS the next row's offset, so cur[0 .. N] (cur[0] = 0) ends as the
@@ -32,8 +33,9 @@ __global__ __launch_bounds__(256) void row_pos_fill_kernel(const int64_t *__rest
 // again from the 16 bytes.  Every slot, not the first that holds t: a probe list can name a list twice.  A chunk
 // belongs to one slot of one query, so no two threads touch the same one.  ex_a: the excluded rows of rows
 // [0, n_a) of the batch, ex_b: of the rows behind them (a pair of calls); NULL or an entry outside [0, N): nothing
-// excluded.  only (or NULL): [count, q_0, q_1, ...] — just these queries, as allow_pass_kernel.  The probed lists'
-// distance bytes are signed (list_replay_job), so the empty value is 127; there is no unsigned form.
+// excluded (tk_pass_entry, chunk_mask.h).  only (or NULL): [count, q_0, q_1, ...] — just these queries
+// (tk_pass_query).  The probed lists' distance bytes are signed (list_replay_job), so the empty value is 127; there is
+// no unsigned form.
 __global__ __launch_bounds__(256) void exclude_pass_kernel(uint4 *__restrict__ dist, int64_t cap,
                                                            uint8_t *__restrict__ mins, int64_t cap_min, int64_t nq,
                                                            const int *__restrict__ slot_prefix,
@@ -49,16 +51,8 @@ __global__ __launch_bounds__(256) void exclude_pass_kernel(uint4 *__restrict__ d
     const int64_t qi = i / S;
     const int s = (int)(i - qi * S);
     if (qi >= nq) return;
-    int64_t q = qi;
-    if (only) {
-        if (qi >= only[0]) return;
-        q = only[1 + qi];
-    }
-    const int64_t row = q0 + q;
-    const int64_t *ex = row < n_a ? ex_a : ex_b;
-    if (!ex) return;
-    const int64_t e = ex[row < n_a ? row : row - n_a];
-    if (e < 0 || e >= N) return;
+    int64_t q, e;
+    if (!tk_pass_query(qi, only, q) || !tk_pass_entry(ex_a, ex_b, n_a, q0 + q, e) || e < 0 || e >= N) return;
     const int n = slot_n[q * S + s];
     const int64_t off = slot_label_off[q * S + s];
     const int c0 = slot_prefix[q * (S + 1) + s];
@@ -107,13 +101,11 @@ void tk_launch_exclude_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap
 // (row_copies_kernel), exclusive scan, fill.  Synchronises the device (once per layout).
 int row_pos_ensure(tk_index *ix)
 {
-    if (ix->row_pos_ok && ix->row_pos_gen == ix->lists_gen) return TK_OK;
-    ARGCHECK(ix->have_lists && ix->have_data, "index has no lists / data yet");
-    ARGCHECK(!ix->capturing, "the row-position table cannot be made inside a stream capture: make one excluding "
-                             "call before the capture");
+    if (ix->row_pos_state.current(ix->lists_gen)) return TK_OK;
+    TRY(table_may_build(ix, "row-position", "excluding"));
     ARGCHECK(ix->total_ids < 0x7fffffffll && ix->N < 0x7ffffff0ll, "row-position table: more than 2^31 stored rows");
     const int64_t N = ix->N, T = ix->total_ids;
-    ix->row_pos_ok = false;
+    ix->row_pos_state.ok = false;
     DevBuf summary, tmp;
     auto run = [&]() -> int {
         const int init[4] = {-1, 0, 0x7fffffff, 0};
@@ -140,9 +132,7 @@ int row_pos_ensure(tk_index *ix)
     summary.release();
     tmp.release();
     if (r != TK_OK) return r;
-    ix->row_pos_ok = true;
-    ix->row_pos_gen = ix->lists_gen;
-    ix->row_pos_builds++;
+    ix->row_pos_state.made(ix->lists_gen);
     return TK_OK;
 }
 
@@ -152,10 +142,10 @@ extern "C" int tk_index_row_table(tk_index *ix, int64_t *info4)
 {
     IXLOCK(ix);
     ARGCHECK(ix && info4, "null index / buffer");
-    const bool have = ix->row_pos_ok && ix->row_pos_gen == ix->lists_gen;
+    const bool have = ix->row_pos_state.current(ix->lists_gen);
     info4[0] = have ? 1 : 0;
     info4[1] = have ? (ix->N + 2) * 4 + (ix->total_ids > 0 ? ix->total_ids : 1) * 4 : 0;
-    info4[2] = ix->row_pos_builds;
+    info4[2] = ix->row_pos_state.builds;
     info4[3] = have ? ix->total_ids : 0;
     return TK_OK;
 }

@@ -19,7 +19,7 @@
 #include "api_internal.h"
 #include "chunk_mask.h"
 
-// One workgroup per list, threads striding over the list's rows padded to whole chunks (group_table_kernel's geometry).
+// One workgroup per list (tk_row_table, chunk_mask.h).
 __global__ __launch_bounds__(256) void tag_table_kernel(const int64_t *__restrict__ list_chunk_off,
                                                         const int64_t *__restrict__ list_n,
                                                         const int64_t *__restrict__ ids_off,
@@ -27,26 +27,13 @@ __global__ __launch_bounds__(256) void tag_table_kernel(const int64_t *__restric
                                                         const uint64_t *__restrict__ row_tags, int64_t N,
                                                         uint64_t *__restrict__ table)
 {
-    const int64_t l = blockIdx.x;
-    const int64_t c0 = list_chunk_off[l];
-    const int64_t rows = (list_chunk_off[l + 1] - c0) * 16;     // padded to whole chunks
-    const int64_t n = list_n[l];
-    const int64_t io = ids_off[l];
-    for (int64_t r = threadIdx.x; r < rows; r += blockDim.x) {
-        uint64_t t = 0;
-        if (r < n) {
-            const int64_t lab = ids[io + r];
-            if (lab >= 0 && lab < N) t = row_tags[lab];
-        }
-        table[c0 * 16 + r] = t;
-    }
+    tk_row_table<uint64_t>(list_chunk_off, list_n, ids_off, ids, row_tags, N, 0, table);
 }
 
-// group_pass_kernel's geometry: one workgroup per query, the slot prefix in LDS, a binary search to the slot,
-// slot_chunk0 to the global chunk.  The 16-bit keep mask is made from the chunk's 16 tag masks (eight 16-byte loads)
-// with 64-bit compares, ALL: (t & m) == m, else (t & m) != 0.  m_a: the masks of rows [0, n_a) of the batch, m_b: of
-// the rows behind them (a pair of calls, both of one mode); NULL, or an entry of 0: the query is unrestricted and its
-// workgroup returns before it touches anything.  q0, only: as group_pass_kernel.
+// One workgroup per query over the query's probed chunks (tk_mask_probed, chunk_mask.h), a chunk's keep mask made from
+// its 16 tag masks (eight 16-byte loads) with 64-bit compares, ALL: (t & m) == m, else (t & m) != 0.  m_a: the masks of
+// rows [0, n_a) of the batch, m_b: of the rows behind them (a pair of calls, both of one mode); NULL, or an entry of 0:
+// the query is unrestricted and its workgroup returns before it touches anything.  q0, only: as group_pass_kernel.
 template <bool SIGNED, bool ALL>
 __global__ __launch_bounds__(256) void tag_pass_kernel(uint4 *__restrict__ dist, int64_t cap,
                                                        uint8_t *__restrict__ mins, int64_t cap_min,
@@ -57,27 +44,11 @@ __global__ __launch_bounds__(256) void tag_pass_kernel(uint4 *__restrict__ dist,
                                                        const uint64_t *__restrict__ m_b, int64_t n_a, int64_t q0,
                                                        const int *__restrict__ only)
 {
-    extern __shared__ int pre[];        // S + 1
-    int64_t q = blockIdx.x;
-    if (only) {
-        if ((int)blockIdx.x >= only[0]) return;
-        q = only[1 + blockIdx.x];
-    }
-    const int64_t row = q0 + q;
-    const uint64_t *ma = row < n_a ? m_a : m_b;
-    if (!ma) return;
-    const uint64_t m = ma[row < n_a ? row : row - n_a];
-    if (m == 0) return;
-    for (int s = threadIdx.x; s <= S; s += blockDim.x) pre[s] = slot_prefix[q * (S + 1) + s];
-    __syncthreads();
-    const int total = pre[S];
-    for (int f = threadIdx.x; f < total; f += blockDim.x) {
-        int lo = 0, hi = S;     // largest lo with pre[lo] <= f (pre is non-decreasing, pre[0] = 0)
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (pre[mid] <= f) lo = mid; else hi = mid;
-        }
-        const ulonglong2 *t = table + (slot_chunk0[q * S + lo] + (f - pre[lo])) * 8;
+    int64_t q;
+    uint64_t m;
+    if (!tk_pass_query(blockIdx.x, only, q) || !tk_pass_entry(m_a, m_b, n_a, q0 + q, m) || m == 0) return;
+    tk_mask_probed<SIGNED>(dist, cap, mins, cap_min, slot_prefix, slot_chunk0, S, q, [=](int64_t c) -> uint32_t {
+        const ulonglong2 *t = table + c * 8;
         uint32_t b = 0;
 #pragma unroll
         for (int j = 0; j < 8; j++) {
@@ -86,8 +57,8 @@ __global__ __launch_bounds__(256) void tag_pass_kernel(uint4 *__restrict__ dist,
             const uint32_t px = ALL ? x == m : x != 0, py = ALL ? y == m : y != 0;
             b |= (px | (py << 1)) << (2 * j);
         }
-        tk_mask_chunk<SIGNED>(dist + q * cap + f, mins + q * cap_min + f, b);
-    }
+        return b;
+    });
 }
 
 void tk_launch_tag_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
@@ -98,43 +69,21 @@ void tk_launch_tag_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min
     if (nq <= 0 || (!m_a && !m_b.b)) return;
     const int64_t n_a = m_b.n_a > 0 ? m_b.n_a : INT64_MAX;     // (no second call: every row is m_a's)
     const size_t lds = (size_t)(S + 1) * 4;
-#define TK_TAG_PASS(SG, AL)                                                                                          \
-    hipLaunchKernelGGL((tag_pass_kernel<SG, AL>), dim3((unsigned)nq), dim3(256), lds, s, dist, cap, mins, cap_min,  \
-                       slot_prefix, slot_chunk0, S, (const ulonglong2 *)table, m_a, (const uint64_t *)m_b.b, n_a,   \
-                       q0, only)
-    if (signd) {
-        if (all) TK_TAG_PASS(true, true); else TK_TAG_PASS(true, false);
-    } else {
-        if (all) TK_TAG_PASS(false, true); else TK_TAG_PASS(false, false);
-    }
-#undef TK_TAG_PASS
+    const auto kernel = signd ? (all ? tag_pass_kernel<true, true> : tag_pass_kernel<true, false>)
+                              : (all ? tag_pass_kernel<false, true> : tag_pass_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nq), dim3(256), lds, s, dist, cap, mins, cap_min, slot_prefix, slot_chunk0,
+                       S, (const ulonglong2 *)table, m_a, (const uint64_t *)m_b.b, n_a, q0, only);
 }
 
-// What a call that names a tag array needs: tags for every row the index has now, and the table for the index's
-// current lists — made on the first such call, and again after the lists changed.  Synchronises the device (once per
-// layout).
+// What a call that names a tag array needs (row_table_ensure): tags for every row, the table of the current lists
 int tag_table_ensure(tk_index *ix)
 {
-    if (ix->tags_n == 0) return fail(TK_ERR_STATE, "a tag array was passed but the index has no tags: tk_index_set_tags first");
-    if (ix->tags_n != ix->N)
-        return fail(TK_ERR_STATE, "the tags cover " + std::to_string(ix->tags_n) + " rows, the index has " +
-                                      std::to_string(ix->N) + " now: set them again (tk_index_set_tags)");
-    if (ix->tag_table_ok && ix->tag_table_gen == ix->lists_gen) return TK_OK;
-    ARGCHECK(ix->have_lists && ix->have_data, "index has no lists / data yet");
-    ARGCHECK(!ix->capturing, "the tag table cannot be made inside a stream capture: make one tagged call before "
-                             "the capture");
-    ix->tag_table_ok = false;
-    TRY(ix->tag_table.ensure((size_t)(ix->total_chunks > 0 ? ix->total_chunks : 1) * 128));
-    if (ix->n_lists > 0)
+    return row_table_ensure(ix, ix->tags, [](const tk_index *ix) {
         hipLaunchKernelGGL(tag_table_kernel, dim3((unsigned)ix->n_lists), dim3(256), 0, 0,
                            ix->list_chunk_off.as<int64_t>(), ix->list_n.as<int64_t>(), ix->ids_off.as<int64_t>(),
-                           ix->ids.as<int64_t>(), ix->row_tags.as<uint64_t>(), ix->N, ix->tag_table.as<uint64_t>());
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipDeviceSynchronize());
-    ix->tag_table_ok = true;
-    ix->tag_table_gen = ix->lists_gen;
-    ix->tag_table_builds++;
-    return TK_OK;
+                           ix->ids.as<int64_t>(), ix->tags.by_row.as<uint64_t>(), ix->N,
+                           ix->tags.table.as<uint64_t>());
+    });
 }
 
 // ---- C ABI ----
@@ -143,39 +92,19 @@ extern "C" int tk_index_set_tags(tk_index *ix, const uint64_t *tags, int64_t n)
 {
     IXLOCK(ix);
     ARGCHECK(ix, "null index");
-    ARGCHECK(n >= 0 && (n == 0 || tags), "tags: n masks, or NULL and 0");
-    ARGCHECK(!ix->sharded, "list-sharded index: row tags are not supported");
-    if (n > 0) ARGCHECK(ix->have_data && n == ix->N, "tags: one mask per row of the index (n == N)");
-    TRY(flush_pending(ix));                 // calls still owed that read the old tags are enqueued ...
-    HIPCHECK(hipDeviceSynchronize());       // ... and have run
-    ix->tag_table_ok = false;
-    ix->tags_n = 0;
-    if (n == 0) {
-        ix->row_tags.release();
-        ix->tag_table.release();
-        return TK_OK;
-    }
-    TRY(ix->row_tags.ensure((size_t)n * 8));
-    HIPCHECK(hipMemcpy(ix->row_tags.p, tags, (size_t)n * 8, hipMemcpyHostToDevice));
-    ix->tags_n = n;
-    return TK_OK;
+    return row_table_set(ix, ix->tags, tags, n);
 }
 
 extern "C" int64_t tk_index_tags(tk_index *ix)
 {
     IXLOCK(ix);
     if (!ix) return fail(TK_ERR_ARG, "bad argument: null index");
-    return ix->tags_n;
+    return ix->tags.n;
 }
 
 extern "C" int tk_index_tag_table(tk_index *ix, int64_t *info4)
 {
     IXLOCK(ix);
     ARGCHECK(ix && info4, "null index / buffer");
-    const bool have = ix->tag_table_ok && ix->tag_table_gen == ix->lists_gen;
-    info4[0] = have ? 1 : 0;
-    info4[1] = have ? (ix->total_chunks > 0 ? ix->total_chunks : 1) * 128 : 0;
-    info4[2] = ix->tag_table_builds;
-    info4[3] = ix->tags_n * 8;
-    return TK_OK;
+    return row_table_info(ix, ix->tags, info4);
 }
