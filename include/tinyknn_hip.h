@@ -779,6 +779,56 @@ int tk_index_query_batch_dev_ex4(tk_index *ix, const tk_allow *allow, const int6
                                  const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
                                  int64_t *out_ids_dev, void *out_dist_dev, void *done_event, void *stream);
 int tk_index_tag_table(tk_index *ix, int64_t *info4);
+/* Every query of a batch restricted to the rows whose values lie in its ranges ("newer than t", "price between a and
+ * b").  Rows carry `cols` numeric columns, 1 <= cols <= 4, as int64 KEYS; a query carries one inclusive interval
+ * [lo_c, hi_c] of keys per column, and a row passes iff lo_c <= key[row, c] <= hi_c for every column c.  The library
+ * compares int64 only: a caller maps its values and bounds to keys with a strictly monotone function (integers: the
+ * value itself; floats, widened to float64, -0.0 folded into +0.0, no NaN: the bits b where b >= 0, else
+ * b ^ 0x7FFFFFFFFFFFFFFF — tinyknn_amd.ivf.value_keys).  An unbounded end is INT64_MIN (lo) / INT64_MAX (hi): the
+ * comparison is simply true.  A query with a bounded column returns what IVF.query (ivf.py:106-163) returns when
+ * `insert` in query_pq runs only for labels that pass — that allowed set, for that query alone, with everything else
+ * the reference's as for allowed sets above; bit for bit that guarded reference.  Every bound unbounded: the query is
+ * unrestricted.  lo > hi, or no row passes: the query returns no id (a row of -1).  With an allowed set, an exclude
+ * array, a group array and / or a tag array as well, `insert` runs only for labels that pass all of them.
+ * tk_index_set_values: keys column-major, (cols, n) with n == N, on the host, uploaded once and kept until they are
+ * replaced, cleared (NULL, 0, 0) or the index is destroyed; completes the batches in flight first.  cols outside
+ * 1..4: TK_ERR_ARG.
+ * tk_index_values: the number of rows the values cover, 0 for none.  tk_index_value_columns: their columns, 0 for none.
+ * On the device the probed rows that do not pass take the heap's empty value in the query's distance row, behind the
+ * tag pass (behind the list scans and every exact re-scan, in front of every replay; never on the coarse stage).
+ * Their keys are read from a table in list-position order, column-major: 128 bytes per stored chunk of 16 rows and
+ * column beside the 8 cols N bytes by row id (0.8 GB each per column at 100M rows stored once, plus the allocator's
+ * eighth of slack; padding rows hold INT64_MIN), made from the device-resident labels by the first call that passes a
+ * range array, once per layout of the lists (again after tk_index_set_lists, _add_rows, _remove_rows, _update_rows and
+ * after tk_index_set_values; that call synchronises the device, so make it outside a stream capture), freed with the
+ * index.  The pass reads only the columns a query bounds.  Calls without an array never make the table and launch
+ * nothing more than before.
+ * tk_index_query_batch_ex5 / _dev_ex5: _ex4 with one more pointer, between / between_dev (int64, nq x cols x 2 keys:
+ * query-major, then column, then lo, hi), which may be NULL.  The host call passes an array of only unbounded entries
+ * on as none (that call takes the unrestricted path).  The device call does not read between_dev on the host: a query
+ * whose entries are all unbounded there is unrestricted.  between_dev belongs to the library until done_event or
+ * tk_index_join, like the other buffers.  _ex4 is this call without a range array.
+ * Refused, nothing run: a range array while no values are set, or while they cover fewer rows than the index has
+ * (after tk_index_add_rows: TK_ERR_STATE, set them again); a list-sharded index (TK_ERR_ARG).
+ * Sub-batches and the pipelined mode as the _ex4 calls.  A call with a range array is a restricted call: in the
+ * automatic plain-scan mode it takes the exact scan and leaves the automatic state alone; two calls pair
+ * (tk_index_set_coalesce) only where both pass a range array or neither passes one.
+ * tk_index_value_table: info4 = {table exists for the current lists, its bytes, times one was made, the bytes of the
+ * keys by row id}. */
+int tk_index_set_values(tk_index *ix, const int64_t *keys, int64_t n, int cols);
+int64_t tk_index_values(tk_index *ix);
+int tk_index_value_columns(tk_index *ix);
+int tk_index_query_batch_ex5(tk_index *ix, const tk_allow *allow, const int64_t *exclude, const int32_t *group,
+                             const uint64_t *tags, int tag_mode, const int64_t *between, const float *q,
+                             const void *q_pq, int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                             int64_t *out_ids, void *out_dist, int64_t *out_probes, int64_t *out_heap_idx,
+                             int32_t *out_heap_val);
+int tk_index_query_batch_dev_ex5(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
+                                 const int32_t *group_dev, const uint64_t *tags_dev, int tag_mode,
+                                 const int64_t *between_dev, const float *q_dev, const void *q_pq_dev, int q_pq_is_f64,
+                                 int64_t nq, int k, int n_probes, int pass_1, int64_t *out_ids_dev, void *out_dist_dev,
+                                 void *done_event, void *stream);
+int tk_index_value_table(tk_index *ix, int64_t *info4);
 /* hipStream_t on which to copy a batch's inputs in (pipelined mode: the index's front stream,
  * where the batch's first kernel runs; NULL: use the stream the batch is enqueued on) */
 void *tk_index_input_stream(tk_index *ix);

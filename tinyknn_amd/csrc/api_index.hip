@@ -89,7 +89,8 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->local_chunk_off, &ix->rot_t, &ix->br_ynorm, &ix->br_vals, &ix->br_tau,
                       &ix->br_cand, &ix->br_count, &ix->br_out, &ix->br_q, &ix->br_sample, &ix->replay_counters,
                       &ix->twin_list, &ix->twin_off, &ix->row_pos_off, &ix->row_pos, &ix->groups.by_row,
-                      &ix->groups.table, &ix->tags.by_row, &ix->tags.table};
+                      &ix->groups.table, &ix->tags.by_row, &ix->tags.table, &ix->values.by_row,
+                      &ix->values.table};
     for (DevBuf *b : bufs) b->release();
     for (Work &w : ix->works) w.release();
     // (the internal streams belong to the process: shared_streams below)
@@ -1013,7 +1014,7 @@ static void plain_verdict_event(tk_index *ix, Work &w, int64_t nq, hipStream_t s
 // What the batch is restricted by, applied to the probed chunks of queries [q0, q0 + nq) — all of them, or (`only`)
 // those of the flag list: behind the list scans and every re-scan, in front of every replay that reads dist / mins.
 // One launch per kind that is set, in this order: the allowed set (allow.hip), the excluded rows (rows.hip), the groups
-// (groups.hip), the tags (tags.hip).  The per-query arrays are the batch's from row 0 (the passes add q0); a pair's
+// (groups.hip), the tags (tags.hip), the ranges (between.hip).  The per-query arrays are the batch's from row 0 (the passes add q0); a pair's
 // second call that names no array masks nothing.
 static void apply_restrictions(const tk_index *ix, Work &w, int64_t q0, int64_t nq, const Plan &p, const TkRestrict &r,
                                hipStream_t st, const int *only = nullptr)
@@ -1038,6 +1039,9 @@ static void apply_restrictions(const tk_index *ix, Work &w, int64_t q0, int64_t 
     if (r.tagged())
         tk_launch_tag_pass(dist, p.cap, mins, p.cap_min, nq, prefix, chunk0, p.S, ix->tags.table.as<uint64_t>(), r.tags,
                            r.tags2, r.tag_mode, q0, 1, only, st);
+    if (r.ranged())
+        tk_launch_between_pass(dist, p.cap, mins, p.cap_min, nq, prefix, chunk0, p.S, ix->values.table.as<int64_t>(),
+                               value_plane(ix), value_columns(ix), r.between, r.between2, q0, 1, only, st);
 }
 
 // The queries the replay flagged (bound above the table's limit at the first plain block, plain_scan.hip): every probed
@@ -1638,6 +1642,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     ARGCHECK(!ix->sharded, "list-sharded index: use tk_index_shard_scan_dev / _finish_dev");
     ARGCHECK(r.tag_mode == 0 || r.tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
     if (!r.tags) r.tag_mode = 0;
+    r.cols = r.between ? value_columns(ix) : 0;
     if (r.allow) {
         ARGCHECK(r.allow->ix == ix, "the allowed set belongs to another index");
         if (r.allow->lists_gen != ix->lists_gen)
@@ -1651,7 +1656,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
                         cs != hipStreamCaptureStatusNone;
         (void)hipGetLastError();
     }
-    TRY(r.ensure_tables(ix, nq));       // (the first excluding / grouped / tagged call of a layout)
+    TRY(r.ensure_tables(ix, nq));       // (the first excluding / grouped / tagged / ranged call of a layout)
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     const int64_t ms = sub_batch(p);
     ARGCHECK(!(out_ids_pinned || done_ev) || (nq >= 1 && nq <= ms),
@@ -1878,13 +1883,23 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
         for (int64_t i = 0; i < nq && !tagged; i++) tagged = r.tags[i] != 0;
     if (!tagged) r.tags = nullptr;
     if (r.tags) ARGCHECK(!ix->sharded, "list-sharded index: row tags are not supported");
+    // ranges: the same (an array of only unbounded entries restricts nothing); how long the array is, the values say
+    if (r.between) {
+        ARGCHECK(!ix->sharded, "list-sharded index: row values are not supported");
+        if (ix->values.n == 0 || ix->values.n != ix->N) return value_table_ensure(ix);      // (its TK_ERR_STATE)
+        r.cols = value_columns(ix);
+        bool ranged = false;
+        for (int64_t i = 0; i < nq * r.cols && !ranged; i++)
+            ranged = r.between[2 * i] != INT64_MIN || r.between[2 * i + 1] != INT64_MAX;
+        if (!ranged) r.between = nullptr;
+    }
     ARGCHECK(!(out_probes || out_heap_idx || out_heap_val) || nq <= sub_batch(p),
              "debug outputs need the batch to fit one sub-batch");
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     TRY(ix->q.ensure((size_t)nq * ix->d * 4));
     TRY(ix->qpq.ensure((size_t)nq * ix->dq * esz));
-    DevBuf outbuf, distbuf, exbuf, rowbuf, grbuf, tgbuf;  // separate from the sub-batch `out` workspace
-    BufRelease rel{{&outbuf, &distbuf, &exbuf, &rowbuf, &grbuf, &tgbuf}};
+    DevBuf outbuf, distbuf, exbuf, rowbuf, grbuf, tgbuf, bwbuf;  // separate from the sub-batch `out` workspace
+    BufRelease rel{{&outbuf, &distbuf, &exbuf, &rowbuf, &grbuf, &tgbuf, &bwbuf}};
     // a per-query host array (or NULL) as the device array the call below names
     const auto upload = [&](auto *&arr, DevBuf &buf) -> int {
         if (!arr) return TK_OK;
@@ -1899,6 +1914,12 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
     TRY(upload(r.exclude, exbuf));
     TRY(upload(r.group, grbuf));
     TRY(upload(r.tags, tgbuf));
+    if (r.between) {
+        const size_t bytes = (size_t)nq * r.cols * 16;
+        TRY(bwbuf.ensure(bytes));
+        HIPCHECK(hipMemcpy(bwbuf.p, r.between, bytes, hipMemcpyHostToDevice));
+        r.between = bwbuf.as<int64_t>();
+    }
     if (rows) {
         TRY(rowbuf.ensure((size_t)nq * 8));
         HIPCHECK(hipMemcpy(rowbuf.p, rows, (size_t)nq * 8, hipMemcpyHostToDevice));
@@ -2027,8 +2048,8 @@ extern "C" int tk_index_query_batch_ex4(tk_index *ix, const tk_allow *allow, con
                                         int64_t *out_ids, void *out_dist, int64_t *out_probes, int64_t *out_heap_idx,
                                         int32_t *out_heap_val)
 {
-    return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
-                            out_heap_val, {allow, exclude, group, tags, tag_mode}, out_dist);
+    return tk_index_query_batch_ex5(ix, allow, exclude, group, tags, tag_mode, nullptr, q, q_pq, q_pq_is_f64, nq, k,
+                                    n_probes, pass_1, out_ids, out_dist, out_probes, out_heap_idx, out_heap_val);
 }
 
 extern "C" int tk_index_query_batch_dev_ex4(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
@@ -2037,10 +2058,32 @@ extern "C" int tk_index_query_batch_dev_ex4(tk_index *ix, const tk_allow *allow,
                                             int k, int n_probes, int pass_1, int64_t *out_ids_dev, void *out_dist_dev,
                                             void *done_event, void *stream)
 {
+    return tk_index_query_batch_dev_ex5(ix, allow, exclude_dev, group_dev, tags_dev, tag_mode, nullptr, q_dev, q_pq_dev,
+                                        q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, out_dist_dev, done_event,
+                                        stream);
+}
+
+// ... and one interval per query and value column (between.hip, tinyknn_hip.h): _ex4 with one more pointer
+extern "C" int tk_index_query_batch_ex5(tk_index *ix, const tk_allow *allow, const int64_t *exclude,
+                                        const int32_t *group, const uint64_t *tags, int tag_mode,
+                                        const int64_t *between, const float *q, const void *q_pq, int q_pq_is_f64,
+                                        int64_t nq, int k, int n_probes, int pass_1, int64_t *out_ids, void *out_dist,
+                                        int64_t *out_probes, int64_t *out_heap_idx, int32_t *out_heap_val)
+{
+    return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
+                            out_heap_val, {allow, exclude, group, tags, tag_mode, between}, out_dist);
+}
+
+extern "C" int tk_index_query_batch_dev_ex5(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
+                                            const int32_t *group_dev, const uint64_t *tags_dev, int tag_mode,
+                                            const int64_t *between_dev, const float *q_dev, const void *q_pq_dev,
+                                            int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                                            int64_t *out_ids_dev, void *out_dist_dev, void *done_event, void *stream)
+{
     IXLOCK(ix);
     return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
-                                (hipEvent_t)done_event, stream, {allow, exclude_dev, group_dev, tags_dev, tag_mode},
-                                out_dist_dev);
+                                (hipEvent_t)done_event, stream,
+                                {allow, exclude_dev, group_dev, tags_dev, tag_mode, between_dev}, out_dist_dev);
 }
 
 // the stored rows `rows` as queries, each leaving itself out where exclude_self

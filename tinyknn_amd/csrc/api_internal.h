@@ -175,7 +175,8 @@ struct TkTableState {
 
 // One value per row that queries are restricted by (row_table.hip): by row id as the caller set them (n of them, 0:
 // none), and in list-position order, 16 per stored chunk — made by the first call that names an array of the kind.
-// noun / called / unit: what the kind's error texts name ("group" / "grouped" / "id").
+// noun / called / unit: what the kind's error texts name ("group" / "grouped" / "id").  esz: bytes per row — fixed by the
+// kind, or (values: 8 per column, column-major) by row_table_set.
 struct TkRowTable {
     size_t esz;
     const char *noun, *called, *unit;
@@ -226,6 +227,8 @@ struct tk_index {
     // tk_index_set_tags uploaded them, and in list-position order — made by the first call that names a group / tag
     // array, for ONE layout, as the table above
     TkRowTable groups{4, "group", "grouped", "id"}, tags{8, "tag", "tagged", "mask"};
+    // 1 to 4 int64 keys per row (between.hip), column-major in both orders: esz = 8 x columns, set by tk_index_set_values
+    TkRowTable values{8, "value", "valued", "key"};
     // members per (list, column of nearest): list l holds its column-0 members first, then column 1's, ...
     // (group_data_by_indices); known after tk_index_build_dev / tk_index_add_rows (list_kp = columns), not
     // after a host upload (list_kp = 0: tk_index_add_rows takes them from the caller)
@@ -293,6 +296,10 @@ struct tk_index {
     int64_t last_replay[4] = {-1, 0, 0, 0};    // tk_index_last_replay: form, lazy, label24 entries, twin width (stage_back)
 };
 
+// the value columns an index has (0: none), and the int64 keys of one column's plane of the value table (between.hip)
+static inline int value_columns(const tk_index *ix) { return ix->values.n > 0 ? (int)(ix->values.esz / 8) : 0; }
+static inline int64_t value_plane(const tk_index *ix) { return (ix->total_chunks > 0 ? ix->total_chunks : 1) * 16; }
+
 // an allowed set (allow.hip): 16 bits per stored chunk in list-position order, for ONE layout of the lists
 struct tk_allow {
     tk_index *ix = nullptr;
@@ -351,26 +358,31 @@ const tk_allow *allow_effective(const tk_allow *a);
 
 // What ONE call restricts its answers by, any of it absent: an allowed set (allow.hip), and per query (device arrays,
 // or NULL) a row the query may not return (rows.hip), a group it is restricted to (groups.hip), a tag mask it is
-// restricted by (tags.hip) in the call's tag_mode (0: a row passes with any of the mask's tags, 1: with all of them).
+// restricted by (tags.hip) in the call's tag_mode (0: a row passes with any of the mask's tags, 1: with all of them),
+// its ranges (between.hip): 2 x cols int64 keys per query, (lo, hi) per column; cols: the index's when the call came.
 struct TkCallRestrict {
     const tk_allow *allow = nullptr;
     const int64_t *exclude = nullptr;
     const int32_t *group = nullptr;
     const uint64_t *tags = nullptr;
     int tag_mode = 0;
+    const int64_t *between = nullptr;
+    int cols = 0;
     // the call's rows from row o on
     TkCallRestrict at(int64_t o) const
     {
-        return {allow, exclude ? exclude + o : nullptr, group ? group + o : nullptr, tags ? tags + o : nullptr, tag_mode};
+        return {allow, exclude ? exclude + o : nullptr, group ? group + o : nullptr, tags ? tags + o : nullptr, tag_mode,
+                between ? between + o * 2 * cols : nullptr, cols};
     }
     // Join rule: two calls run as one batch (coalesce_call) with the same allowed set, both grouped or neither (the
-    // two kinds take different scans: exact_scan), both tagged in one mode or neither (one mode per launch).
+    // two kinds take different scans: exact_scan), both tagged in one mode or neither (one mode per launch), both ranged or neither.
     bool joins(const TkCallRestrict &o) const
     {
-        return allow == o.allow && !group == !o.group && !tags == !o.tags && (!tags || tag_mode == o.tag_mode);
+        return allow == o.allow && !group == !o.group && !tags == !o.tags && (!tags || tag_mode == o.tag_mode) &&
+               !between == !o.between;
     }
     // Table rule: what the passes read exists before the call's first launch (each made once per layout of the lists,
-    // synchronising the device; TK_ERR_STATE where the index has no groups / tags for every row).  Defined below.
+    // synchronising the device; TK_ERR_STATE where the index has no groups / tags / values for every row).  Defined below.
     int ensure_tables(tk_index *ix, int64_t nq) const;
 };
 
@@ -382,22 +394,25 @@ struct TkRestrict {
     const int64_t *exclude = nullptr;
     const int32_t *group = nullptr;
     const uint64_t *tags = nullptr;
-    TkSecond exclude2, group2, tags2;
+    const int64_t *between = nullptr;
+    TkSecond exclude2, group2, tags2, between2;
     TkRestrict() = default;
     // a: the first call; b (or NULL: one call): the second, whose rows start at batch row n_a
     TkRestrict(const TkCallRestrict &a, const TkCallRestrict *b = nullptr, int64_t n_a = 0)
-        : allow(a.allow), tag_mode(a.tag_mode), exclude(a.exclude), group(a.group), tags(a.tags)
+        : allow(a.allow), tag_mode(a.tag_mode), exclude(a.exclude), group(a.group), tags(a.tags),
+          between(a.between)
     {
-        if (b) exclude2 = {b->exclude, n_a}, group2 = {b->group, n_a}, tags2 = {b->tags, n_a};
+        if (b) exclude2 = {b->exclude, n_a}, group2 = {b->group, n_a}, tags2 = {b->tags, n_a}, between2 = {b->between, n_a};
     }
     bool excludes() const { return exclude || exclude2.b; }
     bool grouped() const { return group || group2.b; }
     bool tagged() const { return tags || tags2.b; }
+    bool ranged() const { return between || between2.b; }
     // Anything set: the batch launches at least one restricting pass
-    bool any() const { return allow || excludes() || grouped() || tagged(); }
-    // Exact-scan rule: a batch with an allowed set, a group array or a tag array takes the exact scan in the automatic
+    bool any() const { return allow || excludes() || grouped() || tagged() || ranged(); }
+    // Exact-scan rule: a batch with an allowed set, a group, tag or range array takes the exact scan in the automatic
     // plain-scan mode (plain_for); an excluded row masks a byte or two and does not.
-    bool exact_scan() const { return allow || grouped() || tagged(); }
+    bool exact_scan() const { return allow || grouped() || tagged() || ranged(); }
 };
 struct Plan {
     int kc, rescore, R, S;
@@ -491,19 +506,21 @@ int table_may_build(const tk_index *ix, const char *table, const char *call);
 // rows.hip: the row-position table of the index's current lists exists (made now if not: synchronises the device)
 int row_pos_ensure(tk_index *ix);
 // row_table.hip — set: calls still owed run first, then the values are uploaded (n == N of them; `check`, if any, has
-// the last word on them) or (n == 0) dropped.  ensure: values for every row the index has (else TK_ERR_STATE) and the
+// the last word on them; esz, if not 0, is the kind's bytes per row from now on) or (n == 0) dropped.  ensure: values for every row the index has (else TK_ERR_STATE) and the
 // table of its current lists, made now if not by `launch` (synchronises the device).  info: tk_index_*_table's info4.
 int row_table_set(tk_index *ix, TkRowTable &t, const void *vals, int64_t n,
-                  int (*check)(const void *vals, int64_t n) = nullptr);
+                  int (*check)(const void *vals, int64_t n) = nullptr, size_t esz = 0);
 int row_table_ensure(tk_index *ix, TkRowTable &t, void (*launch)(const tk_index *ix));
 int row_table_info(const tk_index *ix, const TkRowTable &t, int64_t *info4);
 int group_table_ensure(tk_index *ix);       // groups.hip
 int tag_table_ensure(tk_index *ix);         // tags.hip
+int value_table_ensure(tk_index *ix);       // between.hip
 inline int TkCallRestrict::ensure_tables(tk_index *ix, int64_t nq) const
 {
     if (exclude && nq > 0) TRY(row_pos_ensure(ix));
     if (group && nq > 0) TRY(group_table_ensure(ix));
     if (tags && nq > 0) TRY(tag_table_ensure(ix));
+    if (between && nq > 0) TRY(value_table_ensure(ix));
     return TK_OK;
 }
 int head_chunks(const tk_index *ix, const Plan &p);    // chunks of a first probed list the exact kernel keeps (head mode)

@@ -1,5 +1,6 @@
 // chunk_mask.h — the device bodies the restricting passes share (allow.hip: one set per call; rows.hip: one excluded
-// row per query; groups.hip: one group per query; tags.hip: one tag mask per query).  Device code only.
+// row per query; groups.hip: one group per query; tags.hip: one tag mask per query; between.hip: one interval per query
+// and value column).  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -47,7 +47,7 @@ void tk_launch_scan_probes(const uint4 *codes, int M, const uint4 *tables, int64
                            int max_flat_chunks, uint4 *dist, int64_t cap, uint8_t *mins,
                            int64_t min_stride, int signd, int order, hipStream_t s,
                            const int *only = nullptr);
-// The restricting passes (allow.hip here; rows.hip, groups.hip, tags.hip below; device bodies in chunk_mask.h) run over
+// The restricting passes (allow.hip here; rows.hip, groups.hip, tags.hip, between.hip below; device bodies in chunk_mask.h) run over
 // the probed chunks of a batch: the bytes of dist whose rows a query may not return take the empty value (127 signed,
 // 255 unsigned), touched chunks' minima are recomputed.  They share dist / mins rows, the slot arrays, signd, and
 // only: NULL (all nq queries) or [count, q_0, ...] (nq = its capacity).  A per-query array comes as x_a / x_b: the
@@ -514,6 +514,13 @@ void tk_launch_tag_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min
                         const int *slot_prefix, const int64_t *slot_chunk0, int S, const uint64_t *table,
                         const uint64_t *m_a, TkSecond m_b, int all, int64_t q0, int signd, const int *only,
                         hipStream_t s);
+// between.hip: 2 x cols int64 keys per query, (lo, hi) per column — the probed rows with a key outside one of them are
+// masked.  table: cols planes of plane_keys int64 in list-position order; b_a / b_b: the bounds of the batch's rows
+// (the second call's behind n_a, or empty), INT64_MIN / INT64_MAX = unbounded
+void tk_launch_between_pass(uint4 *dist, int64_t cap, uint8_t *mins, int64_t cap_min, int64_t nq,
+                            const int *slot_prefix, const int64_t *slot_chunk0, int S, const int64_t *table,
+                            int64_t plane_keys, int cols, const int64_t *b_a, TkSecond b_b, int64_t q0, int signd,
+                            const int *only, hipStream_t s);
 // half storage of float32 rows (n, d) on the device: *first_bad (preset to ~0) = the first row with a value whose
 // half is not finite (|x| >= 65520, inf, NaN); `out` = the rows as halfs, round-to-nearest-even, subnormals kept
 void tk_launch_check_half(const float *X, int64_t n, int d, unsigned long long *first_bad, hipStream_t s);

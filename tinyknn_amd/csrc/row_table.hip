@@ -1,5 +1,5 @@
 // row_table.hip — the host side that the per-row tables share (TkRowTable, api_internal.h: the groups of groups.hip, the
-// tags of tags.hip; their kernels stay in those files).  The error texts name the kind by the nouns it carries.
+// tags of tags.hip, the values of between.hip; their kernels stay in those files).  The error texts name the kind by the nouns it carries.
 #include "api_internal.h"
 
 int table_may_build(const tk_index *ix, const char *table, const char *call)
@@ -10,7 +10,8 @@ int table_may_build(const tk_index *ix, const char *table, const char *call)
     return TK_OK;
 }
 
-int row_table_set(tk_index *ix, TkRowTable &t, const void *vals, int64_t n, int (*check)(const void *vals, int64_t n))
+int row_table_set(tk_index *ix, TkRowTable &t, const void *vals, int64_t n, int (*check)(const void *vals, int64_t n),
+                  size_t esz)
 {
     const std::string nouns = std::string(t.noun) + "s", unit = t.unit;
     ARGCHECK(n >= 0 && (n == 0 || vals), nouns + ": n " + unit + "s, or NULL and 0");
@@ -28,6 +29,7 @@ int row_table_set(tk_index *ix, TkRowTable &t, const void *vals, int64_t n, int 
         t.table.release();
         return TK_OK;
     }
+    if (esz) t.esz = esz;                   // (a kind whose element size is fixed when it is set: between.hip)
     TRY(t.by_row.ensure((size_t)n * t.esz));
     HIPCHECK(hipMemcpy(t.by_row.p, vals, (size_t)n * t.esz, hipMemcpyHostToDevice));
     t.n = n;

@@ -289,6 +289,127 @@ def query_tags(tags, nq):
     return u
 
 
+INT64_MIN, INT64_MAX = -2**63, 2**63 - 1
+
+
+def value_kind(dtype):
+    """"i" / "f": the kind of value column a dtype makes (TypeError for anything but integers and floats)"""
+    dtype = np.dtype(dtype)
+    if dtype.kind in "iu":
+        return "i"
+    if dtype.kind == "f" and dtype.itemsize <= 8:
+        return "f"
+    raise TypeError(f"values: an integer or floating dtype (float16 / 32 / 64), got {dtype}")
+
+
+def _float_keys(x):
+    """float64 array -> int64 keys, strictly monotone over the finite values and +-inf (the caller refused NaN):
+    -0.0 folded into +0.0, then the bits b where b >= 0, else b ^ 0x7FFFFFFFFFFFFFFF"""
+    b = (np.ascontiguousarray(x, dtype=np.float64) + 0.0).view(np.int64)
+    return np.where(b >= 0, b, b ^ np.int64(INT64_MAX))
+
+
+def value_keys(values, n, what):
+    """The int64 keys the device compares for a `values` argument, in its shape: a (n,) or (n, C) array, 1 <= C <= 4,
+    of ONE integer or floating dtype (n None: any length).  Integers: the key is int64(v); uint64 values above
+    2**63 - 1 raise ValueError.  Floats (float16 / 32 / 64): widened exactly to float64, NaN raises ValueError, -0.0
+    is +0.0, then with b = the bits as int64 the key is b if b >= 0 else b ^ 0x7FFFFFFFFFFFFFFF — strictly monotone
+    over all finite values and +-inf.  TypeError for another kind of value or shape."""
+    a = np.asarray(values)
+    if a.dtype == np.bool_ or a.dtype.kind not in "iuf" or a.ndim not in (1, 2):
+        raise TypeError(f"{what}: a (n,) or (n, C) array of one integer or floating dtype")
+    kind = value_kind(a.dtype)
+    if a.ndim == 2 and not 1 <= a.shape[1] <= 4:
+        raise ValueError(f"{what}: 1 to 4 columns, got {a.shape[1]}")
+    if n is not None and a.shape[0] != n:
+        raise ValueError(f"{what}: one row of values per row ({n}), got {a.shape[0]}")
+    if kind == "i":
+        if a.dtype == np.uint64 and a.size and a.max() > INT64_MAX:
+            raise ValueError(f"{what}: uint64 values above 2**63 - 1 have no int64 key")
+        return np.ascontiguousarray(a, dtype=np.int64)
+    if np.isnan(a).any():
+        raise ValueError(f"{what}: NaN has no place in an order")
+    return _float_keys(a)
+
+
+def _bound_array(x, which, nq, cols):
+    """One end of `between=` as an (nq, cols) array of its own dtype, or None (unbounded).  The shape rule: a scalar
+    is for every query and column; 2-d is (nq, cols); 1-d of length nq is per query where cols == 1; 1-d of length
+    cols is per column, for every query, where cols > 1 — unless nq == cols, where it could be either: ValueError."""
+    if x is None:
+        return None
+    a = np.asarray(x)
+    if a.dtype == np.bool_ or a.dtype.kind not in "iuf":
+        raise TypeError(f"between: {which} must be None, a number or an array of numbers, got dtype {a.dtype}")
+    if a.ndim == 0:
+        return np.full((nq, cols), a[()], dtype=a.dtype)
+    if a.ndim == 2:
+        if a.shape != (nq, cols):
+            raise ValueError(f"between: {which} must have shape ({nq}, {cols}), got {a.shape}")
+        return a
+    if a.ndim != 1:
+        raise ValueError(f"between: {which} must be a scalar, 1-d or 2-d, got {a.ndim} dimensions")
+    if cols == 1:
+        if a.shape[0] != nq:
+            raise ValueError(f"between: {which}: one entry per query ({nq}), got {a.shape[0]}")
+        return a.reshape(nq, 1)
+    if a.shape[0] != cols:
+        raise ValueError(f"between: {which}: with {cols} columns pass ({nq}, {cols}) or one entry per column, "
+                         f"got {a.shape[0]}")
+    if nq == cols:
+        raise ValueError(f"between: {which}: {cols} entries for {nq} queries of {cols} columns could be per query or "
+                         f"per column: pass ({nq}, {cols})")
+    return np.broadcast_to(a, (nq, cols))
+
+
+def _bound_keys(a, kind, low):
+    """(keys, empty) of one end's (nq, cols) array on columns of `kind`: the int64 keys, and where no value can pass
+    that end (the caller empties the interval there).  NaN raises ValueError."""
+    none = INT64_MIN if low else INT64_MAX
+    if a is None:
+        return none, False
+    if a.dtype.kind == "f":
+        if np.isnan(a).any():
+            raise ValueError("between: a NaN bound")
+        if kind == "f":         # (an end that admits every value, -inf below / +inf above, is unbounded)
+            return np.where(a == (-np.inf if low else np.inf), none, _float_keys(a)), False
+        r = np.ceil(a.astype(np.float64)) if low else np.floor(a.astype(np.float64))
+        above, below = r >= 2.0**63, r < -2.0**63          # (beyond every int64: unbounded on one side, empty on the other)
+        keys = np.where(above | below, 0, r).astype(np.int64)
+        keys = np.where(below if low else above, none, keys)
+        return keys, (above if low else below)
+    if a.dtype == np.uint64 and a.size and a.max() > INT64_MAX:
+        if kind == "i":
+            raise ValueError("between: an integer bound above 2**63 - 1")
+    if kind == "i":
+        return a.astype(np.int64), False
+    f = a.astype(np.float64)
+    big = np.abs(f) >= 2.0**53          # (below, every integer is a float64)
+    if big.any() and any(int(v) != int(w) for v, w in zip(a[big].tolist(), f[big].tolist())):
+        raise ValueError("between: an integer bound on floating columns must be exactly representable in float64")
+    return _float_keys(f), False
+
+
+def query_ranges(between, nq, cols, kind):
+    """The (nq, cols, 2) int64 keys a `between=` argument is on `cols` columns of `kind` ("i" / "f": value_kind of the
+    values that were set): between = (lo, hi), each None (unbounded), a scalar for every query, (nq,) for one column,
+    (nq, cols), or (cols,) for every query where nq != cols (_bound_array); both ends inclusive.  Bounds become keys as
+    the column's values did (value_keys); None — and -inf for lo, +inf for hi — is INT64_MIN / INT64_MAX.  On integer columns a floating bound is
+    ceil'ed (lo) / floor'ed (hi), +-inf is unbounded where it admits everything and empties the interval where it
+    admits nothing.  On floating columns an integer bound must be exactly representable in float64.  TypeError for
+    another kind of argument, ValueError for a wrong shape, a NaN, or such an integer."""
+    if not isinstance(between, (tuple, list)) or len(between) != 2:
+        raise TypeError("between: a pair (lo, hi), each None, a number or an array")
+    lo, lo_empty = _bound_keys(_bound_array(between[0], "lo", nq, cols), kind, True)
+    hi, hi_empty = _bound_keys(_bound_array(between[1], "hi", nq, cols), kind, False)
+    out = np.empty((nq, cols, 2), dtype=np.int64)
+    out[:, :, 0] = lo
+    out[:, :, 1] = hi
+    empty = np.broadcast_to(np.logical_or(lo_empty, hi_empty), (nq, cols))
+    out[empty] = (1, 0)
+    return out
+
+
 def _stored(t):
     """Stored rows of one list's codes: a TransformedData, or the raw empty array FastPQ.transform returns for no rows."""
     return 0 if isinstance(t, np.ndarray) else t.size
@@ -420,6 +541,8 @@ class DeviceIndex:
     _source = None          # clone_shard: the index whose arrays this one borrows
     _clones = ()            # ... and the shards cloned from this one
     data_ptr = None         # resident: the device address of the vectors
+    _value_kind = None      # set_values: "i" / "f", the kind of the value columns (value_kind); None: no values
+    _value_cols = 0         # ... and how many
     list_sizes = None
     code_bytes = 0
 
@@ -816,6 +939,40 @@ class DeviceIndex:
         _lib.check(_lib.lib().tk_index_tag_table(self._h, _lib.ptr(o, _lib._i64p)))
         return dict(built=bool(o[0]), bytes=int(o[1]), builds=int(o[2]), row_bytes=int(o[3]))
 
+    def set_values(self, values):
+        """1 to 4 numeric columns per row, (N,) or (N, C) of one integer or floating dtype, for the `between=` argument
+        of the query calls: mapped to int64 keys (value_keys) and uploaded once, column-major (tk_index_set_values);
+        None clears.  After add() they must be set again for all N rows.  Batches in flight finish first.  Not for a
+        list-sharded index."""
+        if _dev_is_sharded(self) or self._source is not None:
+            raise RuntimeError("DeviceIndex.set_values: a list-sharded index takes no row values")
+        if values is None:
+            _lib.check(_lib.lib().tk_index_set_values(self._h, None, 0, 0))
+            self._value_kind, self._value_cols = None, 0
+            return
+        keys = value_keys(values, self.N, "set_values")
+        keys = np.ascontiguousarray(keys.reshape(len(keys), -1).T)          # (C, N)
+        _lib.check(_lib.lib().tk_index_set_values(self._h, keys.ctypes.data, keys.shape[1], keys.shape[0]))
+        self._value_kind, self._value_cols = value_kind(np.asarray(values).dtype), keys.shape[0]
+
+    def values_set(self):
+        """The number of rows the device's values cover, 0 for none (tk_index_values)."""
+        return int(_lib.check(_lib.lib().tk_index_values(self._h)))
+
+    def value_table(self):
+        """The value table behind between= (tk_index_value_table): dict(built, bytes, builds, row_bytes, cols)."""
+        o = np.zeros(4, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_value_table(self._h, _lib.ptr(o, _lib._i64p)))
+        return dict(built=bool(o[0]), bytes=int(o[1]), builds=int(o[2]), row_bytes=int(o[3]),
+                    cols=int(_lib.check(_lib.lib().tk_index_value_columns(self._h))))
+
+    def _ranges_of(self, between, nq):
+        """the (nq, C, 2) int64 keys of a `between=` argument (query_ranges); without values, an array the library
+        refuses (its TK_ERR_STATE names what to do)"""
+        if self._value_kind is None:
+            return np.zeros((nq, 1, 2), dtype=np.int64)
+        return query_ranges(between, nq, self._value_cols, self._value_kind)
+
     def _allow_of(self, allowed):
         """(set, temporary) for an `allowed=` argument: a prepared set of this index, or a mask / ids made into one"""
         if isinstance(allowed, AllowSet):
@@ -933,8 +1090,12 @@ class DeviceIndex:
         return (out, dist) if return_distances else out
 
     def query_batch(self, qn, q_pq, k, n_probes, pass_1=None, debug=False, *, allowed=None, return_distances=False,
-                    exclude=None, group=None, tags=None, tags_mode="any"):
+                    exclude=None, group=None, tags=None, tags_mode="any", between=None):
         """qn: (nq, d) float32 normalised queries; q_pq: (nq, dq) table-build queries.
+        between: None, or (lo, hi): the inclusive interval of values (set_values) each query's rows must lie in, per
+        column — each end None, a scalar, (nq,) for one column, (nq, C), or (C,) where nq != C (query_ranges; the
+        reference's `insert` only for labels that pass); such calls take the library path
+        (tk_index_query_batch_ex5).
         tags: None, an int for every query, or a 1-d integer array of length nq: the 64-bit tag mask each query is
         restricted by, 0 for none; tags_mode "any": a row passes where it carries one of the mask's tags (set_tags),
         "all": where it carries every one (the reference's `insert` only for labels that pass); such
@@ -956,17 +1117,24 @@ class DeviceIndex:
         q_pq = np.ascontiguousarray(q_pq, dtype=np.float64 if is64 else np.float32)
         nq = qn.shape[0]
         assert qn.shape[1] == self.d and q_pq.shape == (nq, self.dq)
-        if group is not None or exclude is not None or tags is not None:
+        if group is not None or exclude is not None or tags is not None or between is not None:
             if group is not None:
                 group = query_groups(group, nq)
+            mode = 0
             if tags is not None:
                 tags, mode = query_tags(tags, nq), tag_mode_of(tags_mode)
+            if between is not None:
+                between = self._ranges_of(between, nq)
             if exclude is not None:
                 exclude = self._exclude_of(exclude, nq)
             L, knobs = _lib.lib(), (int(k), int(n_probes), int(pass_1 or 0))
 
             def call(o, e, a, ex, out, *rest):
                 tail = (_lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o, *knobs, out, *rest)
+                if between is not None:
+                    return L.tk_index_query_batch_ex5(self._h, a, ex, None if group is None else group[o:e].ctypes.data,
+                                                      None if tags is None else tags[o:e].ctypes.data, mode,
+                                                      between[o:e].ctypes.data, *tail)
                 if tags is not None:
                     return L.tk_index_query_batch_ex4(self._h, a, ex, None if group is None else group[o:e].ctypes.data,
                                                       tags[o:e].ctypes.data, mode, *tail)
@@ -1099,7 +1267,7 @@ class DeviceIndex:
 
     def query_batch_dev(self, qn_ptr, qpq_ptr, qpq_is_f64, nq, k, n_probes, out_ptr,
                         pass_1=None, stream=0, done_event=None, *, allowed=None, dist_ptr=None, exclude_ptr=None,
-                        group_ptr=None, tags_ptr=None, tags_mode="any"):
+                        group_ptr=None, tags_ptr=None, tags_mode="any", between_ptr=None):
         """Device pointers in, device pointer out, enqueued on `stream` (no sync).
         done_event: a hipEvent_t (integer handle) recorded behind the batch's last kernel, on
         whichever internal stream that runs (tk_index_query_batch_dev_ex).
@@ -1118,13 +1286,21 @@ class DeviceIndex:
         unrestricted query (tk_index_query_batch_dev_ex3); the caller's again after join() or done_event.
         tags_ptr: None, or a device buffer of nq uint64: the tag mask each query is restricted by under tags_mode
         ("any" / "all"), an entry of 0 for an unrestricted query (tk_index_query_batch_dev_ex4); the caller's again
-        after join() or done_event."""
+        after join() or done_event.
+        between_ptr: None, or a device buffer of nq x C x 2 int64 keys (query_ranges' array): the interval each query
+        is restricted to per value column, INT64_MIN / INT64_MAX for an unbounded end
+        (tk_index_query_batch_dev_ex5); the caller's again after join() or done_event."""
         if allowed is not None:
             if not isinstance(allowed, AllowSet):
                 raise TypeError("query_batch_dev: allowed= takes a prepared set (DeviceIndex.allow / IVF.allow)")
             allowed = self._allow_of(allowed)[0].handle
         L, ev = _lib.lib(), None if done_event is None else C.c_void_p(int(done_event))
-        if tags_ptr is not None:
+        if between_ptr is not None:
+            mode = tag_mode_of(tags_mode) if tags_ptr is not None else 0
+            rc = L.tk_index_query_batch_dev_ex5(
+                self._h, allowed, exclude_ptr, group_ptr, tags_ptr, mode, between_ptr, qn_ptr, qpq_ptr, int(qpq_is_f64),
+                nq, int(k), int(n_probes), int(pass_1 or 0), out_ptr, dist_ptr, ev, stream)
+        elif tags_ptr is not None:
             mode = tag_mode_of(tags_mode)
             rc = L.tk_index_query_batch_dev_ex4(
                 self._h, allowed, exclude_ptr, group_ptr, tags_ptr, mode, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k),
@@ -1400,6 +1576,7 @@ class IVF:
     store = None            # how the device keeps the rescoring vectors: None / "float32" / "float16" (build's store=)
     groups = None           # set_groups' host copy: (N,) int32 group id per row; None (and no instance attribute): none
     tags = None             # set_tags' host copy: (N,) uint64 tag mask per row; None (and no instance attribute): none
+    values = None           # set_values' host copy: (N,) or (N, C) in the caller's dtype; None (and no instance attribute): none
 
     def __init__(self, metric, n_clusters, pq=None):
         assert metric in ["euclidean", "angular"]
@@ -1471,6 +1648,7 @@ class IVF:
         self.store = store
         self.__dict__.pop("groups", None)               # (groups belong to the rows they were set for)
         self.__dict__.pop("tags", None)                 # (tags too)
+        self.__dict__.pop("values", None)               # (and values)
         with timer(verbose, "Computing nearest clusters..."):
             if device:
                 nearest = self._nearest_on_device(data, n_probes)
@@ -1618,6 +1796,8 @@ class IVF:
             extra["groups"] = self.groups
         if self.tags is not None:
             extra["tags"] = self.tags
+        if self.values is not None:
+            extra["values"] = self.values
         path = self._npz_path(path)
         np.savez(path, format_version=1, metric=self.metric, n_clusters=self.n_clusters,
                  use_kmeans=int(self.pq.use_kmeans), rotate_dim=-1 if self.pq.rotate_dim is None else int(self.pq.rotate_dim),
@@ -1663,6 +1843,8 @@ class IVF:
             ivf.groups = np.ascontiguousarray(z["groups"], dtype=np.int32)
         if "tags" in z:
             ivf.tags = np.ascontiguousarray(z["tags"], dtype=np.uint64)
+        if "values" in z:
+            ivf.values = np.ascontiguousarray(z["values"])
         return ivf
 
     def build_resident(self, N, d, seed, centres=None, sigma=1.0, verbose=False, n_probes=1, store=None):
@@ -1709,14 +1891,16 @@ class IVF:
         self.ids = self.pq_transformed_points = None
         self.__dict__.pop("groups", None)               # (groups belong to the rows they were set for, as in build)
         self.__dict__.pop("tags", None)
+        self.__dict__.pop("values", None)
         self._dev = dev
         return self
 
     # ---- growth ------------------------------------------------------------
-    def add(self, X, verbose=False, groups=None, tags=None):
+    def add(self, X, verbose=False, groups=None, tags=None, values=None):
         """Append the rows of X with ids N .. N + n - 1 (returns self).  groups: the new rows' group ids, needed (and
         only taken) where the index has groups (set_groups): ValueError otherwise, before anything changes.  tags: the
-        new rows' tag masks, by the same rule where the index has tags (set_tags).  The index afterwards is the one its own
+        new rows' tag masks, by the same rule where the index has tags (set_tags); values: the new rows' values, (n,) or
+        (n, C) as the index's, by the same rule where it has values (set_values).  The index afterwards is the one its own
         build would make over (old rows, X): new rows are prepared as the build prepared its rows (dtype of
         IVF.data, normalisation, padding, rotation, assignment, PQ codes); every list keeps its old members in
         place, and with n_probes = kp lists per row list l's column-j block becomes old_j ++ new_j (new_j: the
@@ -1742,6 +1926,12 @@ class IVF:
             if tags is None:
                 raise ValueError("IVF.add: this index has tags (set_tags): pass the new rows' with tags=")
             tags = tag_masks(tags, len(X), "IVF.add: tags")
+        if self.values is None and values is not None:
+            raise ValueError("IVF.add: values= on an index without values (set_values first)")
+        if self.values is not None:
+            if values is None:
+                raise ValueError("IVF.add: this index has values (set_values): pass the new rows' with values=")
+            values = self._new_values(values, len(X), "IVF.add: values")
         if self.all_centers is None:
             raise AssertionError("IVF.add: the index has no all_centers (fit, or a file written with them)")
         if len(X) == 0:
@@ -1758,7 +1948,25 @@ class IVF:
             self.tags = np.concatenate([self.tags, tags])
             if self._dev is not None:
                 self._dev.set_tags(self.tags)
+        if values is not None:
+            self.values = np.concatenate([self.values, values])
+            if self._dev is not None:
+                self._dev.set_values(self.values)
         return self
+
+    def _new_values(self, values, n, what):
+        """`values` for n rows of an index that has values: checked as set_values checks (value_keys), in the shape and
+        of the kind (ValueError) of IVF.values, converted to its dtype"""
+        a = np.asarray(values)
+        value_keys(a, n, what)
+        if a.shape[1:] != self.values.shape[1:]:
+            raise ValueError(f"{what}: shape (n,) + {self.values.shape[1:]} as the index's values, got {a.shape}")
+        if value_kind(a.dtype) != value_kind(self.values.dtype):
+            raise ValueError(f"{what}: {self.values.dtype} as the index's values, got {a.dtype}")
+        b = a.astype(self.values.dtype)
+        if value_kind(a.dtype) == "i" and a.size and not np.array_equal(b.astype(object), a.astype(object)):
+            raise ValueError(f"{what}: values that do not fit the index's {self.values.dtype}")
+        return b
 
     def _require_device_free(self, what="add", doing="adding rows to"):
         if self._dev is not None and _dev_is_sharded(self._dev):
@@ -1917,7 +2125,7 @@ class IVF:
         return pts, idl, cols1
 
     # ---- replacement --------------------------------------------------------
-    def update(self, ids, X, verbose=False, groups=None, tags=None):
+    def update(self, ids, X, verbose=False, groups=None, tags=None, values=None):
         """Give the stored rows `ids` (n row ids in [0, N), pairwise distinct) the new vectors X (n, d), ids kept
         (returns self).  The index afterwards is the one that remove(ids) then add(X) gives on the same index, with
         two differences: the added row N + i carries the label ids[i] in every list, and its prepared vector sits in
@@ -1929,7 +2137,7 @@ class IVF:
         nearest list does not change moves to the end of its column block, a list that empties stays with its
         centre, rows that activate centres past the active ones append lists (the prefix rule and AssertionError of
         add); list_columns follows.  groups: new group ids for those rows, only taken where the index has groups;
-        without it they keep their groups; tags: the same for tag masks (set_tags).  A duplicate or out-of-range id raises
+        without it they keep their groups; tags: the same for tag masks (set_tags), values: for values (set_values).  A duplicate or out-of-range id raises
         ValueError.  The device index is
         updated in place (one pass over its codes, one scatter into its vectors): batches in flight finish on the
         old lists and vectors, allowed sets made before fail afterwards.  A refused call changes nothing."""
@@ -1947,6 +2155,10 @@ class IVF:
             if self.tags is None:
                 raise ValueError("IVF.update: tags= on an index without tags (set_tags first)")
             tags = tag_masks(tags, len(X), "IVF.update: tags")
+        if values is not None:
+            if self.values is None:
+                raise ValueError("IVF.update: values= on an index without values (set_values first)")
+            values = self._new_values(values, len(X), "IVF.update: values")
         if self.all_centers is None:
             raise AssertionError("IVF.update: the index has no all_centers (fit, or a file written with them)")
         if len(ids) == 0:
@@ -1965,6 +2177,11 @@ class IVF:
             self.tags[ids] = tags
             if self._dev is not None:
                 self._dev.set_tags(self.tags)
+        if values is not None:
+            self.values = self.values.copy()
+            self.values[ids] = values
+            if self._dev is not None:
+                self._dev.set_values(self.values)
         return self
 
     def _update_resident(self, ids, X, verbose):
@@ -2084,6 +2301,8 @@ class IVF:
                 dev.set_groups(self.groups)
             if self.tags is not None:
                 dev.set_tags(self.tags)
+            if self.values is not None:
+                dev.set_values(self.values)
             self._dev = dev
         return self._dev
 
@@ -2114,6 +2333,30 @@ class IVF:
         else:
             self.tags = t.copy() if t is tags or np.shares_memory(t, tags) else t
         return self
+
+    def set_values(self, values):
+        """1 to 4 numeric columns per row — a timestamp, a price, a version: (N,) or (N, C) of ONE integer or floating
+        dtype (float16 / 32 / 64) — for the `between=` argument of query / query_batch; None clears.
+        TypeError for another kind of value, ValueError for another length, more than 4 columns, a NaN or a uint64
+        above 2**63 - 1.  IVF.values is the host copy in the caller's dtype; save / load and pickling carry it."""
+        v = None
+        if values is not None:
+            v = np.array(values)                    # (a copy, in the caller's dtype)
+            value_keys(v, len(self.data), "IVF.set_values")
+        if self._dev is not None:                # (a list-sharded index raises here, before the host copy changes)
+            self._unsharded_device_index().set_values(v)
+        if v is None:
+            self.__dict__.pop("values", None)
+        else:
+            self.values = v
+        return self
+
+    def _ranges(self, between, nq):
+        """`between=` checked against IVF.values before anything runs (query_ranges): the keys the device takes"""
+        if self.values is None:
+            raise ValueError("between= on an index without values (set_values first)")
+        return query_ranges(between, nq, 1 if self.values.ndim == 1 else self.values.shape[1],
+                            value_kind(self.values.dtype))
 
     def _unsharded_device_index(self):
         dev = self.device_index()
@@ -2147,8 +2390,10 @@ class IVF:
         return self._unsharded_device_index().allow(ids_or_mask)
 
     def query(self, q, k, n_probes=1, pass_1=None, *, allowed=None, return_distances=False, exclude=None, group=None,
-              tags=None, tags_mode="any"):
+              tags=None, tags_mode="any", between=None):
         """Top-k ids for one query.  reference: ivf.py:106-163
+        between: (lo, hi), the inclusive interval of values (set_values) the query's rows must lie in: each end None
+        (unbounded), a number, or one entry per column.
         tags: the 64-bit tag mask the query is restricted by under tags_mode — "any": rows that carry one of its tags
         (set_tags), "all": rows that carry every one; 0 or None for any row.
         group: the group of rows (set_groups) the query may return, -1 or None for any.
@@ -2157,6 +2402,11 @@ class IVF:
         query with `insert` only for those labels.
         return_distances: (ids, dists) of the same length — the exact squared distance of each id to the
         (normalised) query, as the rescoring computed it."""
+        if between is not None:
+            if not isinstance(between, (tuple, list)) or len(between) != 2:
+                raise TypeError("between: a pair (lo, hi), each None, a number or an array")
+            between = tuple(b if b is None or np.ndim(b) == 0 else np.asarray(b).reshape(1, -1) for b in between)
+            self._ranges(between, 1)                # (refused before anything runs)
         q = np.ascontiguousarray(q, dtype=np.float32)
         assert self.data.shape[1] == q.shape[0]
         qn, qp = self._prepare(q[None, :])
@@ -2169,14 +2419,15 @@ class IVF:
             tags = np.asarray(tags).reshape(1)
         if return_distances:
             ids, dist = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, return_distances=True,
-                                        exclude=exclude, group=group, tags=tags, tags_mode=tags_mode)
+                                        exclude=exclude, group=group, tags=tags, tags_mode=tags_mode,
+                                        between=between)
             out, dist = ids[0], dist[0]
             if out[-1] == -1:
                 keep = out != -1
                 return out[keep], dist[keep]
             return out, dist
         out = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, exclude=exclude, group=group, tags=tags,
-                              tags_mode=tags_mode)[0]
+                              tags_mode=tags_mode, between=between)[0]
         return out[out != -1] if out[-1] == -1 else out
 
     def query_rows(self, rows, k, n_probes=1, pass_1=None, *, exclude_self=True, allowed=None,
@@ -2240,7 +2491,7 @@ class IVF:
         return (ids, dist) if return_distances else ids
 
     def query_batch(self, qs, k, n_probes=1, pass_1=None, fast=False, *, allowed=None, return_distances=False,
-                    exclude=None, group=None, tags=None, tags_mode="any"):
+                    exclude=None, group=None, tags=None, tags_mode="any", between=None):
         """(nq, d) queries -> (nq, k) int64 ids, rows padded with -1 when the
         reference would return fewer than k ids.  (The reference's README shows a
         2-d `ivf.query(queries, ...)` that its code does not support; this is that
@@ -2254,7 +2505,15 @@ class IVF:
         it may return, -1 for any; not with fast=True.
         tags: an int for every query, or a 1-d integer array with one 64-bit mask per query: the tags (set_tags) its
         rows must carry — one of them with tags_mode "any", every one with "all" — 0 for any row; not
-        with fast=True."""
+        with fast=True.
+        between: (lo, hi), the inclusive interval of values (set_values) each query's rows must lie in, per column:
+        each end None (unbounded), a number for every query, (nq,) for one column, (nq, C), or (C,) where nq != C
+        (DESIGN §3.14); not with fast=True."""
+        if between is not None and fast:
+            raise NotImplementedError("IVF.query_batch: fast=True with between= is not supported; "
+                                      "use the exact default (fast=False)")
+        if between is not None:
+            self._ranges(between, len(qs))
         if tags is not None and fast:
             raise NotImplementedError("IVF.query_batch: fast=True with tags= is not supported; "
                                       "use the exact default (fast=False)")
@@ -2270,7 +2529,8 @@ class IVF:
             raise NotImplementedError("IVF.query_batch: fast=True with return_distances=True is not supported; "
                                       "use the exact default (fast=False)")
         self._unsharded_device_index()
-        if allowed is not None or return_distances or exclude is not None or group is not None or tags is not None:
+        if allowed is not None or return_distances or exclude is not None or group is not None or tags is not None \
+                or between is not None:
             if fast:
                 raise NotImplementedError("IVF.query_batch: fast=True with allowed= is not supported; "
                                           "use the exact default (fast=False)")
@@ -2284,7 +2544,7 @@ class IVF:
             qn, qp = self._prepare(qs)
             return self.device_index().query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed,
                                                    return_distances=return_distances, exclude=exclude, group=group,
-                                                   tags=tags, tags_mode=tags_mode)
+                                                   tags=tags, tags_mode=tags_mode, between=between)
         if fast:
             return self.device_index().query_batch_raw(qs, k, n_probes, pass_1)
         R = self.pq.R
