@@ -6,6 +6,7 @@ is uploaded once into HBM (`DeviceIndex`); `query` and `query_batch` then run th
 kernel pipeline of libtinyknn_hip.so: distance tables -> coarse scan + heap +
 rescoring -> probed-list scan -> exact heap replay -> exact rescoring.
 """
+import collections
 import ctypes as C
 import time
 import warnings
@@ -408,6 +409,43 @@ def query_ranges(between, nq, cols, kind):
     empty = np.broadcast_to(np.logical_or(lo_empty, hi_empty), (nq, cols))
     out[empty] = (1, 0)
     return out
+
+
+def host_values(values, n, what, like=None):
+    """The host copy of a `values` argument for n rows: the caller's array in its own dtype, checked as the device will
+    take it (value_keys).  like (the index's values, for new rows): in its shape and of its kind (ValueError),
+    converted to its dtype."""
+    a = np.asarray(values)
+    value_keys(a, n, what)
+    if like is None:
+        return a
+    if a.shape[1:] != like.shape[1:]:
+        raise ValueError(f"{what}: shape (n,) + {like.shape[1:]} as the index's values, got {a.shape}")
+    if value_kind(a.dtype) != value_kind(like.dtype):
+        raise ValueError(f"{what}: {like.dtype} as the index's values, got {a.dtype}")
+    b = a.astype(like.dtype)
+    if value_kind(a.dtype) == "i" and a.size and not np.array_equal(b.astype(object), a.astype(object)):
+        raise ValueError(f"{what}: values that do not fit the index's {like.dtype}")
+    return b
+
+
+def _value_columns(keys):
+    """tk_index_set_values' arguments for value_keys' array: the keys column-major (C, N), N, C"""
+    kt = np.ascontiguousarray(keys.reshape(len(keys), -1).T)
+    return _lib.ptr(kt, C.c_void_p), kt.shape[1], kt.shape[0]
+
+
+# The per-row attributes a query can be restricted by (group=, tags=, between=), and what differs between them.
+# name: the IVF attribute, the keyword of add / update, the .npz key, the word of the messages, and with `one` the
+# library's names (tk_index_set_<name>, the counter tk_index_<name>, the reader tk_index_<one>_table); rows: the parser
+# of per-row input -> what the device takes; host: the host copy where it is not that (values: the caller's array);
+# dtype: the host copy's (None: the caller's); upload / clear: tk_index_set_<name>'s arguments behind the handle.
+RowAttr = collections.namedtuple("RowAttr", "name one rows host dtype upload clear")
+ROW_ATTRS = GROUPS, TAGS, VALUES = (
+    RowAttr("groups", "group", group_ids, None, np.int32, lambda g: (_lib.ptr(g, _lib._i32p), len(g)), (None, 0)),
+    RowAttr("tags", "tag", tag_masks, None, np.uint64, lambda t: (_lib.ptr(t, C.c_void_p), len(t)), (None, 0)),
+    RowAttr("values", "value", value_keys, host_values, None, _value_columns, (None, 0, 0)),
+)
 
 
 def _stored(t):
@@ -895,76 +933,70 @@ class DeviceIndex:
         self._live_allows.add(a)
         return a
 
+    def _set_rows(self, at, x):
+        """set_groups / set_tags / set_values: x parsed (at.rows) and uploaded, or cleared for None -> what was uploaded"""
+        if _dev_is_sharded(self) or self._source is not None:
+            raise RuntimeError(f"DeviceIndex.set_{at.name}: a list-sharded index takes no row {at.name}")
+        a = None if x is None else at.rows(x, self.N, f"set_{at.name}")
+        _lib.check(getattr(_lib.lib(), f"tk_index_set_{at.name}")(self._h, *(at.clear if a is None else at.upload(a))))
+        return a
+
+    def _rows_set(self, at):
+        """groups_set / tags_set / values_set: the rows the device's attribute covers (tk_index_<name>)"""
+        return int(_lib.check(getattr(_lib.lib(), f"tk_index_{at.name}")(self._h)))
+
+    def _table_info(self, one, fourth="row_bytes"):
+        """group_table / tag_table / value_table / row_table: the four numbers of tk_index_<one>_table as a dict"""
+        o = np.zeros(4, dtype=np.int64)
+        _lib.check(getattr(_lib.lib(), f"tk_index_{one}_table")(self._h, _lib.ptr(o, _lib._i64p)))
+        return {"built": bool(o[0]), "bytes": int(o[1]), "builds": int(o[2]), fourth: int(o[3])}
+
     def set_groups(self, groups):
         """One group id per row (int, [0, 2**31 - 1)) for the `group=` argument of the query calls, uploaded once
         (tk_index_set_groups); None clears.  After add() they must be set again for all N rows.  Batches in flight
         finish first.  Not for a list-sharded index."""
-        if _dev_is_sharded(self) or self._source is not None:
-            raise RuntimeError("DeviceIndex.set_groups: a list-sharded index takes no row groups")
-        if groups is None:
-            _lib.check(_lib.lib().tk_index_set_groups(self._h, None, 0))
-            return
-        g = group_ids(groups, self.N, "set_groups")
-        _lib.check(_lib.lib().tk_index_set_groups(self._h, _lib.ptr(g, _lib._i32p), len(g)))
+        self._set_rows(GROUPS, groups)
 
     def groups_set(self):
         """The number of rows the device's groups cover, 0 for none (tk_index_groups)."""
-        return int(_lib.check(_lib.lib().tk_index_groups(self._h)))
+        return self._rows_set(GROUPS)
 
     def group_table(self):
         """The group table behind group= (tk_index_group_table): dict(built, bytes, builds, row_bytes)."""
-        o = np.zeros(4, dtype=np.int64)
-        _lib.check(_lib.lib().tk_index_group_table(self._h, _lib.ptr(o, _lib._i64p)))
-        return dict(built=bool(o[0]), bytes=int(o[1]), builds=int(o[2]), row_bytes=int(o[3]))
+        return self._table_info(GROUPS.one)
 
     def set_tags(self, tags):
         """One 64-bit tag mask per row (bit t set: the row carries tag t) for the `tags=` argument of the query
         calls, uploaded once (tk_index_set_tags); None clears.  After add() they must be set again for all N rows.
         Batches in flight finish first.  Not for a list-sharded index."""
-        if _dev_is_sharded(self) or self._source is not None:
-            raise RuntimeError("DeviceIndex.set_tags: a list-sharded index takes no row tags")
-        if tags is None:
-            _lib.check(_lib.lib().tk_index_set_tags(self._h, None, 0))
-            return
-        t = tag_masks(tags, self.N, "set_tags")
-        _lib.check(_lib.lib().tk_index_set_tags(self._h, t.ctypes.data, len(t)))
+        self._set_rows(TAGS, tags)
 
     def tags_set(self):
         """The number of rows the device's tags cover, 0 for none (tk_index_tags)."""
-        return int(_lib.check(_lib.lib().tk_index_tags(self._h)))
+        return self._rows_set(TAGS)
 
     def tag_table(self):
         """The tag table behind tags= (tk_index_tag_table): dict(built, bytes, builds, row_bytes)."""
-        o = np.zeros(4, dtype=np.int64)
-        _lib.check(_lib.lib().tk_index_tag_table(self._h, _lib.ptr(o, _lib._i64p)))
-        return dict(built=bool(o[0]), bytes=int(o[1]), builds=int(o[2]), row_bytes=int(o[3]))
+        return self._table_info(TAGS.one)
 
     def set_values(self, values):
         """1 to 4 numeric columns per row, (N,) or (N, C) of one integer or floating dtype, for the `between=` argument
         of the query calls: mapped to int64 keys (value_keys) and uploaded once, column-major (tk_index_set_values);
         None clears.  After add() they must be set again for all N rows.  Batches in flight finish first.  Not for a
         list-sharded index."""
-        if _dev_is_sharded(self) or self._source is not None:
-            raise RuntimeError("DeviceIndex.set_values: a list-sharded index takes no row values")
-        if values is None:
-            _lib.check(_lib.lib().tk_index_set_values(self._h, None, 0, 0))
+        keys = self._set_rows(VALUES, values)
+        if keys is None:
             self._value_kind, self._value_cols = None, 0
-            return
-        keys = value_keys(values, self.N, "set_values")
-        keys = np.ascontiguousarray(keys.reshape(len(keys), -1).T)          # (C, N)
-        _lib.check(_lib.lib().tk_index_set_values(self._h, keys.ctypes.data, keys.shape[1], keys.shape[0]))
-        self._value_kind, self._value_cols = value_kind(np.asarray(values).dtype), keys.shape[0]
+        else:
+            self._value_kind, self._value_cols = value_kind(np.asarray(values).dtype), int(np.prod(keys.shape[1:]))
 
     def values_set(self):
         """The number of rows the device's values cover, 0 for none (tk_index_values)."""
-        return int(_lib.check(_lib.lib().tk_index_values(self._h)))
+        return self._rows_set(VALUES)
 
     def value_table(self):
         """The value table behind between= (tk_index_value_table): dict(built, bytes, builds, row_bytes, cols)."""
-        o = np.zeros(4, dtype=np.int64)
-        _lib.check(_lib.lib().tk_index_value_table(self._h, _lib.ptr(o, _lib._i64p)))
-        return dict(built=bool(o[0]), bytes=int(o[1]), builds=int(o[2]), row_bytes=int(o[3]),
-                    cols=int(_lib.check(_lib.lib().tk_index_value_columns(self._h))))
+        return dict(self._table_info(VALUES.one), cols=int(_lib.check(_lib.lib().tk_index_value_columns(self._h))))
 
     def _ranges_of(self, between, nq):
         """the (nq, C, 2) int64 keys of a `between=` argument (query_ranges); without values, an array the library
@@ -1056,9 +1088,13 @@ class DeviceIndex:
             raise ValueError(f"exclude: entries must lie in [-1, {self.N})")
         return a
 
-    def _query_ex2(self, call, nq, k, n_probes, pass_1, debug, return_distances, allowed, exclude=None):
-        """The library's everything-at-once host calls (tk_index_query_batch_ex2 / tk_index_query_rows) for rows
-        [o, e) at a time: call(o, e, allow handle, exclude, out, dist, probes, heap_idx, heap_val)."""
+    def _query_host(self, call, nq, k, n_probes, pass_1, debug, return_distances, allowed, split, always=False):
+        """A host query call from its outputs to what it returns.  The outputs: ids filled with -1, with
+        return_distances the distances filled with +inf in the index's precision, with debug the probes and the two
+        heap arrays.  The sub-batches: call(o, e, allowed set's handle, out, dist, probes, heap_idx, heap_val) — each
+        output's rows [o, e) as the library takes it, or None — for all nq rows at once, or under `split` for
+        max_sub_batch rows at a time (which keeps the debug outputs of every row); `always`: once even for nq = 0.
+        A mask or ids in `allowed` are a set for as long as that takes."""
         if return_distances and debug:
             raise ValueError("query_batch: debug=True cannot be combined with return_distances=True")
         out = np.full((nq, k), -1, dtype=np.int64)
@@ -1072,12 +1108,10 @@ class DeviceIndex:
             hval = np.zeros((nq, R), dtype=np.int32)
         aset, temp = (None, False) if allowed is None else self._allow_of(allowed)
         try:
-            # (one sub-batch at a time keeps the debug outputs of every row)
-            step = max(1, self.max_sub_batch(k, n_probes, pass_1)) if debug else max(1, nq)
-            for o in range(0, nq, step):
+            step = max(1, self.max_sub_batch(k, n_probes, pass_1)) if split else max(1, nq)
+            for o in range(0, max(nq, 1) if always else nq, step):
                 e = min(nq, o + step)
                 _lib.check(call(o, e, None if aset is None else aset.handle,
-                                None if exclude is None else _lib.ptr(exclude[o:e], _lib._i64p),
                                 _lib.ptr(out[o:e], _lib._i64p), None if dist is None else dist[o:e].ctypes.data,
                                 None if probes is None else _lib.ptr(probes[o:e], _lib._i64p),
                                 None if hidx is None else _lib.ptr(hidx[o:e], _lib._i64p),
@@ -1094,18 +1128,16 @@ class DeviceIndex:
         """qn: (nq, d) float32 normalised queries; q_pq: (nq, dq) table-build queries.
         between: None, or (lo, hi): the inclusive interval of values (set_values) each query's rows must lie in, per
         column — each end None, a scalar, (nq,) for one column, (nq, C), or (C,) where nq != C (query_ranges; the
-        reference's `insert` only for labels that pass); such calls take the library path
-        (tk_index_query_batch_ex5).
+        reference's `insert` only for labels that pass).
         tags: None, an int for every query, or a 1-d integer array of length nq: the 64-bit tag mask each query is
         restricted by, 0 for none; tags_mode "any": a row passes where it carries one of the mask's tags (set_tags),
-        "all": where it carries every one (the reference's `insert` only for labels that pass); such
-        calls take the library path (tk_index_query_batch_ex4).
+        "all": where it carries every one (the reference's `insert` only for labels that pass).
         group: None, an int for every query, or a 1-d integer array of length nq: the group of rows (set_groups) each
-        query may return, -1 for any (the reference's `insert` only for labels of that group); such
-        calls take the library path (tk_index_query_batch_ex3).
+        query may return, -1 for any (the reference's `insert` only for labels of that group).
         exclude: None, or a 1-d integer array of length nq: the row each query may not return, -1 for none (the
-        reference's `insert` only for labels != that row); such calls take the library path
-        (tk_index_query_batch_ex2), not the cached streaming session.
+        reference's `insert` only for labels != that row).
+        A call with between, tags, group or exclude takes the library's one restricted entry point
+        (tk_index_query_batch_ex5, NULL for what is not given), not the cached streaming session.
         allowed: None, or the rows the queries may return — an AllowSet (allow()), a bool mask of length N or row
         ids (the library's _allow entry point: the reference's `insert` only for those labels).
         return_distances: (ids, dists) — the same ids, and beside each the exact squared distance the rescoring
@@ -1117,78 +1149,49 @@ class DeviceIndex:
         q_pq = np.ascontiguousarray(q_pq, dtype=np.float64 if is64 else np.float32)
         nq = qn.shape[0]
         assert qn.shape[1] == self.d and q_pq.shape == (nq, self.dq)
-        if group is not None or exclude is not None or tags is not None or between is not None:
-            if group is not None:
-                group = query_groups(group, nq)
-            mode = 0
-            if tags is not None:
-                tags, mode = query_tags(tags, nq), tag_mode_of(tags_mode)
-            if between is not None:
-                between = self._ranges_of(between, nq)
-            if exclude is not None:
-                exclude = self._exclude_of(exclude, nq)
-            L, knobs = _lib.lib(), (int(k), int(n_probes), int(pass_1 or 0))
+        L, knobs = _lib.lib(), (int(k), int(n_probes), int(pass_1 or 0))
 
-            def call(o, e, a, ex, out, *rest):
-                tail = (_lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o, *knobs, out, *rest)
-                if between is not None:
-                    return L.tk_index_query_batch_ex5(self._h, a, ex, None if group is None else group[o:e].ctypes.data,
-                                                      None if tags is None else tags[o:e].ctypes.data, mode,
-                                                      between[o:e].ctypes.data, *tail)
-                if tags is not None:
-                    return L.tk_index_query_batch_ex4(self._h, a, ex, None if group is None else group[o:e].ctypes.data,
-                                                      tags[o:e].ctypes.data, mode, *tail)
-                if group is None:
-                    return L.tk_index_query_batch_ex2(self._h, a, ex, *tail)
-                return L.tk_index_query_batch_ex3(self._h, a, ex, group[o:e].ctypes.data, *tail)
-            return self._query_ex2(call, nq, k, n_probes, pass_1, debug, return_distances, allowed, exclude)
-        out = np.full((nq, k), -1, dtype=np.int64)
+        def queries(o, e):
+            return _lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o, *knobs
+
+        if group is not None or exclude is not None or tags is not None or between is not None:
+            group = None if group is None else query_groups(group, nq)
+            tags, mode = (None, 0) if tags is None else (query_tags(tags, nq), tag_mode_of(tags_mode))
+            between = None if between is None else self._ranges_of(between, nq)
+            exclude = None if exclude is None else self._exclude_of(exclude, nq)
+
+            def rows(a, o, e):
+                return None if a is None else a[o:e].ctypes.data
+
+            return self._query_host(
+                lambda o, e, aset, *outs: L.tk_index_query_batch_ex5(
+                    self._h, aset, rows(exclude, o, e), rows(group, o, e), rows(tags, o, e), mode, rows(between, o, e),
+                    *queries(o, e), *outs),
+                nq, k, n_probes, pass_1, debug, return_distances, allowed, split=debug)
         if allowed is None and not return_distances and not debug and nq > 0:
             # the session pads unrotated queries on the device: only for q_pq = pad1(qn)
             plain = is64 or (np.array_equal(q_pq[:, :self.d], qn) and not q_pq[:, self.d:].any())
             if plain and _front.bind():
                 # prepared rows through the streaming session (pinned staging, async copies)
+                out = np.full((nq, k), -1, dtype=np.int64)
                 st = self._cached_stream(nq, k, n_probes, pass_1)
                 for o in range(0, nq, st.max_nq):
                     st.submit_prepared(qn[o:o + st.max_nq],
                                        q_pq[o:o + st.max_nq] if is64 else None, out[o:o + st.max_nq])
                 st.drain()
                 return out
-        dist = probes = hidx = hval = None
         if return_distances:
-            dist = np.full((nq, k), np.inf, dtype=np.float64 if self._f64 else np.float32)
-        if debug:
-            R = pass_1 if pass_1 else (n_probes + 1) * k + 1
-            probes = np.zeros((nq, min(n_probes, self.n_lists)), dtype=np.int64)
-            hidx = np.zeros((nq, R), dtype=np.int64)
-            hval = np.zeros((nq, R), dtype=np.int32)
-        L, knobs = _lib.lib(), (int(k), int(n_probes), int(pass_1 or 0))
-        aset, temp = (None, False) if allowed is None else self._allow_of(allowed)
-        try:
-            if return_distances:
-                _lib.check(L.tk_index_query_batch_dist(
-                    self._h, None if aset is None else aset.handle, _lib.ptr(qn, _lib._f32p), q_pq.ctypes.data,
-                    int(is64), nq, *knobs, _lib.ptr(out, _lib._i64p), dist.ctypes.data))
-                return out, dist
-            # (with a set, one sub-batch at a time keeps the debug outputs of every row)
-            step = max(1, self.max_sub_batch(k, n_probes, pass_1)) if debug and aset is not None else max(1, nq)
-            for o in range(0, nq if aset is not None else 1, step):
-                e = min(nq, o + step)
-                args = (_lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o, *knobs,
-                        _lib.ptr(out[o:e], _lib._i64p),
-                        None if probes is None else _lib.ptr(probes[o:e], _lib._i64p),
-                        None if hidx is None else _lib.ptr(hidx[o:e], _lib._i64p),
-                        None if hval is None else _lib.ptr(hval[o:e], _lib._i32p))
-                if aset is None:
-                    _lib.check(L.tk_index_query_batch(self._h, *args))
-                else:
-                    _lib.check(L.tk_index_query_batch_allow(self._h, aset.handle, *args))
-        finally:
-            if temp:
-                aset.close()
-        if debug:
-            return out, dict(probes=probes, heap_idx=hidx, heap_val=hval)
-        return out
+            def call(o, e, aset, out, dist, *dbg):
+                return L.tk_index_query_batch_dist(self._h, aset, *queries(o, e), out, dist)
+        elif allowed is None:
+            def call(o, e, aset, out, dist, *dbg):
+                return L.tk_index_query_batch(self._h, *queries(o, e), out, *dbg)
+        else:
+            def call(o, e, aset, out, dist, *dbg):
+                return L.tk_index_query_batch_allow(self._h, aset, *queries(o, e), out, *dbg)
+        # (only with a set is a debug call split; without one, and for distances, the library is called even for no query)
+        return self._query_host(call, nq, k, n_probes, pass_1, debug, return_distances, allowed,
+                                split=debug and allowed is not None, always=return_distances or allowed is None)
 
     def _rows_of(self, rows, what):
         """int64 row ids in [0, N), duplicates allowed (validated like remove's ids)"""
@@ -1231,16 +1234,14 @@ class DeviceIndex:
         its own row out where exclude_self.  Outputs as query_batch."""
         rows = self._rows_of(rows, "query_rows")
         L, knobs = _lib.lib(), (int(k), int(n_probes), int(pass_1 or 0))
-        return self._query_ex2(
-            lambda o, e, a, ex, *outs: L.tk_index_query_rows(
-                self._h, a, _lib.ptr(rows[o:e], _lib._i64p), e - o, int(bool(exclude_self)), *knobs, *outs),
-            len(rows), k, n_probes, pass_1, debug, return_distances, allowed)
+        return self._query_host(
+            lambda o, e, aset, *outs: L.tk_index_query_rows(
+                self._h, aset, _lib.ptr(rows[o:e], _lib._i64p), e - o, int(bool(exclude_self)), *knobs, *outs),
+            len(rows), k, n_probes, pass_1, debug, return_distances, allowed, split=debug)
 
     def row_table(self):
         """The row-position table behind exclude= (tk_index_row_table): dict(built, bytes, builds, entries)."""
-        o = np.zeros(4, dtype=np.int64)
-        _lib.check(_lib.lib().tk_index_row_table(self._h, _lib.ptr(o, _lib._i64p)))
-        return dict(built=bool(o[0]), bytes=int(o[1]), builds=int(o[2]), entries=int(o[3]))
+        return self._table_info("row", "entries")
 
     def query_batch_raw(self, qs, k, n_probes, pass_1=None):
         """Fast mode: raw float32 queries, normalisation / padding / rotation on the device
@@ -1281,38 +1282,26 @@ class DeviceIndex:
         the rescoring's exact squared distances beside the ids, complete when out_ptr's ids are
         (tk_index_query_batch_dev_dist).
         exclude_ptr: None, or a device buffer of nq int64: the row each query may not return, anything outside [0, N)
-        for none (tk_index_query_batch_dev_ex2); the library's until join() or done_event, like the others.
+        for none; the library's until join() or done_event, like the others.
         group_ptr: None, or a device buffer of nq int32: the group each query is restricted to, any entry < 0 for an
-        unrestricted query (tk_index_query_batch_dev_ex3); the caller's again after join() or done_event.
+        unrestricted query; the caller's again after join() or done_event.
         tags_ptr: None, or a device buffer of nq uint64: the tag mask each query is restricted by under tags_mode
-        ("any" / "all"), an entry of 0 for an unrestricted query (tk_index_query_batch_dev_ex4); the caller's again
-        after join() or done_event.
+        ("any" / "all"), an entry of 0 for an unrestricted query; the caller's again after join() or done_event.
         between_ptr: None, or a device buffer of nq x C x 2 int64 keys (query_ranges' array): the interval each query
-        is restricted to per value column, INT64_MIN / INT64_MAX for an unbounded end
-        (tk_index_query_batch_dev_ex5); the caller's again after join() or done_event."""
+        is restricted to per value column, INT64_MIN / INT64_MAX for an unbounded end; the caller's again after
+        join() or done_event.
+        A call with any of these four takes the library's one restricted entry point (tk_index_query_batch_dev_ex5,
+        NULL for the ones not given)."""
         if allowed is not None:
             if not isinstance(allowed, AllowSet):
                 raise TypeError("query_batch_dev: allowed= takes a prepared set (DeviceIndex.allow / IVF.allow)")
             allowed = self._allow_of(allowed)[0].handle
         L, ev = _lib.lib(), None if done_event is None else C.c_void_p(int(done_event))
-        if between_ptr is not None:
+        if exclude_ptr is not None or group_ptr is not None or tags_ptr is not None or between_ptr is not None:
             mode = tag_mode_of(tags_mode) if tags_ptr is not None else 0
             rc = L.tk_index_query_batch_dev_ex5(
                 self._h, allowed, exclude_ptr, group_ptr, tags_ptr, mode, between_ptr, qn_ptr, qpq_ptr, int(qpq_is_f64),
                 nq, int(k), int(n_probes), int(pass_1 or 0), out_ptr, dist_ptr, ev, stream)
-        elif tags_ptr is not None:
-            mode = tag_mode_of(tags_mode)
-            rc = L.tk_index_query_batch_dev_ex4(
-                self._h, allowed, exclude_ptr, group_ptr, tags_ptr, mode, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k),
-                int(n_probes), int(pass_1 or 0), out_ptr, dist_ptr, ev, stream)
-        elif group_ptr is not None:
-            rc = L.tk_index_query_batch_dev_ex3(
-                self._h, allowed, exclude_ptr, group_ptr, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes),
-                int(pass_1 or 0), out_ptr, dist_ptr, ev, stream)
-        elif exclude_ptr is not None:
-            rc = L.tk_index_query_batch_dev_ex2(
-                self._h, allowed, exclude_ptr, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes),
-                int(pass_1 or 0), out_ptr, dist_ptr, ev, stream)
         elif dist_ptr is not None:
             rc = L.tk_index_query_batch_dev_dist(
                 self._h, allowed, qn_ptr, qpq_ptr, int(qpq_is_f64), nq, int(k), int(n_probes), int(pass_1 or 0),
@@ -1646,9 +1635,7 @@ class IVF:
         self._dev = None
         self.data = data
         self.store = store
-        self.__dict__.pop("groups", None)               # (groups belong to the rows they were set for)
-        self.__dict__.pop("tags", None)                 # (tags too)
-        self.__dict__.pop("values", None)               # (and values)
+        self._forget_row_attrs()
         with timer(verbose, "Computing nearest clusters..."):
             if device:
                 nearest = self._nearest_on_device(data, n_probes)
@@ -1792,12 +1779,7 @@ class IVF:
             extra["list_columns"] = self.list_columns
         if self.store is not None:          # (the vectors are written unrounded: the upload rounds again, same bits)
             extra["store"] = self.store
-        if self.groups is not None:
-            extra["groups"] = self.groups
-        if self.tags is not None:
-            extra["tags"] = self.tags
-        if self.values is not None:
-            extra["values"] = self.values
+        extra.update((at.name, getattr(self, at.name)) for at in ROW_ATTRS if getattr(self, at.name) is not None)
         path = self._npz_path(path)
         np.savez(path, format_version=1, metric=self.metric, n_clusters=self.n_clusters,
                  use_kmeans=int(self.pq.use_kmeans), rotate_dim=-1 if self.pq.rotate_dim is None else int(self.pq.rotate_dim),
@@ -1839,12 +1821,9 @@ class IVF:
         # (files written before add() existed have no list_columns: add() recovers them)
         ivf.list_columns = z["list_columns"] if "list_columns" in z else None
         ivf.store = check_store(str(z["store"])) if "store" in z else None     # (files written before store= existed)
-        if "groups" in z:
-            ivf.groups = np.ascontiguousarray(z["groups"], dtype=np.int32)
-        if "tags" in z:
-            ivf.tags = np.ascontiguousarray(z["tags"], dtype=np.uint64)
-        if "values" in z:
-            ivf.values = np.ascontiguousarray(z["values"])
+        for at in ROW_ATTRS:
+            if at.name in z:
+                setattr(ivf, at.name, np.ascontiguousarray(z[at.name], dtype=at.dtype))
         return ivf
 
     def build_resident(self, N, d, seed, centres=None, sigma=1.0, verbose=False, n_probes=1, store=None):
@@ -1889,9 +1868,7 @@ class IVF:
         self.list_columns = dev.list_columns()
         self.data = ResidentData(dev)
         self.ids = self.pq_transformed_points = None
-        self.__dict__.pop("groups", None)               # (groups belong to the rows they were set for, as in build)
-        self.__dict__.pop("tags", None)
-        self.__dict__.pop("values", None)
+        self._forget_row_attrs()
         self._dev = dev
         return self
 
@@ -1914,24 +1891,7 @@ class IVF:
         d = self.data.shape[1]
         if X.ndim != 2 or X.shape[1] != d:
             raise AssertionError(f"IVF.add: X must have shape (n, {d}), got {X.shape}")
-        if self.groups is None and groups is not None:
-            raise ValueError("IVF.add: groups= on an index without groups (set_groups first)")
-        if self.groups is not None:
-            if groups is None:
-                raise ValueError("IVF.add: this index has groups (set_groups): pass the new rows' with groups=")
-            groups = group_ids(groups, len(X), "IVF.add: groups")
-        if self.tags is None and tags is not None:
-            raise ValueError("IVF.add: tags= on an index without tags (set_tags first)")
-        if self.tags is not None:
-            if tags is None:
-                raise ValueError("IVF.add: this index has tags (set_tags): pass the new rows' with tags=")
-            tags = tag_masks(tags, len(X), "IVF.add: tags")
-        if self.values is None and values is not None:
-            raise ValueError("IVF.add: values= on an index without values (set_values first)")
-        if self.values is not None:
-            if values is None:
-                raise ValueError("IVF.add: this index has values (set_values): pass the new rows' with values=")
-            values = self._new_values(values, len(X), "IVF.add: values")
+        new = self._new_row_attrs("add", len(X), dict(groups=groups, tags=tags, values=values), needed=True)
         if self.all_centers is None:
             raise AssertionError("IVF.add: the index has no all_centers (fit, or a file written with them)")
         if len(X) == 0:
@@ -1940,33 +1900,55 @@ class IVF:
             self._add_resident(X, verbose)
         else:
             self._add_host(X, verbose)
-        if groups is not None:          # (the device's cover the old rows only: set again for all)
-            self.groups = np.concatenate([self.groups, groups])
-            if self._dev is not None:
-                self._dev.set_groups(self.groups)
-        if tags is not None:
-            self.tags = np.concatenate([self.tags, tags])
-            if self._dev is not None:
-                self._dev.set_tags(self.tags)
-        if values is not None:
-            self.values = np.concatenate([self.values, values])
-            if self._dev is not None:
-                self._dev.set_values(self.values)
+        self._store_row_attrs(new, lambda old, rows: np.concatenate([old, rows]))
         return self
 
-    def _new_values(self, values, n, what):
-        """`values` for n rows of an index that has values: checked as set_values checks (value_keys), in the shape and
-        of the kind (ValueError) of IVF.values, converted to its dtype"""
-        a = np.asarray(values)
-        value_keys(a, n, what)
-        if a.shape[1:] != self.values.shape[1:]:
-            raise ValueError(f"{what}: shape (n,) + {self.values.shape[1:]} as the index's values, got {a.shape}")
-        if value_kind(a.dtype) != value_kind(self.values.dtype):
-            raise ValueError(f"{what}: {self.values.dtype} as the index's values, got {a.dtype}")
-        b = a.astype(self.values.dtype)
-        if value_kind(a.dtype) == "i" and a.size and not np.array_equal(b.astype(object), a.astype(object)):
-            raise ValueError(f"{what}: values that do not fit the index's {self.values.dtype}")
-        return b
+    # ---- the row attributes (ROW_ATTRS: groups, tags, values), one body for each thing done with all three ----
+    def _host_rows(self, at, x, n, what, like=None):
+        """The host copy of attribute `at` for n rows, from the caller's x: as the device takes it (at.rows), or where
+        the host keeps something else (values: the caller's array, checked; host_values) that — like the index's own."""
+        return at.rows(x, n, what) if at.host is None else at.host(x, n, what, like)
+
+    def _set_rows(self, at, x):
+        """set_groups / set_tags / set_values: x checked, handed to the device index where there is one, kept (a copy
+        wherever it shares memory with x); None clears."""
+        a = None if x is None else self._host_rows(at, x, len(self.data), f"IVF.set_{at.name}")
+        if self._dev is not None:                # (a list-sharded index raises here, before the host copy changes)
+            getattr(self._unsharded_device_index(), f"set_{at.name}")(a)
+        if a is None:
+            self.__dict__.pop(at.name, None)
+        else:
+            setattr(self, at.name, a.copy() if np.shares_memory(a, x) else a)
+        return self
+
+    def _forget_row_attrs(self):
+        """(a build: attributes belong to the rows they were set for)"""
+        for at in ROW_ATTRS:
+            self.__dict__.pop(at.name, None)
+
+    def _new_row_attrs(self, what, n, given, needed):
+        """The first half of add / update, before anything changes: `given` {name: the n new rows' attribute, or None}
+        against what the index has -> {name: host rows} of the ones given.  An attribute the index lacks is not taken;
+        `needed`: one it has must be given."""
+        new = {}
+        for at in ROW_ATTRS:
+            x, have = given[at.name], getattr(self, at.name)
+            if have is None and x is not None:
+                raise ValueError(f"IVF.{what}: {at.name}= on an index without {at.name} (set_{at.name} first)")
+            if needed and have is not None and x is None:
+                raise ValueError(f"IVF.{what}: this index has {at.name} (set_{at.name}): pass the new rows' with {at.name}=")
+            if x is not None:
+                new[at.name] = self._host_rows(at, x, n, f"IVF.{what}: {at.name}", like=have)
+        return new
+
+    def _store_row_attrs(self, new, merge):
+        """The second half: merge(the host copy, the new rows) is the host copy, and the device's — which covers the
+        old rows only — is set again for all."""
+        for at in ROW_ATTRS:
+            if at.name in new:
+                setattr(self, at.name, merge(getattr(self, at.name), new[at.name]))
+                if self._dev is not None:
+                    getattr(self._dev, f"set_{at.name}")(getattr(self, at.name))
 
     def _require_device_free(self, what="add", doing="adding rows to"):
         if self._dev is not None and _dev_is_sharded(self._dev):
@@ -2147,18 +2129,7 @@ class IVF:
         d = self.data.shape[1]
         if X.ndim != 2 or X.shape != (len(ids), d):
             raise AssertionError(f"IVF.update: X must have shape ({len(ids)}, {d}), got {X.shape}")
-        if groups is not None:
-            if self.groups is None:
-                raise ValueError("IVF.update: groups= on an index without groups (set_groups first)")
-            groups = group_ids(groups, len(X), "IVF.update: groups")
-        if tags is not None:
-            if self.tags is None:
-                raise ValueError("IVF.update: tags= on an index without tags (set_tags first)")
-            tags = tag_masks(tags, len(X), "IVF.update: tags")
-        if values is not None:
-            if self.values is None:
-                raise ValueError("IVF.update: values= on an index without values (set_values first)")
-            values = self._new_values(values, len(X), "IVF.update: values")
+        new = self._new_row_attrs("update", len(X), dict(groups=groups, tags=tags, values=values), needed=False)
         if self.all_centers is None:
             raise AssertionError("IVF.update: the index has no all_centers (fit, or a file written with them)")
         if len(ids) == 0:
@@ -2167,21 +2138,12 @@ class IVF:
             self._update_resident(ids, X, verbose)
         else:
             self._update_host(ids, X, verbose)
-        if groups is not None:
-            self.groups = self.groups.copy()
-            self.groups[ids] = groups
-            if self._dev is not None:
-                self._dev.set_groups(self.groups)
-        if tags is not None:
-            self.tags = self.tags.copy()
-            self.tags[ids] = tags
-            if self._dev is not None:
-                self._dev.set_tags(self.tags)
-        if values is not None:
-            self.values = self.values.copy()
-            self.values[ids] = values
-            if self._dev is not None:
-                self._dev.set_values(self.values)
+        def put(old, rows):
+            a = old.copy()
+            a[ids] = rows
+            return a
+
+        self._store_row_attrs(new, put)
         return self
 
     def _update_resident(self, ids, X, verbose):
@@ -2297,12 +2259,9 @@ class IVF:
     def device_index(self):
         if self._dev is None:
             dev = DeviceIndex(self)
-            if self.groups is not None:
-                dev.set_groups(self.groups)
-            if self.tags is not None:
-                dev.set_tags(self.tags)
-            if self.values is not None:
-                dev.set_values(self.values)
+            for at in ROW_ATTRS:
+                if getattr(self, at.name) is not None:
+                    getattr(dev, f"set_{at.name}")(getattr(self, at.name))
             self._dev = dev
         return self._dev
 
@@ -2311,45 +2270,21 @@ class IVF:
         [0, 2**31 - 1) — for the `group=` argument of query / query_batch; None clears.  TypeError for
         another kind of value, ValueError for another length or an id outside.  IVF.groups is the host copy (int32);
         save / load and pickling carry it."""
-        g = None if groups is None else group_ids(groups, len(self.data), "IVF.set_groups")
-        if self._dev is not None:                # (a list-sharded index raises here, before the host copy changes)
-            self._unsharded_device_index().set_groups(g)
-        if g is None:
-            self.__dict__.pop("groups", None)
-        else:
-            self.groups = g.copy() if g is groups else g
-        return self
+        return self._set_rows(GROUPS, groups)
 
     def set_tags(self, tags):
         """One 64-bit tag mask per row — categories, ACL principals: a 1-d integer array of length N, uint64 or any
         integer dtype with every value in [0, 2**64), bit t set = the row carries tag t, 0 = no tag — for the `tags=`
         argument of query / query_batch; None clears.  TypeError for another kind of value, ValueError
         for another length or a value outside.  IVF.tags is the host copy (uint64); save / load and pickling carry it."""
-        t = None if tags is None else tag_masks(tags, len(self.data), "IVF.set_tags")
-        if self._dev is not None:                # (a list-sharded index raises here, before the host copy changes)
-            self._unsharded_device_index().set_tags(t)
-        if t is None:
-            self.__dict__.pop("tags", None)
-        else:
-            self.tags = t.copy() if t is tags or np.shares_memory(t, tags) else t
-        return self
+        return self._set_rows(TAGS, tags)
 
     def set_values(self, values):
         """1 to 4 numeric columns per row — a timestamp, a price, a version: (N,) or (N, C) of ONE integer or floating
         dtype (float16 / 32 / 64) — for the `between=` argument of query / query_batch; None clears.
         TypeError for another kind of value, ValueError for another length, more than 4 columns, a NaN or a uint64
         above 2**63 - 1.  IVF.values is the host copy in the caller's dtype; save / load and pickling carry it."""
-        v = None
-        if values is not None:
-            v = np.array(values)                    # (a copy, in the caller's dtype)
-            value_keys(v, len(self.data), "IVF.set_values")
-        if self._dev is not None:                # (a list-sharded index raises here, before the host copy changes)
-            self._unsharded_device_index().set_values(v)
-        if v is None:
-            self.__dict__.pop("values", None)
-        else:
-            self.values = v
-        return self
+        return self._set_rows(VALUES, values)
 
     def _ranges(self, between, nq):
         """`between=` checked against IVF.values before anything runs (query_ranges): the keys the device takes"""
@@ -2411,24 +2346,13 @@ class IVF:
         assert self.data.shape[1] == q.shape[0]
         qn, qp = self._prepare(q[None, :])
         dev = self._unsharded_device_index()
-        if exclude is not None:
-            exclude = np.asarray(exclude).reshape(1)
-        if group is not None:
-            group = np.asarray(group).reshape(1)
-        if tags is not None:
-            tags = np.asarray(tags).reshape(1)
-        if return_distances:
-            ids, dist = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, return_distances=True,
-                                        exclude=exclude, group=group, tags=tags, tags_mode=tags_mode,
-                                        between=between)
-            out, dist = ids[0], dist[0]
-            if out[-1] == -1:
-                keep = out != -1
-                return out[keep], dist[keep]
-            return out, dist
-        out = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, exclude=exclude, group=group, tags=tags,
-                              tags_mode=tags_mode, between=between)[0]
-        return out[out != -1] if out[-1] == -1 else out
+        one = {w: None if x is None else np.asarray(x).reshape(1)
+               for w, x in (("exclude", exclude), ("group", group), ("tags", tags))}
+        got = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, return_distances=return_distances,
+                              tags_mode=tags_mode, between=between, **one)
+        out, dist = (got[0][0], got[1][0]) if return_distances else (got[0], None)
+        keep = out != -1 if out[-1] == -1 else slice(None)
+        return (out[keep], dist[keep]) if return_distances else out[keep]
 
     def query_rows(self, rows, k, n_probes=1, pass_1=None, *, exclude_self=True, allowed=None,
                    return_distances=False):
@@ -2509,31 +2433,22 @@ class IVF:
         between: (lo, hi), the inclusive interval of values (set_values) each query's rows must lie in, per column:
         each end None (unbounded), a number for every query, (nq,) for one column, (nq, C), or (C,) where nq != C
         (DESIGN §3.14); not with fast=True."""
-        if between is not None and fast:
-            raise NotImplementedError("IVF.query_batch: fast=True with between= is not supported; "
+        # what fast=True does not take: the first of these that is asked for is the one refused
+        asked = [word for word, given in (("between=", between is not None), ("tags=", tags is not None),
+                                          ("group=", group is not None), ("exclude=", exclude is not None),
+                                          ("return_distances=True", return_distances), ("allowed=", allowed is not None))
+                 if given]
+        if fast and asked:
+            if asked == ["allowed="]:       # (the one refusal that comes behind a list-sharded index's own)
+                self._unsharded_device_index()
+            raise NotImplementedError(f"IVF.query_batch: fast=True with {asked[0]} is not supported; "
                                       "use the exact default (fast=False)")
         if between is not None:
             self._ranges(between, len(qs))
-        if tags is not None and fast:
-            raise NotImplementedError("IVF.query_batch: fast=True with tags= is not supported; "
-                                      "use the exact default (fast=False)")
         if tags is not None:
             tag_mode_of(tags_mode)
-        if group is not None and fast:
-            raise NotImplementedError("IVF.query_batch: fast=True with group= is not supported; "
-                                      "use the exact default (fast=False)")
-        if exclude is not None and fast:
-            raise NotImplementedError("IVF.query_batch: fast=True with exclude= is not supported; "
-                                      "use the exact default (fast=False)")
-        if return_distances and fast:
-            raise NotImplementedError("IVF.query_batch: fast=True with return_distances=True is not supported; "
-                                      "use the exact default (fast=False)")
         self._unsharded_device_index()
-        if allowed is not None or return_distances or exclude is not None or group is not None or tags is not None \
-                or between is not None:
-            if fast:
-                raise NotImplementedError("IVF.query_batch: fast=True with allowed= is not supported; "
-                                          "use the exact default (fast=False)")
+        if asked:
             qs = np.array(qs, dtype=np.float32, order="C", copy=True)
             if exclude is not None and np.ndim(exclude) == 1 and len(exclude) != len(qs):
                 raise ValueError(f"exclude: one entry per query ({len(qs)}), got {len(exclude)}")
