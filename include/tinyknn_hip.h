@@ -829,6 +829,42 @@ int tk_index_query_batch_dev_ex5(tk_index *ix, const tk_allow *allow, const int6
                                  int64_t nq, int k, int n_probes, int pass_1, int64_t *out_ids_dev, void *out_dist_dev,
                                  void *done_event, void *stream);
 int tk_index_value_table(tk_index *ix, int64_t *info4);
+/* At most m rows of any one group among a query's answers ("the 10 nearest DOCUMENTS, not chunks": field collapsing,
+ * result diversification).  Groups are the ones tk_index_set_groups stores.  Everything up to the query's candidates is
+ * unchanged — probes, scans, restrictions, the heap of R = pass_1 or (n_probes + 1) k + 1 entries — so this extends the
+ * last lines of IVF.query, ivf.py:154-163: let c[0 .. nc) be the heap's ids with the -1 entries dropped, in heap order
+ * (ivf.py:154-155).  Where nc > k they are ranked by ascending exact squared distance, ties to the lower position in c
+ * (what bottom_k returns, ivf.py:160-163); where nc <= k by position (ivf.py:158-159).  That order is walked and a
+ * candidate is kept while fewer than m of its group have been kept, until k are kept — equivalently, a candidate is
+ * kept iff fewer than m candidates of its group rank before it.  The kept ids are returned in rank order, the row
+ * padded with -1 (distances: +inf), every returned id with its exact distance where distances are asked for.  A
+ * candidate's group is groups[id], a negative id meaning id + N as where its vector is fetched.
+ * per_group / per_group_dev: int32, nq entries, m per query; 0: no cap for that query (it returns what the call without
+ * the array returns).  The pool is the heap: with a small m a query can run out of groups before it has k ids — a
+ * larger pass_1 or n_probes widens it; nothing is widened here.
+ * tk_index_query_batch_ex6 / _dev_ex6: _ex5 with one more pointer, which may be NULL.  The host call checks per_group
+ * (an entry < 0: TK_ERR_ARG, nothing run) and passes an array of only zeros on as none.  The device call does not read
+ * per_group_dev on the host: an entry <= 0 there leaves its query uncapped.  per_group_dev belongs to the library
+ * until done_event or tk_index_join, like the other buffers.  _ex5 is this call without a cap array.
+ * Refused, nothing run: a cap array while no groups are set, or while they cover fewer rows than the index has
+ * (TK_ERR_STATE, as for a group array); a list-sharded index; a heap whose ranking does not fit the rescoring's 64 KiB
+ * of LDS beside the heap (R * 28 + 4 d + 32 bytes, float64 vectors R * 36 + 8 d + 32: TK_ERR_ARG).
+ * On the device the final rescoring alone changes: its capped kernels keep every candidate (id, distance, group — one
+ * 4-byte read per candidate from the groups by row id) at its rank in LDS and select from there.  The first capped
+ * call of a layout makes the group table as a call with a group array does (it synchronises the device).  A cap is not
+ * a restriction of the scans: a call with a cap alone takes the scan an unrestricted call takes.  Sub-batches and the
+ * pipelined mode as the _ex5 calls; two calls pair (tk_index_set_coalesce) only where both pass a cap array or neither
+ * does, and a call's answers do not depend on pipeline depth, pairing or sub-batching. */
+int tk_index_query_batch_ex6(tk_index *ix, const tk_allow *allow, const int64_t *exclude, const int32_t *group,
+                             const uint64_t *tags, int tag_mode, const int64_t *between, const int32_t *per_group,
+                             const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k, int n_probes,
+                             int pass_1, int64_t *out_ids, void *out_dist, int64_t *out_probes, int64_t *out_heap_idx,
+                             int32_t *out_heap_val);
+int tk_index_query_batch_dev_ex6(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
+                                 const int32_t *group_dev, const uint64_t *tags_dev, int tag_mode,
+                                 const int64_t *between_dev, const int32_t *per_group_dev, const float *q_dev,
+                                 const void *q_pq_dev, int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                                 int64_t *out_ids_dev, void *out_dist_dev, void *done_event, void *stream);
 /* hipStream_t on which to copy a batch's inputs in (pipelined mode: the index's front stream,
  * where the batch's first kernel runs; NULL: use the stream the batch is enqueued on) */
 void *tk_index_input_stream(tk_index *ix);

@@ -1222,8 +1222,17 @@ int stage_back(tk_index *ix, Work &w, const float *q_dev, int64_t q0, int64_t nq
     }
     TRY(pf.mark(st));
     // 4. strip sentinels, exact rescoring                   ivf.py:154-163
+    // (a capped batch: the kernels that walk the ranking and keep at most per_group[q] rows of any group, cap_select.h)
+    TkCap cap;
+    if (r.capped()) {
+        cap.groups = ix->groups.by_row.as<int32_t>();
+        cap.m = r.per_group ? r.per_group + q0 : nullptr;
+        cap.m_b = (const int32_t *)r.per_group2.b;
+        cap.n_a = r.per_group2.n_a - q0;
+    }
     tk_launch_rescore(q_dev, 0, ix->d, ix->data.p, ix->data_dtype, ix->N, w.heap_idx.as<int64_t>(), p.R, nq, k, 1,
-                      out_dev, nullptr, st, ix->opt_rescore_form, q2, out2, nullptr, dist_dev, dist2);
+                      out_dev, nullptr, st, ix->opt_rescore_form, q2, out2, nullptr, dist_dev, dist2,
+                      r.capped() ? &cap : nullptr);
     TRY(pf.mark(st));
     return TK_OK;
 }
@@ -1643,6 +1652,11 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
     ARGCHECK(r.tag_mode == 0 || r.tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
     if (!r.tags) r.tag_mode = 0;
     r.cols = r.between ? value_columns(ix) : 0;
+    if (r.per_group) {      // (the capped rescoring keeps every candidate by rank beside the uncapped forms' LDS)
+        const size_t dsz = ix->data_dtype == TK_DATA_F64 ? 8 : 4;
+        ARGCHECK((size_t)p.R * (8 + dsz) + (size_t)ix->d * dsz + 32 + cap_lds_bytes(p.R, dsz) <= 64 * 1024,
+                 "per_group: the heap and its ranking do not fit 64 KiB of LDS (a smaller pass_1 / n_probes / k)");
+    }
     if (r.allow) {
         ARGCHECK(r.allow->ix == ix, "the allowed set belongs to another index");
         if (r.allow->lists_gen != ix->lists_gen)
@@ -1893,13 +1907,22 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
             ranged = r.between[2 * i] != INT64_MIN || r.between[2 * i + 1] != INT64_MAX;
         if (!ranged) r.between = nullptr;
     }
+    // per_group: the same (an array of only zeros caps nothing: the kernels an uncapped call takes)
+    bool capped = false;
+    if (r.per_group)
+        for (int64_t i = 0; i < nq; i++) {
+            ARGCHECK(r.per_group[i] >= 0, "per_group: entries must be a count >= 0 (0: no cap)");
+            capped = capped || r.per_group[i] > 0;
+        }
+    if (!capped) r.per_group = nullptr;
+    if (r.per_group) ARGCHECK(!ix->sharded, "list-sharded index: row groups are not supported");
     ARGCHECK(!(out_probes || out_heap_idx || out_heap_val) || nq <= sub_batch(p),
              "debug outputs need the batch to fit one sub-batch");
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     TRY(ix->q.ensure((size_t)nq * ix->d * 4));
     TRY(ix->qpq.ensure((size_t)nq * ix->dq * esz));
-    DevBuf outbuf, distbuf, exbuf, rowbuf, grbuf, tgbuf, bwbuf;  // separate from the sub-batch `out` workspace
-    BufRelease rel{{&outbuf, &distbuf, &exbuf, &rowbuf, &grbuf, &tgbuf, &bwbuf}};
+    DevBuf outbuf, distbuf, exbuf, rowbuf, grbuf, tgbuf, bwbuf, pgbuf;  // separate from the sub-batch `out` workspace
+    BufRelease rel{{&outbuf, &distbuf, &exbuf, &rowbuf, &grbuf, &tgbuf, &bwbuf, &pgbuf}};
     // a per-query host array (or NULL) as the device array the call below names
     const auto upload = [&](auto *&arr, DevBuf &buf) -> int {
         if (!arr) return TK_OK;
@@ -1914,6 +1937,7 @@ static int query_batch_host(tk_index *ix, const float *q, const void *q_pq, int 
     TRY(upload(r.exclude, exbuf));
     TRY(upload(r.group, grbuf));
     TRY(upload(r.tags, tgbuf));
+    TRY(upload(r.per_group, pgbuf));
     if (r.between) {
         const size_t bytes = (size_t)nq * r.cols * 16;
         TRY(bwbuf.ensure(bytes));
@@ -2070,8 +2094,8 @@ extern "C" int tk_index_query_batch_ex5(tk_index *ix, const tk_allow *allow, con
                                         int64_t nq, int k, int n_probes, int pass_1, int64_t *out_ids, void *out_dist,
                                         int64_t *out_probes, int64_t *out_heap_idx, int32_t *out_heap_val)
 {
-    return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
-                            out_heap_val, {allow, exclude, group, tags, tag_mode, between}, out_dist);
+    return tk_index_query_batch_ex6(ix, allow, exclude, group, tags, tag_mode, between, nullptr, q, q_pq, q_pq_is_f64, nq,
+                                    k, n_probes, pass_1, out_ids, out_dist, out_probes, out_heap_idx, out_heap_val);
 }
 
 extern "C" int tk_index_query_batch_dev_ex5(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
@@ -2080,10 +2104,36 @@ extern "C" int tk_index_query_batch_dev_ex5(tk_index *ix, const tk_allow *allow,
                                             int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
                                             int64_t *out_ids_dev, void *out_dist_dev, void *done_event, void *stream)
 {
+    return tk_index_query_batch_dev_ex6(ix, allow, exclude_dev, group_dev, tags_dev, tag_mode, between_dev, nullptr, q_dev,
+                                        q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, out_dist_dev,
+                                        done_event, stream);
+}
+
+// ... and one cap per query on the rows of any one group among its answers (cap_select.h, tinyknn_hip.h): _ex5 with one
+// more pointer — extends IVF.query, ivf.py:154-163
+extern "C" int tk_index_query_batch_ex6(tk_index *ix, const tk_allow *allow, const int64_t *exclude,
+                                        const int32_t *group, const uint64_t *tags, int tag_mode,
+                                        const int64_t *between, const int32_t *per_group, const float *q,
+                                        const void *q_pq, int q_pq_is_f64, int64_t nq, int k, int n_probes, int pass_1,
+                                        int64_t *out_ids, void *out_dist, int64_t *out_probes, int64_t *out_heap_idx,
+                                        int32_t *out_heap_val)
+{
+    return query_batch_host(ix, q, q_pq, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids, out_probes, out_heap_idx,
+                            out_heap_val, {allow, exclude, group, tags, tag_mode, between, 0, per_group}, out_dist);
+}
+
+extern "C" int tk_index_query_batch_dev_ex6(tk_index *ix, const tk_allow *allow, const int64_t *exclude_dev,
+                                            const int32_t *group_dev, const uint64_t *tags_dev, int tag_mode,
+                                            const int64_t *between_dev, const int32_t *per_group_dev,
+                                            const float *q_dev, const void *q_pq_dev, int q_pq_is_f64, int64_t nq,
+                                            int k, int n_probes, int pass_1, int64_t *out_ids_dev, void *out_dist_dev,
+                                            void *done_event, void *stream)
+{
     IXLOCK(ix);
     return query_batch_dev_impl(ix, q_dev, q_pq_dev, q_pq_is_f64, nq, k, n_probes, pass_1, out_ids_dev, nullptr,
                                 (hipEvent_t)done_event, stream,
-                                {allow, exclude_dev, group_dev, tags_dev, tag_mode, between_dev}, out_dist_dev);
+                                {allow, exclude_dev, group_dev, tags_dev, tag_mode, between_dev, 0, per_group_dev},
+                                out_dist_dev);
 }
 
 // the stored rows `rows` as queries, each leaving itself out where exclude_self

@@ -368,18 +368,22 @@ struct TkCallRestrict {
     int tag_mode = 0;
     const int64_t *between = nullptr;
     int cols = 0;
+    // Not a restriction of what the scans see but a shape of what comes back: at most per_group[q] rows of any group
+    // among query q's answers, 0 for no cap (cap_select.h; int32 per query).  It reads the groups by row id only.
+    const int32_t *per_group = nullptr;
     // the call's rows from row o on
     TkCallRestrict at(int64_t o) const
     {
         return {allow, exclude ? exclude + o : nullptr, group ? group + o : nullptr, tags ? tags + o : nullptr, tag_mode,
-                between ? between + o * 2 * cols : nullptr, cols};
+                between ? between + o * 2 * cols : nullptr, cols, per_group ? per_group + o : nullptr};
     }
     // Join rule: two calls run as one batch (coalesce_call) with the same allowed set, both grouped or neither (the
-    // two kinds take different scans: exact_scan), both tagged in one mode or neither (one mode per launch), both ranged or neither.
+    // two kinds take different scans: exact_scan), both tagged in one mode or neither (one mode per launch), both ranged or neither,
+    // both capped or neither (the two kinds take different rescoring kernels).
     bool joins(const TkCallRestrict &o) const
     {
         return allow == o.allow && !group == !o.group && !tags == !o.tags && (!tags || tag_mode == o.tag_mode) &&
-               !between == !o.between;
+               !between == !o.between && !per_group == !o.per_group;
     }
     // Table rule: what the passes read exists before the call's first launch (each made once per layout of the lists,
     // synchronising the device; TK_ERR_STATE where the index has no groups / tags / values for every row).  Defined below.
@@ -395,15 +399,19 @@ struct TkRestrict {
     const int32_t *group = nullptr;
     const uint64_t *tags = nullptr;
     const int64_t *between = nullptr;
-    TkSecond exclude2, group2, tags2, between2;
+    const int32_t *per_group = nullptr;
+    TkSecond exclude2, group2, tags2, between2, per_group2;
     TkRestrict() = default;
     // a: the first call; b (or NULL: one call): the second, whose rows start at batch row n_a
     TkRestrict(const TkCallRestrict &a, const TkCallRestrict *b = nullptr, int64_t n_a = 0)
         : allow(a.allow), tag_mode(a.tag_mode), exclude(a.exclude), group(a.group), tags(a.tags),
-          between(a.between)
+          between(a.between), per_group(a.per_group)
     {
         if (b) exclude2 = {b->exclude, n_a}, group2 = {b->group, n_a}, tags2 = {b->tags, n_a}, between2 = {b->between, n_a};
+        if (b) per_group2 = {b->per_group, n_a};
     }
+    // the final rescoring caps its answers per group; no pass, and the scan an uncapped batch takes (not in any())
+    bool capped() const { return per_group || per_group2.b; }
     bool excludes() const { return exclude || exclude2.b; }
     bool grouped() const { return group || group2.b; }
     bool tagged() const { return tags || tags2.b; }
@@ -518,7 +526,7 @@ int value_table_ensure(tk_index *ix);       // between.hip
 inline int TkCallRestrict::ensure_tables(tk_index *ix, int64_t nq) const
 {
     if (exclude && nq > 0) TRY(row_pos_ensure(ix));
-    if (group && nq > 0) TRY(group_table_ensure(ix));
+    if ((group || per_group) && nq > 0) TRY(group_table_ensure(ix));
     if (tags && nq > 0) TRY(tag_table_ensure(ix));
     if (between && nq > 0) TRY(value_table_ensure(ix));
     return TK_OK;

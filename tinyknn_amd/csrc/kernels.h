@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "cap_select.h"
 
 #define TK_ORDER_SSE 0
 #define TK_ORDER_AVX 1
@@ -333,11 +334,14 @@ struct TkSlotsOut {
 // is float64, else float32), +inf beside a -1; rows the heap order keeps (<= k candidates) get theirs too.  dist2.b:
 // the second call's own buffer (its rows from out2.n_a on; NULL: that call wants none).  With either, the
 // distance-writing forms of the kernels run and `slots` is ignored.
+// cap (or NULL; the index's final stage alone passes one): at most cap->m[query] rows of any group per query
+// (cap_select.h) — the capped kernels run, with or without distances, `slots` is ignored, and a row may end in -1
+// (out_count: the ids kept).  Their LDS is the uncapped forms' plus cap_lds_bytes(R, size of a distance).
 int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int rows_dtype,
                       int64_t n_rows, const int64_t *cand, int R, int64_t nq, int k, int strip,
                       int64_t *out, int *out_count, hipStream_t s, int form = 2, TkSecond q2 = TkSecond(),
                       TkSecond out2 = TkSecond(), const TkSlotsOut *slots = nullptr, void *dist = nullptr,
-                      TkSecond dist2 = TkSecond());
+                      TkSecond dist2 = TkSecond(), const TkCap *cap = nullptr);
 
 // probes (nq, kc) list ids -> per-slot scan descriptors; pair_count (n_lists, zeroed, or
 // NULL) receives the number of (query, slot) pairs per list — with `owner` (n_lists ranks,

@@ -66,25 +66,40 @@ __device__ __forceinline__ T sqdist_row(const TY *__restrict__ y, const T *xs, i
     return acc[0] + acc[1 % L];
 }
 
+// A wave-uniform value of the capped epilogue made HERE and kept in VECTOR registers (no instruction is emitted).  The
+// capped kernels carry four more arguments than the distance forms, which use 97 of the 102 scalar registers: left to
+// itself the compiler keeps every argument a per-query pointer is made of alive through the sums and, in the staged
+// kernels, parks 4 scalars in vector lanes.  The epilogue uses these values per lane anyway (store addresses, a
+// gather's base, a compare).
+#define HELD(x) asm volatile("" : "+v"(x))
+
 // LDS: cand[R] (int64) | dist[R] (T) | x[d] (T)
 // DIST: also write the distance of every id written to out_d (second call of a pair: out_d_b; either may be NULL),
 // +inf beside a -1; where the heap holds <= k ids (no rescoring) their rows are read for it.  The ids-only kernels
 // below are this body with DIST = false, unchanged.
-template <typename T, typename TY, typename TX, bool DIST>
+// CAP (per_group=, cap_select.h): every candidate goes to its rank in LDS behind x[] — id | distance | group, the
+// group read by the row id the vector is fetched by — and cap_select writes the row; where the heap holds <= k ids the
+// rank is the position.  LDS: ... | x[d] | up to 8 bytes of padding | CapRanked<T>(R)
+template <typename T, typename TY, typename TX, bool DIST, bool CAP = false>
 __device__ __forceinline__ void rescore_body(unsigned char *smem, const TX *__restrict__ q, int d,
                                              const TY *__restrict__ rows, int64_t n_rows,
                                              const int64_t *__restrict__ cand, int R, int k, int strip,
                                              int64_t *__restrict__ out, int *__restrict__ out_count,
                                              const TX *__restrict__ q_b, int64_t q_na, int64_t *__restrict__ out_b,
-                                             int64_t out_na, T *__restrict__ out_d, T *__restrict__ out_d_b)
+                                             int64_t out_na, T *__restrict__ out_d, T *__restrict__ out_d_b,
+                                             const TkCap &cap = TkCap())
 {
     int64_t *cs = (int64_t *)smem;
     T *ds = (T *)(smem + (size_t)R * 8);
     T *xs = ds + R;
+    const CapRanked<T> by(CAP ? smem + (((size_t)R * 8 + ((size_t)R + d) * sizeof(T) + 7) & ~(size_t)7) : nullptr, R);
     __shared__ int s_count;
     const int tid = threadIdx.x;
     const int64_t qi = blockIdx.x;
     const int64_t *c = cand + qi * R;
+    unsigned capm = 0;
+    const int32_t *groups = CAP ? cap.groups : nullptr;     // (the epilogue's scalars: read here, kept in vector registers)
+    if (CAP) capm = cap_of(cap, qi);
 
     const TX *qrow = (q_b && qi >= q_na) ? q_b + (qi - q_na) * d : q + qi * d;   // second call of a pair
     for (int t = tid; t < d; t += blockDim.x) xs[t] = (T)qrow[t];
@@ -108,6 +123,26 @@ __device__ __forceinline__ void rescore_body(unsigned char *smem, const TX *__re
     int64_t *o = second ? out_b + (qi - out_na) * k : out + qi * k;
     T *od = nullptr;
     if (DIST) od = second ? (out_d_b ? out_d_b + (qi - out_na) * k : nullptr) : (out_d ? out_d + qi * k : nullptr);
+    int *oc = nullptr;
+    if (CAP) {      // the query's own pointers, made here: the arguments they come from need not outlive the sums
+        oc = out_count ? out_count + qi : nullptr;
+        HELD(o);
+        HELD(od);
+        HELD(oc);
+        HELD(groups);
+        HELD(capm);
+    }
+    if (CAP && nc <= k) {       // heap order: rank = position
+        for (int t = tid; t < nc; t += blockDim.x) {
+            int64_t id = cs[t];
+            by.id[t] = id;
+            if (id < 0) id += n_rows;
+            by.group[t] = groups[id];
+            if (od) by.dist[t] = sqdist_row<T, TY>(rows + id * (int64_t)d, xs, d);
+        }
+        cap_select(by, nc, k, capm, o, od, oc);
+        return;
+    }
     if (nc <= k) {  // ivf.py:158-159 / fast_pq.py:307-308: heap order, no rescoring
         for (int t = tid; t < k; t += blockDim.x) o[t] = t < nc ? cs[t] : -1;
         if (tid == 0 && out_count) out_count[qi] = nc;
@@ -138,10 +173,19 @@ __device__ __forceinline__ void rescore_body(unsigned char *smem, const TX *__re
             const T du = ds[u];
             rank += (du < dv) || (du == dv && u < t);
         }
-        if (rank < k) {
+        if (CAP) {
+            int64_t id = cs[t];
+            by.id[rank] = id;
+            by.dist[rank] = dv;
+            by.group[rank] = groups[id < 0 ? id + n_rows : id];
+        } else if (rank < k) {
             o[rank] = cs[t];
             if (DIST && od) od[rank] = dv;
         }
+    }
+    if (CAP) {
+        cap_select(by, nc, k, capm, o, od, oc);
+        return;
     }
     if (tid == 0 && out_count) out_count[qi] = k;
 }
@@ -336,7 +380,9 @@ __device__ __forceinline__ void slots_epilogue(const TkSlotsOut &so, int64_t qi,
 // LDS: cand[R] (int64) | row offset[R] (int64) | dist[R] | x[d] | tile[TILE + 1 spare][stride] | have_slots: the
 // k results (int64)
 // DIST as rescore_body (the short-heap branch reads its rows with sqdist_row: the same summation as sqdist_row_lds)
-template <typename TY, int TILE, bool DIST>
+// CAP as rescore_body: both rankings and the short-heap branch leave every candidate at its rank in CapRanked<float>(R),
+// which lies where the fused form keeps its k results (a capped launch writes no descriptors), and cap_select writes.
+template <typename TY, int TILE, bool DIST, bool CAP = false>
 __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const float *__restrict__ q, int d,
                                                     const TY *__restrict__ rows, int64_t n_rows,
                                                     const int64_t *__restrict__ cand, int R, int k, int strip,
@@ -344,7 +390,7 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
                                                     int stride, const float *__restrict__ q_b, int64_t q_na,
                                                     int64_t *__restrict__ out_b, int64_t out_na,
                                                     const TkSlotsOut *__restrict__ so_dev, float *__restrict__ out_d,
-                                                    float *__restrict__ out_d_b)
+                                                    float *__restrict__ out_d_b, const TkCap &cap = TkCap())
 {
     typedef typename RowPiece<TY>::type P;
     typedef typename HalfPiece<P>::type H;
@@ -354,9 +400,16 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
     float *ds = (float *)(smem + (size_t)R * 16);
     float *xs = ds + ((R + 3) & ~3);
     P *tile = (P *)(xs + ((d + 3) & ~3));                // 16-byte aligned
+    constexpr int PER16 = 16 / (int)sizeof(P);
+    // behind the tile rounded up to 16 bytes: have_slots, the k results in order; CAP, the candidates by rank
+    unsigned char *const behind = (unsigned char *)(tile + (((TILE + 1) * stride + PER16 - 1) & ~(PER16 - 1)));
+    const CapRanked<float> by(behind, R);
     const int tid = threadIdx.x;
     const int64_t qi = blockIdx.x;
     const int64_t *c = cand + qi * R;
+    unsigned capm = 0;
+    const int32_t *groups = CAP ? cap.groups : nullptr;     // (the epilogue's scalars: read here, kept in vector registers)
+    if (CAP) capm = cap_of(cap, qi);
     const float *qrow = (q_b && qi >= q_na) ? q_b + (qi - q_na) * d : q + qi * d;   // second call of a pair
     for (int t = tid; t < d; t += 64) xs[t] = qrow[t];
     // ordered compaction of the candidate ids (ivf.py:154-155 drops -1)
@@ -381,6 +434,26 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
     int64_t *o = second ? out_b + (qi - out_na) * k : out + qi * k;
     float *od = nullptr;
     if (DIST) od = second ? (out_d_b ? out_d_b + (qi - out_na) * k : nullptr) : (out_d ? out_d + qi * k : nullptr);
+    int *oc = nullptr;
+    if (CAP) {      // the query's own pointers, made here: the arguments they come from need not outlive the sums
+        oc = out_count ? out_count + qi : nullptr;
+        HELD(o);
+        HELD(od);
+        HELD(oc);
+        HELD(groups);
+        HELD(capm);
+    }
+    if (CAP && nc <= k) {       // heap order: rank = position
+        for (int t = tid; t < nc; t += 64) {
+            int64_t id = cs[t];
+            by.id[t] = id;
+            if (id < 0) id += n_rows;
+            by.group[t] = groups[id];
+            if (od) by.dist[t] = sqdist_row<float, TY>(rows + id * (int64_t)d, xs, d);
+        }
+        cap_select(by, nc, k, capm, o, od, oc);
+        return;
+    }
     if (nc <= k) {  // ivf.py:158-159 / fast_pq.py:307-308: heap order, no rescoring
         for (int t = tid; t < k; t += 64) o[t] = t < nc ? cs[t] : -1;
         if (tid == 0 && out_count) out_count[qi] = nc;
@@ -448,9 +521,7 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
         }
         __syncthreads();
     }
-    // have_slots: the k results in order, behind the tile rounded up to 16 bytes
-    constexpr int PER16 = 16 / (int)sizeof(P);
-    int64_t *ps = (int64_t *)(tile + (((TILE + 1) * stride + PER16 - 1) & ~(PER16 - 1)));
+    int64_t *ps = (int64_t *)behind;
     // rank by counting: a lane keeps its values (t = tid, tid + 64, ...: at most four, R <= 256) in registers and
     // walks ds[] once with the strict comparison alone; beyond nc it holds -inf, which nothing is below
     float dv[4];
@@ -468,7 +539,14 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int t = tid + 64 * j;
-            if (t < nc && cnt[j] < k) {
+            if (CAP) {
+                if (t < nc) {
+                    const int64_t id = cs[t];
+                    by.id[cnt[j]] = id;
+                    by.dist[cnt[j]] = dv[j];
+                    by.group[cnt[j]] = groups[id < 0 ? id + n_rows : id];
+                }
+            } else if (t < nc && cnt[j] < k) {
                 o[cnt[j]] = cs[t];
                 if (DIST && od) od[cnt[j]] = dv[j];
                 if (have_slots) ps[cnt[j]] = cs[t];
@@ -482,12 +560,21 @@ __device__ __forceinline__ void rescore_staged_body(unsigned char *smem, const f
                 const float du = ds[u];
                 rank += (du < dvt) || (du == dvt && u < t);
             }
-            if (rank < k) {
+            if (CAP) {
+                const int64_t id = cs[t];
+                by.id[rank] = id;
+                by.dist[rank] = dvt;
+                by.group[rank] = groups[id < 0 ? id + n_rows : id];
+            } else if (rank < k) {
                 o[rank] = cs[t];
                 if (DIST && od) od[rank] = dvt;
                 if (have_slots) ps[rank] = cs[t];
             }
         }
+    }
+    if (CAP) {
+        cap_select(by, nc, k, capm, o, od, oc);
+        return;
     }
     if (tid == 0 && out_count) out_count[qi] = k;
     if (have_slots) {
@@ -579,6 +666,49 @@ __global__ __launch_bounds__(128) void rescore_half_distances_kernel(const float
                                                out_b, out_na, out_d, out_d_b);
 }
 
+// The capped forms (per_group=): the two bodies with CAP, one kernel per form, the distance pointers NULL for ids alone.
+// (Names of their own: the resource tests find the kernels above by substrings of theirs, the half ones by the row
+// type in the mangled name — so the row type is named here by its code, ROWS = TK_DATA_F32 / _F64 / _F16 as
+// tk_launch_rescore's rows_dtype, and the rows come in untyped.)
+template <int ROWS> struct RowsOf;
+template <> struct RowsOf<0> { typedef float type; };
+template <> struct RowsOf<1> { typedef double type; };
+template <> struct RowsOf<2> { typedef _Float16 type; };
+template <typename TY> constexpr int rows_code()
+{
+    return std::is_same<TY, _Float16>::value ? 2 : (std::is_same<TY, double>::value ? 1 : 0);
+}
+
+template <typename T, int ROWS, typename TX>
+__global__ __launch_bounds__(128) void capped_rows_kernel(const TX *__restrict__ q, int d, const void *__restrict__ rows,
+                                                          int64_t n_rows, const int64_t *__restrict__ cand, int R, int k,
+                                                          int strip, int64_t *__restrict__ out,
+                                                          int *__restrict__ out_count, const TX *__restrict__ q_b,
+                                                          int64_t q_na, int64_t *__restrict__ out_b, int64_t out_na,
+                                                          T *__restrict__ out_d, T *__restrict__ out_d_b, const TkCap cap)
+{
+    typedef typename RowsOf<ROWS>::type TY;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rescore_body<T, TY, TX, true, true>(smem, q, d, (const TY *)rows, n_rows, cand, R, k, strip, out, out_count, q_b,
+                                        q_na, out_b, out_na, out_d, out_d_b, cap);
+}
+
+template <int ROWS, int TILE>
+__global__ __launch_bounds__(64) void capped_tile_kernel(const float *__restrict__ q, int d, const void *__restrict__ rows,
+                                                         int64_t n_rows, const int64_t *__restrict__ cand, int R, int k,
+                                                         int strip, int64_t *__restrict__ out,
+                                                         int *__restrict__ out_count, int stride,
+                                                         const float *__restrict__ q_b, int64_t q_na,
+                                                         int64_t *__restrict__ out_b, int64_t out_na,
+                                                         float *__restrict__ out_d, float *__restrict__ out_d_b,
+                                                         const TkCap cap)
+{
+    typedef typename RowsOf<ROWS>::type TY;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    rescore_staged_body<TY, TILE, true, true>(smem, q, d, (const TY *)rows, n_rows, cand, R, k, strip, out, out_count,
+                                              stride, q_b, q_na, out_b, out_na, nullptr, out_d, out_d_b, cap);
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------
 // One call as tk_launch_rescore received it; a launcher casts the pointers to the types it was chosen for.
 struct RescoreCall {
@@ -592,6 +722,7 @@ struct RescoreCall {
     TkSecond q2, out2;
     void *dist, *dist_b;    // want_d: where the distances go (either may be null)
     bool want_d;
+    const TkCap *cap;       // per_group=: the capped kernels (or NULL)
 };
 
 // the kernels by row type
@@ -616,7 +747,11 @@ static void launch_rows(const RescoreCall &c)
     const size_t lds = (size_t)c.R * 8 + ((size_t)c.R + c.d) * sizeof(T) + 16;
     const TX *q = (const TX *)c.q, *q_b = (const TX *)c.q2.b;
     const TY *rows = (const TY *)c.rows;
-    if (c.want_d)
+    if (c.cap)      // (the candidates by rank behind x[], 8-byte aligned)
+        hipLaunchKernelGGL((capped_rows_kernel<T, rows_code<TY>(), TX>), grid, block,
+                           ((lds - 16 + 7) & ~(size_t)7) + cap_lds_bytes(c.R, sizeof(T)), c.s, q, c.d, c.rows, c.n_rows, c.cand, c.R, c.k, c.strip, c.out, c.out_count, q_b, c.q2.n_a,
+                           (int64_t *)c.out2.b, c.out2.n_a, (T *)c.dist, (T *)c.dist_b, *c.cap);
+    else if (c.want_d)
         hipLaunchKernelGGL((rows_dist_kernel<T, TY, TX>()), grid, block, lds, c.s, q, c.d, rows, c.n_rows, c.cand, c.R,
                            c.k, c.strip, c.out, c.out_count, q_b, c.q2.n_a, (int64_t *)c.out2.b, c.out2.n_a,
                            (T *)c.dist, (T *)c.dist_b);
@@ -631,7 +766,11 @@ static void launch_staged_tile(const RescoreCall &c, size_t lds, int stride, con
     const dim3 grid((unsigned)c.nq), block(64);
     const float *q = (const float *)c.q, *q_b = (const float *)c.q2.b;
     const TY *rows = (const TY *)c.rows;
-    if (c.want_d)
+    if (c.cap)
+        hipLaunchKernelGGL((capped_tile_kernel<rows_code<TY>(), TILE>), grid, block, lds, c.s, q, c.d, c.rows, c.n_rows, c.cand, c.R,
+                           c.k, c.strip, c.out, c.out_count, stride, q_b, c.q2.n_a, (int64_t *)c.out2.b, c.out2.n_a,
+                           (float *)c.dist, (float *)c.dist_b, *c.cap);
+    else if (c.want_d)
         hipLaunchKernelGGL(staged_dist_kernel<TILE>(rows), grid, block, lds, c.s, q, c.d, rows, c.n_rows, c.cand, c.R,
                            c.k, c.strip, c.out, c.out_count, stride, q_b, c.q2.n_a, (int64_t *)c.out2.b, c.out2.n_a,
                            (float *)c.dist, (float *)c.dist_b);
@@ -661,10 +800,11 @@ static int launch_float_sums(const RescoreCall &c, int form, const TkSlotsOut *s
         const int tile_rows = staged == 2 ? 32 : 64;
         const bool fuse = slots != nullptr && c.k <= 64;        // (slots: a DEVICE copy of the structure)
         const size_t tile_bytes = (size_t)(tile_rows + 1) * stride * sizeof(typename RowPiece<TY>::type);
-        // ids and resolved row offsets (8 bytes each per candidate) | distances | query | tile | fused: the k results
+        // ids and resolved row offsets (8 bytes each per candidate) | distances | query | tile | fused: the k results;
+        // capped: the candidates by rank
         const size_t lds = (size_t)c.R * 16 +
                            (size_t)(((c.R + 3) & ~3) + ((c.d + 3) & ~3)) * 4 + ((tile_bytes + 15) & ~(size_t)15) +
-                           (fuse ? (size_t)c.k * 8 : 0);
+                           (fuse ? (size_t)c.k * 8 : 0) + (c.cap ? cap_lds_bytes(c.R, 4) : 0);
         if (lds <= 64 * 1024) {
             if (tile_rows == 32) launch_staged_tile<TY, 32>(c, lds, stride, fuse ? slots : nullptr);
             else launch_staged_tile<TY, 64>(c, lds, stride, fuse ? slots : nullptr);
@@ -679,13 +819,14 @@ static int launch_float_sums(const RescoreCall &c, int form, const TkSlotsOut *s
 int tk_launch_rescore(const void *q, int q_is_f64, int d, const void *rows, int rows_dtype,
                       int64_t n_rows, const int64_t *cand, int R, int64_t nq, int k, int strip,
                       int64_t *out, int *out_count, hipStream_t s, int form, TkSecond q2, TkSecond out2,
-                      const TkSlotsOut *slots, void *dist, TkSecond dist2)
+                      const TkSlotsOut *slots, void *dist, TkSecond dist2, const TkCap *cap)
 {
     if (nq == 0 || k == 0) return 0;
     const bool want_d = dist != nullptr || dist2.b != nullptr;
-    if (want_d) slots = nullptr;                // (the descriptors' caller asks for no distances)
+    if (want_d || cap) slots = nullptr;         // (the descriptors' caller asks for no distances and no cap)
     void *dist_b = out2.b ? const_cast<void *>(dist2.b) : nullptr;     // (rows of the second call: out2.n_a on)
-    const RescoreCall c = {q, rows, d, R, k, strip, n_rows, nq, cand, out, out_count, s, q2, out2, dist, dist_b, want_d};
+    const RescoreCall c = {q, rows, d, R, k, strip, n_rows, nq, cand, out, out_count, s, q2, out2, dist, dist_b, want_d,
+                           cap};
     if (rows_dtype == 2)                        // half vectors: float32 queries only (the index's final stage)
         return q_is_f64 ? -1 : launch_float_sums<_Float16>(c, form, slots);
     const int rows_is_f64 = rows_dtype == 1;

@@ -219,6 +219,21 @@ def query_groups(group, nq):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def query_caps(per_group, nq):
+    """The int32 array a `per_group=` argument is: a non-negative int for every query, or a 1-d integer array with one
+    entry per query; each the most rows of any one group the query may return, 0 for no cap."""
+    a = np.asarray(per_group)
+    if a.dtype == np.bool_ or not (a.size == 0 or np.issubdtype(a.dtype, np.integer)) or a.ndim > 1:
+        raise TypeError("per_group: an int, or a 1-d integer array with one count (or 0) per query")
+    if a.ndim == 0:
+        a = np.full(nq, a[()])
+    if a.shape[0] != nq:
+        raise ValueError(f"per_group: one entry per query ({nq}), got {a.shape[0]}")
+    if a.size and (a.min() < 0 or a.max() > 2**31 - 1):
+        raise ValueError("per_group: entries must be a count in [0, 2**31 - 1], 0 for no cap")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 def _u64(a):
     """the integer array `a` as uint64 where every value lies in [0, 2**64), else None"""
     if a.dtype == np.uint64:
@@ -1124,8 +1139,13 @@ class DeviceIndex:
         return (out, dist) if return_distances else out
 
     def query_batch(self, qn, q_pq, k, n_probes, pass_1=None, debug=False, *, allowed=None, return_distances=False,
-                    exclude=None, group=None, tags=None, tags_mode="any", between=None):
+                    exclude=None, group=None, tags=None, tags_mode="any", between=None, per_group=None):
         """qn: (nq, d) float32 normalised queries; q_pq: (nq, dq) table-build queries.
+        per_group: None, an int for every query, or a 1-d integer array of length nq: the most rows of any one group
+        (set_groups) a query returns, 0 for no cap — the ranking the rescoring makes is walked and a candidate kept
+        while fewer than that many of its group have been kept, up to k; rows may end in -1.  The
+        candidates are the heap's: a larger pass_1 or n_probes widens the pool, nothing does by itself.  A call with it
+        takes tk_index_query_batch_ex6.
         between: None, or (lo, hi): the inclusive interval of values (set_values) each query's rows must lie in, per
         column — each end None, a scalar, (nq,) for one column, (nq, C), or (C,) where nq != C (query_ranges; the
         reference's `insert` only for labels that pass).
@@ -1154,8 +1174,10 @@ class DeviceIndex:
         def queries(o, e):
             return _lib.ptr(qn[o:e], _lib._f32p), q_pq[o:e].ctypes.data, int(is64), e - o, *knobs
 
-        if group is not None or exclude is not None or tags is not None or between is not None:
+        if (group is not None or exclude is not None or tags is not None or between is not None
+                or per_group is not None):
             group = None if group is None else query_groups(group, nq)
+            per_group = None if per_group is None else query_caps(per_group, nq)
             tags, mode = (None, 0) if tags is None else (query_tags(tags, nq), tag_mode_of(tags_mode))
             between = None if between is None else self._ranges_of(between, nq)
             exclude = None if exclude is None else self._exclude_of(exclude, nq)
@@ -1163,11 +1185,13 @@ class DeviceIndex:
             def rows(a, o, e):
                 return None if a is None else a[o:e].ctypes.data
 
-            return self._query_host(
-                lambda o, e, aset, *outs: L.tk_index_query_batch_ex5(
-                    self._h, aset, rows(exclude, o, e), rows(group, o, e), rows(tags, o, e), mode, rows(between, o, e),
-                    *queries(o, e), *outs),
-                nq, k, n_probes, pass_1, debug, return_distances, allowed, split=debug)
+            def restricted(o, e, aset, *outs):
+                r = (self._h, aset, rows(exclude, o, e), rows(group, o, e), rows(tags, o, e), mode, rows(between, o, e))
+                if per_group is None:
+                    return L.tk_index_query_batch_ex5(*r, *queries(o, e), *outs)
+                return L.tk_index_query_batch_ex6(*r, rows(per_group, o, e), *queries(o, e), *outs)
+
+            return self._query_host(restricted, nq, k, n_probes, pass_1, debug, return_distances, allowed, split=debug)
         if allowed is None and not return_distances and not debug and nq > 0:
             # the session pads unrotated queries on the device: only for q_pq = pad1(qn)
             plain = is64 or (np.array_equal(q_pq[:, :self.d], qn) and not q_pq[:, self.d:].any())
@@ -1229,10 +1253,15 @@ class DeviceIndex:
         _lib.check(_lib.lib().tk_index_gather_queries_dev(self._h, rows_ptr, int(nq), qn_ptr, qpq_ptr, stream))
 
     def query_rows(self, rows, k, n_probes, pass_1=None, debug=False, *, exclude_self=True, allowed=None,
-                   return_distances=False):
+                   return_distances=False, per_group=None):
         """The neighbours of stored rows (tk_index_query_rows): gather_queries(rows) as the queries, each leaving
-        its own row out where exclude_self.  Outputs as query_batch."""
+        its own row out where exclude_self.  Outputs as query_batch.  per_group: as query_batch's — that call, on
+        gather_queries(rows) with exclude=rows where exclude_self."""
         rows = self._rows_of(rows, "query_rows")
+        if per_group is not None:
+            qn, qp = self.gather_queries(rows)
+            return self.query_batch(qn, qp, k, n_probes, pass_1, debug, allowed=allowed, exclude=rows if exclude_self else None,
+                                    return_distances=return_distances, per_group=per_group)
         L, knobs = _lib.lib(), (int(k), int(n_probes), int(pass_1 or 0))
         return self._query_host(
             lambda o, e, aset, *outs: L.tk_index_query_rows(
@@ -1268,7 +1297,7 @@ class DeviceIndex:
 
     def query_batch_dev(self, qn_ptr, qpq_ptr, qpq_is_f64, nq, k, n_probes, out_ptr,
                         pass_1=None, stream=0, done_event=None, *, allowed=None, dist_ptr=None, exclude_ptr=None,
-                        group_ptr=None, tags_ptr=None, tags_mode="any", between_ptr=None):
+                        group_ptr=None, tags_ptr=None, tags_mode="any", between_ptr=None, per_group_ptr=None):
         """Device pointers in, device pointer out, enqueued on `stream` (no sync).
         done_event: a hipEvent_t (integer handle) recorded behind the batch's last kernel, on
         whichever internal stream that runs (tk_index_query_batch_dev_ex).
@@ -1291,13 +1320,21 @@ class DeviceIndex:
         is restricted to per value column, INT64_MIN / INT64_MAX for an unbounded end; the caller's again after
         join() or done_event.
         A call with any of these four takes the library's one restricted entry point (tk_index_query_batch_dev_ex5,
-        NULL for the ones not given)."""
+        NULL for the ones not given).
+        per_group_ptr: None, or a device buffer of nq int32: the most rows of any one group each query returns, an
+        entry <= 0 for no cap; the caller's again after join() or done_event.  A call with it takes
+        tk_index_query_batch_dev_ex6."""
         if allowed is not None:
             if not isinstance(allowed, AllowSet):
                 raise TypeError("query_batch_dev: allowed= takes a prepared set (DeviceIndex.allow / IVF.allow)")
             allowed = self._allow_of(allowed)[0].handle
         L, ev = _lib.lib(), None if done_event is None else C.c_void_p(int(done_event))
-        if exclude_ptr is not None or group_ptr is not None or tags_ptr is not None or between_ptr is not None:
+        if per_group_ptr is not None:
+            mode = tag_mode_of(tags_mode) if tags_ptr is not None else 0
+            rc = L.tk_index_query_batch_dev_ex6(
+                self._h, allowed, exclude_ptr, group_ptr, tags_ptr, mode, between_ptr, per_group_ptr, qn_ptr, qpq_ptr,
+                int(qpq_is_f64), nq, int(k), int(n_probes), int(pass_1 or 0), out_ptr, dist_ptr, ev, stream)
+        elif exclude_ptr is not None or group_ptr is not None or tags_ptr is not None or between_ptr is not None:
             mode = tag_mode_of(tags_mode) if tags_ptr is not None else 0
             rc = L.tk_index_query_batch_dev_ex5(
                 self._h, allowed, exclude_ptr, group_ptr, tags_ptr, mode, between_ptr, qn_ptr, qpq_ptr, int(qpq_is_f64),
@@ -2325,8 +2362,10 @@ class IVF:
         return self._unsharded_device_index().allow(ids_or_mask)
 
     def query(self, q, k, n_probes=1, pass_1=None, *, allowed=None, return_distances=False, exclude=None, group=None,
-              tags=None, tags_mode="any", between=None):
+              tags=None, tags_mode="any", between=None, per_group=None):
         """Top-k ids for one query.  reference: ivf.py:106-163
+        per_group: the most rows of any one group (set_groups) among the ids returned, 0 or None for no cap; fewer
+        than k ids come back where the candidates run out of groups — raise pass_1 or n_probes then.
         between: (lo, hi), the inclusive interval of values (set_values) the query's rows must lie in: each end None
         (unbounded), a number, or one entry per column.
         tags: the 64-bit tag mask the query is restricted by under tags_mode — "any": rows that carry one of its tags
@@ -2342,12 +2381,14 @@ class IVF:
                 raise TypeError("between: a pair (lo, hi), each None, a number or an array")
             between = tuple(b if b is None or np.ndim(b) == 0 else np.asarray(b).reshape(1, -1) for b in between)
             self._ranges(between, 1)                # (refused before anything runs)
+        if per_group is not None:
+            query_caps(np.asarray(per_group).reshape(-1), 1)
         q = np.ascontiguousarray(q, dtype=np.float32)
         assert self.data.shape[1] == q.shape[0]
         qn, qp = self._prepare(q[None, :])
         dev = self._unsharded_device_index()
         one = {w: None if x is None else np.asarray(x).reshape(1)
-               for w, x in (("exclude", exclude), ("group", group), ("tags", tags))}
+               for w, x in (("exclude", exclude), ("group", group), ("tags", tags), ("per_group", per_group))}
         got = dev.query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed, return_distances=return_distances,
                               tags_mode=tags_mode, between=between, **one)
         out, dist = (got[0][0], got[1][0]) if return_distances else (got[0], None)
@@ -2355,14 +2396,18 @@ class IVF:
         return (out[keep], dist[keep]) if return_distances else out[keep]
 
     def query_rows(self, rows, k, n_probes=1, pass_1=None, *, exclude_self=True, allowed=None,
-                   return_distances=False):
+                   return_distances=False, per_group=None):
         """The neighbours of stored rows: (len(rows), k) ids padded with -1 — (ids, dists) with return_distances —
         of the queries float32(data[rows]), made on the device without a second normalisation.
+        per_group: as query_batch's.
         exclude_self: a row's own copies are never inserted, so it is not among its neighbours; its twin with an equal
         vector is.  rows: ids in [0, N), duplicates allowed (ValueError outside).  A removed row is still a vector:
         it can be a query row, and nothing is masked for it."""
+        if per_group is not None:
+            per_group = query_caps(per_group, len(rows))
         return self._unsharded_device_index().query_rows(rows, k, n_probes, pass_1, exclude_self=exclude_self,
-                                                         allowed=allowed, return_distances=return_distances)
+                                                         allowed=allowed, return_distances=return_distances,
+                                                         per_group=per_group)
 
     def knn_graph(self, k, n_probes=1, pass_1=None, *, chunk=10000, return_distances=False):
         """query_rows over every row, itself left out: (N, k) ids — (ids, dists) with return_distances.  Chunks of
@@ -2415,7 +2460,7 @@ class IVF:
         return (ids, dist) if return_distances else ids
 
     def query_batch(self, qs, k, n_probes=1, pass_1=None, fast=False, *, allowed=None, return_distances=False,
-                    exclude=None, group=None, tags=None, tags_mode="any", between=None):
+                    exclude=None, group=None, tags=None, tags_mode="any", between=None, per_group=None):
         """(nq, d) queries -> (nq, k) int64 ids, rows padded with -1 when the
         reference would return fewer than k ids.  (The reference's README shows a
         2-d `ivf.query(queries, ...)` that its code does not support; this is that
@@ -2432,9 +2477,15 @@ class IVF:
         with fast=True.
         between: (lo, hi), the inclusive interval of values (set_values) each query's rows must lie in, per column:
         each end None (unbounded), a number for every query, (nq,) for one column, (nq, C), or (C,) where nq != C
-        (DESIGN §3.14); not with fast=True."""
+        (DESIGN §3.14); not with fast=True.
+        per_group: an int for every query, or a 1-d integer array with one entry per query: the most rows of any one
+        group (set_groups) among a query's ids, 0 for no cap — "the k nearest documents, not chunks".  The rescoring's
+        ranking is walked and a candidate kept while fewer than that many of its group have been kept; the candidates
+        are the heap's pass_1 or (n_probes + 1) k + 1, so with a small cap a row can end in -1 before k ids: raise
+        pass_1 or n_probes for a wider pool, nothing widens it by itself; not with fast=True."""
         # what fast=True does not take: the first of these that is asked for is the one refused
-        asked = [word for word, given in (("between=", between is not None), ("tags=", tags is not None),
+        asked = [word for word, given in (("per_group=", per_group is not None),
+                                          ("between=", between is not None), ("tags=", tags is not None),
                                           ("group=", group is not None), ("exclude=", exclude is not None),
                                           ("return_distances=True", return_distances), ("allowed=", allowed is not None))
                  if given]
@@ -2447,6 +2498,8 @@ class IVF:
             self._ranges(between, len(qs))
         if tags is not None:
             tag_mode_of(tags_mode)
+        if per_group is not None:
+            per_group = query_caps(per_group, len(qs))
         self._unsharded_device_index()
         if asked:
             qs = np.array(qs, dtype=np.float32, order="C", copy=True)
@@ -2459,7 +2512,8 @@ class IVF:
             qn, qp = self._prepare(qs)
             return self.device_index().query_batch(qn, qp, k, n_probes, pass_1, allowed=allowed,
                                                    return_distances=return_distances, exclude=exclude, group=group,
-                                                   tags=tags, tags_mode=tags_mode, between=between)
+                                                   tags=tags, tags_mode=tags_mode, between=between,
+                                                   per_group=per_group)
         if fast:
             return self.device_index().query_batch_raw(qs, k, n_probes, pass_1)
         R = self.pq.R
