@@ -912,6 +912,26 @@ void tk_stream_destroy(tk_stream *s);
  * that distance (thousands of duplicates) or near rows stored together so densely that one
  * segment holds more than 4 times its share of them.  A list is never cut silently. */
 int tk_index_knn_brute(tk_index *ix, const float *q, int64_t nq, int k, int64_t *out_ids);
+/* The same under the restrictions of the query calls: the k rows with the smallest (part, row) among the rows j in
+ * [0, N) that pass every condition given (host arrays, NULL: not given):
+ *   allowed_mask (N,) uint8 by ROW ID (not an allowed set, which is laid out by list position): allowed_mask[j] != 0
+ *   exclude (nq,)   j != exclude[i]; -1 excludes nothing
+ *   group (nq,)     group[i] < 0, or the row's group (tk_index_set_groups) == group[i]
+ *   tags (nq,)      tags[i] == 0, or with the row's mask m (tk_index_set_tags) tag_mode 0: (m & tags[i]) != 0,
+ *                   1: (m & tags[i]) == tags[i]
+ *   between (nq, C, 2)  lo <= key <= hi on each of the C columns of tk_index_set_values (int64 keys, both inclusive)
+ * Fewer than k passing rows: the row of out_ids ends in -1.  out_dist (or NULL): (nq, k) float32, the `part` value
+ * beside each id (numpy's knn_brute value, which rounding can make slightly negative — not the knn_brute1 distance
+ * the query calls' _dist entry points return), +inf beside -1.
+ * The predicate is applied inside the tile kernel before a row is appended, and the first tau is taken over the
+ * sample rows that pass (+inf below k of them).  A candidate list that overflows under the segment rule is not an
+ * error here: the selection is repeated once with segments of the largest multiple of 32 not above 8192 - k rows,
+ * which cannot overflow.  TK_ERR_STATE with the query calls' texts where group / tags / between is given and the
+ * index has no such values for all N rows; only the arrays by row id are read — no list-order table is made.
+ * Not for a list-sharded index; float32 vectors, d, k and N as above. */
+int tk_index_knn_brute_ex(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
+                          const int64_t *exclude, const int32_t *group, const uint64_t *tags, int tag_mode,
+                          const int64_t *between, int64_t *out_ids, float *out_dist);
 
 /* ---- list-sharded index over `world` ranks, one process per GPU --------
  * The inverted lists (ivf.py:100-102) are partitioned by cluster id: owner[l] is the rank

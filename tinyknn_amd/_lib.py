@@ -227,6 +227,8 @@ SIGNATURES = {
     "tk_stream_prepare_seconds": (C.c_double, [C.c_void_p]),
     "tk_stream_destroy": (None, [C.c_void_p]),
     "tk_index_knn_brute": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, _i64p]),
+    "tk_index_knn_brute_ex": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),
     "tk_index_set_pipeline": (C.c_int, [C.c_void_p, C.c_int]),
     "tk_index_set_coalesce": (C.c_int, [C.c_void_p, C.c_int]),
     "tk_index_join": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1141,9 +1141,12 @@ extern "C" int tk_index_query_batch_raw(tk_index *ix, const float *q_raw, int64_
 
 // ---------------------------------------------------------------------------
 // exact k nearest vectors of IVF.data: the ground truth of recall (brute.hip)
-extern "C" int tk_index_knn_brute(tk_index *ix, const float *q, int64_t nq, int k, int64_t *out_ids)
+// r (or NULL): the restriction, its arrays on the device.  retry: a candidate list that overflowed under the segment
+// rule is not an error — the selection runs once more from the sampled tau with the segment length that cannot
+// overflow, the largest multiple of 32 not above cap - k (a segment appends at most `seg` rows to at most k kept ones).
+static int knn_brute(tk_index *ix, const float *q, int64_t nq, int k, const TkBruteRestrict *r, bool retry,
+                     int64_t *out_ids, float *out_dist)
 {
-    IXLOCK(ix);
     ARGCHECK(ix && ix->have_data, "set_data first");
     ARGCHECK(ix->data_dtype != TK_DATA_F64, "float32 vectors only");
     ARGCHECK(ix->data_dtype != TK_DATA_F16, "knn_brute is the ground truth on float32 vectors: this index stores "
@@ -1157,28 +1160,99 @@ extern "C" int tk_index_knn_brute(tk_index *ix, const float *q, int64_t nq, int 
     const int64_t ns = ix->N < 8192 ? ix->N : 8192;
     const int cap = 8192;
     TRY(ix->br_ynorm.ensure((size_t)ix->N * 4));
-    TRY(ix->br_tau.ensure((size_t)nq * 4));
+    TRY(ix->br_tau.ensure((size_t)nq * 4 * 2));              // tau, and its copy as the sample gave it
     TRY(ix->br_vals.ensure((size_t)nq * ns * 4));
     TRY(ix->br_cand.ensure((size_t)nq * cap * 8));
     TRY(ix->br_count.ensure((size_t)nq * 4 + 4));
     TRY(ix->br_out.ensure((size_t)nq * k * 8));
     TRY(ix->br_q.ensure((size_t)nq * ix->d * 4));
     TRY(ix->br_sample.ensure((size_t)ns * (ix->d + 1) * 4));
+    if (out_dist) TRY(ix->br_dist.ensure((size_t)nq * k * 4));
     HIPCHECK(hipMemcpy(ix->br_q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
     int *overflow = ix->br_count.as<int>() + nq;
-    if (tk_launch_knn_brute(ix->br_q.as<float>(), nq, ix->d, ix->data.as<float>(), ix->N, k,
-                            ix->br_ynorm.as<float>(), ix->br_vals.as<float>(), ns,
-                            ix->br_tau.as<float>(), ix->br_cand.as<unsigned long long>(), cap,
-                            ix->br_count.as<int>(), overflow, ix->br_out.as<int64_t>(),
-                            ix->br_sample.as<float>(), nullptr))
+    float *tau = ix->br_tau.as<float>(), *tau0 = tau + nq, *dist = out_dist ? ix->br_dist.as<float>() : nullptr;
+    const float *X = ix->br_q.as<float>(), *Y = ix->data.as<float>();
+    if (tk_launch_brute_tau(X, nq, ix->d, Y, ix->N, k, ix->br_ynorm.as<float>(), ix->br_vals.as<float>(), ns, tau,
+                            ix->br_sample.as<float>(), r, nullptr))
         return fail(TK_ERR_HIP, "tk_launch_knn_brute: unsupported size / LDS attribute");
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipDeviceSynchronize());
-    int ov = 0;
-    HIPCHECK(hipMemcpy(&ov, overflow, 4, hipMemcpyDeviceToHost));
-    if (ov) return fail(TK_ERR_HIP, "knn_brute: candidate list overflow (one segment of rows holds more than 8192 rows within a query's running k-th distance: tied or stored together)");
+    if (retry) HIPCHECK(hipMemcpyAsync(tau0, tau, (size_t)nq * 4, hipMemcpyDeviceToDevice, nullptr));
+    int64_t seg = tk_brute_segment(k, ns, cap);
+    for (int attempt = 0;; attempt++) {
+        if (tk_launch_brute_select(X, nq, ix->d, Y, ix->N, k, ix->br_ynorm.as<float>(), tau,
+                                   ix->br_cand.as<unsigned long long>(), cap, ix->br_count.as<int>(), overflow,
+                                   ix->br_out.as<int64_t>(), dist, seg, r, nullptr))
+            return fail(TK_ERR_HIP, "tk_launch_knn_brute: unsupported size / LDS attribute");
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipDeviceSynchronize());
+        int ov = 0;
+        HIPCHECK(hipMemcpy(&ov, overflow, 4, hipMemcpyDeviceToHost));
+        if (!ov) break;
+        if (!retry || attempt == 1)
+            return fail(TK_ERR_HIP, "knn_brute: candidate list overflow (one segment of rows holds more than 8192 rows within a query's running k-th distance: tied or stored together)");
+        HIPCHECK(hipMemcpyAsync(tau, tau0, (size_t)nq * 4, hipMemcpyDeviceToDevice, nullptr));
+        seg = (cap - k) / 32 * 32;
+    }
     HIPCHECK(hipMemcpy(out_ids, ix->br_out.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    if (out_dist) HIPCHECK(hipMemcpy(out_dist, dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
     return TK_OK;
+}
+
+extern "C" int tk_index_knn_brute(tk_index *ix, const float *q, int64_t nq, int k, int64_t *out_ids)
+{
+    IXLOCK(ix);
+    return knn_brute(ix, q, nq, k, nullptr, false, out_ids, nullptr);
+}
+
+// A host array of a restricted call in its workspace buffer (NULL stays NULL)
+template <typename T>
+static int brute_upload(DevBuf &b, const T *host, size_t n, const T *&dev)
+{
+    dev = nullptr;
+    if (!host) return TK_OK;
+    TRY(b.ensure((n > 0 ? n : 1) * sizeof(T)));
+    HIPCHECK(hipMemcpy(b.p, host, n * sizeof(T), hipMemcpyHostToDevice));
+    dev = b.as<T>();
+    return TK_OK;
+}
+
+extern "C" int tk_index_knn_brute_ex(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
+                                     const int64_t *exclude, const int32_t *group, const uint64_t *tags, int tag_mode,
+                                     const int64_t *between, int64_t *out_ids, float *out_dist)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix && ix->have_data, "set_data first");
+    ARGCHECK(!ix->sharded, "list-sharded index: knn_brute with restrictions is not supported");
+    ARGCHECK(nq >= 0, "buffers");
+    ARGCHECK(tag_mode == 0 || tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
+    // the by-row arrays only: no list-order table is made or read
+    if (group) TRY(row_table_covers(ix, ix->groups));
+    if (tags) TRY(row_table_covers(ix, ix->tags));
+    if (between) TRY(row_table_covers(ix, ix->values));
+    if (exclude)
+        for (int64_t i = 0; i < nq; i++) ARGCHECK(exclude[i] >= -1 && exclude[i] < ix->N, "exclude: entries in [-1, N)");
+    if (!allowed_mask && !exclude && !group && !tags && !between)
+        return knn_brute(ix, q, nq, k, nullptr, true, out_ids, out_dist);
+    if (nq == 0) return TK_OK;
+    TkBruteRestrict r{};
+    r.n_rows = ix->N;
+    r.tag_mode = tag_mode;
+    if (allowed_mask) {
+        std::vector<uint32_t> bits((size_t)(ix->N + 31) / 32, 0u);
+        for (int64_t j = 0; j < ix->N; j++)         // (no branch: a random mask would mispredict every other row)
+            bits[(size_t)(j >> 5)] |= (uint32_t)(allowed_mask[j] != 0) << (j & 31);
+        TRY(brute_upload(ix->br_mask, bits.data(), bits.size(), r.allowed));
+    }
+    TRY(brute_upload(ix->br_exclude, exclude, (size_t)nq, r.exclude));
+    TRY(brute_upload(ix->br_group, group, (size_t)nq, r.group));
+    TRY(brute_upload(ix->br_tags, tags, (size_t)nq, r.tags));
+    if (group) r.row_groups = ix->groups.by_row.as<int32_t>();
+    if (tags) r.row_tags = ix->tags.by_row.as<uint64_t>();
+    if (between) {
+        r.cols = value_columns(ix);
+        r.row_keys = ix->values.by_row.as<int64_t>();
+        TRY(brute_upload(ix->br_ranges, between, (size_t)nq * 2 * r.cols, r.ranges));
+    }
+    return knn_brute(ix, q, nq, k, &r, true, out_ids, out_dist);
 }
 
 // _FastDistanceTable.top (fast_pq.py:284-312) for a BATCH of queries against the coded rows the

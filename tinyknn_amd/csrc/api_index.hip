@@ -87,7 +87,8 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->list_n, &ix->ids_off, &ix->ids, &ix->codes, &ix->ids32, &ix->data, &ix->cslots_i,
                       &ix->cslots_l, &ix->c_chunk_off, &ix->q, &ix->qpq, &ix->stage, &ix->owner,
                       &ix->local_chunk_off, &ix->rot_t, &ix->br_ynorm, &ix->br_vals, &ix->br_tau,
-                      &ix->br_cand, &ix->br_count, &ix->br_out, &ix->br_q, &ix->br_sample, &ix->replay_counters,
+                      &ix->br_cand, &ix->br_count, &ix->br_out, &ix->br_q, &ix->br_sample, &ix->br_dist, &ix->br_mask,
+                      &ix->br_exclude, &ix->br_group, &ix->br_tags, &ix->br_ranges, &ix->replay_counters,
                       &ix->twin_list, &ix->twin_off, &ix->row_pos_off, &ix->row_pos, &ix->groups.by_row,
                       &ix->groups.table, &ix->tags.by_row, &ix->tags.table, &ix->values.by_row,
                       &ix->values.table};

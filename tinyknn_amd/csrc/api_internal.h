@@ -244,6 +244,7 @@ struct tk_index {
     DevBuf owner, local_chunk_off;
     DevBuf rot_t;            // fast mode: R transposed (d_pad, dq) float64, or empty
     DevBuf br_ynorm, br_vals, br_tau, br_cand, br_count, br_out, br_q, br_sample;   // tk_index_knn_brute
+    DevBuf br_dist, br_mask, br_exclude, br_group, br_tags, br_ranges;              // ... and what _ex adds
     int rot_d_pad = 0;
     int rank = 0, world = 1;
     bool sharded = false;
@@ -519,6 +520,7 @@ int row_pos_ensure(tk_index *ix);
 int row_table_set(tk_index *ix, TkRowTable &t, const void *vals, int64_t n,
                   int (*check)(const void *vals, int64_t n) = nullptr, size_t esz = 0);
 int row_table_ensure(tk_index *ix, TkRowTable &t, void (*launch)(const tk_index *ix));
+int row_table_covers(const tk_index *ix, const TkRowTable &t);    // TK_ERR_STATE unless by_row covers all N rows
 int row_table_info(const tk_index *ix, const TkRowTable &t, int64_t *info4);
 int group_table_ensure(tk_index *ix);       // groups.hip
 int tag_table_ensure(tk_index *ix);         // tags.hip

@@ -541,3 +541,29 @@ int tk_launch_knn_brute(const float *X, int64_t nq, int d, const float *Y, int64
                         float *ynorm2, float *vals, int64_t ns, float *tau,
                         unsigned long long *cand, int cap, int *count, int *overflow, int64_t *out,
                         float *sample, hipStream_t s);
+// What restricts the rows a query of knn_brute may return (brute.hip: brute_passes), device pointers, NULL for a
+// restriction that was not given.  By row id: allowed (bit j of word j / 32), row_groups (N), row_tags (N),
+// row_keys (cols, N) column-major.  Per query: exclude (nq) row id or -1, group (nq) id or -1, tags (nq) mask or 0
+// (tag_mode 0 any / 1 all), ranges (nq, cols, 2) inclusive int64 keys.
+struct TkBruteRestrict {
+    const uint32_t *allowed;
+    const int32_t *row_groups;
+    const uint64_t *row_tags;
+    const int64_t *row_keys;
+    const int64_t *exclude;
+    const int32_t *group;
+    const uint64_t *tags;
+    const int64_t *ranges;
+    int64_t n_rows;                 // rows of the index: column c of row_keys begins at c * n_rows
+    int tag_mode, cols;
+};
+// The two halves of tk_launch_knn_brute, each with the restriction (NULL: none).  _tau: the norms of Y and tau (nq)
+// from the strided sample, counted over the sample rows a query's restriction passes (+inf below k of them).
+// _select: the selection over segments of `seg` rows (a multiple of 32) from that tau, which it tightens in place;
+// out_dist (or NULL): (nq, k) float32, the part value beside each id, +inf beside -1.
+int64_t tk_brute_segment(int k, int64_t ns, int cap);
+int tk_launch_brute_tau(const float *X, int64_t nq, int d, const float *Y, int64_t N, int k, float *ynorm2,
+                        float *vals, int64_t ns, float *tau, float *sample, const TkBruteRestrict *r, hipStream_t s);
+int tk_launch_brute_select(const float *X, int64_t nq, int d, const float *Y, int64_t N, int k, const float *ynorm2,
+                           float *tau, unsigned long long *cand, int cap, int *count, int *overflow, int64_t *out,
+                           float *out_dist, int64_t seg, const TkBruteRestrict *r, hipStream_t s);

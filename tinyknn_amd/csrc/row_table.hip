@@ -36,8 +36,8 @@ int row_table_set(tk_index *ix, TkRowTable &t, const void *vals, int64_t n, int 
     return TK_OK;
 }
 
-// Made on the first call that names an array of the kind, and again after the lists changed: once per layout.
-int row_table_ensure(tk_index *ix, TkRowTable &t, void (*launch)(const tk_index *ix))
+// What every call that names an array of the kind needs: the kind's values by row id, for all N rows
+int row_table_covers(const tk_index *ix, const TkRowTable &t)
 {
     if (t.n == 0 || t.n != ix->N) {
         const std::string noun = t.noun, nouns = noun + "s";
@@ -47,6 +47,13 @@ int row_table_ensure(tk_index *ix, TkRowTable &t, void (*launch)(const tk_index 
         return fail(TK_ERR_STATE, "the " + nouns + " cover " + std::to_string(t.n) + " rows, the index has " +
                                       std::to_string(ix->N) + " now: set them again (tk_index_set_" + nouns + ")");
     }
+    return TK_OK;
+}
+
+// Made on the first call that names an array of the kind, and again after the lists changed: once per layout.
+int row_table_ensure(tk_index *ix, TkRowTable &t, void (*launch)(const tk_index *ix))
+{
+    TRY(row_table_covers(ix, t));
     if (t.state.current(ix->lists_gen)) return TK_OK;
     TRY(table_may_build(ix, t.noun, t.called));
     t.state.ok = false;

@@ -1284,16 +1284,59 @@ class DeviceIndex:
             int(pass_1 or 0), _lib.ptr(out, _lib._i64p)))
         return out
 
-    def knn_brute(self, qn, k):
+    def knn_brute(self, qn, k, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any", between=None):
         """Exact k nearest rows of IVF.data for normalised queries (ground truth of recall;
         tk_index_knn_brute: f32 MFMA, numpy's distances bit for bit), ascending.  Float32 vectors only:
-        refused on a float64 and on a half index."""
+        refused on a float64 and on a half index.
+        allowed / exclude / group / tags, tags_mode / between: the restrictions of query_batch, with its meanings — the
+        k nearest among the rows that pass all of them, exactly, the row ending in -1 where fewer than k pass
+        (tk_index_knn_brute_ex: the ground truth of restricted recall, and the answer for a filter so selective that
+        the probed lists hold too few passing rows).  allowed: a bool mask of length N or row ids; an AllowSet is
+        laid out by list position and refused (TypeError).  A mask of the surviving rows is the truth after remove():
+        the vectors of removed rows stay in HBM and the unrestricted call still returns them.
+        With nothing given the call is tk_index_knn_brute's.  The values the rows were ranked by: knn_brute_dist."""
+        return self._knn_brute(qn, k, False, allowed, exclude, group, tags, tags_mode, between)
+
+    def knn_brute_dist(self, qn, k, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
+                       between=None):
+        """knn_brute's ids and, beside each, the float32 `part` value it was ranked by: (ids, part), part = (|q|^2 +
+        |y|^2) - 2 q.y as numpy's knn_brute sums it (utils.py:84; rounding can make it slightly negative), +inf
+        beside -1.  Not the knn_brute1 distance that query_batch(return_distances=True) returns.  Always
+        tk_index_knn_brute_ex; with no restriction the ids are knn_brute's."""
+        return self._knn_brute(qn, k, True, allowed, exclude, group, tags, tags_mode, between)
+
+    def _knn_brute(self, qn, k, want_dist, allowed, exclude, group, tags, tags_mode, between):
+        """knn_brute / knn_brute_dist: the old entry point where nothing is asked beyond it, else tk_index_knn_brute_ex
+        with the arguments parsed as query_batch parses them"""
         qn = np.ascontiguousarray(qn, dtype=np.float32)
         assert qn.shape[1] == self.d
-        out = np.empty((qn.shape[0], k), dtype=np.int64)
-        _lib.check(_lib.lib().tk_index_knn_brute(self._h, _lib.ptr(qn, _lib._f32p), qn.shape[0],
-                                                 int(k), _lib.ptr(out, _lib._i64p)))
-        return out
+        nq = qn.shape[0]
+        out = np.empty((nq, k), dtype=np.int64)
+        if (allowed is None and exclude is None and group is None and tags is None and between is None
+                and not want_dist):
+            _lib.check(_lib.lib().tk_index_knn_brute(self._h, _lib.ptr(qn, _lib._f32p), nq, int(k),
+                                                     _lib.ptr(out, _lib._i64p)))
+            return out
+        if isinstance(allowed, AllowSet):
+            raise TypeError("knn_brute: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
+                            "list position")
+        if _dev_is_sharded(self):
+            raise RuntimeError("knn_brute with restrictions is not supported on a list-sharded index")
+        mask = None if allowed is None else AllowSet.mask_of(allowed, self.N)
+        exclude = None if exclude is None else self._exclude_of(exclude, nq)
+        group = None if group is None else query_groups(group, nq)
+        tags, mode = (None, 0) if tags is None else (query_tags(tags, nq), tag_mode_of(tags_mode))
+        between = None if between is None else np.ascontiguousarray(self._ranges_of(between, nq))
+        dist = np.full((nq, k), np.inf, dtype=np.float32) if want_dist else None
+        out[:] = -1
+
+        def host(a):
+            return None if a is None else a.ctypes.data
+
+        _lib.check(_lib.lib().tk_index_knn_brute_ex(
+            self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), host(mask), host(exclude), host(group), host(tags), mode,
+            host(between), _lib.ptr(out, _lib._i64p), host(dist)))
+        return (out, dist) if want_dist else out
 
     def query_batch_dev(self, qn_ptr, qpq_ptr, qpq_is_f64, nq, k, n_probes, out_ptr,
                         pass_1=None, stream=0, done_event=None, *, allowed=None, dist_ptr=None, exclude_ptr=None,
@@ -2355,6 +2398,26 @@ class IVF:
             qn, qp = _front.prepare(qs, self.metric == "angular", R, pad)
         assert qp.shape[1] == dq
         return qn, qp
+
+    def knn_brute(self, qs, k, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any", between=None,
+                  return_distances=False):
+        """The exact k nearest rows of IVF.data for raw queries, under the restrictions of query_batch (DeviceIndex.
+        knn_brute on the prepared queries: an angular index ranks its normalised rows): (nq, k) int64 ids ascending
+        by (part, row), ending in -1 where fewer than k rows pass; with return_distances (ids, part): also the float32
+        `part` values (DeviceIndex.knn_brute_dist: numpy's knn_brute values, not the rescoring's distances), +inf beside -1.  The ground truth of
+        restricted recall; allowed= with a mask of the surviving rows is the truth after remove().  allowed: a bool
+        mask of length N or row ids, not an AllowSet.  Not for a list-sharded index."""
+        if isinstance(allowed, AllowSet):
+            raise TypeError("knn_brute: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
+                            "list position")
+        if between is not None:
+            self._ranges(between, len(qs))
+        if tags is not None:
+            tag_mode_of(tags_mode)
+        dev = self._unsharded_device_index()
+        qn, _ = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
+        call = dev.knn_brute_dist if return_distances else dev.knn_brute
+        return call(qn, k, allowed=allowed, exclude=exclude, group=group, tags=tags, tags_mode=tags_mode, between=between)
 
     def allow(self, ids_or_mask):
         """Prepare an allowed set (a bool mask over the N rows, or row ids) for `allowed=`: made once on the
