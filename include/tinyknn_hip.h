@@ -932,6 +932,36 @@ int tk_index_knn_brute(tk_index *ix, const float *q, int64_t nq, int k, int64_t 
 int tk_index_knn_brute_ex(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
                           const int64_t *exclude, const int32_t *group, const uint64_t *tags, int tag_mode,
                           const int64_t *between, int64_t *out_ids, float *out_dist);
+/* The exact k nearest rows inside each query's own group (group_exact.hip): what the restricted call
+ * above answers for group[i] >= 0 among the rows that are STORED, at a cost that follows the size of the group instead
+ * of N — a query reads the rows of its group and no other.  Ranked by the rescoring's distance (numpy's einsum order
+ * bit for bit, the value the query calls' _dist entry points return), so ids and distances mix freely with theirs:
+ * the k smallest (distance, row id) among the rows j with
+ *   group (nq,)     REQUIRED: the row's group (tk_index_set_groups) == group[i]; every entry >= 0, else TK_ERR_ARG and
+ *                   nothing is run.  An id no row carries: a row of -1.
+ *   stored          some list holds label j: rows taken out by tk_index_remove_rows never come back (their vectors
+ *                   stay in HBM), so the call answers what the index would answer
+ *   allowed_mask / exclude / tags, tag_mode / between   as above (host arrays, NULL: not given)
+ * Fewer than k such rows: the row of out_ids ends in -1.  out_dist (or NULL): (nq, k) squared distances beside the
+ * ids, float32 — float64 on an index of float64 vectors, as numpy promotes — and +inf beside -1.  All three vector
+ * stores (float32, half, float64); 1 <= k <= min(1024, N); N < 2^31.
+ * One workgroup per query walks the group's rows, so a group of any size is answered — the whole index in one group
+ * included — but a large one slowly: tk_index_knn_brute_ex(group) is the call there.
+ * Two tables are made by the first call that needs them (each synchronises the device: not inside a stream capture):
+ * the row ids gathered by group id (a radix sort on the device; 4 N + 8 G + 4 bytes for G distinct groups, about 20 N
+ * bytes of work memory while it is made), made again after tk_index_set_groups and by nothing else; and an N-bit map of
+ * the stored rows, made again after the lists changed.  Calls that do not ask for them never make them.
+ * TK_ERR_STATE with the query calls' texts where the groups (or, given tags / between, the tags / values) do not
+ * cover all N rows.  Synchronous; not for a list-sharded index.
+ * tk_index_group_sizes: out[i] = the number of rows that carry group[i] (host arrays of n entries), 0 for an id no
+ * row carries — counted over all N rows, the removed ones too.  It makes the first table where it is missing.
+ * tk_index_group_rows: info4 = {that table exists for the current groups, its bytes, times one was made, distinct
+ * group ids}. */
+int tk_index_knn_group(tk_index *ix, const float *q, int64_t nq, int k, const int32_t *group,
+                       const uint8_t *allowed_mask, const int64_t *exclude, const uint64_t *tags, int tag_mode,
+                       const int64_t *between, int64_t *out_ids, void *out_dist);
+int tk_index_group_sizes(tk_index *ix, const int32_t *group, int64_t n, int64_t *out);
+int tk_index_group_rows(tk_index *ix, int64_t *info4);
 
 /* ---- list-sharded index over `world` ranks, one process per GPU --------
  * The inverted lists (ivf.py:100-102) are partitioned by cluster id: owner[l] is the rank

@@ -183,6 +183,13 @@ struct TkRowTable {
     DevBuf by_row, table;
     int64_t n = 0;
     TkTableState state;
+    // The groups alone (group_exact.hip): every row id gathered by group id — span_rows[N] int32, a group's rows one
+    // contiguous span, ascending; span_gid[G] the sorted distinct ids; span_off[G + 1] where each span begins.  Made by
+    // the first call that needs it, for ONE upload of the values: set_gen counts them (row_table_set), not the lists.
+    DevBuf span_rows, span_gid, span_off;
+    int64_t span_groups = 0;
+    uint64_t set_gen = 0;
+    TkTableState span_state;
 };
 
 #define IXLOCK(ix_)                                               \
@@ -223,6 +230,10 @@ struct tk_index {
     // where every row is stored (rows.hip): made by the first call that names an exclude array, for ONE layout
     DevBuf row_pos_off, row_pos;
     TkTableState row_pos_state;
+    // which rows are stored (group_exact.hip): bit r of an N-bit map = some list holds label r; made from the labels
+    // by the first tk_index_knn_group call, for ONE layout
+    DevBuf stored_bits;
+    TkTableState stored_state;
     // a group id per row (groups.hip) and a 64-bit tag mask per row (tags.hip): by row id as tk_index_set_groups /
     // tk_index_set_tags uploaded them, and in list-position order — made by the first call that names a group / tag
     // array, for ONE layout, as the table above
@@ -245,6 +256,7 @@ struct tk_index {
     DevBuf rot_t;            // fast mode: R transposed (d_pad, dq) float64, or empty
     DevBuf br_ynorm, br_vals, br_tau, br_cand, br_count, br_out, br_q, br_sample;   // tk_index_knn_brute
     DevBuf br_dist, br_mask, br_exclude, br_group, br_tags, br_ranges;              // ... and what _ex adds
+    DevBuf gx_begin, gx_len;                                                        // tk_index_knn_group: a query's span
     int rot_d_pad = 0;
     int rank = 0, world = 1;
     bool sharded = false;
@@ -523,6 +535,7 @@ int row_table_ensure(tk_index *ix, TkRowTable &t, void (*launch)(const tk_index 
 int row_table_covers(const tk_index *ix, const TkRowTable &t);    // TK_ERR_STATE unless by_row covers all N rows
 int row_table_info(const tk_index *ix, const TkRowTable &t, int64_t *info4);
 int group_table_ensure(tk_index *ix);       // groups.hip
+int group_rows_ensure(tk_index *ix);        // group_rows.hip: the rows by group of the groups the index has now
 int tag_table_ensure(tk_index *ix);         // tags.hip
 int value_table_ensure(tk_index *ix);       // between.hip
 inline int TkCallRestrict::ensure_tables(tk_index *ix, int64_t nq) const

@@ -23,10 +23,11 @@ int row_table_set(tk_index *ix, TkRowTable &t, const void *vals, int64_t n, int 
     TRY(flush_pending(ix));                 // calls still owed that read the old values are enqueued ...
     HIPCHECK(hipDeviceSynchronize());       // ... and have run
     t.state.ok = false;
+    t.span_state.ok = false;                // (the rows by group follow the values, not the lists)
+    t.set_gen++;
     t.n = 0;
     if (n == 0) {
-        t.by_row.release();
-        t.table.release();
+        for (DevBuf *b : {&t.by_row, &t.table, &t.span_rows, &t.span_gid, &t.span_off}) b->release();
         return TK_OK;
     }
     if (esz) t.esz = esz;                   // (a kind whose element size is fixed when it is set: between.hip)

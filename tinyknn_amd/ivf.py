@@ -204,6 +204,19 @@ def group_ids(groups, n, what):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def exact_below_parts(routed, between):
+    """The parts a batch is split into by query_batch(exact_below=): [(exact?, query rows ascending, that part's
+    between=)], the exact part (routed: bool per query) first, an empty part left out.  between: None, or (lo, hi) with
+    each end None or (nq, C) (_bound_array's form, which a part of any size keeps unambiguous), cut to the part's rows."""
+    routed = np.asarray(routed, dtype=bool)
+    parts = []
+    for exact, rows in ((True, np.flatnonzero(routed)), (False, np.flatnonzero(~routed))):
+        if len(rows):
+            parts.append((exact, rows, None if between is None else
+                          tuple(None if b is None else np.asarray(b)[rows] for b in between)))
+    return parts
+
+
 def query_groups(group, nq):
     """The int32 array a `group=` argument is: an int for every query, or a 1-d integer array with one entry per
     query; each a group id or -1 (unrestricted)."""
@@ -1338,6 +1351,63 @@ class DeviceIndex:
             host(between), _lib.ptr(out, _lib._i64p), host(dist)))
         return (out, dist) if want_dist else out
 
+    def knn_group(self, qn, k, group, *, allowed=None, exclude=None, tags=None, tags_mode="any", between=None,
+                  return_distances=False):
+        """The exact k nearest STORED rows inside each query's own group (tk_index_knn_group) for
+        normalised queries: (nq, k) int64 ids ascending by (distance, row id), ending in -1 where fewer than k rows
+        pass; with return_distances (ids, dists), the rescoring's exact squared distances — what query_batch(
+        return_distances=True) returns, bit for bit: float32, float64 on float64 vectors — +inf beside -1.
+        group: an int for every query or one id >= 0 per query (required; -1 is refused: an unrestricted query is
+        knn_brute's or query_batch's).  A query reads the rows of its group and no other, so the cost follows the
+        group's size; one workgroup walks a group, so for large groups knn_brute(group=) is the call.  Rows taken out
+        by remove() never come back.  allowed / exclude / tags, tags_mode / between: as knn_brute's; an AllowSet is
+        refused (TypeError).  Every vector store.  Not for a list-sharded index."""
+        if isinstance(allowed, AllowSet):
+            raise TypeError("knn_group: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
+                            "list position")
+        if _dev_is_sharded(self) or self._source is not None:
+            raise RuntimeError("knn_group is not supported on a list-sharded index")
+        qn = np.ascontiguousarray(qn, dtype=np.float32)
+        assert qn.ndim == 2 and qn.shape[1] == self.d
+        nq = qn.shape[0]
+        group = query_groups(group, nq)
+        if len(group) and int(group.min()) < 0:
+            raise AssertionError("knn_group: group= needs a group id >= 0 for every query (-1, any group, is "
+                                 "knn_brute's or query_batch's to answer)")
+        mask = None if allowed is None else AllowSet.mask_of(allowed, self.N)
+        exclude = None if exclude is None else self._exclude_of(exclude, nq)
+        tags, mode = (None, 0) if tags is None else (query_tags(tags, nq), tag_mode_of(tags_mode))
+        between = None if between is None else np.ascontiguousarray(self._ranges_of(between, nq))
+        out = np.full((nq, k), -1, dtype=np.int64)
+        dist = np.full((nq, k), np.inf, dtype=np.float64 if self._f64 else np.float32) if return_distances else None
+
+        def host(a):
+            return None if a is None else a.ctypes.data
+
+        _lib.check(_lib.lib().tk_index_knn_group(
+            self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), host(group), host(mask), host(exclude), host(tags), mode,
+            host(between), _lib.ptr(out, _lib._i64p), host(dist)))
+        return (out, dist) if return_distances else out
+
+    def group_sizes(self, g):
+        """The number of rows that carry each group id of g (an int or a 1-d integer array; tk_index_group_sizes):
+        int64, 0 for an id no row carries.  Counted over all N rows: the rows remove() took out are still counted."""
+        g = np.ascontiguousarray(np.atleast_1d(np.asarray(g)))
+        if g.ndim != 1 or not np.issubdtype(g.dtype, np.integer):
+            raise TypeError("group_sizes: an int or a 1-d integer array of group ids")
+        if len(g) and (int(g.min()) < -(2 ** 31) or int(g.max()) >= 2 ** 31):
+            raise ValueError("group_sizes: group ids must fit int32")
+        g = np.ascontiguousarray(g, dtype=np.int32)
+        out = np.zeros(len(g), dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_group_sizes(self._h, g.ctypes.data, len(g), _lib.ptr(out, _lib._i64p)))
+        return out
+
+    def group_rows(self):
+        """The rows gathered by group behind knn_group (tk_index_group_rows): dict(built, bytes, builds, groups)."""
+        o = np.zeros(4, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_group_rows(self._h, _lib.ptr(o, _lib._i64p)))
+        return {"built": bool(o[0]), "bytes": int(o[1]), "builds": int(o[2]), "groups": int(o[3])}
+
     def query_batch_dev(self, qn_ptr, qpq_ptr, qpq_is_f64, nq, k, n_probes, out_ptr,
                         pass_1=None, stream=0, done_event=None, *, allowed=None, dist_ptr=None, exclude_ptr=None,
                         group_ptr=None, tags_ptr=None, tags_mode="any", between_ptr=None, per_group_ptr=None):
@@ -2419,6 +2489,31 @@ class IVF:
         call = dev.knn_brute_dist if return_distances else dev.knn_brute
         return call(qn, k, allowed=allowed, exclude=exclude, group=group, tags=tags, tags_mode=tags_mode, between=between)
 
+    def knn_group(self, qs, k, group, *, allowed=None, exclude=None, tags=None, tags_mode="any", between=None,
+                  return_distances=False):
+        """The exact k nearest stored rows inside each raw query's own group (DeviceIndex.knn_group on the prepared
+        queries): (nq, k) int64 ids ascending by (distance, row id), ending in -1 where fewer than k
+        rows pass; with return_distances (ids, dists), the distances of query_batch(return_distances=True), +inf
+        beside -1.  group: an int or one id >= 0 per query.  The cost follows the group's size — the call for small
+        groups, where the probed lists hold too few of a group's rows; knn_brute(group=) is the one for large groups,
+        query_batch(group=, exact_below=) routes a batch by size.  The other restrictions as knn_brute's; allowed: a
+        bool mask of length N or row ids, not an AllowSet.  Not for a list-sharded index."""
+        if isinstance(allowed, AllowSet):
+            raise TypeError("knn_group: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
+                            "list position")
+        if between is not None:
+            self._ranges(between, len(qs))
+        if tags is not None:
+            tag_mode_of(tags_mode)
+        group = query_groups(group, len(qs))
+        if len(group) and int(group.min()) < 0:
+            raise AssertionError("knn_group: group= needs a group id >= 0 for every query (-1, any group, is "
+                                 "knn_brute's or query_batch's to answer)")
+        dev = self._unsharded_device_index()
+        qn, _ = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
+        return dev.knn_group(qn, k, group, allowed=allowed, exclude=exclude, tags=tags, tags_mode=tags_mode,
+                             between=between, return_distances=return_distances)
+
     def allow(self, ids_or_mask):
         """Prepare an allowed set (a bool mask over the N rows, or row ids) for `allowed=`: made once on the
         device, reused across calls; .close() frees it, len() = allowed stored rows."""
@@ -2523,7 +2618,8 @@ class IVF:
         return (ids, dist) if return_distances else ids
 
     def query_batch(self, qs, k, n_probes=1, pass_1=None, fast=False, *, allowed=None, return_distances=False,
-                    exclude=None, group=None, tags=None, tags_mode="any", between=None, per_group=None):
+                    exclude=None, group=None, tags=None, tags_mode="any", between=None, per_group=None,
+                    exact_below=None):
         """(nq, d) queries -> (nq, k) int64 ids, rows padded with -1 when the
         reference would return fewer than k ids.  (The reference's README shows a
         2-d `ivf.query(queries, ...)` that its code does not support; this is that
@@ -2545,7 +2641,18 @@ class IVF:
         group (set_groups) among a query's ids, 0 for no cap — "the k nearest documents, not chunks".  The rescoring's
         ranking is walked and a candidate kept while fewer than that many of its group have been kept; the candidates
         are the heap's pass_1 or (n_probes + 1) k + 1, so with a small cap a row can end in -1 before k ids: raise
-        pass_1 or n_probes for a wider pool, nothing widens it by itself; not with fast=True."""
+        pass_1 or n_probes for a wider pool, nothing widens it by itself; not with fast=True.
+        exact_below: None, or a number of rows T, with group=: the queries whose group carries fewer than T rows
+        (group_sizes) are answered exactly by knn_group under the call's other restrictions — the probed lists hold
+        too few rows of a small group — and all others, every query with group -1 among them, by this call without
+        it; the rows come back in query order, both parts with the same kind of distance.  Not with
+        per_group= (inside one group the cap would just cut k), an AllowSet or fast=True."""
+        if exact_below is not None:
+            if fast:
+                raise NotImplementedError("IVF.query_batch: fast=True with exact_below= is not supported; "
+                                          "use the exact default (fast=False)")
+            return self._query_batch_exact_below(qs, k, n_probes, pass_1, exact_below, allowed, return_distances,
+                                                 exclude, group, tags, tags_mode, between, per_group)
         # what fast=True does not take: the first of these that is asked for is the one refused
         asked = [word for word, given in (("per_group=", per_group is not None),
                                           ("between=", between is not None), ("tags=", tags is not None),
@@ -2587,3 +2694,62 @@ class IVF:
         qs = np.array(qs, dtype=np.float32, order="C", copy=True)
         qn, qp = self._prepare(qs)
         return self.device_index().query_batch(qn, qp, k, n_probes, pass_1)
+
+    def _query_batch_exact_below(self, qs, k, n_probes, pass_1, exact_below, allowed, return_distances, exclude, group,
+                                 tags, tags_mode, between, per_group):
+        """query_batch(group=, exact_below=T): the refusals, the split by group size, the two calls on their subsets
+        (an empty part runs nothing), the rows put back in query order"""
+        if group is None:
+            raise ValueError("exact_below= routes queries by the size of their group: it needs group=")
+        if per_group is not None:
+            raise ValueError("exact_below= with per_group= is not supported: inside one group the cap would just cut k")
+        if isinstance(allowed, AllowSet):
+            raise TypeError("exact_below=: allowed= takes a bool mask of length N or row ids here (knn_group's); an "
+                            "AllowSet is laid out by list position")
+        if isinstance(exact_below, (bool, np.bool_)) or not isinstance(exact_below, (int, np.integer)):
+            raise TypeError("exact_below: None or an int, the number of rows below which a group is searched exactly")
+        if exact_below < 0:
+            raise ValueError("exact_below: a number of rows >= 0")
+        nq = len(qs)
+        group = query_groups(group, nq)
+        if between is not None:
+            self._ranges(between, nq)
+            cols = 1 if self.values.ndim == 1 else self.values.shape[1]
+            between = (_bound_array(between[0], "lo", nq, cols), _bound_array(between[1], "hi", nq, cols))
+        if tags is not None:
+            tag_mode_of(tags_mode)
+            tags = query_tags(tags, nq)
+        if exclude is not None and (np.ndim(exclude) != 1 or len(exclude) != nq):
+            raise ValueError(f"exclude: a 1-d array with one entry per query ({nq})")
+        dev = self._unsharded_device_index()
+        qs = np.array(qs, dtype=np.float32, order="C", copy=True)
+        sizes = np.zeros(nq, dtype=np.int64)
+        grouped = np.flatnonzero(group >= 0)
+        if len(grouped):
+            sizes[grouped] = dev.group_sizes(group[grouped])
+        routed = (group >= 0) & (sizes < int(exact_below))
+        parts = exact_below_parts(routed, between)
+
+        def sub(x, rows):
+            return None if x is None else np.asarray(x)[rows]
+
+        ids = np.full((nq, k), -1, dtype=np.int64)
+        dist = None
+        for exact, rows, btw in parts:
+            if exact:
+                got = self.knn_group(qs[rows], k, group[rows], allowed=allowed, exclude=sub(exclude, rows),
+                                     tags=sub(tags, rows), tags_mode=tags_mode, between=btw,
+                                     return_distances=return_distances)
+            else:
+                got = self.query_batch(qs[rows], k, n_probes, pass_1, allowed=allowed,
+                                       return_distances=return_distances, exclude=sub(exclude, rows), group=group[rows],
+                                       tags=sub(tags, rows), tags_mode=tags_mode, between=btw)
+            if return_distances:
+                if dist is None:
+                    dist = np.full((nq, k), np.inf, dtype=got[1].dtype)
+                ids[rows], dist[rows] = got
+            else:
+                ids[rows] = got
+        if return_distances and dist is None:       # (no query at all)
+            dist = np.full((nq, k), np.inf, dtype=np.float64 if np.asarray(self.data).dtype == np.float64 else np.float32)
+        return (ids, dist) if return_distances else ids
