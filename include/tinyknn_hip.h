@@ -962,6 +962,34 @@ int tk_index_knn_group(tk_index *ix, const float *q, int64_t nq, int k, const in
                        const int64_t *between, int64_t *out_ids, void *out_dist);
 int tk_index_group_sizes(tk_index *ix, const int32_t *group, int64_t n, int64_t *out);
 int tk_index_group_rows(tk_index *ix, int64_t *info4);
+/* The exact k nearest rows inside each query's value range (value_exact.hip): what tk_index_knn_brute_ex
+ * answers under `between` among the rows that are STORED, at a cost that follows the number of rows ONE column of the
+ * range admits instead of N.  A range over one column is a contiguous span of the rows sorted by that column; query i
+ * walks the shortest such span among the columns it bounds (ties: the lowest column) and tests every condition given
+ * on each row of it, by row id — the formulas of the restricted call above.  Ranked as tk_index_knn_group ranks: the k
+ * smallest (rescoring distance, row id), the same bits as that call's and the query calls' distances.
+ *   between (nq, C, 2)  REQUIRED: inclusive int64 keys (lo, hi) per value column, INT64_MIN / INT64_MAX for an end that
+ *                   is not bounded.  A query that bounds no column: TK_ERR_ARG and nothing is run (an unrestricted
+ *                   query is tk_index_knn_brute's or tk_index_query_batch's to answer).  lo > hi: a row of -1.
+ *   allowed_mask / exclude / group (-1: any) / tags, tag_mode   as above (host arrays, NULL: not given)
+ * Outputs, stores, k, N, d as tk_index_knn_group.  One workgroup per query walks the span, so a wide range is
+ * answered slowly: tk_index_knn_brute_ex(between) is the call there.
+ * Two tables are made by the first call that needs them (each synchronises the device: not inside a stream capture):
+ * per value column the row ids ascending by (key, row id) — a radix sort on the device over all 64 key bits; 4 N bytes
+ * per column stay, about 24 N bytes of work memory while it is made — made again after tk_index_set_values and by
+ * nothing else; and tk_index_knn_group's N-bit map of the stored rows.  Calls that do not ask for them never make them.
+ * TK_ERR_STATE with the query calls' texts where the values (or, given group / tags, the groups / tags) do not cover
+ * all N rows.  Synchronous; not for a list-sharded index.
+ * tk_index_range_sizes: for n queries' ranges (host, (n, C, 2)) out_len[i] = the length of the span query i would
+ * walk and out_col[i] its column: (N, -1) for a query that bounds no column, 0 for an empty interval.  Counted over all
+ * N rows, the removed ones too — what the walk costs, and an upper bound on the rows that pass.  It makes the first
+ * table where it is missing.
+ * tk_index_value_rows: info4 = {that table exists for the current values, its bytes, times one was made, columns}. */
+int tk_index_knn_between(tk_index *ix, const float *q, int64_t nq, int k, const int64_t *between,
+                         const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
+                         const uint64_t *tags, int tag_mode, int64_t *out_ids, void *out_dist);
+int tk_index_range_sizes(tk_index *ix, const int64_t *between, int64_t n, int64_t *out_len, int32_t *out_col);
+int tk_index_value_rows(tk_index *ix, int64_t *info4);
 
 /* ---- list-sharded index over `world` ranks, one process per GPU --------
  * The inverted lists (ivf.py:100-102) are partitioned by cluster id: owner[l] is the rank

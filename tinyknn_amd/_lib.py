@@ -38,7 +38,8 @@ OPT_PAIR_NQ, OPT_LABELS24 = 8, 9
 # tk_index_last_replay: the forms of a batch's heap replay (TK_REPLAY_*)
 REPLAY_PAIR, REPLAY_LANES, REPLAY_PACKED_DISTINCT, REPLAY_LANES_TWIN, REPLAY_LANES_DEDUPE, REPLAY_PACKED, REPLAY_GENERAL = range(7)
 REPLAY_NAMES = ("pair", "lanes", "packed_distinct", "lanes_twin", "lanes_dedupe", "packed", "general")
-# tk_index_knn_group (group_exact.hip: GX_TILE, GX_CAP): rows of a group's span per pass, entries of the candidate buffer
+# tk_index_knn_group / tk_index_knn_between (span_exact.h: GX_TILE, GX_CAP): rows of a span per pass, entries of the
+# candidate buffer
 GROUP_EXACT_TILE, GROUP_EXACT_CAP = 256, 2048
 
 SIGNATURES = {
@@ -235,6 +236,10 @@ SIGNATURES = {
                                      C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),
     "tk_index_group_sizes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _i64p]),
     "tk_index_group_rows": (C.c_int, [C.c_void_p, _i64p]),
+    "tk_index_knn_between": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int, _i64p, C.c_void_p]),
+    "tk_index_range_sizes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _i64p, _i32p]),
+    "tk_index_value_rows": (C.c_int, [C.c_void_p, _i64p]),
     "tk_index_set_pipeline": (C.c_int, [C.c_void_p, C.c_int]),
     "tk_index_set_coalesce": (C.c_int, [C.c_void_p, C.c_int]),
     "tk_index_join": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -92,7 +92,7 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->twin_list, &ix->twin_off, &ix->row_pos_off, &ix->row_pos, &ix->groups.by_row,
                       &ix->groups.table, &ix->tags.by_row, &ix->tags.table, &ix->values.by_row,
                       &ix->values.table, &ix->groups.span_rows, &ix->groups.span_gid, &ix->groups.span_off,
-                      &ix->stored_bits, &ix->gx_begin, &ix->gx_len};
+                      &ix->stored_bits, &ix->gx_begin, &ix->gx_len, &ix->values.span_rows, &ix->gx_col};
     for (DevBuf *b : bufs) b->release();
     for (Work &w : ix->works) w.release();
     // (the internal streams belong to the process: shared_streams below)

@@ -186,6 +186,9 @@ struct TkRowTable {
     // The groups alone (group_exact.hip): every row id gathered by group id — span_rows[N] int32, a group's rows one
     // contiguous span, ascending; span_gid[G] the sorted distinct ids; span_off[G + 1] where each span begins.  Made by
     // the first call that needs it, for ONE upload of the values: set_gen counts them (row_table_set), not the lists.
+    // The values (value_exact.hip) keep one thing of the kind, with the same lifetime: span_rows[C][N] int32, column c's
+    // plane the row ids ascending by (key of column c, row id) — a range over one column is a contiguous span of it.
+    // span_gid / span_off stay empty there; span_groups is the number of columns the planes were made for.
     DevBuf span_rows, span_gid, span_off;
     int64_t span_groups = 0;
     uint64_t set_gen = 0;
@@ -257,6 +260,7 @@ struct tk_index {
     DevBuf br_ynorm, br_vals, br_tau, br_cand, br_count, br_out, br_q, br_sample;   // tk_index_knn_brute
     DevBuf br_dist, br_mask, br_exclude, br_group, br_tags, br_ranges;              // ... and what _ex adds
     DevBuf gx_begin, gx_len;                                                        // tk_index_knn_group: a query's span
+    DevBuf gx_col;                                                                  // tk_index_knn_between: ... and its column
     int rot_d_pad = 0;
     int rank = 0, world = 1;
     bool sharded = false;
@@ -536,6 +540,10 @@ int row_table_covers(const tk_index *ix, const TkRowTable &t);    // TK_ERR_STAT
 int row_table_info(const tk_index *ix, const TkRowTable &t, int64_t *info4);
 int group_table_ensure(tk_index *ix);       // groups.hip
 int group_rows_ensure(tk_index *ix);        // group_rows.hip: the rows by group of the groups the index has now
+int value_rows_ensure(tk_index *ix);        // value_rows.hip: the rows in value order, per column, of the values it has now
+// group_exact.hip: the N-bit map of stored rows of the current lists (made now if not: synchronises the device);
+// call: the entry point that asks, named in the error where the map cannot be made
+int stored_bits_ensure(tk_index *ix, const char *call);
 int tag_table_ensure(tk_index *ix);         // tags.hip
 int value_table_ensure(tk_index *ix);       // between.hip
 inline int TkCallRestrict::ensure_tables(tk_index *ix, int64_t nq) const

@@ -13,7 +13,8 @@
 //                   holds its id.  An N-bit map (bit r: label r occurs), made from the labels by one kernel per layout
 //                   of the lists (lists_gen): N / 8 bytes, 32 times smaller than the row-position table of rows.hip,
 //                   and one L2-resident word per row where that table costs two loads.
-//   the kernel      one workgroup per query.  The span is walked in tiles of GX_TILE rows, a lane a row: rows that are
+//   the kernel      (the walk itself is span_exact.h's, shared with value_exact.hip; group_exact_kernel hands it the
+//                   group's span.)  One workgroup per query.  The span is walked in tiles of GX_TILE rows, a lane a row: rows that are
 //                   not stored or fail a restriction (allowed bit, exclude, tags any / all, ranges — by row id, the
 //                   formulas of brute.hip's restricted form; the query's own attributes sit in scalar registers) are
 //                   dropped, the others get sqdist_row<T, TY> (sqdist_row.h: the rescoring's distance, numpy's einsum
@@ -29,40 +30,11 @@
 // one group share row reads only through L2.
 #include "api_internal.h"
 #include "sqdist_row.h"
+#include "span_exact.h"
 
-#define GX_THREADS 256
+// (stated here as span_exact.h states them: the walk, GxKey and gx_lds_bytes live there, shared with value_exact.hip)
 #define GX_TILE 256       // rows of the span per pass of the workgroup: a lane a row
 #define GX_CAP 2048       // entries of the candidate buffer; k + GX_TILE <= GX_CAP for every k <= 1024
-
-// the distance as an unsigned key that orders as the distance does (a NaN, which no finite data gives, sorts last)
-template <typename T> struct GxKey;
-template <> struct GxKey<float> {
-    typedef uint32_t type;
-    __device__ static type of(float v)
-    {
-        const uint32_t u = __float_as_uint(v);
-        return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    __device__ static float back(type u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-};
-template <> struct GxKey<double> {
-    typedef uint64_t type;
-    __device__ static type of(double v)
-    {
-        const uint64_t u = (uint64_t)__double_as_longlong(v);
-        return (u >> 63) ? ~u : (u | (1ull << 63));
-    }
-    __device__ static double back(type u)
-    {
-        return __longlong_as_double((long long)((u >> 63) ? (u & ~(1ull << 63)) : ~u));
-    }
-};
-
-// LDS: kd[GX_CAP] distance keys | kid[GX_CAP] row ids | x[d] the query in T
-static size_t gx_lds_bytes(int d, size_t key_bytes, size_t t_bytes)
-{
-    return (size_t)GX_CAP * (key_bytes + 4) + (size_t)d * t_bytes;
-}
 
 // r: the restriction's device arrays (TkBruteRestrict; its group fields are not read: the span IS the group).
 // begin / len: the query's span of span_rows (len 0: an id no row carries).  stored: the N-bit map.
@@ -76,100 +48,8 @@ __global__ __launch_bounds__(GX_THREADS) void group_exact_kernel(const float *__
                                                                  const TkBruteRestrict r, int k,
                                                                  int64_t *__restrict__ out, T *__restrict__ out_d)
 {
-    typedef typename GxKey<T>::type K;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    K *kd = (K *)smem;
-    int32_t *kid = (int32_t *)(kd + GX_CAP);
-    T *xs = (T *)(kid + GX_CAP);
-    __shared__ int s_count;
-    const int tid = threadIdx.x;
     const int64_t qi = blockIdx.x;
-    for (int t = tid; t < d; t += GX_THREADS) xs[t] = (T)q[qi * d + t];
-    if (tid == 0) s_count = 0;
-    // the query's own attributes, once
-    const int64_t q_ex = r.exclude ? r.exclude[qi] : -1;
-    const uint64_t q_tags = r.tags ? r.tags[qi] : 0;
-    int64_t q_lo[4] = {0, 0, 0, 0}, q_hi[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-        if (c < r.cols) {
-            q_lo[c] = r.ranges[(qi * r.cols + c) * 2];
-            q_hi[c] = r.ranges[(qi * r.cols + c) * 2 + 1];
-        }
-    const int n = len[qi];
-    const int32_t *span = span_rows + begin[qi];
-    K tau = ~(K)0;          // the bound: the k-th distance key of the last cut
-    int kept = 0;           // entries the buffer holds at most (an upper bound, the same in every lane)
-
-    // Sort what the buffer holds by (distance, row id), keep the k best, tighten the bound.  Every lane arrives.
-    auto cut = [&]() {
-        __syncthreads();                        // every append so far is in LDS (and the first time: xs, s_count)
-        const int nc = s_count < GX_CAP ? s_count : GX_CAP;
-        int P = 1;
-        while (P < nc) P <<= 1;
-        for (int e = nc + tid; e < P; e += GX_THREADS) {
-            kd[e] = ~(K)0;
-            kid[e] = 0x7fffffff;
-        }
-        __syncthreads();
-        for (int size = 2; size <= P; size <<= 1)
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int e = tid; e < P / 2; e += GX_THREADS) {
-                    const int lo = (e / stride) * 2 * stride + (e % stride), hi = lo + stride;
-                    const bool up = (lo & size) == 0;
-                    const K a = kd[lo], b = kd[hi];
-                    const int32_t ia = kid[lo], ib = kid[hi];
-                    const bool gt = a > b || (a == b && ia > ib);
-                    if (gt == up) {
-                        kd[lo] = b; kd[hi] = a;
-                        kid[lo] = ib; kid[hi] = ia;
-                    }
-                }
-                __syncthreads();
-            }
-        kept = nc < k ? nc : k;
-        if (nc >= k) tau = kd[k - 1];
-        if (tid == 0) s_count = kept;
-        __syncthreads();                        // the count is back before the next append, tau read before it
-    };
-
-    __syncthreads();                            // xs and the zero count, before the first append
-    for (int t0 = 0; t0 < n; t0 += GX_TILE) {
-        if (kept + GX_TILE > GX_CAP) cut();
-        kept += GX_TILE;
-        const int t = t0 + tid;
-        if (t >= n) continue;
-        const int32_t rid = span[t];
-        bool ok = (stored[rid >> 5] >> (rid & 31)) & 1u;
-        if (r.allowed) ok &= (r.allowed[rid >> 5] >> (rid & 31)) & 1u;
-        ok &= (int64_t)rid != q_ex;
-        if (!ok) continue;
-        if (q_tags != 0) {
-            const uint64_t rt = r.row_tags[rid];
-            if (!(r.tag_mode ? (rt & q_tags) == q_tags : (rt & q_tags) != 0)) continue;
-        }
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-            if (c < r.cols) {
-                const int64_t key = r.row_keys[c * r.n_rows + rid];
-                ok &= q_lo[c] <= key && key <= q_hi[c];
-            }
-        if (!ok) continue;
-        const T dv = sqdist_row<T, TY>(rows + (int64_t)rid * d, xs, d);
-        const K key = GxKey<T>::of(dv);
-        if (key <= tau) {
-            const int pos = atomicAdd(&s_count, 1);
-            if (pos < GX_CAP) {                 // (always: kept bounds the count)
-                kd[pos] = key;
-                kid[pos] = rid;
-            }
-        }
-    }
-    cut();
-    for (int e = tid; e < k; e += GX_THREADS) {
-        out[qi * k + e] = e < kept ? (int64_t)kid[e] : -1;
-        if (out_d) out_d[qi * k + e] = e < kept ? GxKey<T>::back(kd[e]) : (T)__builtin_huge_valf();
-    }
+    span_exact_body<T, TY, false>(q, d, rows, span_rows + begin[qi], len[qi], stored, r, k, out, out_d);
 }
 
 // group ids -> their spans: the lower bound of g among the sorted distinct ids; (0, 0) for an id no row carries
@@ -204,10 +84,11 @@ __global__ __launch_bounds__(256) void stored_bits_kernel(const int64_t *__restr
 }
 
 // The stored-row map of the index's current lists: made on the first call, and again after the lists changed.
-static int stored_bits_ensure(tk_index *ix)
+// call: the entry point that asks (tk_index_knn_group, tk_index_knn_between), named where the map cannot be made.
+int stored_bits_ensure(tk_index *ix, const char *call)
 {
     if (ix->stored_state.current(ix->lists_gen)) return TK_OK;
-    TRY(table_may_build(ix, "stored-row", "tk_index_knn_group"));
+    TRY(table_may_build(ix, "stored-row", call));
     ix->stored_state.ok = false;
     const size_t bytes = (size_t)((ix->N + 31) / 32) * 4;
     TRY(ix->stored_bits.ensure(bytes));
@@ -278,7 +159,7 @@ extern "C" int tk_index_knn_group(tk_index *ix, const float *q, int64_t nq, int 
     if (nq == 0) return TK_OK;
     TRY(flush_pending(ix));
     TRY(group_rows_ensure(ix));
-    TRY(stored_bits_ensure(ix));
+    TRY(stored_bits_ensure(ix, "tk_index_knn_group"));
     TkBruteRestrict r{};
     r.n_rows = ix->N;
     r.tag_mode = tag_mode;

@@ -439,6 +439,25 @@ def query_ranges(between, nq, cols, kind):
     return out
 
 
+def unbounded_queries(keys):
+    """bool (nq,) of query_ranges' (nq, cols, 2) keys: the query bounds no column (every end INT64_MIN / INT64_MAX) —
+    what knn_between refuses and query_batch(between=, exact_below=) never routes"""
+    keys = np.asarray(keys)
+    return ((keys[:, :, 0] == INT64_MIN) & (keys[:, :, 1] == INT64_MAX)).all(axis=1)
+
+
+def ranges_length(between, cols):
+    """The number of queries a `between=` argument speaks for by itself on `cols` columns (_bound_array's shape rule):
+    the rows of a 2-d end, the length of a 1-d end of one column; 1 where every end is None, a scalar or per column."""
+    if not isinstance(between, (tuple, list)) or len(between) != 2:
+        raise TypeError("between: a pair (lo, hi), each None, a number or an array")
+    for b in between:
+        a = None if b is None else np.asarray(b)
+        if a is not None and (a.ndim == 2 or (a.ndim == 1 and cols == 1)):
+            return a.shape[0]
+    return 1
+
+
 def host_values(values, n, what, like=None):
     """The host copy of a `values` argument for n rows: the caller's array in its own dtype, checked as the device will
     take it (value_keys).  like (the index's values, for new rows): in its shape and of its kind (ValueError),
@@ -1407,6 +1426,69 @@ class DeviceIndex:
         o = np.zeros(4, dtype=np.int64)
         _lib.check(_lib.lib().tk_index_group_rows(self._h, _lib.ptr(o, _lib._i64p)))
         return {"built": bool(o[0]), "bytes": int(o[1]), "builds": int(o[2]), "groups": int(o[3])}
+
+    def knn_between(self, qn, k, between, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
+                    return_distances=False):
+        """The exact k nearest STORED rows inside each query's value range (tk_index_knn_between) for
+        normalised queries: outputs as knn_group's — (nq, k) int64 ids ascending by (distance, row id), ending in -1
+        where fewer than k rows pass; with return_distances (ids, dists), the rescoring's exact squared distances,
+        +inf beside -1.  between: (lo, hi) as query_batch's (required); every query must bound at least one column
+        (ValueError naming the first that does not: an unrestricted query is knn_brute's or query_batch's).  A query
+        walks the rows that ONE column of its range admits — the column that admits the fewest (range_sizes) — in
+        value order and tests every condition on them, so the cost follows that number; one workgroup walks a span, so
+        for wide ranges knn_brute(between=) is the call.  Rows taken out by remove() never come back.  allowed /
+        exclude / group (-1: any) / tags, tags_mode: as knn_brute's; an AllowSet is refused (TypeError).  Every vector
+        store.  Not for a list-sharded index."""
+        if isinstance(allowed, AllowSet):
+            raise TypeError("knn_between: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
+                            "list position")
+        if _dev_is_sharded(self) or self._source is not None:
+            raise RuntimeError("knn_between is not supported on a list-sharded index")
+        qn = np.ascontiguousarray(qn, dtype=np.float32)
+        assert qn.ndim == 2 and qn.shape[1] == self.d
+        nq = qn.shape[0]
+        if between is None:
+            raise TypeError("knn_between: between= is required: a pair (lo, hi)")
+        between = np.ascontiguousarray(self._ranges_of(between, nq))
+        free = np.flatnonzero(unbounded_queries(between))
+        if len(free):
+            raise ValueError(f"knn_between: query {int(free[0])} bounds no column (an unrestricted query is knn_brute's "
+                             "or query_batch's to answer)")
+        mask = None if allowed is None else AllowSet.mask_of(allowed, self.N)
+        exclude = None if exclude is None else self._exclude_of(exclude, nq)
+        group = None if group is None else query_groups(group, nq)
+        tags, mode = (None, 0) if tags is None else (query_tags(tags, nq), tag_mode_of(tags_mode))
+        out = np.full((nq, k), -1, dtype=np.int64)
+        dist = np.full((nq, k), np.inf, dtype=np.float64 if self._f64 else np.float32) if return_distances else None
+
+        def host(a):
+            return None if a is None else a.ctypes.data
+
+        _lib.check(_lib.lib().tk_index_knn_between(
+            self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), host(between), host(mask), host(exclude), host(group),
+            host(tags), mode, _lib.ptr(out, _lib._i64p), host(dist)))
+        return (out, dist) if return_distances else out
+
+    def range_sizes(self, between, nq=None):
+        """(len, col) per query of a `between=` argument (tk_index_range_sizes): the number of rows of the span
+        knn_between would walk for it — the rows that the column admitting the fewest admits — and that column; (N, -1)
+        for a query that bounds no column, length 0 for an empty interval.  int64 / int32.  Counted over all N rows, the
+        rows remove() took out too: what the walk costs, and an upper bound on the rows that pass.  nq: the number
+        of queries where the argument does not say (scalars for every query); default: the length of its arrays, or 1."""
+        if nq is None:
+            nq = ranges_length(between, self._value_cols or 1)
+        keys = np.ascontiguousarray(self._ranges_of(between, int(nq)))
+        length = np.zeros(len(keys), dtype=np.int64)
+        col = np.zeros(len(keys), dtype=np.int32)
+        _lib.check(_lib.lib().tk_index_range_sizes(self._h, keys.ctypes.data, len(keys), _lib.ptr(length, _lib._i64p),
+                                                   _lib.ptr(col, _lib._i32p)))
+        return length, col
+
+    def value_rows(self):
+        """The rows in value order behind knn_between (tk_index_value_rows): dict(built, bytes, builds, columns)."""
+        o = np.zeros(4, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_value_rows(self._h, _lib.ptr(o, _lib._i64p)))
+        return {"built": bool(o[0]), "bytes": int(o[1]), "builds": int(o[2]), "columns": int(o[3])}
 
     def query_batch_dev(self, qn_ptr, qpq_ptr, qpq_is_f64, nq, k, n_probes, out_ptr,
                         pass_1=None, stream=0, done_event=None, *, allowed=None, dist_ptr=None, exclude_ptr=None,
@@ -2514,6 +2596,34 @@ class IVF:
         return dev.knn_group(qn, k, group, allowed=allowed, exclude=exclude, tags=tags, tags_mode=tags_mode,
                              between=between, return_distances=return_distances)
 
+    def knn_between(self, qs, k, between, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
+                    return_distances=False):
+        """The exact k nearest stored rows inside each raw query's value range (DeviceIndex.knn_between on the
+        prepared queries): (nq, k) int64 ids ascending by (distance, row id), ending in -1 where fewer
+        than k rows pass; with return_distances (ids, dists), the distances of query_batch(return_distances=True),
+        +inf beside -1.  between: (lo, hi) as query_batch's; every query must bound a column (ValueError).  The cost
+        follows the number of rows the query's narrowest column admits — the call for narrow ranges, where the probed
+        lists hold too few passing rows; knn_brute(between=) is the one for wide ranges, query_batch(between=,
+        exact_below=) routes a batch by length.  The other restrictions as knn_brute's; allowed: a bool mask of length
+        N or row ids, not an AllowSet.  Not for a list-sharded index."""
+        if isinstance(allowed, AllowSet):
+            raise TypeError("knn_between: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
+                            "list position")
+        if between is None:
+            raise TypeError("knn_between: between= is required: a pair (lo, hi)")
+        free = np.flatnonzero(unbounded_queries(self._ranges(between, len(qs))))
+        if len(free):
+            raise ValueError(f"knn_between: query {int(free[0])} bounds no column (an unrestricted query is knn_brute's "
+                             "or query_batch's to answer)")
+        if tags is not None:
+            tag_mode_of(tags_mode)
+        if group is not None:
+            group = query_groups(group, len(qs))
+        dev = self._unsharded_device_index()
+        qn, _ = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
+        return dev.knn_between(qn, k, between, allowed=allowed, exclude=exclude, group=group, tags=tags,
+                               tags_mode=tags_mode, return_distances=return_distances)
+
     def allow(self, ids_or_mask):
         """Prepare an allowed set (a bool mask over the N rows, or row ids) for `allowed=`: made once on the
         device, reused across calls; .close() frees it, len() = allowed stored rows."""
@@ -2645,8 +2755,11 @@ class IVF:
         exact_below: None, or a number of rows T, with group=: the queries whose group carries fewer than T rows
         (group_sizes) are answered exactly by knn_group under the call's other restrictions — the probed lists hold
         too few rows of a small group — and all others, every query with group -1 among them, by this call without
-        it; the rows come back in query order, both parts with the same kind of distance.  Not with
-        per_group= (inside one group the cap would just cut k), an AllowSet or fast=True."""
+        it; the rows come back in query order, both parts with the same kind of distance.  With
+        between= and no group=: the queries that bound a column and whose range's span (range_sizes) is shorter than T
+        rows are answered exactly by knn_between, all others by this call without it; with both, the
+        routing is by group.  Not with per_group= (inside one group the cap would just cut k), an AllowSet or
+        fast=True."""
         if exact_below is not None:
             if fast:
                 raise NotImplementedError("IVF.query_batch: fast=True with exact_below= is not supported; "
@@ -2697,10 +2810,12 @@ class IVF:
 
     def _query_batch_exact_below(self, qs, k, n_probes, pass_1, exact_below, allowed, return_distances, exclude, group,
                                  tags, tags_mode, between, per_group):
-        """query_batch(group=, exact_below=T): the refusals, the split by group size, the two calls on their subsets
-        (an empty part runs nothing), the rows put back in query order"""
-        if group is None:
-            raise ValueError("exact_below= routes queries by the size of their group: it needs group=")
+        """query_batch(group= / between=, exact_below=T): the refusals, the split — by group size where group= is given,
+        else by the length of the range's span — the two calls on their subsets (an empty part runs nothing), the rows
+        put back in query order"""
+        if group is None and between is None:
+            raise ValueError("exact_below= routes queries by the size of their group or the length of their range: it "
+                             "needs group= or between=")
         if per_group is not None:
             raise ValueError("exact_below= with per_group= is not supported: inside one group the cap would just cut k")
         if isinstance(allowed, AllowSet):
@@ -2711,9 +2826,11 @@ class IVF:
         if exact_below < 0:
             raise ValueError("exact_below: a number of rows >= 0")
         nq = len(qs)
-        group = query_groups(group, nq)
+        by_group = group is not None
+        if by_group:
+            group = query_groups(group, nq)
         if between is not None:
-            self._ranges(between, nq)
+            keys = self._ranges(between, nq)
             cols = 1 if self.values.ndim == 1 else self.values.shape[1]
             between = (_bound_array(between[0], "lo", nq, cols), _bound_array(between[1], "hi", nq, cols))
         if tags is not None:
@@ -2724,10 +2841,17 @@ class IVF:
         dev = self._unsharded_device_index()
         qs = np.array(qs, dtype=np.float32, order="C", copy=True)
         sizes = np.zeros(nq, dtype=np.int64)
-        grouped = np.flatnonzero(group >= 0)
-        if len(grouped):
-            sizes[grouped] = dev.group_sizes(group[grouped])
-        routed = (group >= 0) & (sizes < int(exact_below))
+        if by_group:
+            grouped = np.flatnonzero(group >= 0)
+            if len(grouped):
+                sizes[grouped] = dev.group_sizes(group[grouped])
+            routed = (group >= 0) & (sizes < int(exact_below))
+        else:       # by the span a range would walk; a query that bounds no column is the restricted call's
+            bounded = np.flatnonzero(~unbounded_queries(keys))
+            if len(bounded):
+                sizes[bounded] = dev.range_sizes(tuple(None if b is None else b[bounded] for b in between),
+                                                 len(bounded))[0]
+            routed = ~unbounded_queries(keys) & (sizes < int(exact_below))
         parts = exact_below_parts(routed, between)
 
         def sub(x, rows):
@@ -2736,14 +2860,17 @@ class IVF:
         ids = np.full((nq, k), -1, dtype=np.int64)
         dist = None
         for exact, rows, btw in parts:
-            if exact:
+            if exact and by_group:
                 got = self.knn_group(qs[rows], k, group[rows], allowed=allowed, exclude=sub(exclude, rows),
                                      tags=sub(tags, rows), tags_mode=tags_mode, between=btw,
                                      return_distances=return_distances)
+            elif exact:
+                got = self.knn_between(qs[rows], k, btw, allowed=allowed, exclude=sub(exclude, rows),
+                                       tags=sub(tags, rows), tags_mode=tags_mode, return_distances=return_distances)
             else:
                 got = self.query_batch(qs[rows], k, n_probes, pass_1, allowed=allowed,
-                                       return_distances=return_distances, exclude=sub(exclude, rows), group=group[rows],
-                                       tags=sub(tags, rows), tags_mode=tags_mode, between=btw)
+                                       return_distances=return_distances, exclude=sub(exclude, rows),
+                                       group=sub(group, rows), tags=sub(tags, rows), tags_mode=tags_mode, between=btw)
             if return_distances:
                 if dist is None:
                     dist = np.full((nq, k), np.inf, dtype=got[1].dtype)
