@@ -12,7 +12,9 @@ from conftest import G6_TAGS, golden
 from per_group_reference import capped_from_heaps, heaps_of
 from store_reference import fixture_ivf, oracle_index
 
-K, N_PROBES = 10, 5                     # heaps of (5 + 1) * 10 + 1 = 61 entries: the staged kernels, one 64-rank chunk
+# heaps of (5 + 1) * 10 + 1 = 61 entries: the staged kernels, one 64-rank chunk.  (The pass_1 = 300 legs of the GPU file
+# take the lane-per-row kernel under every form; larger staged heaps are tests/per_group_edge_shapes.py's.)
+K, N_PROBES = 10, 5
 ASSIGNMENTS = ("mod3", "oct", "one", "own")
 CAPS = (1, 2, K, "mix")                 # "mix": a per-query array of 0, 1 and 3
 

@@ -110,7 +110,8 @@ def test_every_rescoring_form(tk, oracle):
     m = shapes.caps("mix", len(qn))
     m[:4] = 1
     want = capped_from_heaps(oracle, ox, qn, shapes.heaps("syn", N_PROBES), m, groups, K)
-    # pass_1 = 300: a heap beyond the staged kernels' 256 entries, the lane-per-row kernel whatever the form
+    # pass_1 = 300: a heap beyond the staged kernels' 256 entries: the lane-per-row kernel alone, whatever the form is
+    # set to (the staged kernels beyond one chunk: tests/test_per_group_edges_gpu.py)
     big = capped_batch(oracle, ox, qn, m, groups, K, N_PROBES, pass_1=300)
     try:
         for form in (0, 1, 2):
