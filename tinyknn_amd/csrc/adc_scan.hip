@@ -638,7 +638,7 @@ __global__ __launch_bounds__(256, (FORM == 1 ? 4 : 3)) void scan_units_kernel(
     uint4 *lw = tk_lds_tables + (threadIdx.x >> 6) * (gmax * TK_UNIT_Q * M);
     const int U = unit_prefix[n_lists];
     int *ticket = const_cast<int *>(unit_prefix) + TK_TICKET_OFF(n_lists);
-    ticketed_blocks((U + 63) >> 6, ticket, [&](int blk) {
+    ticketed_blocks<TK_START_WAVE>((U + 63) >> 6, ticket, [&](int blk) {
         if (FORM != 0)
             scan_units_block_lds<ORDER, SIGNED, FORM == 1>(codes, P, tables, M, list_chunk_off, n_lists,
                                                 unit_prefix, pair_off, pair_q, pair_f0, dist, cap,
@@ -678,7 +678,7 @@ __global__ __launch_bounds__(256, (FORM == 1 ? 4 : 3)) void scan_units2_kernel(T
                       : const_cast<int *>(upc) + TK_TICKET_OFF(jobs[2].n_lists);
     // (captures by VALUE: by reference, `which == 0 ? UA : ...` becomes a select between the addresses
     // of the closure's members, and the closure goes to scratch)
-    ticketed_blocks(NBA + NBB + NBC, ticket, [=](int blk) {
+    ticketed_blocks<TK_START_WAVE>(NBA + NBB + NBC, ticket, [=](int blk) {
         // one copy of the block body; `which` is wave-uniform
         const int which = blk < NBA ? 0 : (blk < NBA + NBB ? 1 : 2);
         tk_kernarg_job &j = jobs[which];
@@ -795,8 +795,8 @@ struct PairSets {
 
 // Units of the plain kernel (plain_scan.hip: one wave per unit): a tile of 32 of a list's pairs
 // times a range of at most K chunk pairs, numbered (list, tile, range) with the range fastest —
-// the waves of a workgroup take neighbouring units, i.e. ranges of ONE tile, and read the same
-// table rows.  unit_prefix[l] = units before list l.
+// the waves of an XCD draw consecutive units (tickets.h: TK_START_XCD), i.e. ranges of ONE tile and
+// tiles of ONE list, and find the same table rows and codes in their L2.  unit_prefix[l] = units before list l.
 __device__ __forceinline__ int plain_units_of(int cnt, int C, int K)
 {
     if (cnt <= 0 || C <= 0) return 0;

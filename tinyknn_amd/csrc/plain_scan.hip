@@ -37,7 +37,8 @@
 // 26 table rows of its lane's query straight into the B registers, walks the unit's chunk pairs with
 // two code groups in flight (ONE 16-byte load per lane and chunk pair, re-sliced through a per-wave
 // LDS region), and writes its outputs through an LDS tile as whole lines per query.  Units are
-// handed out like the exact kernel's blocks (tickets.h).
+// drawn from the work counters of tickets.h, a wave starting at the counter of the XCD it runs on:
+// consecutive units share table rows and codes, and so meet in one L2.
 #include <limits.h>
 #include <stdlib.h>
 
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(256, 2) void scan_plain_wave_kernel(TkScanJob j, in
     uint32_t *stw = st + (lch * 4) * PS + lp;
     const uint32_t *rd = st + ((r >> 4) * 4 + (rr >> 2)) * PS;
 
-    ticketed_blocks(n_units, ticket, [&](int u) {
+    ticketed_blocks<TK_START_XCD>(n_units, ticket, [&](int u) {
         TK_STAMP(5);        // between units: ticket
         const int4 d = ((const int4 *)j.unit_desc4)[u];
         const int l = __builtin_amdgcn_readfirstlane(d.x), t = __builtin_amdgcn_readfirstlane(d.y);
