@@ -932,6 +932,30 @@ int tk_index_knn_brute(tk_index *ix, const float *q, int64_t nq, int k, int64_t 
 int tk_index_knn_brute_ex(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
                           const int64_t *exclude, const int32_t *group, const uint64_t *tags, int tag_mode,
                           const int64_t *between, int64_t *out_ids, float *out_dist);
+/* Every row within a radius of each query, exactly (radius.hip): row j is a hit of query i iff it passes
+ * the query's restrictions — allowed_mask / exclude / group / tags, tag_mode / between exactly as
+ * tk_index_knn_brute_ex takes them, host arrays, NULL: not given — and part(i, j) <= radius[i], compared in float32,
+ * inclusive; part is the value that call reports in out_dist, bit for bit (the two share the tile loop), so for every
+ * k its ids are the first k entries of this call's list at radius = its k-th part value.  q: (nq, d) prepared
+ * queries; radius: (nq) float32, +inf (every passing row) and negative values (normally no row) allowed, NaN refused.
+ * The result is CSR: out_lims (nq + 1) int64 with out_lims[0] = 0, query i's hits at [out_lims[i], out_lims[i + 1]),
+ * *out_total = out_lims[nq].  Both are written before the total is compared with max_results (< 2^31): a total
+ * above it is TK_ERR_ARG with the total in the text, and no result is held — a list is never cut.  count_only: the
+ * count pass alone (max_results is not looked at, nothing is held; nq x N may exceed 2^31, the sums are int64).
+ * Otherwise the decoded result stays on the device, in buffers of the index, until the next call of this function on
+ * the index or its destruction; tk_index_radius_fetch copies it out: out_ids (total) int64 and out_dist (total, or
+ * NULL) float32 part values.  sorted != 0: every list ascending by (part, id) — knn_brute's order, the same bytes
+ * from run to run; 0: the order inside a list is unspecified (the sort is skipped).  tk_index_radius_fetch with no
+ * result held: TK_ERR_STATE.  Two passes over all N rows on the f32 matrix cores plus a segmented radix sort; the
+ * counts cross to the host between the passes (one synchronisation).  The vectors of removed rows stay in HBM, as for
+ * tk_index_knn_brute: allowed_mask with the surviving rows is the truth after a removal.
+ * Float32 vectors, d <= 128, N < 2^31; not for a list-sharded index; TK_ERR_STATE with the query calls' texts where
+ * group / tags / between is given and the index has no such values for all N rows.  Synchronous. */
+int tk_index_radius_brute(tk_index *ix, const float *q, int64_t nq, const float *radius, const uint8_t *allowed_mask,
+                          const int64_t *exclude, const int32_t *group, const uint64_t *tags, int tag_mode,
+                          const int64_t *between, int sorted, int count_only, int64_t max_results, int64_t *out_lims,
+                          int64_t *out_total);
+int tk_index_radius_fetch(tk_index *ix, int64_t *out_ids, float *out_dist);
 /* The exact k nearest rows inside each query's own group (group_exact.hip): what the restricted call
  * above answers for group[i] >= 0 among the rows that are STORED, at a cost that follows the size of the group instead
  * of N — a query reads the rows of its group and no other.  Ranked by the rescoring's distance (numpy's einsum order

@@ -1215,14 +1215,14 @@ static int brute_upload(DevBuf &b, const T *host, size_t n, const T *&dev)
     return TK_OK;
 }
 
-extern "C" int tk_index_knn_brute_ex(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
-                                     const int64_t *exclude, const int32_t *group, const uint64_t *tags, int tag_mode,
-                                     const int64_t *between, int64_t *out_ids, float *out_dist)
+// The restriction of a restricted exact call (tk_index_knn_brute_ex, tk_index_radius_brute) from the caller's host
+// arrays: the checks both make, the per-query arrays in the br_* workspace buffers, the by-row arrays of the index.
+// any = false: nothing was given and r is empty.
+static int brute_restrict(tk_index *ix, int64_t nq, const uint8_t *allowed_mask, const int64_t *exclude,
+                          const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between,
+                          TkBruteRestrict &r, bool &any)
 {
-    IXLOCK(ix);
-    ARGCHECK(ix && ix->have_data, "set_data first");
-    ARGCHECK(!ix->sharded, "list-sharded index: knn_brute with restrictions is not supported");
-    ARGCHECK(nq >= 0, "buffers");
+    r = TkBruteRestrict{};
     ARGCHECK(tag_mode == 0 || tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
     // the by-row arrays only: no list-order table is made or read
     if (group) TRY(row_table_covers(ix, ix->groups));
@@ -1230,10 +1230,8 @@ extern "C" int tk_index_knn_brute_ex(tk_index *ix, const float *q, int64_t nq, i
     if (between) TRY(row_table_covers(ix, ix->values));
     if (exclude)
         for (int64_t i = 0; i < nq; i++) ARGCHECK(exclude[i] >= -1 && exclude[i] < ix->N, "exclude: entries in [-1, N)");
-    if (!allowed_mask && !exclude && !group && !tags && !between)
-        return knn_brute(ix, q, nq, k, nullptr, true, out_ids, out_dist);
-    if (nq == 0) return TK_OK;
-    TkBruteRestrict r{};
+    any = allowed_mask || exclude || group || tags || between;
+    if (!any || nq == 0) return TK_OK;
     r.n_rows = ix->N;
     r.tag_mode = tag_mode;
     if (allowed_mask) {
@@ -1252,7 +1250,126 @@ extern "C" int tk_index_knn_brute_ex(tk_index *ix, const float *q, int64_t nq, i
         r.row_keys = ix->values.by_row.as<int64_t>();
         TRY(brute_upload(ix->br_ranges, between, (size_t)nq * 2 * r.cols, r.ranges));
     }
+    return TK_OK;
+}
+
+extern "C" int tk_index_knn_brute_ex(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
+                                     const int64_t *exclude, const int32_t *group, const uint64_t *tags, int tag_mode,
+                                     const int64_t *between, int64_t *out_ids, float *out_dist)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix && ix->have_data, "set_data first");
+    ARGCHECK(!ix->sharded, "list-sharded index: knn_brute with restrictions is not supported");
+    ARGCHECK(nq >= 0, "buffers");
+    TkBruteRestrict r;
+    bool any;
+    TRY(brute_restrict(ix, nq, allowed_mask, exclude, group, tags, tag_mode, between, r, any));
+    if (!any) return knn_brute(ix, q, nq, k, nullptr, true, out_ids, out_dist);
+    if (nq == 0) return TK_OK;
     return knn_brute(ix, q, nq, k, &r, true, out_ids, out_dist);
+}
+
+// ---------------------------------------------------------------------------
+// every row within a radius of each query (radius.hip): count pass, offsets on the host, fill pass,
+// segmented sort, decode; the decoded result stays in the index for tk_index_radius_fetch
+extern "C" int tk_index_radius_brute(tk_index *ix, const float *q, int64_t nq, const float *radius,
+                                     const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
+                                     const uint64_t *tags, int tag_mode, const int64_t *between, int sorted,
+                                     int count_only, int64_t max_results, int64_t *out_lims, int64_t *out_total)
+{
+    IXLOCK(ix);
+    if (ix) ix->rd_total = -1;          // whatever this call does, the result of the last one is gone
+    ARGCHECK(ix && ix->have_data, "set_data first");
+    ARGCHECK(!ix->sharded, "list-sharded index: radius_search is not supported");
+    ARGCHECK(ix->data_dtype != TK_DATA_F64, "float32 vectors only");
+    ARGCHECK(ix->data_dtype != TK_DATA_F16, "radius_search compares knn_brute's part values on float32 vectors: this "
+                                            "index stores them as half (store=\"float16\"); ask a float32 index");
+    ARGCHECK(ix->d <= 128, "d <= 128");
+    ARGCHECK(ix->N < (1ll << 31), "N < 2^31");
+    ARGCHECK(nq >= 0 && out_lims && out_total && (nq == 0 || (q && radius)), "buffers");
+    ARGCHECK(count_only || (max_results >= 0 && max_results < (1ll << 31)), "0 <= max_results < 2^31");
+    for (int64_t i = 0; i < nq; i++) ARGCHECK(radius[i] == radius[i], "radius: NaN");
+    TkBruteRestrict r;
+    bool any;
+    TRY(brute_restrict(ix, nq, allowed_mask, exclude, group, tags, tag_mode, between, r, any));
+    out_lims[0] = 0;
+    *out_total = 0;
+    if (nq == 0) {
+        if (!count_only) ix->rd_total = 0;
+        return TK_OK;
+    }
+    TRY(flush_pending(ix));
+    TRY(ix->br_ynorm.ensure((size_t)ix->N * 4));
+    TRY(ix->br_q.ensure((size_t)nq * ix->d * 4));
+    TRY(ix->rd_radius.ensure((size_t)nq * 4));
+    TRY(ix->rd_count.ensure((size_t)nq * 8 + 4));
+    HIPCHECK(hipMemcpy(ix->br_q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(ix->rd_radius.p, radius, (size_t)nq * 4, hipMemcpyHostToDevice));
+    const float *X = ix->br_q.as<float>(), *Y = ix->data.as<float>(), *rad = ix->rd_radius.as<float>();
+    float *yn = ix->br_ynorm.as<float>();
+    int *count = ix->rd_count.as<int>(), *slots = count + nq, *err = slots + nq;
+    const TkBruteRestrict *rp = any ? &r : nullptr;
+    if (tk_launch_radius_count(X, nq, ix->d, Y, ix->N, yn, rad, count, rp, nullptr))
+        return fail(TK_ERR_HIP, "tk_launch_radius_count: unsupported size / LDS attribute");
+    HIPCHECK(hipGetLastError());
+    std::vector<int> counts((size_t)nq);
+    HIPCHECK(hipMemcpy(counts.data(), count, (size_t)nq * 4, hipMemcpyDeviceToHost));     // (synchronises)
+    for (int64_t i = 0; i < nq; i++) out_lims[i + 1] = out_lims[i] + counts[(size_t)i];   // int64: nq x N may pass 2^31
+    const int64_t total = *out_total = out_lims[nq];
+    if (count_only) return TK_OK;
+    if (total > max_results) {
+        char b[160];
+        snprintf(b, sizeof b, "radius_search: %lld rows lie within the radii, more than max_results = %lld",
+                 (long long)total, (long long)max_results);
+        return fail(TK_ERR_ARG, b);
+    }
+    if (total == 0) {
+        ix->rd_total = 0;
+        return TK_OK;
+    }
+    TRY(ix->rd_off.ensure((size_t)(nq + 1) * 8));
+    TRY(ix->rd_keys.ensure((size_t)total * 8));
+    TRY(ix->rd_alt.ensure((size_t)total * 8));
+    TRY(ix->rd_dist.ensure((size_t)total * 4));
+    HIPCHECK(hipMemcpy(ix->rd_off.p, out_lims, (size_t)(nq + 1) * 8, hipMemcpyHostToDevice));
+    unsigned long long *keys = ix->rd_keys.as<unsigned long long>(), *alt = ix->rd_alt.as<unsigned long long>();
+    if (tk_launch_radius_fill(X, nq, ix->d, Y, ix->N, yn, rad, count, ix->rd_off.as<int64_t>(), slots, keys, err, rp,
+                              nullptr))
+        return fail(TK_ERR_HIP, "tk_launch_radius_fill: unsupported size / LDS attribute");
+    HIPCHECK(hipGetLastError());
+    int bad = 0;
+    HIPCHECK(hipMemcpy(&bad, err, 4, hipMemcpyDeviceToHost));
+    if (bad) return fail(TK_ERR_HIP, "radius_search: count and fill passes disagree");
+    if (sorted) {
+        size_t bytes = 0;
+        if (tk_launch_radius_sort(nullptr, &bytes, keys, alt, total, nq, ix->rd_off.as<int64_t>(), nullptr))
+            return fail(TK_ERR_HIP, "tk_launch_radius_sort: work memory query failed");
+        TRY(ix->rd_tmp.ensure(bytes > 0 ? bytes : 1));
+        if (tk_launch_radius_sort(ix->rd_tmp.p, &bytes, keys, alt, total, nq, ix->rd_off.as<int64_t>(), nullptr))
+            return fail(TK_ERR_HIP, "tk_launch_radius_sort failed");
+        std::swap(keys, alt);           // the sorted keys; the ids go where the unsorted ones were
+    }
+    tk_launch_radius_decode(keys, total, (int64_t *)alt, ix->rd_dist.as<float>(), nullptr);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    ix->rd_ids_alt = alt == ix->rd_alt.as<unsigned long long>();
+    ix->rd_total = total;
+    return TK_OK;
+}
+
+extern "C" int tk_index_radius_fetch(tk_index *ix, int64_t *out_ids, float *out_dist)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix, "index");
+    if (ix->rd_total < 0)
+        return fail(TK_ERR_STATE, "tk_index_radius_fetch: no result is held (tk_index_radius_brute first; a call that "
+                                  "failed or only counted holds none)");
+    if (ix->rd_total == 0) return TK_OK;
+    ARGCHECK(out_ids, "buffers");
+    HIPCHECK(hipMemcpy(out_ids, ix->rd_ids_alt ? ix->rd_alt.p : ix->rd_keys.p, (size_t)ix->rd_total * 8,
+                       hipMemcpyDeviceToHost));
+    if (out_dist) HIPCHECK(hipMemcpy(out_dist, ix->rd_dist.p, (size_t)ix->rd_total * 4, hipMemcpyDeviceToHost));
+    return TK_OK;
 }
 
 // _FastDistanceTable.top (fast_pq.py:284-312) for a BATCH of queries against the coded rows the

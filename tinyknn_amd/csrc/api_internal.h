@@ -259,6 +259,12 @@ struct tk_index {
     DevBuf rot_t;            // fast mode: R transposed (d_pad, dq) float64, or empty
     DevBuf br_ynorm, br_vals, br_tau, br_cand, br_count, br_out, br_q, br_sample;   // tk_index_knn_brute
     DevBuf br_dist, br_mask, br_exclude, br_group, br_tags, br_ranges;              // ... and what _ex adds
+    // tk_index_radius_brute: radii, counts (nq) + slots (nq) + error flag, offsets (nq + 1), the keys as filled, the
+    // other half of the sort (keys in one, ids in the other), the part values, the sort's work memory.  rd_total >= 0:
+    // a result is held for tk_index_radius_fetch, its ids in rd_alt (rd_ids_alt) or rd_keys
+    DevBuf rd_radius, rd_count, rd_off, rd_keys, rd_alt, rd_dist, rd_tmp;
+    int64_t rd_total = -1;
+    bool rd_ids_alt = false;
     DevBuf gx_begin, gx_len;                                                        // tk_index_knn_group: a query's span
     DevBuf gx_col;                                                                  // tk_index_knn_between: ... and its column
     int rot_d_pad = 0;

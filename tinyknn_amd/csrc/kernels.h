@@ -567,3 +567,14 @@ int tk_launch_brute_tau(const float *X, int64_t nq, int d, const float *Y, int64
 int tk_launch_brute_select(const float *X, int64_t nq, int d, const float *Y, int64_t N, int k, const float *ynorm2,
                            float *tau, unsigned long long *cand, int cap, int *count, int *overflow, int64_t *out,
                            float *out_dist, int64_t seg, const TkBruteRestrict *r, hipStream_t s);
+
+// ---- every row within a radius of each query (radius.hip): count, fill, sort, decode ----
+// see radius.hip for the buffers; the launchers return -1 on unsupported sizes
+int tk_launch_radius_count(const float *X, int64_t nq, int d, const float *Y, int64_t N, float *ynorm2,
+                           const float *radius, int *count, const TkBruteRestrict *r, hipStream_t s);
+int tk_launch_radius_fill(const float *X, int64_t nq, int d, const float *Y, int64_t N, const float *ynorm2,
+                          const float *radius, int *count, const int64_t *offset, int *slots,
+                          unsigned long long *keys, int *err, const TkBruteRestrict *r, hipStream_t s);
+int tk_launch_radius_sort(void *tmp, size_t *tmp_bytes, const unsigned long long *keys_in, unsigned long long *keys_out,
+                          int64_t total, int64_t nq, const int64_t *offsets, hipStream_t s);
+void tk_launch_radius_decode(const unsigned long long *keys, int64_t n, int64_t *ids, float *dist, hipStream_t s);

@@ -294,6 +294,25 @@ def tag_masks(tags, n, what):
 TAG_MODES = {"any": 0, "all": 1}
 
 
+def query_radius(radius, nq):
+    """The float32 array a `radius=` argument is: a scalar for every query, or one radius per query, cast with
+    np.float32; +inf and negative values are allowed, NaN and a wrong length are a ValueError."""
+    a = np.asarray(radius)
+    if a.dtype == np.bool_ or a.dtype == object or not np.issubdtype(a.dtype, np.number) or a.ndim > 1:
+        raise TypeError("radius: a number, or a 1-d array with one radius per query")
+    if np.iscomplexobj(a):
+        raise TypeError("radius: a number, or a 1-d array with one radius per query")
+    if a.ndim == 0:
+        a = np.full(nq, a[()])
+    if a.shape[0] != nq:
+        raise ValueError(f"radius: one entry per query ({nq}), got {a.shape[0]}")
+    with np.errstate(over="ignore"):
+        a = np.ascontiguousarray(a.astype(np.float32))
+    if np.isnan(a).any():
+        raise ValueError(f"radius: query {int(np.flatnonzero(np.isnan(a))[0])} has a NaN radius")
+    return a
+
+
 def tag_mode_of(tags_mode):
     """0 / 1 for tags_mode "any" / "all" (ValueError for anything else)"""
     if not isinstance(tags_mode, str) or tags_mode not in TAG_MODES:
@@ -1349,26 +1368,91 @@ class DeviceIndex:
             _lib.check(_lib.lib().tk_index_knn_brute(self._h, _lib.ptr(qn, _lib._f32p), nq, int(k),
                                                      _lib.ptr(out, _lib._i64p)))
             return out
+        restrict = self._brute_restrictions("knn_brute", nq, allowed, exclude, group, tags, tags_mode, between)
+        dist = np.full((nq, k), np.inf, dtype=np.float32) if want_dist else None
+        out[:] = -1
+        _lib.check(_lib.lib().tk_index_knn_brute_ex(
+            self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), *self._host_pointers(restrict),
+            _lib.ptr(out, _lib._i64p), None if dist is None else dist.ctypes.data))
+        return (out, dist) if want_dist else out
+
+    def _brute_restrictions(self, call, nq, allowed, exclude, group, tags, tags_mode, between):
+        """The host arrays of a restricted exact call (knn_brute, radius_search), parsed as query_batch parses them:
+        (mask, exclude, group, tags, tag mode, ranges), None for what was not given.  An AllowSet is refused
+        (TypeError) and so is a list-sharded index, before the device is touched."""
         if isinstance(allowed, AllowSet):
-            raise TypeError("knn_brute: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
+            raise TypeError(f"{call}: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
                             "list position")
         if _dev_is_sharded(self):
-            raise RuntimeError("knn_brute with restrictions is not supported on a list-sharded index")
+            raise RuntimeError(f"{call} with restrictions is not supported on a list-sharded index")
         mask = None if allowed is None else AllowSet.mask_of(allowed, self.N)
         exclude = None if exclude is None else self._exclude_of(exclude, nq)
         group = None if group is None else query_groups(group, nq)
         tags, mode = (None, 0) if tags is None else (query_tags(tags, nq), tag_mode_of(tags_mode))
         between = None if between is None else np.ascontiguousarray(self._ranges_of(between, nq))
-        dist = np.full((nq, k), np.inf, dtype=np.float32) if want_dist else None
-        out[:] = -1
+        return mask, exclude, group, tags, mode, between
 
-        def host(a):
-            return None if a is None else a.ctypes.data
+    @staticmethod
+    def _host_pointers(restrict):
+        """_brute_restrictions' arrays as the C ABI takes them (NULL for None; the caller keeps the arrays alive)"""
+        return [a if isinstance(a, int) else (None if a is None else a.ctypes.data) for a in restrict]
 
-        _lib.check(_lib.lib().tk_index_knn_brute_ex(
-            self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), host(mask), host(exclude), host(group), host(tags), mode,
-            host(between), _lib.ptr(out, _lib._i64p), host(dist)))
-        return (out, dist) if want_dist else out
+    def radius_brute(self, qn, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
+                     between=None, sort=True, max_results=None):
+        """Every row within a radius of each normalised query, exactly (tk_index_radius_brute): CSR
+        (lims, ids, part) — lims (nq + 1,) int64, query i's hits ids[lims[i]:lims[i + 1]] int64 with their float32
+        `part` values beside them.  Row j is a hit of query i iff it passes the query's restrictions (allowed /
+        exclude / group / tags, tags_mode / between: knn_brute's, parsed alike; an AllowSet is refused) and
+        part(i, j) <= radius[i] in float32, inclusive; part is knn_brute_dist's value bit for bit, so for every k the
+        ids of knn_brute_dist(k) are the first k entries of the list at radius = part[k - 1].
+        radius: a scalar or (nq,), cast with np.float32; +inf: every passing row; negative: normally nothing; NaN and a
+        wrong length: ValueError.  sort=True: every list ascending by (part, id), knn_brute's order, the same bytes from
+        run to run; sort=False: the order inside a list is unspecified, lims and the sets are the same.
+        max_results (default 1 << 26, < 2**31): a total above it raises ValueError naming the true total — nothing is
+        returned, no list is ever cut, and the index stays usable.  Float32 vectors, d <= 128; not for a list-sharded
+        index.  The vectors of removed rows stay in HBM, as for knn_brute: allowed= with the mask of the surviving
+        rows is the truth after remove()."""
+        qn, radius, restrict = self._radius_args("radius_search", qn, radius, allowed, exclude, group, tags, tags_mode,
+                                                 between)
+        max_results = (1 << 26) if max_results is None else int(max_results)
+        if not 0 <= max_results < 2**31:
+            raise ValueError(f"max_results: in [0, 2**31), got {max_results}")
+        nq = len(qn)
+        lims = np.zeros(nq + 1, dtype=np.int64)
+        total = np.zeros(1, dtype=np.int64)
+        lib = _lib.lib()
+        rc = lib.tk_index_radius_brute(
+            self._h, _lib.ptr(qn, _lib._f32p), nq, _lib.ptr(radius, _lib._f32p), *self._host_pointers(restrict),
+            int(bool(sort)), 0, max_results, _lib.ptr(lims, _lib._i64p), _lib.ptr(total, _lib._i64p))
+        if rc == -1 and int(total[0]) > max_results:
+            raise ValueError(f"radius_search: {int(total[0])} rows lie within the radii, more than max_results = "
+                             f"{max_results}; nothing is returned (raise max_results, or ask radius_count first)")
+        _lib.check(rc)
+        ids = np.empty(int(total[0]), dtype=np.int64)
+        part = np.empty(int(total[0]), dtype=np.float32)
+        _lib.check(lib.tk_index_radius_fetch(self._h, ids.ctypes.data, part.ctypes.data))
+        return lims, ids, part
+
+    def radius_count(self, qn, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
+                     between=None):
+        """How many rows radius_brute would list per query: (nq,) int64, from the count pass alone (one pass over the
+        rows instead of two and no sort).  No limit: the counts are summed in int64."""
+        qn, radius, restrict = self._radius_args("radius_count", qn, radius, allowed, exclude, group, tags, tags_mode,
+                                                 between)
+        nq = len(qn)
+        lims = np.zeros(nq + 1, dtype=np.int64)
+        total = np.zeros(1, dtype=np.int64)
+        _lib.check(_lib.lib().tk_index_radius_brute(
+            self._h, _lib.ptr(qn, _lib._f32p), nq, _lib.ptr(radius, _lib._f32p), *self._host_pointers(restrict),
+            0, 1, 0, _lib.ptr(lims, _lib._i64p), _lib.ptr(total, _lib._i64p)))
+        return np.diff(lims)
+
+    def _radius_args(self, call, qn, radius, allowed, exclude, group, tags, tags_mode, between):
+        """the prepared queries, the (nq,) float32 radii and the restrictions of a radius call"""
+        qn = np.ascontiguousarray(qn, dtype=np.float32)
+        assert qn.ndim == 2 and qn.shape[1] == self.d
+        restrict = self._brute_restrictions(call, len(qn), allowed, exclude, group, tags, tags_mode, between)
+        return qn, query_radius(radius, len(qn)), restrict
 
     def knn_group(self, qn, k, group, *, allowed=None, exclude=None, tags=None, tags_mode="any", between=None,
                   return_distances=False):
@@ -2570,6 +2654,47 @@ class IVF:
         qn, _ = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
         call = dev.knn_brute_dist if return_distances else dev.knn_brute
         return call(qn, k, allowed=allowed, exclude=exclude, group=group, tags=tags, tags_mode=tags_mode, between=between)
+
+    def radius_search(self, qs, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
+                      between=None, sort=True, max_results=None):
+        """Every row of IVF.data within a radius of each raw query, exactly, under the restrictions of query_batch
+        (DeviceIndex.radius_brute on the prepared queries): CSR (lims, ids, part) — lims (nq + 1,)
+        int64, query i's hits ids[lims[i]:lims[i + 1]] (int64) with their float32 `part` values, knn_brute's, beside
+        them: part(i, j) <= radius[i], float32, inclusive, however many rows that is.  With sort=True (default) a list
+        is ascending by (part, row) — knn_brute(k)'s ids are its first k entries at radius = the k-th part — and
+        byte-identical from run to run; sort=False leaves the order inside a list unspecified.
+        An angular index ranks its normalised rows, as knn_brute does: part = 2 - 2 cos, so radius = 2 - 2c asks for
+        every row with cosine >= c.  radius: a scalar or (nq,), cast with np.float32; +inf: every passing row;
+        negative: normally an empty list; NaN or a wrong length: ValueError.  max_results (default 1 << 26, < 2**31):
+        a larger total raises ValueError with the true total, returns nothing and leaves the index usable — a list is
+        never cut silently.  The vectors of removed rows stay in HBM: allowed= with a mask of the surviving rows is the
+        truth after remove().  allowed: a bool mask of length N or row ids, not an AllowSet.  Float32 vectors,
+        d <= 128; not for a list-sharded index."""
+        qn, dev = self._radius_front("radius_search", qs, radius, allowed, tags, tags_mode, between)
+        return dev.radius_brute(qn, radius, allowed=allowed, exclude=exclude, group=group, tags=tags,
+                                tags_mode=tags_mode, between=between, sort=sort, max_results=max_results)
+
+    def radius_count(self, qs, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
+                     between=None):
+        """How many rows radius_search would list per raw query: (nq,) int64, from its count pass alone — no limit
+        (the totals are summed in int64), half the work and no sort.  Arguments as radius_search's."""
+        qn, dev = self._radius_front("radius_count", qs, radius, allowed, tags, tags_mode, between)
+        return dev.radius_count(qn, radius, allowed=allowed, exclude=exclude, group=group, tags=tags,
+                                tags_mode=tags_mode, between=between)
+
+    def _radius_front(self, call, qs, radius, allowed, tags, tags_mode, between):
+        """knn_brute's early refusals in its order, then the radius', before any device call; the prepared queries"""
+        if isinstance(allowed, AllowSet):
+            raise TypeError(f"{call}: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
+                            "list position")
+        if between is not None:
+            self._ranges(between, len(qs))
+        if tags is not None:
+            tag_mode_of(tags_mode)
+        query_radius(radius, len(qs))
+        dev = self._unsharded_device_index()
+        qn, _ = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
+        return qn, dev
 
     def knn_group(self, qs, k, group, *, allowed=None, exclude=None, tags=None, tags_mode="any", between=None,
                   return_distances=False):
