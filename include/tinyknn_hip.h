@@ -37,6 +37,7 @@ extern "C" {
 #define TK_ERR_ARG (-1)     /* bad argument (shape/size contract violated)   */
 #define TK_ERR_HIP (-2)     /* HIP runtime error                              */
 #define TK_ERR_STATE (-3)   /* index not fully populated for this call        */
+#define TK_ERR_WORKSPACE (-4) /* the call's device work memory would exceed the workspace budget: ask fewer queries */
 
 /* ---- library -------------------------------------------------------------- */
 const char *tk_last_error(void);
@@ -956,6 +957,41 @@ int tk_index_radius_brute(tk_index *ix, const float *q, int64_t nq, const float 
                           const int64_t *between, int sorted, int count_only, int64_t max_results, int64_t *out_lims,
                           int64_t *out_total);
 int tk_index_radius_fetch(tk_index *ix, int64_t *out_ids, float *out_dist);
+/* Every row within a radius of each query among the rows of the lists the query probes (radius_probe.hip, DESIGN
+ * 3.20): FAISS's range_search on an IVF index.  For query i with n_probes = P >= 1:
+ *   probes      the index's own coarse stage for P — the row tk_index_top_centers(k = P) gives and the query calls
+ *               probe; it depends on P alone (kc = min(P, n_lists), coarse rescore 2 kc + 10), on no k.  q: (nq, d)
+ *               prepared queries, q_pq: (nq, dq) float32, or float64 where q_pq_is_f64, as the query calls take them.
+ *   lists       the distinct lists that row names; a -1 left by an unfilled coarse heap names the last list, as the
+ *               reference's negative index does; a list named twice is walked once.
+ *   candidates  the labels in [0, N) stored in those lists at positions < list_n.  Rows that tk_index_remove_rows took
+ *               out are therefore never candidates (tk_index_radius_brute needs allowed_mask for that).  A row stored
+ *               in several probed lists is a candidate once.
+ *   hits        candidate j is a hit iff it passes the query's restrictions — allowed_mask / exclude / group / tags,
+ *               tag_mode / between exactly as tk_index_radius_brute takes them — and dist(i, j) <= radius[i],
+ *               inclusive: dist is the rescoring's squared distance (sqdist_row.h), float32 on float32 and half
+ *               stores, float64 on float64 vectors (compared with (double)radius[i]) — the values the query calls
+ *               return as distances and tk_index_knn_group returns, bit for bit.  It is NOT tk_index_radius_brute's
+ *               `part`: the two round differently and agree exactly on integer data.
+ * radius, out_lims, *out_total, max_results, count_only, sorted: as tk_index_radius_brute's; sorted lists ascend by
+ * (dist, id), the same bytes from run to run; max_results is compared with the final total (every row once).  The
+ * decoded result is held on the device until the next radius call of either kind on the index (tk_index_radius_brute
+ * drops it too, and this call drops that one's) or its destruction; tk_index_radius_probe_fetch copies it out:
+ * out_ids (total) int64, out_dist (total, or NULL) float32 — float64 on float64 vectors.  With nothing held:
+ * TK_ERR_STATE.
+ * The count pass leaves one bit per candidate, the fill pass reads it: sum over the query's distinct probed lists of
+ * ceil(list_n / 64) 64-bit words.  A call whose bitmap would exceed the workspace budget (16 GB, TINYKNN_WORKSPACE_GB)
+ * is TK_ERR_WORKSPACE before either pass runs: ask fewer queries per call.  The coarse stage synchronises per chunk of
+ * queries, as tk_index_top_centers does; after it the word total and the counts cross to the host.
+ * Every vector store, d <= 4096, N < 2^31, nq * min(P, n_lists) < 2^31.  Refused before any device work: a
+ * list-sharded index, n_probes < 1, a NaN radius (TK_ERR_ARG); group / tags / between without their row values for
+ * all N rows, and an index whose labels repeat but that holds no twin table — a row stored in two probed lists could
+ * not be listed once (TK_ERR_STATE).  Synchronous, under the index lock, after the calls still owed. */
+int tk_index_radius_probe(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int n_probes,
+                          const float *radius, const uint8_t *allowed_mask, const int64_t *exclude,
+                          const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between, int sorted,
+                          int count_only, int64_t max_results, int64_t *out_lims, int64_t *out_total);
+int tk_index_radius_probe_fetch(tk_index *ix, int64_t *out_ids, void *out_dist);
 /* The exact k nearest rows inside each query's own group (group_exact.hip): what the restricted call
  * above answers for group[i] >= 0 among the rows that are STORED, at a cost that follows the size of the group instead
  * of N — a query reads the rows of its group and no other.  Ranked by the rescoring's distance (numpy's einsum order

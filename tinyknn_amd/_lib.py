@@ -235,6 +235,10 @@ SIGNATURES = {
     "tk_index_radius_brute": (C.c_int, [C.c_void_p, _f32p, C.c_int64, _f32p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, _i64p, _i64p]),
     "tk_index_radius_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tk_index_radius_probe": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int, _f32p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_int64, _i64p, _i64p]),
+    "tk_index_radius_probe_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tk_index_knn_group": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),
     "tk_index_group_sizes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _i64p]),

@@ -1215,12 +1215,13 @@ static int brute_upload(DevBuf &b, const T *host, size_t n, const T *&dev)
     return TK_OK;
 }
 
-// The restriction of a restricted exact call (tk_index_knn_brute_ex, tk_index_radius_brute) from the caller's host
-// arrays: the checks both make, the per-query arrays in the br_* workspace buffers, the by-row arrays of the index.
+// The restriction of a restricted exact call (tk_index_knn_brute_ex, tk_index_radius_brute, tk_index_radius_probe) from
+// the caller's host arrays: the checks they make, the per-query arrays in the br_* workspace buffers, the by-row
+// arrays of the index.
 // any = false: nothing was given and r is empty.
-static int brute_restrict(tk_index *ix, int64_t nq, const uint8_t *allowed_mask, const int64_t *exclude,
-                          const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between,
-                          TkBruteRestrict &r, bool &any)
+int brute_restrict(tk_index *ix, int64_t nq, const uint8_t *allowed_mask, const int64_t *exclude,
+                   const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between,
+                   TkBruteRestrict &r, bool &any)
 {
     r = TkBruteRestrict{};
     ARGCHECK(tag_mode == 0 || tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
@@ -1278,7 +1279,7 @@ extern "C" int tk_index_radius_brute(tk_index *ix, const float *q, int64_t nq, c
                                      int count_only, int64_t max_results, int64_t *out_lims, int64_t *out_total)
 {
     IXLOCK(ix);
-    if (ix) ix->rd_total = -1;          // whatever this call does, the result of the last one is gone
+    if (ix) ix->rd_total = ix->rp_total = -1;       // whatever this call does, the result of the last one is gone
     ARGCHECK(ix && ix->have_data, "set_data first");
     ARGCHECK(!ix->sharded, "list-sharded index: radius_search is not supported");
     ARGCHECK(ix->data_dtype != TK_DATA_F64, "float32 vectors only");
@@ -1385,11 +1386,14 @@ extern "C" int tk_index_radius_fetch(tk_index *ix, int64_t *out_ids, float *out_
 // of queries in which any query fails the check is answered again by the exact kernel alone, and an
 // index on which more than 1 % fail (rows without structure) stays on the exact kernel.
 // out_dist (or NULL): the float32 exact squared distances beside the ids (+inf beside a -1 of the padding)
-static int top_centers(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
-                       int64_t *out_ids, float *out_dist)
+// The chunks of that call, their result left on the device: for every chunk of m queries from query o on, once its
+// (m, kc) probes are in the workspace (and, where want_dist, their distances) and the device is idle, sink(o, m, kc,
+// probes, dist) is called with device pointers that hold until it returns.  kc = min(k, n_lists).
+int coarse_top_chunks(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
+                      bool want_dist, const TkProbeSink &sink)
 {
     ARGCHECK(ix && ix->have_pq && ix->have_centers, "set_pq and set_centers first");
-    ARGCHECK(nq >= 0 && k >= 1 && (nq == 0 || (q && q_pq && out_ids)), "buffers / sizes");
+    ARGCHECK(nq >= 0 && k >= 1 && (nq == 0 || (q && q_pq)), "buffers / sizes");
     if (nq == 0) return TK_OK;
     TRY(flush_pending(ix));
     Plan p;
@@ -1408,8 +1412,8 @@ static int top_centers(tk_index *ix, const float *q, const void *q_pq, int q_pq_
     struct ScopedBuf : DevBuf {
         ~ScopedBuf() { release(); }
     } dbuf;             // (freed on every return)
-    if (out_dist) TRY(dbuf.ensure((size_t)chunk * p.kc * 4));
-    float *dist = out_dist ? dbuf.as<float>() : nullptr;
+    if (want_dist) TRY(dbuf.ensure((size_t)chunk * p.kc * 4));
+    float *dist = want_dist ? dbuf.as<float>() : nullptr;
     const bool lanes = ix->heap_mode == 0 && tk_positions_fit(ix->center_chunks) && p.rescore <= TK_LANES_MAX_R;
     const bool lazy = lanes && ix->center_chunks >= 1024;
     const int hc = (int)(ix->center_chunks / 64 < 16 ? 16 : ix->center_chunks / 64);     // exact head, in chunks
@@ -1512,25 +1516,36 @@ static int top_centers(tk_index *ix, const float *q, const void *q_pq, int q_pq_
             HIPCHECK(hipGetLastError());
             HIPCHECK(hipDeviceSynchronize());
         }
-        if (p.kc == k) {
-            HIPCHECK(hipMemcpy(out_ids + o * k, w.probes.p, (size_t)m * k * 8, hipMemcpyDeviceToHost));
+        TRY(sink(o, m, p.kc, w.probes.as<int64_t>(), dist));
+    }
+    return TK_OK;
+}
+
+static int top_centers(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
+                       int64_t *out_ids, float *out_dist)
+{
+    ARGCHECK(nq <= 0 || out_ids, "buffers / sizes");
+    return coarse_top_chunks(ix, q, q_pq, q_pq_is_f64, nq, k, out_dist != nullptr,
+                             [&](int64_t o, int64_t m, int kc, const int64_t *probes, const float *dist) -> int {
+        if (kc == k) {
+            HIPCHECK(hipMemcpy(out_ids + o * k, probes, (size_t)m * k * 8, hipMemcpyDeviceToHost));
             if (out_dist) HIPCHECK(hipMemcpy(out_dist + o * k, dist, (size_t)m * k * 4, hipMemcpyDeviceToHost));
         } else {    // fewer rows than k: rows of kc ids into rows of k, padded with -1 (+inf)
-            std::vector<int64_t> tmp((size_t)m * p.kc);
-            HIPCHECK(hipMemcpy(tmp.data(), w.probes.p, tmp.size() * 8, hipMemcpyDeviceToHost));
+            std::vector<int64_t> tmp((size_t)m * kc);
+            HIPCHECK(hipMemcpy(tmp.data(), probes, tmp.size() * 8, hipMemcpyDeviceToHost));
             for (int64_t i = 0; i < m; i++)
                 for (int t = 0; t < k; t++)
-                    out_ids[(o + i) * k + t] = t < p.kc ? tmp[(size_t)i * p.kc + t] : -1;
+                    out_ids[(o + i) * k + t] = t < kc ? tmp[(size_t)i * kc + t] : -1;
             if (out_dist) {
-                std::vector<float> tmpd((size_t)m * p.kc);
+                std::vector<float> tmpd((size_t)m * kc);
                 HIPCHECK(hipMemcpy(tmpd.data(), dist, tmpd.size() * 4, hipMemcpyDeviceToHost));
                 for (int64_t i = 0; i < m; i++)
                     for (int t = 0; t < k; t++)
-                        out_dist[(o + i) * k + t] = t < p.kc ? tmpd[(size_t)i * p.kc + t] : HUGE_VALF;
+                        out_dist[(o + i) * k + t] = t < kc ? tmpd[(size_t)i * kc + t] : HUGE_VALF;
             }
         }
-    }
-    return TK_OK;
+        return TK_OK;
+    });
 }
 
 extern "C" int tk_index_top_centers(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64,

@@ -89,7 +89,8 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->local_chunk_off, &ix->rot_t, &ix->br_ynorm, &ix->br_vals, &ix->br_tau,
                       &ix->br_cand, &ix->br_count, &ix->br_out, &ix->br_q, &ix->br_sample, &ix->br_dist, &ix->br_mask,
                       &ix->br_exclude, &ix->br_group, &ix->br_tags, &ix->br_ranges, &ix->rd_radius, &ix->rd_count,
-                      &ix->rd_off, &ix->rd_keys, &ix->rd_alt, &ix->rd_dist, &ix->rd_tmp, &ix->replay_counters,
+                      &ix->rd_off, &ix->rd_keys, &ix->rd_alt, &ix->rd_dist, &ix->rd_tmp, &ix->rp_probes, &ix->rp_words, &ix->rp_woff, &ix->rp_scan,
+                      &ix->rp_bitmap, &ix->rp_rows, &ix->rp_ids, &ix->rp_dist, &ix->replay_counters,
                       &ix->twin_list, &ix->twin_off, &ix->row_pos_off, &ix->row_pos, &ix->groups.by_row,
                       &ix->groups.table, &ix->tags.by_row, &ix->tags.table, &ix->values.by_row,
                       &ix->values.table, &ix->groups.span_rows, &ix->groups.span_gid, &ix->groups.span_off,

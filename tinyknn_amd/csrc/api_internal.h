@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <stdlib.h>
@@ -265,6 +266,14 @@ struct tk_index {
     DevBuf rd_radius, rd_count, rd_off, rd_keys, rd_alt, rd_dist, rd_tmp;
     int64_t rd_total = -1;
     bool rd_ids_alt = false;
+    // tk_index_radius_probe (radius_probe.hip): the call's probes (nq, kc) int64, bitmap words per (query, rank) int32
+    // and their exclusive prefix sum int64 (+ the scan's work memory), the hit bitmap; float64 vectors: the row ids
+    // beside the distance keys; the decoded ids and distances.  rp_total >= 0: a result is held for
+    // tk_index_radius_probe_fetch (rp_f64: its distances are float64).  The radii, counters, offsets, keys and the
+    // sort's buffers are the rd_* ones above: one radius result of either kind is held at a time.
+    DevBuf rp_probes, rp_words, rp_woff, rp_scan, rp_bitmap, rp_rows, rp_ids, rp_dist;
+    int64_t rp_total = -1;
+    bool rp_f64 = false;
     DevBuf gx_begin, gx_len;                                                        // tk_index_knn_group: a query's span
     DevBuf gx_col;                                                                  // tk_index_knn_between: ... and its column
     int rot_d_pad = 0;
@@ -514,6 +523,15 @@ int plain_blocks();
 int shard_plain_blocks();
 void launch_coarse_scan(tk_index *ix, Work &w, int64_t nq, const Plan &p, hipStream_t st,
                         const uint4 *tables = nullptr);
+// ---- api_build.hip, used by radius_probe.hip
+// The index's coarse stage for k probes (tk_index_top_centers' chunks), its result left on the device: see there.
+typedef std::function<int(int64_t o, int64_t m, int kc, const int64_t *probes_dev, const float *dist_dev)> TkProbeSink;
+int coarse_top_chunks(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
+                      bool want_dist, const TkProbeSink &sink);
+// the restriction of a restricted exact call from the caller's host arrays (see there); any = false: none given
+int brute_restrict(tk_index *ix, int64_t nq, const uint8_t *allowed_mask, const int64_t *exclude,
+                   const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between,
+                   TkBruteRestrict &r, bool &any);
 // the replay over the coded centres of queries [0, nq) (one slot every query shares, positions as labels)
 TkReplayJob centre_replay_job(const tk_index *ix, Work &w, int64_t nq, const Plan &p);
 // dist (or NULL): the probes' exact float32 distances beside probes_out (FlatTop; the IVF coarse stage asks for none)

@@ -294,6 +294,57 @@ def tag_masks(tags, n, what):
 TAG_MODES = {"any": 0, "all": 1}
 
 
+def join_radius_parts(nq, chunk, max_results, part):
+    """The CSR result of a radius call made in parts of at most `chunk` queries.  part(o, e, limit) answers queries
+    [o, e): (lims, fetch) — lims (e - o + 1,) int64 from 0; fetch() -> (ids, dist) while the device still holds the
+    part, or None where the part was only counted (limit None, or its total above limit) — or None where the part is
+    too large for the device's work memory: it is asked again in halves.  max_results None: counts alone.  The limit
+    holds for the sum and is checked before any part is fetched: a call of several parts counts them all first (the
+    device holds one result at a time), then asks each again for its rows; a call of one part is checked by the part
+    itself.  Above the limit: ValueError naming the true total, nothing returned."""
+    lims = np.zeros(nq + 1, dtype=np.int64)
+
+    def walk(spans, limit_of):
+        """every span in order, halved where it is too large -> (the spans as answered, their fetches)"""
+        todo, done, fetches = spans[::-1], [], []
+        while todo:
+            o, e = todo.pop()
+            got = part(o, e, limit_of(o))
+            if got is None:
+                if e - o <= 1:
+                    raise MemoryError("radius_search(n_probes=): one query's candidate bitmap exceeds the workspace "
+                                      "budget")
+                mid = (o + e) // 2
+                todo += [(mid, e), (o, mid)]
+                continue
+            lims[o + 1:e + 1] = lims[o] + got[0][1:]
+            done.append((o, e))
+            fetches.append(None if got[1] is None else got[1]())
+        return done, fetches
+
+    def refuse():
+        raise ValueError(f"radius_search: {int(lims[nq])} rows lie within the radii, more than max_results = "
+                         f"{max_results}; nothing is returned (raise max_results, or ask radius_count first)")
+
+    spans = [(o, min(o + chunk, nq)) for o in range(0, nq, chunk)] if nq > 0 else [(0, 0)]
+    if max_results is not None and len(spans) == 1:
+        got = part(*spans[0], max_results)                      # one part: its own check
+        if got is not None:
+            lims[1:] = got[0][1:]
+            if got[1] is None:
+                refuse()
+            return (lims,) + tuple(got[1]())
+    spans, _ = walk(spans, lambda o: None)                      # the counts alone (a part too large goes in halves)
+    if max_results is None:
+        return lims, None, None
+    if lims[nq] > max_results:
+        refuse()
+    _, fetches = walk(spans, lambda o: max_results - int(lims[o]))
+    if any(f is None for f in fetches):
+        refuse()
+    return lims, np.concatenate([f[0] for f in fetches]), np.concatenate([f[1] for f in fetches])
+
+
 def query_radius(radius, nq):
     """The float32 array a `radius=` argument is: a scalar for every query, or one radius per query, cast with
     np.float32; +inf and negative values are allowed, NaN and a wrong length are a ValueError."""
@@ -1446,6 +1497,86 @@ class DeviceIndex:
             self._h, _lib.ptr(qn, _lib._f32p), nq, _lib.ptr(radius, _lib._f32p), *self._host_pointers(restrict),
             0, 1, 0, _lib.ptr(lims, _lib._i64p), _lib.ptr(total, _lib._i64p)))
         return np.diff(lims)
+
+    # queries per tk_index_radius_probe call: a larger batch is cut here and its CSR parts joined (a part whose
+    # candidate bitmap would not fit the workspace is halved again: TK_ERR_WORKSPACE)
+    RADIUS_PROBE_CHUNK = 16384
+
+    def radius_probe(self, qn, q_pq, radius, n_probes, *, allowed=None, exclude=None, group=None, tags=None,
+                     tags_mode="any", between=None, sort=True, max_results=None):
+        """Every row within a radius of each normalised query among the rows of the lists the query probes
+        (tk_index_radius_probe): CSR (lims, ids, dist) — lims (nq + 1,) int64, query i's hits
+        ids[lims[i]:lims[i + 1]] int64 with the rescoring's squared distances beside them, float32, float64 on float64
+        vectors: the values query_batch(return_distances=True) and knn_group return, bit for bit.
+        The probes are the index's own coarse stage for n_probes (query_batch(debug=True)["probes"]; they depend on
+        n_probes alone).  The candidates are the labels in [0, N) stored in the distinct lists that row names — removed
+        rows are never candidates, a row stored in several probed lists is one candidate — and a candidate is a hit iff
+        it passes the restrictions (radius_brute's) and dist <= radius[i], inclusive (float64 vectors:
+        dist <= float64(float32(r))).  Not radius_brute's `part`: the two round differently and agree exactly on
+        integer data.  qn, q_pq: as query_batch takes them.  radius, sort, max_results: as radius_brute's; the limit
+        holds for the whole call and is checked before any part of the result is fetched (join_radius_parts).  Every store, d <= 4096;
+        not for a list-sharded index."""
+        qn, radius, restrict = self._radius_args("radius_search", qn, radius, allowed, exclude, group, tags, tags_mode,
+                                                 between)
+        max_results = (1 << 26) if max_results is None else int(max_results)
+        if not 0 <= max_results < 2**31:
+            raise ValueError(f"max_results: in [0, 2**31), got {max_results}")
+        q_pq, n_probes = self._probe_args(qn, q_pq, n_probes)
+        return join_radius_parts(
+            len(qn), self.RADIUS_PROBE_CHUNK, max_results,
+            lambda o, e, limit: self._radius_probe_part(qn, q_pq, radius, n_probes, restrict, o, e, bool(sort), limit))
+
+    def radius_probe_count(self, qn, q_pq, radius, n_probes, *, allowed=None, exclude=None, group=None, tags=None,
+                           tags_mode="any", between=None):
+        """How many rows radius_probe would list per query: (nq,) int64, from its count pass alone — no limit, no
+        sort, nothing fetched."""
+        qn, radius, restrict = self._radius_args("radius_count", qn, radius, allowed, exclude, group, tags, tags_mode,
+                                                 between)
+        q_pq, n_probes = self._probe_args(qn, q_pq, n_probes)
+        lims, _, _ = join_radius_parts(
+            len(qn), self.RADIUS_PROBE_CHUNK, None,
+            lambda o, e, limit: self._radius_probe_part(qn, q_pq, radius, n_probes, restrict, o, e, False, None))
+        return np.diff(lims)
+
+    def _probe_args(self, qn, q_pq, n_probes):
+        """the table-build queries as the C ABI takes them, and n_probes >= 1"""
+        n_probes = int(n_probes)
+        if n_probes < 1:
+            raise ValueError(f"n_probes: at least 1, got {n_probes}")
+        q_pq = np.ascontiguousarray(q_pq, dtype=np.float32 if q_pq.dtype == np.float32 else np.float64)
+        assert q_pq.shape == (len(qn), self.dq)
+        return q_pq, n_probes
+
+    def _radius_probe_part(self, qn, q_pq, radius, n_probes, restrict, o, e, sort, limit):
+        """Queries [o, e) through tk_index_radius_probe.  limit None: the count pass alone -> (lims, None);
+        else (lims, fetch) with fetch() -> (ids, dist) of the result the index holds until its next radius call, or
+        (lims, None) where the part's total is above the limit.  None where the part's bitmap does not fit."""
+        mask, exclude, group, tags, mode, between = restrict
+        part = (mask, None if exclude is None else exclude[o:e], None if group is None else group[o:e],
+                None if tags is None else tags[o:e], mode, None if between is None else between[o:e])
+        nq = e - o
+        lims = np.zeros(nq + 1, dtype=np.int64)
+        total = np.zeros(1, dtype=np.int64)
+        lib = _lib.lib()
+        qs, qp, rad = qn[o:e], q_pq[o:e], radius[o:e]
+        rc = lib.tk_index_radius_probe(
+            self._h, _lib.ptr(qs, _lib._f32p), qp.ctypes.data, int(qp.dtype == np.float64), nq, n_probes,
+            _lib.ptr(rad, _lib._f32p), *self._host_pointers(part), int(sort), int(limit is None),
+            0 if limit is None else limit, _lib.ptr(lims, _lib._i64p), _lib.ptr(total, _lib._i64p))
+        if rc == -4:
+            return None
+        if rc == -1 and limit is not None and int(total[0]) > limit:
+            return lims, None
+        _lib.check(rc)
+        if limit is None:
+            return lims, None
+
+        def fetch():
+            ids = np.empty(int(total[0]), dtype=np.int64)
+            dist = np.empty(int(total[0]), dtype=np.float64 if self._f64 else np.float32)
+            _lib.check(lib.tk_index_radius_probe_fetch(self._h, ids.ctypes.data, dist.ctypes.data))
+            return ids, dist
+        return lims, fetch
 
     def _radius_args(self, call, qn, radius, allowed, exclude, group, tags, tags_mode, between):
         """the prepared queries, the (nq,) float32 radii and the restrictions of a radius call"""
@@ -2656,7 +2787,7 @@ class IVF:
         return call(qn, k, allowed=allowed, exclude=exclude, group=group, tags=tags, tags_mode=tags_mode, between=between)
 
     def radius_search(self, qs, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                      between=None, sort=True, max_results=None):
+                      between=None, sort=True, max_results=None, n_probes=None):
         """Every row of IVF.data within a radius of each raw query, exactly, under the restrictions of query_batch
         (DeviceIndex.radius_brute on the prepared queries): CSR (lims, ids, part) — lims (nq + 1,)
         int64, query i's hits ids[lims[i]:lims[i + 1]] (int64) with their float32 `part` values, knn_brute's, beside
@@ -2669,21 +2800,40 @@ class IVF:
         a larger total raises ValueError with the true total, returns nothing and leaves the index usable — a list is
         never cut silently.  The vectors of removed rows stay in HBM: allowed= with a mask of the surviving rows is the
         truth after remove().  allowed: a bool mask of length N or row ids, not an AllowSet.  Float32 vectors,
-        d <= 128; not for a list-sharded index."""
+        d <= 128; not for a list-sharded index.
+        n_probes=P (an int >= 1; DESIGN §3.20, DeviceIndex.radius_probe): the rows of the P lists the query probes
+        alone — FAISS's range_search on an IVF index — instead of all N: CSR (lims, ids, dist).  The probes are
+        query_batch's for P; the candidates are the rows stored in the distinct probed lists, each once, so a row taken
+        out by remove() is never listed (no allowed= needed, unlike the call over all rows); `dist` is the rescoring's
+        squared distance — query_batch(return_distances=True)'s and knn_group's values bit for bit: float32, float64
+        on float64 vectors — compared with float32(radius) inclusively.  It is not `part`: the two round differently
+        and agree exactly on integer data, so a row on the boundary of one call may be outside the other's.  Every
+        store (float32, float16, float64 vectors) and d <= 4096.  n_probes=None is the call over all rows, as it
+        always was."""
+        if n_probes is not None:
+            qn, qp, dev = self._radius_front("radius_search", qs, radius, allowed, tags, tags_mode, between, n_probes)
+            return dev.radius_probe(qn, qp, radius, n_probes, allowed=allowed, exclude=exclude, group=group, tags=tags,
+                                    tags_mode=tags_mode, between=between, sort=sort, max_results=max_results)
         qn, dev = self._radius_front("radius_search", qs, radius, allowed, tags, tags_mode, between)
         return dev.radius_brute(qn, radius, allowed=allowed, exclude=exclude, group=group, tags=tags,
                                 tags_mode=tags_mode, between=between, sort=sort, max_results=max_results)
 
     def radius_count(self, qs, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                     between=None):
+                     between=None, n_probes=None):
         """How many rows radius_search would list per raw query: (nq,) int64, from its count pass alone — no limit
-        (the totals are summed in int64), half the work and no sort.  Arguments as radius_search's."""
+        (the totals are summed in int64), half the work and no sort.  Arguments as radius_search's, n_probes=
+        included (DeviceIndex.radius_probe_count)."""
+        if n_probes is not None:
+            qn, qp, dev = self._radius_front("radius_count", qs, radius, allowed, tags, tags_mode, between, n_probes)
+            return dev.radius_probe_count(qn, qp, radius, n_probes, allowed=allowed, exclude=exclude, group=group,
+                                          tags=tags, tags_mode=tags_mode, between=between)
         qn, dev = self._radius_front("radius_count", qs, radius, allowed, tags, tags_mode, between)
         return dev.radius_count(qn, radius, allowed=allowed, exclude=exclude, group=group, tags=tags,
                                 tags_mode=tags_mode, between=between)
 
-    def _radius_front(self, call, qs, radius, allowed, tags, tags_mode, between):
-        """knn_brute's early refusals in its order, then the radius', before any device call; the prepared queries"""
+    def _radius_front(self, call, qs, radius, allowed, tags, tags_mode, between, n_probes=None):
+        """knn_brute's early refusals in its order, then the radius', before any device call; the prepared queries
+        (qn, dev) — with n_probes (qn, q_pq, dev)"""
         if isinstance(allowed, AllowSet):
             raise TypeError(f"{call}: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
                             "list position")
@@ -2692,9 +2842,11 @@ class IVF:
         if tags is not None:
             tag_mode_of(tags_mode)
         query_radius(radius, len(qs))
+        if n_probes is not None and int(n_probes) < 1:
+            raise ValueError(f"n_probes: at least 1, got {int(n_probes)}")
         dev = self._unsharded_device_index()
-        qn, _ = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
-        return qn, dev
+        qn, qp = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
+        return (qn, dev) if n_probes is None else (qn, qp, dev)
 
     def knn_group(self, qs, k, group, *, allowed=None, exclude=None, tags=None, tags_mode="any", between=None,
                   return_distances=False):
