@@ -985,8 +985,12 @@ int tk_index_radius_fetch(tk_index *ix, int64_t *out_ids, float *out_dist);
  * queries, as tk_index_top_centers does; after it the word total and the counts cross to the host.
  * Every vector store, d <= 4096, N < 2^31, nq * min(P, n_lists) < 2^31.  Refused before any device work: a
  * list-sharded index, n_probes < 1, a NaN radius (TK_ERR_ARG); group / tags / between without their row values for
- * all N rows, and an index whose labels repeat but that holds no twin table — a row stored in two probed lists could
- * not be listed once (TK_ERR_STATE).  Synchronous, under the index lock, after the calls still owed. */
+ * all N rows, and an index whose labels repeat and for which no twin table can be made — a row stored in two probed
+ * lists could not be listed once (TK_ERR_STATE): a label stored more than 17 times, copies of a label with different
+ * codes or in one list, repeating labels beyond int32, no free memory for the table.  An index that keeps no table only
+ * because its labels are sparse (tk_index_twin_table: width 0 after tk_index_remove_rows thinned it) gets one made by
+ * the first such call of a layout, kept until the lists change.  Synchronous, under the index lock, after the calls
+ * still owed. */
 int tk_index_radius_probe(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int n_probes,
                           const float *radius, const uint8_t *allowed_mask, const int64_t *exclude,
                           const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between, int sorted,

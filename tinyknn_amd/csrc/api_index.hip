@@ -91,7 +91,7 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->br_exclude, &ix->br_group, &ix->br_tags, &ix->br_ranges, &ix->rd_radius, &ix->rd_count,
                       &ix->rd_off, &ix->rd_keys, &ix->rd_alt, &ix->rd_dist, &ix->rd_tmp, &ix->rp_probes, &ix->rp_words, &ix->rp_woff, &ix->rp_scan,
                       &ix->rp_bitmap, &ix->rp_rows, &ix->rp_ids, &ix->rp_dist, &ix->replay_counters,
-                      &ix->twin_list, &ix->twin_off, &ix->row_pos_off, &ix->row_pos, &ix->groups.by_row,
+                      &ix->twin_list, &ix->twin_off, &ix->rp_twin_list, &ix->rp_twin_off, &ix->row_pos_off, &ix->row_pos, &ix->groups.by_row,
                       &ix->groups.table, &ix->tags.by_row, &ix->tags.table, &ix->values.by_row,
                       &ix->values.table, &ix->groups.span_rows, &ix->groups.span_gid, &ix->groups.span_off,
                       &ix->stored_bits, &ix->gx_begin, &ix->gx_len, &ix->values.span_rows, &ix->gx_col};
@@ -168,44 +168,61 @@ struct TwinScratch {
     ~TwinScratch() { cnt.release(); where.release(); }
 };
 
-static int build_twins_try(tk_index *ix, int64_t label_bound, TwinScratch &t)
+// why a table was not made (build_twins_try): the caller's words for it
+enum { TWIN_MADE = 0, TWIN_COPIES, TWIN_MEMORY, TWIN_CODES };
+
+// list / off / w: where the table goes (w = 0: none was made, `why` says which rule refused it)
+static int build_twins_try(tk_index *ix, int64_t label_bound, TwinScratch &t, DevBuf &list, DevBuf &off, int &w_out,
+                           int &why)
 {
     const int64_t T = ix->total_ids;
+    w_out = 0;
+    why = TWIN_MEMORY;
     TRY(t.cnt.ensure((size_t)(label_bound + 1) * 4));
     HIPCHECK(hipMemsetAsync(t.cnt.p, 0, (size_t)(label_bound + 1) * 4, 0));
     int *cnt_max = t.cnt.as<int>() + label_bound;
     tk_launch_twin_count(ix->ids32.as<int32_t>(), T, t.cnt.as<int>(), cnt_max, 0);
     int b = 0;
     HIPCHECK(hipMemcpy(&b, cnt_max, 4, hipMemcpyDeviceToHost));
+    why = TWIN_COPIES;
     if (!(b >= 2 && b <= 17 && T * (b - 1) < (1ll << 31)))     // (the replay indexes the table with 32-bit arithmetic)
         return TK_OK;
     const int w = b - 1;
     // transient label_bound * b * 4 bytes + 2 * T * w * 4 persistent: only where the device has them to spare
+    why = TWIN_MEMORY;
     size_t free_b = 0, total_b = 0;
     HIPCHECK(hipMemGetInfo(&free_b, &total_b));
     const size_t need = (size_t)label_bound * b * 4 + 2 * (size_t)T * w * 4;
     if (need + need / 4 + (512u << 20) > free_b) return TK_OK;
     TRY(t.where.ensure((size_t)label_bound * b * 4));
-    TRY(ix->twin_list.ensure((size_t)T * w * 4));
-    TRY(ix->twin_off.ensure((size_t)T * w * 4));
+    TRY(list.ensure((size_t)T * w * 4));
+    TRY(off.ensure((size_t)T * w * 4));
     HIPCHECK(hipMemsetAsync(t.cnt.p, 0, (size_t)label_bound * 4, 0));
     tk_launch_twin_fill(ix->ids32.as<int32_t>(), T, t.cnt.as<int>(), t.where.as<int>(), b,
-                        ix->ids_off.as<int64_t>(), (int)ix->n_lists, ix->twin_list.as<int32_t>(),
-                        ix->twin_off.as<int32_t>(), 0);
+                        ix->ids_off.as<int64_t>(), (int)ix->n_lists, list.as<int32_t>(), off.as<int32_t>(), 0);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
     if (!ix->sharded) {      // every list's codes are here: the table's two premises, checked (twins.hip)
         HIPCHECK(hipMemsetAsync(t.cnt.p, 0, 4, 0));
         tk_launch_twin_verify(ix->codes.as<uint4>(), ix->M / 2, ix->list_chunk_off.as<int64_t>(),
-                              ix->ids_off.as<int64_t>(), (int)ix->n_lists, ix->twin_list.as<int32_t>(),
-                              ix->twin_off.as<int32_t>(), w, T, t.cnt.as<int>(), 0);
+                              ix->ids_off.as<int64_t>(), (int)ix->n_lists, list.as<int32_t>(), off.as<int32_t>(), w, T,
+                              t.cnt.as<int>(), 0);
         int bad = 0;
         HIPCHECK(hipMemcpy(&bad, t.cnt.p, 4, hipMemcpyDeviceToHost));
+        why = TWIN_CODES;
         if (bad) return TK_OK;   // copies with different codes, or two in one list: the label-based test only
     }
-    ix->twin_w = w;              // (set last: a failure above leaves "no table")
-    ix->twin_unverified = ix->sharded;
+    why = TWIN_MADE;
+    w_out = w;                   // (set last: a failure above leaves "no table")
     return TK_OK;
+}
+
+// what twins.hip's passes need of an index whose labels repeat
+static bool twins_possible(const tk_index *ix, int64_t label_bound)
+{
+    const int64_t T = ix->total_ids;
+    return ix->have_ids32 && !ix->ids_unique && T > 0 && T < (1ll << 31) && label_bound > 0 &&
+           ix->n_lists < (1ll << 31);
 }
 
 static int build_twins(tk_index *ix, int64_t label_bound)
@@ -214,19 +231,72 @@ static int build_twins(tk_index *ix, int64_t label_bound)
     ix->twin_unverified = false;
     ix->twin_list.release();
     ix->twin_off.release();
-    const int64_t T = ix->total_ids;
-    if (!ix->have_ids32 || ix->ids_unique || T <= 0 || T >= (1ll << 31) || label_bound <= 0 ||
-        label_bound > 8 * T + 1024 || ix->n_lists >= (1ll << 31))
-        return TK_OK;
+    ix->rp_twin_w = 0;           // radius_probe_twins' own table was made for the old lists
+    ix->rp_twin_list.release();
+    ix->rp_twin_off.release();
+    // labels sparser than this (a few stored entries under a large largest label): the count array would dwarf the
+    // table, and the replays have their label-based test
+    if (!twins_possible(ix, label_bound) || label_bound > 8 * ix->total_ids + 1024) return TK_OK;
     TwinScratch t;
-    const int rc = build_twins_try(ix, label_bound, t);
+    int why = 0;
+    const int rc = build_twins_try(ix, label_bound, t, ix->twin_list, ix->twin_off, ix->twin_w, why);
     if (rc != TK_OK || ix->twin_w == 0) {
         ix->twin_w = 0;
-        ix->twin_unverified = false;
         ix->twin_list.release();
         ix->twin_off.release();
     }
+    ix->twin_unverified = ix->twin_w > 0 && ix->sharded;
     if (rc != TK_OK) (void)hipGetLastError();      // (an out-of-memory answer is sticky until read)
+    return TK_OK;
+}
+
+// (api_internal.h) The lists of every stored entry's other copies for tk_index_radius_probe, which cannot list a row
+// once without them: the index's own table where it has one; otherwise one made by the same passes into buffers of
+// the call's own, for the present layout of the lists (install_lists drops it), WITHOUT the sparsity rule above —
+// IVF.remove can leave 100 entries under a label of 3000 (tests/exact_chain_shapes.py: thinned) — and with the rest:
+// at most 17 copies of a label, equal codes in different lists, and the memory to spare.  ix->twin_w and with it the
+// replay form query_batch chooses stay as they are.
+int radius_probe_twins(tk_index *ix, const int32_t **list, int *w)
+{
+    *list = nullptr;
+    *w = 0;
+    if (ix->ids_unique) return TK_OK;
+    if (ix->twin_w > 0) {
+        *list = ix->twin_list.as<int32_t>();
+        *w = ix->twin_w;
+        return TK_OK;
+    }
+    if (ix->rp_twin_w == 0) {
+        if (!twins_possible(ix, ix->label_bound))
+            return fail(TK_ERR_STATE, "radius_search(n_probes=): the labels of this index repeat and do not all fit "
+                                      "int32, so no twin table (twins.hip) can be made and a row stored in two probed "
+                                      "lists could not be listed once");
+        TwinScratch t;
+        int why = 0;
+        const int rc = build_twins_try(ix, ix->label_bound, t, ix->rp_twin_list, ix->rp_twin_off, ix->rp_twin_w, why);
+        if (rc != TK_OK || ix->rp_twin_w == 0) {
+            ix->rp_twin_w = 0;
+            ix->rp_twin_list.release();
+            ix->rp_twin_off.release();
+        }
+        if (rc != TK_OK) {
+            (void)hipGetLastError();
+            return rc;
+        }
+        if (ix->rp_twin_w == 0)
+            return fail(TK_ERR_STATE,
+                        why == TWIN_COPIES ? "radius_search(n_probes=): a label of this index is stored more than 17 "
+                                             "times, so it holds no twin table (twins.hip) and a row stored in two "
+                                             "probed lists could not be listed once"
+                        : why == TWIN_CODES ? "radius_search(n_probes=): two copies of a label carry different codes or "
+                                              "lie in one list, so the index holds no twin table (twins.hip) and a row "
+                                              "stored in two probed lists could not be listed once"
+                                            : "radius_search(n_probes=): the device has no memory to spare for a twin "
+                                              "table (twins.hip), so a row stored in two probed lists could not be "
+                                              "listed once");
+    }
+    *list = ix->rp_twin_list.as<int32_t>();
+    *w = ix->rp_twin_w;
     return TK_OK;
 }
 
@@ -258,6 +328,7 @@ int install_lists(tk_index *ix, ListLayout &lay)
     ix->list_kp = ix->list_cols.empty() ? 0 : lay.kp;
     ix->have_lists = true;
     ix->lists_gen++;
+    ix->label_bound = lay.max_label + 1;
     // labels that repeat: where every row's other copies are (the lane replay's duplicate test)
     return build_twins(ix, lay.max_label + 1);
 }

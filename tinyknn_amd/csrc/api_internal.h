@@ -223,6 +223,11 @@ struct tk_index {
     // repeating labels: where the other copies of every stored row are (twins.hip); twin_w = copies - 1, 0 = no table
     DevBuf twin_list, twin_off;
     int twin_w = 0;
+    // tk_index_radius_probe's table where the index keeps none (radius_probe_twins, api_index.hip): made by the first
+    // such call of a layout whose labels repeat, dropped with the layout; label_bound: the layout's largest label + 1
+    DevBuf rp_twin_list, rp_twin_off;
+    int rp_twin_w = 0;
+    int64_t label_bound = 0;
     // the table rests on two facts the index build checks where it holds every list's codes (twins.hip: copies of a
     // label lie in different lists and carry the same code); a rank that was handed only its own lists' codes
     // (tk_index_set_lists_shard) cannot, and uses the table only if the caller vouches (TK_OPT_TWIN_VOUCH)
@@ -508,6 +513,10 @@ int settle_lists(tk_index *ix);
 // Nothing fails once the swap has begun — a twin table that cannot be made is no table — so a caller that did its
 // checks and allocations first changes the index entirely or not at all.
 int install_lists(tk_index *ix, ListLayout &lay);
+// tk_index_radius_probe's twin table (api_index.hip): the index's own, or one made for the call where the labels repeat
+// and the index keeps none; *w = 0: the labels are distinct.  Refused (TK_ERR_STATE): a label stored more than 17 times,
+// copies with different codes or in one list, labels beyond int32, no memory to spare
+int radius_probe_twins(tk_index *ix, const int32_t **list, int *w);
 bool twin_replay(const tk_index *ix, const struct Plan &p);
 int make_plan(const tk_index *ix, int k, int n_probes, int pass_1, Plan &p);
 bool plain_env_on();

@@ -11,7 +11,11 @@
 //   candidates  the labels in [0, N) at positions < list_n of those lists; a label stored in several probed lists
 //               (build(n_probes >= 2)) is a candidate at the earliest rank that holds a copy — decided from the twin
 //               table (twins.hip: the lists of a stored row's other copies) against the probes row, before any vector
-//               is read
+//               is read.  The table is the index's own, or — where the index keeps none because its labels are sparse,
+//               as after IVF.remove has thinned it — one the first call of a layout makes for itself
+//               (radius_probe_twins, api_index.hip).  Refused (TK_ERR_STATE) is only what no table describes: a label
+//               stored more than 17 times, copies with different codes or in one list, repeating labels beyond int32,
+//               and a table that does not fit the free memory
 //   hits        candidates that pass the restriction (TkBruteRestrict by row id, span_exact.h's formulas) with
 //               sqdist_row<T, TY>(row, query) <= radius[i]: the rescoring's distance, float32 on float32 and half
 //               stores, float64 on float64 vectors (the radius widened from float32), inclusive
@@ -298,9 +302,9 @@ extern "C" int tk_index_radius_probe(tk_index *ix, const float *q, const void *q
     ARGCHECK(nq >= 0 && out_lims && out_total && (nq == 0 || (q && q_pq && radius)), "buffers");
     ARGCHECK(count_only || (max_results >= 0 && max_results < (1ll << 31)), "0 <= max_results < 2^31");
     for (int64_t i = 0; i < nq; i++) ARGCHECK(radius[i] == radius[i], "radius: NaN");
-    if (!ix->ids_unique && ix->twin_w == 0)
-        return fail(TK_ERR_STATE, "radius_search(n_probes=): the labels of this index repeat and it holds no twin table "
-                                  "(twins.hip), so a row stored in two probed lists could not be listed once");
+    const int32_t *twin_list = nullptr;
+    int twin_w = 0;
+    TRY(radius_probe_twins(ix, &twin_list, &twin_w));
     TkBruteRestrict r;
     bool any;
     TRY(brute_restrict(ix, nq, allowed_mask, exclude, group, tags, tag_mode, between, r, any));
@@ -358,7 +362,7 @@ extern "C" int tk_index_radius_probe(tk_index *ix, const float *q, const void *q
     j.ids = ix->ids.as<int64_t>();
     j.ids_off = ix->ids_off.as<int64_t>();
     j.list_n = ix->list_n.as<int64_t>();
-    j.twin_list = ix->twin_list.as<int32_t>();
+    j.twin_list = twin_list;
     j.radius = ix->rd_radius.as<float>();
     j.words = words;
     j.woff = woff;
@@ -370,7 +374,7 @@ extern "C" int tk_index_radius_probe(tk_index *ix, const float *q, const void *q
     j.N = ix->N;
     j.d = ix->d;
     j.kc = kc;
-    j.twin_w = ix->ids_unique ? 0 : ix->twin_w;
+    j.twin_w = twin_w;
     rp_pass(ix, j, nq, any ? &r : nullptr, false);
     HIPCHECK(hipGetLastError());
     std::vector<int> counts((size_t)nq);
