@@ -720,14 +720,20 @@ __global__ void gather_rows_kernel(const TY *__restrict__ X, int d, const int64_
 void tk_launch_gather_rows(const void *X, int data_dtype, int d, const int64_t *rows, int64_t n, float *out,
                            hipStream_t s)
 {
-    if (n <= 0) return;
-    const dim3 grid((unsigned)((n * d + 255) / 256)), block(256);
-    if (data_dtype == 2)
-        hipLaunchKernelGGL(gather_rows_kernel<_Float16>, grid, block, 0, s, (const _Float16 *)X, d, rows, n, out);
-    else if (data_dtype == 1)       // (double -> float: round to nearest even, numpy's astype)
-        hipLaunchKernelGGL(gather_rows_kernel<double>, grid, block, 0, s, (const double *)X, d, rows, n, out);
-    else
-        hipLaunchKernelGGL(gather_rows_kernel<float>, grid, block, 0, s, (const float *)X, d, rows, n, out);
+    // slabs of fewer than 2^31 elements: the block count of a launch is cast to 32 bits and must fit them
+    const int64_t slab = (((int64_t)1 << 31) - 256) / d;
+    for (int64_t o = 0; o < n; o += slab) {
+        const int64_t m = n - o < slab ? n - o : slab;
+        const dim3 grid((unsigned)((m * d + 255) / 256)), block(256);
+        const int64_t *r = rows + o;
+        float *to = out + o * d;
+        if (data_dtype == 2)
+            hipLaunchKernelGGL(gather_rows_kernel<_Float16>, grid, block, 0, s, (const _Float16 *)X, d, r, m, to);
+        else if (data_dtype == 1)       // (double -> float: round to nearest even, numpy's astype)
+            hipLaunchKernelGGL(gather_rows_kernel<double>, grid, block, 0, s, (const double *)X, d, r, m, to);
+        else
+            hipLaunchKernelGGL(gather_rows_kernel<float>, grid, block, 0, s, (const float *)X, d, r, m, to);
+    }
 }
 
 // Half storage of float32 rows.  The check pass: *first_bad (set to INT64_MAX by the caller) = the first row
