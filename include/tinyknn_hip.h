@@ -264,7 +264,15 @@ int tk_index_coalesce(tk_index *ix);
  * fork from the capturing stream through the events the calls record on it and are all joined
  * again by tk_index_join, so the capture is one self-contained graph: replaying it runs the
  * captured batches at the pipelined rate (workspaces, events and streams must exist beforehand:
- * run the same calls once uncaptured, tk_index_set_profiling off). */
+ * run the same calls once uncaptured, tk_index_set_profiling off).
+ * The capture state is the CALL's, not the index's: an entry point is "inside a capture" iff the stream it is given
+ * is being captured (tk_index_query_batch_dev and its _ex forms, tk_index_join); it then queries no event, and
+ * refuses to make a restriction's table.  Entry points that take no stream (tk_index_query_batch, tk_index_knn_group,
+ * tk_index_knn_between, tk_index_set_*, ...) are never inside a capture: they may follow a capture at once, with no
+ * tk_index_quiesce in between, and make the tables they need.  A call still owed (held for its partner, or pending
+ * in the pipeline) keeps the state of the stream IT was issued on: whoever enqueues its remaining stages — the next
+ * call, tk_index_join, a tk_index_set_* that flushes — does so as inside that capture.  A capture is complete only
+ * after tk_index_join on the capturing stream. */
 int tk_index_quiesce(tk_index *ix);
 
 /* Heap replay strategy.  0 = automatic: when the replay can skip `insert`'s

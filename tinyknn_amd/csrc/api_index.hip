@@ -563,6 +563,7 @@ static bool plain_possible(const tk_index *ix, const Plan &p)
 // tk_index_set_plain_scan(ix, 2): always plain (A/B, the tests' forced re-scans).  Results never
 // depend on any of this.
 enum { PLAIN_PROBE = 0, PLAIN_WAIT = 1, PLAIN_ON = 2, PLAIN_OFF = 3 };
+
 static bool plain_adaptive(const tk_index *ix)
 {
     return ix->plain_mode == 0 && ix->opt_plain_limit == 0x7fffffff;
@@ -1660,6 +1661,41 @@ static int pipe_launch(tk_index *ix, std::unique_ptr<Pending> b)
     return TK_OK;
 }
 
+// ix->capturing belongs to the entry point that is running, not to the index: it is read from the stream the entry
+// point was given (tk_index_query_batch_dev*, tk_index_join) and dropped when that call returns.  Entry points that
+// take no stream never see it set: tk_index_knn_group right after a capture may build its tables (it used to be
+// refused until the next tk_index_quiesce).
+static bool stream_capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const bool on = st != nullptr && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+    (void)hipGetLastError();
+    return on;
+}
+struct CaptureScope {
+    tk_index *ix;
+    CaptureScope(tk_index *ix_, void *stream) : ix(ix_) { ix->capturing = stream_capturing((hipStream_t)stream); }
+    ~CaptureScope() { ix->capturing = false; }
+    CaptureScope(const CaptureScope &) = delete;
+    CaptureScope &operator=(const CaptureScope &) = delete;
+};
+// ... and while batches that are still owed are enqueued, to the streams THEY were issued on: a call held or pending on
+// a capturing stream is captured whoever flushes it (tk_index_join on another stream, tk_index_set_*, tk_index_plain_stats)
+struct OwedCaptureScope {
+    tk_index *ix;
+    bool was;
+    explicit OwedCaptureScope(tk_index *ix_) : ix(ix_), was(ix_->capturing)
+    {
+        if (was) return;
+        bool on = ix->held && stream_capturing(ix->held->st);
+        for (const auto &b : ix->pending) on = on || stream_capturing(b->st);
+        ix->capturing = on;
+    }
+    ~OwedCaptureScope() { ix->capturing = was; }
+    OwedCaptureScope(const OwedCaptureScope &) = delete;
+    OwedCaptureScope &operator=(const OwedCaptureScope &) = delete;
+};
+
 // ---- two consecutive calls as ONE batch (tk_index_set_coalesce(ix, 2), pipelined mode) ----
 // The kernels that leave most of the chip idle — the two heap replays (157 waves of 64 queries for
 // 10 000 queries, a dependent chain per wave), the nine small kernels of the front stream — take as
@@ -1676,12 +1712,14 @@ static int pipe_launch(tk_index *ix, std::unique_ptr<Pending> b)
 static int launch_held(tk_index *ix)
 {
     if (!ix->held) return TK_OK;
+    OwedCaptureScope owed(ix);
     TK_DBG_SYNC("launch_held");
     return pipe_launch(ix, std::move(ix->held));
 }
 
 int flush_pending(tk_index *ix)
 {
+    OwedCaptureScope owed(ix);
     int r = launch_held(ix);
     while (!ix->pending.empty() && r == TK_OK) r = pipeline_advance(ix, true);
     ix->pending.clear();
@@ -1739,12 +1777,7 @@ static int query_batch_dev_impl(tk_index *ix, const float *q_dev, const void *q_
         r.allow = allow_effective(r.allow);
     }
     hipStream_t caller = (hipStream_t)stream;
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        ix->capturing = caller != nullptr && hipStreamIsCapturing(caller, &cs) == hipSuccess &&
-                        cs != hipStreamCaptureStatusNone;
-        (void)hipGetLastError();
-    }
+    CaptureScope capture(ix, stream);
     TRY(r.ensure_tables(ix, nq));       // (the first excluding / grouped / tagged / ranged call of a layout)
     const size_t esz = q_pq_is_f64 ? 8 : 4;
     const int64_t ms = sub_batch(p);
@@ -1851,8 +1884,7 @@ static int settle(tk_index *ix)
 {
     TRY(flush_pending(ix));
     HIPCHECK(hipDeviceSynchronize());
-    ix->capturing = false;
-    plain_poll(ix);         // (every verdict is in: none is lost with a workspace set_pipeline releases)
+    plain_poll(ix);        // (every verdict is in: none is lost with a workspace set_pipeline releases)
     if (ix->plain_state == PLAIN_WAIT) ix->plain_state = PLAIN_PROBE;
     for (Work &w : ix->works) w.busy = false;
     ix->calls = 0;
@@ -1900,6 +1932,7 @@ extern "C" int tk_index_join(tk_index *ix, void *stream)
 {
     IXLOCK(ix);
     ARGCHECK(ix, "null index");
+    CaptureScope capture(ix, stream);       // (the stages still owed are enqueued here: no event queries in a capture)
     TRY(flush_pending(ix));
     if (ix->depth > 1)
         for (Work &w : ix->works)

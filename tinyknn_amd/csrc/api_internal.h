@@ -304,7 +304,8 @@ struct tk_index {
     int plain_skip = 0;        // OFF: batches left before the next probe
     int plain_backoff = 256;   // OFF: length of the next pause (doubled by a failed probe, up to 4096)
     int plain_wait = 0;        // WAIT: batches seen while no verdict is pending (a probe that was abandoned)
-    bool capturing = false;    // the current call is being captured into a hipGraph: no event queries
+    bool capturing = false;    // the entry point now running was given a stream that is being captured into a hipGraph
+                               // (api_index.hip: CaptureScope; false between calls): no event queries, no table builds
     int plain_mode = 0;        // 0 auto: probed lists behind the first ones as plain sums on the matrix
                                // cores where the lemma of plain_scan.hip allows AND few queries need the
                                // re-scan (plain_poll); 1: exact kernel only; 2: plain always
