@@ -387,6 +387,9 @@ int tk_label_buckets(uint32_t label, int *b1, int *b2);
  *                        slot, as with positions — where every label of the index is below 0xffffff (16.7 M rows);
  *                        0 = always on (value, label64) entries, three registers per slot (what larger indexes get). */
 #define TK_OPT_LABELS24 9
+/*   TK_OPT_PROBE_BUDGET  bytes of distance keys one query chunk of tk_index_knn_probe may hold; 0 (DEFAULT) = the
+ *                        workspace budget (16 GB, TINYKNN_WORKSPACE_GB).  Tests set a small one to see a call cut. */
+#define TK_OPT_PROBE_BUDGET 10
 int tk_index_set_option(tk_index *ix, int option, int value);
 /* The table behind TK_OPT_REPLAY_TWIN (diagnostics, tests): *rows = stored rows (the length of the concatenated
  * ids), *w = other copies listed per row (0: no table — labels distinct, not int32, or one label stored more
@@ -1004,6 +1007,29 @@ int tk_index_radius_probe(tk_index *ix, const float *q, const void *q_pq, int q_
                           const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between, int sorted,
                           int count_only, int64_t max_results, int64_t *out_lims, int64_t *out_total);
 int tk_index_radius_probe_fetch(tk_index *ix, int64_t *out_ids, void *out_dist);
+/* The exact k nearest rows among the rows of the lists each query probes (probe_exact.hip): FAISS's
+ * IVF-Flat search.  Probes, lists, candidates, restrictions and dist are tk_index_radius_probe's above, word for word;
+ * the answer of query i is its first k candidates that pass, ascending by (dist, row id) — the first k entries of
+ * tk_index_radius_probe's sorted list at radius +inf, ids and distance bits alike.  out_ids (nq, k) int64, the row
+ * ending in -1 where fewer than k pass; out_dist (or NULL) (nq, k) float32 — float64 on float64 vectors — +inf
+ * beside -1.
+ * Two passes: the distances are made list-major — the (query, rank) pairs of a call are grouped by list and cut into
+ * tiles of QT queries; a workgroup stages its list's rows through LDS in blocks of RB and every staged row meets the
+ * whole tile, so a row is read once per tile and not once per query — into one segment of list_n distance keys per
+ * pair; then a workgroup per query selects over its segments and reads no vector.  The key buffer is sum list_n x 4
+ * bytes (8 on float64 vectors) over the pairs: the call is cut into chunks of whole queries whose buffers stay within
+ * the workspace budget (TINYKNN_WORKSPACE_GB, TK_OPT_PROBE_BUDGET), with the answer of the uncut call byte for byte; a
+ * single query whose keys alone exceed it is TK_ERR_WORKSPACE before any pass runs.
+ * Every vector store; 1 <= k <= 1024, n_probes >= 1, N < 2^31, nq * min(P, n_lists) < 2^31; d as large as 4 queries
+ * and 8 rows in 64 KiB of LDS admit (1 350 on float32 vectors, 2 040 on half, 680 on float64), else TK_ERR_ARG naming
+ * the limit.  Refused as tk_index_radius_probe refuses: a list-sharded index, restrictions without their row values,
+ * labels that repeat where no twin table can be made.  It keeps and drops nothing of the radius calls' held results.
+ * Synchronous, under the index lock, after the calls still owed.
+ * tk_index_knn_probe_tile: the QT and RB the distance pass takes on this index (tests, diagnostics). */
+int tk_index_knn_probe(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k, int n_probes,
+                       const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group, const uint64_t *tags,
+                       int tag_mode, const int64_t *between, int64_t *out_ids, void *out_dist);
+int tk_index_knn_probe_tile(tk_index *ix, int *qt, int *rb);
 /* The exact k nearest rows inside each query's own group (group_exact.hip): what the restricted call
  * above answers for group[i] >= 0 among the rows that are STORED, at a cost that follows the size of the group instead
  * of N — a query reads the rows of its group and no other.  Ranked by the rescoring's distance (numpy's einsum order

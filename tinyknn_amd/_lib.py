@@ -34,7 +34,7 @@ _f64p = C.POINTER(C.c_double)
 # name -> (restype, argtypes); mirrors include/tinyknn_hip.h one to one
 # tk_index_set_option
 OPT_SCAN_FORM, OPT_RESCORE_FORM, OPT_PLAIN_LIMIT, OPT_REPLAY_LAZY, OPT_REPLAY_COUNT, OPT_REPLAY_TWIN, OPT_TWIN_VOUCH = 1, 2, 3, 4, 5, 6, 7
-OPT_PAIR_NQ, OPT_LABELS24 = 8, 9
+OPT_PAIR_NQ, OPT_LABELS24, OPT_PROBE_BUDGET = 8, 9, 10
 # tk_index_last_replay: the forms of a batch's heap replay (TK_REPLAY_*)
 REPLAY_PAIR, REPLAY_LANES, REPLAY_PACKED_DISTINCT, REPLAY_LANES_TWIN, REPLAY_LANES_DEDUPE, REPLAY_PACKED, REPLAY_GENERAL = range(7)
 REPLAY_NAMES = ("pair", "lanes", "packed_distinct", "lanes_twin", "lanes_dedupe", "packed", "general")
@@ -239,6 +239,9 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                         C.c_int64, _i64p, _i64p]),
     "tk_index_radius_probe_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tk_index_knn_probe": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),
+    "tk_index_knn_probe_tile": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tk_index_knn_group": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),
     "tk_index_group_sizes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _i64p]),

@@ -91,6 +91,8 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->br_exclude, &ix->br_group, &ix->br_tags, &ix->br_ranges, &ix->rd_radius, &ix->rd_count,
                       &ix->rd_off, &ix->rd_keys, &ix->rd_alt, &ix->rd_dist, &ix->rd_tmp, &ix->rp_probes, &ix->rp_words, &ix->rp_woff, &ix->rp_scan,
                       &ix->rp_bitmap, &ix->rp_rows, &ix->rp_ids, &ix->rp_dist, &ix->replay_counters,
+                      &ix->pe_probes, &ix->pe_seglen, &ix->pe_segoff, &ix->pe_scan, &ix->pe_lists, &ix->pe_pairs,
+                      &ix->pe_tiles, &ix->pe_keys, &ix->pe_out,
                       &ix->twin_list, &ix->twin_off, &ix->rp_twin_list, &ix->rp_twin_off, &ix->row_pos_off, &ix->row_pos, &ix->groups.by_row,
                       &ix->groups.table, &ix->tags.by_row, &ix->tags.table, &ix->values.by_row,
                       &ix->values.table, &ix->groups.span_rows, &ix->groups.span_gid, &ix->groups.span_off,
@@ -2308,6 +2310,10 @@ extern "C" int tk_index_set_option(tk_index *ix, int option, int value)
     case TK_OPT_TWIN_VOUCH:
         ARGCHECK(value == 0 || value == 1, "TK_OPT_TWIN_VOUCH: 0 or 1");
         ix->twin_vouched = value != 0;
+        return TK_OK;
+    case TK_OPT_PROBE_BUDGET:
+        ARGCHECK(value >= 0, "TK_OPT_PROBE_BUDGET: >= 0");
+        ix->opt_probe_budget = value;
         return TK_OK;
     default:
         return fail(TK_ERR_ARG, "bad argument: unknown option");

@@ -49,3 +49,66 @@ __device__ __forceinline__ T sqdist_row(const TY *__restrict__ y, const T *xs, i
     if (L == 4) return (acc[0] + acc[1]) + (acc[2 % L] + acc[3 % L]);
     return acc[0] + acc[1 % L];
 }
+
+// The 4-query form (probe_exact.hip): one row against four queries in one walk over d.  y is a row staged in LDS, x[0..3]
+// four queries in LDS, all 16-byte aligned; every 16-byte piece of the row is read once (sq4_load: one 16-byte read a
+// piece) and feeds four sets of the lane-accumulators above.  Per query the operations and their order are
+// sqdist_row's exactly — the difference, the square, the folds 3, 2, 1, 0, the zero tail, the final pairing — so out[u]
+// has the bits of sqdist_row(y, x[u], d).
+template <typename T, typename E, int CNT>
+__device__ __forceinline__ void sq4_load(const E *p, T *dst)
+{
+    constexpr int N = 16 / (int)sizeof(E);
+    typedef E vec __attribute__((ext_vector_type(N)));
+#pragma unroll
+    for (int c = 0; c < CNT / N; c++) {
+        const vec v = ((const vec *)p)[c];
+#pragma unroll
+        for (int t = 0; t < N; t++) dst[c * N + t] = (T)v[t];
+    }
+}
+
+template <typename T, typename TY>
+__device__ __forceinline__ void sqdist_row4(const TY *__restrict__ y, const T *const x[4], int d, T out[4])
+{
+    constexpr int L = 16 / (int)sizeof(T);
+    T acc[4][L];
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+#pragma unroll
+        for (int l = 0; l < L; l++) acc[u][l] = 0;
+    int i = 0;
+    for (; d - i >= 4 * L; i += 4 * L) {
+        T yv[4 * L];
+        sq4_load<T, TY, 4 * L>(y + i, yv);
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            T df[4 * L];
+            sq4_load<T, T, 4 * L>(x[u] + i, df);
+#pragma unroll
+            for (int t = 0; t < 4 * L; t++) df[t] = yv[t] - df[t];
+#pragma unroll
+            for (int l = 0; l < L; l++) {
+                T ab3 = df[3 * L + l] * df[3 * L + l] + acc[u][l];
+                T ab2 = df[2 * L + l] * df[2 * L + l] + ab3;
+                T ab1 = df[L + l] * df[L + l] + ab2;
+                acc[u][l] = df[l] * df[l] + ab1;
+            }
+        }
+    }
+    for (; i < d; i += L) {
+#pragma unroll
+        for (int l = 0; l < L; l++) {
+            const bool in = i + l < d;
+            const T yv = in ? (T)y[i + l] : (T)0;
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                T df = in ? (yv - x[u][i + l]) : (T)0;
+                acc[u][l] = df * df + acc[u][l];
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+        out[u] = (L == 4) ? (acc[u][0] + acc[u][1]) + (acc[u][2 % L] + acc[u][3 % L]) : acc[u][0] + acc[u][1 % L];
+}

@@ -1585,6 +1585,40 @@ class DeviceIndex:
         restrict = self._brute_restrictions(call, len(qn), allowed, exclude, group, tags, tags_mode, between)
         return qn, query_radius(radius, len(qn)), restrict
 
+    def knn_probe(self, qn, q_pq, k, n_probes, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
+                  between=None, return_distances=False):
+        """The exact k nearest rows among the rows of the lists each normalised query probes (tk_index_knn_probe,
+        DESIGN §3.21; FAISS's IVF-Flat search): (nq, k) int64 ids ascending by (distance, row id), ending in -1 where
+        fewer than k candidates pass; with return_distances (ids, dists), the rescoring's squared distances — float32,
+        float64 on float64 vectors — +inf beside -1.  Probes, candidates (each stored row of the distinct probed lists
+        once, removed rows never), restrictions and distance are radius_probe's: the answer is the first k entries of
+        every list of radius_probe(+inf, n_probes), ids and distance bits alike.  qn, q_pq: as query_batch takes them.
+        1 <= k <= 1024, n_probes >= 1 (ValueError).  allowed: a bool mask of length N or row ids; an AllowSet is
+        refused (TypeError).  Every vector store.  Not for a list-sharded index."""
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError(f"knn_probe: k in [1, 1024], got {k}")
+        if _dev_is_sharded(self) or self._source is not None:
+            raise RuntimeError("knn_probe is not supported on a list-sharded index")
+        qn = np.ascontiguousarray(qn, dtype=np.float32)
+        assert qn.ndim == 2 and qn.shape[1] == self.d
+        nq = len(qn)
+        restrict = self._brute_restrictions("knn_probe", nq, allowed, exclude, group, tags, tags_mode, between)
+        q_pq, n_probes = self._probe_args(qn, q_pq, n_probes)
+        out = np.full((nq, k), -1, dtype=np.int64)
+        dist = np.full((nq, k), np.inf, dtype=np.float64 if self._f64 else np.float32) if return_distances else None
+        _lib.check(_lib.lib().tk_index_knn_probe(
+            self._h, _lib.ptr(qn, _lib._f32p), q_pq.ctypes.data, int(q_pq.dtype == np.float64), nq, k, n_probes,
+            *self._host_pointers(restrict), _lib.ptr(out, _lib._i64p), None if dist is None else dist.ctypes.data))
+        return (out, dist) if return_distances else out
+
+    def knn_probe_tile(self):
+        """(QT, RB): the queries per tile and the rows per staged block of knn_probe's distance pass on this index
+        (tk_index_knn_probe_tile; they follow from d and the vector store)"""
+        qt, rb = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.lib().tk_index_knn_probe_tile(self._h, C.byref(qt), C.byref(rb)))
+        return qt.value, rb.value
+
     def knn_group(self, qn, k, group, *, allowed=None, exclude=None, tags=None, tags_mode="any", between=None,
                   return_distances=False):
         """The exact k nearest STORED rows inside each query's own group (tk_index_knn_group) for
@@ -2847,6 +2881,23 @@ class IVF:
         dev = self._unsharded_device_index()
         qn, qp = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
         return (qn, dev) if n_probes is None else (qn, qp, dev)
+
+    def knn_probe(self, qs, k, n_probes, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
+                  between=None, return_distances=False):
+        """The exact k nearest rows among the rows of the n_probes lists each raw query probes (DeviceIndex.knn_probe
+        on the prepared queries): FAISS's IVF-Flat search, the call between query_batch — which ranks
+        the same lists by PQ estimates — and knn_brute, which reads all N rows.  (nq, k) int64 ids ascending by
+        (distance, row id), ending in -1 where fewer than k candidates pass; with return_distances (ids, dists), the
+        distances of query_batch(return_distances=True), +inf beside -1.  The probes are query_batch's for n_probes;
+        a row stored in several probed lists is one candidate and a row taken out by remove() is none; the answer is
+        the first k entries of every list of radius_search(qs, +inf, n_probes=n_probes), ids and distance bits alike.
+        The restrictions as knn_brute's; allowed: a bool mask of length N or row ids, not an AllowSet.
+        1 <= k <= 1024, n_probes >= 1 (ValueError).  Every vector store.  Not for a list-sharded index."""
+        if not 1 <= int(k) <= 1024:
+            raise ValueError(f"knn_probe: k in [1, 1024], got {int(k)}")
+        qn, qp, dev = self._radius_front("knn_probe", qs, np.inf, allowed, tags, tags_mode, between, n_probes)
+        return dev.knn_probe(qn, qp, k, n_probes, allowed=allowed, exclude=exclude, group=group, tags=tags,
+                             tags_mode=tags_mode, between=between, return_distances=return_distances)
 
     def knn_group(self, qs, k, group, *, allowed=None, exclude=None, tags=None, tags_mode="any", between=None,
                   return_distances=False):
