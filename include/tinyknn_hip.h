@@ -390,6 +390,11 @@ int tk_label_buckets(uint32_t label, int *b1, int *b2);
 /*   TK_OPT_PROBE_BUDGET  bytes of distance keys one query chunk of tk_index_knn_probe may hold; 0 (DEFAULT) = the
  *                        workspace budget (16 GB, TINYKNN_WORKSPACE_GB).  Tests set a small one to see a call cut. */
 #define TK_OPT_PROBE_BUDGET 10
+/*   TK_OPT_PROBE_WIDE    the distance kernel of tk_index_knn_probe: 0 (DEFAULT) = by width — the whole-row kernel where
+ *                        4 queries and 8 rows fit its LDS, the wide kernel (d walked in slabs) beyond; 1 = the wide
+ *                        kernel at any d.  A test switch: it puts d on both sides of a slab edge on indexes of a few KB
+ *                        a row.  The answer is the same bytes either way. */
+#define TK_OPT_PROBE_WIDE 11
 int tk_index_set_option(tk_index *ix, int option, int value);
 /* The table behind TK_OPT_REPLAY_TWIN (diagnostics, tests): *rows = stored rows (the length of the concatenated
  * ids), *w = other copies listed per row (0: no table — labels distinct, not int32, or one label stored more
@@ -1020,12 +1025,15 @@ int tk_index_radius_probe_fetch(tk_index *ix, int64_t *out_ids, void *out_dist);
  * bytes (8 on float64 vectors) over the pairs: the call is cut into chunks of whole queries whose buffers stay within
  * the workspace budget (TINYKNN_WORKSPACE_GB, TK_OPT_PROBE_BUDGET), with the answer of the uncut call byte for byte; a
  * single query whose keys alone exceed it is TK_ERR_WORKSPACE before any pass runs.
- * Every vector store; 1 <= k <= 1024, n_probes >= 1, N < 2^31, nq * min(P, n_lists) < 2^31; d as large as 4 queries
- * and 8 rows in 64 KiB of LDS admit (1 350 on float32 vectors, 2 040 on half, 680 on float64), else TK_ERR_ARG naming
- * the limit.  Refused as tk_index_radius_probe refuses: a list-sharded index, restrictions without their row values,
+ * Every vector store; 1 <= k <= 1024, n_probes >= 1, N < 2^31, nq * min(P, n_lists) < 2^31, d <= 4096.  Where 4
+ * queries and 8 whole rows do not fit 64 KiB of LDS (d > 1 350 on float32 vectors, 2 040 on half, 680 on float64) the
+ * distance pass is probe_dist_wide_kernel: tiles of 32 queries, blocks of 64 rows, d walked in slabs of 128 elements
+ * (64 on float64 vectors) with the accumulators in registers from slab to slab; the same keys, the same answer.
+ * Refused as tk_index_radius_probe refuses: a list-sharded index, restrictions without their row values,
  * labels that repeat where no twin table can be made.  It keeps and drops nothing of the radius calls' held results.
  * Synchronous, under the index lock, after the calls still owed.
- * tk_index_knn_probe_tile: the QT and RB the distance pass takes on this index (tests, diagnostics). */
+ * tk_index_knn_probe_tile: the QT and RB the distance pass takes on this index, the wide kernel's (32, 64) where it
+ * runs (tests, diagnostics). */
 int tk_index_knn_probe(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k, int n_probes,
                        const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group, const uint64_t *tags,
                        int tag_mode, const int64_t *between, int64_t *out_ids, void *out_dist);

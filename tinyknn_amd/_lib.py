@@ -34,7 +34,11 @@ _f64p = C.POINTER(C.c_double)
 # name -> (restype, argtypes); mirrors include/tinyknn_hip.h one to one
 # tk_index_set_option
 OPT_SCAN_FORM, OPT_RESCORE_FORM, OPT_PLAIN_LIMIT, OPT_REPLAY_LAZY, OPT_REPLAY_COUNT, OPT_REPLAY_TWIN, OPT_TWIN_VOUCH = 1, 2, 3, 4, 5, 6, 7
-OPT_PAIR_NQ, OPT_LABELS24, OPT_PROBE_BUDGET = 8, 9, 10
+OPT_PAIR_NQ, OPT_LABELS24, OPT_PROBE_BUDGET, OPT_PROBE_WIDE = 8, 9, 10, 11
+# tk_index_knn_probe's wide distance kernel (probe_exact.hip: PEW_QT, PEW_RB, PeWide<T>::DS): its tile, and the elements
+# of a slab of d per vector store
+PROBE_WIDE_TILE = (32, 64)
+PROBE_WIDE_DS = {"float32": 128, "float16": 128, "float64": 64}
 # tk_index_last_replay: the forms of a batch's heap replay (TK_REPLAY_*)
 REPLAY_PAIR, REPLAY_LANES, REPLAY_PACKED_DISTINCT, REPLAY_LANES_TWIN, REPLAY_LANES_DEDUPE, REPLAY_PACKED, REPLAY_GENERAL = range(7)
 REPLAY_NAMES = ("pair", "lanes", "packed_distinct", "lanes_twin", "lanes_dedupe", "packed", "general")

@@ -2315,6 +2315,10 @@ extern "C" int tk_index_set_option(tk_index *ix, int option, int value)
         ARGCHECK(value >= 0, "TK_OPT_PROBE_BUDGET: >= 0");
         ix->opt_probe_budget = value;
         return TK_OK;
+    case TK_OPT_PROBE_WIDE:
+        ARGCHECK(value == 0 || value == 1, "TK_OPT_PROBE_WIDE: 0 or 1");
+        ix->opt_probe_wide = value;
+        return TK_OK;
     default:
         return fail(TK_ERR_ARG, "bad argument: unknown option");
     }

@@ -282,9 +282,10 @@ struct tk_index {
     // tk_index_knn_probe (probe_exact.hip): the call's probes, the keys per (query, rank) and their exclusive prefix sum
     // (+ the scans' work memory), per list 5 ints (pairs, cursor, first pair, tiles, first tile), a chunk's pairs by
     // list, its tile table and its distance keys, the call's ids and distances.  opt_probe_budget (TK_OPT_PROBE_BUDGET):
-    // bytes of distance keys a chunk may hold, 0: workspace_bytes()
+    // bytes of distance keys a chunk may hold, 0: workspace_bytes().  opt_probe_wide (TK_OPT_PROBE_WIDE): 1 = the wide
+    // distance kernel at any d
     DevBuf pe_probes, pe_seglen, pe_segoff, pe_scan, pe_lists, pe_pairs, pe_tiles, pe_keys, pe_out;
-    int opt_probe_budget = 0;
+    int opt_probe_budget = 0, opt_probe_wide = 0;
     DevBuf gx_begin, gx_len;                                                        // tk_index_knn_group: a query's span
     DevBuf gx_col;                                                                  // tk_index_knn_between: ... and its column
     int rot_d_pad = 0;

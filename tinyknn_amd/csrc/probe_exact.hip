@@ -34,6 +34,8 @@
 // which 4 queries fit, QT as the most queries that fit beside it (a multiple of 4, at most 64), and doubles RB up to
 // 256 while a full tile leaves room.  Assumed, not measured: that a CU's 160 KiB hold two or three such workgroups
 // whose staging and arithmetic overlap; nothing is double-buffered inside one.
+// Where not even 4 queries and 8 whole rows fit (d from 1 365 on float32 vectors, 2 041 on half, 683 on float64; up to
+// 4 096) the distance pass is probe_dist_wide_kernel below: the same tiles, keys and places, d walked in slabs.
 #include "api_internal.h"
 #include "sqdist_row.h"
 #include "span_exact.h"
@@ -47,6 +49,7 @@ struct PeTile {
     int xstride;            // elements of T between two queries in LDS
     int ystride;            // bytes between two staged rows in LDS
     size_t lds;
+    int DS;                 // 0: probe_dist_kernel; else probe_dist_wide_kernel and the elements of its slab
 };
 
 struct PeJob {
@@ -203,6 +206,151 @@ __global__ __launch_bounds__(PE_THREADS) void probe_dist_kernel(const PeJob j)
     }
 }
 
+// ---- the wide distance kernel: d walked in slabs (d beyond what probe_dist_kernel's LDS holds) ----
+// A tile is PEW_QT queries, a block PEW_RB rows, a slab DS = 32 * L elements (128 floats, 64 doubles: a multiple of
+// sqdist_row's group of 4 * L, so a slab edge falls between two iterations of its main loop).  LDS holds one slab of
+// the queries (T) and one slab of the rows (TY, DS * sizeof(TY) + 16 bytes apart: an odd number of 16-byte pieces), the
+// labels of two blocks and per query its row of q and its key segment — static, the compiler reports it.  The walk is
+// one loop over (block, slab) steps: the next step's global loads go into registers (fetch) while this step's slab is
+// summed, and are written to LDS (commit) between the two barriers of the next step.  A lane owns one row of the block
+// and the PEW_NI query quads  wave, wave + 4, ...  for the whole walk over d: PEW_NI * 4 * L accumulators in registers
+// from slab to slab, the row's pieces read once a group for all its quads, the queries' pieces LDS broadcasts.
+#define PEW_QT 32
+#define PEW_RB 64
+#define PEW_NI (PEW_RB * PEW_QT / 4 / PE_THREADS)
+static_assert(PEW_RB == 64 && PEW_NI * 4 * PE_THREADS == PEW_RB * PEW_QT, "a wave is one block of rows; whole items a lane");
+
+template <typename T> struct PeWide {
+    static constexpr int L = 16 / (int)sizeof(T);
+    static constexpr int DS = 32 * L;
+};
+
+template <typename T, typename TY>
+struct PeWideLds {
+    static constexpr int DS = PeWide<T>::DS, YS = DS * (int)sizeof(TY) + 16;
+    T xq[PEW_QT * DS];
+    unsigned char yr[PEW_RB * YS];
+    int32_t rid[2][PEW_RB];         // the labels of this block and the next, -1: no row
+    long long pseg[PEW_QT];         // where each query's keys of this list begin
+    int64_t qrow[PEW_QT];           // each query's row of q
+};
+
+// QUADS: d * sizeof(TY) is a multiple of 16, rows are staged in 16-byte pieces; else element by element
+template <typename T, typename TY, bool QUADS>
+__device__ __forceinline__ void pe_wide_walk(const PeJob &j, PeWideLds<T, TY> &s, const int4 tile)
+{
+    typedef typename GxKey<T>::type K;
+    typedef typename std::conditional<QUADS, uint4, TY>::type U;        // what a lane fetches of the rows
+    constexpr int L = PeWide<T>::L, DS = PeWide<T>::DS, YS = PeWideLds<T, TY>::YS;
+    constexpr int UR = DS * (int)sizeof(TY) / (int)sizeof(U);           // units of a row's slab
+    constexpr int NU = PEW_RB * UR / PE_THREADS, NX = PEW_QT * DS / PE_THREADS;
+    const int tid = threadIdx.x, d = j.d, cnt = tile.z;
+    const int64_t n = j.list_n[tile.x], base = j.ids_off[tile.x];
+    const int ud = QUADS ? (int)((size_t)d * sizeof(TY) / 16) : d;      // units of a whole row
+    const int NS = (d + DS - 1) / DS, G = d / (4 * L);                  // slabs; whole groups of a row
+    const int64_t steps = (n + PEW_RB - 1) / PEW_RB * NS;
+    const TY *rows = (const TY *)j.rows;
+    K *keys = (K *)j.keys;
+    const int rr = tid & (PEW_RB - 1);                                  // the lane's row of every block
+    bool on[PEW_NI];
+    const T *x[PEW_NI][4];
+#pragma unroll
+    for (int it = 0; it < PEW_NI; it++) {
+        const int u0 = (tid / PEW_RB + it * (PE_THREADS / PEW_RB)) * 4;
+        on[it] = u0 < cnt;
+#pragma unroll
+        for (int u = 0; u < 4; u++) x[it][u] = s.xq + (u0 + u < cnt ? u0 + u : 0) * DS;
+    }
+    U ry[NU];
+    float rx[NX];
+    auto label = [&](int64_t pos) -> int32_t {
+        const int64_t id = pos < n ? j.ids[base + pos] : -1;
+        return (id >= 0 && id < j.N) ? (int32_t)id : -1;
+    };
+    auto fetch = [&](int64_t step) {                // the step's slab of the block's rows and of the tile's queries
+        const int64_t b = step / NS;
+        const int sl = (int)(step - b * NS);
+#pragma unroll
+        for (int p = 0; p < NU; p++) {
+            const int e = tid + p * PE_THREADS, r = e / UR, c = sl * UR + e % UR;
+            const int32_t id = s.rid[b & 1][r];
+            U v = U();
+            if (id >= 0 && c < ud) v = ((const U *)(rows + (int64_t)id * d))[c];
+            ry[p] = v;
+        }
+#pragma unroll
+        for (int p = 0; p < NX; p++) {
+            const int e = tid + p * PE_THREADS, u = e / DS, c = sl * DS + e % DS;
+            rx[p] = (u < cnt && c < d) ? j.q[s.qrow[u] * d + c] : 0.0f;
+        }
+    };
+    auto commit = [&]() {
+#pragma unroll
+        for (int p = 0; p < NU; p++) {
+            const int e = tid + p * PE_THREADS;
+            ((U *)(s.yr + (size_t)(e / UR) * YS))[e % UR] = ry[p];
+        }
+#pragma unroll
+        for (int p = 0; p < NX; p++) s.xq[tid + p * PE_THREADS] = (T)rx[p];
+    };
+
+    for (int u = tid; u < cnt; u += PE_THREADS) {
+        const int pr = j.pair_of[tile.y + u];
+        s.pseg[u] = j.segoff[pr] - j.seg_base;
+        s.qrow[u] = pr / j.kc;
+    }
+    if (tid < PEW_RB) s.rid[0][tid] = label(tid);
+    __syncthreads();
+    if (steps > 0) fetch(0);
+    T acc[PEW_NI][4][L];
+    bool stored = false;
+    for (int64_t step = 0; step < steps; step++) {
+        const int64_t b = step / NS;
+        const int sl = (int)(step - b * NS);
+        const bool last = sl == NS - 1;
+        int32_t next = -1;
+        if (last && tid < PEW_RB) next = label((b + 1) * PEW_RB + tid);
+        __syncthreads();                            // the last step's arithmetic is done with xq and yr
+        commit();
+        if (last && tid < PEW_RB) s.rid[(b + 1) & 1][tid] = next;      // (read again two blocks on, behind barriers)
+        __syncthreads();
+        if (step + 1 < steps) fetch(step + 1);
+        const int64_t pos = b * PEW_RB + rr;
+        if (sl == 0) {
+            stored = pos < n && s.rid[b & 1][rr] >= 0;
+            sq4_init<T, PEW_NI>(acc);
+        }
+        const TY *y = (const TY *)(s.yr + (size_t)rr * YS);
+        int ng = G - sl * (DS / (4 * L));
+        ng = ng < 0 ? 0 : ng < DS / (4 * L) ? ng : DS / (4 * L);
+        if (stored) sq4_groups<T, TY, PEW_NI>(y, x, on, ng, acc);
+        if (!last) continue;
+        T dv[PEW_NI][4];
+        if (stored) {
+            sq4_tail<T, TY, PEW_NI>(y, x, on, ng * 4 * L, d - G * 4 * L, acc);
+            sq4_finish<T, PEW_NI>(acc, dv);
+        }
+        if (pos < n)
+#pragma unroll
+            for (int it = 0; it < PEW_NI; it++) {
+                const int u0 = (tid / PEW_RB + it * (PE_THREADS / PEW_RB)) * 4;
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (u0 + u < cnt) keys[s.pseg[u0 + u] + pos] = stored ? GxKey<T>::of(dv[it][u]) : ~(K)0;
+            }
+    }
+}
+
+template <typename T, typename TY>
+__global__ __launch_bounds__(PE_THREADS) void probe_dist_wide_kernel(const PeJob j)
+{
+    __shared__ __attribute__((aligned(16))) PeWideLds<T, TY> s;
+    if ((int)blockIdx.x >= j.tile_off[j.n_lists]) return;               // (the grid is an upper bound of the tiles)
+    const int4 tile = j.tiles[blockIdx.x];
+    if (((size_t)j.d * sizeof(TY)) % 16 == 0) pe_wide_walk<T, TY, true>(j, s, tile);
+    else pe_wide_walk<T, TY, false>(j, s, tile);
+}
+
 // LDS: kd[GX_CAP] distance keys | kid[GX_CAP] row ids | pl[kc] the lists of the query's ranks
 static size_t pe_select_lds(int kc, size_t key_bytes) { return (size_t)GX_CAP * (key_bytes + 4) + (size_t)kc * 4; }
 
@@ -344,17 +492,23 @@ static bool pe_tile_for(int d, size_t tb, size_t yb, PeTile &t)
     return true;
 }
 
+// the tile of the call: probe_dist_kernel's where the whole rows fit its LDS (and TK_OPT_PROBE_WIDE does not ask
+// otherwise), else the wide kernel's fixed one
 static int pe_tile(const tk_index *ix, PeTile &t)
 {
-    const size_t tb = ix->data_dtype == TK_DATA_F64 ? 8 : 4, yb = data_esz(ix->data_dtype);
-    if (pe_tile_for(ix->d, tb, yb, t)) return TK_OK;
-    int lim = ix->d;
-    PeTile u;
-    while (lim > 1 && !pe_tile_for(lim, tb, yb, u)) lim--;     // (never below 1 024 on float32 vectors)
-    char b[200];
-    snprintf(b, sizeof b, "bad argument: knn_probe: 4 queries and 8 rows of d = %d do not fit the distance pass's 64 KiB "
-                          "of LDS; d <= %d for this vector store", ix->d, lim);
-    return fail(TK_ERR_ARG, b);
+    ARGCHECK(ix->d <= 4096, "d <= 4096");
+    const bool f64 = ix->data_dtype == TK_DATA_F64;
+    const size_t tb = f64 ? 8 : 4, yb = data_esz(ix->data_dtype);
+    t.DS = 0;
+    if (!ix->opt_probe_wide && pe_tile_for(ix->d, tb, yb, t)) return TK_OK;
+    t.QT = PEW_QT;
+    t.RB = PEW_RB;
+    t.DS = f64 ? PeWide<double>::DS : PeWide<float>::DS;
+    t.xstride = t.DS;
+    t.ystride = t.DS * (int)yb + 16;
+    t.lds = f64 ? sizeof(PeWideLds<double, double>)
+                : yb == 2 ? sizeof(PeWideLds<float, _Float16>) : sizeof(PeWideLds<float, float>);
+    return TK_OK;
 }
 
 template <typename T, typename TY>
@@ -362,7 +516,8 @@ static void pe_launch(const PeJob &j, unsigned max_tiles, const TkBruteRestrict 
                       int64_t *out, void *out_d)
 {
     typedef typename GxKey<T>::type K;
-    hipLaunchKernelGGL((probe_dist_kernel<T, TY>), dim3(max_tiles), dim3(PE_THREADS), j.t.lds, 0, j);
+    if (j.t.DS) hipLaunchKernelGGL((probe_dist_wide_kernel<T, TY>), dim3(max_tiles), dim3(PE_THREADS), 0, 0, j);
+    else hipLaunchKernelGGL((probe_dist_kernel<T, TY>), dim3(max_tiles), dim3(PE_THREADS), j.t.lds, 0, j);
     hipLaunchKernelGGL((probe_select_kernel<T>), dim3((unsigned)m), dim3(GX_THREADS), pe_select_lds(j.kc, sizeof(K)), 0,
                        j, r, q0, k, out, (T *)out_d);
 }

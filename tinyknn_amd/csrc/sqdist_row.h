@@ -112,3 +112,86 @@ __device__ __forceinline__ void sqdist_row4(const TY *__restrict__ y, const T *c
     for (int u = 0; u < 4; u++)
         out[u] = (L == 4) ? (acc[u][0] + acc[u][1]) + (acc[u][2 % L] + acc[u][3 % L]) : acc[u][0] + acc[u][1 % L];
 }
+
+// The 4-query form cut into pieces along d (probe_exact.hip's wide kernel): the accumulator sets of NI items — one row
+// against NI quads of queries — live in the caller's registers while d is walked in slabs whose length is a multiple of
+// 4 * L, so every slab edge falls between two iterations of the main loop above.  sq4_init, then per slab sq4_groups
+// over the slab's whole groups (y and x[it][u] point at the slab's first element), in the last slab sq4_tail, then
+// sq4_finish: per query sqdist_row4's operations in sqdist_row4's order, the same bits.  An item whose on[it] is false
+// is left alone; the row's pieces are read once a group for all NI items.
+template <typename T, int NI>
+__device__ __forceinline__ void sq4_init(T (&acc)[NI][4][16 / sizeof(T)])
+{
+#pragma unroll
+    for (int it = 0; it < NI; it++)
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+#pragma unroll
+            for (int l = 0; l < 16 / (int)sizeof(T); l++) acc[it][u][l] = 0;
+}
+
+template <typename T, typename TY, int NI>
+__device__ __forceinline__ void sq4_groups(const TY *__restrict__ y, const T *const (&x)[NI][4], const bool (&on)[NI],
+                                           int n, T (&acc)[NI][4][16 / sizeof(T)])
+{
+    constexpr int L = 16 / (int)sizeof(T);
+    for (int g = 0; g < n; g++) {
+        const int i = g * 4 * L;
+        T yv[4 * L];
+        sq4_load<T, TY, 4 * L>(y + i, yv);
+#pragma unroll
+        for (int it = 0; it < NI; it++) {
+            if (!on[it]) continue;
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                T df[4 * L];
+                sq4_load<T, T, 4 * L>(x[it][u] + i, df);
+#pragma unroll
+                for (int t = 0; t < 4 * L; t++) df[t] = yv[t] - df[t];
+#pragma unroll
+                for (int l = 0; l < L; l++) {
+                    T ab3 = df[3 * L + l] * df[3 * L + l] + acc[it][u][l];
+                    T ab2 = df[2 * L + l] * df[2 * L + l] + ab3;
+                    T ab1 = df[L + l] * df[L + l] + ab2;
+                    acc[it][u][l] = df[l] * df[l] + ab1;
+                }
+            }
+        }
+    }
+}
+
+// the zero-padded tail: the elements [i, i + rem) of the slab, rem < 4 * L, in steps of L
+template <typename T, typename TY, int NI>
+__device__ __forceinline__ void sq4_tail(const TY *__restrict__ y, const T *const (&x)[NI][4], const bool (&on)[NI],
+                                         int i, int rem, T (&acc)[NI][4][16 / sizeof(T)])
+{
+    constexpr int L = 16 / (int)sizeof(T);
+    for (const int end = i + rem; i < end; i += L) {
+#pragma unroll
+        for (int l = 0; l < L; l++) {
+            const bool in = i + l < end;
+            const T yv = in ? (T)y[i + l] : (T)0;
+#pragma unroll
+            for (int it = 0; it < NI; it++) {
+                if (!on[it]) continue;
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    T df = in ? (yv - x[it][u][i + l]) : (T)0;
+                    acc[it][u][l] = df * df + acc[it][u][l];
+                }
+            }
+        }
+    }
+}
+
+template <typename T, int NI>
+__device__ __forceinline__ void sq4_finish(const T (&acc)[NI][4][16 / sizeof(T)], T (&out)[NI][4])
+{
+    constexpr int L = 16 / (int)sizeof(T);
+#pragma unroll
+    for (int it = 0; it < NI; it++)
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            out[it][u] = (L == 4) ? (acc[it][u][0] + acc[it][u][1]) + (acc[it][u][2 % L] + acc[it][u][3 % L])
+                                  : acc[it][u][0] + acc[it][u][1 % L];
+}

@@ -1594,7 +1594,8 @@ class DeviceIndex:
         once, removed rows never), restrictions and distance are radius_probe's: the answer is the first k entries of
         every list of radius_probe(+inf, n_probes), ids and distance bits alike.  qn, q_pq: as query_batch takes them.
         1 <= k <= 1024, n_probes >= 1 (ValueError).  allowed: a bool mask of length N or row ids; an AllowSet is
-        refused (TypeError).  Every vector store.  Not for a list-sharded index."""
+        refused (TypeError).  Every vector store, d <= 4096 (beyond 1 364 dims in float32, 2 040 in half, 682 in
+        float64 the distance pass walks d in slabs: the same answer).  Not for a list-sharded index."""
         k = int(k)
         if not 1 <= k <= 1024:
             raise ValueError(f"knn_probe: k in [1, 1024], got {k}")
@@ -1614,7 +1615,8 @@ class DeviceIndex:
 
     def knn_probe_tile(self):
         """(QT, RB): the queries per tile and the rows per staged block of knn_probe's distance pass on this index
-        (tk_index_knn_probe_tile; they follow from d and the vector store)"""
+        (tk_index_knn_probe_tile; they follow from d and the vector store: _lib.PROBE_WIDE_TILE where d is walked in
+        slabs of _lib.PROBE_WIDE_DS elements, at wide d or under OPT_PROBE_WIDE)"""
         qt, rb = C.c_int(0), C.c_int(0)
         _lib.check(_lib.lib().tk_index_knn_probe_tile(self._h, C.byref(qt), C.byref(rb)))
         return qt.value, rb.value
@@ -2892,7 +2894,7 @@ class IVF:
         a row stored in several probed lists is one candidate and a row taken out by remove() is none; the answer is
         the first k entries of every list of radius_search(qs, +inf, n_probes=n_probes), ids and distance bits alike.
         The restrictions as knn_brute's; allowed: a bool mask of length N or row ids, not an AllowSet.
-        1 <= k <= 1024, n_probes >= 1 (ValueError).  Every vector store.  Not for a list-sharded index."""
+        1 <= k <= 1024, n_probes >= 1 (ValueError).  Every vector store, d <= 4096.  Not for a list-sharded index."""
         if not 1 <= int(k) <= 1024:
             raise ValueError(f"knn_probe: k in [1, 1024], got {int(k)}")
         qn, qp, dev = self._radius_front("knn_probe", qs, np.inf, allowed, tags, tags_mode, between, n_probes)
