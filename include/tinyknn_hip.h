@@ -1038,6 +1038,27 @@ int tk_index_knn_probe(tk_index *ix, const float *q, const void *q_pq, int q_pq_
                        const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group, const uint64_t *tags,
                        int tag_mode, const int64_t *between, int64_t *out_ids, void *out_dist);
 int tk_index_knn_probe_tile(tk_index *ix, int *qt, int *rb);
+/* tk_index_knn_probe with its distances made on the f16 matrix cores (probe_matrix.hip), for an index that
+ * stores its vectors in half (TK_DATA_F16).  Arguments, probes, lists, candidates, the twin rule, the restrictions,
+ * the -1 / +inf padding, k <= 1024, d <= 4096 and the cut into query chunks are tk_index_knn_probe's, word for word;
+ * the tables, the key buffer and the selection are its code.  out_dist is float32.  Only the distance differs: for the
+ * prepared query x (float32) and the stored row y (half, read as exact reals)
+ *   dist_m = max(0, (xn + yn) - 2 * dot)  in float32
+ *   xn, yn: the float32 self-dots of x and of float(y) in numpy's einsum order
+ *   dot   = 2^-e * sum_t (x_hi,t + x_lo,t) * y_t, accumulated in float32 by v_mfma_f32_32x32x16_f16
+ *   x_hi  = half(2^e x), x_lo = half(2^e x - float(x_hi)); e puts the query's largest component into [2^14, 2^15)
+ *           (e = 0 for a zero query, at most 126)
+ * A product of two halfs is exact in float32 and the scaling is exact: dist_m differs from dist by float32 accumulation
+ * rounding and 2^-22 of the query, and equals it bit for bit where every sum is exact in float32 (integer data).  With
+ * D the real squared distance and S = sum |x_t y_t|: |dist_m - D| <= (2d + 8) 2^-24 (|x|^2 + |y|^2 + 2S) + 2^-21 S.
+ * Answers ascend by (dist_m, row id).
+ * Refused before any device work (TK_ERR_ARG): a float32 or float64 vector store; a query holding a NaN or an infinity;
+ * everything tk_index_knn_probe refuses.  The distance pass takes tiles of 64 queries and blocks of 128 rows and walks
+ * d in slabs of 112; tk_index_knn_probe_tile keeps reporting the exact pass's tile. */
+int tk_index_knn_probe_matrix(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
+                              int n_probes, const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
+                              const uint64_t *tags, int tag_mode, const int64_t *between, int64_t *out_ids,
+                              void *out_dist);
 /* The exact k nearest rows inside each query's own group (group_exact.hip): what the restricted call
  * above answers for group[i] >= 0 among the rows that are STORED, at a cost that follows the size of the group instead
  * of N — a query reads the rows of its group and no other.  Ranked by the rescoring's distance (numpy's einsum order

@@ -39,6 +39,9 @@ OPT_PAIR_NQ, OPT_LABELS24, OPT_PROBE_BUDGET, OPT_PROBE_WIDE = 8, 9, 10, 11
 # of a slab of d per vector store
 PROBE_WIDE_TILE = (32, 64)
 PROBE_WIDE_DS = {"float32": 128, "float16": 128, "float64": 64}
+# tk_index_knn_probe_matrix's distance kernel (probe_matrix.hip: PM_QT, PM_RB, PM_DS): its tile and the halfs of a slab
+PROBE_MATRIX_TILE = (64, 128)
+PROBE_MATRIX_DS = 112
 # tk_index_last_replay: the forms of a batch's heap replay (TK_REPLAY_*)
 REPLAY_PAIR, REPLAY_LANES, REPLAY_PACKED_DISTINCT, REPLAY_LANES_TWIN, REPLAY_LANES_DEDUPE, REPLAY_PACKED, REPLAY_GENERAL = range(7)
 REPLAY_NAMES = ("pair", "lanes", "packed_distinct", "lanes_twin", "lanes_dedupe", "packed", "general")
@@ -245,6 +248,9 @@ SIGNATURES = {
     "tk_index_radius_probe_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tk_index_knn_probe": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),
+    "tk_index_knn_probe_matrix": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64p,
+                                            C.c_void_p]),
     "tk_index_knn_probe_tile": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tk_index_knn_group": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),

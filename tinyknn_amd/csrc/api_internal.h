@@ -286,6 +286,9 @@ struct tk_index {
     // distance kernel at any d
     DevBuf pe_probes, pe_seglen, pe_segoff, pe_scan, pe_lists, pe_pairs, pe_tiles, pe_keys, pe_out;
     int opt_probe_budget = 0, opt_probe_wide = 0;
+    // tk_index_knn_probe_matrix (probe_matrix.hip): the call's queries as two half planes (nq, dpad) each, and per query
+    // its float32 self-dot and the scale 2^-e
+    DevBuf pm_xh, pm_xl, pm_xn;
     DevBuf gx_begin, gx_len;                                                        // tk_index_knn_group: a query's span
     DevBuf gx_col;                                                                  // tk_index_knn_between: ... and its column
     int rot_d_pad = 0;

@@ -36,39 +36,9 @@
 // whose staging and arithmetic overlap; nothing is double-buffered inside one.
 // Where not even 4 queries and 8 whole rows fit (d from 1 365 on float32 vectors, 2 041 on half, 683 on float64; up to
 // 4 096) the distance pass is probe_dist_wide_kernel below: the same tiles, keys and places, d walked in slabs.
-#include "api_internal.h"
+#include "probe_job.h"
 #include "sqdist_row.h"
 #include "span_exact.h"
-
-#define PE_THREADS 256
-#define PE_LDS_LIMIT (64 * 1024)
-#define PE_QT_MAX 64
-
-struct PeTile {
-    int QT, RB;
-    int xstride;            // elements of T between two queries in LDS
-    int ystride;            // bytes between two staged rows in LDS
-    size_t lds;
-    int DS;                 // 0: probe_dist_kernel; else probe_dist_wide_kernel and the elements of its slab
-};
-
-struct PeJob {
-    const float *q;                 // (nq, d) prepared queries of the whole call
-    const void *rows;               // the vectors, TY
-    const int64_t *probes;          // (nq, kc)
-    const int64_t *ids, *ids_off, *list_n;
-    const int32_t *twin_list;       // twins.hip, twin_w > 0
-    const long long *seglen, *segoff;   // (nq * kc + 1): keys of the (query, rank), and where they begin in the call
-    long long seg_base;             // segoff of the chunk's first (query, rank): its key buffer begins there
-    int64_t pair0, n_pairs;         // the chunk's (query, rank)s: [pair0, pair0 + n_pairs)
-    int *count, *cursor, *list_off, *ntiles, *tile_off;    // (n_lists + 1) each
-    int *pair_of;                   // the chunk's pairs by list: the (query, rank) index of each
-    int4 *tiles;                    // (list, first pair, count, -)
-    void *keys;                     // GxKey<T>::type per candidate position
-    int64_t n_lists, N;
-    int d, kc, twin_w;
-    PeTile t;
-};
 
 // the list a probe names: -1 (an unfilled coarse heap) is the last list; -1 for what names none (radius_probe.hip)
 __device__ __forceinline__ int32_t pe_list(int64_t p, int64_t n_lists)
@@ -512,11 +482,12 @@ static int pe_tile(const tk_index *ix, PeTile &t)
 }
 
 template <typename T, typename TY>
-static void pe_launch(const PeJob &j, unsigned max_tiles, const TkBruteRestrict &r, int64_t q0, int64_t m, int k,
-                      int64_t *out, void *out_d)
+static void pe_launch(const PeJob &j, const PmQueries *mx, unsigned max_tiles, const TkBruteRestrict &r, int64_t q0,
+                      int64_t m, int k, int64_t *out, void *out_d)
 {
     typedef typename GxKey<T>::type K;
-    if (j.t.DS) hipLaunchKernelGGL((probe_dist_wide_kernel<T, TY>), dim3(max_tiles), dim3(PE_THREADS), 0, 0, j);
+    if (mx) pm_launch_dist(j, *mx, max_tiles);      // (float keys on half rows: pe_knn_probe)
+    else if (j.t.DS) hipLaunchKernelGGL((probe_dist_wide_kernel<T, TY>), dim3(max_tiles), dim3(PE_THREADS), 0, 0, j);
     else hipLaunchKernelGGL((probe_dist_kernel<T, TY>), dim3(max_tiles), dim3(PE_THREADS), j.t.lds, 0, j);
     hipLaunchKernelGGL((probe_select_kernel<T>), dim3((unsigned)m), dim3(GX_THREADS), pe_select_lds(j.kc, sizeof(K)), 0,
                        j, r, q0, k, out, (T *)out_d);
@@ -545,10 +516,10 @@ extern "C" int tk_index_knn_probe_tile(tk_index *ix, int *qt, int *rb)
     return TK_OK;
 }
 
-extern "C" int tk_index_knn_probe(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
-                                  int n_probes, const uint8_t *allowed_mask, const int64_t *exclude,
-                                  const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between,
-                                  int64_t *out_ids, void *out_dist)
+// the body of tk_index_knn_probe and tk_index_knn_probe_matrix: matrix picks the distance pass (probe_matrix.hip)
+static int pe_knn_probe(tk_index *ix, bool matrix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
+                        int n_probes, const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
+                        const uint64_t *tags, int tag_mode, const int64_t *between, int64_t *out_ids, void *out_dist)
 {
     IXLOCK(ix);
     ARGCHECK(ix && ix->have_data && ix->have_lists && ix->have_pq && ix->have_centers,
@@ -560,6 +531,10 @@ extern "C" int tk_index_knn_probe(tk_index *ix, const float *q, const void *q_pq
     PeTile tile;
     TRY(pe_tile(ix, tile));
     ARGCHECK(nq >= 0 && (nq == 0 || (q && q_pq && out_ids)), "buffers");
+    if (matrix) {
+        TRY(pm_check(ix, q, nq));
+        pm_tile(tile);
+    }
     const int32_t *twin_list = nullptr;
     int twin_w = 0;
     TRY(radius_probe_twins(ix, &twin_list, &twin_w));
@@ -589,6 +564,8 @@ extern "C" int tk_index_knn_probe(tk_index *ix, const float *q, const void *q_pq
                               return TK_OK;
                           }));
     HIPCHECK(hipMemcpy(ix->br_q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
+    PmQueries mx{};
+    if (matrix) TRY(pm_prepare(ix, nq, mx));
     // the keys of every (query, rank) and where they begin
     long long *seglen = ix->pe_seglen.as<long long>(), *segoff = ix->pe_segoff.as<long long>();
     hipLaunchKernelGGL(pe_seg_kernel, dim3((unsigned)((pairs + 256) / 256)), dim3(256), 0, 0,
@@ -660,13 +637,32 @@ extern "C" int tk_index_knn_probe(tk_index *ix, const float *q, const void *q_pq
         TRY(pe_scan(ix, j.ntiles, j.tile_off, nl1));
         hipLaunchKernelGGL(pe_fill_kernel, dim3(pgrid), dim3(256), 0, 0, j);
         hipLaunchKernelGGL(pe_table_kernel, dim3(lgrid), dim3(256), 0, 0, j);
-        if (f64) pe_launch<double, double>(j, (unsigned)max_tiles, r, o, m, k, out, out_d);
-        else if (ix->data_dtype == TK_DATA_F16) pe_launch<float, _Float16>(j, (unsigned)max_tiles, r, o, m, k, out, out_d);
-        else pe_launch<float, float>(j, (unsigned)max_tiles, r, o, m, k, out, out_d);
+        if (f64) pe_launch<double, double>(j, nullptr, (unsigned)max_tiles, r, o, m, k, out, out_d);
+        else if (ix->data_dtype == TK_DATA_F16)
+            pe_launch<float, _Float16>(j, matrix ? &mx : nullptr, (unsigned)max_tiles, r, o, m, k, out, out_d);
+        else pe_launch<float, float>(j, nullptr, (unsigned)max_tiles, r, o, m, k, out, out_d);
         HIPCHECK(hipGetLastError());
         o = e;
     }
     HIPCHECK(hipMemcpy(out_ids, out, (size_t)nq * k * 8, hipMemcpyDeviceToHost));                 // (synchronises)
     if (out_dist) HIPCHECK(hipMemcpy(out_dist, out_d, (size_t)nq * k * ksz, hipMemcpyDeviceToHost));
     return TK_OK;
+}
+
+extern "C" int tk_index_knn_probe(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
+                                  int n_probes, const uint8_t *allowed_mask, const int64_t *exclude,
+                                  const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between,
+                                  int64_t *out_ids, void *out_dist)
+{
+    return pe_knn_probe(ix, false, q, q_pq, q_pq_is_f64, nq, k, n_probes, allowed_mask, exclude, group, tags, tag_mode,
+                        between, out_ids, out_dist);
+}
+
+extern "C" int tk_index_knn_probe_matrix(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq,
+                                         int k, int n_probes, const uint8_t *allowed_mask, const int64_t *exclude,
+                                         const int32_t *group, const uint64_t *tags, int tag_mode,
+                                         const int64_t *between, int64_t *out_ids, void *out_dist)
+{
+    return pe_knn_probe(ix, true, q, q_pq, q_pq_is_f64, nq, k, n_probes, allowed_mask, exclude, group, tags, tag_mode,
+                        between, out_ids, out_dist);
 }

@@ -1586,7 +1586,7 @@ class DeviceIndex:
         return qn, query_radius(radius, len(qn)), restrict
 
     def knn_probe(self, qn, q_pq, k, n_probes, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                  between=None, return_distances=False):
+                  between=None, return_distances=False, matrix=False):
         """The exact k nearest rows among the rows of the lists each normalised query probes (tk_index_knn_probe,
         DESIGN §3.21; FAISS's IVF-Flat search): (nq, k) int64 ids ascending by (distance, row id), ending in -1 where
         fewer than k candidates pass; with return_distances (ids, dists), the rescoring's squared distances — float32,
@@ -1595,7 +1595,15 @@ class DeviceIndex:
         every list of radius_probe(+inf, n_probes), ids and distance bits alike.  qn, q_pq: as query_batch takes them.
         1 <= k <= 1024, n_probes >= 1 (ValueError).  allowed: a bool mask of length N or row ids; an AllowSet is
         refused (TypeError).  Every vector store, d <= 4096 (beyond 1 364 dims in float32, 2 040 in half, 682 in
-        float64 the distance pass walks d in slabs: the same answer).  Not for a list-sharded index."""
+        float64 the distance pass walks d in slabs: the same answer).  Not for a list-sharded index.
+        matrix=True (tk_index_knn_probe_matrix; store="float16" only, finite queries — else AssertionError):
+        the same probes, candidates, restrictions and order, the distance made on the f16 matrix cores —
+        dist_m = max(0, (xn + yn) - 2 dot) in float32, xn and yn the float32 self-dots of the query and of the row in
+        einsum order, dot = 2^-e sum (x_hi + x_lo) y accumulated in float32, x_hi = half(2^e x),
+        x_lo = half(2^e x - x_hi), e putting the query's largest component into [2^14, 2^15).  It differs from the
+        exact distance by float32 accumulation rounding and 2^-22 of the query, by nothing where the sums are exact
+        in float32; ids ascend by (dist_m, row id).  Opt-in: it routes nothing by itself, and at narrow d (the GloVe
+        shape, d = 100) the call is bound by its table, selection and host passes, so expect the gain at wide d."""
         k = int(k)
         if not 1 <= k <= 1024:
             raise ValueError(f"knn_probe: k in [1, 1024], got {k}")
@@ -1608,7 +1616,8 @@ class DeviceIndex:
         q_pq, n_probes = self._probe_args(qn, q_pq, n_probes)
         out = np.full((nq, k), -1, dtype=np.int64)
         dist = np.full((nq, k), np.inf, dtype=np.float64 if self._f64 else np.float32) if return_distances else None
-        _lib.check(_lib.lib().tk_index_knn_probe(
+        call = _lib.lib().tk_index_knn_probe_matrix if matrix else _lib.lib().tk_index_knn_probe
+        _lib.check(call(
             self._h, _lib.ptr(qn, _lib._f32p), q_pq.ctypes.data, int(q_pq.dtype == np.float64), nq, k, n_probes,
             *self._host_pointers(restrict), _lib.ptr(out, _lib._i64p), None if dist is None else dist.ctypes.data))
         return (out, dist) if return_distances else out
@@ -2885,7 +2894,7 @@ class IVF:
         return (qn, dev) if n_probes is None else (qn, qp, dev)
 
     def knn_probe(self, qs, k, n_probes, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                  between=None, return_distances=False):
+                  between=None, return_distances=False, matrix=False):
         """The exact k nearest rows among the rows of the n_probes lists each raw query probes (DeviceIndex.knn_probe
         on the prepared queries): FAISS's IVF-Flat search, the call between query_batch — which ranks
         the same lists by PQ estimates — and knn_brute, which reads all N rows.  (nq, k) int64 ids ascending by
@@ -2894,12 +2903,16 @@ class IVF:
         a row stored in several probed lists is one candidate and a row taken out by remove() is none; the answer is
         the first k entries of every list of radius_search(qs, +inf, n_probes=n_probes), ids and distance bits alike.
         The restrictions as knn_brute's; allowed: a bool mask of length N or row ids, not an AllowSet.
-        1 <= k <= 1024, n_probes >= 1 (ValueError).  Every vector store, d <= 4096.  Not for a list-sharded index."""
+        1 <= k <= 1024, n_probes >= 1 (ValueError).  Every vector store, d <= 4096.  Not for a list-sharded index.
+        matrix=True: the distances on the f16 matrix cores (DeviceIndex.knn_probe; store="float16" only, finite
+        queries): dist_m = max(0, (|x|^2 + |y|^2) - 2 x.y) with the query split into two halfs, within float32
+        accumulation rounding and 2^-22 of the query of the exact distance and equal to it where the sums are exact
+        in float32; ids ascend by (dist_m, row id)."""
         if not 1 <= int(k) <= 1024:
             raise ValueError(f"knn_probe: k in [1, 1024], got {int(k)}")
         qn, qp, dev = self._radius_front("knn_probe", qs, np.inf, allowed, tags, tags_mode, between, n_probes)
         return dev.knn_probe(qn, qp, k, n_probes, allowed=allowed, exclude=exclude, group=group, tags=tags,
-                             tags_mode=tags_mode, between=between, return_distances=return_distances)
+                             tags_mode=tags_mode, between=between, return_distances=return_distances, matrix=matrix)
 
     def knn_group(self, qs, k, group, *, allowed=None, exclude=None, tags=None, tags_mode="any", between=None,
                   return_distances=False):
