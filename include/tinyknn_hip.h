@@ -949,6 +949,20 @@ int tk_index_knn_brute(tk_index *ix, const float *q, int64_t nq, int k, int64_t 
 int tk_index_knn_brute_ex(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
                           const int64_t *exclude, const int32_t *group, const uint64_t *tags, int tag_mode,
                           const int64_t *between, int64_t *out_ids, float *out_dist);
+/* tk_index_knn_brute_ex for an index that stores its vectors as half (store float16), any d <= 4096, on the f16 matrix
+ * cores (brute_matrix.hip): the k rows with the smallest (dist_m, row) among the rows that pass the
+ * restrictions, arguments and padding as tk_index_knn_brute_ex's.  dist_m is tk_index_knn_probe_matrix's value bit for
+ * bit — max(0, (xn + yn) - 2 * (acc * 2^-e)), xn and yn the float32 self-dots in einsum order, acc one float32
+ * accumulator of v_mfma_f32_32x32x16_f16 over (x_hi + x_lo) y, K ascending, hi before lo — so both calls return the
+ * same bytes where every list is probed; it equals the exact distance where every sum is exact in float32 and lies
+ * within that call's bound of the real squared distance otherwise.  out_dist (or NULL): dist_m, never negative.
+ * Sample, segments, candidate lists, the overflow retry and the selection are tk_index_knn_brute_ex's.
+ * TK_ERR_ARG before any device work: float32 or float64 vectors ("needs store=\"float16\""), a NaN or an infinity in
+ * q, d > 4096, k outside [1, min(1024, N)], N >= 2^31, a list-sharded index.  tk_index_knn_brute(_ex) itself is
+ * unchanged: float32 vectors, d <= 128. */
+int tk_index_knn_brute_matrix(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
+                              const int64_t *exclude, const int32_t *group, const uint64_t *tags, int tag_mode,
+                              const int64_t *between, int64_t *out_ids, float *out_dist);
 /* Every row within a radius of each query, exactly (radius.hip): row j is a hit of query i iff it passes
  * the query's restrictions — allowed_mask / exclude / group / tags, tag_mode / between exactly as
  * tk_index_knn_brute_ex takes them, host arrays, NULL: not given — and part(i, j) <= radius[i], compared in float32,

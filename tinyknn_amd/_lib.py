@@ -42,6 +42,9 @@ PROBE_WIDE_DS = {"float32": 128, "float16": 128, "float64": 64}
 # tk_index_knn_probe_matrix's distance kernel (probe_matrix.hip: PM_QT, PM_RB, PM_DS): its tile and the halfs of a slab
 PROBE_MATRIX_TILE = (64, 128)
 PROBE_MATRIX_DS = 112
+# tk_index_knn_brute_matrix's tile kernel (brute_matrix.hip: BM_QT, BM_RB, BM_DS)
+BRUTE_MATRIX_TILE = (128, 128)
+BRUTE_MATRIX_DS = 64
 # tk_index_last_replay: the forms of a batch's heap replay (TK_REPLAY_*)
 REPLAY_PAIR, REPLAY_LANES, REPLAY_PACKED_DISTINCT, REPLAY_LANES_TWIN, REPLAY_LANES_DEDUPE, REPLAY_PACKED, REPLAY_GENERAL = range(7)
 REPLAY_NAMES = ("pair", "lanes", "packed_distinct", "lanes_twin", "lanes_dedupe", "packed", "general")
@@ -239,6 +242,8 @@ SIGNATURES = {
     "tk_index_knn_brute": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, _i64p]),
     "tk_index_knn_brute_ex": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),
+    "tk_index_knn_brute_matrix": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),
     "tk_index_radius_brute": (C.c_int, [C.c_void_p, _f32p, C.c_int64, _f32p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, _i64p, _i64p]),
     "tk_index_radius_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,6 +1,7 @@
 // api_build.hip — device-side build of an index, raw-query preparation, exact brute force and the batch
 // form of _FastDistanceTable.top over one flat array (FlatTop).  (Split from api.hip in round 4.)
 #include "api_internal.h"
+#include "probe_job.h"
 
 // ---------------------------------------------------------------------------
 // device-resident build (devbuild.hip): IVF.build for vectors that live in HBM
@@ -1144,14 +1145,20 @@ extern "C" int tk_index_query_batch_raw(tk_index *ix, const float *q_raw, int64_
 // r (or NULL): the restriction, its arrays on the device.  retry: a candidate list that overflowed under the segment
 // rule is not an error — the selection runs once more from the sampled tau with the segment length that cannot
 // overflow, the largest multiple of 32 not above cap - k (a segment appends at most `seg` rows to at most k kept ones).
+// matrix: the rows are half and the tiles run on the f16 matrix cores (brute_matrix.hip); the values are
+// §3.22's dist_m and d may reach 4096.  false: float32 rows, d <= 128, numpy's part values.
 static int knn_brute(tk_index *ix, const float *q, int64_t nq, int k, const TkBruteRestrict *r, bool retry,
-                     int64_t *out_ids, float *out_dist)
+                     int64_t *out_ids, float *out_dist, bool matrix = false)
 {
     ARGCHECK(ix && ix->have_data, "set_data first");
-    ARGCHECK(ix->data_dtype != TK_DATA_F64, "float32 vectors only");
-    ARGCHECK(ix->data_dtype != TK_DATA_F16, "knn_brute is the ground truth on float32 vectors: this index stores "
-                                            "them as half (store=\"float16\"); ask a float32 index");
-    ARGCHECK(ix->d <= 128, "d <= 128");
+    if (matrix) {           // (tk_index_knn_brute_matrix has made pm_check's refusals)
+        ARGCHECK(ix->d <= 4096, "d <= 4096");
+    } else {
+        ARGCHECK(ix->data_dtype != TK_DATA_F64, "float32 vectors only");
+        ARGCHECK(ix->data_dtype != TK_DATA_F16, "knn_brute is the ground truth on float32 vectors: this index stores "
+                                                "them as half (store=\"float16\"); ask a float32 index");
+        ARGCHECK(ix->d <= 128, "d <= 128");
+    }
     ARGCHECK(nq >= 0 && q && out_ids, "buffers");
     ARGCHECK(k >= 1 && k <= 1024 && k <= ix->N, "1 <= k <= min(1024, N)");
     ARGCHECK(ix->N < (1ll << 31), "N < 2^31");
@@ -1172,15 +1179,18 @@ static int knn_brute(tk_index *ix, const float *q, int64_t nq, int k, const TkBr
     int *overflow = ix->br_count.as<int>() + nq;
     float *tau = ix->br_tau.as<float>(), *tau0 = tau + nq, *dist = out_dist ? ix->br_dist.as<float>() : nullptr;
     const float *X = ix->br_q.as<float>(), *Y = ix->data.as<float>();
+    PmQueries pq{};
+    if (matrix) TRY(pm_prepare(ix, nq, pq));
+    const TkBruteMatrix planes{pq.xh, pq.xl, pq.xn, pq.xs, pq.dpad}, *mx = matrix ? &planes : nullptr;
     if (tk_launch_brute_tau(X, nq, ix->d, Y, ix->N, k, ix->br_ynorm.as<float>(), ix->br_vals.as<float>(), ns, tau,
-                            ix->br_sample.as<float>(), r, nullptr))
+                            ix->br_sample.as<float>(), r, nullptr, mx))
         return fail(TK_ERR_HIP, "tk_launch_knn_brute: unsupported size / LDS attribute");
     if (retry) HIPCHECK(hipMemcpyAsync(tau0, tau, (size_t)nq * 4, hipMemcpyDeviceToDevice, nullptr));
     int64_t seg = tk_brute_segment(k, ns, cap);
     for (int attempt = 0;; attempt++) {
         if (tk_launch_brute_select(X, nq, ix->d, Y, ix->N, k, ix->br_ynorm.as<float>(), tau,
                                    ix->br_cand.as<unsigned long long>(), cap, ix->br_count.as<int>(), overflow,
-                                   ix->br_out.as<int64_t>(), dist, seg, r, nullptr))
+                                   ix->br_out.as<int64_t>(), dist, seg, r, nullptr, mx))
             return fail(TK_ERR_HIP, "tk_launch_knn_brute: unsupported size / LDS attribute");
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipDeviceSynchronize());
@@ -1268,6 +1278,27 @@ extern "C" int tk_index_knn_brute_ex(tk_index *ix, const float *q, int64_t nq, i
     if (!any) return knn_brute(ix, q, nq, k, nullptr, true, out_ids, out_dist);
     if (nq == 0) return TK_OK;
     return knn_brute(ix, q, nq, k, &r, true, out_ids, out_dist);
+}
+
+// tk_index_knn_brute_ex on the f16 matrix cores for a half store, d <= 4096 (brute_matrix.hip)
+extern "C" int tk_index_knn_brute_matrix(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
+                                         const int64_t *exclude, const int32_t *group, const uint64_t *tags,
+                                         int tag_mode, const int64_t *between, int64_t *out_ids, float *out_dist)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix && ix->have_data, "set_data first");
+    ARGCHECK(!ix->sharded, "list-sharded index: knn_brute(matrix=True) is not supported");
+    ARGCHECK(nq >= 0 && (nq == 0 || q), "buffers");
+    TRY(pm_check(ix, q, nq));
+    // (knn_brute's own, here in front of the restriction's uploads: nothing reaches the device for a refused call)
+    ARGCHECK(ix->d <= 4096, "d <= 4096");
+    ARGCHECK(k >= 1 && k <= 1024 && k <= ix->N, "1 <= k <= min(1024, N)");
+    ARGCHECK(ix->N < (1ll << 31), "N < 2^31");
+    TkBruteRestrict r;
+    bool any;
+    TRY(brute_restrict(ix, nq, allowed_mask, exclude, group, tags, tag_mode, between, r, any));
+    if (any && nq == 0) return TK_OK;
+    return knn_brute(ix, q, nq, k, any ? &r : nullptr, true, out_ids, out_dist, true);
 }
 
 // ---------------------------------------------------------------------------

@@ -561,12 +561,30 @@ struct TkBruteRestrict {
 // from the strided sample, counted over the sample rows a query's restriction passes (+inf below k of them).
 // _select: the selection over segments of `seg` rows (a multiple of 32) from that tau, which it tightens in place;
 // out_dist (or NULL): (nq, k) float32, the part value beside each id, +inf beside -1.
+// mx (or NULL): the rows are half and the tiles run on the f16 matrix cores (brute_matrix.hip) — Y and
+// sample are then half arrays behind their float pointers, X is not read (the queries are mx's planes) and d <= 4096.
+// NULL: float32 rows, the f32 tile kernel, d <= 128.
+struct TkBruteMatrix {
+    const void *xh, *xl;            // pm_prepare's planes (PmQueries): x_hi and x_lo of 2^e x, (nq, dpad) halfs each
+    const float *xn, *xs;           // |x|^2 and 2^-e
+    int dpad;                       // d rounded up to 16
+};
 int64_t tk_brute_segment(int k, int64_t ns, int cap);
 int tk_launch_brute_tau(const float *X, int64_t nq, int d, const float *Y, int64_t N, int k, float *ynorm2,
-                        float *vals, int64_t ns, float *tau, float *sample, const TkBruteRestrict *r, hipStream_t s);
+                        float *vals, int64_t ns, float *tau, float *sample, const TkBruteRestrict *r, hipStream_t s,
+                        const TkBruteMatrix *mx = nullptr);
 int tk_launch_brute_select(const float *X, int64_t nq, int d, const float *Y, int64_t N, int k, const float *ynorm2,
                            float *tau, unsigned long long *cand, int cap, int *count, int *overflow, int64_t *out,
-                           float *out_dist, int64_t seg, const TkBruteRestrict *r, hipStream_t s);
+                           float *out_dist, int64_t seg, const TkBruteRestrict *r, hipStream_t s,
+                           const TkBruteMatrix *mx = nullptr);
+// brute_matrix.hip, for the two halves above: the half forms of row_norms_kernel and sample_rows_kernel, and one launch
+// of brute_matrix_tiles_kernel<mode, r != NULL> over `cols` columns (the arguments of brute.hip's brute_tiles)
+void tk_launch_brute_half_norms(const void *Y, int64_t n, int d, float *out, hipStream_t s);
+void tk_launch_brute_half_sample(const void *Y, int d, int64_t ns, int64_t stride, void *out, hipStream_t s);
+void tk_launch_brute_matrix_tiles(int mode, const TkBruteMatrix &mx, int64_t nq, int d, const void *Y,
+                                  const float *ynorm2, int64_t cols, float *vals, const float *tau,
+                                  unsigned long long *cand, int cap, int *count, int64_t j_base, int64_t j_stride,
+                                  const TkBruteRestrict *r, hipStream_t s);
 
 // ---- every row within a radius of each query (radius.hip): count, fill, sort, decode ----
 // see radius.hip for the buffers; the launchers return -1 on unsupported sizes

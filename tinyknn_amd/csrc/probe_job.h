@@ -44,3 +44,21 @@ int pm_check(const tk_index *ix, const float *q, int64_t nq);           // the r
 void pm_tile(PeTile &t);                                                // the matrix pass's tile
 int pm_prepare(tk_index *ix, int64_t nq, PmQueries &mx);                // the queries in br_q -> mx (workspace of ix)
 void pm_launch_dist(const PeJob &j, const PmQueries &mx, unsigned max_tiles);
+
+// ---- probe_matrix.hip and brute_matrix.hip: how both stage a half row ----
+// piece c (8 halfs) of a row of d halfs, zeros behind d, in loads of U: uint4 where d % 8 == 0, uint2 where d % 4 == 0
+// (d = 100), else halfs — d is a multiple of the halfs of U, so a load is whole or not made
+template <typename U>
+__device__ __forceinline__ uint4 pm_row_piece(const _Float16 *row, int c, int d)
+{
+    constexpr int NU = 16 / (int)sizeof(U), E = (int)sizeof(U) / 2;
+    union {
+        uint4 v;
+        U u[NU];
+    } p;
+    p.v = make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < NU; i++)
+        if (c * 8 + i * E < d) p.u[i] = *(const U *)(row + c * 8 + i * E);
+    return p.v;
+}

@@ -99,23 +99,6 @@ __global__ __launch_bounds__(64) void pm_prepare_kernel(const float *__restrict_
     }
 }
 
-// piece c (8 halfs) of a row of d halfs, zeros behind d, in loads of U: uint4 where d % 8 == 0, uint2 where d % 4 == 0
-// (d = 100), else halfs — d is a multiple of the halfs of U, so a load is whole or not made
-template <typename U>
-__device__ __forceinline__ uint4 pm_row_piece(const _Float16 *row, int c, int d)
-{
-    constexpr int NU = 16 / (int)sizeof(U), E = (int)sizeof(U) / 2;
-    union {
-        uint4 v;
-        U u[NU];
-    } p;
-    p.v = make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < NU; i++)
-        if (c * 8 + i * E < d) p.u[i] = *(const U *)(row + c * 8 + i * E);
-    return p.v;
-}
-
 template <typename U>
 __device__ __forceinline__ void pm_walk(const PeJob &j, const PmQueries &mx, PmLds &s, const int4 tile)
 {

@@ -1386,7 +1386,8 @@ class DeviceIndex:
             int(pass_1 or 0), _lib.ptr(out, _lib._i64p)))
         return out
 
-    def knn_brute(self, qn, k, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any", between=None):
+    def knn_brute(self, qn, k, matrix=False, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
+                  between=None):
         """Exact k nearest rows of IVF.data for normalised queries (ground truth of recall;
         tk_index_knn_brute: f32 MFMA, numpy's distances bit for bit), ascending.  Float32 vectors only:
         refused on a float64 and on a half index.
@@ -1396,18 +1397,22 @@ class DeviceIndex:
         the probed lists hold too few passing rows).  allowed: a bool mask of length N or row ids; an AllowSet is
         laid out by list position and refused (TypeError).  A mask of the surviving rows is the truth after remove():
         the vectors of removed rows stay in HBM and the unrestricted call still returns them.
-        With nothing given the call is tk_index_knn_brute's.  The values the rows were ranked by: knn_brute_dist."""
-        return self._knn_brute(qn, k, False, allowed, exclude, group, tags, tags_mode, between)
+        With nothing given the call is tk_index_knn_brute's.  The values the rows were ranked by: knn_brute_dist.
+        matrix=True (tk_index_knn_brute_matrix; store="float16" only, finite queries, d <= 4096 — else
+        AssertionError): the search over all rows of a half store on the f16 matrix cores, ranked by knn_probe(matrix=
+        True)'s dist_m — the same bytes as that call with every list probed, within its bound B of the real distance."""
+        return self._knn_brute(qn, k, False, allowed, exclude, group, tags, tags_mode, between, matrix)
 
-    def knn_brute_dist(self, qn, k, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                       between=None):
+    def knn_brute_dist(self, qn, k, matrix=False, *, allowed=None, exclude=None, group=None, tags=None,
+                       tags_mode="any", between=None):
         """knn_brute's ids and, beside each, the float32 `part` value it was ranked by: (ids, part), part = (|q|^2 +
         |y|^2) - 2 q.y as numpy's knn_brute sums it (utils.py:84; rounding can make it slightly negative), +inf
         beside -1.  Not the knn_brute1 distance that query_batch(return_distances=True) returns.  Always
-        tk_index_knn_brute_ex; with no restriction the ids are knn_brute's."""
-        return self._knn_brute(qn, k, True, allowed, exclude, group, tags, tags_mode, between)
+        tk_index_knn_brute_ex; with no restriction the ids are knn_brute's.  matrix=True: knn_brute's, and the values
+        are dist_m (never negative)."""
+        return self._knn_brute(qn, k, True, allowed, exclude, group, tags, tags_mode, between, matrix)
 
-    def _knn_brute(self, qn, k, want_dist, allowed, exclude, group, tags, tags_mode, between):
+    def _knn_brute(self, qn, k, want_dist, allowed, exclude, group, tags, tags_mode, between, matrix=False):
         """knn_brute / knn_brute_dist: the old entry point where nothing is asked beyond it, else tk_index_knn_brute_ex
         with the arguments parsed as query_batch parses them"""
         qn = np.ascontiguousarray(qn, dtype=np.float32)
@@ -1415,14 +1420,15 @@ class DeviceIndex:
         nq = qn.shape[0]
         out = np.empty((nq, k), dtype=np.int64)
         if (allowed is None and exclude is None and group is None and tags is None and between is None
-                and not want_dist):
+                and not want_dist and not matrix):
             _lib.check(_lib.lib().tk_index_knn_brute(self._h, _lib.ptr(qn, _lib._f32p), nq, int(k),
                                                      _lib.ptr(out, _lib._i64p)))
             return out
         restrict = self._brute_restrictions("knn_brute", nq, allowed, exclude, group, tags, tags_mode, between)
         dist = np.full((nq, k), np.inf, dtype=np.float32) if want_dist else None
         out[:] = -1
-        _lib.check(_lib.lib().tk_index_knn_brute_ex(
+        call = _lib.lib().tk_index_knn_brute_matrix if matrix else _lib.lib().tk_index_knn_brute_ex
+        _lib.check(call(
             self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), *self._host_pointers(restrict),
             _lib.ptr(out, _lib._i64p), None if dist is None else dist.ctypes.data))
         return (out, dist) if want_dist else out
@@ -2811,14 +2817,16 @@ class IVF:
         assert qp.shape[1] == dq
         return qn, qp
 
-    def knn_brute(self, qs, k, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any", between=None,
-                  return_distances=False):
+    def knn_brute(self, qs, k, matrix=False, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
+                  between=None, return_distances=False):
         """The exact k nearest rows of IVF.data for raw queries, under the restrictions of query_batch (DeviceIndex.
         knn_brute on the prepared queries: an angular index ranks its normalised rows): (nq, k) int64 ids ascending
         by (part, row), ending in -1 where fewer than k rows pass; with return_distances (ids, part): also the float32
         `part` values (DeviceIndex.knn_brute_dist: numpy's knn_brute values, not the rescoring's distances), +inf beside -1.  The ground truth of
         restricted recall; allowed= with a mask of the surviving rows is the truth after remove().  allowed: a bool
-        mask of length N or row ids, not an AllowSet.  Not for a list-sharded index."""
+        mask of length N or row ids, not an AllowSet.  Not for a list-sharded index.
+        matrix=True: DeviceIndex.knn_brute(matrix=True) — a half store of any d <= 4096 on the f16 matrix cores, the
+        values knn_probe(matrix=True)'s dist_m."""
         if isinstance(allowed, AllowSet):
             raise TypeError("knn_brute: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
                             "list position")
@@ -2829,7 +2837,8 @@ class IVF:
         dev = self._unsharded_device_index()
         qn, _ = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
         call = dev.knn_brute_dist if return_distances else dev.knn_brute
-        return call(qn, k, allowed=allowed, exclude=exclude, group=group, tags=tags, tags_mode=tags_mode, between=between)
+        return call(qn, k, allowed=allowed, exclude=exclude, group=group, tags=tags, tags_mode=tags_mode, between=between,
+                    matrix=matrix)
 
     def radius_search(self, qs, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
                       between=None, sort=True, max_results=None, n_probes=None):
