@@ -764,3 +764,211 @@ def test_mask_or_ids_parsers_keep_their_words():
         got = AllowSet.mask_of(arg, N)
         assert got.dtype == np.uint8 and got.shape == (N,) and got.flags.c_contiguous and np.array_equal(got, m)
     assert ivf_mod.removal_rows([], N).shape == (0,) and not AllowSet.mask_of([], N).any()
+
+
+# ---- the exact calls: knn_brute, radius_brute / _count, radius_probe, knn_probe, knn_group, knn_between ----
+
+RADIUS = np.array([0.5, 1.0, np.inf, -1.0, 2.0])
+GROUP_IDS = np.array([2, 0, 0, 5, 2**31 - 2], dtype=np.int64)       # knn_group's own argument: no -1
+
+# per foreign function: where its arguments sit — the restrictions by name, the outputs, and the scalars in front
+EXACT_PLACES = {
+    "tk_index_knn_brute_ex": dict(mask=4, exclude=5, group=6, tags=7, mode=8, between=9, out=10, dist=11, n=12),
+    "tk_index_knn_brute_matrix": dict(mask=4, exclude=5, group=6, tags=7, mode=8, between=9, out=10, dist=11, n=12),
+    "tk_index_radius_brute": dict(mask=4, exclude=5, group=6, tags=7, mode=8, between=9, n=15),
+    "tk_index_radius_probe": dict(mask=7, exclude=8, group=9, tags=10, mode=11, between=12, n=18),
+    "tk_index_knn_probe": dict(mask=7, exclude=8, group=9, tags=10, mode=11, between=12, out=13, dist=14, n=15),
+    "tk_index_knn_probe_matrix": dict(mask=7, exclude=8, group=9, tags=10, mode=11, between=12, out=13, dist=14, n=15),
+    "tk_index_knn_group": dict(group=4, mask=5, exclude=6, tags=7, mode=8, between=9, out=10, dist=11, n=12),
+    "tk_index_knn_between": dict(between=4, mask=5, exclude=6, group=7, tags=8, mode=9, out=10, dist=11, n=12),
+}
+EXACT_ROW_BYTES = dict(mask=N, exclude=8 * NQ, group=4 * NQ, tags=8 * NQ, between=16 * VCOLS * NQ)
+
+# (the DeviceIndex call, its foreign function, the restriction it cannot do without)
+EXACT_CALLS = [
+    ("knn_brute", "tk_index_knn_brute_ex", None), ("knn_brute_dist", "tk_index_knn_brute_ex", None),
+    ("knn_brute_matrix", "tk_index_knn_brute_matrix", None), ("knn_brute_dist_matrix", "tk_index_knn_brute_matrix", None),
+    ("radius_brute", "tk_index_radius_brute", None), ("radius_count", "tk_index_radius_brute", None),
+    ("radius_probe", "tk_index_radius_probe", None), ("radius_probe_count", "tk_index_radius_probe", None),
+    ("knn_probe", "tk_index_knn_probe", None), ("knn_probe_dist", "tk_index_knn_probe", None),
+    ("knn_probe_matrix", "tk_index_knn_probe_matrix", None),
+    ("knn_group", "tk_index_knn_group", "group"), ("knn_group_dist", "tk_index_knn_group", "group"),
+    ("knn_between", "tk_index_knn_between", "between"), ("knn_between_dist", "tk_index_knn_between", "between"),
+]
+EXACT_SUBSETS = [(a, x, g, t, b) for a in (False, True) for x in (False, True) for g in (False, True)
+                 for t in (None, "any", "all") for b in (False, True)]
+
+
+def exact_call(dev, call, qn, q_pq, kw):
+    """one DeviceIndex exact call by the names of EXACT_CALLS -> what it returns"""
+    matrix = dict(matrix=True) if call.endswith("_matrix") else {}
+    stem = call[:-len("_matrix")] if matrix else call
+    if stem in ("knn_brute", "knn_brute_dist"):
+        return getattr(dev, stem)(qn, K, **matrix, **kw)
+    if stem in ("radius_brute", "radius_count"):
+        return getattr(dev, stem)(qn, RADIUS, **kw)
+    if stem in ("radius_probe", "radius_probe_count"):
+        return getattr(dev, stem)(qn, q_pq, RADIUS, NP, **kw)
+    if stem in ("knn_probe", "knn_probe_dist"):
+        return dev.knn_probe(qn, q_pq, K, NP, return_distances=stem.endswith("_dist"), **matrix, **kw)
+    kw = dict(kw)
+    first = kw.pop("group" if stem.startswith("knn_group") else "between")
+    return getattr(dev, stem.replace("_dist", ""))(qn, K, first, return_distances=stem.endswith("_dist"), **kw)
+
+
+# (the call's own argument is always given)
+EXACT_CASES = [c + s for c in EXACT_CALLS for s in EXACT_SUBSETS
+               if not (c[2] == "group" and not s[2]) and not (c[2] == "between" and not s[4])]
+
+
+@pytest.mark.parametrize("q64", [False, True])
+@pytest.mark.parametrize("call,name,required,a,x,g,t,b", EXACT_CASES)
+def test_exact_calls_hand_the_library_one_form(rec, call, name, required, a, x, g, t, b, q64):
+    """every subset of the restrictions: the foreign function, its argument order, NULL for what was not given, the
+    dtype and shape of every buffer, ids of -1 and distances of +inf"""
+    dev = bare_index(f64=q64, values=True)
+    qn, q_pq = queries(q64)
+    kw, want = restrictions(x, g, t, b)
+    if required == "group":
+        kw["group"], want["group"] = GROUP_IDS, GROUP_IDS.astype(np.int32)
+    mask = None
+    if a:
+        mask = np.zeros(N, dtype=bool)
+        mask[::3] = True
+        kw["allowed"] = mask
+    want["mask"] = None if mask is None else mask.astype(np.uint8)
+    seen = []
+
+    def on_call(fn, args):
+        if fn in EXACT_PLACES:
+            pl = EXACT_PLACES[fn]
+            assert len(args) == pl["n"]
+            seen.append({w: None if args[pl[w]] is None else C.string_at(addr(args[pl[w]]), EXACT_ROW_BYTES[w])
+                         for w in EXACT_ROW_BYTES})
+    rec.on_call = on_call
+    got = exact_call(dev, call, qn, q_pq, kw)
+
+    entry = [c for c in rec.calls if not c[0].endswith("_fetch")]
+    plain = call == "knn_brute" and not (a or x or g or t or b)
+    if plain:       # nothing asked beyond the old entry point
+        (fn, args), = entry
+        assert fn == "tk_index_knn_brute" and args[0] == HANDLE and args[2:4] == (NQ, K) and len(args) == 5
+        assert is_buffer(args[1], qn, np.float32, (NQ, D)) and is_buffer(args[4], got, np.int64, (NQ, K))
+        return
+    (fn, args), = entry
+    assert fn == name and args[0] == HANDLE and len(seen) == 1
+    pl = EXACT_PLACES[fn]
+    for w in EXACT_ROW_BYTES:
+        assert seen[0][w] == (None if want[w] is None else want[w].tobytes()), w
+        assert (args[pl[w]] is None) == (want[w] is None)
+    assert args[pl["mode"]] == (TAG_MODE[t] if t else 0) and isinstance(args[pl["mode"]], int)
+    assert is_buffer(args[1], qn, np.float32, (NQ, D))
+
+    # ---- the scalars and the queries in front, the outputs behind
+    if "radius" in call:
+        count = call.endswith("count")
+        lims_p, total_p = args[pl["n"] - 2], args[pl["n"] - 1]
+        assert lims_p._arr.dtype == np.int64 and lims_p._arr.shape == (NQ + 1,) and not lims_p._arr.any()
+        assert total_p._arr.dtype == np.int64 and total_p._arr.shape == (1,)
+        if "probe" in call:
+            assert args[2] == q_pq.ctypes.data and args[3:6] == (int(q64), NQ, NP)
+            rad_p, flags = args[6], args[13:16]
+            assert flags == ((0, 1, 0) if count else (1, 0, 1 << 26))
+        else:
+            assert args[2] == NQ
+            rad_p, flags = args[3], args[10:13]
+            assert flags == ((0, 1, 0) if count else (1, 0, 1 << 26))
+        assert rad_p._arr.dtype == np.float32 and rad_p._arr.shape == (NQ,)
+        assert np.array_equal(rad_p._arr, RADIUS.astype(np.float32))
+        if count:
+            assert got.dtype == np.int64 and got.shape == (NQ,) and not got.any()
+        else:
+            lims, ids, dist = got
+            assert lims.dtype == np.int64 and lims.shape == (NQ + 1,) and ids.shape == dist.shape == (0,)
+            assert ids.dtype == np.int64
+            assert dist.dtype == (np.float64 if q64 and "probe" in call else np.float32)
+        return
+    if "probe" in call:
+        assert args[2] == q_pq.ctypes.data and args[3:7] == (int(q64), NQ, K, NP)
+    else:
+        assert args[2:4] == (NQ, K)
+    want_dist = "_dist" in call
+    out, dist = got if want_dist else (got, None)
+    assert is_buffer(args[pl["out"]], out, np.int64, (NQ, K)) and (out == -1).all()
+    if want_dist:
+        assert dist.dtype == (np.float32 if "brute" in call or not q64 else np.float64)
+        assert args[pl["dist"]] == dist.ctypes.data and dist.shape == (NQ, K) and np.isposinf(dist).all()
+        assert dist.flags.c_contiguous
+    else:
+        assert args[pl["dist"]] is None
+
+
+def an_allow_set():
+    return AllowSet.__new__(AllowSet)
+
+
+SOME_MODE = "tags_mode: \"any\" or \"all\", got 'some'"
+NO_VALUES_SET = "between= on an index without values (set_values first)"
+NOT_A_SET = "{}: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by list position"
+GROUP_NEEDED = ("knn_group: group= needs a group id >= 0 for every query (-1, any group, is knn_brute's or "
+                "query_batch's to answer)")
+GROUP_KIND = "group: an int, or a 1-d integer array with one group id (or -1) per query"
+BAD_TAGS = dict(tags=1, tags_mode="some")
+QS = np.zeros((NQ, D), np.float32)
+
+# (the IVF call, the name it refuses an AllowSet under) and the two-fault cases every one of them shares
+IVF_EXACT = [
+    (lambda i, **kw: i.knn_brute(QS, K, **kw), "knn_brute"),
+    (lambda i, **kw: i.radius_search(QS, 1.0, **kw), "radius_search"),
+    (lambda i, **kw: i.radius_search(QS, 1.0, n_probes=NP, **kw), "radius_search"),
+    (lambda i, **kw: i.radius_count(QS, 1.0, **kw), "radius_count"),
+    (lambda i, **kw: i.radius_count(QS, 1.0, n_probes=NP, **kw), "radius_count"),
+    (lambda i, **kw: i.knn_probe(QS, K, NP, **kw), "knn_probe"),
+    (lambda i, **kw: i.knn_group(QS, K, 0, **kw), "knn_group"),
+]
+
+
+def raises(exc, text, fn, *args, **kw):
+    with pytest.raises(exc) as e:
+        fn(*args, **kw)
+    assert str(e.value) == text
+
+
+def test_exact_ivf_calls_keep_the_order_of_their_refusals(rec):
+    """two faults per call, the first in the call's order raised: an AllowSet; between= against the values; tags_mode;
+    the call's own (radius, n_probes, group); a list-sharded device index — all before the device is asked anything"""
+    ivf = host_ivf()
+    ivf._dev = bare_index()
+    ivf._dev.world = 2              # (asking for the device index raises)
+    for call, word in IVF_EXACT:
+        raises(TypeError, NOT_A_SET.format(word), call, ivf, allowed=an_allow_set(), between=(0, 1))
+        raises(ValueError, NO_VALUES_SET, call, ivf, between=(0, 1), **BAD_TAGS)
+        raises(ValueError, SOME_MODE, call, ivf, **BAD_TAGS)
+        raises(RuntimeError, IVF_SHARDED, call, ivf, exclude=np.zeros(NQ + 1, int))
+    # knn_between: the ranges are its own argument
+    valued = host_ivf("values")
+    valued._dev = ivf._dev
+    for i, between, exc, text in (
+            (ivf, None, TypeError, "knn_between: between= is required: a pair (lo, hi)"),
+            (ivf, (0, 1), ValueError, NO_VALUES_SET),
+            (valued, (None, None), ValueError, "knn_between: query 0 bounds no column (an unrestricted query is "
+                                               "knn_brute's or query_batch's to answer)"),
+            (valued, (0, 1), ValueError, SOME_MODE)):
+        raises(TypeError, NOT_A_SET.format("knn_between"), i.knn_between, QS, K, between, allowed=an_allow_set())
+        raises(exc, text, i.knn_between, QS, K, between, group=0.5, **BAD_TAGS)
+    raises(TypeError, GROUP_KIND, valued.knn_between, QS, K, (0, 1), group=0.5)
+    raises(RuntimeError, IVF_SHARDED, valued.knn_between, QS, K, (0, 1), group=np.zeros(NQ, int))
+    # the radius calls: the radii, then n_probes, between tags_mode and the device index
+    for call in (ivf.radius_search, ivf.radius_count):
+        raises(ValueError, SOME_MODE, call, QS, np.nan, **BAD_TAGS)
+        raises(ValueError, "radius: query 0 has a NaN radius", call, QS, np.nan, n_probes=0)
+        raises(ValueError, "n_probes: at least 1, got 0", call, QS, 1.0, n_probes=0)
+    # knn_probe: k in front of everything, n_probes behind tags_mode
+    raises(ValueError, "knn_probe: k in [1, 1024], got 0", ivf.knn_probe, QS, 0, NP, allowed=an_allow_set())
+    raises(ValueError, SOME_MODE, ivf.knn_probe, QS, K, 0, **BAD_TAGS)
+    raises(ValueError, "n_probes: at least 1, got 0", ivf.knn_probe, QS, K, 0)
+    # knn_group: its group ids behind tags_mode, in front of the device index
+    raises(ValueError, SOME_MODE, ivf.knn_group, QS, K, -1, **BAD_TAGS)
+    raises(AssertionError, GROUP_NEEDED, ivf.knn_group, QS, K, -1)
+    raises(TypeError, GROUP_KIND, ivf.knn_group, QS, K, 0.5)
+    assert rec.calls == []

@@ -39,7 +39,7 @@ def _forms(usage):
 
 
 def test_no_kernel_of_radius_probe_hip_uses_scratch_or_spills_vector_registers(usage):
-    for kernel in ("rp_words_kernel", "rp_rank_kernel", "rp_decode64_kernel", "radius_probe_count_kernel",
+    for kernel in ("probe_len_kernel", "rp_rank_kernel", "rp_decode64_kernel", "radius_probe_count_kernel",
                    "radius_probe_fill_kernel"):
         assert any(kernel in n for n in usage), (kernel, sorted(usage))
     for name, u in usage.items():

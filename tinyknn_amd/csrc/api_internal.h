@@ -1,6 +1,7 @@
 // api_internal.h — what the translation units of the C ABI share (api.hip: host-pointer entry points and
 // resident code arrays; api_index.hip: the resident index and its pipeline; api_shard.hip: the list-sharded
-// entry points; api_build.hip: device build, raw queries, brute force, FlatTop).  Not part of the ABI.
+// entry points; api_build.hip: device build, raw queries, FlatTop; api_exact.hip: brute force, the radius call over
+// all rows, the exact calls' restriction builder).  Not part of the ABI.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -271,20 +272,22 @@ struct tk_index {
     DevBuf rd_radius, rd_count, rd_off, rd_keys, rd_alt, rd_dist, rd_tmp;
     int64_t rd_total = -1;
     bool rd_ids_alt = false;
-    // tk_index_radius_probe (radius_probe.hip): the call's probes (nq, kc) int64, bitmap words per (query, rank) int32
-    // and their exclusive prefix sum int64 (+ the scan's work memory), the hit bitmap; float64 vectors: the row ids
+    // tk_index_radius_probe and tk_index_knn_probe (probe_job.h: probe_lengths): the call's probes (nq, kc) int64, the
+    // length per (query, rank) — bitmap words or keys — and their exclusive prefix sum, int64 (nq * kc + 1) each, the
+    // scans' work memory.  One set: the index lock serialises the two calls and no held result lives here.
+    DevBuf pl_probes, pl_len, pl_off, pl_scan;
+    // tk_index_radius_probe (radius_probe.hip): the hit bitmap; float64 vectors: the row ids
     // beside the distance keys; the decoded ids and distances.  rp_total >= 0: a result is held for
     // tk_index_radius_probe_fetch (rp_f64: its distances are float64).  The radii, counters, offsets, keys and the
     // sort's buffers are the rd_* ones above: one radius result of either kind is held at a time.
-    DevBuf rp_probes, rp_words, rp_woff, rp_scan, rp_bitmap, rp_rows, rp_ids, rp_dist;
+    DevBuf rp_bitmap, rp_rows, rp_ids, rp_dist;
     int64_t rp_total = -1;
     bool rp_f64 = false;
-    // tk_index_knn_probe (probe_exact.hip): the call's probes, the keys per (query, rank) and their exclusive prefix sum
-    // (+ the scans' work memory), per list 5 ints (pairs, cursor, first pair, tiles, first tile), a chunk's pairs by
+    // tk_index_knn_probe (probe_exact.hip): per list 5 ints (pairs, cursor, first pair, tiles, first tile), a chunk's pairs by
     // list, its tile table and its distance keys, the call's ids and distances.  opt_probe_budget (TK_OPT_PROBE_BUDGET):
     // bytes of distance keys a chunk may hold, 0: workspace_bytes().  opt_probe_wide (TK_OPT_PROBE_WIDE): 1 = the wide
     // distance kernel at any d
-    DevBuf pe_probes, pe_seglen, pe_segoff, pe_scan, pe_lists, pe_pairs, pe_tiles, pe_keys, pe_out;
+    DevBuf pe_lists, pe_pairs, pe_tiles, pe_keys, pe_out;
     int opt_probe_budget = 0, opt_probe_wide = 0;
     // tk_index_knn_probe_matrix (probe_matrix.hip): the call's queries as two half planes (nq, dpad) each, and per query
     // its float32 self-dot and the scale 2^-e
@@ -548,10 +551,56 @@ void launch_coarse_scan(tk_index *ix, Work &w, int64_t nq, const Plan &p, hipStr
 typedef std::function<int(int64_t o, int64_t m, int kc, const int64_t *probes_dev, const float *dist_dev)> TkProbeSink;
 int coarse_top_chunks(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
                       bool want_dist, const TkProbeSink &sink);
-// the restriction of a restricted exact call from the caller's host arrays (see there); any = false: none given
-int brute_restrict(tk_index *ix, int64_t nq, const uint8_t *allowed_mask, const int64_t *exclude,
-                   const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between,
-                   TkBruteRestrict &r, bool &any);
+// ---- api_exact.hip: what the exact calls (knn_brute_ex / _matrix, radius_brute, radius_probe, knn_probe / _matrix,
+// knn_group, knn_between) share on the host
+// The restrictions of one exact call as its entry point got them: host arrays, NULL for what was not given
+struct TkHostRestrict {
+    const uint8_t *allowed_mask;    // (N) a byte per row
+    const int64_t *exclude;         // (nq)
+    const int32_t *group;           // (nq)
+    const uint64_t *tags;           // (nq)
+    int tag_mode;
+    const int64_t *between;         // (nq, cols, 2)
+    bool any() const { return allowed_mask || exclude || group || tags || between; }
+};
+// a byte per row -> a bit per row, 32 rows a word
+static inline std::vector<uint32_t> pack_row_mask(const uint8_t *mask, int64_t N)
+{
+    std::vector<uint32_t> bits((size_t)(N + 31) / 32, 0u);
+    for (int64_t j = 0; j < N; j++)             // (no branch: a random mask would mispredict every other row)
+        bits[(size_t)(j >> 5)] |= (uint32_t)(mask[j] != 0) << (j & 31);
+    return bits;
+}
+// A host array of the call in its workspace buffer (NULL stays NULL)
+template <typename T>
+static int host_upload(DevBuf &b, const T *host, size_t n, const T *&dev)
+{
+    dev = nullptr;
+    if (!host) return TK_OK;
+    TRY(b.ensure((n > 0 ? n : 1) * sizeof(T)));
+    HIPCHECK(hipMemcpy(b.p, host, n * sizeof(T), hipMemcpyHostToDevice));
+    dev = b.as<T>();
+    return TK_OK;
+}
+// The restriction's device form from the host arrays, in phases, so that a call with checks of its own (knn_group,
+// knn_between) makes them where it always did.  mode: tag_mode is 0 or 1.  tables: the index has a value for every row
+// of what group, tags and between name, asked in this order (the by-row arrays only: no list-order table is made or
+// read).  ranges: exclude's entries lie in [-1, N).  upload: the per-query arrays in the br_* workspace buffers, the
+// by-row arrays of the index, cols; any = false (nothing given) or nq == 0: r stays empty, nothing is uploaded.
+int restrict_mode(const TkHostRestrict &h);
+int restrict_tables(const tk_index *ix, const TkHostRestrict &h);
+int restrict_ranges(const tk_index *ix, int64_t nq, const TkHostRestrict &h);
+int restrict_upload(tk_index *ix, int64_t nq, const TkHostRestrict &h, TkBruteRestrict &r, bool &any);
+// the four in that order: what the brute, radius and probe calls ask
+int brute_restrict(tk_index *ix, int64_t nq, const TkHostRestrict &h, TkBruteRestrict &r, bool &any);
+// The tail of a radius call (radius_brute, radius_probe) behind its count pass.  lims: the counts (nq ints, device) as
+// int64 lims and their total; fill = false where the call ends here — count_only, or no hit (what the call then holds
+// is its own to set) — else the limit is checked (TK_ERR_ARG naming the total) and the lims are in rd_off, rd_keys /
+// rd_alt hold `total` keys each.  agree: the fill pass raised no flag.  sort: radius.hip's segmented sort, in -> out.
+int radius_lims(tk_index *ix, const int *count, int64_t nq, int count_only, int64_t max_results, int64_t *out_lims,
+                int64_t *out_total, bool &fill);
+int radius_passes_agree(const int *err);
+int radius_sort(tk_index *ix, const unsigned long long *in, unsigned long long *out, int64_t total, int64_t nq);
 // the replay over the coded centres of queries [0, nq) (one slot every query shares, positions as labels)
 TkReplayJob centre_replay_job(const tk_index *ix, Work &w, int64_t nq, const Plan &p);
 // dist (or NULL): the probes' exact float32 distances beside probes_out (FlatTop; the IVF coarse stage asks for none)

@@ -113,28 +113,6 @@ static int group_spans(tk_index *ix, const int32_t *group_dev, int64_t n)
     return TK_OK;
 }
 
-template <typename T, typename TY>
-static void launch_group_exact(const tk_index *ix, const float *q, int64_t nq, int k, const TkBruteRestrict &r,
-                               int64_t *out, void *out_d)
-{
-    const size_t lds = gx_lds_bytes(ix->d, sizeof(typename GxKey<T>::type), sizeof(T));
-    hipLaunchKernelGGL((group_exact_kernel<T, TY>), dim3((unsigned)nq), dim3(GX_THREADS), lds, 0, q, ix->d,
-                       ix->data.as<TY>(), ix->groups.span_rows.as<int32_t>(), ix->gx_begin.as<int32_t>(),
-                       ix->gx_len.as<int32_t>(), ix->stored_bits.as<uint32_t>(), r, k, out, (T *)out_d);
-}
-
-// A host array of the call in its workspace buffer (NULL stays NULL)
-template <typename T>
-static int gx_upload(DevBuf &b, const T *host, size_t n, const T *&dev)
-{
-    dev = nullptr;
-    if (!host) return TK_OK;
-    TRY(b.ensure((n > 0 ? n : 1) * sizeof(T)));
-    HIPCHECK(hipMemcpy(b.p, host, n * sizeof(T), hipMemcpyHostToDevice));
-    dev = b.as<T>();
-    return TK_OK;
-}
-
 // ---- C ABI ----
 
 extern "C" int tk_index_knn_group(tk_index *ix, const float *q, int64_t nq, int k, const int32_t *group,
@@ -142,59 +120,33 @@ extern "C" int tk_index_knn_group(tk_index *ix, const float *q, int64_t nq, int 
                                   int tag_mode, const int64_t *between, int64_t *out_ids, void *out_dist)
 {
     IXLOCK(ix);
-    ARGCHECK(ix && ix->have_data, "set_data first");
-    ARGCHECK(!ix->sharded, "list-sharded index: knn_group is not supported");
-    ARGCHECK(nq >= 0 && (nq == 0 || (q && out_ids)), "buffers");
-    ARGCHECK(nq == 0 || group, "group: one group id per query is required");
-    ARGCHECK(k >= 1 && k <= 1024 && k <= ix->N, "1 <= k <= min(1024, N)");
-    ARGCHECK(ix->N < (1ll << 31), "N < 2^31");
-    ARGCHECK(ix->d <= 4096, "d <= 4096");
-    ARGCHECK(tag_mode == 0 || tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
+    TRY(span_call_checks(ix, "knn_group", q, nq, k, out_ids, group, "group: one group id per query is required"));
+    const TkHostRestrict h{allowed_mask, exclude, group, tags, tag_mode, between};
+    TRY(restrict_mode(h));
     for (int64_t i = 0; i < nq; i++) ARGCHECK(group[i] >= 0, "group: every entry must be a group id >= 0");
-    TRY(row_table_covers(ix, ix->groups));
-    if (tags) TRY(row_table_covers(ix, ix->tags));
-    if (between) TRY(row_table_covers(ix, ix->values));
-    if (exclude)
-        for (int64_t i = 0; i < nq; i++) ARGCHECK(exclude[i] >= -1 && exclude[i] < ix->N, "exclude: entries in [-1, N)");
+    TRY(row_table_covers(ix, ix->groups));          // (also where nq == 0 came without the array)
+    TRY(restrict_tables(ix, h));
+    TRY(restrict_ranges(ix, nq, h));
     if (nq == 0) return TK_OK;
     TRY(flush_pending(ix));
     TRY(group_rows_ensure(ix));
     TRY(stored_bits_ensure(ix, "tk_index_knn_group"));
-    TkBruteRestrict r{};
-    r.n_rows = ix->N;
-    r.tag_mode = tag_mode;
-    if (allowed_mask) {
-        std::vector<uint32_t> bits((size_t)(ix->N + 31) / 32, 0u);
-        for (int64_t j = 0; j < ix->N; j++) bits[(size_t)(j >> 5)] |= (uint32_t)(allowed_mask[j] != 0) << (j & 31);
-        TRY(gx_upload(ix->br_mask, bits.data(), bits.size(), r.allowed));
-    }
-    const int32_t *group_dev = nullptr;
-    TRY(gx_upload(ix->br_group, group, (size_t)nq, group_dev));
-    TRY(gx_upload(ix->br_exclude, exclude, (size_t)nq, r.exclude));
-    TRY(gx_upload(ix->br_tags, tags, (size_t)nq, r.tags));
-    if (tags) r.row_tags = ix->tags.by_row.as<uint64_t>();
-    if (between) {
-        r.cols = value_columns(ix);
-        r.row_keys = ix->values.by_row.as<int64_t>();
-        TRY(gx_upload(ix->br_ranges, between, (size_t)nq * 2 * r.cols, r.ranges));
-    }
-    const size_t dsz = ix->data_dtype == TK_DATA_F64 ? 8 : 4;
-    TRY(ix->br_q.ensure((size_t)nq * ix->d * 4));
-    TRY(ix->br_out.ensure((size_t)nq * k * 8));
-    if (out_dist) TRY(ix->br_dist.ensure((size_t)nq * k * dsz));
-    HIPCHECK(hipMemcpy(ix->br_q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
-    TRY(group_spans(ix, group_dev, nq));
-    void *dist = out_dist ? ix->br_dist.p : nullptr;
-    const float *X = ix->br_q.as<float>();
-    int64_t *out = ix->br_out.as<int64_t>();
-    if (ix->data_dtype == TK_DATA_F64) launch_group_exact<double, double>(ix, X, nq, k, r, out, dist);
-    else if (ix->data_dtype == TK_DATA_F16) launch_group_exact<float, _Float16>(ix, X, nq, k, r, out, dist);
-    else launch_group_exact<float, float>(ix, X, nq, k, r, out, dist);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipDeviceSynchronize());
-    HIPCHECK(hipMemcpy(out_ids, ix->br_out.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-    if (out_dist) HIPCHECK(hipMemcpy(out_dist, dist, (size_t)nq * k * dsz, hipMemcpyDeviceToHost));
-    return TK_OK;
+    TkBruteRestrict r;
+    bool any;
+    TRY(restrict_upload(ix, nq, h, r, any));
+    const int32_t *group_dev = r.group;     // the span IS the group: the walk does not test it again
+    r.group = r.row_groups = nullptr;
+    return span_call(ix, q, nq, k, out_ids, out_dist,
+                     [&](auto t, auto ty, size_t lds, const float *X, int64_t *out, void *dist) -> int {
+                         typedef decltype(t) T;
+                         typedef decltype(ty) TY;
+                         TRY(group_spans(ix, group_dev, nq));
+                         hipLaunchKernelGGL((group_exact_kernel<T, TY>), dim3((unsigned)nq), dim3(GX_THREADS), lds, 0, X,
+                                            ix->d, ix->data.as<TY>(), ix->groups.span_rows.as<int32_t>(),
+                                            ix->gx_begin.as<int32_t>(), ix->gx_len.as<int32_t>(),
+                                            ix->stored_bits.as<uint32_t>(), r, k, out, (T *)dist);
+                         return TK_OK;
+                     });
 }
 
 extern "C" int tk_index_group_sizes(tk_index *ix, const int32_t *group, int64_t n, int64_t *out)
@@ -208,7 +160,7 @@ extern "C" int tk_index_group_sizes(tk_index *ix, const int32_t *group, int64_t 
     TRY(flush_pending(ix));
     TRY(group_rows_ensure(ix));
     const int32_t *group_dev = nullptr;
-    TRY(gx_upload(ix->br_group, group, (size_t)n, group_dev));
+    TRY(host_upload(ix->br_group, group, (size_t)n, group_dev));
     TRY(group_spans(ix, group_dev, n));
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
@@ -224,9 +176,5 @@ extern "C" int tk_index_group_rows(tk_index *ix, int64_t *info4)
     ARGCHECK(ix && info4, "null index / buffer");
     const TkRowTable &t = ix->groups;
     const bool have = t.span_state.current(t.set_gen) && t.n == ix->N;
-    info4[0] = have ? 1 : 0;
-    info4[1] = have ? ix->N * 4 + t.span_groups * 4 + (t.span_groups + 1) * 4 : 0;
-    info4[2] = t.span_state.builds;
-    info4[3] = have ? t.span_groups : 0;
-    return TK_OK;
+    return span_rows_info(t, have, ix->N * 4 + t.span_groups * 4 + (t.span_groups + 1) * 4, info4);
 }

@@ -6,8 +6,8 @@
 // radius_probe.hip is query-major: a workgroup per (query, rank), a lane per row, every lane fetching its own row — a
 // list probed by 92 queries of a batch is read 92 times.  Here the distances are made LIST-major and selected
 // QUERY-major:
-//   segments  pe_seg_kernel: per (query, rank) of the whole call the keys its list needs — list_n, 0 at a rank whose
-//             list an earlier rank names or that names none.  tk_scan_exclusive64: where each (query, rank)'s segment of
+//   segments  probe_len_kernel<1> (probe_job.h: the prologue radius_probe shares): per (query, rank) of the whole call
+//             the keys its list needs — list_n, 0 at a rank whose list an earlier rank names or that names none.  tk_scan_exclusive64: where each (query, rank)'s segment of
 //             distance keys begins.  The offsets cross to the host once: the call is cut into chunks of whole queries
 //             whose key buffers fit the budget (workspace_bytes(); TK_OPT_PROBE_BUDGET for tests).
 //   pairs     per chunk: pe_count_kernel counts the pairs (a (query, rank) with keys) per list with atomics,
@@ -40,31 +40,6 @@
 #include "sqdist_row.h"
 #include "span_exact.h"
 
-// the list a probe names: -1 (an unfilled coarse heap) is the last list; -1 for what names none (radius_probe.hip)
-__device__ __forceinline__ int32_t pe_list(int64_t p, int64_t n_lists)
-{
-    if (p < 0) p += n_lists;
-    return (p >= 0 && p < n_lists) ? (int32_t)p : -1;
-}
-
-__global__ __launch_bounds__(256) void pe_seg_kernel(const int64_t *__restrict__ probes, int64_t n, int kc,
-                                                     int64_t n_lists, const int64_t *__restrict__ list_n,
-                                                     long long *__restrict__ seglen)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n) return;
-    if (i == n) {               // (the scan's last entry: the total)
-        seglen[i] = 0;
-        return;
-    }
-    const int rank = (int)(i % kc);
-    const int64_t *row = probes + (i - rank);
-    const int32_t L = pe_list(row[rank], n_lists);
-    bool walk = L >= 0;
-    for (int t = 0; walk && t < rank; t++) walk = pe_list(row[t], n_lists) != L;
-    seglen[i] = walk ? list_n[L] : 0;
-}
-
 __global__ __launch_bounds__(256) void pe_clear_kernel(int *__restrict__ a, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -76,7 +51,7 @@ __global__ __launch_bounds__(256) void pe_count_kernel(const PeJob j)
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= j.n_pairs) return;
     const int64_t p = j.pair0 + i;
-    if (j.seglen[p] > 0) atomicAdd(&j.count[pe_list(j.probes[p], j.n_lists)], 1);
+    if (j.seglen[p] > 0) atomicAdd(&j.count[probe_list(j.probes[p], j.n_lists)], 1);
 }
 
 __global__ __launch_bounds__(256) void pe_ntiles_kernel(const PeJob j)
@@ -92,7 +67,7 @@ __global__ __launch_bounds__(256) void pe_fill_kernel(const PeJob j)
     if (i >= j.n_pairs) return;
     const int64_t p = j.pair0 + i;
     if (j.seglen[p] <= 0) return;
-    const int32_t L = pe_list(j.probes[p], j.n_lists);
+    const int32_t L = probe_list(j.probes[p], j.n_lists);
     const int slot = atomicAdd(&j.cursor[L], 1);
     if (slot < j.count[L]) j.pair_of[j.list_off[L] + slot] = (int)p;           // (always: the count pass saw the same)
 }
@@ -337,7 +312,7 @@ __global__ __launch_bounds__(GX_THREADS) void probe_select_kernel(const PeJob j,
     __shared__ int s_count;
     const int tid = threadIdx.x;
     const int64_t qi = q0 + blockIdx.x;
-    for (int t = tid; t < j.kc; t += GX_THREADS) pl[t] = pe_list(j.probes[qi * j.kc + t], j.n_lists);
+    for (int t = tid; t < j.kc; t += GX_THREADS) pl[t] = probe_list(j.probes[qi * j.kc + t], j.n_lists);
     if (tid == 0) s_count = 0;
     // the query's own attributes, once
     const int32_t q_ex = r.exclude ? (int32_t)r.exclude[qi] : -1;
@@ -497,8 +472,8 @@ static int pe_scan(tk_index *ix, const int *in, int *out, int64_t n)
 {
     size_t bytes = 0;
     (void)tk_scan_exclusive(nullptr, &bytes, in, out, n, nullptr);
-    TRY(ix->pe_scan.ensure(bytes > 0 ? bytes : 1));
-    if (tk_scan_exclusive(ix->pe_scan.p, &bytes, in, out, n, nullptr))
+    TRY(ix->pl_scan.ensure(bytes > 0 ? bytes : 1));
+    if (tk_scan_exclusive(ix->pl_scan.p, &bytes, in, out, n, nullptr))
         return fail(TK_ERR_HIP, "tk_scan_exclusive failed");
     return TK_OK;
 }
@@ -518,8 +493,7 @@ extern "C" int tk_index_knn_probe_tile(tk_index *ix, int *qt, int *rb)
 
 // the body of tk_index_knn_probe and tk_index_knn_probe_matrix: matrix picks the distance pass (probe_matrix.hip)
 static int pe_knn_probe(tk_index *ix, bool matrix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
-                        int n_probes, const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
-                        const uint64_t *tags, int tag_mode, const int64_t *between, int64_t *out_ids, void *out_dist)
+                        int n_probes, const TkHostRestrict &h, int64_t *out_ids, void *out_dist)
 {
     IXLOCK(ix);
     ARGCHECK(ix && ix->have_data && ix->have_lists && ix->have_pq && ix->have_centers,
@@ -540,42 +514,23 @@ static int pe_knn_probe(tk_index *ix, bool matrix, const float *q, const void *q
     TRY(radius_probe_twins(ix, &twin_list, &twin_w));
     TkBruteRestrict r;
     bool any;
-    TRY(brute_restrict(ix, nq, allowed_mask, exclude, group, tags, tag_mode, between, r, any));
+    TRY(brute_restrict(ix, nq, h, r, any));
     if (nq == 0) return TK_OK;
     TRY(flush_pending(ix));
     const bool f64 = ix->data_dtype == TK_DATA_F64;
     const size_t ksz = f64 ? 8 : 4;
-    const int kc = (int)(n_probes < ix->n_lists ? n_probes : ix->n_lists);
+    int kc;
+    TRY(probe_pairs(ix, nq, n_probes, kc));
     const int64_t pairs = nq * kc;
-    ARGCHECK(pairs < (1ll << 31), "nq * min(n_probes, n_lists) < 2^31");
     ARGCHECK(pe_select_lds(kc, ksz) <= 64 * 1024, "n_probes: the probed lists of a query do not fit 64 KiB of LDS");
-    TRY(ix->pe_probes.ensure((size_t)pairs * 8));
-    TRY(ix->pe_seglen.ensure((size_t)(pairs + 1) * 8));
-    TRY(ix->pe_segoff.ensure((size_t)(pairs + 1) * 8));
     TRY(ix->pe_lists.ensure((size_t)(ix->n_lists + 1) * 5 * 4));
     TRY(ix->pe_out.ensure((size_t)nq * k * (8 + ksz)));
-    TRY(ix->br_q.ensure((size_t)nq * ix->d * 4));
-    // the coarse stage, chunk by chunk; its probes stay on the device
-    TRY(coarse_top_chunks(ix, q, q_pq, q_pq_is_f64, nq, n_probes, false,
-                          [&](int64_t o, int64_t m, int kc_, const int64_t *probes, const float *) -> int {
-                              if (kc_ != kc) return fail(TK_ERR_HIP, "knn_probe: the coarse stage's row width");
-                              HIPCHECK(hipMemcpy(ix->pe_probes.as<int64_t>() + o * kc, probes, (size_t)m * kc * 8,
-                                                 hipMemcpyDeviceToDevice));
-                              return TK_OK;
-                          }));
-    HIPCHECK(hipMemcpy(ix->br_q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
+    PeJob j{};
+    // the coarse stage; the keys of every (query, rank) and where they begin
+    TRY(probe_lengths<1>(ix, "knn_probe", q, q_pq, q_pq_is_f64, nq, n_probes, kc, twin_list, twin_w, j));
     PmQueries mx{};
     if (matrix) TRY(pm_prepare(ix, nq, mx));
-    // the keys of every (query, rank) and where they begin
-    long long *seglen = ix->pe_seglen.as<long long>(), *segoff = ix->pe_segoff.as<long long>();
-    hipLaunchKernelGGL(pe_seg_kernel, dim3((unsigned)((pairs + 256) / 256)), dim3(256), 0, 0,
-                       ix->pe_probes.as<int64_t>(), pairs, kc, ix->n_lists, ix->list_n.as<int64_t>(), seglen);
-    size_t sbytes = 0;
-    (void)tk_scan_exclusive64(nullptr, &sbytes, seglen, segoff, pairs + 1, nullptr);
-    TRY(ix->pe_scan.ensure(sbytes > 0 ? sbytes : 1));
-    if (tk_scan_exclusive64(ix->pe_scan.p, &sbytes, seglen, segoff, pairs + 1, nullptr))
-        return fail(TK_ERR_HIP, "tk_scan_exclusive64 failed");
-    HIPCHECK(hipGetLastError());
+    const long long *segoff = ix->pl_off.as<long long>();
     std::vector<long long> off((size_t)pairs + 1);
     HIPCHECK(hipMemcpy(off.data(), segoff, (size_t)(pairs + 1) * 8, hipMemcpyDeviceToHost));      // (synchronises)
     // chunks of whole queries whose keys fit the budget
@@ -589,15 +544,7 @@ static int pe_knn_probe(tk_index *ix, bool matrix, const float *q, const void *q
             return fail(TK_ERR_WORKSPACE, b);
         }
     }
-    PeJob j{};
-    j.q = ix->br_q.as<float>();
-    j.rows = ix->data.p;
-    j.probes = ix->pe_probes.as<int64_t>();
-    j.ids = ix->ids.as<int64_t>();
-    j.ids_off = ix->ids_off.as<int64_t>();
-    j.list_n = ix->list_n.as<int64_t>();
-    j.twin_list = twin_list;
-    j.seglen = seglen;
+    j.seglen = ix->pl_len.as<long long>();
     j.segoff = segoff;
     const int64_t nl1 = ix->n_lists + 1;
     j.count = ix->pe_lists.as<int>();
@@ -605,11 +552,6 @@ static int pe_knn_probe(tk_index *ix, bool matrix, const float *q, const void *q
     j.list_off = j.cursor + nl1;
     j.ntiles = j.list_off + nl1;
     j.tile_off = j.ntiles + nl1;
-    j.n_lists = ix->n_lists;
-    j.N = ix->N;
-    j.d = ix->d;
-    j.kc = kc;
-    j.twin_w = twin_w;
     j.t = tile;
     int64_t *out = ix->pe_out.as<int64_t>();
     void *out_d = (void *)(out + nq * k);
@@ -654,8 +596,8 @@ extern "C" int tk_index_knn_probe(tk_index *ix, const float *q, const void *q_pq
                                   const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between,
                                   int64_t *out_ids, void *out_dist)
 {
-    return pe_knn_probe(ix, false, q, q_pq, q_pq_is_f64, nq, k, n_probes, allowed_mask, exclude, group, tags, tag_mode,
-                        between, out_ids, out_dist);
+    return pe_knn_probe(ix, false, q, q_pq, q_pq_is_f64, nq, k, n_probes,
+                        {allowed_mask, exclude, group, tags, tag_mode, between}, out_ids, out_dist);
 }
 
 extern "C" int tk_index_knn_probe_matrix(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq,
@@ -663,6 +605,6 @@ extern "C" int tk_index_knn_probe_matrix(tk_index *ix, const float *q, const voi
                                          const int32_t *group, const uint64_t *tags, int tag_mode,
                                          const int64_t *between, int64_t *out_ids, void *out_dist)
 {
-    return pe_knn_probe(ix, true, q, q_pq, q_pq_is_f64, nq, k, n_probes, allowed_mask, exclude, group, tags, tag_mode,
-                        between, out_ids, out_dist);
+    return pe_knn_probe(ix, true, q, q_pq, q_pq_is_f64, nq, k, n_probes,
+                        {allowed_mask, exclude, group, tags, tag_mode, between}, out_ids, out_dist);
 }

@@ -1,7 +1,101 @@
-// probe_job.h — what the two distance passes of knn_probe share (probe_exact.hip: the exact pass, the tables, the
-// selection and the host driver; probe_matrix.hip: the f16 matrix-core pass of matrix=True).
+// probe_job.h — what the calls over the probed lists share: radius_probe.hip and knn_probe's two
+// distance passes (probe_exact.hip: the exact pass, the tables, the selection and the host driver; probe_matrix.hip:
+// the f16 matrix-core pass of matrix=True, §3.22).
 #pragma once
 #include "api_internal.h"
+
+// What a job over the probed lists of a call's queries reads, whichever call it is
+struct ProbeJob {
+    const float *q;                 // (nq, d) prepared queries of the whole call
+    const void *rows;               // the vectors, TY
+    const int64_t *probes;          // (nq, kc)
+    const int64_t *ids, *ids_off, *list_n;
+    const int32_t *twin_list;       // twins.hip, twin_w > 0
+    int64_t n_lists, N;
+    int d, kc, twin_w;
+};
+
+// the list a probe names: -1 (an unfilled coarse heap) is the last list; -1 for what names none
+__device__ __forceinline__ int32_t probe_list(int64_t p, int64_t n_lists)
+{
+    if (p < 0) p += n_lists;
+    return (p >= 0 && p < n_lists) ? (int32_t)p : -1;
+}
+
+// Per (query, rank) of the whole call what its list needs, in units of UNIT rows — 1: a distance key a row (knn_probe),
+// 64: a bitmap word per 64 rows (radius_probe) — and 0 at a rank whose list an earlier rank names or that names none
+template <int UNIT>
+__global__ __launch_bounds__(256) void probe_len_kernel(const int64_t *__restrict__ probes, int64_t n, int kc,
+                                                        int64_t n_lists, const int64_t *__restrict__ list_n,
+                                                        long long *__restrict__ len)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    if (i == n) {               // (the scan's last entry: the total)
+        len[i] = 0;
+        return;
+    }
+    const int rank = (int)(i % kc);
+    const int64_t *row = probes + (i - rank);
+    const int32_t L = probe_list(row[rank], n_lists);
+    bool walk = L >= 0;
+    for (int t = 0; walk && t < rank; t++) walk = probe_list(row[t], n_lists) != L;
+    len[i] = walk ? (list_n[L] + (UNIT - 1)) / UNIT : 0;
+}
+
+// kc = min(n_probes, n_lists) and the refusal of a call with 2^31 (query, rank)s or more
+static inline int probe_pairs(const tk_index *ix, int64_t nq, int n_probes, int &kc)
+{
+    kc = (int)(n_probes < ix->n_lists ? n_probes : ix->n_lists);
+    ARGCHECK(nq * kc < (1ll << 31), "nq * min(n_probes, n_lists) < 2^31");
+    return TK_OK;
+}
+
+// The prologue of a call over the probed lists, behind probe_pairs: the index's coarse stage for n_probes, chunk by
+// chunk, its probes kept on the device (pl_probes); the queries in br_q; the lengths (probe_len_kernel<UNIT>, pl_len)
+// and their exclusive prefix sum (pl_off), nq * kc + 1 entries each, still in flight when it returns; the fields of j
+// every such job has.  call: named where the coarse stage's rows are not kc wide.
+template <int UNIT>
+static int probe_lengths(tk_index *ix, const char *call, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq,
+                         int n_probes, int kc, const int32_t *twin_list, int twin_w, ProbeJob &j)
+{
+    const int64_t pairs = nq * kc;
+    TRY(ix->pl_probes.ensure((size_t)pairs * 8));
+    TRY(ix->pl_len.ensure((size_t)(pairs + 1) * 8));
+    TRY(ix->pl_off.ensure((size_t)(pairs + 1) * 8));
+    TRY(ix->br_q.ensure((size_t)nq * ix->d * 4));
+    TRY(coarse_top_chunks(ix, q, q_pq, q_pq_is_f64, nq, n_probes, false,
+                          [&](int64_t o, int64_t m, int kc_, const int64_t *probes, const float *) -> int {
+                              if (kc_ != kc)
+                                  return fail(TK_ERR_HIP, std::string(call) + ": the coarse stage's row width");
+                              HIPCHECK(hipMemcpy(ix->pl_probes.as<int64_t>() + o * kc, probes, (size_t)m * kc * 8,
+                                                 hipMemcpyDeviceToDevice));
+                              return TK_OK;
+                          }));
+    HIPCHECK(hipMemcpy(ix->br_q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
+    long long *len = ix->pl_len.as<long long>(), *off = ix->pl_off.as<long long>();
+    hipLaunchKernelGGL(probe_len_kernel<UNIT>, dim3((unsigned)((pairs + 256) / 256)), dim3(256), 0, 0,
+                       ix->pl_probes.as<int64_t>(), pairs, kc, ix->n_lists, ix->list_n.as<int64_t>(), len);
+    size_t sbytes = 0;
+    (void)tk_scan_exclusive64(nullptr, &sbytes, len, off, pairs + 1, nullptr);
+    TRY(ix->pl_scan.ensure(sbytes > 0 ? sbytes : 1));
+    if (tk_scan_exclusive64(ix->pl_scan.p, &sbytes, len, off, pairs + 1, nullptr))
+        return fail(TK_ERR_HIP, "tk_scan_exclusive64 failed");
+    HIPCHECK(hipGetLastError());
+    j.q = ix->br_q.as<float>();
+    j.rows = ix->data.p;
+    j.probes = ix->pl_probes.as<int64_t>();
+    j.ids = ix->ids.as<int64_t>();
+    j.ids_off = ix->ids_off.as<int64_t>();
+    j.list_n = ix->list_n.as<int64_t>();
+    j.twin_list = twin_list;
+    j.n_lists = ix->n_lists;
+    j.N = ix->N;
+    j.d = ix->d;
+    j.kc = kc;
+    j.twin_w = twin_w;
+    return TK_OK;
+}
 
 #define PE_THREADS 256
 #define PE_LDS_LIMIT (64 * 1024)
@@ -15,12 +109,7 @@ struct PeTile {
     int DS;                 // 0: probe_dist_kernel; else probe_dist_wide_kernel and the elements of its slab
 };
 
-struct PeJob {
-    const float *q;                 // (nq, d) prepared queries of the whole call
-    const void *rows;               // the vectors, TY
-    const int64_t *probes;          // (nq, kc)
-    const int64_t *ids, *ids_off, *list_n;
-    const int32_t *twin_list;       // twins.hip, twin_w > 0
+struct PeJob : ProbeJob {
     const long long *seglen, *segoff;   // (nq * kc + 1): keys of the (query, rank), and where they begin in the call
     long long seg_base;             // segoff of the chunk's first (query, rank): its key buffer begins there
     int64_t pair0, n_pairs;         // the chunk's (query, rank)s: [pair0, pair0 + n_pairs)
@@ -28,8 +117,6 @@ struct PeJob {
     int *pair_of;                   // the chunk's pairs by list: the (query, rank) index of each
     int4 *tiles;                    // (list, first pair, count, -)
     void *keys;                     // GxKey<T>::type per candidate position
-    int64_t n_lists, N;
-    int d, kc, twin_w;
     PeTile t;
 };
 

@@ -20,8 +20,9 @@
 //               sqdist_row<T, TY>(row, query) <= radius[i]: the rescoring's distance, float32 on float32 and half
 //               stores, float64 on float64 vectors (the radius widened from float32), inclusive
 // Passes:
-//   words    rp_words_kernel: per (query, rank) the 64-row words its list needs, ceil(list_n / 64); 0 at a rank whose
-//            list an earlier rank names.  tk_scan_exclusive64 over them: where each (query, rank)'s words begin.
+//   words    probe_len_kernel<64> (probe_job.h: the prologue knn_probe shares): per (query, rank) the 64-row words its
+//            list needs, ceil(list_n / 64); 0 at a rank whose list an earlier rank names.  tk_scan_exclusive64 over
+//            them: where each (query, rank)'s words begin.
 //   count    radius_probe_count_kernel<T, TY, RESTRICTED>: one workgroup of 256 lanes per (query, rank), the query in
 //            LDS in T, the list walked in blocks of 64 rows a wave, a lane a row.  The hit predicate is ballotted per
 //            wave; the 64-bit ballot IS the bitmap word of that (query, rank, block), written by one lane — every word
@@ -41,18 +42,13 @@
 //            distances get equal ranks) and (rank, row id) is sorted.  Both sorts order distinct 64-bit keys, so the
 //            result does not depend on the order the fill left.
 //   decode   keys -> int64 ids and distances
-#include "api_internal.h"
+#include "probe_job.h"
 #include "sqdist_row.h"
 #include "span_exact.h"
 
 #define RP_THREADS 256
 
-struct RpJob {
-    const float *q;                 // (nq, d) prepared queries
-    const void *rows;               // the vectors, TY
-    const int64_t *probes;          // (nq, kc)
-    const int64_t *ids, *ids_off, *list_n;
-    const int32_t *twin_list;       // twins.hip, twin_w > 0
+struct RpJob : ProbeJob {
     const float *radius;            // (nq)
     const long long *words, *woff;  // (nq * kc): bitmap words of the (query, rank), and where they begin
     unsigned long long *bitmap;
@@ -62,34 +58,7 @@ struct RpJob {
     int *slots, *err;
     unsigned long long *keys;
     int32_t *key_rows;              // float64 vectors: the row id beside its distance key
-    int64_t n_lists, N;
-    int d, kc, twin_w;
 };
-
-// the list a probe names: -1 (an unfilled coarse heap) is the last list; -1 for what names none
-__device__ __forceinline__ int32_t rp_list(int64_t p, int64_t n_lists)
-{
-    if (p < 0) p += n_lists;
-    return (p >= 0 && p < n_lists) ? (int32_t)p : -1;
-}
-
-__global__ __launch_bounds__(256) void rp_words_kernel(const int64_t *__restrict__ probes, int64_t n, int kc,
-                                                       int64_t n_lists, const int64_t *__restrict__ list_n,
-                                                       long long *__restrict__ words)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n) return;
-    if (i == n) {               // (the scan's last entry: the total)
-        words[i] = 0;
-        return;
-    }
-    const int rank = (int)(i % kc);
-    const int64_t *row = probes + (i - rank);
-    const int32_t L = rp_list(row[rank], n_lists);
-    bool walk = L >= 0;
-    for (int t = 0; walk && t < rank; t++) walk = rp_list(row[t], n_lists) != L;
-    words[i] = walk ? (list_n[L] + 63) / 64 : 0;
-}
 
 template <typename T, typename TY, bool RESTRICTED>
 __global__ __launch_bounds__(RP_THREADS) void radius_probe_count_kernel(const RpJob j, const TkBruteRestrict r)
@@ -105,8 +74,8 @@ __global__ __launch_bounds__(RP_THREADS) void radius_probe_count_kernel(const Rp
     const int rank = (int)(b - qi * j.kc);
     for (int t = tid; t < j.d; t += RP_THREADS) xs[t] = (T)j.q[qi * j.d + t];
     if (j.twin_w > 0)
-        for (int t = tid; t < rank; t += RP_THREADS) pl[t] = rp_list(j.probes[qi * j.kc + t], j.n_lists);
-    const int32_t L = rp_list(j.probes[b], j.n_lists);
+        for (int t = tid; t < rank; t += RP_THREADS) pl[t] = probe_list(j.probes[qi * j.kc + t], j.n_lists);
+    const int32_t L = probe_list(j.probes[b], j.n_lists);
     const int64_t n = j.list_n[L], base = j.ids_off[L];
     const T rad = (T)j.radius[qi];
     // the query's own attributes, once
@@ -176,7 +145,7 @@ __global__ __launch_bounds__(RP_THREADS) void radius_probe_fill_kernel(const RpJ
     if (nw == 0) return;
     const int64_t qi = b / j.kc;
     for (int t = tid; t < j.d; t += RP_THREADS) xs[t] = (T)j.q[qi * j.d + t];
-    const int32_t L = rp_list(j.probes[b], j.n_lists);
+    const int32_t L = probe_list(j.probes[b], j.n_lists);
     const int64_t base = j.ids_off[L], off = j.offset[qi];
     const uint32_t cnt = (uint32_t)j.count[qi];
     const TY *rows = (const TY *)j.rows;
@@ -272,17 +241,6 @@ static void rp_pass(const tk_index *ix, const RpJob &j, int64_t nq, const TkBrut
     else rp_launch<float, float>(j, nq, r, fill);
 }
 
-static int rp_sort(tk_index *ix, const unsigned long long *in, unsigned long long *out, int64_t total, int64_t nq)
-{
-    size_t bytes = 0;
-    if (tk_launch_radius_sort(nullptr, &bytes, in, out, total, nq, ix->rd_off.as<int64_t>(), nullptr))
-        return fail(TK_ERR_HIP, "tk_launch_radius_sort: work memory query failed");
-    TRY(ix->rd_tmp.ensure(bytes > 0 ? bytes : 1));
-    if (tk_launch_radius_sort(ix->rd_tmp.p, &bytes, in, out, total, nq, ix->rd_off.as<int64_t>(), nullptr))
-        return fail(TK_ERR_HIP, "tk_launch_radius_sort failed");
-    return TK_OK;
-}
-
 // ---- C ABI ----
 
 extern "C" int tk_index_radius_probe(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq,
@@ -307,45 +265,26 @@ extern "C" int tk_index_radius_probe(tk_index *ix, const float *q, const void *q
     TRY(radius_probe_twins(ix, &twin_list, &twin_w));
     TkBruteRestrict r;
     bool any;
-    TRY(brute_restrict(ix, nq, allowed_mask, exclude, group, tags, tag_mode, between, r, any));
+    TRY(brute_restrict(ix, nq, {allowed_mask, exclude, group, tags, tag_mode, between}, r, any));
     out_lims[0] = 0;
     *out_total = 0;
+    const bool f64 = ix->data_dtype == TK_DATA_F64;
     if (nq == 0) {
-        if (!count_only) ix->rp_total = 0, ix->rp_f64 = ix->data_dtype == TK_DATA_F64;
+        if (!count_only) ix->rp_total = 0, ix->rp_f64 = f64;
         return TK_OK;
     }
     TRY(flush_pending(ix));
-    const int kc = (int)(n_probes < ix->n_lists ? n_probes : ix->n_lists);
+    int kc;
+    TRY(probe_pairs(ix, nq, n_probes, kc));
     const int64_t pairs = nq * kc;
-    ARGCHECK(pairs < (1ll << 31), "nq * min(n_probes, n_lists) < 2^31");
-    TRY(ix->rp_probes.ensure((size_t)pairs * 8));
-    TRY(ix->rp_words.ensure((size_t)(pairs + 1) * 8));
-    TRY(ix->rp_woff.ensure((size_t)(pairs + 1) * 8));
-    TRY(ix->br_q.ensure((size_t)nq * ix->d * 4));
     TRY(ix->rd_radius.ensure((size_t)nq * 4));
     TRY(ix->rd_count.ensure((size_t)nq * 8 + 4));
-    // the coarse stage, chunk by chunk; its probes stay on the device
-    TRY(coarse_top_chunks(ix, q, q_pq, q_pq_is_f64, nq, n_probes, false,
-                          [&](int64_t o, int64_t m, int kc_, const int64_t *probes, const float *) -> int {
-                              if (kc_ != kc) return fail(TK_ERR_HIP, "radius_probe: the coarse stage's row width");
-                              HIPCHECK(hipMemcpy(ix->rp_probes.as<int64_t>() + o * kc, probes, (size_t)m * kc * 8,
-                                                 hipMemcpyDeviceToDevice));
-                              return TK_OK;
-                          }));
-    HIPCHECK(hipMemcpy(ix->br_q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
+    RpJob j{};
+    // the coarse stage; the bitmap words per (query, rank) and where they begin
+    TRY(probe_lengths<64>(ix, "radius_probe", q, q_pq, q_pq_is_f64, nq, n_probes, kc, twin_list, twin_w, j));
     HIPCHECK(hipMemcpy(ix->rd_radius.p, radius, (size_t)nq * 4, hipMemcpyHostToDevice));
-    // bitmap words per (query, rank) and where they begin
-    long long *words = ix->rp_words.as<long long>(), *woff = ix->rp_woff.as<long long>();
-    hipLaunchKernelGGL(rp_words_kernel, dim3((unsigned)((pairs + 256) / 256)), dim3(256), 0, 0,
-                       ix->rp_probes.as<int64_t>(), pairs, kc, ix->n_lists, ix->list_n.as<int64_t>(), words);
-    size_t sbytes = 0;
-    (void)tk_scan_exclusive64(nullptr, &sbytes, words, woff, pairs + 1, nullptr);
-    TRY(ix->rp_scan.ensure(sbytes));
-    if (tk_scan_exclusive64(ix->rp_scan.p, &sbytes, words, woff, pairs + 1, nullptr))
-        return fail(TK_ERR_HIP, "tk_scan_exclusive64 failed");
-    HIPCHECK(hipGetLastError());
     long long n_words = 0;
-    HIPCHECK(hipMemcpy(&n_words, woff + pairs, 8, hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(&n_words, ix->pl_off.as<long long>() + pairs, 8, hipMemcpyDeviceToHost));
     if ((double)n_words * 8.0 > workspace_bytes()) {
         char b[200];
         snprintf(b, sizeof b, "radius_search(n_probes=): the candidate bitmap of %lld queries needs %lld bytes, more than "
@@ -355,69 +294,41 @@ extern "C" int tk_index_radius_probe(tk_index *ix, const float *q, const void *q
     TRY(ix->rp_bitmap.ensure((size_t)(n_words > 0 ? n_words : 1) * 8));
     int *count = ix->rd_count.as<int>(), *slots = count + nq, *err = slots + nq;
     HIPCHECK(hipMemsetAsync(count, 0, (size_t)nq * 8 + 4, nullptr));
-    RpJob j{};
-    j.q = ix->br_q.as<float>();
-    j.rows = ix->data.p;
-    j.probes = ix->rp_probes.as<int64_t>();
-    j.ids = ix->ids.as<int64_t>();
-    j.ids_off = ix->ids_off.as<int64_t>();
-    j.list_n = ix->list_n.as<int64_t>();
-    j.twin_list = twin_list;
     j.radius = ix->rd_radius.as<float>();
-    j.words = words;
-    j.woff = woff;
+    j.words = ix->pl_len.as<long long>();
+    j.woff = ix->pl_off.as<long long>();
     j.bitmap = ix->rp_bitmap.as<unsigned long long>();
     j.count = count;
     j.slots = slots;
     j.err = err;
-    j.n_lists = ix->n_lists;
-    j.N = ix->N;
-    j.d = ix->d;
-    j.kc = kc;
-    j.twin_w = twin_w;
     rp_pass(ix, j, nq, any ? &r : nullptr, false);
     HIPCHECK(hipGetLastError());
-    std::vector<int> counts((size_t)nq);
-    HIPCHECK(hipMemcpy(counts.data(), count, (size_t)nq * 4, hipMemcpyDeviceToHost));     // (synchronises)
-    for (int64_t i = 0; i < nq; i++) out_lims[i + 1] = out_lims[i] + counts[(size_t)i];
-    const int64_t total = *out_total = out_lims[nq];
-    if (count_only) return TK_OK;
-    if (total > max_results) {
-        char b[160];
-        snprintf(b, sizeof b, "radius_search: %lld rows lie within the radii, more than max_results = %lld",
-                 (long long)total, (long long)max_results);
-        return fail(TK_ERR_ARG, b);
-    }
-    const bool f64 = ix->data_dtype == TK_DATA_F64;
-    if (total == 0) {
-        ix->rp_total = 0, ix->rp_f64 = f64;
+    bool fill;
+    TRY(radius_lims(ix, count, nq, count_only, max_results, out_lims, out_total, fill));
+    if (!fill) {
+        if (!count_only) ix->rp_total = 0, ix->rp_f64 = f64;
         return TK_OK;
     }
-    TRY(ix->rd_off.ensure((size_t)(nq + 1) * 8));
-    TRY(ix->rd_keys.ensure((size_t)total * 8));
-    TRY(ix->rd_alt.ensure((size_t)total * 8));
+    const int64_t total = *out_total;
     TRY(ix->rp_ids.ensure((size_t)total * 8));
     TRY(ix->rp_dist.ensure((size_t)total * (f64 ? 8 : 4)));
     if (f64) TRY(ix->rp_rows.ensure((size_t)total * 4));
-    HIPCHECK(hipMemcpy(ix->rd_off.p, out_lims, (size_t)(nq + 1) * 8, hipMemcpyHostToDevice));
     unsigned long long *keys = ix->rd_keys.as<unsigned long long>(), *alt = ix->rd_alt.as<unsigned long long>();
     j.offset = ix->rd_off.as<int64_t>();
     j.keys = keys;
     j.key_rows = ix->rp_rows.as<int32_t>();
     rp_pass(ix, j, nq, nullptr, true);
     HIPCHECK(hipGetLastError());
-    int bad = 0;
-    HIPCHECK(hipMemcpy(&bad, err, 4, hipMemcpyDeviceToHost));
-    if (bad) return fail(TK_ERR_HIP, "radius_search: count and fill passes disagree");
+    TRY(radius_passes_agree(err));
     int64_t *ids = ix->rp_ids.as<int64_t>();
     const unsigned grid = (unsigned)((total + 255) / 256);
     if (!f64) {
-        if (sorted) TRY(rp_sort(ix, keys, alt, total, nq));
+        if (sorted) TRY(radius_sort(ix, keys, alt, total, nq));
         tk_launch_radius_decode(sorted ? alt : keys, total, ids, ix->rp_dist.as<float>(), nullptr);
     } else if (sorted) {
-        TRY(rp_sort(ix, keys, alt, total, nq));                                 // the distance keys alone
+        TRY(radius_sort(ix, keys, alt, total, nq));                                 // the distance keys alone
         hipLaunchKernelGGL(rp_rank_kernel, dim3(grid), dim3(256), 0, 0, keys, j.key_rows, alt, j.offset, nq, total);
-        TRY(rp_sort(ix, keys, (unsigned long long *)ids, total, nq));           // (rank, row id)
+        TRY(radius_sort(ix, keys, (unsigned long long *)ids, total, nq));           // (rank, row id)
         hipLaunchKernelGGL(rp_decode64_kernel, dim3(grid), dim3(256), 0, 0, (const unsigned long long *)ids,
                            j.key_rows, alt, total, ids, ix->rp_dist.as<double>());
     } else {

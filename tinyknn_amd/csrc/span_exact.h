@@ -11,7 +11,7 @@
 // workgroup stream through their rows independently.  The last cut is the result: ascending by (distance, row id),
 // -1 / +inf behind fewer than k survivors — the same whatever order the span lists its rows in.
 #pragma once
-#include "kernels.h"
+#include "api_internal.h"
 #include "sqdist_row.h"
 
 #define GX_THREADS 256
@@ -156,4 +156,57 @@ __device__ __forceinline__ void span_exact_body(const float *__restrict__ q, int
         out[qi * k + e] = e < kept ? (int64_t)kid[e] : -1;
         if (out_d) out_d[qi * k + e] = e < kept ? GxKey<T>::back(kd[e]) : (T)__builtin_huge_valf();
     }
+}
+
+// ---- the host frame of the two span calls (tk_index_knn_group, tk_index_knn_between) ----
+// The argument checks both make in the same words.  call: "knn_group" / "knn_between"; required: the argument the call
+// cannot do without, and what it says where it is missing.
+static inline int span_call_checks(const tk_index *ix, const char *call, const float *q, int64_t nq, int k,
+                                   const int64_t *out_ids, const void *required, const char *required_msg)
+{
+    ARGCHECK(ix && ix->have_data, "set_data first");
+    ARGCHECK(!ix->sharded, std::string("list-sharded index: ") + call + " is not supported");
+    ARGCHECK(nq >= 0 && (nq == 0 || (q && out_ids)), "buffers");
+    ARGCHECK(nq == 0 || required, required_msg);
+    ARGCHECK(k >= 1 && k <= 1024 && k <= ix->N, "1 <= k <= min(1024, N)");
+    ARGCHECK(ix->N < (1ll << 31), "N < 2^31");
+    ARGCHECK(ix->d <= 4096, "d <= 4096");
+    return TK_OK;
+}
+
+// The queries into br_q, the walk, the ids (and distances, where asked) back to the host.  walk(T(), TY(), lds, X, out,
+// dist) makes the spans of the nq queries and launches the call's kernel<T, TY> with lds bytes of LDS; out / dist:
+// (nq, k) on the device.
+template <typename F>
+static int span_call(tk_index *ix, const float *q, int64_t nq, int k, int64_t *out_ids, void *out_dist, F walk)
+{
+    const bool f64 = ix->data_dtype == TK_DATA_F64;
+    const size_t dsz = f64 ? 8 : 4;
+    TRY(ix->br_q.ensure((size_t)nq * ix->d * 4));
+    TRY(ix->br_out.ensure((size_t)nq * k * 8));
+    if (out_dist) TRY(ix->br_dist.ensure((size_t)nq * k * dsz));
+    HIPCHECK(hipMemcpy(ix->br_q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
+    void *dist = out_dist ? ix->br_dist.p : nullptr;
+    const float *X = ix->br_q.as<float>();
+    int64_t *out = ix->br_out.as<int64_t>();
+    const size_t lds = gx_lds_bytes(ix->d, dsz, dsz);       // (the key of T is as wide as T)
+    if (f64) TRY(walk(double(), double(), lds, X, out, dist));
+    else if (ix->data_dtype == TK_DATA_F16) TRY(walk(float(), _Float16(), lds, X, out, dist));
+    else TRY(walk(float(), float(), lds, X, out, dist));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(out_ids, ix->br_out.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
+    if (out_dist) HIPCHECK(hipMemcpy(out_dist, dist, (size_t)nq * k * dsz, hipMemcpyDeviceToHost));
+    return TK_OK;
+}
+
+// info4 of tk_index_group_rows / tk_index_value_rows: whether the rows gathered for the walk exist, their bytes, how
+// often they were made, the groups / columns they were made for
+static inline int span_rows_info(const TkRowTable &t, bool have, int64_t bytes, int64_t *info4)
+{
+    info4[0] = have ? 1 : 0;
+    info4[1] = have ? bytes : 0;
+    info4[2] = t.span_state.builds;
+    info4[3] = have ? t.span_groups : 0;
+    return TK_OK;
 }

@@ -87,29 +87,6 @@ static int range_spans(tk_index *ix, const int64_t *ranges_dev, int64_t n)
     return TK_OK;
 }
 
-template <typename T, typename TY>
-static void launch_range_exact(const tk_index *ix, const float *q, int64_t nq, int k, const TkBruteRestrict &r,
-                               int64_t *out, void *out_d)
-{
-    const size_t lds = gx_lds_bytes(ix->d, sizeof(typename GxKey<T>::type), sizeof(T));
-    hipLaunchKernelGGL((range_exact_kernel<T, TY>), dim3((unsigned)nq), dim3(GX_THREADS), lds, 0, q, ix->d,
-                       ix->data.as<TY>(), ix->values.span_rows.as<int32_t>(), ix->N, ix->gx_col.as<int32_t>(),
-                       ix->gx_begin.as<int32_t>(), ix->gx_len.as<int32_t>(), ix->stored_bits.as<uint32_t>(), r, k, out,
-                       (T *)out_d);
-}
-
-// A host array of the call in its workspace buffer (NULL stays NULL)
-template <typename T>
-static int vx_upload(DevBuf &b, const T *host, size_t n, const T *&dev)
-{
-    dev = nullptr;
-    if (!host) return TK_OK;
-    TRY(b.ensure((n > 0 ? n : 1) * sizeof(T)));
-    HIPCHECK(hipMemcpy(b.p, host, n * sizeof(T), hipMemcpyHostToDevice));
-    dev = b.as<T>();
-    return TK_OK;
-}
-
 // query i of (n, cols, 2) host keys bounds some column
 static bool range_bounded(const int64_t *between, int64_t i, int cols)
 {
@@ -125,17 +102,12 @@ extern "C" int tk_index_knn_between(tk_index *ix, const float *q, int64_t nq, in
                                     const uint64_t *tags, int tag_mode, int64_t *out_ids, void *out_dist)
 {
     IXLOCK(ix);
-    ARGCHECK(ix && ix->have_data, "set_data first");
-    ARGCHECK(!ix->sharded, "list-sharded index: knn_between is not supported");
-    ARGCHECK(nq >= 0 && (nq == 0 || (q && out_ids)), "buffers");
-    ARGCHECK(nq == 0 || between, "between: the ranges of every query are required");
-    ARGCHECK(k >= 1 && k <= 1024 && k <= ix->N, "1 <= k <= min(1024, N)");
-    ARGCHECK(ix->N < (1ll << 31), "N < 2^31");
-    ARGCHECK(ix->d <= 4096, "d <= 4096");
-    ARGCHECK(tag_mode == 0 || tag_mode == 1, "tag_mode: 0 (any) or 1 (all)");
-    TRY(row_table_covers(ix, ix->values));
-    if (group) TRY(row_table_covers(ix, ix->groups));
-    if (tags) TRY(row_table_covers(ix, ix->tags));
+    TRY(span_call_checks(ix, "knn_between", q, nq, k, out_ids, between,
+                         "between: the ranges of every query are required"));
+    const TkHostRestrict h{allowed_mask, exclude, group, tags, tag_mode, between};
+    TRY(restrict_mode(h));
+    TRY(row_table_covers(ix, ix->values));          // (in front of the groups and tags: the call's own argument)
+    TRY(restrict_tables(ix, h));
     const int cols = value_columns(ix);
     for (int64_t i = 0; i < nq; i++)
         ARGCHECK(range_bounded(between, i, cols),
@@ -143,45 +115,26 @@ extern "C" int tk_index_knn_between(tk_index *ix, const float *q, int64_t nq, in
                  "tk_index_knn_brute's or tk_index_query_batch's to answer)");
     if (group)
         for (int64_t i = 0; i < nq; i++) ARGCHECK(group[i] >= -1, "group: entries must be a group id >= 0 or -1");
-    if (exclude)
-        for (int64_t i = 0; i < nq; i++) ARGCHECK(exclude[i] >= -1 && exclude[i] < ix->N, "exclude: entries in [-1, N)");
+    TRY(restrict_ranges(ix, nq, h));
     if (nq == 0) return TK_OK;
     TRY(flush_pending(ix));
     TRY(value_rows_ensure(ix));
     TRY(stored_bits_ensure(ix, "tk_index_knn_between"));
-    TkBruteRestrict r{};
-    r.n_rows = ix->N;
-    r.tag_mode = tag_mode;
-    if (allowed_mask) {
-        std::vector<uint32_t> bits((size_t)(ix->N + 31) / 32, 0u);
-        for (int64_t j = 0; j < ix->N; j++) bits[(size_t)(j >> 5)] |= (uint32_t)(allowed_mask[j] != 0) << (j & 31);
-        TRY(vx_upload(ix->br_mask, bits.data(), bits.size(), r.allowed));
-    }
-    TRY(vx_upload(ix->br_exclude, exclude, (size_t)nq, r.exclude));
-    TRY(vx_upload(ix->br_group, group, (size_t)nq, r.group));
-    if (group) r.row_groups = ix->groups.by_row.as<int32_t>();
-    TRY(vx_upload(ix->br_tags, tags, (size_t)nq, r.tags));
-    if (tags) r.row_tags = ix->tags.by_row.as<uint64_t>();
-    r.cols = cols;
-    r.row_keys = ix->values.by_row.as<int64_t>();
-    TRY(vx_upload(ix->br_ranges, between, (size_t)nq * 2 * cols, r.ranges));
-    const size_t dsz = ix->data_dtype == TK_DATA_F64 ? 8 : 4;
-    TRY(ix->br_q.ensure((size_t)nq * ix->d * 4));
-    TRY(ix->br_out.ensure((size_t)nq * k * 8));
-    if (out_dist) TRY(ix->br_dist.ensure((size_t)nq * k * dsz));
-    HIPCHECK(hipMemcpy(ix->br_q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
-    TRY(range_spans(ix, r.ranges, nq));
-    void *dist = out_dist ? ix->br_dist.p : nullptr;
-    const float *X = ix->br_q.as<float>();
-    int64_t *out = ix->br_out.as<int64_t>();
-    if (ix->data_dtype == TK_DATA_F64) launch_range_exact<double, double>(ix, X, nq, k, r, out, dist);
-    else if (ix->data_dtype == TK_DATA_F16) launch_range_exact<float, _Float16>(ix, X, nq, k, r, out, dist);
-    else launch_range_exact<float, float>(ix, X, nq, k, r, out, dist);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipDeviceSynchronize());
-    HIPCHECK(hipMemcpy(out_ids, ix->br_out.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost));
-    if (out_dist) HIPCHECK(hipMemcpy(out_dist, dist, (size_t)nq * k * dsz, hipMemcpyDeviceToHost));
-    return TK_OK;
+    TkBruteRestrict r;
+    bool any;
+    TRY(restrict_upload(ix, nq, h, r, any));
+    return span_call(ix, q, nq, k, out_ids, out_dist,
+                     [&](auto t, auto ty, size_t lds, const float *X, int64_t *out, void *dist) -> int {
+                         typedef decltype(t) T;
+                         typedef decltype(ty) TY;
+                         TRY(range_spans(ix, r.ranges, nq));
+                         hipLaunchKernelGGL((range_exact_kernel<T, TY>), dim3((unsigned)nq), dim3(GX_THREADS), lds, 0, X,
+                                            ix->d, ix->data.as<TY>(), ix->values.span_rows.as<int32_t>(), ix->N,
+                                            ix->gx_col.as<int32_t>(), ix->gx_begin.as<int32_t>(),
+                                            ix->gx_len.as<int32_t>(), ix->stored_bits.as<uint32_t>(), r, k, out,
+                                            (T *)dist);
+                         return TK_OK;
+                     });
 }
 
 extern "C" int tk_index_range_sizes(tk_index *ix, const int64_t *between, int64_t n, int64_t *out_len,
@@ -197,7 +150,7 @@ extern "C" int tk_index_range_sizes(tk_index *ix, const int64_t *between, int64_
     TRY(flush_pending(ix));
     TRY(value_rows_ensure(ix));
     const int64_t *ranges_dev = nullptr;
-    TRY(vx_upload(ix->br_ranges, between, (size_t)n * 2 * value_columns(ix), ranges_dev));
+    TRY(host_upload(ix->br_ranges, between, (size_t)n * 2 * value_columns(ix), ranges_dev));
     TRY(range_spans(ix, ranges_dev, n));
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
@@ -214,9 +167,5 @@ extern "C" int tk_index_value_rows(tk_index *ix, int64_t *info4)
     ARGCHECK(ix && info4, "null index / buffer");
     const TkRowTable &t = ix->values;
     const bool have = t.span_state.current(t.set_gen) && t.n == ix->N && t.n > 0;
-    info4[0] = have ? 1 : 0;
-    info4[1] = have ? t.span_groups * ix->N * 4 : 0;
-    info4[2] = t.span_state.builds;
-    info4[3] = have ? t.span_groups : 0;
-    return TK_OK;
+    return span_rows_info(t, have, t.span_groups * ix->N * 4, info4);
 }

@@ -1425,29 +1425,55 @@ class DeviceIndex:
                                                      _lib.ptr(out, _lib._i64p)))
             return out
         restrict = self._brute_restrictions("knn_brute", nq, allowed, exclude, group, tags, tags_mode, between)
-        dist = np.full((nq, k), np.inf, dtype=np.float32) if want_dist else None
-        out[:] = -1
+        out, dist = self._out_pair(nq, k, want_dist, np.float32)
         call = _lib.lib().tk_index_knn_brute_matrix if matrix else _lib.lib().tk_index_knn_brute_ex
         _lib.check(call(
             self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), *self._host_pointers(restrict),
             _lib.ptr(out, _lib._i64p), None if dist is None else dist.ctypes.data))
         return (out, dist) if want_dist else out
 
-    def _brute_restrictions(self, call, nq, allowed, exclude, group, tags, tags_mode, between):
-        """The host arrays of a restricted exact call (knn_brute, radius_search), parsed as query_batch parses them:
-        (mask, exclude, group, tags, tag mode, ranges), None for what was not given.  An AllowSet is refused
-        (TypeError) and so is a list-sharded index, before the device is touched."""
+    def _brute_restrictions(self, call, nq, allowed, exclude, group, tags, tags_mode, between, required=None):
+        """The host arrays of an exact call (knn_brute, radius_search, knn_probe, knn_group, knn_between), parsed as
+        query_batch parses them: (mask, exclude, group, tags, tag mode, ranges), None for what was not given.  An
+        AllowSet is refused (TypeError) and so is a list-sharded index, before the device is touched.
+        required ("group" / "between"): the argument knn_group / knn_between cannot do without — parsed first, with the
+        call's own conditions on it; those two calls also refuse a cloned shard, in their own words."""
         if isinstance(allowed, AllowSet):
             raise TypeError(f"{call}: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
                             "list position")
-        if _dev_is_sharded(self):
-            raise RuntimeError(f"{call} with restrictions is not supported on a list-sharded index")
+        if required is None:
+            if _dev_is_sharded(self):
+                raise RuntimeError(f"{call} with restrictions is not supported on a list-sharded index")
+        elif _dev_is_sharded(self) or self._source is not None:
+            raise RuntimeError(f"{call} is not supported on a list-sharded index")
+        if required == "group":
+            group = query_groups(group, nq)
+            if len(group) and int(group.min()) < 0:
+                raise AssertionError("knn_group: group= needs a group id >= 0 for every query (-1, any group, is "
+                                     "knn_brute's or query_batch's to answer)")
+        if required == "between":
+            if between is None:
+                raise TypeError("knn_between: between= is required: a pair (lo, hi)")
+            between = np.ascontiguousarray(self._ranges_of(between, nq))
+            free = np.flatnonzero(unbounded_queries(between))
+            if len(free):
+                raise ValueError(f"knn_between: query {int(free[0])} bounds no column (an unrestricted query is "
+                                 "knn_brute's or query_batch's to answer)")
         mask = None if allowed is None else AllowSet.mask_of(allowed, self.N)
         exclude = None if exclude is None else self._exclude_of(exclude, nq)
-        group = None if group is None else query_groups(group, nq)
+        if required != "group":
+            group = None if group is None else query_groups(group, nq)
         tags, mode = (None, 0) if tags is None else (query_tags(tags, nq), tag_mode_of(tags_mode))
-        between = None if between is None else np.ascontiguousarray(self._ranges_of(between, nq))
+        if required != "between":
+            between = None if between is None else np.ascontiguousarray(self._ranges_of(between, nq))
         return mask, exclude, group, tags, mode, between
+
+    def _out_pair(self, nq, k, want_dist, dtype=None):
+        """What an exact call fills: (nq, k) int64 ids of -1 and, where asked, the distances of +inf beside them (in
+        the dtype of the rescoring's distances unless the call has its own)"""
+        if dtype is None:
+            dtype = np.float64 if self._f64 else np.float32
+        return np.full((nq, k), -1, dtype=np.int64), np.full((nq, k), np.inf, dtype=dtype) if want_dist else None
 
     @staticmethod
     def _host_pointers(restrict):
@@ -1620,8 +1646,7 @@ class DeviceIndex:
         nq = len(qn)
         restrict = self._brute_restrictions("knn_probe", nq, allowed, exclude, group, tags, tags_mode, between)
         q_pq, n_probes = self._probe_args(qn, q_pq, n_probes)
-        out = np.full((nq, k), -1, dtype=np.int64)
-        dist = np.full((nq, k), np.inf, dtype=np.float64 if self._f64 else np.float32) if return_distances else None
+        out, dist = self._out_pair(nq, k, return_distances)
         call = _lib.lib().tk_index_knn_probe_matrix if matrix else _lib.lib().tk_index_knn_probe
         _lib.check(call(
             self._h, _lib.ptr(qn, _lib._f32p), q_pq.ctypes.data, int(q_pq.dtype == np.float64), nq, k, n_probes,
@@ -1647,31 +1672,15 @@ class DeviceIndex:
         group's size; one workgroup walks a group, so for large groups knn_brute(group=) is the call.  Rows taken out
         by remove() never come back.  allowed / exclude / tags, tags_mode / between: as knn_brute's; an AllowSet is
         refused (TypeError).  Every vector store.  Not for a list-sharded index."""
-        if isinstance(allowed, AllowSet):
-            raise TypeError("knn_group: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
-                            "list position")
-        if _dev_is_sharded(self) or self._source is not None:
-            raise RuntimeError("knn_group is not supported on a list-sharded index")
         qn = np.ascontiguousarray(qn, dtype=np.float32)
         assert qn.ndim == 2 and qn.shape[1] == self.d
         nq = qn.shape[0]
-        group = query_groups(group, nq)
-        if len(group) and int(group.min()) < 0:
-            raise AssertionError("knn_group: group= needs a group id >= 0 for every query (-1, any group, is "
-                                 "knn_brute's or query_batch's to answer)")
-        mask = None if allowed is None else AllowSet.mask_of(allowed, self.N)
-        exclude = None if exclude is None else self._exclude_of(exclude, nq)
-        tags, mode = (None, 0) if tags is None else (query_tags(tags, nq), tag_mode_of(tags_mode))
-        between = None if between is None else np.ascontiguousarray(self._ranges_of(between, nq))
-        out = np.full((nq, k), -1, dtype=np.int64)
-        dist = np.full((nq, k), np.inf, dtype=np.float64 if self._f64 else np.float32) if return_distances else None
-
-        def host(a):
-            return None if a is None else a.ctypes.data
-
+        mask, exclude, group, tags, mode, between = self._brute_restrictions(
+            "knn_group", nq, allowed, exclude, group, tags, tags_mode, between, required="group")
+        out, dist = self._out_pair(nq, k, return_distances)
         _lib.check(_lib.lib().tk_index_knn_group(
-            self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), host(group), host(mask), host(exclude), host(tags), mode,
-            host(between), _lib.ptr(out, _lib._i64p), host(dist)))
+            self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), *self._host_pointers((group, mask, exclude, tags, mode, between)),
+            _lib.ptr(out, _lib._i64p), None if dist is None else dist.ctypes.data))
         return (out, dist) if return_distances else out
 
     def group_sizes(self, g):
@@ -1705,34 +1714,15 @@ class DeviceIndex:
         for wide ranges knn_brute(between=) is the call.  Rows taken out by remove() never come back.  allowed /
         exclude / group (-1: any) / tags, tags_mode: as knn_brute's; an AllowSet is refused (TypeError).  Every vector
         store.  Not for a list-sharded index."""
-        if isinstance(allowed, AllowSet):
-            raise TypeError("knn_between: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
-                            "list position")
-        if _dev_is_sharded(self) or self._source is not None:
-            raise RuntimeError("knn_between is not supported on a list-sharded index")
         qn = np.ascontiguousarray(qn, dtype=np.float32)
         assert qn.ndim == 2 and qn.shape[1] == self.d
         nq = qn.shape[0]
-        if between is None:
-            raise TypeError("knn_between: between= is required: a pair (lo, hi)")
-        between = np.ascontiguousarray(self._ranges_of(between, nq))
-        free = np.flatnonzero(unbounded_queries(between))
-        if len(free):
-            raise ValueError(f"knn_between: query {int(free[0])} bounds no column (an unrestricted query is knn_brute's "
-                             "or query_batch's to answer)")
-        mask = None if allowed is None else AllowSet.mask_of(allowed, self.N)
-        exclude = None if exclude is None else self._exclude_of(exclude, nq)
-        group = None if group is None else query_groups(group, nq)
-        tags, mode = (None, 0) if tags is None else (query_tags(tags, nq), tag_mode_of(tags_mode))
-        out = np.full((nq, k), -1, dtype=np.int64)
-        dist = np.full((nq, k), np.inf, dtype=np.float64 if self._f64 else np.float32) if return_distances else None
-
-        def host(a):
-            return None if a is None else a.ctypes.data
-
+        mask, exclude, group, tags, mode, between = self._brute_restrictions(
+            "knn_between", nq, allowed, exclude, group, tags, tags_mode, between, required="between")
+        out, dist = self._out_pair(nq, k, return_distances)
         _lib.check(_lib.lib().tk_index_knn_between(
-            self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), host(between), host(mask), host(exclude), host(group),
-            host(tags), mode, _lib.ptr(out, _lib._i64p), host(dist)))
+            self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), *self._host_pointers((between, mask, exclude, group, tags, mode)),
+            _lib.ptr(out, _lib._i64p), None if dist is None else dist.ctypes.data))
         return (out, dist) if return_distances else out
 
     def range_sizes(self, between, nq=None):
@@ -2827,15 +2817,7 @@ class IVF:
         mask of length N or row ids, not an AllowSet.  Not for a list-sharded index.
         matrix=True: DeviceIndex.knn_brute(matrix=True) — a half store of any d <= 4096 on the f16 matrix cores, the
         values knn_probe(matrix=True)'s dist_m."""
-        if isinstance(allowed, AllowSet):
-            raise TypeError("knn_brute: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
-                            "list position")
-        if between is not None:
-            self._ranges(between, len(qs))
-        if tags is not None:
-            tag_mode_of(tags_mode)
-        dev = self._unsharded_device_index()
-        qn, _ = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
+        qn, _, dev = self._exact_front("knn_brute", qs, allowed, tags, tags_mode, between)
         call = dev.knn_brute_dist if return_distances else dev.knn_brute
         return call(qn, k, allowed=allowed, exclude=exclude, group=group, tags=tags, tags_mode=tags_mode, between=between,
                     matrix=matrix)
@@ -2868,7 +2850,7 @@ class IVF:
             qn, qp, dev = self._radius_front("radius_search", qs, radius, allowed, tags, tags_mode, between, n_probes)
             return dev.radius_probe(qn, qp, radius, n_probes, allowed=allowed, exclude=exclude, group=group, tags=tags,
                                     tags_mode=tags_mode, between=between, sort=sort, max_results=max_results)
-        qn, dev = self._radius_front("radius_search", qs, radius, allowed, tags, tags_mode, between)
+        qn, _, dev = self._radius_front("radius_search", qs, radius, allowed, tags, tags_mode, between)
         return dev.radius_brute(qn, radius, allowed=allowed, exclude=exclude, group=group, tags=tags,
                                 tags_mode=tags_mode, between=between, sort=sort, max_results=max_results)
 
@@ -2881,26 +2863,39 @@ class IVF:
             qn, qp, dev = self._radius_front("radius_count", qs, radius, allowed, tags, tags_mode, between, n_probes)
             return dev.radius_probe_count(qn, qp, radius, n_probes, allowed=allowed, exclude=exclude, group=group,
                                           tags=tags, tags_mode=tags_mode, between=between)
-        qn, dev = self._radius_front("radius_count", qs, radius, allowed, tags, tags_mode, between)
+        qn, _, dev = self._radius_front("radius_count", qs, radius, allowed, tags, tags_mode, between)
         return dev.radius_count(qn, radius, allowed=allowed, exclude=exclude, group=group, tags=tags,
                                 tags_mode=tags_mode, between=between)
 
-    def _radius_front(self, call, qs, radius, allowed, tags, tags_mode, between, n_probes=None):
-        """knn_brute's early refusals in its order, then the radius', before any device call; the prepared queries
-        (qn, dev) — with n_probes (qn, q_pq, dev)"""
+    def _exact_front(self, call, qs, allowed, tags, tags_mode, between, then=None, bounded=False):
+        """The early refusals every exact call makes, in their order, before any device call: an AllowSet; between=
+        against the index's values (bounded: it is required, and every query bounds a column); tags_mode; then() — the
+        call's own; a list-sharded device index.  -> (qn, q_pq, dev): the queries prepared on a copy, the device index"""
         if isinstance(allowed, AllowSet):
             raise TypeError(f"{call}: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
                             "list position")
+        if bounded and between is None:
+            raise TypeError(f"{call}: between= is required: a pair (lo, hi)")
         if between is not None:
-            self._ranges(between, len(qs))
+            keys = self._ranges(between, len(qs))
+            free = np.flatnonzero(unbounded_queries(keys)) if bounded else ()
+            if len(free):
+                raise ValueError(f"{call}: query {int(free[0])} bounds no column (an unrestricted query is knn_brute's "
+                                 "or query_batch's to answer)")
         if tags is not None:
             tag_mode_of(tags_mode)
-        query_radius(radius, len(qs))
-        if n_probes is not None and int(n_probes) < 1:
-            raise ValueError(f"n_probes: at least 1, got {int(n_probes)}")
+        if then is not None:
+            then()
         dev = self._unsharded_device_index()
-        qn, qp = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
-        return (qn, dev) if n_probes is None else (qn, qp, dev)
+        return self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True)) + (dev,)
+
+    def _radius_front(self, call, qs, radius, allowed, tags, tags_mode, between, n_probes=None):
+        """_exact_front with the radius' own refusals: the radii, then n_probes >= 1"""
+        def then():
+            query_radius(radius, len(qs))
+            if n_probes is not None and int(n_probes) < 1:
+                raise ValueError(f"n_probes: at least 1, got {int(n_probes)}")
+        return self._exact_front(call, qs, allowed, tags, tags_mode, between, then)
 
     def knn_probe(self, qs, k, n_probes, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
                   between=None, return_distances=False, matrix=False):
@@ -2932,19 +2927,12 @@ class IVF:
         groups, where the probed lists hold too few of a group's rows; knn_brute(group=) is the one for large groups,
         query_batch(group=, exact_below=) routes a batch by size.  The other restrictions as knn_brute's; allowed: a
         bool mask of length N or row ids, not an AllowSet.  Not for a list-sharded index."""
-        if isinstance(allowed, AllowSet):
-            raise TypeError("knn_group: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
-                            "list position")
-        if between is not None:
-            self._ranges(between, len(qs))
-        if tags is not None:
-            tag_mode_of(tags_mode)
-        group = query_groups(group, len(qs))
-        if len(group) and int(group.min()) < 0:
-            raise AssertionError("knn_group: group= needs a group id >= 0 for every query (-1, any group, is "
-                                 "knn_brute's or query_batch's to answer)")
-        dev = self._unsharded_device_index()
-        qn, _ = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
+        def then():
+            g = query_groups(group, len(qs))
+            if len(g) and int(g.min()) < 0:
+                raise AssertionError("knn_group: group= needs a group id >= 0 for every query (-1, any group, is "
+                                     "knn_brute's or query_batch's to answer)")
+        qn, _, dev = self._exact_front("knn_group", qs, allowed, tags, tags_mode, between, then)
         return dev.knn_group(qn, k, group, allowed=allowed, exclude=exclude, tags=tags, tags_mode=tags_mode,
                              between=between, return_distances=return_distances)
 
@@ -2958,21 +2946,10 @@ class IVF:
         lists hold too few passing rows; knn_brute(between=) is the one for wide ranges, query_batch(between=,
         exact_below=) routes a batch by length.  The other restrictions as knn_brute's; allowed: a bool mask of length
         N or row ids, not an AllowSet.  Not for a list-sharded index."""
-        if isinstance(allowed, AllowSet):
-            raise TypeError("knn_between: allowed= takes a bool mask of length N or row ids; an AllowSet is laid out by "
-                            "list position")
-        if between is None:
-            raise TypeError("knn_between: between= is required: a pair (lo, hi)")
-        free = np.flatnonzero(unbounded_queries(self._ranges(between, len(qs))))
-        if len(free):
-            raise ValueError(f"knn_between: query {int(free[0])} bounds no column (an unrestricted query is knn_brute's "
-                             "or query_batch's to answer)")
-        if tags is not None:
-            tag_mode_of(tags_mode)
-        if group is not None:
-            group = query_groups(group, len(qs))
-        dev = self._unsharded_device_index()
-        qn, _ = self._prepare(np.array(qs, dtype=np.float32, order="C", copy=True))
+        def then():
+            if group is not None:
+                query_groups(group, len(qs))
+        qn, _, dev = self._exact_front("knn_between", qs, allowed, tags, tags_mode, between, then, bounded=True)
         return dev.knn_between(qn, k, between, allowed=allowed, exclude=exclude, group=group, tags=tags,
                                tags_mode=tags_mode, return_distances=return_distances)
 
