@@ -987,6 +987,23 @@ int tk_index_radius_brute(tk_index *ix, const float *q, int64_t nq, const float 
                           const int64_t *between, int sorted, int count_only, int64_t max_results, int64_t *out_lims,
                           int64_t *out_total);
 int tk_index_radius_fetch(tk_index *ix, int64_t *out_ids, float *out_dist);
+/* tk_index_radius_brute over all rows of a HALF store (TK_DATA_F16) on the f16 matrix cores, any d <= 4096
+ * (radius_matrix.hip).  The arguments, the CSR result, count_only, max_results, sorted and
+ * tk_index_radius_fetch are that call's; the value compared and returned is dist_m, tk_index_knn_brute_matrix's and
+ * tk_index_knn_probe_matrix's, bit for bit — max(0, (|x|^2 + |y|^2) - 2 dot), never negative — so for every k <= 1024
+ * that call's ids and values are the first k entries of this call's list at radius = its k-th value: a negative radius
+ * lists nothing, +inf every passing row.  One pass over the rows counts and keeps the first `cap` keys of every query
+ * in a staging buffer of the index (nq * cap * 8 bytes); only the tiles of 128 queries that hold a longer list are
+ * walked a second time.  stage_cap: 0 = the default capacity (the largest power of two with nq * cap * 8 <= 128 MiB,
+ * at most 16 384), else a capacity in [1, 2^20] with nq * stage_cap * 8 <= 4 GiB — it changes the route a list takes,
+ * never the result.  Refused, in this order and before any device work: a list-sharded index; a float32 / float64
+ * store; a NaN or an infinity in a query; d > 4096; N >= 2^31; a NaN radius; max_results outside [0, 2^31); then the
+ * restrictions' own refusals.  Synchronous. */
+int tk_index_radius_brute_matrix(tk_index *ix, const float *q, int64_t nq, const float *radius,
+                                 const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
+                                 const uint64_t *tags, int tag_mode, const int64_t *between, int sorted,
+                                 int count_only, int64_t max_results, int64_t *out_lims, int64_t *out_total,
+                                 int stage_cap);
 /* Every row within a radius of each query among the rows of the lists the query probes (radius_probe.hip, DESIGN
  * 3.20): FAISS's range_search on an IVF index.  For query i with n_probes = P >= 1:
  *   probes      the index's own coarse stage for P — the row tk_index_top_centers(k = P) gives and the query calls

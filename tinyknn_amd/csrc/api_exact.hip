@@ -282,6 +282,103 @@ extern "C" int tk_index_radius_brute(tk_index *ix, const float *q, int64_t nq, c
     return TK_OK;
 }
 
+// ---------------------------------------------------------------------------
+// tk_index_radius_brute on the f16 matrix cores for a half store, d <= 4096 (radius_matrix.hip): ONE pass
+// counts and stages the first `cap` keys of every query; the counts cross to the host (the lims); the query tiles that
+// hold a longer list are walked once more, every other query's keys are copied out of the stage; then radius_brute's
+// tail.  stage_cap: 0 = the largest power of two with nq * cap * 8 <= RM_STAGE_BUDGET, within [1, RM_STAGE_MOST].
+#define RM_STAGE_BUDGET ((int64_t)128 << 20)
+#define RM_STAGE_MOST (1 << 14)
+extern "C" int tk_index_radius_brute_matrix(tk_index *ix, const float *q, int64_t nq, const float *radius,
+                                            const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
+                                            const uint64_t *tags, int tag_mode, const int64_t *between, int sorted,
+                                            int count_only, int64_t max_results, int64_t *out_lims, int64_t *out_total,
+                                            int stage_cap)
+{
+    IXLOCK(ix);
+    if (ix) ix->rd_total = ix->rp_total = -1;       // whatever this call does, the result of the last one is gone
+    ARGCHECK(ix && ix->have_data, "set_data first");
+    ARGCHECK(!ix->sharded, "list-sharded index: radius_search(matrix=True) is not supported");
+    ARGCHECK(nq >= 0 && out_lims && out_total && (nq == 0 || (q && radius)), "buffers");
+    TRY(pm_check(ix, q, nq));
+    ARGCHECK(ix->d <= 4096, "d <= 4096");
+    ARGCHECK(ix->N < (1ll << 31), "N < 2^31");
+    for (int64_t i = 0; i < nq; i++) ARGCHECK(radius[i] == radius[i], "radius: NaN");
+    ARGCHECK(count_only || (max_results >= 0 && max_results < (1ll << 31)), "0 <= max_results < 2^31");
+    ARGCHECK(stage_cap >= 0 && stage_cap <= (1 << 20) && (int64_t)stage_cap * nq * 8 <= ((int64_t)4 << 30),
+             "stage_cap: 0, or a capacity in [1, 2^20] with nq * stage_cap * 8 <= 4 GiB");
+    TkBruteRestrict r;
+    bool any;
+    TRY(brute_restrict(ix, nq, {allowed_mask, exclude, group, tags, tag_mode, between}, r, any));
+    out_lims[0] = 0;
+    *out_total = 0;
+    if (nq == 0) {
+        if (!count_only) ix->rd_total = 0;
+        return TK_OK;
+    }
+    int cap = stage_cap;
+    if (cap == 0)
+        for (cap = 1; cap < RM_STAGE_MOST && (int64_t)2 * cap * nq * 8 <= RM_STAGE_BUDGET;) cap *= 2;
+    const int64_t n_qt = (nq + 127) / 128;
+    TRY(flush_pending(ix));
+    TRY(ix->br_ynorm.ensure((size_t)(ix->N > 0 ? ix->N : 1) * 4));
+    TRY(ix->br_q.ensure((size_t)nq * ix->d * 4));
+    TRY(ix->rd_radius.ensure((size_t)nq * 4));
+    TRY(ix->rd_count.ensure((size_t)nq * 8 + 4));
+    if (!count_only) TRY(ix->rd_stage.ensure((size_t)nq * cap * 8));
+    HIPCHECK(hipMemcpy(ix->br_q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(ix->rd_radius.p, radius, (size_t)nq * 4, hipMemcpyHostToDevice));
+    PmQueries pq{};
+    TRY(pm_prepare(ix, nq, pq));
+    const TkBruteMatrix mx{pq.xh, pq.xl, pq.xn, pq.xs, pq.dpad};
+    const float *rad = ix->rd_radius.as<float>();
+    float *yn = ix->br_ynorm.as<float>();
+    int *count = ix->rd_count.as<int>(), *slots = count + nq, *err = slots + nq;
+    unsigned long long *stage = count_only ? nullptr : ix->rd_stage.as<unsigned long long>();
+    const TkBruteRestrict *rp = any ? &r : nullptr;
+    if (ix->N > 0) tk_launch_brute_half_norms(ix->data.p, ix->N, ix->d, yn, nullptr);
+    if (tk_launch_radius_matrix_count(mx, nq, ix->d, ix->data.p, ix->N, yn, rad, count, stage, cap, rp, nullptr))
+        return fail(TK_ERR_HIP, "tk_launch_radius_matrix_count: unsupported size");
+    HIPCHECK(hipGetLastError());
+    bool fill;
+    TRY(radius_lims(ix, count, nq, count_only, max_results, out_lims, out_total, fill));
+    if (!fill) {
+        if (!count_only) ix->rd_total = 0;
+        return TK_OK;
+    }
+    const int64_t total = *out_total;
+    // the query tiles that hold a list longer than the stage: their list, and a flag per tile
+    std::vector<int> tiles((size_t)(2 * n_qt), 0);
+    int n_tiles = 0;
+    for (int64_t t = 0; t < n_qt; t++) {
+        bool over = false;
+        for (int64_t i = t * 128; i < nq && i < (t + 1) * 128 && !over; i++) over = out_lims[i + 1] - out_lims[i] > cap;
+        if (over) {
+            tiles[(size_t)n_tiles++] = (int)t;
+            tiles[(size_t)(n_qt + t)] = 1;
+        }
+    }
+    const int *dev_tiles;
+    TRY(host_upload(ix->rd_tiles, tiles.data(), tiles.size(), dev_tiles));
+    TRY(ix->rd_dist.ensure((size_t)total * 4));
+    unsigned long long *keys = ix->rd_keys.as<unsigned long long>(), *alt = ix->rd_alt.as<unsigned long long>();
+    if (tk_launch_radius_matrix_fill(mx, nq, ix->d, ix->data.p, ix->N, yn, rad, count, stage, cap, dev_tiles, n_tiles,
+                                     dev_tiles + n_qt, ix->rd_off.as<int64_t>(), slots, keys, err, rp, nullptr))
+        return fail(TK_ERR_HIP, "tk_launch_radius_matrix_fill: unsupported size");
+    HIPCHECK(hipGetLastError());
+    TRY(radius_passes_agree(err));
+    if (sorted) {
+        TRY(radius_sort(ix, keys, alt, total, nq));
+        std::swap(keys, alt);           // the sorted keys; the ids go where the unsorted ones were
+    }
+    tk_launch_radius_decode(keys, total, (int64_t *)alt, ix->rd_dist.as<float>(), nullptr);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    ix->rd_ids_alt = alt == ix->rd_alt.as<unsigned long long>();
+    ix->rd_total = total;
+    return TK_OK;
+}
+
 extern "C" int tk_index_radius_fetch(tk_index *ix, int64_t *out_ids, float *out_dist)
 {
     IXLOCK(ix);

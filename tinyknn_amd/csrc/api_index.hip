@@ -89,7 +89,7 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->local_chunk_off, &ix->rot_t, &ix->br_ynorm, &ix->br_vals, &ix->br_tau,
                       &ix->br_cand, &ix->br_count, &ix->br_out, &ix->br_q, &ix->br_sample, &ix->br_dist, &ix->br_mask,
                       &ix->br_exclude, &ix->br_group, &ix->br_tags, &ix->br_ranges, &ix->rd_radius, &ix->rd_count,
-                      &ix->rd_off, &ix->rd_keys, &ix->rd_alt, &ix->rd_dist, &ix->rd_tmp, &ix->pl_probes, &ix->pl_len, &ix->pl_off, &ix->pl_scan,
+                      &ix->rd_off, &ix->rd_keys, &ix->rd_alt, &ix->rd_dist, &ix->rd_tmp, &ix->rd_stage, &ix->rd_tiles, &ix->pl_probes, &ix->pl_len, &ix->pl_off, &ix->pl_scan,
                       &ix->rp_bitmap, &ix->rp_rows, &ix->rp_ids, &ix->rp_dist, &ix->replay_counters,
                       &ix->pe_lists, &ix->pe_pairs,
                       &ix->pe_tiles, &ix->pe_keys, &ix->pe_out, &ix->pm_xh, &ix->pm_xl, &ix->pm_xn,

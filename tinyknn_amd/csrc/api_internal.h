@@ -270,6 +270,9 @@ struct tk_index {
     // other half of the sort (keys in one, ids in the other), the part values, the sort's work memory.  rd_total >= 0:
     // a result is held for tk_index_radius_fetch, its ids in rd_alt (rd_ids_alt) or rd_keys
     DevBuf rd_radius, rd_count, rd_off, rd_keys, rd_alt, rd_dist, rd_tmp;
+    // tk_index_radius_brute_matrix (radius_matrix.hip): the first cap keys of every query (nq, cap), and the query
+    // tiles to refill: their list and a flag per tile
+    DevBuf rd_stage, rd_tiles;
     int64_t rd_total = -1;
     bool rd_ids_alt = false;
     // tk_index_radius_probe and tk_index_knn_probe (probe_job.h: probe_lengths): the call's probes (nq, kc) int64, the

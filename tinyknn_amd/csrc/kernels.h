@@ -596,3 +596,16 @@ int tk_launch_radius_fill(const float *X, int64_t nq, int d, const float *Y, int
 int tk_launch_radius_sort(void *tmp, size_t *tmp_bytes, const unsigned long long *keys_in, unsigned long long *keys_out,
                           int64_t total, int64_t nq, const int64_t *offsets, hipStream_t s);
 void tk_launch_radius_decode(const unsigned long long *keys, int64_t n, int64_t *ids, float *dist, hipStream_t s);
+// ---- ... over all rows of a half store on the f16 matrix cores (radius_matrix.hip) ----
+// _count: the one pass over Y (N, d) half that counts (count (nq), zeroed there) and, where stage (nq, cap) is given,
+// keeps the first cap keys of every query; _fill: the refill of the query tiles named (tiles (n_tiles) ascending,
+// refilled (ceil(nq / 128)) 1 for each) into keys at offset, guarded by count, and the copy of every other query's
+// staged keys; err != 0 afterwards: the passes disagreed.  -1 on unsupported sizes.
+int tk_launch_radius_matrix_count(const TkBruteMatrix &mx, int64_t nq, int d, const void *Y, int64_t N,
+                                  const float *ynorm2, const float *radius, int *count, unsigned long long *stage,
+                                  int cap, const TkBruteRestrict *r, hipStream_t s);
+int tk_launch_radius_matrix_fill(const TkBruteMatrix &mx, int64_t nq, int d, const void *Y, int64_t N,
+                                 const float *ynorm2, const float *radius, const int *count,
+                                 const unsigned long long *stage, int cap, const int *tiles, int n_tiles,
+                                 const int *refilled, const int64_t *offset, int *slots, unsigned long long *keys,
+                                 int *err, const TkBruteRestrict *r, hipStream_t s);

@@ -1480,8 +1480,12 @@ class DeviceIndex:
         """_brute_restrictions' arrays as the C ABI takes them (NULL for None; the caller keeps the arrays alive)"""
         return [a if isinstance(a, int) else (None if a is None else a.ctypes.data) for a in restrict]
 
+    # tk_index_radius_brute_matrix's stage_cap: keys a query's list may hold in the staging buffer of the one-pass
+    # route (0: the library's default).  It changes the route a list takes, never the result.
+    RADIUS_MATRIX_STAGE = 0
+
     def radius_brute(self, qn, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                     between=None, sort=True, max_results=None):
+                     between=None, sort=True, max_results=None, matrix=False):
         """Every row within a radius of each normalised query, exactly (tk_index_radius_brute): CSR
         (lims, ids, part) — lims (nq + 1,) int64, query i's hits ids[lims[i]:lims[i + 1]] int64 with their float32
         `part` values beside them.  Row j is a hit of query i iff it passes the query's restrictions (allowed /
@@ -1494,7 +1498,12 @@ class DeviceIndex:
         max_results (default 1 << 26, < 2**31): a total above it raises ValueError naming the true total — nothing is
         returned, no list is ever cut, and the index stays usable.  Float32 vectors, d <= 128; not for a list-sharded
         index.  The vectors of removed rows stay in HBM, as for knn_brute: allowed= with the mask of the surviving
-        rows is the truth after remove()."""
+        rows is the truth after remove().
+        matrix=True (tk_index_radius_brute_matrix; store="float16" only, finite queries, d <= 4096 — else
+        AssertionError): all rows of a half store on the f16 matrix cores.  The values are knn_brute_dist(matrix=True)'s
+        dist_m (never negative: a negative radius lists nothing) bit for bit, so that call's ids and values are the
+        first k entries of the list at radius = its k-th value.  One pass over the rows wherever the lists are short:
+        RADIUS_MATRIX_STAGE."""
         qn, radius, restrict = self._radius_args("radius_search", qn, radius, allowed, exclude, group, tags, tags_mode,
                                                  between)
         max_results = (1 << 26) if max_results is None else int(max_results)
@@ -1504,9 +1513,12 @@ class DeviceIndex:
         lims = np.zeros(nq + 1, dtype=np.int64)
         total = np.zeros(1, dtype=np.int64)
         lib = _lib.lib()
-        rc = lib.tk_index_radius_brute(
+        call, more = lib.tk_index_radius_brute, ()
+        if matrix:
+            call, more = lib.tk_index_radius_brute_matrix, (int(self.RADIUS_MATRIX_STAGE),)
+        rc = call(
             self._h, _lib.ptr(qn, _lib._f32p), nq, _lib.ptr(radius, _lib._f32p), *self._host_pointers(restrict),
-            int(bool(sort)), 0, max_results, _lib.ptr(lims, _lib._i64p), _lib.ptr(total, _lib._i64p))
+            int(bool(sort)), 0, max_results, _lib.ptr(lims, _lib._i64p), _lib.ptr(total, _lib._i64p), *more)
         if rc == -1 and int(total[0]) > max_results:
             raise ValueError(f"radius_search: {int(total[0])} rows lie within the radii, more than max_results = "
                              f"{max_results}; nothing is returned (raise max_results, or ask radius_count first)")
@@ -1517,17 +1529,20 @@ class DeviceIndex:
         return lims, ids, part
 
     def radius_count(self, qn, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                     between=None):
+                     between=None, matrix=False):
         """How many rows radius_brute would list per query: (nq,) int64, from the count pass alone (one pass over the
-        rows instead of two and no sort).  No limit: the counts are summed in int64."""
+        rows instead of two and no sort).  No limit: the counts are summed in int64.  matrix=True: radius_brute(matrix=
+        True)'s counts, from its tile pass with nothing stored."""
         qn, radius, restrict = self._radius_args("radius_count", qn, radius, allowed, exclude, group, tags, tags_mode,
                                                  between)
         nq = len(qn)
         lims = np.zeros(nq + 1, dtype=np.int64)
         total = np.zeros(1, dtype=np.int64)
-        _lib.check(_lib.lib().tk_index_radius_brute(
+        lib = _lib.lib()
+        call, more = (lib.tk_index_radius_brute_matrix, (0,)) if matrix else (lib.tk_index_radius_brute, ())
+        _lib.check(call(
             self._h, _lib.ptr(qn, _lib._f32p), nq, _lib.ptr(radius, _lib._f32p), *self._host_pointers(restrict),
-            0, 1, 0, _lib.ptr(lims, _lib._i64p), _lib.ptr(total, _lib._i64p)))
+            0, 1, 0, _lib.ptr(lims, _lib._i64p), _lib.ptr(total, _lib._i64p), *more))
         return np.diff(lims)
 
     # queries per tk_index_radius_probe call: a larger batch is cut here and its CSR parts joined (a part whose
@@ -2822,8 +2837,8 @@ class IVF:
         return call(qn, k, allowed=allowed, exclude=exclude, group=group, tags=tags, tags_mode=tags_mode, between=between,
                     matrix=matrix)
 
-    def radius_search(self, qs, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                      between=None, sort=True, max_results=None, n_probes=None):
+    def radius_search(self, qs, radius, matrix=False, *, allowed=None, exclude=None, group=None, tags=None,
+                      tags_mode="any", between=None, sort=True, max_results=None, n_probes=None):
         """Every row of IVF.data within a radius of each raw query, exactly, under the restrictions of query_batch
         (DeviceIndex.radius_brute on the prepared queries): CSR (lims, ids, part) — lims (nq + 1,)
         int64, query i's hits ids[lims[i]:lims[i + 1]] (int64) with their float32 `part` values, knn_brute's, beside
@@ -2845,27 +2860,35 @@ class IVF:
         on float64 vectors — compared with float32(radius) inclusively.  It is not `part`: the two round differently
         and agree exactly on integer data, so a row on the boundary of one call may be outside the other's.  Every
         store (float32, float16, float64 vectors) and d <= 4096.  n_probes=None is the call over all rows, as it
-        always was."""
+        always was.
+        matrix=True (DeviceIndex.radius_brute(matrix=True)): the call over all rows for a half store
+        (store="float16") of any d <= 4096, on the f16 matrix cores: CSR (lims, ids, dist_m), dist_m the value
+        knn_brute(matrix=True) ranks by, bit for bit — that call's ids are the first k entries of the list at radius =
+        its k-th value.  Not with n_probes= (ValueError)."""
+        if matrix and n_probes is not None:
+            raise ValueError("radius_search: matrix=True is the search over all rows; it cannot be combined with n_probes=")
         if n_probes is not None:
             qn, qp, dev = self._radius_front("radius_search", qs, radius, allowed, tags, tags_mode, between, n_probes)
             return dev.radius_probe(qn, qp, radius, n_probes, allowed=allowed, exclude=exclude, group=group, tags=tags,
                                     tags_mode=tags_mode, between=between, sort=sort, max_results=max_results)
         qn, _, dev = self._radius_front("radius_search", qs, radius, allowed, tags, tags_mode, between)
         return dev.radius_brute(qn, radius, allowed=allowed, exclude=exclude, group=group, tags=tags,
-                                tags_mode=tags_mode, between=between, sort=sort, max_results=max_results)
+                                tags_mode=tags_mode, between=between, sort=sort, max_results=max_results, matrix=matrix)
 
-    def radius_count(self, qs, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                     between=None, n_probes=None):
+    def radius_count(self, qs, radius, matrix=False, *, allowed=None, exclude=None, group=None, tags=None,
+                     tags_mode="any", between=None, n_probes=None):
         """How many rows radius_search would list per raw query: (nq,) int64, from its count pass alone — no limit
         (the totals are summed in int64), half the work and no sort.  Arguments as radius_search's, n_probes=
-        included (DeviceIndex.radius_probe_count)."""
+        (DeviceIndex.radius_probe_count) and matrix= (not both: ValueError) included."""
+        if matrix and n_probes is not None:
+            raise ValueError("radius_count: matrix=True is the search over all rows; it cannot be combined with n_probes=")
         if n_probes is not None:
             qn, qp, dev = self._radius_front("radius_count", qs, radius, allowed, tags, tags_mode, between, n_probes)
             return dev.radius_probe_count(qn, qp, radius, n_probes, allowed=allowed, exclude=exclude, group=group,
                                           tags=tags, tags_mode=tags_mode, between=between)
         qn, _, dev = self._radius_front("radius_count", qs, radius, allowed, tags, tags_mode, between)
         return dev.radius_count(qn, radius, allowed=allowed, exclude=exclude, group=group, tags=tags,
-                                tags_mode=tags_mode, between=between)
+                                tags_mode=tags_mode, between=between, matrix=matrix)
 
     def _exact_front(self, call, qs, allowed, tags, tags_mode, between, then=None, bounded=False):
         """The early refusals every exact call makes, in their order, before any device call: an AllowSet; between=
