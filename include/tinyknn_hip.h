@@ -963,6 +963,19 @@ int tk_index_knn_brute_ex(tk_index *ix, const float *q, int64_t nq, int k, const
 int tk_index_knn_brute_matrix(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
                               const int64_t *exclude, const int32_t *group, const uint64_t *tags, int tag_mode,
                               const int64_t *between, int64_t *out_ids, float *out_dist);
+/* tk_index_knn_brute_ex for a float32 index of any d <= 4096 (brute_wide.hip): the k rows with the
+ * smallest (part, row) among the rows that pass the restrictions, arguments and padding as tk_index_knn_brute_ex's.
+ * part is that call's value bit for bit — (|x|^2 + |y|^2) - acc, the norms in numpy's einsum order, acc one float32
+ * accumulator of v_mfma_f32_32x32x2_f32 over (2 x) y, k ascending from 0 over all of d — so at d <= 128 both calls
+ * return the same bytes, and beyond it the FMA chain is carried on: d is walked in slabs of 32 floats through LDS
+ * instead of being held there whole.  out_dist (or NULL): part.  Sample, segments, candidate lists, the overflow retry
+ * and the selection are tk_index_knn_brute_ex's.
+ * TK_ERR_ARG before any device work: float64 or half vectors ("needs store=\"float32\""; a half index has
+ * tk_index_knn_brute_matrix), d > 4096, k outside [1, min(1024, N)], N >= 2^31, a list-sharded index.
+ * tk_index_knn_brute(_ex) itself is unchanged: d <= 128, its own tile kernel. */
+int tk_index_knn_brute_wide(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
+                            const int64_t *exclude, const int32_t *group, const uint64_t *tags, int tag_mode,
+                            const int64_t *between, int64_t *out_ids, float *out_dist);
 /* Every row within a radius of each query, exactly (radius.hip): row j is a hit of query i iff it passes
  * the query's restrictions — allowed_mask / exclude / group / tags, tag_mode / between exactly as
  * tk_index_knn_brute_ex takes them, host arrays, NULL: not given — and part(i, j) <= radius[i], compared in float32,

@@ -45,6 +45,9 @@ PROBE_MATRIX_DS = 112
 # tk_index_knn_brute_matrix's tile kernel (brute_matrix.hip: BM_QT, BM_RB, BM_DS)
 BRUTE_MATRIX_TILE = (128, 128)
 BRUTE_MATRIX_DS = 64
+# tk_index_knn_brute_wide's tile kernel (brute_wide.hip: BW_QT, BW_RB, BW_DS): its tile and the floats of a slab
+BRUTE_WIDE_TILE = (128, 128)
+BRUTE_WIDE_DS = 32
 # tk_index_last_replay: the forms of a batch's heap replay (TK_REPLAY_*)
 REPLAY_PAIR, REPLAY_LANES, REPLAY_PACKED_DISTINCT, REPLAY_LANES_TWIN, REPLAY_LANES_DEDUPE, REPLAY_PACKED, REPLAY_GENERAL = range(7)
 REPLAY_NAMES = ("pair", "lanes", "packed_distinct", "lanes_twin", "lanes_dedupe", "packed", "general")
@@ -244,6 +247,8 @@ SIGNATURES = {
                                         C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),
     "tk_index_knn_brute_matrix": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),
+    "tk_index_knn_brute_wide": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),
     "tk_index_radius_brute": (C.c_int, [C.c_void_p, _f32p, C.c_int64, _f32p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, _i64p, _i64p]),
     "tk_index_radius_brute_matrix": (C.c_int, [C.c_void_p, _f32p, C.c_int64, _f32p, C.c_void_p, C.c_void_p, C.c_void_p,

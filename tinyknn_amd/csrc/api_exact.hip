@@ -10,8 +10,10 @@
 // overflow, the largest multiple of 32 not above cap - k (a segment appends at most `seg` rows to at most k kept ones).
 // matrix: the rows are half and the tiles run on the f16 matrix cores (brute_matrix.hip); the values are
 // §3.22's dist_m and d may reach 4096.  false: float32 rows, d <= 128, numpy's part values.
+// wide (not beside matrix): float32 rows through the slabbed tile kernel (brute_wide.hip): the same part
+// values and d may reach 4096.
 static int knn_brute(tk_index *ix, const float *q, int64_t nq, int k, const TkBruteRestrict *r, bool retry,
-                     int64_t *out_ids, float *out_dist, bool matrix = false)
+                     int64_t *out_ids, float *out_dist, bool matrix = false, bool wide = false)
 {
     ARGCHECK(ix && ix->have_data, "set_data first");
     if (matrix) {           // (tk_index_knn_brute_matrix has made pm_check's refusals)
@@ -20,7 +22,8 @@ static int knn_brute(tk_index *ix, const float *q, int64_t nq, int k, const TkBr
         ARGCHECK(ix->data_dtype != TK_DATA_F64, "float32 vectors only");
         ARGCHECK(ix->data_dtype != TK_DATA_F16, "knn_brute is the ground truth on float32 vectors: this index stores "
                                                 "them as half (store=\"float16\"); ask a float32 index");
-        ARGCHECK(ix->d <= 128, "d <= 128");
+        if (wide) ARGCHECK(ix->d <= 4096, "d <= 4096");
+        else ARGCHECK(ix->d <= 128, "d <= 128");
     }
     ARGCHECK(nq >= 0 && q && out_ids, "buffers");
     ARGCHECK(k >= 1 && k <= 1024 && k <= ix->N, "1 <= k <= min(1024, N)");
@@ -45,15 +48,22 @@ static int knn_brute(tk_index *ix, const float *q, int64_t nq, int k, const TkBr
     PmQueries pq{};
     if (matrix) TRY(pm_prepare(ix, nq, pq));
     const TkBruteMatrix planes{pq.xh, pq.xl, pq.xn, pq.xs, pq.dpad}, *mx = matrix ? &planes : nullptr;
+    if (wide) {
+        TRY(ix->bw_x2.ensure((size_t)nq * tk_brute_wide_dq(ix->d) * 4));
+        TRY(ix->bw_xn.ensure((size_t)nq * 4));
+        tk_launch_brute_wide_prepare(X, nq, ix->d, ix->bw_x2.as<float>(), ix->bw_xn.as<float>(), nullptr);
+    }
+    const TkBruteWide doubled{ix->bw_x2.as<float>(), ix->bw_xn.as<float>(), tk_brute_wide_dq(ix->d)},
+        *wd = wide ? &doubled : nullptr;
     if (tk_launch_brute_tau(X, nq, ix->d, Y, ix->N, k, ix->br_ynorm.as<float>(), ix->br_vals.as<float>(), ns, tau,
-                            ix->br_sample.as<float>(), r, nullptr, mx))
+                            ix->br_sample.as<float>(), r, nullptr, mx, wd))
         return fail(TK_ERR_HIP, "tk_launch_knn_brute: unsupported size / LDS attribute");
     if (retry) HIPCHECK(hipMemcpyAsync(tau0, tau, (size_t)nq * 4, hipMemcpyDeviceToDevice, nullptr));
     int64_t seg = tk_brute_segment(k, ns, cap);
     for (int attempt = 0;; attempt++) {
         if (tk_launch_brute_select(X, nq, ix->d, Y, ix->N, k, ix->br_ynorm.as<float>(), tau,
                                    ix->br_cand.as<unsigned long long>(), cap, ix->br_count.as<int>(), overflow,
-                                   ix->br_out.as<int64_t>(), dist, seg, r, nullptr, mx))
+                                   ix->br_out.as<int64_t>(), dist, seg, r, nullptr, mx, wd))
             return fail(TK_ERR_HIP, "tk_launch_knn_brute: unsupported size / LDS attribute");
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipDeviceSynchronize());
@@ -166,6 +176,30 @@ extern "C" int tk_index_knn_brute_matrix(tk_index *ix, const float *q, int64_t n
     TRY(brute_restrict(ix, nq, {allowed_mask, exclude, group, tags, tag_mode, between}, r, any));
     if (any && nq == 0) return TK_OK;
     return knn_brute(ix, q, nq, k, any ? &r : nullptr, true, out_ids, out_dist, true);
+}
+
+// tk_index_knn_brute_ex for a float32 store of any d <= 4096: the same part values from the slabbed tile kernel
+// (brute_wide.hip)
+extern "C" int tk_index_knn_brute_wide(tk_index *ix, const float *q, int64_t nq, int k, const uint8_t *allowed_mask,
+                                       const int64_t *exclude, const int32_t *group, const uint64_t *tags,
+                                       int tag_mode, const int64_t *between, int64_t *out_ids, float *out_dist)
+{
+    IXLOCK(ix);
+    ARGCHECK(ix && ix->have_data, "set_data first");
+    ARGCHECK(!ix->sharded, "list-sharded index: knn_brute(wide=True) is not supported");
+    ARGCHECK(nq >= 0 && (nq == 0 || q), "buffers");
+    // (knn_brute's own, here in front of the restriction's uploads: nothing reaches the device for a refused call)
+    ARGCHECK(ix->data_dtype != TK_DATA_F64, "wide=True needs store=\"float32\": this index stores float64 vectors");
+    ARGCHECK(ix->data_dtype != TK_DATA_F16, "wide=True needs store=\"float32\": this index stores its vectors as half "
+                                            "(store=\"float16\"); its search over all rows is matrix=True");
+    ARGCHECK(ix->d <= 4096, "d <= 4096");
+    ARGCHECK(k >= 1 && k <= 1024 && k <= ix->N, "1 <= k <= min(1024, N)");
+    ARGCHECK(ix->N < (1ll << 31), "N < 2^31");
+    TkBruteRestrict r;
+    bool any;
+    TRY(brute_restrict(ix, nq, {allowed_mask, exclude, group, tags, tag_mode, between}, r, any));
+    if (any && nq == 0) return TK_OK;
+    return knn_brute(ix, q, nq, k, any ? &r : nullptr, true, out_ids, out_dist, false, true);
 }
 
 // ---------------------------------------------------------------------------

@@ -93,6 +93,7 @@ extern "C" void tk_index_destroy(tk_index *ix)
                       &ix->rp_bitmap, &ix->rp_rows, &ix->rp_ids, &ix->rp_dist, &ix->replay_counters,
                       &ix->pe_lists, &ix->pe_pairs,
                       &ix->pe_tiles, &ix->pe_keys, &ix->pe_out, &ix->pm_xh, &ix->pm_xl, &ix->pm_xn,
+                      &ix->bw_x2, &ix->bw_xn,
                       &ix->twin_list, &ix->twin_off, &ix->rp_twin_list, &ix->rp_twin_off, &ix->row_pos_off, &ix->row_pos, &ix->groups.by_row,
                       &ix->groups.table, &ix->tags.by_row, &ix->tags.table, &ix->values.by_row,
                       &ix->values.table, &ix->groups.span_rows, &ix->groups.span_gid, &ix->groups.span_off,

@@ -295,6 +295,8 @@ struct tk_index {
     // tk_index_knn_probe_matrix (probe_matrix.hip): the call's queries as two half planes (nq, dpad) each, and per query
     // its float32 self-dot and the scale 2^-e
     DevBuf pm_xh, pm_xl, pm_xn;
+    // tk_index_knn_brute_wide (brute_wide.hip): the call's queries doubled, (nq, d rounded up to 4) floats, and |x|^2
+    DevBuf bw_x2, bw_xn;
     DevBuf gx_begin, gx_len;                                                        // tk_index_knn_group: a query's span
     DevBuf gx_col;                                                                  // tk_index_knn_between: ... and its column
     int rot_d_pad = 0;

@@ -335,15 +335,21 @@ static int brute_attrs()
 
 // One launch of the tile kernel over `cols` columns: enough workgroups for the chip (the rows of Y are split when
 // there are few query tiles), the restricted form with its queries' attributes behind the tiles in LDS.
-// mx: half rows, brute_matrix.hip's tile kernel instead.
+// mx: half rows, brute_matrix.hip's tile kernel instead.  wd: float32 rows of any d <= 4096, brute_wide.hip's.
 template <int MODE>
 static void brute_tiles(const float *X, int64_t nq, int d, const float *Y, const float *ynorm2, int64_t cols,
                         float *vals, const float *tau, unsigned long long *cand, int cap, int *count, int64_t j_base,
-                        int64_t j_stride, const TkBruteRestrict *r, hipStream_t s, const TkBruteMatrix *mx)
+                        int64_t j_stride, const TkBruteRestrict *r, hipStream_t s, const TkBruteMatrix *mx,
+                        const TkBruteWide *wd)
 {
     if (mx) {
         tk_launch_brute_matrix_tiles(MODE, *mx, nq, d, Y, ynorm2, cols, vals, tau, cand, cap, count, j_base, j_stride,
                                      r, s);
+        return;
+    }
+    if (wd) {
+        tk_launch_brute_wide_tiles(MODE, *wd, nq, d, Y, ynorm2, cols, vals, tau, cand, cap, count, j_base, j_stride, r,
+                                   s);
         return;
     }
     const int KT = (d + 1) / 2;
@@ -364,12 +370,13 @@ static void brute_tiles(const float *X, int64_t nq, int d, const float *Y, const
 // X (nq, d), Y (N, d) float32 on the device, d <= 128, N < 2^31; ynorm2 (N), vals (nq * ns), tau (nq), sample
 // (ns * (d + 1)) floats are the caller's.  ns <= TK_BR_SORT, k <= ns <= N.
 // mx: Y (N, d) half, d <= 4096; the sample's rows are halfs at the head of the same buffer, their norms where they were.
+// wd: d <= 4096, everything else as without it.
 int tk_launch_brute_tau(const float *X, int64_t nq, int d, const float *Y, int64_t N, int k, float *ynorm2,
                         float *vals, int64_t ns, float *tau, float *sample, const TkBruteRestrict *r, hipStream_t s,
-                        const TkBruteMatrix *mx)
+                        const TkBruteMatrix *mx, const TkBruteWide *wd)
 {
     if (nq == 0) return 0;
-    if (d > (mx ? 4096 : 128) || ns > TK_BR_SORT || k > ns || ns > N || brute_attrs()) return -1;
+    if ((mx && wd) || d > (mx || wd ? 4096 : 128) || ns > TK_BR_SORT || k > ns || ns > N || brute_attrs()) return -1;
     // tau from a strided sample of the whole matrix (its rows are rows of Y: tau >= the true
     // k-th smallest part, bit for bit the same arithmetic)
     float *snorm = sample + (size_t)ns * d;
@@ -383,7 +390,7 @@ int tk_launch_brute_tau(const float *X, int64_t nq, int d, const float *Y, int64
                            N / ns, sample);
         hipLaunchKernelGGL(row_norms_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, sample, ns, d, snorm);
     }
-    brute_tiles<0>(X, nq, d, sample, snorm, ns, vals, nullptr, nullptr, 0, nullptr, 0, N / ns, r, s, mx);
+    brute_tiles<0>(X, nq, d, sample, snorm, ns, vals, nullptr, nullptr, 0, nullptr, 0, N / ns, r, s, mx, wd);
     hipLaunchKernelGGL(brute_select_kernel<0>, dim3((unsigned)nq), dim3(1024), (size_t)TK_BR_SORT * 8, s,
                        vals, ns, nullptr, 0, nullptr, k, tau, nullptr, nullptr, nullptr);
     return 0;
@@ -394,17 +401,17 @@ int tk_launch_brute_tau(const float *X, int64_t nq, int d, const float *Y, int64
 int tk_launch_brute_select(const float *X, int64_t nq, int d, const float *Y, int64_t N, int k, const float *ynorm2,
                            float *tau, unsigned long long *cand, int cap, int *count, int *overflow, int64_t *out,
                            float *out_dist, int64_t seg, const TkBruteRestrict *r, hipStream_t s,
-                           const TkBruteMatrix *mx)
+                           const TkBruteMatrix *mx, const TkBruteWide *wd)
 {
     if (nq == 0) return 0;
-    if (d > (mx ? 4096 : 128) || cap > TK_BR_SORT || 2 * k > cap || seg < 32 || seg % 32 || brute_attrs()) return -1;
+    if ((mx && wd) || d > (mx || wd ? 4096 : 128) || cap > TK_BR_SORT || 2 * k > cap || seg < 32 || seg % 32 || brute_attrs()) return -1;
     (void)hipMemsetAsync(count, 0, (size_t)nq * 4, s);
     (void)hipMemsetAsync(overflow, 0, 4, s);
     const size_t row_bytes = (size_t)d * (mx ? 2 : 4);
     for (int64_t s0 = 0; s0 < N; s0 += seg) {
         const int64_t m = N - s0 < seg ? N - s0 : seg;
         brute_tiles<1>(X, nq, d, (const float *)((const char *)Y + s0 * row_bytes), ynorm2 + s0, m, nullptr, tau, cand,
-                       cap, count, s0, 1, r, s, mx);
+                       cap, count, s0, 1, r, s, mx, wd);
         hipLaunchKernelGGL(brute_select_kernel<1>, dim3((unsigned)nq), dim3(1024), (size_t)TK_BR_SORT * 8, s,
                            nullptr, 0, cand, cap, count, k, tau, out, overflow, out_dist);
     }

@@ -569,14 +569,29 @@ struct TkBruteMatrix {
     const float *xn, *xs;           // |x|^2 and 2^-e
     int dpad;                       // d rounded up to 16
 };
+// wd (or NULL; not beside mx): float32 rows of any d <= 4096 through brute_wide.hip's slabbed tile kernel
+// — the same part values, bit for bit; X is not read (the queries are wd's doubled copy), everything else is NULL's.
+struct TkBruteWide {
+    const float *x2;                // tk_launch_brute_wide_prepare's 2 x, (nq, dq) floats, zeros behind d
+    const float *xn;                // |x|^2 in numpy's einsum order
+    int dq;                         // tk_brute_wide_dq(d)
+};
+static inline int tk_brute_wide_dq(int d) { return (d + 3) / 4 * 4; }   // d in whole 16-byte pieces
 int64_t tk_brute_segment(int k, int64_t ns, int cap);
 int tk_launch_brute_tau(const float *X, int64_t nq, int d, const float *Y, int64_t N, int k, float *ynorm2,
                         float *vals, int64_t ns, float *tau, float *sample, const TkBruteRestrict *r, hipStream_t s,
-                        const TkBruteMatrix *mx = nullptr);
+                        const TkBruteMatrix *mx = nullptr, const TkBruteWide *wd = nullptr);
 int tk_launch_brute_select(const float *X, int64_t nq, int d, const float *Y, int64_t N, int k, const float *ynorm2,
                            float *tau, unsigned long long *cand, int cap, int *count, int *overflow, int64_t *out,
                            float *out_dist, int64_t seg, const TkBruteRestrict *r, hipStream_t s,
-                           const TkBruteMatrix *mx = nullptr);
+                           const TkBruteMatrix *mx = nullptr, const TkBruteWide *wd = nullptr);
+// brute_wide.hip: the queries of a wide call once (X (nq, d) -> x2 (nq, dq), xn (nq)), and one launch of
+// brute_wide_tiles_kernel<mode, r != NULL> over `cols` columns (the arguments of brute.hip's brute_tiles)
+void tk_launch_brute_wide_prepare(const float *X, int64_t nq, int d, float *x2, float *xn, hipStream_t s);
+void tk_launch_brute_wide_tiles(int mode, const TkBruteWide &wd, int64_t nq, int d, const float *Y,
+                                const float *ynorm2, int64_t cols, float *vals, const float *tau,
+                                unsigned long long *cand, int cap, int *count, int64_t j_base, int64_t j_stride,
+                                const TkBruteRestrict *r, hipStream_t s);
 // brute_matrix.hip, for the two halves above: the half forms of row_norms_kernel and sample_rows_kernel, and one launch
 // of brute_matrix_tiles_kernel<mode, r != NULL> over `cols` columns (the arguments of brute.hip's brute_tiles)
 void tk_launch_brute_half_norms(const void *Y, int64_t n, int d, float *out, hipStream_t s);

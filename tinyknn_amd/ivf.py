@@ -1386,8 +1386,8 @@ class DeviceIndex:
             int(pass_1 or 0), _lib.ptr(out, _lib._i64p)))
         return out
 
-    def knn_brute(self, qn, k, matrix=False, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                  between=None):
+    def knn_brute(self, qn, k, matrix=False, wide=False, *, allowed=None, exclude=None, group=None, tags=None,
+                  tags_mode="any", between=None):
         """Exact k nearest rows of IVF.data for normalised queries (ground truth of recall;
         tk_index_knn_brute: f32 MFMA, numpy's distances bit for bit), ascending.  Float32 vectors only:
         refused on a float64 and on a half index.
@@ -1400,33 +1400,41 @@ class DeviceIndex:
         With nothing given the call is tk_index_knn_brute's.  The values the rows were ranked by: knn_brute_dist.
         matrix=True (tk_index_knn_brute_matrix; store="float16" only, finite queries, d <= 4096 — else
         AssertionError): the search over all rows of a half store on the f16 matrix cores, ranked by knn_probe(matrix=
-        True)'s dist_m — the same bytes as that call with every list probed, within its bound B of the real distance."""
-        return self._knn_brute(qn, k, False, allowed, exclude, group, tags, tags_mode, between, matrix)
+        True)'s dist_m — the same bytes as that call with every list probed, within its bound B of the real distance.
+        wide=True (tk_index_knn_brute_wide; store="float32" only, d <= 4096 — else AssertionError; not
+        beside matrix=True: ValueError): the same part values from a tile kernel that walks d in slabs, so a float32
+        index wider than 128 dimensions has its ground truth; at d <= 128 the bytes of the default call."""
+        return self._knn_brute(qn, k, False, allowed, exclude, group, tags, tags_mode, between, matrix, wide)
 
-    def knn_brute_dist(self, qn, k, matrix=False, *, allowed=None, exclude=None, group=None, tags=None,
+    def knn_brute_dist(self, qn, k, matrix=False, wide=False, *, allowed=None, exclude=None, group=None, tags=None,
                        tags_mode="any", between=None):
         """knn_brute's ids and, beside each, the float32 `part` value it was ranked by: (ids, part), part = (|q|^2 +
         |y|^2) - 2 q.y as numpy's knn_brute sums it (utils.py:84; rounding can make it slightly negative), +inf
         beside -1.  Not the knn_brute1 distance that query_batch(return_distances=True) returns.  Always
         tk_index_knn_brute_ex; with no restriction the ids are knn_brute's.  matrix=True: knn_brute's, and the values
-        are dist_m (never negative)."""
-        return self._knn_brute(qn, k, True, allowed, exclude, group, tags, tags_mode, between, matrix)
+        are dist_m (never negative).  wide=True: knn_brute's, any d <= 4096, the same part values."""
+        return self._knn_brute(qn, k, True, allowed, exclude, group, tags, tags_mode, between, matrix, wide)
 
-    def _knn_brute(self, qn, k, want_dist, allowed, exclude, group, tags, tags_mode, between, matrix=False):
+    def _knn_brute(self, qn, k, want_dist, allowed, exclude, group, tags, tags_mode, between, matrix=False,
+                   wide=False):
         """knn_brute / knn_brute_dist: the old entry point where nothing is asked beyond it, else tk_index_knn_brute_ex
-        with the arguments parsed as query_batch parses them"""
+        (matrix: _matrix, wide: _wide) with the arguments parsed as query_batch parses them"""
+        if matrix and wide:
+            raise ValueError("knn_brute: matrix=True is the search of a half store, wide=True that of a float32 "
+                             "store; not both")
         qn = np.ascontiguousarray(qn, dtype=np.float32)
         assert qn.shape[1] == self.d
         nq = qn.shape[0]
         out = np.empty((nq, k), dtype=np.int64)
         if (allowed is None and exclude is None and group is None and tags is None and between is None
-                and not want_dist and not matrix):
+                and not want_dist and not matrix and not wide):
             _lib.check(_lib.lib().tk_index_knn_brute(self._h, _lib.ptr(qn, _lib._f32p), nq, int(k),
                                                      _lib.ptr(out, _lib._i64p)))
             return out
         restrict = self._brute_restrictions("knn_brute", nq, allowed, exclude, group, tags, tags_mode, between)
         out, dist = self._out_pair(nq, k, want_dist, np.float32)
-        call = _lib.lib().tk_index_knn_brute_matrix if matrix else _lib.lib().tk_index_knn_brute_ex
+        lib = _lib.lib()
+        call = lib.tk_index_knn_brute_matrix if matrix else lib.tk_index_knn_brute_wide if wide else lib.tk_index_knn_brute_ex
         _lib.check(call(
             self._h, _lib.ptr(qn, _lib._f32p), nq, int(k), *self._host_pointers(restrict),
             _lib.ptr(out, _lib._i64p), None if dist is None else dist.ctypes.data))
@@ -2822,8 +2830,8 @@ class IVF:
         assert qp.shape[1] == dq
         return qn, qp
 
-    def knn_brute(self, qs, k, matrix=False, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                  between=None, return_distances=False):
+    def knn_brute(self, qs, k, matrix=False, wide=False, *, allowed=None, exclude=None, group=None, tags=None,
+                  tags_mode="any", between=None, return_distances=False):
         """The exact k nearest rows of IVF.data for raw queries, under the restrictions of query_batch (DeviceIndex.
         knn_brute on the prepared queries: an angular index ranks its normalised rows): (nq, k) int64 ids ascending
         by (part, row), ending in -1 where fewer than k rows pass; with return_distances (ids, part): also the float32
@@ -2831,11 +2839,13 @@ class IVF:
         restricted recall; allowed= with a mask of the surviving rows is the truth after remove().  allowed: a bool
         mask of length N or row ids, not an AllowSet.  Not for a list-sharded index.
         matrix=True: DeviceIndex.knn_brute(matrix=True) — a half store of any d <= 4096 on the f16 matrix cores, the
-        values knn_probe(matrix=True)'s dist_m."""
+        values knn_probe(matrix=True)'s dist_m.
+        wide=True: DeviceIndex.knn_brute(wide=True) — a float32 store of any d <= 4096, the same part values
+        (DESIGN §3.25).  Not beside matrix=True (ValueError)."""
         qn, _, dev = self._exact_front("knn_brute", qs, allowed, tags, tags_mode, between)
         call = dev.knn_brute_dist if return_distances else dev.knn_brute
         return call(qn, k, allowed=allowed, exclude=exclude, group=group, tags=tags, tags_mode=tags_mode, between=between,
-                    matrix=matrix)
+                    matrix=matrix, wide=wide)
 
     def radius_search(self, qs, radius, matrix=False, *, allowed=None, exclude=None, group=None, tags=None,
                       tags_mode="any", between=None, sort=True, max_results=None, n_probes=None):
