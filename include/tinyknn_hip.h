@@ -1017,6 +1017,19 @@ int tk_index_radius_brute_matrix(tk_index *ix, const float *q, int64_t nq, const
                                  const uint64_t *tags, int tag_mode, const int64_t *between, int sorted,
                                  int count_only, int64_t max_results, int64_t *out_lims, int64_t *out_total,
                                  int stage_cap);
+/* tk_index_radius_brute over all rows of a FLOAT32 store of any d <= 4096 on the f32 matrix cores (radius_wide.hip,
+ * DESIGN 3.26).  tk_index_radius_brute_matrix's arguments, stage and routes; the value compared and returned is part,
+ * tk_index_radius_brute's and tk_index_knn_brute_wide's, bit for bit — it may be negative, so a negative radius can
+ * list rows — so for every k <= 1024 tk_index_knn_brute_wide's ids and values are the first k entries of this call's
+ * list at radius = its k-th value, and at d <= 128 the result is tk_index_radius_brute's byte for byte.  Refused, in
+ * this order and before any device work: a list-sharded index; a float64 store; a half store (its call is
+ * tk_index_radius_brute_matrix); d > 4096; N >= 2^31; a NaN radius; max_results outside [0, 2^31); stage_cap; then the
+ * restrictions' own refusals.  Synchronous. */
+int tk_index_radius_brute_wide(tk_index *ix, const float *q, int64_t nq, const float *radius,
+                               const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
+                               const uint64_t *tags, int tag_mode, const int64_t *between, int sorted,
+                               int count_only, int64_t max_results, int64_t *out_lims, int64_t *out_total,
+                               int stage_cap);
 /* Every row within a radius of each query among the rows of the lists the query probes (radius_probe.hip, DESIGN
  * 3.20): FAISS's range_search on an IVF index.  For query i with n_probes = P >= 1:
  *   probes      the index's own coarse stage for P — the row tk_index_top_centers(k = P) gives and the query calls

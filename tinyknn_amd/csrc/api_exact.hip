@@ -317,24 +317,19 @@ extern "C" int tk_index_radius_brute(tk_index *ix, const float *q, int64_t nq, c
 }
 
 // ---------------------------------------------------------------------------
-// tk_index_radius_brute on the f16 matrix cores for a half store, d <= 4096 (radius_matrix.hip): ONE pass
-// counts and stages the first `cap` keys of every query; the counts cross to the host (the lims); the query tiles that
-// hold a longer list are walked once more, every other query's keys are copied out of the stage; then radius_brute's
-// tail.  stage_cap: 0 = the largest power of two with nq * cap * 8 <= RM_STAGE_BUDGET, within [1, RM_STAGE_MOST].
+// tk_index_radius_brute through a 128 x 128 tile kernel with a stage, d <= 4096: on the f16 matrix cores for a half
+// store (radius_matrix.hip) or, wide, on the f32 ones for a float32 store (radius_wide.hip).
+// ONE pass counts and stages the first `cap` keys of every query; the counts cross to the host (the lims); the query
+// tiles that hold a longer list are walked once more, every other query's keys are copied out of the stage; then
+// radius_brute's tail.  stage_cap: 0 = the largest power of two with nq * cap * 8 <= RM_STAGE_BUDGET, within
+// [1, RM_STAGE_MOST].  The two entry points have made the refusals in front of d <= 4096; the two forms differ in the
+// queries' preparation, the rows' norms and the two launchers.
 #define RM_STAGE_BUDGET ((int64_t)128 << 20)
 #define RM_STAGE_MOST (1 << 14)
-extern "C" int tk_index_radius_brute_matrix(tk_index *ix, const float *q, int64_t nq, const float *radius,
-                                            const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
-                                            const uint64_t *tags, int tag_mode, const int64_t *between, int sorted,
-                                            int count_only, int64_t max_results, int64_t *out_lims, int64_t *out_total,
-                                            int stage_cap)
+static int radius_brute_staged(tk_index *ix, bool wide, const float *q, int64_t nq, const float *radius,
+                               const TkHostRestrict &h, int sorted, int count_only, int64_t max_results,
+                               int64_t *out_lims, int64_t *out_total, int stage_cap)
 {
-    IXLOCK(ix);
-    if (ix) ix->rd_total = ix->rp_total = -1;       // whatever this call does, the result of the last one is gone
-    ARGCHECK(ix && ix->have_data, "set_data first");
-    ARGCHECK(!ix->sharded, "list-sharded index: radius_search(matrix=True) is not supported");
-    ARGCHECK(nq >= 0 && out_lims && out_total && (nq == 0 || (q && radius)), "buffers");
-    TRY(pm_check(ix, q, nq));
     ARGCHECK(ix->d <= 4096, "d <= 4096");
     ARGCHECK(ix->N < (1ll << 31), "N < 2^31");
     for (int64_t i = 0; i < nq; i++) ARGCHECK(radius[i] == radius[i], "radius: NaN");
@@ -343,7 +338,7 @@ extern "C" int tk_index_radius_brute_matrix(tk_index *ix, const float *q, int64_
              "stage_cap: 0, or a capacity in [1, 2^20] with nq * stage_cap * 8 <= 4 GiB");
     TkBruteRestrict r;
     bool any;
-    TRY(brute_restrict(ix, nq, {allowed_mask, exclude, group, tags, tag_mode, between}, r, any));
+    TRY(brute_restrict(ix, nq, h, r, any));
     out_lims[0] = 0;
     *out_total = 0;
     if (nq == 0) {
@@ -363,16 +358,28 @@ extern "C" int tk_index_radius_brute_matrix(tk_index *ix, const float *q, int64_
     HIPCHECK(hipMemcpy(ix->br_q.p, q, (size_t)nq * ix->d * 4, hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(ix->rd_radius.p, radius, (size_t)nq * 4, hipMemcpyHostToDevice));
     PmQueries pq{};
-    TRY(pm_prepare(ix, nq, pq));
+    if (wide) {
+        TRY(ix->bw_x2.ensure((size_t)nq * tk_brute_wide_dq(ix->d) * 4));
+        TRY(ix->bw_xn.ensure((size_t)nq * 4));
+        tk_launch_brute_wide_prepare(ix->br_q.as<float>(), nq, ix->d, ix->bw_x2.as<float>(), ix->bw_xn.as<float>(), nullptr);
+    } else {
+        TRY(pm_prepare(ix, nq, pq));
+    }
     const TkBruteMatrix mx{pq.xh, pq.xl, pq.xn, pq.xs, pq.dpad};
+    const TkBruteWide wd{ix->bw_x2.as<float>(), ix->bw_xn.as<float>(), tk_brute_wide_dq(ix->d)};
     const float *rad = ix->rd_radius.as<float>();
     float *yn = ix->br_ynorm.as<float>();
     int *count = ix->rd_count.as<int>(), *slots = count + nq, *err = slots + nq;
     unsigned long long *stage = count_only ? nullptr : ix->rd_stage.as<unsigned long long>();
     const TkBruteRestrict *rp = any ? &r : nullptr;
-    if (ix->N > 0) tk_launch_brute_half_norms(ix->data.p, ix->N, ix->d, yn, nullptr);
-    if (tk_launch_radius_matrix_count(mx, nq, ix->d, ix->data.p, ix->N, yn, rad, count, stage, cap, rp, nullptr))
-        return fail(TK_ERR_HIP, "tk_launch_radius_matrix_count: unsupported size");
+    if (wide) {
+        if (tk_launch_radius_wide_count(wd, nq, ix->d, ix->data.as<float>(), ix->N, yn, rad, count, stage, cap, rp, nullptr))
+            return fail(TK_ERR_HIP, "tk_launch_radius_wide_count: unsupported size");
+    } else {
+        if (ix->N > 0) tk_launch_brute_half_norms(ix->data.p, ix->N, ix->d, yn, nullptr);
+        if (tk_launch_radius_matrix_count(mx, nq, ix->d, ix->data.p, ix->N, yn, rad, count, stage, cap, rp, nullptr))
+            return fail(TK_ERR_HIP, "tk_launch_radius_matrix_count: unsupported size");
+    }
     HIPCHECK(hipGetLastError());
     bool fill;
     TRY(radius_lims(ix, count, nq, count_only, max_results, out_lims, out_total, fill));
@@ -396,9 +403,15 @@ extern "C" int tk_index_radius_brute_matrix(tk_index *ix, const float *q, int64_
     TRY(host_upload(ix->rd_tiles, tiles.data(), tiles.size(), dev_tiles));
     TRY(ix->rd_dist.ensure((size_t)total * 4));
     unsigned long long *keys = ix->rd_keys.as<unsigned long long>(), *alt = ix->rd_alt.as<unsigned long long>();
-    if (tk_launch_radius_matrix_fill(mx, nq, ix->d, ix->data.p, ix->N, yn, rad, count, stage, cap, dev_tiles, n_tiles,
-                                     dev_tiles + n_qt, ix->rd_off.as<int64_t>(), slots, keys, err, rp, nullptr))
+    if (wide) {
+        if (tk_launch_radius_wide_fill(wd, nq, ix->d, ix->data.as<float>(), ix->N, yn, rad, count, stage, cap, dev_tiles,
+                                       n_tiles, dev_tiles + n_qt, ix->rd_off.as<int64_t>(), slots, keys, err, rp, nullptr))
+            return fail(TK_ERR_HIP, "tk_launch_radius_wide_fill: unsupported size");
+    } else if (tk_launch_radius_matrix_fill(mx, nq, ix->d, ix->data.p, ix->N, yn, rad, count, stage, cap, dev_tiles,
+                                            n_tiles, dev_tiles + n_qt, ix->rd_off.as<int64_t>(), slots, keys, err, rp,
+                                            nullptr)) {
         return fail(TK_ERR_HIP, "tk_launch_radius_matrix_fill: unsupported size");
+    }
     HIPCHECK(hipGetLastError());
     TRY(radius_passes_agree(err));
     if (sorted) {
@@ -411,6 +424,41 @@ extern "C" int tk_index_radius_brute_matrix(tk_index *ix, const float *q, int64_
     ix->rd_ids_alt = alt == ix->rd_alt.as<unsigned long long>();
     ix->rd_total = total;
     return TK_OK;
+}
+
+extern "C" int tk_index_radius_brute_matrix(tk_index *ix, const float *q, int64_t nq, const float *radius,
+                                            const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
+                                            const uint64_t *tags, int tag_mode, const int64_t *between, int sorted,
+                                            int count_only, int64_t max_results, int64_t *out_lims, int64_t *out_total,
+                                            int stage_cap)
+{
+    IXLOCK(ix);
+    if (ix) ix->rd_total = ix->rp_total = -1;       // whatever this call does, the result of the last one is gone
+    ARGCHECK(ix && ix->have_data, "set_data first");
+    ARGCHECK(!ix->sharded, "list-sharded index: radius_search(matrix=True) is not supported");
+    ARGCHECK(nq >= 0 && out_lims && out_total && (nq == 0 || (q && radius)), "buffers");
+    TRY(pm_check(ix, q, nq));
+    return radius_brute_staged(ix, false, q, nq, radius, {allowed_mask, exclude, group, tags, tag_mode, between}, sorted,
+                               count_only, max_results, out_lims, out_total, stage_cap);
+}
+
+// ... for a float32 store of any d <= 4096: part, knn_brute(wide=True)'s value (radius_wide.hip)
+extern "C" int tk_index_radius_brute_wide(tk_index *ix, const float *q, int64_t nq, const float *radius,
+                                          const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
+                                          const uint64_t *tags, int tag_mode, const int64_t *between, int sorted,
+                                          int count_only, int64_t max_results, int64_t *out_lims, int64_t *out_total,
+                                          int stage_cap)
+{
+    IXLOCK(ix);
+    if (ix) ix->rd_total = ix->rp_total = -1;       // whatever this call does, the result of the last one is gone
+    ARGCHECK(ix && ix->have_data, "set_data first");
+    ARGCHECK(!ix->sharded, "list-sharded index: radius_search(wide=True) is not supported");
+    ARGCHECK(nq >= 0 && out_lims && out_total && (nq == 0 || (q && radius)), "buffers");
+    ARGCHECK(ix->data_dtype != TK_DATA_F64, "wide=True needs store=\"float32\": this index stores float64 vectors");
+    ARGCHECK(ix->data_dtype != TK_DATA_F16, "wide=True needs store=\"float32\": this index stores its vectors as half "
+                                            "(store=\"float16\"); its search over all rows is matrix=True");
+    return radius_brute_staged(ix, true, q, nq, radius, {allowed_mask, exclude, group, tags, tag_mode, between}, sorted,
+                               count_only, max_results, out_lims, out_total, stage_cap);
 }
 
 extern "C" int tk_index_radius_fetch(tk_index *ix, int64_t *out_ids, float *out_dist)

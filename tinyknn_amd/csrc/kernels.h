@@ -624,3 +624,19 @@ int tk_launch_radius_matrix_fill(const TkBruteMatrix &mx, int64_t nq, int d, con
                                  const unsigned long long *stage, int cap, const int *tiles, int n_tiles,
                                  const int *refilled, const int64_t *offset, int *slots, unsigned long long *keys,
                                  int *err, const TkBruteRestrict *r, hipStream_t s);
+// radius_matrix.hip's two small kernels for radius_wide.hip: p[0 .. n) = 0 (a kernel, not a memset node), and
+// radius_unstage_kernel over the nq queries (those of the tiles with refilled == 0 are copied out of the stage)
+void tk_launch_radius_zero(int *p, int64_t n, hipStream_t s);
+void tk_launch_radius_unstage(const unsigned long long *stage, int cap, const int *count, const int64_t *offset,
+                              const int *refilled, int64_t nq, unsigned long long *keys, hipStream_t s);
+// ---- ... over all rows of a float32 store of any d <= 4096 (radius_wide.hip) ----
+// the _matrix_ pair for float32 rows: wd is tk_launch_brute_wide_prepare's copy of the queries, and _count also takes
+// the norms of Y into ynorm2 (row_norms_kernel, per call, as tk_launch_radius_count)
+int tk_launch_radius_wide_count(const TkBruteWide &wd, int64_t nq, int d, const float *Y, int64_t N, float *ynorm2,
+                                const float *radius, int *count, unsigned long long *stage, int cap,
+                                const TkBruteRestrict *r, hipStream_t s);
+int tk_launch_radius_wide_fill(const TkBruteWide &wd, int64_t nq, int d, const float *Y, int64_t N,
+                               const float *ynorm2, const float *radius, const int *count,
+                               const unsigned long long *stage, int cap, const int *tiles, int n_tiles,
+                               const int *refilled, const int64_t *offset, int *slots, unsigned long long *keys,
+                               int *err, const TkBruteRestrict *r, hipStream_t s);

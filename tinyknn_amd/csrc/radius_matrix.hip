@@ -347,9 +347,16 @@ __global__ void radius_matrix_zero_kernel(int *__restrict__ p, int64_t n)
     if (i < n) p[i] = 0;
 }
 
-static void rm_zero(int *p, int64_t n, hipStream_t s)
+void tk_launch_radius_zero(int *p, int64_t n, hipStream_t s)
 {
     if (n > 0) hipLaunchKernelGGL(radius_matrix_zero_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, n);
+}
+
+void tk_launch_radius_unstage(const unsigned long long *stage, int cap, const int *count, const int64_t *offset,
+                              const int *refilled, int64_t nq, unsigned long long *keys, hipStream_t s)
+{
+    hipLaunchKernelGGL(radius_unstage_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, stage, cap, count, offset,
+                       refilled, nq, keys);
 }
 
 template <int PASS>
@@ -368,7 +375,7 @@ int tk_launch_radius_matrix_count(const TkBruteMatrix &mx, int64_t nq, int d, co
 {
     if (nq <= 0) return 0;
     if (d > 4096 || N >= (1ll << 31) || (stage && (cap < 1 || cap > (1 << 20)))) return -1;
-    rm_zero(count, nq, s);
+    tk_launch_radius_zero(count, nq, s);
     if (N <= 0) return 0;
     const RmJob j{mx, nq, d, (const _Float16 *)Y, ynorm2, N, radius, count, stage, stage ? cap : 0, nullptr, nullptr,
                   nullptr, nullptr, nullptr, r ? *r : TkBruteRestrict{}};
@@ -389,15 +396,14 @@ int tk_launch_radius_matrix_fill(const TkBruteMatrix &mx, int64_t nq, int d, con
 {
     if (nq <= 0 || N <= 0) return 0;
     if (d > 4096 || N >= (1ll << 31) || cap < 1 || cap > (1 << 20)) return -1;
-    rm_zero(err, 1, s);
+    tk_launch_radius_zero(err, 1, s);
     if (n_tiles > 0) {
-        rm_zero(slots, nq, s);
+        tk_launch_radius_zero(slots, nq, s);
         const RmJob j{mx, nq, d, (const _Float16 *)Y, ynorm2, N, radius, (int *)count, nullptr, 0, tiles, offset,
                       slots, keys, err, r ? *r : TkBruteRestrict{}};
         const dim3 grid(n_tiles, brute_tile_grid((int64_t)n_tiles * RM_QT, N).y);
         rm_tiles<2>(j, grid, r != nullptr, s);
     }
-    hipLaunchKernelGGL(radius_unstage_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, stage, cap, count, offset,
-                       refilled, nq, keys);
+    tk_launch_radius_unstage(stage, cap, count, offset, refilled, nq, keys, s);
     return 0;
 }

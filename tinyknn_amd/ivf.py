@@ -1491,9 +1491,11 @@ class DeviceIndex:
     # tk_index_radius_brute_matrix's stage_cap: keys a query's list may hold in the staging buffer of the one-pass
     # route (0: the library's default).  It changes the route a list takes, never the result.
     RADIUS_MATRIX_STAGE = 0
+    # tk_index_radius_brute_wide's stage_cap, with the same meaning
+    RADIUS_WIDE_STAGE = 0
 
     def radius_brute(self, qn, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                     between=None, sort=True, max_results=None, matrix=False):
+                     between=None, sort=True, max_results=None, matrix=False, wide=False):
         """Every row within a radius of each normalised query, exactly (tk_index_radius_brute): CSR
         (lims, ids, part) — lims (nq + 1,) int64, query i's hits ids[lims[i]:lims[i + 1]] int64 with their float32
         `part` values beside them.  Row j is a hit of query i iff it passes the query's restrictions (allowed /
@@ -1511,7 +1513,15 @@ class DeviceIndex:
         AssertionError): all rows of a half store on the f16 matrix cores.  The values are knn_brute_dist(matrix=True)'s
         dist_m (never negative: a negative radius lists nothing) bit for bit, so that call's ids and values are the
         first k entries of the list at radius = its k-th value.  One pass over the rows wherever the lists are short:
-        RADIUS_MATRIX_STAGE."""
+        RADIUS_MATRIX_STAGE.
+        wide=True (tk_index_radius_brute_wide; store="float32" only, d <= 4096 — else AssertionError; not
+        beside matrix=True: ValueError): all rows of a float32 store of any width on the f32 matrix cores.  The values
+        are knn_brute_dist(wide=True)'s part bit for bit (it may be negative), so that call's ids and values are the
+        first k entries of the list at radius = its k-th value; at d <= 128 the result is the default call's byte for
+        byte.  The stage and its routes are matrix=True's: RADIUS_WIDE_STAGE."""
+        if matrix and wide:
+            raise ValueError("radius_search: matrix=True is the search of a half store, wide=True that of a float32 "
+                             "store; not both")
         qn, radius, restrict = self._radius_args("radius_search", qn, radius, allowed, exclude, group, tags, tags_mode,
                                                  between)
         max_results = (1 << 26) if max_results is None else int(max_results)
@@ -1524,6 +1534,8 @@ class DeviceIndex:
         call, more = lib.tk_index_radius_brute, ()
         if matrix:
             call, more = lib.tk_index_radius_brute_matrix, (int(self.RADIUS_MATRIX_STAGE),)
+        if wide:
+            call, more = lib.tk_index_radius_brute_wide, (int(self.RADIUS_WIDE_STAGE),)
         rc = call(
             self._h, _lib.ptr(qn, _lib._f32p), nq, _lib.ptr(radius, _lib._f32p), *self._host_pointers(restrict),
             int(bool(sort)), 0, max_results, _lib.ptr(lims, _lib._i64p), _lib.ptr(total, _lib._i64p), *more)
@@ -1537,10 +1549,14 @@ class DeviceIndex:
         return lims, ids, part
 
     def radius_count(self, qn, radius, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                     between=None, matrix=False):
+                     between=None, matrix=False, wide=False):
         """How many rows radius_brute would list per query: (nq,) int64, from the count pass alone (one pass over the
         rows instead of two and no sort).  No limit: the counts are summed in int64.  matrix=True: radius_brute(matrix=
-        True)'s counts, from its tile pass with nothing stored."""
+        True)'s counts, from its tile pass with nothing stored.  wide=True: radius_brute(wide=True)'s, likewise (not
+        both: ValueError)."""
+        if matrix and wide:
+            raise ValueError("radius_count: matrix=True is the search of a half store, wide=True that of a float32 "
+                             "store; not both")
         qn, radius, restrict = self._radius_args("radius_count", qn, radius, allowed, exclude, group, tags, tags_mode,
                                                  between)
         nq = len(qn)
@@ -1548,6 +1564,8 @@ class DeviceIndex:
         total = np.zeros(1, dtype=np.int64)
         lib = _lib.lib()
         call, more = (lib.tk_index_radius_brute_matrix, (0,)) if matrix else (lib.tk_index_radius_brute, ())
+        if wide:
+            call, more = lib.tk_index_radius_brute_wide, (0,)
         _lib.check(call(
             self._h, _lib.ptr(qn, _lib._f32p), nq, _lib.ptr(radius, _lib._f32p), *self._host_pointers(restrict),
             0, 1, 0, _lib.ptr(lims, _lib._i64p), _lib.ptr(total, _lib._i64p), *more))
@@ -2847,7 +2865,7 @@ class IVF:
         return call(qn, k, allowed=allowed, exclude=exclude, group=group, tags=tags, tags_mode=tags_mode, between=between,
                     matrix=matrix, wide=wide)
 
-    def radius_search(self, qs, radius, matrix=False, *, allowed=None, exclude=None, group=None, tags=None,
+    def radius_search(self, qs, radius, matrix=False, wide=False, *, allowed=None, exclude=None, group=None, tags=None,
                       tags_mode="any", between=None, sort=True, max_results=None, n_probes=None):
         """Every row of IVF.data within a radius of each raw query, exactly, under the restrictions of query_batch
         (DeviceIndex.radius_brute on the prepared queries): CSR (lims, ids, part) — lims (nq + 1,)
@@ -2874,31 +2892,40 @@ class IVF:
         matrix=True (DeviceIndex.radius_brute(matrix=True)): the call over all rows for a half store
         (store="float16") of any d <= 4096, on the f16 matrix cores: CSR (lims, ids, dist_m), dist_m the value
         knn_brute(matrix=True) ranks by, bit for bit — that call's ids are the first k entries of the list at radius =
-        its k-th value.  Not with n_probes= (ValueError)."""
+        its k-th value.  Not with n_probes= (ValueError).
+        wide=True (DeviceIndex.radius_brute(wide=True)): the call over all rows for a float32 store of
+        any d <= 4096: CSR (lims, ids, part), part the value knn_brute(wide=True) ranks by, bit for bit — that call's ids
+        are the first k entries of the list at radius = its k-th value, and at d <= 128 the result is the default
+        call's.  Not with n_probes=, not beside matrix=True (ValueError)."""
         if matrix and n_probes is not None:
             raise ValueError("radius_search: matrix=True is the search over all rows; it cannot be combined with n_probes=")
+        if wide and n_probes is not None:
+            raise ValueError("radius_search: wide=True is the search over all rows; it cannot be combined with n_probes=")
         if n_probes is not None:
             qn, qp, dev = self._radius_front("radius_search", qs, radius, allowed, tags, tags_mode, between, n_probes)
             return dev.radius_probe(qn, qp, radius, n_probes, allowed=allowed, exclude=exclude, group=group, tags=tags,
                                     tags_mode=tags_mode, between=between, sort=sort, max_results=max_results)
         qn, _, dev = self._radius_front("radius_search", qs, radius, allowed, tags, tags_mode, between)
         return dev.radius_brute(qn, radius, allowed=allowed, exclude=exclude, group=group, tags=tags,
-                                tags_mode=tags_mode, between=between, sort=sort, max_results=max_results, matrix=matrix)
+                                tags_mode=tags_mode, between=between, sort=sort, max_results=max_results, matrix=matrix,
+                                wide=wide)
 
-    def radius_count(self, qs, radius, matrix=False, *, allowed=None, exclude=None, group=None, tags=None,
+    def radius_count(self, qs, radius, matrix=False, wide=False, *, allowed=None, exclude=None, group=None, tags=None,
                      tags_mode="any", between=None, n_probes=None):
         """How many rows radius_search would list per raw query: (nq,) int64, from its count pass alone — no limit
         (the totals are summed in int64), half the work and no sort.  Arguments as radius_search's, n_probes=
-        (DeviceIndex.radius_probe_count) and matrix= (not both: ValueError) included."""
+        (DeviceIndex.radius_probe_count) and matrix= / wide= (neither with n_probes=: ValueError) included."""
         if matrix and n_probes is not None:
             raise ValueError("radius_count: matrix=True is the search over all rows; it cannot be combined with n_probes=")
+        if wide and n_probes is not None:
+            raise ValueError("radius_count: wide=True is the search over all rows; it cannot be combined with n_probes=")
         if n_probes is not None:
             qn, qp, dev = self._radius_front("radius_count", qs, radius, allowed, tags, tags_mode, between, n_probes)
             return dev.radius_probe_count(qn, qp, radius, n_probes, allowed=allowed, exclude=exclude, group=group,
                                           tags=tags, tags_mode=tags_mode, between=between)
         qn, _, dev = self._radius_front("radius_count", qs, radius, allowed, tags, tags_mode, between)
         return dev.radius_count(qn, radius, allowed=allowed, exclude=exclude, group=group, tags=tags,
-                                tags_mode=tags_mode, between=between, matrix=matrix)
+                                tags_mode=tags_mode, between=between, matrix=matrix, wide=wide)
 
     def _exact_front(self, call, qs, allowed, tags, tags_mode, between, then=None, bounded=False):
         """The early refusals every exact call makes, in their order, before any device call: an AllowSet; between=
