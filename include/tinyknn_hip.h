@@ -1116,6 +1116,28 @@ int tk_index_knn_probe_matrix(tk_index *ix, const float *q, const void *q_pq, in
                               int n_probes, const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
                               const uint64_t *tags, int tag_mode, const int64_t *between, int64_t *out_ids,
                               void *out_dist);
+/* tk_index_knn_probe with its distances made on the f32 matrix cores (probe_f32.hip), for an index that
+ * stores its vectors in float32 (TK_DATA_F32), any d <= 4096.  Arguments, probes, lists, candidates, the twin rule, the
+ * restrictions, the -1 / +inf padding, k <= 1024 and the cut into query chunks are tk_index_knn_probe's, word for word;
+ * the tables, the key buffer and the selection are its code.  out_dist is float32.  Only the value behind each key
+ * differs: it is tk_index_knn_brute_wide's part, bit for bit —
+ *   part = (xn + yn) - acc   in float32, NOT clamped: rounding can make it slightly negative
+ *   acc  = one float32 accumulator of v_mfma_f32_32x32x2_f32 per (query, row): k ascending from 0 over all of d, the A
+ *          operand 2 * x, starting at 0, carried across the slabs of d; no split-K
+ *   xn, yn: the float32 self-dots of the query and of the row in numpy's einsum order; yn is summed inside the distance
+ *          kernel from the staged rows, so the call reads the probed lists and not the whole store
+ * Answers ascend by (part, row id).  With every list probed, every row stored once and none removed, the call returns
+ * tk_index_knn_brute_wide's ids and bytes; where every product and sum is exact in float32 (integer data) it returns
+ * tk_index_knn_probe's.  With D the real squared distance and S = sum |x_t y_t|:
+ * |part - D| <= (d + 4) 2^-23 (|x|^2 + |y|^2 + 2S).
+ * Refused before any device work (TK_ERR_ARG): a half or float64 vector store; everything tk_index_knn_probe refuses.
+ * The distance pass takes tiles of 64 queries and blocks of 128 rows and walks d in slabs of 64 floats;
+ * tk_index_knn_probe_tile keeps reporting the exact pass's tile, and TK_OPT_PROBE_WIDE — the exact pass's slabbed lane
+ * kernel — has no bearing on this call. */
+int tk_index_knn_probe_wide(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
+                            int n_probes, const uint8_t *allowed_mask, const int64_t *exclude, const int32_t *group,
+                            const uint64_t *tags, int tag_mode, const int64_t *between, int64_t *out_ids,
+                            void *out_dist);
 /* The exact k nearest rows inside each query's own group (group_exact.hip): what the restricted call
  * above answers for group[i] >= 0 among the rows that are STORED, at a cost that follows the size of the group instead
  * of N — a query reads the rows of its group and no other.  Ranked by the rescoring's distance (numpy's einsum order

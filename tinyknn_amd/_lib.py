@@ -42,6 +42,10 @@ PROBE_WIDE_DS = {"float32": 128, "float16": 128, "float64": 64}
 # tk_index_knn_probe_matrix's distance kernel (probe_matrix.hip: PM_QT, PM_RB, PM_DS): its tile and the halfs of a slab
 PROBE_MATRIX_TILE = (64, 128)
 PROBE_MATRIX_DS = 112
+# tk_index_knn_probe_wide's distance kernel (probe_f32.hip: PF_QT, PF_RB, PF_DS): its tile and the floats of a slab.  (Not
+# PROBE_WIDE_* and OPT_PROBE_WIDE above: those are the exact pass's slabbed lane kernel.)
+PROBE_F32_TILE = (64, 128)
+PROBE_F32_DS = 64
 # tk_index_knn_brute_matrix's tile kernel (brute_matrix.hip: BM_QT, BM_RB, BM_DS)
 BRUTE_MATRIX_TILE = (128, 128)
 BRUTE_MATRIX_DS = 64
@@ -267,6 +271,9 @@ SIGNATURES = {
     "tk_index_knn_probe_matrix": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64p,
                                             C.c_void_p]),
+    "tk_index_knn_probe_wide": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64p,
+                                          C.c_void_p]),
     "tk_index_knn_probe_tile": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tk_index_knn_group": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.c_void_p, _i64p, C.c_void_p]),

@@ -16,6 +16,24 @@
 
 typedef float tk_f32x16 __attribute__((ext_vector_type(16)));
 
+// ---- brute_wide.hip and probe_f32.hip: how both stage a float32 row ----
+// piece c (4 floats) of a row of d floats, zeros behind d, in loads of U: uint4 where d % 4 == 0, uint2 where d % 2 == 0,
+// else floats — d is a multiple of the floats of U, so a load is whole or not made (pm_row_piece's forms)
+template <typename U>
+__device__ __forceinline__ uint4 bw_row_piece(const float *row, int c, int d)
+{
+    constexpr int NU = 16 / (int)sizeof(U), E = (int)sizeof(U) / 4;
+    union {
+        uint4 v;
+        U u[NU];
+    } p;
+    p.v = make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < NU; i++)
+        if (c * 4 + i * E < d) p.u[i] = *(const U *)(row + c * 4 + i * E);
+    return p.v;
+}
+
 // The attributes of a workgroup's 128 queries, staged in LDS behind the tiles (RESTRICTED), only those of the
 // restrictions given: ranges [128][2 cols] int64 (lo_0, hi_0, lo_1, ...), tags [128] uint64, exclude [128] int32
 // (N < 2^31), group [128] int32 — 4 to 84 bytes a query.  At d = 100 the tiles take 76 800 bytes, so two workgroups

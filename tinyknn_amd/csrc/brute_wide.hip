@@ -79,23 +79,6 @@ __global__ void brute_wide_prepare_kernel(const float *__restrict__ X, int64_t n
     x2[i] = k < d ? 2.0f * X[q * d + k] : 0.0f;
 }
 
-// piece c (4 floats) of a row of d floats, zeros behind d, in loads of U: uint4 where d % 4 == 0, uint2 where d % 2 == 0,
-// else floats — d is a multiple of the floats of U, so a load is whole or not made (pm_row_piece's forms)
-template <typename U>
-__device__ __forceinline__ uint4 bw_row_piece(const float *row, int c, int d)
-{
-    constexpr int NU = 16 / (int)sizeof(U), E = (int)sizeof(U) / 4;
-    union {
-        uint4 v;
-        U u[NU];
-    } p;
-    p.v = make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < NU; i++)
-        if (c * 4 + i * E < d) p.u[i] = *(const U *)(row + c * 4 + i * E);
-    return p.v;
-}
-
 template <int MODE, bool RESTRICTED, typename U>
 __device__ __forceinline__ void bw_walk(const BwJob &j, BwLds<RESTRICTED> &s)
 {

@@ -36,6 +36,8 @@
 // whose staging and arithmetic overlap; nothing is double-buffered inside one.
 // Where not even 4 queries and 8 whole rows fit (d from 1 365 on float32 vectors, 2 041 on half, 683 on float64; up to
 // 4 096) the distance pass is probe_dist_wide_kernel below: the same tiles, keys and places, d walked in slabs.
+// The driver at the end of this file also serves the two matrix-core passes, which replace the distance kernel and
+// nothing else: probe_matrix.hip (matrix=True, half rows, §3.22) and probe_f32.hip (wide=True, float32 rows, §3.27).
 #include "probe_job.h"
 #include "sqdist_row.h"
 #include "span_exact.h"
@@ -456,12 +458,14 @@ static int pe_tile(const tk_index *ix, PeTile &t)
     return TK_OK;
 }
 
+// mx / wd: the queries of the f16 / f32 matrix pass where the call takes one (pe_knn_probe), else NULL
 template <typename T, typename TY>
-static void pe_launch(const PeJob &j, const PmQueries *mx, unsigned max_tiles, const TkBruteRestrict &r, int64_t q0,
-                      int64_t m, int k, int64_t *out, void *out_d)
+static void pe_launch(const PeJob &j, const PmQueries *mx, const TkBruteWide *wd, unsigned max_tiles,
+                      const TkBruteRestrict &r, int64_t q0, int64_t m, int k, int64_t *out, void *out_d)
 {
     typedef typename GxKey<T>::type K;
-    if (mx) pm_launch_dist(j, *mx, max_tiles);      // (float keys on half rows: pe_knn_probe)
+    if (mx) pm_launch_dist(j, *mx, max_tiles);      // (float keys on half rows)
+    else if (wd) pf_launch_dist(j, *wd, max_tiles); // (float keys on float rows)
     else if (j.t.DS) hipLaunchKernelGGL((probe_dist_wide_kernel<T, TY>), dim3(max_tiles), dim3(PE_THREADS), 0, 0, j);
     else hipLaunchKernelGGL((probe_dist_kernel<T, TY>), dim3(max_tiles), dim3(PE_THREADS), j.t.lds, 0, j);
     hipLaunchKernelGGL((probe_select_kernel<T>), dim3((unsigned)m), dim3(GX_THREADS), pe_select_lds(j.kc, sizeof(K)), 0,
@@ -491,8 +495,11 @@ extern "C" int tk_index_knn_probe_tile(tk_index *ix, int *qt, int *rb)
     return TK_OK;
 }
 
-// the body of tk_index_knn_probe and tk_index_knn_probe_matrix: matrix picks the distance pass (probe_matrix.hip)
-static int pe_knn_probe(tk_index *ix, bool matrix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
+// the distance pass of a call: the exact one, probe_matrix.hip's (matrix=True) or probe_f32.hip's (wide=True)
+enum PePass { PE_EXACT, PE_F16_MATRIX, PE_F32_MATRIX };
+
+// the body of tk_index_knn_probe, tk_index_knn_probe_matrix and tk_index_knn_probe_wide
+static int pe_knn_probe(tk_index *ix, PePass pass, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
                         int n_probes, const TkHostRestrict &h, int64_t *out_ids, void *out_dist)
 {
     IXLOCK(ix);
@@ -505,9 +512,12 @@ static int pe_knn_probe(tk_index *ix, bool matrix, const float *q, const void *q
     PeTile tile;
     TRY(pe_tile(ix, tile));
     ARGCHECK(nq >= 0 && (nq == 0 || (q && q_pq && out_ids)), "buffers");
-    if (matrix) {
+    if (pass == PE_F16_MATRIX) {
         TRY(pm_check(ix, q, nq));
         pm_tile(tile);
+    } else if (pass == PE_F32_MATRIX) {
+        TRY(pf_check(ix));
+        pf_tile(tile);
     }
     const int32_t *twin_list = nullptr;
     int twin_w = 0;
@@ -529,7 +539,14 @@ static int pe_knn_probe(tk_index *ix, bool matrix, const float *q, const void *q
     // the coarse stage; the keys of every (query, rank) and where they begin
     TRY(probe_lengths<1>(ix, "knn_probe", q, q_pq, q_pq_is_f64, nq, n_probes, kc, twin_list, twin_w, j));
     PmQueries mx{};
-    if (matrix) TRY(pm_prepare(ix, nq, mx));
+    if (pass == PE_F16_MATRIX) TRY(pm_prepare(ix, nq, mx));
+    const int dq = tk_brute_wide_dq(ix->d);
+    if (pass == PE_F32_MATRIX) {
+        TRY(ix->bw_x2.ensure((size_t)nq * dq * 4));
+        TRY(ix->bw_xn.ensure((size_t)nq * 4));
+        tk_launch_brute_wide_prepare(ix->br_q.as<float>(), nq, ix->d, ix->bw_x2.as<float>(), ix->bw_xn.as<float>(), nullptr);
+    }
+    const TkBruteWide wd{ix->bw_x2.as<float>(), ix->bw_xn.as<float>(), dq};
     const long long *segoff = ix->pl_off.as<long long>();
     std::vector<long long> off((size_t)pairs + 1);
     HIPCHECK(hipMemcpy(off.data(), segoff, (size_t)(pairs + 1) * 8, hipMemcpyDeviceToHost));      // (synchronises)
@@ -579,10 +596,13 @@ static int pe_knn_probe(tk_index *ix, bool matrix, const float *q, const void *q
         TRY(pe_scan(ix, j.ntiles, j.tile_off, nl1));
         hipLaunchKernelGGL(pe_fill_kernel, dim3(pgrid), dim3(256), 0, 0, j);
         hipLaunchKernelGGL(pe_table_kernel, dim3(lgrid), dim3(256), 0, 0, j);
-        if (f64) pe_launch<double, double>(j, nullptr, (unsigned)max_tiles, r, o, m, k, out, out_d);
+        if (f64) pe_launch<double, double>(j, nullptr, nullptr, (unsigned)max_tiles, r, o, m, k, out, out_d);
         else if (ix->data_dtype == TK_DATA_F16)
-            pe_launch<float, _Float16>(j, matrix ? &mx : nullptr, (unsigned)max_tiles, r, o, m, k, out, out_d);
-        else pe_launch<float, float>(j, nullptr, (unsigned)max_tiles, r, o, m, k, out, out_d);
+            pe_launch<float, _Float16>(j, pass == PE_F16_MATRIX ? &mx : nullptr, nullptr, (unsigned)max_tiles, r, o, m, k,
+                                       out, out_d);
+        else
+            pe_launch<float, float>(j, nullptr, pass == PE_F32_MATRIX ? &wd : nullptr, (unsigned)max_tiles, r, o, m, k, out,
+                                    out_d);
         HIPCHECK(hipGetLastError());
         o = e;
     }
@@ -596,7 +616,7 @@ extern "C" int tk_index_knn_probe(tk_index *ix, const float *q, const void *q_pq
                                   const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between,
                                   int64_t *out_ids, void *out_dist)
 {
-    return pe_knn_probe(ix, false, q, q_pq, q_pq_is_f64, nq, k, n_probes,
+    return pe_knn_probe(ix, PE_EXACT, q, q_pq, q_pq_is_f64, nq, k, n_probes,
                         {allowed_mask, exclude, group, tags, tag_mode, between}, out_ids, out_dist);
 }
 
@@ -605,6 +625,15 @@ extern "C" int tk_index_knn_probe_matrix(tk_index *ix, const float *q, const voi
                                          const int32_t *group, const uint64_t *tags, int tag_mode,
                                          const int64_t *between, int64_t *out_ids, void *out_dist)
 {
-    return pe_knn_probe(ix, true, q, q_pq, q_pq_is_f64, nq, k, n_probes,
+    return pe_knn_probe(ix, PE_F16_MATRIX, q, q_pq, q_pq_is_f64, nq, k, n_probes,
+                        {allowed_mask, exclude, group, tags, tag_mode, between}, out_ids, out_dist);
+}
+
+extern "C" int tk_index_knn_probe_wide(tk_index *ix, const float *q, const void *q_pq, int q_pq_is_f64, int64_t nq, int k,
+                                       int n_probes, const uint8_t *allowed_mask, const int64_t *exclude,
+                                       const int32_t *group, const uint64_t *tags, int tag_mode, const int64_t *between,
+                                       int64_t *out_ids, void *out_dist)
+{
+    return pe_knn_probe(ix, PE_F32_MATRIX, q, q_pq, q_pq_is_f64, nq, k, n_probes,
                         {allowed_mask, exclude, group, tags, tag_mode, between}, out_ids, out_dist);
 }

@@ -1,6 +1,6 @@
 // probe_job.h — what the calls over the probed lists share: radius_probe.hip and knn_probe's two
 // distance passes (probe_exact.hip: the exact pass, the tables, the selection and the host driver; probe_matrix.hip:
-// the f16 matrix-core pass of matrix=True, §3.22).
+// the f16 matrix-core pass of matrix=True, §3.22; probe_f32.hip: the f32 matrix-core pass of wide=True, §3.27).
 #pragma once
 #include "api_internal.h"
 
@@ -106,7 +106,7 @@ struct PeTile {
     int xstride;            // elements of T between two queries in LDS
     int ystride;            // bytes between two staged rows in LDS
     size_t lds;
-    int DS;                 // 0: probe_dist_kernel; else probe_dist_wide_kernel and the elements of its slab
+    int DS;                 // 0: probe_dist_kernel; else a slabbed kernel (wide, matrix, f32) and the elements of its slab
 };
 
 struct PeJob : ProbeJob {
@@ -131,6 +131,12 @@ int pm_check(const tk_index *ix, const float *q, int64_t nq);           // the r
 void pm_tile(PeTile &t);                                                // the matrix pass's tile
 int pm_prepare(tk_index *ix, int64_t nq, PmQueries &mx);                // the queries in br_q -> mx (workspace of ix)
 void pm_launch_dist(const PeJob &j, const PmQueries &mx, unsigned max_tiles);
+
+// ---- probe_f32.hip, used by probe_exact.hip's driver ----
+// the queries are tk_launch_brute_wide_prepare's: 2 x zero-extended and |x|^2 (TkBruteWide, kernels.h)
+int pf_check(const tk_index *ix);                                       // the refusals of wide=True; no device work
+void pf_tile(PeTile &t);                                                // the f32 matrix pass's tile
+void pf_launch_dist(const PeJob &j, const TkBruteWide &wd, unsigned max_tiles);
 
 // ---- probe_matrix.hip and brute_matrix.hip: how both stage a half row ----
 // piece c (8 halfs) of a row of d halfs, zeros behind d, in loads of U: uint4 where d % 8 == 0, uint2 where d % 4 == 0

@@ -1659,7 +1659,7 @@ class DeviceIndex:
         return qn, query_radius(radius, len(qn)), restrict
 
     def knn_probe(self, qn, q_pq, k, n_probes, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                  between=None, return_distances=False, matrix=False):
+                  between=None, return_distances=False, matrix=False, wide=False):
         """The exact k nearest rows among the rows of the lists each normalised query probes (tk_index_knn_probe,
         DESIGN §3.21; FAISS's IVF-Flat search): (nq, k) int64 ids ascending by (distance, row id), ending in -1 where
         fewer than k candidates pass; with return_distances (ids, dists), the rescoring's squared distances — float32,
@@ -1676,8 +1676,17 @@ class DeviceIndex:
         x_lo = half(2^e x - x_hi), e putting the query's largest component into [2^14, 2^15).  It differs from the
         exact distance by float32 accumulation rounding and 2^-22 of the query, by nothing where the sums are exact
         in float32; ids ascend by (dist_m, row id).  Opt-in: it routes nothing by itself, and at narrow d (the GloVe
-        shape, d = 100) the call is bound by its table, selection and host passes, so expect the gain at wide d."""
+        shape, d = 100) the call is bound by its table, selection and host passes, so expect the gain at wide d.
+        wide=True (tk_index_knn_probe_wide; store="float32" only — else AssertionError; not beside
+        matrix=True: ValueError): the same probes, candidates, restrictions and order, the value behind each key made on
+        the f32 matrix cores — knn_brute(wide=True)'s part = (xn + yn) - acc in float32, not clamped, acc one
+        accumulator of 2 x . y over k ascending.  With every list probed (every row stored once, none removed) the ids
+        and bytes of knn_brute(wide=True); those of the exact call where the sums are exact in float32; elsewhere within
+        (d + 4) 2^-23 (|x|^2 + |y|^2 + 2 sum |x_k y_k|) of the real distance.  Opt-in: it routes nothing by itself."""
         k = int(k)
+        if matrix and wide:
+            raise ValueError("knn_probe: matrix=True is the pass of a half store, wide=True that of a float32 store; "
+                             "not both")
         if not 1 <= k <= 1024:
             raise ValueError(f"knn_probe: k in [1, 1024], got {k}")
         if _dev_is_sharded(self) or self._source is not None:
@@ -1688,7 +1697,8 @@ class DeviceIndex:
         restrict = self._brute_restrictions("knn_probe", nq, allowed, exclude, group, tags, tags_mode, between)
         q_pq, n_probes = self._probe_args(qn, q_pq, n_probes)
         out, dist = self._out_pair(nq, k, return_distances)
-        call = _lib.lib().tk_index_knn_probe_matrix if matrix else _lib.lib().tk_index_knn_probe
+        lib = _lib.lib()
+        call = lib.tk_index_knn_probe_matrix if matrix else lib.tk_index_knn_probe_wide if wide else lib.tk_index_knn_probe
         _lib.check(call(
             self._h, _lib.ptr(qn, _lib._f32p), q_pq.ctypes.data, int(q_pq.dtype == np.float64), nq, k, n_probes,
             *self._host_pointers(restrict), _lib.ptr(out, _lib._i64p), None if dist is None else dist.ctypes.data))
@@ -2958,7 +2968,7 @@ class IVF:
         return self._exact_front(call, qs, allowed, tags, tags_mode, between, then)
 
     def knn_probe(self, qs, k, n_probes, *, allowed=None, exclude=None, group=None, tags=None, tags_mode="any",
-                  between=None, return_distances=False, matrix=False):
+                  between=None, return_distances=False, matrix=False, wide=False):
         """The exact k nearest rows among the rows of the n_probes lists each raw query probes (DeviceIndex.knn_probe
         on the prepared queries): FAISS's IVF-Flat search, the call between query_batch — which ranks
         the same lists by PQ estimates — and knn_brute, which reads all N rows.  (nq, k) int64 ids ascending by
@@ -2971,12 +2981,20 @@ class IVF:
         matrix=True: the distances on the f16 matrix cores (DeviceIndex.knn_probe; store="float16" only, finite
         queries): dist_m = max(0, (|x|^2 + |y|^2) - 2 x.y) with the query split into two halfs, within float32
         accumulation rounding and 2^-22 of the query of the exact distance and equal to it where the sums are exact
-        in float32; ids ascend by (dist_m, row id)."""
+        in float32; ids ascend by (dist_m, row id).
+        wide=True: the distances on the f32 matrix cores (DeviceIndex.knn_probe; store="float32" only, not beside
+        matrix=True): knn_brute(wide=True)'s part = (|x|^2 + |y|^2) - 2 x.y in float32, not clamped, within float32
+        accumulation rounding of the exact distance and equal to it where the sums are exact in float32; ids ascend
+        by (part, row id), and with every list probed they are knn_brute(wide=True)'s."""
+        if matrix and wide:
+            raise ValueError("knn_probe: matrix=True is the pass of a half store, wide=True that of a float32 store; "
+                             "not both")
         if not 1 <= int(k) <= 1024:
             raise ValueError(f"knn_probe: k in [1, 1024], got {int(k)}")
         qn, qp, dev = self._radius_front("knn_probe", qs, np.inf, allowed, tags, tags_mode, between, n_probes)
         return dev.knn_probe(qn, qp, k, n_probes, allowed=allowed, exclude=exclude, group=group, tags=tags,
-                             tags_mode=tags_mode, between=between, return_distances=return_distances, matrix=matrix)
+                             tags_mode=tags_mode, between=between, return_distances=return_distances, matrix=matrix,
+                             wide=wide)
 
     def knn_group(self, qs, k, group, *, allowed=None, exclude=None, tags=None, tags_mode="any", between=None,
                   return_distances=False):
